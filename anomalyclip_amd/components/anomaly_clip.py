@@ -220,7 +220,7 @@ class AnomalyCLIP(nn.Module):
                         self._text_features_eager()                      # lazy workspaces, function attributes
                     torch.cuda.synchronize(dev)
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+                    with ops.capture_without_gc(), torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
                         out = self._text_features_eager()
                     torch.cuda.synchronize(dev)
             except Exception as e:                                       # noqa: BLE001 -- capture support is best effort

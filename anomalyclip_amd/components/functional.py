@@ -222,11 +222,12 @@ class _TextGraphs:
                 _text_backward_rows(net, P, state, torch.zeros_like(tf))
         torch.cuda.synchronize()
         self.g_fwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fwd, stream=self.side, capture_error_mode="thread_local"):
+        with ops.capture_without_gc(), torch.cuda.graph(self.g_fwd, stream=self.side, capture_error_mode="thread_local"):
             self.tf, self.state = _text_forward_rows(net, ctx_param, P, lo, hi)
         self.d_tf = torch.zeros_like(self.tf)
         self.g_bwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_bwd, stream=self.side, pool=self.g_fwd.pool(), capture_error_mode="thread_local"):
+        with ops.capture_without_gc(), torch.cuda.graph(self.g_bwd, stream=self.side, pool=self.g_fwd.pool(),
+                                                        capture_error_mode="thread_local"):
             self.d_ctx, self.d_P = _text_backward_rows(net, P, self.state, self.d_tf)
         torch.cuda.synchronize()
         self.fwd_done = torch.cuda.Event()
@@ -656,12 +657,13 @@ class _TemporalGraphs:
         ops.prime_capture_stream(cap, self.x.device)
         self.cx = SimpleNamespace(needs_input_grad=(need_dfeats,))
         self.g_fwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fwd, stream=cap, capture_error_mode="thread_local"), torch.no_grad():
+        with ops.capture_without_gc(), torch.cuda.graph(self.g_fwd, stream=cap, capture_error_mode="thread_local"), torch.no_grad():
             tm.refresh_prepared(True)
             self.scores = TemporalFn.forward(self.cx, self.x, a_sub, tm, *params)
         self.d_scores = torch.zeros_like(self.scores)
         self.g_bwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_bwd, stream=cap, pool=self.g_fwd.pool(), capture_error_mode="thread_local"), torch.no_grad():
+        with ops.capture_without_gc(), torch.cuda.graph(self.g_bwd, stream=cap, pool=self.g_fwd.pool(),
+                                                        capture_error_mode="thread_local"), torch.no_grad():
             self.outs = TemporalFn.backward(self.cx, self.d_scores)
         torch.cuda.synchronize()
 

@@ -543,7 +543,8 @@ class TrainStepGraph:
             pg = _Program("capture", self.cap, self.tstream)
             self.buckets.arm()
             try:
-                self._sequence(pg)
+                with ops.capture_without_gc():
+                    self._sequence(pg)
             except Exception:
                 pg.abort()
                 raise

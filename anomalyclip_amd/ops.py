@@ -3,7 +3,9 @@ current HIP stream, every arithmetic step runs in the hand-written HIP kernels. 
 contiguous CUDA(HIP) tensors; nothing here silently falls back to a torch op."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import gc
 from typing import Optional
 
 import torch
@@ -208,6 +210,22 @@ def prime_capture_stream(stream: "torch.cuda.Stream", device) -> None:
     _zero_page(device)
     with torch.cuda.stream(stream):
         _colsum_counters(device)
+
+
+@contextlib.contextmanager
+def capture_without_gc():
+    """Python's cyclic garbage collector paused while HIP graphs are captured.  A collection that starts inside a capture
+    runs the destructors of unreachable objects left by earlier work -- captured graphs, streams, events and the device
+    memory they hold -- while the capture is open: the GPU suite once aborted inside such a collection during the training
+    step's capture.  The garbage is collected after the capture instead.  Nests: only the outermost use re-enables the
+    collector."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def cast_bf16(src: torch.Tensor) -> torch.Tensor:

@@ -10,15 +10,22 @@ the leg `text_recomputed_every_step` runs the text encoder in every step like th
 softmax(similarity)*score (anomaly_clip_module.py:474-477).  Random-init weights of the UCF-Crime configuration
 (no checkpoints/network in this environment), data synthetic.
 
-    python bench.py --gpus N --steps K --warmup W [--precision f32|bf16]
+    python bench.py --gpus N --steps K --warmup W [--precision f32|bf16] [--dump-outputs DIR] [--full]
     (N>1: typed like that it re-launches itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
      --master-addr 127.0.0.1`; started by that launcher -- the driver's form -- it just runs as rank RANK of WORLD_SIZE)
 
 `value`: clips shard across ranks (one process per GPU); the eval path has no data-path collective (the reference's
 test_step is rank-local too) => weak scaling; value = frames of all ranks / max-over-ranks time.
 
-Extra legs, each timed like the main one (barrier + synchronize on both sides, max over ranks), reported as extra
-keys of the same JSON line:
+A plain run does only what `value` needs: set-up, two initialisation steps, W warm-up steps, the K timed steps, the outputs
+of the last timed step if --dump-outputs is given, one JSON line (`value`, `ms_per_step`, `dtype`, the configuration).
+--dump-outputs DIR: rank 0 writes what the timed step returns to its caller in the last timed step -- DIR/class_probs.npy and
+DIR/scores.npy, float32 -- from inputs and weights fixed by seeds, so that two builds can be compared output for output.
+
+--full adds everything below (the roofline of the timed steps, the per-kind kernel times, the extra legs, the live traffic
+passes, the CPU baseline) to the same line, as in earlier rounds; --no-extra-legs / --no-cpu-baseline / --no-live-pmc /
+--leg-limit apply to such a run.  Extra legs, each timed like the main one (barrier + synchronize on both sides, max over
+ranks), reported as extra keys of the same JSON line:
   * `encode_only`, `vit_chunk_256` -- ViT encode alone; the headline step with two 256-frame ViT launches (config[2]'s
     literal batch).
   * `head` (configs[1]) -- UCF-shaped 512-d feature sequences, B = 64 videos on one GPU: forward-only and the full
@@ -635,7 +642,7 @@ def live_pmc_traffic(vit_chunk, precision="auto", timeout_s=150):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(tmp, ctr)
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", out, "-o", "p", "--", sys.executable,
-                   os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs",
+                   os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra-legs",
                    "--no-live-pmc", "--vit-chunk", str(vit_chunk), "--precision", precision]
             env = dict(os.environ, TMPDIR="/tmp")
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout_s)
@@ -727,6 +734,31 @@ def config4_leg(dev, timer, prof, world, steps):
     return out
 
 
+def headline_fields(args, world, backend, dt):
+    """the keys of the result line that the headline measurement alone determines (a plain run prints just these)"""
+    return {
+        "metric": "frames/sec encoded + anomaly-scored (whole node), ViT-B/16 224^2",
+        "value": round(FRAMES_PER_CLIP * args.steps * world / dt, 2), "unit": "frames/s", "n_gpus": world,
+        "world": {"size": world, "backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None}, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE_TEXT[args.precision],
+        "data": "synthetic",
+        "config": {"workload": "configs[2]: synthetic 224x224 RGB frames, ViT-B/16 encode + selector + axial temporal head + eval "
+                               "post-processing; step = one 512-frame clip per GPU in ONE ViT launch, UCF-Crime head config, "
+                               "random-init weights; text features cached (frozen prompts): leg text_recomputed_every_step "
+                               "runs the text encoder in every step; leg vit_chunk_256 = the config's literal batch of 256",
+                   "frames_per_step_per_gpu": FRAMES_PER_CLIP, "vit_chunk": args.vit_chunk, "precision": args.precision},
+    }
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32 (the headline step's outputs: ~30 KB)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def self_launch(n):
     """Re-run this command line under `python -m torch.distributed.run --nnodes=1 --nproc-per-node n` (rendezvous on
     127.0.0.1, a free port); returns the launcher's exit code."""
@@ -759,6 +791,11 @@ def main():
     ap.add_argument("--leg-limit", type=float, default=1200.0,
                     help="seconds the secondary legs + CPU baseline may take after the headline measurement before rank 0 prints the line "
                          "from the headline alone and exits (0: no limit); a normal run needs ~60 s")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the per-kind kernel times, the extra legs, the live traffic passes and the CPU baseline "
+                         "(a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (class_probs, scores; float32 .npy) into DIR")
     args = ap.parse_args()
     if args.precision == "f32x6":
         args.precision = "auto"
@@ -799,7 +836,7 @@ def main():
     frames = torch.randn(1, FRAMES_PER_CLIP, 3, 224, 224, generator=g, device=dev)      # resident in HBM
     nc = torch.zeros(512, device=dev)
     timer = Timer(dist, dev)
-    prof = Prof(local_rank)
+    prof = Prof(local_rank) if args.full else None
 
     def step():
         with torch.no_grad():
@@ -811,17 +848,33 @@ def main():
     def step_keep():
         out_holder["o"] = step()
 
-    # ---- library initialisation, outside the W + K protocol: two steps with the per-launch event pairs armed (lazy
-    # workspaces, kernel attributes, the profiler's event pool) so that the W warm-up steps warm the chip, not the host
-    timer.run(step_keep, 2, 0, prof.start, prof.stop)
-    _, counts_all, tot_all = prof.collect()           # per-kind breakdown (attention / norm / other): from these two steps
-    # ---- headline: EXACTLY --steps timed steps after --warmup untimed ones.  The timed region carries HIP-event pairs around
-    # the dominant kernel's launches (acx_gemm) only: with every launch kind bracketed the ~260 pairs of a step cost 1.9 ms of
-    # its 131.5 ms (tools/probes/headline_decomp.py), the ~110 GEMM pairs 0.8 ms
-    dt = timer.run(step_keep, args.steps, args.warmup, prof.start_gemm_only, prof.stop)
-    gflops_exec, counts, tot = prof.collect()             # GEMM launches of the timed steps only (roofline)
+    # ---- library initialisation, outside the W + K protocol: two steps (lazy workspaces, kernel attributes; under --full with the
+    # per-launch event pairs armed, which also fills the profiler's event pool) so that the W warm-up steps warm the chip, not the host
+    if args.full:
+        timer.run(step_keep, 2, 0, prof.start, prof.stop)
+        _, counts_all, tot_all = prof.collect()       # per-kind breakdown (attention / norm / other): from these two steps
+    else:
+        timer.run(step_keep, 2, 0)
+    # ---- headline: EXACTLY --steps timed steps after --warmup untimed ones.  Under --full the timed region carries HIP-event pairs
+    # around the dominant kernel's launches (acx_gemm) only, for the roofline: with every launch kind bracketed the ~260 pairs of a
+    # step cost 1.9 ms of its 131.5 ms (tools/probes/headline_decomp.py), the ~110 GEMM pairs 0.8 ms
+    if args.full:
+        dt = timer.run(step_keep, args.steps, args.warmup, prof.start_gemm_only, prof.stop)
+        gflops_exec, counts, tot = prof.collect()         # GEMM launches of the timed steps only (roofline)
+    else:
+        dt = timer.run(step_keep, args.steps, args.warmup)
     probs, sc = out_holder["o"]
     assert torch.isfinite(sc).all() and torch.isfinite(probs).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"class_probs": probs, "scores": sc})
+    headline = headline_fields(args, world, backend, dt)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     extra = {}
     # ---- the headline is measured: a secondary leg that stops making progress (one unexplained stop of a replayed training step in
@@ -1026,7 +1079,6 @@ def main():
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
-        value = FRAMES_PER_CLIP * args.steps * world / dt
         # roofline of the dominant kernel (acx_gemm): algorithmic flops per launch / avg launch time.
         # per step the GEMM kernel runs the ViT GEMMs of 512 frames, the text encoder's GEMMs and the
         # head's GEMMs/convs; algorithmic flops = SURVEY 8(d) per-unit figures x units per step.
@@ -1075,18 +1127,8 @@ def main():
                 + (Mv * 4 * Wd + 4 * Wd * Wd + 2 * Mv * Wd)
             algo_bytes_step = bpe * (11 * per_layer + FRAMES_PER_CLIP * 196 * (768 + Wd) + 768 * Wd + 3 * Mv * Wd)
         algo_bytes_per_launch = algo_bytes_step / max(n_gemm / args.steps, 1) if n_gemm else None
-        out = {
-            "metric": "frames/sec encoded + anomaly-scored (whole node), ViT-B/16 224^2",
-            "value": round(value, 2), "unit": "frames/s", "n_gpus": world,
-            "world": {"size": world, "backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None}, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE_TEXT[args.precision],
-            "data": "synthetic",
-            "config": {"workload": "configs[2]: synthetic 224x224 RGB frames, ViT-B/16 encode + selector + axial temporal head + eval "
-                                   "post-processing; step = one 512-frame clip per GPU in ONE ViT launch, UCF-Crime head config, "
-                                   "random-init weights; text features cached (frozen prompts): leg text_recomputed_every_step "
-                                   "runs the text encoder in every step; leg vit_chunk_256 = the config's literal batch of 256",
-                       "frames_per_step_per_gpu": FRAMES_PER_CLIP, "vit_chunk": args.vit_chunk, "precision": args.precision},
+        out = dict(headline)
+        out.update({
             "roofline": {"bound": "mfma", "kernel": {
                              "f32": "acx_gemm (gemm_f32_p256_kernel / gemm_f32_w8_kernel, v_mfma_f32_32x32x2_f32)",
                              "bf16": "acx_gemm (gemm_bf16_p8_kernel / gemm_bf16_dma_kernel / gemm_kernel, v_mfma_f32_32x32x16_bf16)",
@@ -1119,7 +1161,7 @@ def main():
                                         "source": "the two INITIALISATION steps, every launch bracketed by HIP events (they run ~2 ms "
                                                   "longer than a timed step: compare gemm_ms_per_timed_step, not ms_per_step)"},
             "end_to_end_tflops": round((VIT_GFLOP_PER_FRAME * FRAMES_PER_CLIP + HEAD_GFLOP_PER_TILE) * world / ms_per_step, 2),
-        }
+        })
         out.update(extra)
         # the secondary figures a reader wants next to `value`, lifted to the top level
         out["value_vit_chunk_256"] = extra.get("vit_chunk_256", {}).get("frames_per_s")

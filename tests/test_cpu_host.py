@@ -557,3 +557,28 @@ def test_x6_convs_only_for_shapes_the_kernels_take(E, N, L, want):
     assert m.x6_convs() is False              # stand-alone default "f32"; AnomalyCLIP(precision="auto") sets it on its head
     m.precision = "auto"
     assert m.x6_convs() is want
+
+
+def test_capture_without_gc_pauses_the_collector_and_nests():
+    """ops.capture_without_gc() (around every HIP graph capture): no cyclic collection -- and so no destructor of an unreachable
+    object of earlier work -- inside it; the collector's previous state comes back after the outermost use, also on an error."""
+    import gc
+    from anomalyclip_amd import ops
+    assert gc.isenabled()
+    with ops.capture_without_gc():
+        assert not gc.isenabled()
+        with ops.capture_without_gc():
+            assert not gc.isenabled()
+        assert not gc.isenabled()
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with ops.capture_without_gc():
+            raise RuntimeError("capture failed")
+    assert gc.isenabled()
+    gc.disable()
+    try:
+        with ops.capture_without_gc():
+            pass
+        assert not gc.isenabled()
+    finally:
+        gc.enable()

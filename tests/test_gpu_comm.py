@@ -89,7 +89,7 @@ def _worker(rank, world, port, q):
 def test_comm_two_ranks_when_two_gpus_are_visible():
     """self-arming: runs the day the box shows two GPUs (the driver's multi-GPU node); skips on the single-GPU boxes"""
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs 2 GPUs (RCCL)")
+        pytest.skip(f"needs 2 GPUs (RCCL), found {torch.cuda.device_count()}")
     import socket
     import torch.multiprocessing as mp
     s = socket.socket()

@@ -1198,7 +1198,7 @@ def test_train_batch_gradbuckets_world2(backend, path):
     bit-identical gradient buffers.  "nccl" = RCCL, one GPU per rank (skips below 2 GPUs); "gloo" = the same device code
     with both ranks on ONE GPU and the collectives carried by gloo -- the path a single-GPU box can run."""
     if backend == "nccl" and torch.cuda.device_count() < 2:
-        pytest.skip("needs 2 GPUs (RCCL)")
+        pytest.skip(f"needs 2 GPUs (RCCL), found {torch.cuda.device_count()}")
     import socket
     import torch.multiprocessing as mp
     s = socket.socket()
@@ -1245,18 +1245,18 @@ def test_train_batch_more_ranks_than_classes_world8():
 
 def test_bench_two_gpus_over_rccl_when_available():
     """Self-arming multi-GPU evidence: on a box with >= 2 GPUs this runs the driver's own command at N = 2
-    (`python bench.py --gpus 2 --steps 3 --warmup 1`: one process per GPU over RCCL) and checks the line -- the backend really is
+    (`python bench.py --gpus 2 --steps 3 --warmup 1 --full`: one process per GPU over RCCL) and checks the line -- the backend really is
     RCCL, the data-parallel training leg stepped (finite time, positive same-run efficiency), the headline value is finite.
     The JSON line is also left under gpurun_out/ so the first multi-GPU box yields a record.  Skipped on one GPU."""
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs 2 GPUs (RCCL)")
+        pytest.skip(f"needs 2 GPUs (RCCL), found {torch.cuda.device_count()}")
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("ACX_BENCH_BACKEND", None)
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        cwd=repo, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

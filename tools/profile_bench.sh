@@ -3,10 +3,11 @@
 # --kernel-trace only (gpurun refuses --pmc together with sys/hip traces).  Outputs under gpurun_out/prof_bench/.
 # usage: profile_bench.sh [auto|f32|bf16]   (auto = the default / headline; -> gpurun_out/prof_bench_<mode>/)
 PREC=${1:-auto}
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 OUT=/root/repo/gpurun_out/prof_bench_$PREC
 rm -rf $OUT; mkdir -p $OUT
-CMD="python /root/repo/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs --no-live-pmc --precision $PREC"
+CMD="python $REPO/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra-legs --no-live-pmc --precision $PREC"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- $CMD > $OUT/stats.log 2>&1
 pmc() { rocprofv3 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -o p -- $CMD > $OUT/$1.log 2>&1; }
 pmc fetch "FETCH_SIZE"

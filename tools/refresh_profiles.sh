@@ -6,10 +6,10 @@ OUT=$R/gpurun_out/refresh
 rm -rf $OUT; mkdir -p $OUT
 cd $R
 # the default (precision auto: f32 results, the large products as bf16 x 6 on the bf16 matrix cores) = the driver's command
-python bench.py --steps 10 --warmup 3 > $OUT/bench_auto.json 2> $OUT/bench_auto.err
-python bench.py --steps 10 --warmup 3 --precision bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
+python bench.py --steps 10 --warmup 3 --full > $OUT/bench_auto.json 2> $OUT/bench_auto.err
+python bench.py --steps 10 --warmup 3 --precision bf16 --full --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err
 # the f32 MFMA kernels everywhere (a leg of the default run; here as its own line)
-python bench.py --steps 10 --warmup 3 --precision f32 --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err
+python bench.py --steps 10 --warmup 3 --precision f32 --full --no-cpu-baseline > $OUT/bench_f32.json 2> $OUT/bench_f32.err
 python tools/probes/x6_probe.py > $OUT/x6_probe.txt 2>&1
 python tools/probes/x6_time.py all > $OUT/x6_time.txt 2>&1
 python tools/probes/attn_p3_time.py > $OUT/attn_p3_time.txt 2>&1
@@ -47,7 +47,7 @@ python tools/tn_bench.py > $OUT/tn_bench.txt 2>&1
 python tools/bench_preprocess.py 2>/dev/null | tail -1 > $OUT/preprocess.json
 python tools/bench_preprocess.py --hw 720x1280 --frames 64 --cpu-frames 8 2>/dev/null | tail -1 >> $OUT/preprocess.json
 python tools/bench_feature_stream.py 2>/dev/null | tail -1 > $OUT/feature_stream.json
-ACX_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_gloo2_smoke.json 2> $OUT/bench_gloo2_smoke.err
+ACX_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/bench_gloo2_smoke.json 2> $OUT/bench_gloo2_smoke.err
 bash tools/profile_bench.sh auto > $OUT/profile_bench_auto.log 2>&1
 bash tools/profile_bench.sh f32 > $OUT/profile_bench.log 2>&1
 bash tools/profile_bench.sh bf16 > $OUT/profile_bench_bf16.log 2>&1
