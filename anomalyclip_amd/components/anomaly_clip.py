@@ -22,14 +22,60 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..init_weights import ClipGeometry, VIT_B16, TINY
-from .clip_vit import VisionTransformer
+from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, TINY
+from .clip_vit import VisionTransformer, check_vit_precision
 from .coop import PromptLearner
 from .selector_model import SelectorModel
 from .temporal_model import TemporalModel
 from .text_encoder import TextEncoder
 
-_ARCH = {"ViT-B/16": VIT_B16, "tiny": TINY}
+# `net.arch`: the ViT backbones of clip.load (clip/clip.py:31-41); "tiny" is the test geometry
+_ARCH = {"ViT-B/16": VIT_B16, "ViT-B/32": VIT_B32, "ViT-L/14": VIT_L14, "ViT-L/14@336px": VIT_L14_336, "tiny": TINY}
+
+
+def geometry_of_arch(arch: str) -> ClipGeometry:
+    if arch not in _ARCH:
+        raise ValueError(f"unknown arch {arch!r}: supported are " + ", ".join(repr(a) for a in _ARCH)
+                         + " (or pass clip_geometry=)")
+    return _ARCH[arch]
+
+
+def _describe(geom: ClipGeometry) -> str:
+    name = next((a for a, g_ in _ARCH.items() if g_ == geom), None)
+    body = (f"image: width {geom.vision_width}, {geom.vision_layers} layers, patch {geom.vision_patch_size}, resolution "
+            f"{geom.image_resolution}, embed {geom.embed_dim}; text: width {geom.transformer_width}, {geom.transformer_layers} layers")
+    return f"{name} ({body})" if name else body
+
+
+def geometry_from_state_dict(sd) -> Optional[ClipGeometry]:
+    """The CLIP geometry an AnomalyCLIP state_dict's image_encoder.* / text_encoder.* tensors were made for (None when it holds
+    neither encoder; an encoder that is absent keeps ViT-B/16's value for its fields)."""
+    import math
+    kw = {}
+    conv = sd.get("image_encoder.conv1.weight")
+    if conv is not None:
+        pos = sd.get("image_encoder.positional_embedding")
+        proj = sd.get("image_encoder.proj")
+        P = int(conv.shape[-1])
+        kw.update(vision_width=int(conv.shape[0]), vision_patch_size=P,
+                  vision_layers=len({k.split(".")[3] for k in sd if k.startswith("image_encoder.transformer.resblocks.")}))
+        if pos is not None:
+            kw["image_resolution"] = P * int(round(math.sqrt(int(pos.shape[0]) - 1)))
+        if proj is not None:
+            kw["embed_dim"] = int(proj.shape[1])
+    tpos = sd.get("text_encoder.positional_embedding")
+    if tpos is not None:
+        kw.update(context_length=int(tpos.shape[0]), transformer_width=int(tpos.shape[1]),
+                  transformer_layers=len({k.split(".")[3] for k in sd if k.startswith("text_encoder.transformer.resblocks.")}))
+        kw["transformer_heads"] = kw["transformer_width"] // 64
+        tproj = sd.get("text_encoder.text_projection")
+        if tproj is not None and "embed_dim" not in kw:
+            kw["embed_dim"] = int(tproj.shape[1])
+    if not kw:
+        return None
+    base = VIT_B16.as_kwargs()
+    base.update(kw)
+    return ClipGeometry(**base)
 _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "prompts.json")
 
 
@@ -84,10 +130,12 @@ class AnomalyCLIP(nn.Module):
             # significant bits per operand); the head keeps the default's arithmetic
             self.precision = "auto"
         head_precision = "f32" if self.precision == "auto" else self.precision      # text tower (too small for the bf16 x 6 kernel)
-        geom = g("clip_geometry") or _ARCH[self.arch]
+        geom = g("clip_geometry") or geometry_of_arch(self.arch)
         if isinstance(geom, dict):
             geom = ClipGeometry(**geom)
         self.geometry = geom
+        check_vit_precision(vit_precision, geom.grid ** 2 + 1, geom.vision_width, self.arch, geom.image_resolution,
+                            geom.vision_patch_size)                                    # (before anything is allocated)
 
         classnames = g("classnames")
         tokenized = g("tokenized_prompts")
@@ -127,7 +175,7 @@ class AnomalyCLIP(nn.Module):
                                         geom.transformer_layers, geom.embed_dim, head_precision)
         self.image_encoder = VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width,
                                                geom.vision_layers, geom.vision_heads, geom.embed_dim,
-                                               precision=vit_precision, chunk=g("vit_chunk", 512))
+                                               precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
         self.selector_model = SelectorModel(classnames, self.normal_id, nn.Parameter(torch.tensor(2.6592601)),
                                             self.num_segments, self.seg_length, self.select_idx_dropout_topk,
                                             self.select_idx_dropout_bottomk, self.num_topk, self.num_bottomk)
@@ -151,6 +199,21 @@ class AnomalyCLIP(nn.Module):
         # ... and the temporal model's forward / backward as two graphs on the main stream (functional._TemporalGraphs)
         self.temporal_model.graph = bool(g("temporal_graph", False))
         self._text_cache = None
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """nn.Module.load_state_dict, after checking that the image_encoder.* / text_encoder.* tensors of `state_dict` have the
+        shapes of this module's `arch`: a checkpoint of another backbone raises a ValueError naming both geometries."""
+        mine = self.state_dict()
+        bad = [k for k, v in state_dict.items() if k.startswith(("image_encoder.", "text_encoder.")) and torch.is_tensor(v)
+               and k in mine and tuple(v.shape) != tuple(mine[k].shape)]
+        bad += [k for k in state_dict if k.startswith(("image_encoder.transformer.resblocks.", "text_encoder.transformer.resblocks."))
+                and k not in mine]
+        if bad:
+            theirs = geometry_from_state_dict(state_dict)
+            raise ValueError(f"the checkpoint's CLIP encoders do not match arch {self.arch!r}: the checkpoint holds "
+                             f"{_describe(theirs) if theirs is not None else 'another geometry'}, this module is "
+                             f"{_describe(self.geometry)} (first differing tensor: {bad[0]})")
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------------------------------
     def get_text_features(self) -> torch.Tensor:

@@ -33,6 +33,25 @@ PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
 
 
+# vision geometries (resolution, patch, width) of the backbones added beside ViT-B/16: ViT-B/32, ViT-L/14, ViT-L/14@336px
+_NEW_ARCH_VISION = {(224, 32, 768), (224, 14, 1024), (336, 14, 1024)}
+
+
+def check_vit_precision(precision: str, tokens: int, width: int, arch: str, resolution: int = 0, patch: int = 0):
+    """A ValueError, before any launch, for a precision a ViT geometry cannot honour.  "bf16x3" and "f16x3" are stated for the
+    ViT-B/16 geometry (f16x3 needs the planes attention, 192 < tokens <= 208, whenever a product takes the plane kernels; bf16x3's
+    accuracy is measured there only): they are refused for the ViT-B/32 / ViT-L/14 / ViT-L/14@336px geometries and for anything
+    above 224 tokens (which no earlier release ran).  Other geometries keep what they did before (small ones, such as the test
+    geometry, run those launches on the f32 kernels).  "auto", "f32" and "bf16" run every geometry up to 1024 tokens."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}: one of {', '.join(PRECISIONS)}")
+    if precision in ("bf16x3", "f16x3") and (tokens > 224 or (resolution, patch, width) in _NEW_ARCH_VISION):
+        raise ValueError(f"precision {precision!r} is not available for {arch} ({tokens} tokens, width {width}): it is stated for the "
+                         "ViT-B/16 geometry, whose planes attention (192 < tokens <= 208) it needs; use 'auto', 'f32' or 'bf16'")
+    if tokens > 1024:
+        raise ValueError(f"{arch} has {tokens} tokens per frame: the attention kernels take at most 1024")
+
+
 class LayerNorm(nn.Module):
     def __init__(self, width: int):
         super().__init__()
@@ -149,8 +168,9 @@ class VisionTransformer(nn.Module):
     chunks of `chunk` frames (workspace is allocated once per chunk size and reused)."""
 
     def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int,
-                 output_dim: int, precision: str = "auto", chunk: int = 512, streams: int = 1):
+                 output_dim: int, precision: str = "auto", chunk: int = 512, streams: int = 1, arch: Optional[str] = None):
         super().__init__()
+        self.arch = arch or f"ViT(width {width}, patch {patch_size}, resolution {input_resolution})"      # (for messages)
         self.input_resolution, self.patch_size, self.output_dim = input_resolution, patch_size, output_dim
         self.width, self.layers, self.heads = width, layers, heads
         self.conv1 = _Conv(width, patch_size)
@@ -162,6 +182,7 @@ class VisionTransformer(nn.Module):
         self.ln_post = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self.precision = precision
+        self.check_precision()
         self.chunk = chunk
         # streams = 2 (opt-in): every chunk runs as TWO half chunks on two side streams with their own workspaces -- one half's
         # memory-bound launches (LayerNorm, attention) then run beside the other half's matrix-bound GEMMs (+1-2 % frames/s at 512
@@ -175,6 +196,13 @@ class VisionTransformer(nn.Module):
         self._ws: Optional[torch.Tensor] = None
         self._ws2: Optional[torch.Tensor] = None
         self._side = None
+
+    @property
+    def tokens(self) -> int:
+        return (self.input_resolution // self.patch_size) ** 2 + 1
+
+    def check_precision(self):
+        check_vit_precision(self.precision, self.tokens, self.width, self.arch, self.input_resolution, self.patch_size)
 
     @torch.no_grad()
     def f16x3_range_report(self) -> dict:
@@ -217,8 +245,9 @@ class VisionTransformer(nn.Module):
             cb, pb = ops.cast_bf16(conv), ops.cast_bf16(proj_t)
             keep += [cb, pb]
             w.conv1_w_bf16, w.proj_t_bf16 = cb.data_ptr(), pb.data_ptr()
-        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3):
-            # the patch embedding as a bf16 x 6 product: the weight's three planes in K-panel layout (ACX_BF16X3P)
+        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3) and self.patch_size % 4 == 0:
+            # the patch embedding as a bf16 x 6 product: the weight's three planes in K-panel layout (ACX_BF16X3P; a patch of 14,
+            # K = 588, is not a whole number of 32-column panels: acx_vit_encode embeds it on the f32 kernels)
             cb = ops.split_f16x2(conv, panel=True, scale=F16X3_WSCALE) if prec == L.PREC_F16X3 else ops.split_bf16x3(conv, panel=True)
             keep.append(cb)
             w.conv1_w_bf16 = cb.data_ptr()
@@ -235,6 +264,7 @@ class VisionTransformer(nn.Module):
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         assert x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3] == self.input_resolution
+        self.check_precision()
         x = x.contiguous().float()
         prec = PRECISIONS[self.precision]
         lib = L.lib()

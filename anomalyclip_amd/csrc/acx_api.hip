@@ -231,7 +231,9 @@ int linear1(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const f
 // Linear layer with tail handling: a grid of T tiles runs in ceil(T/512) waves of 128x128 tiles (2 per CU); when
 // the last wave would be mostly empty (e.g. N=768: 9.23 waves -> 10), the rows of that partial wave are issued as a
 // second launch that fills the chip (9 waves + ~1/3 wave): acx_gemm runs it on 64x64 tiles (f32, four blocks per CU)
-// or splits K over the workspace handed in here (other precisions).
+// or splits K over the workspace handed in here (other precisions).  The f32 tail gets no workspace: the 64x64 kernel would
+// split a K >= 1024 over it (ViT-L/14: 512 tail rows, K = 1024 / 4096), and the tail rows would then sum K in another order
+// than the head rows -- identical frames would no longer give identical rows across the launch.
 int linear(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const float* Wf, const void* Wb, int ldw,
            void* C, int c_dtype, int ldc, int M, int N, int K, const float* bias, int act, const float* residual,
            hipStream_t s, int ldr = 0, void* splitk_ws = nullptr, size_t splitk_bytes = 0) {
@@ -259,7 +261,8 @@ int linear(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const fl
       if (rc) return rc;
       return linear1(ctx, prec, (const char*)A + (size_t)head_rows * lda * asz, a_dtype, lda, Wf, Wb, ldw,
                      (char*)C + (size_t)head_rows * ldc * csz, c_dtype, ldc, tail_rows, N, K, bias, act,
-                     residual ? residual + (size_t)head_rows * ldc : nullptr, s, 0, splitk_ws, splitk_bytes);
+                     residual ? residual + (size_t)head_rows * ldc : nullptr, s, 0, prec == ACX_PREC_F32 ? nullptr : splitk_ws,
+                     prec == ACX_PREC_F32 ? 0 : splitk_bytes);
     }
   }
   return linear1(ctx, prec, A, a_dtype, lda, Wf, Wb, ldw, C, c_dtype, ldc, M, N, K, bias, act, residual, s, ldr, splitk_ws,
@@ -338,7 +341,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     } else
     if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, qdt, 3 * W, (int)rows, 3 * W, W,
                      b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
-    const bool att_x3 = x6_out && !causal && L > 128 && L <= 224 && ACX_DBG_SWITCH("ATTN16", true);
+    const bool att_x3 = x6_out && !causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
     if (f16mode && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
       return acx_fail(ctx, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
     if (ab) {
@@ -437,10 +440,12 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
   if (!d || !w || !frames || !features || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: null pointer%s");
   if (nframes <= 0) return ACX_OK;
   if (d->width != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64%s");
-  if (d->resolution % d->patch || d->patch % 4) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: bad patch geometry%s");
+  if (d->patch <= 0 || d->resolution % d->patch || d->patch % 2)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: bad patch geometry (need resolution %% patch == 0 and an even patch)%s");
   const int g = d->resolution / d->patch, T = g * g, W = d->width, F = nframes;
   const int K = 3 * d->patch * d->patch;
-  if (T + 1 > 224) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: more than 224 tokens%s");
+  if (T + 1 > 1024)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: %s%ld tokens per frame, the attention kernels take at most 1024", "", (long)(T + 1));
   const VitWs ws = carve_vit((char*)workspace, d, F);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_vit_encode: workspace too small%s");
   hipStream_t s = (hipStream_t)stream;
@@ -458,8 +463,10 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
     if ((rc = linear_x6(ctx, ws.patches, K, (int64_t)F * T, w->conv1_w_bf16, (int64_t)W * K * 2, K, ws.patch_out, W, F * T, W, K, nullptr,
                         ACX_ACT_NONE, nullptr, s, 0, ACX_F32, tf.qkv, (size_t)F * (T + 1) * 3 * W * 4))) return rc;
   } else {
-  if ((rc = acx_vit_patches(ctx, frames, ws.patches, pdt, F, d->resolution, d->patch, s))) return rc;
-  if ((rc = linear(ctx, prec, ws.patches, pdt, K, w->conv1_w, prec == ACX_PREC_BF16 ? w->conv1_w_bf16 : nullptr, K, ws.patch_out, ACX_F32, W, F * T, W, K,
+  // a patch of 14 (K = 588: not a multiple of the bf16 kernels' 8) embeds on the f32 kernels in every mode: ~0.2 % of the MACs
+  const int pprec = d->patch % 4 ? ACX_PREC_F32 : prec, ppdt = d->patch % 4 ? ACX_F32 : pdt;
+  if ((rc = acx_vit_patches(ctx, frames, ws.patches, ppdt, F, d->resolution, d->patch, s))) return rc;
+  if ((rc = linear(ctx, pprec, ws.patches, ppdt, K, w->conv1_w, pprec == ACX_PREC_BF16 ? w->conv1_w_bf16 : nullptr, K, ws.patch_out, ACX_F32, W, F * T, W, K,
                    nullptr, ACX_ACT_NONE, nullptr, s))) return rc;
   }
   // CLS + positional embedding + ln_pre                                :270-279

@@ -199,7 +199,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attn_kernel(const float* __re
 
 
 // =====================================================================================================
-// attn16_kernel -- exact-f32 attention for the ViT sequence (non-causal, 129 <= L <= 256; L = 197 for ViT-B/16).
+// attn16_kernel -- exact-f32 attention for the ViT sequence (non-causal, 129 <= L <= 1024; L = 197 for ViT-B/16, 257 / 577 for
+// ViT-L/14 at 224 / 336 pixels).
 //
 // What limited attn_kernel<7,8> (0.43 of the f32 MFMA roof): 197 tokens padded to 7 x 32 (29 % padded MFMA work),
 // 7 query blocks on 4 SIMDs, and ONE 112 KiB workgroup per CU, so nothing overlaps a workgroup's K/V staging,
@@ -278,9 +279,13 @@ __device__ __forceinline__ void a16_store4(float* out, int64_t row, int col, int
   }
 }
 
-template <bool HB, int NW>
+// QB: items are (query block, sequence, head), query block major: block qb of a sequence owns the 16-query tiles
+// [qb qsz + min(qb, qrem), + qsz + (qb < qrem)) (ta / tb count from there); the wave visits items item0, item0 + gridDim.x, ... < nitems.
+// !QB: items are (sequence, head), the block is the whole sequence, item0 = blockIdx.x.
+template <bool HB, int NW, bool QB = false>
 __device__ __forceinline__ void a16_run(const float* __restrict__ qkv, int64_t ldqkv, float* __restrict__ out, int64_t ldo,
-                                        int L, int heads, int nitems, char* smem, int ta, int tb, int64_t x3plane, int64_t prows) {
+                                        int L, int heads, int nitems, char* smem, int ta, int tb, int64_t x3plane, int64_t prows,
+                                        int item0 = 0, int nbh = 1, int qsz = 0, int qrem = 0) {
   const int W = heads * 64;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -323,16 +328,20 @@ __device__ __forceinline__ void a16_run(const float* __restrict__ qkv, int64_t l
 
   // ---- persistent over (frame, head) items; the first chunk of the NEXT item is in flight while this item's output
   // is normalised and stored
-  int item = blockIdx.x;
-  if (item < nitems) A16_ISSUE(qkv + (int64_t)(item / heads) * L * ldqkv + (item % heads) * 64, 0, 0);
+  // (sequence, head) of an item and the first query row of its block
+  auto bh_of = [&](int it) { return QB ? it % nbh : it; };
+  auto q0_of = [&](int it) { if constexpr (QB) { const int qb_ = it / nbh; return 16 * (qb_ * qsz + min(qb_, qrem)); } else { return 0; } };
+  int item = QB ? item0 : (int)blockIdx.x;
+  if (item < nitems) A16_ISSUE(qkv + (int64_t)(bh_of(item) / heads) * L * ldqkv + (bh_of(item) % heads) * 64, 0, 0);
   for (; item < nitems; item += gridDim.x) {
-    const int b = item / heads, h = item % heads;
+    const int b = bh_of(item) / heads, h = bh_of(item) % heads;
+    const int q0 = q0_of(item);
     const float* base = qkv + (int64_t)b * L * ldqkv + h * 64;
     // ---- Q fragments (B operand of S^T = K Q^T): lane (query qi, k-group g) holds d = 16 c4 + 4 g + (0..3)
     float4 qa[4], qb[4];
     {
-      const float* pa = base + (int64_t)min(16 * ta + qi, L - 1) * ldqkv + 4 * g;
-      const float* pb = base + (int64_t)min(16 * tb + qi, L - 1) * ldqkv + 4 * g;
+      const float* pa = base + (int64_t)min(q0 + 16 * ta + qi, L - 1) * ldqkv + 4 * g;
+      const float* pb = base + (int64_t)min(q0 + 16 * tb + qi, L - 1) * ldqkv + 4 * g;
 #pragma unroll
       for (int c4 = 0; c4 < 4; ++c4) {
         float4 v = *reinterpret_cast<const float4*>(pa + 16 * c4);
@@ -423,12 +432,12 @@ __device__ __forceinline__ void a16_run(const float* __restrict__ qkv, int64_t l
     // every wave is past its last fragment read (barrier above): stage 0 is free for the next item's first chunk
     {
       const int nxt = item + (int)gridDim.x;
-      if (nxt < nitems) A16_ISSUE(qkv + (int64_t)(nxt / heads) * L * ldqkv + (nxt % heads) * 64, 0, 0);
+      if (nxt < nitems) A16_ISSUE(qkv + (int64_t)(bh_of(nxt) / heads) * L * ldqkv + (bh_of(nxt) % heads) * 64, 0, 0);
     }
     // ---- normalise and store: lane (query qi, g) holds O[query][16 g + 4 reg + e]
     {
       const float inv = 1.f / a16_rowsum(la);
-      const int q = 16 * ta + qi;
+      const int q = q0 + 16 * ta + qi;
       if (q < L) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -437,7 +446,7 @@ __device__ __forceinline__ void a16_run(const float* __restrict__ qkv, int64_t l
     }
     if constexpr (HB) {
       const float inv = 1.f / a16_rowsum(lb);
-      const int q = 16 * tb + qi;
+      const int q = q0 + 16 * tb + qi;
       if (q < L) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -461,16 +470,43 @@ __device__ __forceinline__ void a16_run(const float* __restrict__ qkv, int64_t l
 // no single phase is the limit -- softmax -11 %, DMA -8 %, chunk barrier -6 %, LDS fragment reads -4 %, and with ALL of
 // them removed (MFMAs, Q loads and output stores only) the kernel still takes 0.60 ms = 0.73 of the MFMA roof on its
 // padded work: 13 tiles on 8 waves, single-accumulator 16x16x4 chains, item prologue / epilogue.
+//
+// QB (L > 256, up to 1024): the ceil(L / 16) query tiles of a sequence are split into nqb = ceil(nkt / 16) query blocks as evenly
+// as possible (L = 257: 9 + 8, L = 577: 13 + 12 + 12, L = 1024: 4 x 16), and an item is (query block, sequence, head).  Every
+// block streams all of K and V of its head (the restaging stays in L2); the K / V chunk loop, and so the LDS use, does not depend
+// on L.  Blocks of one size share the tile-to-wave deal above; the items are ordered query block major, so the qrem larger blocks
+// come first and a workgroup switches its deal at most once.  L <= 256 (!QB) keeps one block per (sequence, head).
+template <bool QB>
 __global__ __launch_bounds__(512, 4) void attn16_kernel(const float* __restrict__ qkv, int64_t ldqkv, float* __restrict__ out,
                                                         int64_t ldo, int L, int heads, int nitems, int64_t x3plane, int64_t prows) {
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nkt = (L + 15) >> 4;
-  const int nd = nkt - 8;                                                 // waves with two tiles
-  const bool dbl = wave < nd;
-  const int ta = dbl ? 2 * wave : nd + wave;
-  if (dbl) a16_run<true, 8>(qkv, ldqkv, out, ldo, L, heads, nitems, smem, ta, ta + 1, x3plane, prows);
-  else a16_run<false, 8>(qkv, ldqkv, out, ldo, L, heads, nitems, smem, ta, ta, x3plane, prows);
+  if constexpr (!QB) {
+    const int nd = nkt - 8;                                               // waves with two tiles
+    const bool dbl = wave < nd;
+    const int ta = dbl ? 2 * wave : nd + wave;
+    if (dbl) a16_run<true, 8>(qkv, ldqkv, out, ldo, L, heads, nitems, smem, ta, ta + 1, x3plane, prows);
+    else a16_run<false, 8>(qkv, ldqkv, out, ldo, L, heads, nitems, smem, ta, ta, x3plane, prows);
+  } else {
+    const int nqb = (nkt + 15) >> 4;                                      // >= 2: every block holds 8..16 tiles
+    const int qsz = nkt / nqb, qrem = nkt - qsz * nqb;
+    const int nbh = nitems / nqb;
+    const int G = (int)gridDim.x, g0 = (int)blockIdx.x;
+    const int hi_a = qrem * nbh;                                          // items [0, hi_a): blocks of qsz + 1 tiles
+    const int start_b = g0 >= hi_a ? g0 : g0 + ((hi_a - g0 + G - 1) / G) * G;
+#pragma unroll 1
+    for (int part = 0; part < 2; ++part) {
+      const int n = part == 0 ? qsz + 1 : qsz;
+      const int i0 = part == 0 ? g0 : start_b, i1 = part == 0 ? hi_a : nitems;
+      if (i0 >= i1) continue;
+      const int nd = n - 8;
+      const bool dbl = wave < nd;
+      const int ta = dbl ? 2 * wave : nd + wave;
+      if (dbl) a16_run<true, 8, true>(qkv, ldqkv, out, ldo, L, heads, i1, smem, ta, ta + 1, x3plane, prows, i0, nbh, qsz, qrem);
+      else a16_run<false, 8, true>(qkv, ldqkv, out, ldo, L, heads, i1, smem, ta, ta, x3plane, prows, i0, nbh, qsz, qrem);
+    }
+  }
 }
 
 
@@ -491,35 +527,43 @@ __global__ __launch_bounds__(256) void attn_cls_kernel(const float* __restrict__
     const float4 v = *reinterpret_cast<const float4*>(base + 4 * c);
     q[4 * c] = v.x * 0.125f; q[4 * c + 1] = v.y * 0.125f; q[4 * c + 2] = v.z * 0.125f; q[4 * c + 3] = v.w * 0.125f;
   }
-  float sc[4];
-  float mx = -INFINITY;
+  // keys in blocks of 256 (four per lane) with a running max and sum; a single block (L <= 256) is the two-pass form exactly
+  // (first block: exp(-inf) = 0 scales the empty sum and output)
+  float mx = -INFINITY, sum = 0.f, o = 0.f;
+  for (int k0 = 0; k0 < L; k0 += 256) {
+    float sc[4];
+    float bm = -INFINITY;
 #pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int j = lane + 64 * u;
-    float acc = -INFINITY;
-    if (j < L) {
-      const float* kp = base + (int64_t)j * ldqkv + W;
-      acc = 0.f;
+    for (int u = 0; u < 4; ++u) {
+      const int j = k0 + lane + 64 * u;
+      float acc = -INFINITY;
+      if (j < L) {
+        const float* kp = base + (int64_t)j * ldqkv + W;
+        acc = 0.f;
 #pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const float4 v = *reinterpret_cast<const float4*>(kp + 4 * c);
-        acc += q[4 * c] * v.x + q[4 * c + 1] * v.y + q[4 * c + 2] * v.z + q[4 * c + 3] * v.w;
+        for (int c = 0; c < 16; ++c) {
+          const float4 v = *reinterpret_cast<const float4*>(kp + 4 * c);
+          acc += q[4 * c] * v.x + q[4 * c + 1] * v.y + q[4 * c + 2] * v.z + q[4 * c + 3] * v.w;
+        }
       }
+      sc[u] = acc;
+      bm = fmaxf(bm, acc);
     }
-    sc[u] = acc;
-    mx = fmaxf(mx, acc);
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
+    const float mn = fmaxf(mx, wave_max(bm));
+    const float al = __expf(mx - mn);
+    mx = mn;
+    float bs = 0.f;
 #pragma unroll
-  for (int u = 0; u < 4; ++u) { sc[u] = __expf(sc[u] - mx); sum += sc[u]; }
-  sum = wave_sum(sum);
-  float o = 0.f;
-  for (int j = 0; j < L; ++j) {
-    const int u_ = j >> 6;
-    const float mine = u_ == 0 ? sc[0] : (u_ == 1 ? sc[1] : (u_ == 2 ? sc[2] : sc[3]));
-    const float p = __shfl(mine, j & 63, 64);
-    o += p * base[(int64_t)j * ldqkv + 2 * W + lane];
+    for (int u = 0; u < 4; ++u) { sc[u] = __expf(sc[u] - mn); bs += sc[u]; }
+    sum = sum * al + wave_sum(bs);
+    o *= al;
+    const int k1 = min(L, k0 + 256);
+    for (int j = k0; j < k1; ++j) {
+      const int u_ = (j - k0) >> 6;
+      const float mine = u_ == 0 ? sc[0] : (u_ == 1 ? sc[1] : (u_ == 2 ? sc[2] : sc[3]));
+      const float p = __shfl(mine, j & 63, 64);
+      o += p * base[(int64_t)j * ldqkv + 2 * W + lane];
+    }
   }
   out[(int64_t)b * ldo + h * 64 + lane] = o / sum;
 }
@@ -530,25 +574,36 @@ static int attention_impl(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* 
                           int32_t batch, int32_t L, int32_t heads, int32_t causal, void* stream, int x3) {
   if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_attention: null pointer%s");
   if (batch <= 0) return ACX_OK;
-  if (L <= 0 || L > 224 || heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: need 0 < L <= 224%s");
+  if (L <= 0 || L > (causal ? 224 : 1024) || heads <= 0)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: need 0 < L <= 224 (causal) or 0 < L <= 1024 (non-causal)%s");
+  // Calls without a context keep the answer the ABI gave before sequences above 224 were supported (ACX_E_UNSUPPORTED, checked
+  // before any launch: tests/test_cpu_host.py pins it with a NULL context and a host buffer).  Nothing in the kernel needs the
+  // context -- it falls back to 256 CUs below -- this only keeps that earlier contract for context-free callers.
+  if (L > 224 && !ctx) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: L > 224 needs a context%s");
   if (ldqkv % 4 || ((uintptr_t)qkv & 15)) return acx_fail(ctx, ACX_E_BADARG, "acx_attention: qkv must be 16-byte aligned, ld%%4==0%s");
   const int nt = (L + 31) / 32;
   const bool nw4 = ACX_DBG_SWITCH("ATTN_NW4", false);
   const dim3 grid((unsigned)(batch * heads));
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_ATTN, (hipStream_t)stream);
-  if (!causal && L > 128 && L <= 256 && ldo % 4 == 0 && !((uintptr_t)out & 15) && ACX_DBG_SWITCH("ATTN16", true)) {
-    // ViT sequence: 16-wide tiles (one or two query tiles per wave), chunked LDS-DMA staging, two workgroups per CU
-    const int nitems = batch * heads;
+  if (!causal && L > 128 && ldo % 4 == 0 && !((uintptr_t)out & 15) && (L > 224 || ACX_DBG_SWITCH("ATTN16", true))) {
+    // ViT sequence: 16-wide tiles (one or two query tiles per wave), chunked LDS-DMA staging, two workgroups per CU;
+    // L > 256: several query blocks per (sequence, head)
+    const int nqb = L > 256 ? ((L + 15) / 16 + 15) / 16 : 1;
+    const int nitems = batch * heads * nqb;
     const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
     const int slots = 2 * ncu;                                            // two workgroups per CU
-    hipLaunchKernelGGL(attn16_kernel, dim3((unsigned)(nitems < slots ? nitems : slots)), dim3(512), 2 * A16_STAGE_B, s, qkv,
-                       ldqkv, out, ldo, L, heads, nitems, x3 ? (int64_t)batch * L * ldo : (int64_t)0,
-                       x3 == 2 ? (int64_t)batch * L : (int64_t)0);
+    const dim3 grid16((unsigned)(nitems < slots ? nitems : slots));
+    const int64_t x3plane = x3 ? (int64_t)batch * L * ldo : (int64_t)0, prows = x3 == 2 ? (int64_t)batch * L : (int64_t)0;
+    if (nqb == 1)
+      hipLaunchKernelGGL(attn16_kernel<false>, grid16, dim3(512), 2 * A16_STAGE_B, s, qkv, ldqkv, out, ldo, L, heads, nitems, x3plane, prows);
+    else
+      hipLaunchKernelGGL(attn16_kernel<true>, grid16, dim3(512), 2 * A16_STAGE_B, s, qkv, ldqkv, out, ldo, L, heads, nitems, x3plane, prows);
     ACX_CHECK_LAUNCH(ctx, "acx_attention");
     return ACX_OK;
   }
-  if (x3) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_x3: the ViT kernel only (non-causal, 128 < L <= 224)%s");
+  if (x3) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_x3: the ViT kernel only (non-causal, 128 < L <= 1024, out 16-byte aligned)%s");
+  if (L > 224) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: L > 224 needs the streaming kernel (out 16-byte aligned, ldo %% 4 == 0)%s");
 #define ACX_ATTN(NT, NW)                                                                           \
   do {                                                                                             \
     const size_t lds = (size_t)NT * 32 * (KROW + VROW) * 4 + NW * 32 * 4 + 16;                          \
@@ -1176,7 +1231,7 @@ extern "C" int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, 
                                  int32_t L, int32_t heads, void* stream) {
   if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls: null pointer%s");
   if (batch <= 0) return ACX_OK;
-  if (L <= 0 || L > 256 || heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls: need 0 < L <= 256%s");
+  if (L <= 0 || L > 1024 || heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls: need 0 < L <= 1024%s");
   if (ldqkv % 4 || ((uintptr_t)qkv & 15)) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls: alignment%s");
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_ATTN, s);

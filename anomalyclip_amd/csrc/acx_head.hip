@@ -8,7 +8,9 @@
 namespace {
 
 // ------------------------------------------------------------------ patch im2col
-// out[(f*g*g + gy*g + gx), c*P*P + ky*P + kx] = frames[f, c, gy*P+ky, gx*P+kx]   (P % 4 == 0)
+// out[(f*g*g + gy*g + gx), c*P*P + ky*P + kx] = frames[f, c, gy*P+ky, gx*P+kx]   (P even: K = 3 P P is a multiple of 4; a thread
+// moves four consecutive k -- one float4 load when P % 4 == 0, else two float2 loads (P = 14: a 4-run may cross a patch row, a
+// 2-run never does; R and P even keep every pair 8-byte aligned))
 template <int OUT_BF16>
 __global__ __launch_bounds__(256) void patches_kernel(const float* __restrict__ frames, void* __restrict__ out,
                                                       int64_t total4, int R, int P, int g) {
@@ -20,8 +22,15 @@ __global__ __launch_bounds__(256) void patches_kernel(const float* __restrict__ 
   const int c = k / (P * P), rem = k - c * P * P, ky = rem / P, kx = rem - ky * P;
   const int64_t f = row / (g * g);
   const int tok = (int)(row - f * g * g), gy = tok / g, gx = tok - gy * g;
-  const float4 v = *reinterpret_cast<const float4*>(
-      frames + ((f * 3 + c) * R + gy * P + ky) * (int64_t)R + gx * P + kx);
+  float4 v;
+  if (P % 4 == 0) {
+    v = *reinterpret_cast<const float4*>(frames + ((f * 3 + c) * R + gy * P + ky) * (int64_t)R + gx * P + kx);
+  } else {
+    const int k2 = k + 2, c2 = k2 / (P * P), rem2 = k2 - c2 * P * P, ky2 = rem2 / P, kx2 = rem2 - ky2 * P;
+    const float2 a = *reinterpret_cast<const float2*>(frames + ((f * 3 + c) * R + gy * P + ky) * (int64_t)R + gx * P + kx);
+    const float2 b = *reinterpret_cast<const float2*>(frames + ((f * 3 + c2) * R + gy * P + ky2) * (int64_t)R + gx * P + kx2);
+    v = make_float4(a.x, a.y, b.x, b.y);
+  }
   if constexpr (OUT_BF16 >= 2) {
     // three bf16 planes hi | mid | lo of the f32 pixel in K-panel layout (OUT_BF16 == 3, ACX_BF16X2P: hi and mid only) (ACX_BF16X3P: plane = [K / 32][rows][32]): the A operand
     // of the patch embedding as a pairs = 6 product (ACX_PREC_F32X6)
@@ -700,7 +709,7 @@ extern "C" int acx_vit_patches(acx_ctx* ctx, const float* frames, void* patches,
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
   if (!frames || !patches) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_patches: null pointer%s");
   if (F <= 0) return ACX_OK;
-  if (P % 4 || R % P) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_patches: need P%%4==0 and R%%P==0%s");
+  if (P <= 0 || P % 2 || R % P) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_patches: need P%%2==0 and R%%P==0%s");
   const int g = R / P;
   const int64_t total4 = (int64_t)F * g * g * 3 * P * P / 4;
   const dim3 grid((unsigned)((total4 + 255) / 256)), block(256);

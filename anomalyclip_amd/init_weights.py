@@ -52,6 +52,13 @@ class ClipGeometry:
 
 
 VIT_B16 = ClipGeometry()
+# the other ViT backbones of clip.load (clip/clip.py:31-41), with CLIP's published shapes
+VIT_B32 = ClipGeometry(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=32,
+                       transformer_width=512, transformer_heads=8, transformer_layers=12)
+VIT_L14 = ClipGeometry(embed_dim=768, image_resolution=224, vision_layers=24, vision_width=1024, vision_patch_size=14,
+                       transformer_width=768, transformer_heads=12, transformer_layers=12)
+VIT_L14_336 = ClipGeometry(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
+                           transformer_width=768, transformer_heads=12, transformer_layers=12)
 # tiny geometry used by fixtures (head dim stays 64 like every CLIP ViT)
 TINY = ClipGeometry(embed_dim=128, image_resolution=32, vision_layers=2, vision_width=128,
                     vision_patch_size=16, context_length=77, vocab_size=49408,

@@ -197,13 +197,14 @@ int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, con
                   int32_t mode, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * acx_attention: multi-head softmax(q k^T / sqrt(64)) v for head dim 64, sequence <= 224.
- * replaces nn.MultiheadAttention's core as used by clip/model.py:206-212 (ViT: L=197, no mask;
- * text: L=77, causal mask clip/model.py:386-392).  qkv: [batch*L, 3*heads*64] packed as
+ * acx_attention: multi-head softmax(q k^T / sqrt(64)) v for head dim 64; causal L <= 224, non-causal L <= 1024
+ * (L > 224: out 16-byte aligned with ldo % 4 == 0, and a non-NULL ctx -- a NULL ctx keeps the earlier answer ACX_E_UNSUPPORTED
+ * above 224, the contract context-free callers had before longer sequences were supported).  Replaces nn.MultiheadAttention's core as used by clip/model.py:206-212
+ * (ViT: L = 50 / 197 / 257 / 577 for B/32, B/16, L/14, L/14@336px, no mask; text: L=77, causal mask clip/model.py:386-392).  qkv: [batch*L, 3*heads*64] packed as
  * in_proj output (q | k | v); out: [batch*L, heads*64]. */
 int acx_attention(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo,
                   int32_t batch, int32_t L, int32_t heads, int32_t causal, void* stream);
-/* the same (non-causal ViT sequences, 128 < L <= 224) with the output as three bf16 planes hi | mid | lo (ACX_BF16X3:
+/* the same (non-causal ViT sequences, 128 < L <= 1024) with the output as three bf16 planes hi | mid | lo (ACX_BF16X3:
  * plane p at (uint16_t*)out_planes + p * batch * L * ldo): the out-projection's A operand in ACX_PREC_F32X6 mode */
 int acx_attention_x3(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
                      int32_t batch, int32_t L, int32_t heads, void* stream);
@@ -226,15 +227,16 @@ int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* 
  * [batch*L, ldo] are bf16, QK^T and PV run on the bf16 MFMA, softmax in f32.  Non-causal only. */
 int acx_attention_bf16(acx_ctx* ctx, const void* qkv, int64_t ldqkv, void* out, int64_t ldo, int32_t batch,
                        int32_t L, int32_t heads, void* stream);
-/* acx_attention_cls: same attention, but only for query row 0 of every sequence (out [batch, heads*64]).
+/* acx_attention_cls: same attention, but only for query row 0 of every sequence (out [batch, heads*64]); 0 < L <= 1024.
  * Used for the LAST ViT layer, whose output is consumed at the CLS token only (clip/model.py:285). */
 int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo,
                       int32_t batch, int32_t L, int32_t heads, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * acx_vit_patches: im2col of 16x16/16 patches (clip/model.py:246-252,267-269).
+ * acx_vit_patches: im2col of PxP/P patches, P even and R % P == 0 (P = 14 / 16 / 32: clip/model.py:246-252,267-269).
  * frames [F,3,R,R] f32 -> patches [F*g*g, 3*P*P] (k = c*P*P + ky*P + kx, token = gy*g+gx); out_dtype ACX_F32, ACX_BF16, or
- * ACX_BF16X3P (three bf16 planes of the f32 pixels in K-panel layout: the patch embedding's A operand in ACX_PREC_F32X6). */
+ * ACX_BF16X3P (three bf16 planes of the f32 pixels in K-panel layout: the patch embedding's A operand in ACX_PREC_F32X6; the plane
+ * layouts need 3 P P % 32 == 0, which P = 14 does not meet). */
 int acx_vit_patches(acx_ctx* ctx, const float* frames, void* patches, int32_t out_dtype,
                     int32_t F, int32_t R, int32_t P, void* stream);
 /* acx_vit_embed: x[f,0,:] = cls + pos[0]; x[f,1+t,:] = patch_out[f,t,:] + pos[1+t]; then ln_pre
@@ -272,7 +274,9 @@ typedef struct acx_vit_desc {
 } acx_vit_desc;
 
 /* acx_vit_encode: VisionTransformer.forward (clip/model.py:266-290): frames [F,3,R,R] f32 ->
- * features [F, embed_dim] f32.  Workspace from acx_vit_workspace_bytes(desc, F). */
+ * features [F, embed_dim] f32.  Workspace from acx_vit_workspace_bytes(desc, F).  Geometry: resolution % patch == 0, patch even,
+ * (resolution / patch)^2 + 1 <= 1024 tokens (ACX_E_UNSUPPORTED above), width == 64 heads.  A patch that is not a multiple of 4
+ * embeds on the f32 kernels in every precision. */
 size_t acx_vit_workspace_bytes(const acx_vit_desc* d, int32_t frames);
 int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w,
                    const float* frames, int32_t nframes, float* features, void* workspace,
