@@ -13,7 +13,7 @@ c_void_p, c_int32, c_int64, c_float, c_size_t = C.c_void_p, C.c_int32, C.c_int64
 ACX_F32, ACX_BF16, BF16X3, BF16X3P = 0, 1, 2, 3      # BF16X3 / BF16X3P: output only (three bf16 planes hi | mid | lo; P: K-panel layout)
 BF16X2P, ACX_F16, F16X2P = 4, 5, 6                     # hi + mid planes only; fp16 planes of the two-plane split (pairs = 3); their K-panel output
 PREC_F32, PREC_BF16, PREC_F32X6, PREC_F32X3, PREC_F16X3 = 0, 1, 2, 3, 4
-ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU = 0, 1, 2
+ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
 OPT_RING_MIN_TILES, OPT_SK_MAX_M, OPT_TN_P256_MIN_ROWS, OPT_X6_CUS, OPT_X6_TAIL_SPLIT = 1, 2, 3, 4, 5
@@ -80,6 +80,37 @@ class VitDesc(C.Structure):
     _fields_ = [(n, c_int32) for n in ("resolution", "patch", "width", "layers", "heads", "embed_dim", "prec")]
 
 
+class ResnetConv(C.Structure):          # == struct acx_resnet_conv
+    _fields_ = [("w", c_void_p), ("b", c_void_p)]
+
+
+class ResnetBlock(C.Structure):         # == struct acx_resnet_block
+    _fields_ = [("conv1", ResnetConv), ("conv2", ResnetConv), ("conv3", ResnetConv), ("downsample", ResnetConv)]
+
+
+class ResnetWeights(C.Structure):       # == struct acx_resnet_weights
+    _fields_ = [("stem", ResnetConv * 3), ("blocks", C.POINTER(ResnetBlock)), ("positional_embedding", c_void_p),
+                ("q_w", c_void_p), ("q_b", c_void_p), ("kv_w", c_void_p), ("kv_b", c_void_p), ("c_w", c_void_p), ("c_b", c_void_p)]
+
+
+class ResnetBn(C.Structure):            # == struct acx_resnet_bn
+    _fields_ = [("weight", c_void_p), ("bias", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("num_batches_tracked", c_void_p)]
+
+
+class ResnetBlockBn(C.Structure):       # == struct acx_resnet_block_bn
+    _fields_ = [("bn1", ResnetBn), ("bn2", ResnetBn), ("bn3", ResnetBn), ("downsample", ResnetBn)]
+
+
+class ResnetTrainBn(C.Structure):       # == struct acx_resnet_train_bn
+    _fields_ = [("stem", ResnetBn * 3), ("blocks", C.POINTER(ResnetBlockBn)), ("eps", c_float), ("momentum", c_float)]
+
+
+class ResnetDesc(C.Structure):          # == struct acx_resnet_desc
+    _fields_ = [("resolution", c_int32), ("width", c_int32), ("layers", c_int32 * 4), ("heads", c_int32), ("output_dim", c_int32),
+                ("prec", c_int32)]
+
+
 _SIGS = {
     "acx_version": (C.c_int, []),
     "acx_create": (C.c_int, [C.POINTER(c_void_p), C.c_int]),
@@ -99,6 +130,17 @@ _SIGS = {
     "acx_attention_cls": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_vit_patches": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "acx_vit_embed": (C.c_int, [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_void_p]),
+    "acx_resnet_stem_im2col": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "acx_avgpool2_nhwc": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attnpool_tokens": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_resnet_workspace_bytes": (c_size_t, [C.POINTER(ResnetDesc), c_int32]),
+    "acx_bn_apply_nhwc": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                    c_int32, c_float, c_int32, c_void_p, c_void_p]),
+    "acx_resnet_train_workspace_bytes": (c_size_t, [C.POINTER(ResnetDesc), c_int32]),
+    "acx_resnet_encode_train": (C.c_int, [c_void_p, C.POINTER(ResnetDesc), C.POINTER(ResnetWeights), C.POINTER(ResnetTrainBn), c_void_p,
+                                          c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "acx_resnet_encode": (C.c_int, [c_void_p, C.POINTER(ResnetDesc), C.POINTER(ResnetWeights), c_void_p, c_int32, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     "acx_vit_workspace_bytes": (c_size_t, [C.POINTER(VitDesc), c_int32]),
     "acx_vit_encode": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_int32, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),

@@ -22,15 +22,17 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, TINY
+from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, RN50, RN101, RN50X4, RN50X16, RN50X64, TINY
+from .clip_resnet import ModifiedResNet, check_resnet_precision
 from .clip_vit import VisionTransformer, check_vit_precision
 from .coop import PromptLearner
 from .selector_model import SelectorModel
 from .temporal_model import TemporalModel
 from .text_encoder import TextEncoder
 
-# `net.arch`: the ViT backbones of clip.load (clip/clip.py:31-41); "tiny" is the test geometry
-_ARCH = {"ViT-B/16": VIT_B16, "ViT-B/32": VIT_B32, "ViT-L/14": VIT_L14, "ViT-L/14@336px": VIT_L14_336, "tiny": TINY}
+# `net.arch`: the nine backbones of clip.load (clip/clip.py:31-41); "tiny" is the test geometry
+_ARCH = {"ViT-B/16": VIT_B16, "ViT-B/32": VIT_B32, "ViT-L/14": VIT_L14, "ViT-L/14@336px": VIT_L14_336,
+         "RN50": RN50, "RN101": RN101, "RN50x4": RN50X4, "RN50x16": RN50X16, "RN50x64": RN50X64, "tiny": TINY}
 
 
 def geometry_of_arch(arch: str) -> ClipGeometry:
@@ -42,8 +44,12 @@ def geometry_of_arch(arch: str) -> ClipGeometry:
 
 def _describe(geom: ClipGeometry) -> str:
     name = next((a for a, g_ in _ARCH.items() if g_ == geom), None)
-    body = (f"image: width {geom.vision_width}, {geom.vision_layers} layers, patch {geom.vision_patch_size}, resolution "
-            f"{geom.image_resolution}, embed {geom.embed_dim}; text: width {geom.transformer_width}, {geom.transformer_layers} layers")
+    if geom.is_resnet:
+        image = f"image: ResNet width {geom.vision_width}, blocks {tuple(geom.vision_layers)}"
+    else:
+        image = f"image: width {geom.vision_width}, {geom.vision_layers} layers, patch {geom.vision_patch_size}"
+    body = (f"{image}, resolution {geom.image_resolution}, embed {geom.embed_dim}; text: width {geom.transformer_width}, "
+            f"{geom.transformer_layers} layers")
     return f"{name} ({body})" if name else body
 
 
@@ -53,7 +59,17 @@ def geometry_from_state_dict(sd) -> Optional[ClipGeometry]:
     import math
     kw = {}
     conv = sd.get("image_encoder.conv1.weight")
-    if conv is not None:
+    rpos = sd.get("image_encoder.attnpool.positional_embedding")
+    if conv is not None and (rpos is not None or "image_encoder.layer1.0.conv1.weight" in sd):
+        # ModifiedResNet (clip/model.py:111-171; CLIP's build_model reads the same keys)
+        layers = tuple(len({k.split(".")[2] for k in sd if k.startswith(f"image_encoder.layer{i}.")}) for i in (1, 2, 3, 4))
+        kw.update(vision_layers=layers, vision_width=2 * int(conv.shape[0]), vision_patch_size=None)
+        if rpos is not None:
+            kw["image_resolution"] = 32 * int(round(math.sqrt(int(rpos.shape[0]) - 1)))
+        cproj = sd.get("image_encoder.attnpool.c_proj.weight")
+        if cproj is not None:
+            kw["embed_dim"] = int(cproj.shape[0])
+    elif conv is not None:
         pos = sd.get("image_encoder.positional_embedding")
         proj = sd.get("image_encoder.proj")
         P = int(conv.shape[-1])
@@ -134,8 +150,17 @@ class AnomalyCLIP(nn.Module):
         if isinstance(geom, dict):
             geom = ClipGeometry(**geom)
         self.geometry = geom
-        check_vit_precision(vit_precision, geom.grid ** 2 + 1, geom.vision_width, self.arch, geom.image_resolution,
-                            geom.vision_patch_size)                                    # (before anything is allocated)
+        if geom.is_resnet:
+            check_resnet_precision(vit_precision, self.arch, geom.vision_width)      # (before anything is allocated)
+            if geom.embed_dim != geom.transformer_width:
+                # the reference takes embedding_dim from ln_final (anomaly_clip.py:72): TemporalModel.projection and the ncentroid
+                # re-centring then meet image features of another width and fail (RN50: 1024-wide features, 512-wide text tower)
+                raise ValueError(f"{self.arch} cannot run inside AnomalyCLIP: its image features are {geom.embed_dim} wide, its text "
+                                 f"tower (embedding_dim, anomaly_clip.py:72) is {geom.transformer_width} wide; use its image "
+                                 "encoder (components.clip_resnet.ModifiedResNet) on its own as a feature extractor")
+        else:
+            check_vit_precision(vit_precision, geom.grid ** 2 + 1, geom.vision_width, self.arch, geom.image_resolution,
+                                geom.vision_patch_size)                                # (before anything is allocated)
 
         classnames = g("classnames")
         tokenized = g("tokenized_prompts")
@@ -173,9 +198,13 @@ class AnomalyCLIP(nn.Module):
         self.text_len = min(full, (int(tokenized.argmax(dim=-1).max()) + 1 + 3) // 4 * 4) if bool(g("text_truncate", True)) else full
         self.text_encoder = TextEncoder(geom.context_length, geom.transformer_width, geom.transformer_heads,
                                         geom.transformer_layers, geom.embed_dim, head_precision)
-        self.image_encoder = VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width,
-                                               geom.vision_layers, geom.vision_heads, geom.embed_dim,
-                                               precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
+        if geom.is_resnet:
+            self.image_encoder = ModifiedResNet(geom.vision_layers, geom.embed_dim, geom.resnet_heads, geom.image_resolution,
+                                                geom.vision_width, precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
+        else:
+            self.image_encoder = VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width,
+                                                   geom.vision_layers, geom.vision_heads, geom.embed_dim,
+                                                   precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
         self.selector_model = SelectorModel(classnames, self.normal_id, nn.Parameter(torch.tensor(2.6592601)),
                                             self.num_segments, self.seg_length, self.select_idx_dropout_topk,
                                             self.select_idx_dropout_bottomk, self.num_topk, self.num_bottomk)
@@ -206,7 +235,8 @@ class AnomalyCLIP(nn.Module):
         mine = self.state_dict()
         bad = [k for k, v in state_dict.items() if k.startswith(("image_encoder.", "text_encoder.")) and torch.is_tensor(v)
                and k in mine and tuple(v.shape) != tuple(mine[k].shape)]
-        bad += [k for k in state_dict if k.startswith(("image_encoder.transformer.resblocks.", "text_encoder.transformer.resblocks."))
+        bad += [k for k in state_dict if k.startswith(("image_encoder.transformer.resblocks.", "text_encoder.transformer.resblocks.",
+                                                       "image_encoder.layer", "image_encoder.attnpool."))
                 and k not in mine]
         if bad:
             theirs = geometry_from_state_dict(state_dict)

@@ -404,7 +404,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
         const int act = FAST ? ACT : d.act;
         if (act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
         else if (act == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
+        else if (act == ACX_ACT_RELU) v = fmaxf(v, 0.f);
         outv[r] += v;
+        if (act == ACX_ACT_RESRELU) outv[r] = fmaxf(outv[r], 0.f);
       }
       // all loads consumed: make that explicit so the store loop below carries no memory dependencies
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -453,6 +455,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   if (d.bias) v += d.bias[col];
   if (d.act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
   else if (d.act == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
+  else if (d.act == ACX_ACT_RELU) v = fmaxf(v, 0.f);
   // same order as the unsplit kernel's epilogue: (residual + (pos0 + pos1)) + activation(acc + bias)
   float o = d.residual ? d.residual[(size_t)row * d.ldr + col] : 0.f;
   if (d.pos0) {
@@ -460,6 +463,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     o += d.pos0[(size_t)n * d.N + col] + d.pos1[(size_t)l * d.N + col];
   }
   o += v;
+  if (d.act == ACX_ACT_RESRELU) o = fmaxf(o, 0.f);
   if constexpr (C_BF16 == 2) {               // ACX_BF16X3: three bf16 planes hi | mid | lo of the f32 value
     const size_t pe = (d.c_plane_rows ? (size_t)d.c_plane_rows : (size_t)d.M) * d.ldc, at = (size_t)row * d.ldc + col;
     const u16 h = f2bf(o);
@@ -501,11 +505,16 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __rest
   for (int e = 0; e < 4; ++e) {
     if (d.act == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);
     else if (d.act == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
+    else if (d.act == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
   }
   float o[4] = {0.f, 0.f, 0.f, 0.f};
   if (d.residual) { const float4 r4 = *reinterpret_cast<const float4*>(d.residual + (size_t)row * d.ldr + col); o[0] = r4.x; o[1] = r4.y; o[2] = r4.z; o[3] = r4.w; }
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] += v[e];
+  if (d.act == ACX_ACT_RESRELU) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+  }
   if constexpr (OUT == 2) {
     const size_t crows = d.c_plane_rows ? (size_t)d.c_plane_rows : (size_t)d.M;
     const size_t pe = crows * d.ldc;
@@ -614,6 +623,14 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
   }
   if ((d->pos0 != nullptr) != (d->pos1 != nullptr) || (d->pos0 && (d->gn <= 0 || d->gl <= 0)))
     return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: pos0/pos1 need both pointers and a grid%s");
+  // the ReLU epilogues (ResNet encoder): f32 products on the identity / CONV3X3 row maps only
+  const bool relu_act = d->act == ACX_ACT_RELU || d->act == ACX_ACT_RESRELU;
+  if (relu_act && (prec != ACX_PREC_F32 || d->pairs > 1 || c_bf16 || d->a_sub || d->pos0 || d->a_act != ACX_ACT_NONE ||
+                   d->gelu_grad_of || d->a_norm_w || (d->amap != ACX_AMAP_IDENTITY && d->amap != ACX_AMAP_CONV3X3)))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_RELU / ACX_ACT_RESRELU need an f32 product on identity or CONV3X3 rows%s");
+  if (d->act == ACX_ACT_RESRELU && !d->residual)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: ACX_ACT_RESRELU needs a residual%s");
+  if (d->act < ACX_ACT_NONE || d->act > ACX_ACT_RESRELU) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: unknown act%s");
 
   // ---- pairs = 6, more 256 x 256 tiles than CUs, a last round that fills only part of the chip (the ViT's N = 768 products: 1182
   // tiles = 4.6 rounds at 512 frames, 591 = 2.3 at 256): the whole tile rows of the full rounds go out as one launch, the rest
@@ -712,7 +729,8 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
                        !((uintptr_t)d->C & 15) && (!d->residual || (d->ldr % 4 == 0 && !((uintptr_t)d->residual & 15))) &&
                        (!d->gelu_grad_of || (d->ldg % 4 == 0 && !((uintptr_t)d->gelu_grad_of & 15) && !d->residual &&
                                              d->act == ACX_ACT_NONE)) &&
-                       !(d->act == ACX_ACT_QUICKGELU && d->residual) && (d->a_act == ACX_ACT_NONE || d->a_act == ACX_ACT_QUICKGELU) &&
+                       !(d->act == ACX_ACT_QUICKGELU && d->residual) && !relu_act &&
+                       (d->a_act == ACX_ACT_NONE || d->a_act == ACX_ACT_QUICKGELU) &&
                        (size_t)d->M * d->lda < ((size_t)1 << 31) && (size_t)d->N * d->ldw < ((size_t)1 << 31);
     if (sk_fusion && !sk_ok)
       return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_act / gelu_grad_of / a_norm need the few-row f32 kernel (see acx_gemm_desc)%s");
@@ -950,6 +968,8 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
     hipLaunchKernelGGL((gemm_f32_s64_kernel<ACT, RES>), sgrid, dim3(256), lds_s, s, g);             \
   } while (0)
     if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_S64L(1, 1); else ACX_S64L(1, 0); }
+    else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_S64L(3, 1); else ACX_S64L(3, 0); }
+    else if (d->act == ACX_ACT_RESRELU) ACX_S64L(4, 1);
     else { if (d->residual) ACX_S64L(0, 1); else ACX_S64L(0, 0); }
 #undef ACX_S64L
     if (g.ksplit > 1) {
@@ -998,8 +1018,9 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
     }                                                                                               \
     hipLaunchKernelGGL((gemm_f32_p256_kernel<ACT, 0, CV>), pgrid, dim3(1024), plds, s, g);          \
   } while (0)
-    if (d->amap == ACX_AMAP_CONV3X3) { if (d->act == ACX_ACT_LEAKYRELU) ACX_P2L(2, 1); else ACX_P2L(0, 1); }
-    else if (d->act == ACX_ACT_QUICKGELU) ACX_P2L(1, 0); else ACX_P2L(0, 0);
+    if (d->amap == ACX_AMAP_CONV3X3) {
+      if (d->act == ACX_ACT_LEAKYRELU) ACX_P2L(2, 1); else if (d->act == ACX_ACT_RELU) ACX_P2L(3, 1); else ACX_P2L(0, 1);
+    } else if (d->act == ACX_ACT_QUICKGELU) ACX_P2L(1, 0); else if (d->act == ACX_ACT_RELU) ACX_P2L(3, 0); else ACX_P2L(0, 0);
 #undef ACX_P2L
     ACX_CHECK_LAUNCH(ctx, "acx_gemm");
     return ACX_OK;
@@ -1020,9 +1041,13 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
     if (w8_conv) {
       if (d->act == ACX_ACT_LEAKYRELU) { if (d->residual) ACX_W8L(2, 1, 1); else ACX_W8L(2, 0, 1); }
       else if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_W8L(1, 1, 1); else ACX_W8L(1, 0, 1); }
+      else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_W8L(3, 1, 1); else ACX_W8L(3, 0, 1); }
+      else if (d->act == ACX_ACT_RESRELU) ACX_W8L(4, 1, 1);
       else { if (d->residual) ACX_W8L(0, 1, 1); else ACX_W8L(0, 0, 1); }
     } else {
       if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_W8L(1, 1, 0); else ACX_W8L(1, 0, 0); }
+      else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_W8L(3, 1, 0); else ACX_W8L(3, 0, 0); }
+      else if (d->act == ACX_ACT_RESRELU) ACX_W8L(4, 1, 0);
       else { if (d->residual) ACX_W8L(0, 1, 0); else ACX_W8L(0, 0, 0); }
     }
 #undef ACX_W8L
@@ -1161,7 +1186,7 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
       default: ACX_DMA(1, 1, 1); break;
     }
 #undef ACX_DMA
-  } else if (fast) {
+  } else if (fast && !relu_act) {          // (the ReLU epilogues take the generic instantiation's run-time act)
     switch (variant) {
       case 0: ACX_FAST(0, 0, 0); break;
       case 1: ACX_FAST(0, 0, 1); break;

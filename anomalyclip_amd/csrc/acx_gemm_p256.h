@@ -250,6 +250,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_f32_p256_kernel(const Args g) {
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
           if constexpr (ACT == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);                      \
           if constexpr (ACT == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];          \
+          if constexpr (ACT == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);                                \
         }                                                                                          \
         float4 ov = make_float4(v[0], v[1], v[2], v[3]);                                           \
         if constexpr (RES != 0) ov = make_float4(rs[i].x + v[0], rs[i].y + v[1], rs[i].z + v[2], rs[i].w + v[3]); \
@@ -266,6 +267,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_f32_p256_kernel(const Args g) {
         float v = ACC[r] + bias;                                                                   \
         if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);                              \
         if constexpr (ACT == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;                       \
+        if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);                                      \
         if constexpr (RES != 0) v += d.residual[(size_t)min(row, d.M - 1) * d.ldr + colc];         \
         if (cok && row < d.M) ((float*)d.C)[(size_t)row * d.ldc + col] = v;                        \
         ACC[r] = 0.f;                                                                              \

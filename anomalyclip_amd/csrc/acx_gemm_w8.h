@@ -313,8 +313,11 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_w8_kernel(const Args g) {
         for (int e = 0; e < 4; ++e) {
           if constexpr (ACT == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);
           if constexpr (ACT == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
+          if constexpr (ACT == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
         }
         ov[i] = make_float4(rs[i].x + v[0], rs[i].y + v[1], rs[i].z + v[2], rs[i].w + v[3]);
+        if constexpr (ACT == ACX_ACT_RESRELU)
+          ov[i] = make_float4(fmaxf(ov[i].x, 0.f), fmaxf(ov[i].y, 0.f), fmaxf(ov[i].z, 0.f), fmaxf(ov[i].w, 0.f));
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -349,7 +352,9 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_w8_kernel(const Args g) {
       float v = acc[mi][r] + bias;
       if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
       if constexpr (ACT == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
+      if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);
       outv[r] += v;
+      if constexpr (ACT == ACX_ACT_RESRELU) outv[r] = fmaxf(outv[r], 0.f);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -476,7 +481,9 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_s64_kernel(const Args g) {
   for (int r = 0; r < 16; ++r) {
     float v = acc[r] + bias;
     if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
+    if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);
     outv[r] += v;
+    if constexpr (ACT == ACX_ACT_RESRELU) outv[r] = fmaxf(outv[r], 0.f);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll

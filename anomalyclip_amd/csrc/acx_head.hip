@@ -741,9 +741,47 @@ static inline int bn_blocks(int64_t rows) {
   return (int)(nb < 1 ? 1 : (nb > 512 ? 512 : nb));
 }
 extern "C" size_t acx_bn_workspace_bytes(int64_t rows, int32_t C1) {
-  (void)rows;
+  if (C1 > 64) return (size_t)bn_blocks(rows) * 2 * C1 * sizeof(double);   // wide: [slabs][2][C1] f64
   return (size_t)1024 * 2 * 64 * sizeof(double) * (C1 > 0 ? 1 : 1);     // [<= 1024 blocks][2][<= 64 columns] f64
 }
+
+namespace {
+// acx_bn_stats for C1 > 64 (the ResNet encoders' training-mode BatchNorm2d over NHWC rows, up to 4096 channels): stage 1 gives
+// each lane ONE column of a slab of rows (coalesced across the block's 256 columns) and sums (x, x^2) in f64 in row order; stage
+// 2 adds the slabs' partials per column in slab order.  A pure function of (rows, C1): run-to-run identical.
+__global__ __launch_bounds__(256) void bn_wide_partial_kernel(const float* __restrict__ raw, int64_t rows, int C, int64_t rpb,
+                                                              double* __restrict__ part) {
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= C) return;
+  const int64_t r0 = (int64_t)blockIdx.x * rpb;
+  const int64_t r1 = r0 + rpb < rows ? r0 + rpb : rows;
+  double s = 0.0, q = 0.0;
+  for (int64_t r = r0; r < r1; ++r) {
+    const double v = raw[r * C + c];
+    s += v;
+    q += v * v;
+  }
+  part[(size_t)blockIdx.x * 2 * C + c] = s;
+  part[((size_t)blockIdx.x * 2 + 1) * C + c] = q;
+}
+__global__ __launch_bounds__(256) void bn_wide_finalize_kernel(const double* __restrict__ part, int nb, int C, int64_t rows,
+                                                               float* __restrict__ mean, float* __restrict__ var_b,
+                                                               float* __restrict__ var_u) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  double s = 0.0, qq = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    s += part[(size_t)b * 2 * C + c];
+    qq += part[((size_t)b * 2 + 1) * C + c];
+  }
+  const double n = (double)rows, m = s / n;                            // (the expressions of bn_finalize_kernel)
+  double m2 = qq - s * m;
+  if (m2 < 0.0) m2 = 0.0;
+  mean[c] = (float)m;
+  var_b[c] = (float)(m2 / n);
+  var_u[c] = rows > 1 ? (float)(m2 / (n - 1.0)) : 0.f;
+}
+}  // namespace
 
 // shared launcher: projection (+ optional fused batch statistics); returns false when the shape does not fit the MFMA kernel
 static bool launch_selector_mfma(const float* x, const float* nc, const float* dirs, float* raw, int64_t rows, int D, int C1,
@@ -829,8 +867,8 @@ extern "C" int acx_selector_project(acx_ctx* ctx, const float* x, const float* n
   if (!x || !ncentroid || !dirs || !raw) return acx_fail(ctx, ACX_E_BADARG, "acx_selector_project: null pointer%s");
   if (rows <= 0) return ACX_OK;
   if (C1 <= 0 || C1 > 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_selector_project: need 1 <= C-1 <= 64%s");
-  if (D % 64 || D > 1024 || (D / 64 != 1 && D / 64 != 2 && (D / 64) % 4))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_selector_project: D must be 64/128/256/512/768/1024%s");
+  if (D % 64 || D > 1024 || (D / 64 != 1 && D / 64 != 2 && D / 64 != 10 && (D / 64) % 4))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_selector_project: D must be 64/128/256/512/640/768/1024%s");
   if ((((uintptr_t)x | (uintptr_t)ncentroid | (uintptr_t)dirs) & 15))
     return acx_fail(ctx, ACX_E_BADARG, "acx_selector_project: x / ncentroid / dirs must be 16-byte aligned%s");
   hipStream_t s = (hipStream_t)stream;
@@ -856,6 +894,7 @@ extern "C" int acx_selector_project(acx_ctx* ctx, const float* x, const float* n
     case 2: ACX_SEL(2); break;
     case 4: ACX_SEL(4); break;
     case 8: ACX_SEL(8); break;
+    case 10: ACX_SEL(10); break;     // (640, RN50x4: the wave-per-row kernel; the MFMA kernel's chunking needs D / 32 even chunks)
     case 12: ACX_SEL(12); break;
     default: ACX_SEL(16); break;
   }
@@ -897,12 +936,20 @@ extern "C" int acx_bn_stats(acx_ctx* ctx, const float* raw, int64_t rows, int32_
                             float* var_unbiased, void* workspace, size_t workspace_bytes, void* stream) {
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
   if (!raw || !mean || !var_biased || !var_unbiased || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_bn_stats: null pointer%s");
-  if (rows <= 0 || C1 <= 0 || C1 > 64) return acx_fail(ctx, ACX_E_BADARG, "acx_bn_stats: need rows > 0 and 1 <= C1 <= 64%s");
+  if (rows <= 0 || C1 <= 0 || C1 > 65536) return acx_fail(ctx, ACX_E_BADARG, "acx_bn_stats: need rows > 0 and 1 <= C1 <= 65536%s");
   if (workspace_bytes < acx_bn_workspace_bytes(rows, C1) || ((uintptr_t)workspace & 7))
     return acx_fail(ctx, ACX_E_BADARG, "acx_bn_stats: workspace too small (acx_bn_workspace_bytes) or misaligned%s");
   hipStream_t s = (hipStream_t)stream;
   const int nb = bn_blocks(rows);
   const int64_t rpb = (rows + nb - 1) / nb;
+  if (C1 > 64) {                                  // wide: its own decomposition (C1 <= 64 keeps the kernels and bits below)
+    hipLaunchKernelGGL(bn_wide_partial_kernel, dim3((unsigned)nb, (unsigned)((C1 + 255) / 256)), dim3(256), 0, s, raw, rows, C1, rpb,
+                       (double*)workspace);
+    hipLaunchKernelGGL(bn_wide_finalize_kernel, dim3((unsigned)((C1 + 255) / 256)), dim3(256), 0, s, (const double*)workspace, nb, C1,
+                       rows, mean, var_biased, var_unbiased);
+    ACX_CHECK_LAUNCH(ctx, "acx_bn_stats");
+    return ACX_OK;
+  }
   hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(nb), dim3(256), 0, s, raw, (const float*)nullptr, rows, C1, 64, rpb, (double*)workspace);
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, nb, 64, C1, rows, mean, var_biased,
                      var_unbiased);

@@ -245,9 +245,10 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__
     case 2: { constexpr int V = 2; CALL; } break;      \
     case 4: { constexpr int V = 4; CALL; } break;      \
     case 8: { constexpr int V = 8; CALL; } break;      \
+    case 10: { constexpr int V = 10; CALL; } break;    \
     case 12: { constexpr int V = 12; CALL; } break;    \
     case 16: { constexpr int V = 16; CALL; } break;    \
-    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,768,1024}", "", (long)(D)); \
+    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,640,768,1024}", "", (long)(D)); \
   }
 
 extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,

@@ -339,7 +339,7 @@ __global__ void bn_pack_kernel(const float* __restrict__ mean, const float* __re
 // nn.BatchNorm1d's running statistics: r = (1 - momentum) r + momentum x (selector_model.py:30,65), batch counter + 1
 __global__ void bn_running_kernel(const float* __restrict__ mean, const float* __restrict__ var_u, float* __restrict__ rm,
                                   float* __restrict__ rv, long long* __restrict__ nbt, int C, float momentum, float om) {
-  const int i = threadIdx.x;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < C) {
     rm[i] = acx_bn_running(momentum, om, mean[i], rm[i]);
     rv[i] = acx_bn_running(momentum, om, var_u[i], rv[i]);
@@ -584,9 +584,11 @@ extern "C" int acx_bn_running_update(acx_ctx* ctx, const float* mean, const floa
                                      void* stream) {
   if (!mean || !var_unbiased || !running_mean || !running_var)
     return acx_fail(ctx, ACX_E_BADARG, "acx_bn_running_update: null pointer%s");
-  if (C1 <= 0 || C1 > 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_bn_running_update: 1 <= C1 <= 1024%s");
+  if (C1 <= 0 || C1 > 65536) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_bn_running_update: 1 <= C1 <= 65536%s");
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
-  hipLaunchKernelGGL(bn_running_kernel, dim3(1), dim3((unsigned)((C1 + 63) / 64 * 64)), 0, (hipStream_t)stream, mean, var_unbiased,
+  // one block up to 1024 channels (as before), blocks of 1024 beyond (the ResNet encoders' BatchNorm2d: up to 4096)
+  const unsigned nblk = (unsigned)((C1 + 1023) / 1024), bs = C1 > 1024 ? 1024u : (unsigned)((C1 + 63) / 64 * 64);
+  hipLaunchKernelGGL(bn_running_kernel, dim3(nblk), dim3(bs), 0, (hipStream_t)stream, mean, var_unbiased,
                      running_mean, running_var, (long long*)num_batches_tracked, C1, momentum, one_minus);
   ACX_CHECK_LAUNCH(ctx, "acx_bn_running_update");
   return ACX_OK;

@@ -1777,9 +1777,10 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restri
     case 2: { constexpr int V = 2; CALL; } break;      \
     case 4: { constexpr int V = 4; CALL; } break;      \
     case 8: { constexpr int V = 8; CALL; } break;      \
+    case 10: { constexpr int V = 10; CALL; } break;    \
     case 12: { constexpr int V = 12; CALL; } break;    \
     case 16: { constexpr int V = 16; CALL; } break;    \
-    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,768,1024}", "", (long)(D)); \
+    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,640,768,1024}", "", (long)(D)); \
   }
 #define GRID1(n) dim3((unsigned)(((n) + 255) / 256))
 

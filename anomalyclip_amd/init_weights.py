@@ -15,19 +15,20 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 
 
 @dataclass
 class ClipGeometry:
-    """Constructor arguments of the reference CLIP (clip/model.py:294-308)."""
+    """Constructor arguments of the reference CLIP (clip/model.py:294-308).  `vision_layers` is a tuple of four block counts for
+    the ResNet image encoders (clip/model.py:313-321, vision_patch_size None), an int for the ViTs."""
     embed_dim: int = 512
     image_resolution: int = 224
-    vision_layers: int = 12
+    vision_layers: Union[int, Tuple[int, int, int, int]] = 12
     vision_width: int = 768
-    vision_patch_size: int = 16
+    vision_patch_size: Optional[int] = 16
     context_length: int = 77
     vocab_size: int = 49408
     transformer_width: int = 512
@@ -35,12 +36,25 @@ class ClipGeometry:
     transformer_layers: int = 12
 
     @property
+    def is_resnet(self) -> bool:
+        return isinstance(self.vision_layers, (tuple, list))
+
+    @property
     def vision_heads(self) -> int:
+        if self.is_resnet:
+            raise ValueError("vision_heads is a ViT field: a ResNet's attention pool has resnet_heads = vision_width * 32 // 64")
         return self.vision_width // 64
 
     @property
     def grid(self) -> int:
+        if self.is_resnet:
+            raise ValueError("grid is a ViT field: a ResNet has no patch grid (its attention pool sees resolution // 32 squared)")
         return self.image_resolution // self.vision_patch_size
+
+    @property
+    def resnet_heads(self) -> int:
+        """AttentionPool2d heads (clip/model.py:314): head dim 64 over the 32 * width features."""
+        return self.vision_width * 32 // 64
 
     def as_kwargs(self) -> dict:
         return dict(embed_dim=self.embed_dim, image_resolution=self.image_resolution,
@@ -59,6 +73,17 @@ VIT_L14 = ClipGeometry(embed_dim=768, image_resolution=224, vision_layers=24, vi
                        transformer_width=768, transformer_heads=12, transformer_layers=12)
 VIT_L14_336 = ClipGeometry(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
                            transformer_width=768, transformer_heads=12, transformer_layers=12)
+# the ResNet backbones of clip.load (clip/clip.py:31-41), CLIP's published shapes (vision_layers: blocks of layer1..4)
+RN50 = ClipGeometry(embed_dim=1024, image_resolution=224, vision_layers=(3, 4, 6, 3), vision_width=64, vision_patch_size=None,
+                    transformer_width=512, transformer_heads=8, transformer_layers=12)
+RN101 = ClipGeometry(embed_dim=512, image_resolution=224, vision_layers=(3, 4, 23, 3), vision_width=64, vision_patch_size=None,
+                     transformer_width=512, transformer_heads=8, transformer_layers=12)
+RN50X4 = ClipGeometry(embed_dim=640, image_resolution=288, vision_layers=(4, 6, 10, 6), vision_width=80, vision_patch_size=None,
+                      transformer_width=640, transformer_heads=10, transformer_layers=12)
+RN50X16 = ClipGeometry(embed_dim=768, image_resolution=384, vision_layers=(6, 8, 18, 8), vision_width=96, vision_patch_size=None,
+                       transformer_width=768, transformer_heads=12, transformer_layers=12)
+RN50X64 = ClipGeometry(embed_dim=1024, image_resolution=448, vision_layers=(3, 15, 36, 10), vision_width=128, vision_patch_size=None,
+                       transformer_width=1024, transformer_heads=16, transformer_layers=12)
 # tiny geometry used by fixtures (head dim stays 64 like every CLIP ViT)
 TINY = ClipGeometry(embed_dim=128, image_resolution=32, vision_layers=2, vision_width=128,
                     vision_patch_size=16, context_length=77, vocab_size=49408,
@@ -139,6 +164,60 @@ def init_vit_state_dict(geom: ClipGeometry, seed: int, prefix: str = "image_enco
     return sd
 
 
+def _bn(sd: Dict[str, torch.Tensor], p: str, c: int, gen, gamma: float = 1.0):
+    """BatchNorm2d affine and running statistics, all perturbed away from 1 / 0 / 0 / 1 (a dropped or mis-folded BN fails)."""
+    sd[p + "weight"] = _n(gen, c, std=0.05, mean=gamma)
+    sd[p + "bias"] = _n(gen, c, std=0.05)
+    sd[p + "running_mean"] = _n(gen, c, std=0.1)
+    sd[p + "running_var"] = _n(gen, c, std=0.1, mean=1.0).abs() + 0.05
+    sd[p + "num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
+
+
+def init_resnet_state_dict(geom: ClipGeometry, seed: int, prefix: str = "image_encoder.") -> Dict[str, torch.Tensor]:
+    """Seeded weights of the reference ModifiedResNet (clip/model.py:111-171) under its own key names.  Convolutions at std
+    sqrt(1.5 / fan_in); bn3 (and downsample.1) start at gamma ~0.5 instead of CLIP's zero (clip/model.py:364-372), which would
+    make every residual branch dead in the tests.  With these scales 50-200 convolutions in eval mode keep the features at
+    O(0.1-10) (reference outputs: std 0.22 for RN50 up to 5.0 for RN50x64)."""
+    if not geom.is_resnet:
+        raise ValueError("init_resnet_state_dict needs a ResNet geometry (vision_layers a tuple)")
+    gen = torch.Generator().manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    w = geom.vision_width
+
+    def conv(p, cout, cin, k):
+        sd[p + "weight"] = _n(gen, cout, cin, k, k, std=(1.5 / (cin * k * k)) ** 0.5)
+    conv(prefix + "conv1.", w // 2, 3, 3)
+    _bn(sd, prefix + "bn1.", w // 2, gen)
+    conv(prefix + "conv2.", w // 2, w // 2, 3)
+    _bn(sd, prefix + "bn2.", w // 2, gen)
+    conv(prefix + "conv3.", w, w // 2, 3)
+    _bn(sd, prefix + "bn3.", w, gen)
+    inplanes = w
+    for li, blocks in enumerate(geom.vision_layers):
+        planes = w * 2 ** li
+        for j in range(blocks):
+            p = f"{prefix}layer{li + 1}.{j}."
+            conv(p + "conv1.", planes, inplanes, 1)
+            _bn(sd, p + "bn1.", planes, gen)
+            conv(p + "conv2.", planes, planes, 3)
+            _bn(sd, p + "bn2.", planes, gen)
+            conv(p + "conv3.", 4 * planes, planes, 1)
+            _bn(sd, p + "bn3.", 4 * planes, gen, gamma=0.5)
+            if j == 0 and (li > 0 or inplanes != 4 * planes):
+                conv(p + "downsample.0.", 4 * planes, inplanes, 1)
+                _bn(sd, p + "downsample.1.", 4 * planes, gen, gamma=0.5)
+            inplanes = 4 * planes
+    E = w * 32
+    a = prefix + "attnpool."
+    sd[a + "positional_embedding"] = _n(gen, (geom.image_resolution // 32) ** 2 + 1, E, std=E ** -0.5)
+    for name in ("k_proj", "q_proj", "v_proj"):
+        sd[a + name + ".weight"] = _n(gen, E, E, std=E ** -0.5)
+        sd[a + name + ".bias"] = _n(gen, E, std=0.02)
+    sd[a + "c_proj.weight"] = _n(gen, geom.embed_dim, E, std=E ** -0.5)
+    sd[a + "c_proj.bias"] = _n(gen, geom.embed_dim, std=0.02)
+    return sd
+
+
 def init_text_state_dict(geom: ClipGeometry, seed: int) -> Dict[str, torch.Tensor]:
     gen = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
@@ -194,7 +273,7 @@ def init_anomalyclip_state_dict(geom: ClipGeometry, hc: HeadConfig, tokenized_pr
     "X X X X X X X X <classname>." (reference coop.py:53-56)."""
     sd: Dict[str, torch.Tensor] = {}
     if with_image_encoder:
-        sd.update(init_vit_state_dict(geom, seed + 1))
+        sd.update(init_resnet_state_dict(geom, seed + 1) if geom.is_resnet else init_vit_state_dict(geom, seed + 1))
     sd.update(init_text_state_dict(geom, seed + 2))
     gen = torch.Generator().manual_seed(seed + 3)
     C, w = hc.num_classes, geom.transformer_width

@@ -1309,3 +1309,34 @@ def eval_counts(scores, probs, labels, C: int, normal_idx: int, threshold_dev: t
     L.check(L.lib().acx_test_counts(h, scores.data_ptr(), probs.data_ptr(), labels.data_ptr(), n, C, normal_idx,
                                     threshold_dev.data_ptr(), y.data_ptr(), counts.data_ptr(), _stream()), h)
     return y, counts
+
+
+# ---- the CLIP ResNet encoders' own kernels (include/acx.h acx_resnet_*; the products are acx_gemm with ACX_ACT_RELU / RESRELU)
+def resnet_stem_im2col(frames: torch.Tensor) -> torch.Tensor:
+    """frames [F,3,R,R] f32 -> [F * (R/2)^2, 32]: the stem's 3x3 stride-2 pad-1 columns (k = c * 9 + ky * 3 + kx, 27..31 zero)."""
+    assert frames.dim() == 4 and frames.shape[1] == 3 and frames.dtype == torch.float32 and frames.is_contiguous()
+    F, R = frames.shape[0], frames.shape[2]
+    out = torch.empty(F * (R // 2) ** 2, 32, dtype=torch.float32, device=frames.device)
+    h = _h(frames)
+    L.check(L.lib().acx_resnet_stem_im2col(h, frames.data_ptr(), out.data_ptr(), F, R, _stream()), h)
+    return out
+
+
+def avgpool2_nhwc(x: torch.Tensor) -> torch.Tensor:
+    """x [F, H, W, C] f32 -> [F, H/2, W/2, C]: nn.AvgPool2d(2) on NHWC rows."""
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+    F, H, W, Cc = x.shape
+    out = torch.empty(F, H // 2, W // 2, Cc, dtype=torch.float32, device=x.device)
+    h = _h(x)
+    L.check(L.lib().acx_avgpool2_nhwc(h, x.data_ptr(), out.data_ptr(), F, H, W, Cc, _stream()), h)
+    return out
+
+
+def attnpool_tokens(x: torch.Tensor, pos: torch.Tensor, F: int, HW: int) -> torch.Tensor:
+    """x [F * HW, E] -> [F * (HW + 1), E]: mean token first, + positional embedding [HW + 1, E]."""
+    E = x.shape[1]
+    assert x.is_contiguous() and pos.is_contiguous() and x.shape[0] == F * HW and pos.shape == (HW + 1, E)
+    out = torch.empty(F * (HW + 1), E, dtype=torch.float32, device=x.device)
+    h = _h(x)
+    L.check(L.lib().acx_attnpool_tokens(h, x.data_ptr(), pos.data_ptr(), out.data_ptr(), F, HW, E, _stream()), h)
+    return out

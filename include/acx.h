@@ -66,7 +66,11 @@ enum { ACX_PREC_F32 = 0, ACX_PREC_BF16 = 1,          /* MFMA arithmetic: exact f
                                  planes each (acx_split_bf16x3 of the f32 weight) */
 #define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
-enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2 };
+enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
+       ACX_ACT_RELU = 3,      /* max(x, 0) in the activation slot (clip/model.py:18-22,122-130 ReLU after a folded BatchNorm) */
+       ACX_ACT_RESRELU = 4 }; /* ReLU AFTER the residual add: C = max(residual + (acc + bias), 0) (clip/model.py:62-64, Bottleneck's
+                                 `out += identity; relu3`); needs `residual`.  Both: f32 products (prec ACX_PREC_F32, pairs <= 1) on
+                                 the identity or CONV3X3 row maps, no a_sub / positional epilogue; ACX_E_UNSUPPORTED otherwise */
 enum { ACX_AMAP_IDENTITY = 0, ACX_AMAP_CONV3X3 = 1, ACX_AMAP_TESTTILE = 2, ACX_AMAP_TILETABLE = 3 };
 enum { ACX_NORM_LAYER = 0, ACX_NORM_CHAN = 1 };     /* nn.LayerNorm vs axial_attention ChanLayerNorm (eps added to std) */
 
@@ -282,6 +286,83 @@ int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w
                    const float* frames, int32_t nframes, float* features, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The CLIP ResNet image encoders (RN50, RN101, RN50x4, RN50x16, RN50x64: ModifiedResNet, clip/model.py:111-171), eval mode.
+ * Activations are NHWC rows [frames * H * W][Cp] with Cp = the channel count rounded up to a multiple of 32; the padding
+ * channels are zero (their weight rows / columns and biases are zero). */
+
+/* acx_resnet_stem_im2col: the stem's 3x3 stride-2 pad-1 convolution (clip/model.py:123) as im2col: frames [F,3,R,R] f32 ->
+ * cols [F * (R/2)^2][32], column k = c * 9 + ky * 3 + kx (conv1.weight.reshape(N, 27)'s order), columns 27..31 zero. */
+int acx_resnet_stem_im2col(acx_ctx* ctx, const float* frames, float* cols, int32_t F, int32_t R, void* stream);
+/* acx_avgpool2_nhwc: nn.AvgPool2d(2) (clip/model.py:24,37,132) on NHWC rows: in [F][H][W][C] -> out [F][H/2][W/2][C]; H, W even,
+ * C % 4 == 0, 16-byte aligned. */
+int acx_avgpool2_nhwc(acx_ctx* ctx, const float* in, float* out, int32_t F, int32_t H, int32_t W, int32_t C, void* stream);
+/* acx_attnpool_tokens: AttentionPool2d's tokens (clip/model.py:82-84): x [F * HW][E] -> tokens [F * (HW + 1)][E], token 0 = the
+ * mean over the HW tokens (f64 sum in token order), every token + positional_embedding[t]. */
+int acx_attnpool_tokens(acx_ctx* ctx, const float* x, const float* pos, float* tokens, int32_t F, int32_t HW, int32_t E, void* stream);
+
+/* One convolution with its eval BatchNorm folded in: w' = w * gamma / sqrt(running_var + eps), b' = beta - running_mean * gamma /
+ * sqrt(running_var + eps) (folded in f64, stored f32).  1x1: w [Cout_p][Cin_p]; 3x3: w [Cout_p][tap = ky * 3 + kx][Cin_p]; the
+ * stem's first conv: [Cout_p][32] over acx_resnet_stem_im2col's columns.  b [Cout_p]. */
+typedef struct acx_resnet_conv {
+  const float* w;
+  const float* b;
+} acx_resnet_conv;
+typedef struct acx_resnet_block {           /* Bottleneck (clip/model.py:10-68) */
+  acx_resnet_conv conv1, conv2, conv3;
+  acx_resnet_conv downsample;               /* w == NULL: no downsample (identity) */
+} acx_resnet_block;
+typedef struct acx_resnet_weights {
+  acx_resnet_conv stem[3];                  /* conv1/bn1, conv2/bn2, conv3/bn3 */
+  const acx_resnet_block* blocks;           /* layers[0] + ... + layers[3] blocks, layer after layer (host array) */
+  const float* positional_embedding;        /* [HW + 1, E] (AttentionPool2d, E = 32 width) */
+  const float *q_w, *q_b;                   /* q_proj [E, E], [E] */
+  const float *kv_w, *kv_b;                 /* k_proj | v_proj stacked: [2E, E], [2E] */
+  const float *c_w, *c_b;                   /* c_proj [output_dim, E], [output_dim] */
+} acx_resnet_weights;
+typedef struct acx_resnet_desc {
+  int32_t resolution, width;
+  int32_t layers[4];
+  int32_t heads, output_dim;                /* heads = width * 32 / 64 (clip/model.py:314) */
+  int32_t prec;                             /* ACX_PREC_F32 or ACX_PREC_F32X6: both run the f32 MFMA kernels */
+} acx_resnet_desc;
+/* acx_resnet_encode: ModifiedResNet.forward in eval mode (clip/model.py:156-171): frames [F,3,R,R] f32 -> features
+ * [F, output_dim] f32.  The frames run in internal batches whose largest activation stays below 2^31 bytes; workspace from
+ * acx_resnet_workspace_bytes(desc, F) (0: the geometry is not supported).  R % 32 == 0, heads * 64 == 32 * width. */
+size_t acx_resnet_workspace_bytes(const acx_resnet_desc* d, int32_t frames);
+int acx_resnet_encode(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const float* frames, int32_t nframes,
+                      float* features, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Training mode (BatchNorm2d.train(): Lightning's model.train() reaches the frozen encoder, anomaly_clip_module.py:68-69,160-166):
+ * every BatchNorm normalises with the batch statistics over ALL frames, H and W of the call (biased variance), updates running_mean /
+ * running_var with `momentum` (unbiased variance, torch.nn.functional.batch_norm) and increments num_batches_tracked. */
+typedef struct acx_resnet_bn {              /* one nn.BatchNorm2d: device pointers to its parameters and buffers ([C]) */
+  const float *weight, *bias;
+  float *running_mean, *running_var;
+  int64_t* num_batches_tracked;             /* may be NULL */
+} acx_resnet_bn;
+typedef struct acx_resnet_block_bn {
+  acx_resnet_bn bn1, bn2, bn3, downsample;  /* downsample: unused without downsample weights */
+} acx_resnet_block_bn;
+typedef struct acx_resnet_train_bn {
+  acx_resnet_bn stem[3];
+  const acx_resnet_block_bn* blocks;        /* host array, as acx_resnet_weights.blocks */
+  float eps, momentum;                      /* 1e-5, 0.1 (nn.BatchNorm2d's defaults, clip/model.py:18-28) */
+} acx_resnet_train_bn;
+/* acx_bn_apply_nhwc: y = x * alpha + shift (+ residual), then ReLU when relu != 0, over rows of Cp channels (in place allowed), with
+ * alpha = gamma / sqrt(var_biased + eps), shift = beta - mean * alpha for the C real channels and 0 for the padding ones
+ * (BatchNorm2d in training mode, clip/model.py:56-64,157-160).  scratch: 2 * Cp floats, 16-byte aligned. */
+int acx_bn_apply_nhwc(acx_ctx* ctx, const float* x, const float* mean, const float* var_biased, const float* gamma, const float* beta,
+                      const float* residual, float* y, int64_t rows, int32_t C, int32_t Cp, float eps, int32_t relu, float* scratch,
+                      void* stream);
+/* acx_resnet_encode_train: ModifiedResNet.forward with its BatchNorms in training mode (clip/model.py:156-171), layer by layer over
+ * all F frames of the call (acx_bn_stats over each convolution's F * H * W rows).  w: the UNFOLDED convolution weights in the layouts
+ * of acx_resnet_conv (the b fields are not read) and the attention pool; bn: every BatchNorm's parameters and buffers, which are
+ * updated in place.  Workspace from acx_resnet_train_workspace_bytes(desc, F): every activation of all F frames. */
+size_t acx_resnet_train_workspace_bytes(const acx_resnet_desc* d, int32_t frames);
+int acx_resnet_encode_train(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const acx_resnet_train_bn* bn,
+                            const float* frames, int32_t F, float* features, void* workspace, size_t workspace_bytes, void* stream);
+
 /* acx_transformer_forward: Transformer.forward (clip/model.py:220-230) in place on x
  * [batch*L, W] f32 -- used by the text encoder (text_encoder.py:16-18). */
 size_t acx_transformer_workspace_bytes(int32_t width, int32_t rows);
@@ -299,12 +380,13 @@ int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, in
 int acx_text_directions(acx_ctx* ctx, const float* text, const float* ncentroid, float* dirs,
                         int32_t C, int32_t D, int32_t normal_id, void* stream);
 /* acx_selector_project: raw[r, c] = (x[r,:] - ncentroid) . dirs[c,:]  (selector_model.py:54,62).
- * x [rows, D] (D in {64,128,256,512,768,1024}), raw [rows, C1], C1 <= 64. */
+ * x [rows, D] (D in {64,128,256,512,640,768,1024}), raw [rows, C1], C1 <= 64. */
 int acx_selector_project(acx_ctx* ctx, const float* x, const float* ncentroid, const float* dirs,
                          float* raw, int64_t rows, int32_t D, int32_t C1, void* stream);
 /* acx_bn_stats: deterministic per-column batch statistics of raw[rows, C1] (training BatchNorm1d,
  * selector_model.py:30,65: biased variance normalises, unbiased variance feeds running_var).  Two
- * stages (row slabs -> f64 partials in `workspace` -> fixed-order sum); C1 <= 64;
+ * stages (row slabs -> f64 partials in `workspace` -> fixed-order sum); C1 <= 64 -- or, with its own kernels, up to 65536 columns
+ * (the ResNet encoders' training-mode BatchNorm2d, clip/model.py:18-28: one lane per column of a row slab, slabs added in order);
  * workspace >= acx_bn_workspace_bytes(rows, C1), 8-byte aligned. */
 size_t acx_bn_workspace_bytes(int64_t rows, int32_t C1);
 /* SyncBN (configs/trainer/ddp.yaml sync_batchnorm): combine the ranks' statistics.  gathered[ranks][2 * C1 + 1] holds, per rank,
@@ -593,7 +675,8 @@ int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, const void* 
 /* SyncBatchNorm payload of a rank (configs/trainer/ddp.yaml:9): out[2 C1 + 1] = [mean | biased var * rows | rows] */
 int acx_bn_pack(acx_ctx* ctx, const float* mean, const float* var_biased, int64_t rows, int32_t C1, float* out,
                 void* stream);
-/* nn.BatchNorm1d running statistics (selector_model.py:30,65): r = one_minus * r + momentum * batch; counter += 1 */
+/* nn.BatchNorm1d running statistics (selector_model.py:30,65; and BatchNorm2d, clip/model.py:18-28): r = one_minus * r + momentum *
+ * batch; counter += 1.  C1 <= 65536 */
 int acx_bn_running_update(acx_ctx* ctx, const float* mean, const float* var_unbiased, float* running_mean,
                           float* running_var, int64_t* num_batches_tracked, int32_t C1, float momentum, float one_minus,
                           void* stream);
