@@ -28,10 +28,24 @@
 //     splitk_reduce_kernel's;
 //   * CONV: implicit-GEMM 3x3 convolution over the (gn, gl) token grid (power-of-two grid, cin % 32 == 0): the DMA source
 //     of an A row is the row shifted by the K-step's tap, or the caller's zero page outside the grid.
+//   * MFMA SHAPE (ACX_X6_MFMA16, default 1; NT products -- not TN / PLAIN / X3): the half-steps run on
+//     v_mfma_f32_16x16x32_bf16, ONE instruction per (16-row block, 16-column block, product) and 32-wide K-step: 192 per wave and
+//     half-step, the same 3,072 MFMA cycles, the same 32 ds_read_b128 (X: 8 A.hi + 24 W fragments, Y: 8 A.mid + 8 A.lo + 16 W).
+//     The chip holds a higher clock on this shape under the kernel's load (profiles/x6_mfma_shape_gate.txt: 1.15 x the FLOP/s of
+//     the 32x32x16 loop with every fragment re-read from LDS).  A fragment is 16 rows x 32 k: lane l reads row l & 15, 16-byte
+//     chunk l >> 4 of the unit's 64-byte rows; the units of this path are swizzled chunk ^ ((row >> 1) & 3) (the 32-row map is
+//     2-way bank-conflicted for this read).  Registers: 256 accumulators (8 x 2 NI of 16 x 16) + A fragments resident per
+//     half-step (8 / 16) + two groups of W fragments (6 each) = 144 fragment registers; the schedule is described at the
+//     half-steps.  Per accumulator the products arrive in the same order as on 32x32x16; only the order of the additions INSIDE
+//     a 32-wide K-step differs (one 32-term MFMA instead of two 16-term ones), so results move in the last bits.  With 0 the
+//     description above (96 MFMAs of 32x32x16, two fragment sets of 16) is the whole kernel: the A/B arm.
 // Accumulation order differs from the p8 kernel's (all six products of a k range before the next range, smallest cross
 // terms first inside a range); the result is an f32 dot product's either way (tests hold both to the same bounds).
 #ifndef ACX_X6_ABL
 #define ACX_X6_ABL 0     // timing ablations (wrong results), bit mask: 1 no DMA in the K loop, 2 no vmcnt waits, 4 no epilogue stores, 8 every ds_read from one address
+#endif
+#ifndef ACX_X6_MFMA16
+#define ACX_X6_MFMA16 1  // the NT plane-reuse path (TN = PLAIN = X3 = 0) on v_mfma_f32_16x16x32_bf16; 0: on v_mfma_f32_32x32x16_bf16 (the A/B arm)
 #endif
 constexpr int X6_UNIT_B = 256 * 64;              // one plane tile: 256 rows x 32 bf16
 constexpr int X6_LDS_B = 8 * X6_UNIT_B + 4 * 4096;
@@ -101,6 +115,11 @@ __device__ __forceinline__ f32x16 x6_mfma(const bf16x8 a, const bf16x8 b, const 
 // fragment / MFMA pattern (its "A.mid" is A.hi, its "A.lo" is A.mid), all four units (A.hi, A.mid, W.hi, W.mid) double-buffered by
 // K-step parity in the eight slots (A.hi: AH / AM, A.mid: WL / AL) and restaged a K-step ahead: 96 MFMAs per wave and K-step behind
 // one barrier, 16 LDS-DMA instructions between them.  The lo planes are never read.
+template <bool FIRST, class T>
+__device__ __forceinline__ T& x6_sel(T& a, T& b) {
+  if constexpr (FIRST) return a; else return b;
+}
+
 template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0>
 __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   static_assert(X3 == 0 || (CONV == 0 && TN == 0 && PLAIN == 0 && W14 == 0), "three-product mode: identity rows, NT");
@@ -110,6 +129,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = W14 ? 0 : wave >> 1, wn = W14 ? wave : wave & 1;
   const int li = lane & 31, hh = lane >> 5;
+  constexpr bool S16 = ACX_X6_MFMA16 != 0 && TN == 0 && PLAIN == 0 && X3 == 0;   // 16 x 16 x 32 MFMAs (see "half-steps on 16x16x32" below)
   static_assert(NI == 4 || ((NI == 2 || NI == 1) && PLAIN == 0), "narrow tiles: not for the PLAIN schedule");
   static_assert(W14 == 0 || (TN != 0 && NI == 2), "1 x 4 wave grid: TN products, 128 x 256 tiles");
   constexpr int TH = W14 ? 128 : 256, TW = W14 ? 128 * NI : 64 * NI;      // tile height / width
@@ -130,7 +150,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   // lane -> row (lane >> 2) of the instruction's 16, LDS chunk position lane & 3 = global chunk ^ ((row >> 2) & 3)
   const int dr = 64 * wave + (lane >> 2);                        // + 16 i: this lane's unit row of instruction i
   const int dwr = 16 * NI * wave + (lane >> 2);                  // the same for a W unit (64 NI rows: NI instructions per wave)
-  const int dc = ((lane & 3) ^ ((lane >> 4) & 3)) * 16;          // byte offset of its 16-byte piece inside the row's 64 B
+  // (S16: global chunk ^ ((row >> 1) & 3) -- the 16-row fragment read of that path is 2-way bank-conflicted under the other map)
+  const int dc = ((lane & 3) ^ (S16 ? (lane >> 3) & 3 : (lane >> 4) & 3)) * 16;   // byte offset of its 16-byte piece inside the row's 64 B
   const char* zsrc = (CONV || TN) ? (const char*)g.zeros + (lane & 3) * 16 : nullptr;
   const int sh_gl = CONV ? __builtin_ctz((unsigned)d.gl) : 0;
   const int steps_per_tap = (CONV && !TN) ? d.cin / 32 : 1;
@@ -281,6 +302,10 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   const int fa0 = (wm * 128 + li) * 64 + ((0 + hh) ^ sw) * 16, fa1 = (wm * 128 + li) * 64 + ((2 + hh) ^ sw) * 16;
   const int fw0 = (wn * 32 * NI + li) * 64 + ((0 + hh) ^ sw) * 16, fw1 = (wn * 32 * NI + li) * 64 + ((2 + hh) ^ sw) * 16;
 
+  // S16: a fragment is 16 rows x 32 k -- lane l reads row l & 15, chunk l >> 4 at position chunk ^ ((row >> 1) & 3); + 1024 per 16-row block
+  const int sw16 = (lane >> 1) & 3;
+  const int fa16 = (wm * 128 + (lane & 15)) * 64 + ((lane >> 4) ^ sw16) * 16, fw16 = (wn * 32 * NI + (lane & 15)) * 64 + ((lane >> 4) ^ sw16) * 16;
+
   // TN: transpose-read addresses of row block / column block blk, k half r (see x6_tr_frag); + 8192 for substep 1
   int trA[4][2], trW[4][2];
 #pragma unroll
@@ -300,6 +325,19 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
     for (int jj = 0; jj < NI; ++jj)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
+  // S16: 8 x 2 NI accumulators of 16 x 16 (the same 64 NI registers); acc16[i][j] = rows 16 i .., columns 16 j .. of the wave's block
+  f32x4 acc16[8][2 * NI];
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+#pragma unroll
+    for (int jj = 0; jj < 2 * NI; ++jj) acc16[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // S16 fragments: AX = A.hi row blocks (X), AY = A.mid [0..7] and A.lo [8..15] row blocks (Y), WA / WB = two groups of W fragments
+  // (two column blocks x the half-step's planes).  What an item's first block multiplies is ZERO (as F1 below).
+  bf16x8 AX[8], AY[16], WA[6], WB[6];
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { AY[q][e] = (__bf16)0.f; if (q < 8) AX[q][e] = (__bf16)0.f; if (q < 6) { WA[q][e] = (__bf16)0.f; WB[q][e] = (__bf16)0.f; } }
   // fragment sets: [0..3] A.hi (X) / A.mid (Y) row blocks, [4..7] W.hi, [8..11] W.mid column blocks, [12..15] W.lo column
   // blocks (X) / A.lo row blocks (Y)
   bf16x8 F0[16], F1[16];
@@ -457,6 +495,128 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
         X6_ADVANCE(c1, ra1, rw1, vm1);
         continue;
       }
+      if constexpr (S16) {
+        // ======================================================================= half-steps on 16x16x32 (ACX_X6_MFMA16)
+        // A 32-wide K-step is ONE v_mfma_f32_16x16x32_bf16 per (16-row block, 16-column block, product): 192 MFMAs per wave and
+        // half-step (the 3,072 MFMA cycles of the 96 32x32x16), fed by the same 32 ds_read_b128 -- X: 8 A.hi + 24 W fragments, Y: 8 A.mid +
+        // 8 A.lo + 16 W.  The A fragments of a half-step stay resident; the W fragments come in NI GROUPS of two column blocks (X: W.lo,
+        // W.mid, W.hi = 6 fragments, Y: W.hi, W.mid = 4) into two buffers.  A BLOCK is the 48 MFMAs of one group (product-major: every
+        // accumulator of the group sees lo, mid, hi / (lo,hi), (mid,mid), (mid,hi) in the order of the 32x32x16 path, 16 MFMAs apart)
+        // with the NEXT group's reads between its MFMAs; a half-step's LAST group runs after the barrier, beside the next half-step's A reads
+        // and first group reads; the half-step's 12 DMA instructions follow (never more than one read or DMA in a gap).  Registers: 256 accumulators + 144 of
+        // fragments.  The MFMA is inline asm with the accumulator as an in-out AGPR operand: hipcc does not tie the destination of
+        // this 4-register MFMA to its SrcC and then shuffles accumulators through v_accvgpr moves.
+#define X6_MFMA16(ACC, WF, AF) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(ACC) : "v"(WF), "v"(AF))
+#define X6_MM16_X(WBUF, g, q)                                                                      \
+  do {                                                                                             \
+    constexpr int p_ = (q) / 16, mi_ = ((q) % 16) / 2, nj_ = (q) % 2;                              \
+    X6_MFMA16(acc16[mi_][2 * (g) + nj_], WBUF[2 * p_ + nj_], AX[mi_]);                             \
+  } while (0)
+#define X6_MM16_Y(WBUF, g, q)                                                                      \
+  do {                                                                                             \
+    constexpr int p_ = (q) / 16, mi_ = ((q) % 16) / 2, nj_ = (q) % 2;                              \
+    X6_MFMA16(acc16[mi_][2 * (g) + nj_], WBUF[(p_ == 1 ? 2 : 0) + nj_], AY[(p_ == 0 ? 8 : 0) + mi_]); \
+  } while (0)
+        // fragment f of W group g: X f = 0, 1 W.lo, 2, 3 W.mid, 4, 5 W.hi; Y f = 0, 1 W.hi, 2, 3 W.mid (column blocks 2 g, 2 g + 1)
+#define X6_RDW16_X(WBUF, g, f)                                                                     \
+  WBUF[f] = X6_FRAG(((f) < 2 ? X6_WL * X6_UNIT_B : (f) < 4 ? wpar + X6_WM0 * X6_UNIT_B : wpar + X6_WH0 * X6_UNIT_B) + fw16 + (2 * (g) + ((f) & 1)) * 1024)
+#define X6_RDW16_Y(WBUF, g, f)                                                                     \
+  WBUF[f] = X6_FRAG(((f) < 2 ? wpar + X6_WH0 * X6_UNIT_B : wpar + X6_WM0 * X6_UNIT_B) + fw16 + (2 * (g) + ((f) & 1)) * 1024)
+        // the W buffers: group g of a half-step goes to WA (g even) / WB (g odd); one group per half-step (NI = 1): X in WA, Y in WB
+#define X6_WX_LAST x6_sel<(NI == 1)>(WA, WB)
+#define X6_WY_FIRST x6_sel<(NI == 1)>(WB, WA)
+        // ----------------------------------------------------------------------- half-step X
+        if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        X6_FENCE();
+        __builtin_amdgcn_s_barrier();
+        X6_FENCE();
+        // first block: the previous Y half-step's last group (zero fragments at an item's first K-step: no branch around the
+        // accumulators) + the A.hi reads, the first W group's reads and the half-step's 12 DMA instructions
+        // (reads in the EVEN gaps only: one ds_read_b128 per 16-cycle gap from each of the CU's four waves is the LDS array's whole
+        // 256 B/clk.  The DMA instructions: whole tiles issue them in the second block, one every third gap; strips -- whose half-step
+        // is one or two blocks long -- in the odd gaps of the first)
+#define X6_DMA16_X(idx)                                                                            \
+  do {                                                                                             \
+    constexpr int u_ = ((idx) / 4) & 3, i_ = (idx) & 3;                                            \
+    if (u_ == 0) X6_DMA_A(c0, ra0, vm0, 1, X6_AM, i_);                                             \
+    else if (u_ == 1) X6_DMA_A(c0, ra0, vm0, 2, X6_AL, i_);                                        \
+    else X6_DMA_W(c1, rw1, 0, slot_wh_next, i_);                                                   \
+  } while (0)
+#define X6_DMA16_Y(idx)                                                                            \
+  do {                                                                                             \
+    constexpr int u_ = ((idx) / 4) & 3, i_ = (idx) & 3;                                            \
+    if (u_ == 0) X6_DMA_W(c1, rw1, 1, slot_wm_next, i_);                                           \
+    else if (u_ == 1) X6_DMA_A(c1, ra1, vm1, 0, X6_AH, i_);                                        \
+    else X6_DMA_W(c1, rw1, 2, X6_WL, i_);                                                          \
+  } while (0)
+#define X6_H0_X(q)                                                                                 \
+  do {                                                                                             \
+    if constexpr ((q) % 2 == 0 && (q) / 2 < 8) AX[((q) / 2) & 7] = X6_FRAG(X6_AH * X6_UNIT_B + fa16 + (((q) / 2) & 7) * 1024); \
+    else if constexpr ((q) % 2 == 0 && (q) / 2 < 14) X6_RDW16_X(WA, 0, ((q) / 2 + 16) % 6);        \
+    if constexpr (NI < 4 && (q) % 2 == 1 && (q) < 24) X6_DMA16_X((q) / 2);                         \
+    X6_MM16_Y(WB, NI - 1, (q));                                                                    \
+    X6_FENCE();                                                                                    \
+  } while (0);
+        X6_REP48(X6_H0_X)
+#undef X6_H0_X
+#define X6_HB(q, RDW, MM, WNEW, gn, WCUR, gc, NF, DMA)                                             \
+  do {                                                                                             \
+    if constexpr ((q) % 2 == 0 && (q) / 2 < NF) RDW(WNEW, gn, ((q) / 2) % NF);                     \
+    if constexpr (NI == 4 && (gn) == 1 && (q) >= 12 && ((q) - 12) % 3 == 0) DMA((((q) - 12) / 3) % 12); \
+    MM(WCUR, gc, (q));                                                                             \
+    X6_FENCE();                                                                                    \
+  } while (0);
+        if constexpr (NI >= 2) {
+#define X6_H1(q) X6_HB(q, X6_RDW16_X, X6_MM16_X, WB, 1, WA, 0, 6, X6_DMA16_X)
+          X6_REP48(X6_H1)
+#undef X6_H1
+        }
+        if constexpr (NI == 4) {
+#define X6_H2(q) X6_HB(q, X6_RDW16_X, X6_MM16_X, WA, 2, WB, 1, 6, X6_DMA16_X)
+#define X6_H3(q) X6_HB(q, X6_RDW16_X, X6_MM16_X, WB, 3, WA, 2, 6, X6_DMA16_X)
+          X6_REP48(X6_H2)
+          X6_REP48(X6_H3)
+#undef X6_H3
+#undef X6_H2
+        }
+        // ----------------------------------------------------------------------- half-step Y
+        if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(NI) : "memory");     // A.mid, A.lo landed (W.hi of the next K-step -- NI instructions -- may be in flight)
+        X6_FENCE();
+        __builtin_amdgcn_s_barrier();
+        X6_FENCE();
+#define X6_H0_Y(q)                                                                                 \
+  do {                                                                                             \
+    if constexpr ((q) % 2 == 0 && (q) / 2 < 16) AY[((q) / 2) & 15] = X6_FRAG(((q) / 2 < 8 ? X6_AM : X6_AL) * X6_UNIT_B + fa16 + (((q) / 2) & 7) * 1024); \
+    else if constexpr ((q) % 2 == 0 && (q) / 2 < 20) X6_RDW16_Y(X6_WY_FIRST, 0, ((q) / 2) % 4);    \
+    if constexpr (NI < 4 && (q) % 2 == 1 && (q) < 24) X6_DMA16_Y((q) / 2);                         \
+    X6_MM16_X(X6_WX_LAST, NI - 1, (q));                                                            \
+    X6_FENCE();                                                                                    \
+  } while (0);
+        X6_REP48(X6_H0_Y)
+#undef X6_H0_Y
+        if constexpr (NI >= 2) {
+#define X6_H1(q) X6_HB(q, X6_RDW16_Y, X6_MM16_Y, WB, 1, WA, 0, 4, X6_DMA16_Y)
+          X6_REP48(X6_H1)
+#undef X6_H1
+        }
+        if constexpr (NI == 4) {
+#define X6_H2(q) X6_HB(q, X6_RDW16_Y, X6_MM16_Y, WA, 2, WB, 1, 4, X6_DMA16_Y)
+#define X6_H3(q) X6_HB(q, X6_RDW16_Y, X6_MM16_Y, WB, 3, WA, 2, 4, X6_DMA16_Y)
+          X6_REP48(X6_H2)
+          X6_REP48(X6_H3)
+#undef X6_H3
+#undef X6_H2
+        }
+#undef X6_HB
+#undef X6_DMA16_Y
+#undef X6_DMA16_X
+        wpar = wnext;
+        c0 = c1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { ra0[i] = ra1[i]; rw0[i] = rw1[i]; vm0[i] = vm1[i]; }
+        X6_ADVANCE(c1, ra1, rw1, vm1);
+        continue;
+      }
       // =========================================================================== half-step X
       if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       X6_FENCE();
@@ -527,6 +687,11 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
 #define X6_DRAINP(q) X6_MM_P(F1, (q));
       X6_REP16(X6_DRAINP)
 #undef X6_DRAINP
+    } else if constexpr (S16) {
+#define X6_DRAIN(q) X6_MM16_Y(WB, NI - 1, (q));
+      X6_REP48(X6_DRAIN)
+#undef X6_DRAIN
+      asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // (inline-asm MFMAs: the last results, before the epilogue reads them)
     } else {
 #define X6_DRAIN(q) X6_MM_Y(F1, (q));
     X6_REP48(X6_DRAIN)
@@ -589,6 +754,13 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
     constexpr int ni = (bi) >> 2, mi = (bi) & 3;                                                   \
     const int col = colw + 32 * ni;                                                                \
     const float4 b4 = bia[ni];                                                                     \
+    if constexpr (S16) {   /* four 16 x 16 accumulators (C^T layout): row 16 rb + (lane & 15), columns 16 cb + 4 (lane >> 4) .. +3 = chunk 4 cb + (lane >> 4) */ \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                              \
+        const int rw_ = 16 * (k >> 1) + (lane & 15);                                               \
+        const f32x4 a_ = acc16[2 * mi + (k >> 1)][2 * ni + (k & 1)];                               \
+        *reinterpret_cast<float4*>(scr + rw_ * 128 + (((4 * (k & 1) + (lane >> 4)) ^ (rw_ & 7)) * 16)) = make_float4(a_[0], a_[1], a_[2], a_[3]); \
+      }                                                                                            \
+    } else                                                                                         \
     _Pragma("unroll") for (int k = 0; k < 4; ++k)   /* accumulator (C^T layout): row li, columns 8k + 4hh .. +3 = chunk 2k + hh */ \
       *reinterpret_cast<float4*>(scr + li * 128 + (((2 * k + hh) ^ (li & 7)) * 16)) =             \
           make_float4(acc[mi][ni][4 * k], acc[mi][ni][4 * k + 1], acc[mi][ni][4 * k + 2], acc[mi][ni][4 * k + 3]); \
@@ -659,6 +831,9 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
         }                                                                                          \
       }                                                                                            \
     }                                                                                              \
+    if constexpr (S16) {                                                                           \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) acc16[2 * mi + (k >> 1)][2 * ni + (k & 1)] = f32x4{0.f, 0.f, 0.f, 0.f}; \
+    } else                                                                                         \
     _Pragma("unroll") for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;                          \
   } while (0)
       float4 R0[4], R1[4];
@@ -702,7 +877,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
 #pragma unroll
     for (int q = 0; q < 16; ++q)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) F1[q][e] = (__bf16)0.f;
+      for (int e = 0; e < 8; ++e) { F1[q][e] = (__bf16)0.f; AY[q][e] = (__bf16)0.f; if (q < 6) WB[q][e] = (__bf16)0.f; }
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // no DMA may still be writing this workgroup's LDS at exit
 #undef X6_REP48
@@ -711,6 +886,13 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
 #undef X6_RD_P
 #undef X6_DMA_W_K
 #undef X6_DMA_A_K
+#undef X6_WY_FIRST
+#undef X6_WX_LAST
+#undef X6_RDW16_Y
+#undef X6_RDW16_X
+#undef X6_MM16_Y
+#undef X6_MM16_X
+#undef X6_MFMA16
 #undef X6_FENCE
 #undef X6_MM_Y
 #undef X6_MM_X

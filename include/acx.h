@@ -771,6 +771,11 @@ int acx_prof_gemm_tn(acx_ctx* ctx, double* flops, double* total_ms, int32_t* lau
  * Measured roofline denominators (bench.py `peaks_measured`).  Not on the product path.
  * acx_probe_mfma: register-only MFMA loop on every SIMD (bf16 = 0: v_mfma_f32_32x32x2_f32, 1: v_mfma_f32_32x32x16_bf16),
  *   `iters` x 4 MFMAs per wave, waves_per_simd waves per SIMD; *flops_out (host) = flops the launch executes.
+ *   bf16 = 2: mode 1 on RANDOM operands (four fragment pairs per lane); bf16 = 3: the same on v_mfma_f32_16x16x32_bf16 (sixteen
+ *   16 x 16 accumulators = the same 64 registers, `iters` x 16 MFMAs per wave); bf16 = 4 (32x32x16) / 5 (16x16x32): one wave per SIMD
+ *   (waves_per_simd must be 1), 128 x 128 outputs per wave, an iteration = one 32-wide K-step of three products whose operand
+ *   fragments are all re-read from random bf16 data in LDS by ds_read_b128 (32 reads per wave: the plane-reuse kernel's half-step
+ *   without DMA and barriers).
  * acx_probe_copy: dst = src, 16 bytes per lane, grid-stride: the HBM stream (read + write) ceiling. */
 int acx_probe_mfma(acx_ctx* ctx, int32_t bf16, int32_t iters, int32_t waves_per_simd, float* sink, double* flops_out,
                    void* stream);
