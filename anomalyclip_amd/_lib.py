@@ -17,7 +17,7 @@ ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
 OPT_RING_MIN_TILES, OPT_SK_MAX_M, OPT_TN_P256_MIN_ROWS, OPT_X6_CUS, OPT_X6_TAIL_SPLIT = 1, 2, 3, 4, 5
-OPT_X6_STRIP_TAIL, OPT_X6_MIN_TILES = 6, 7
+OPT_X6_STRIP_TAIL, OPT_X6_MIN_TILES, OPT_LN_RIDER = 6, 7, 8
 ACX_F64, ACX_I64 = 16, 17                              # element types of the collectives only (acx_allreduce / acx_allgather)
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 COMM_ID_BYTES = 128
@@ -42,6 +42,10 @@ class GemmDesc(C.Structure):
         ("pairs", c_int32), ("panels", c_int32), ("a_plane_stride", c_int64), ("w_plane_stride", c_int64),
         ("c_plane_rows", c_int64), ("out_scale", c_float),
     ]
+
+
+class LnJob(C.Structure):      # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("y", c_void_p), ("y_dtype", c_int32), ("eps", c_float), ("mode", c_int32)]
 
 
 class BlockWeights(C.Structure):
@@ -118,6 +122,8 @@ _SIGS = {
     "acx_last_error": (C.c_char_p, [c_void_p]),
     "acx_set_option": (C.c_int, [c_void_p, c_int32, c_int64]),
     "acx_gemm": (C.c_int, [c_void_p, C.POINTER(GemmDesc), c_void_p]),
+    "acx_gemm_ln": (C.c_int, [c_void_p, C.POINTER(GemmDesc), C.POINTER(LnJob), c_void_p]),
+    "acx_gemm_ln_plan": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, C.c_double, C.POINTER(c_int64)]),
     "acx_layernorm": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int64, c_int32, c_float, c_int32, c_void_p]),
     "acx_attention": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
@@ -308,6 +314,13 @@ def lib() -> C.CDLL:
                 try:
                     fn = getattr(L, name)
                 except AttributeError as e:
+                    if os.environ.get("ACX_LIB_PATH"):
+                        # an A/B library built from another commit (tools/ab_x6.sh) may lack an entry point this tree declares:
+                        # calling it is the error, loading the library is not
+                        def _missing(*_a, _name=name, _path=path):
+                            raise AcxError(f"{_path} (ACX_LIB_PATH) does not export {_name}")
+                        setattr(L, name, _missing)
+                        continue
                     raise AcxError(f"libacx.so does not export {name}") from e
                 fn.restype = res
                 fn.argtypes = args

@@ -42,6 +42,7 @@ extern "C" int acx_create(acx_ctx** out, int device) {
   c->opt_x6_cus = 0;
   c->opt_x6_tail = 0;
   c->opt_x6_strip = 1;
+  c->opt_ln_rider = 1;
   c->comm = nullptr; c->comm_rank = 0; c->comm_world = 0;
   c->opt_x6_min_tiles = 18;
   c->err[0] = 0;
@@ -123,6 +124,10 @@ extern "C" int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value) {
       if (value < 0 || value > 3) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: x6_strip_tail is 0 (off), 1 (cost model), 2 or 3 (forced strip width)%s");
       ctx->opt_x6_strip = (int)value;
       return ACX_OK;
+    case ACX_OPT_LN_RIDER:
+      if (value < 0) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: ln_rider is 0 (off), 1 (cost model) or a row count%s");
+      ctx->opt_ln_rider = (long long)value;
+      return ACX_OK;
     case ACX_OPT_X6_MIN_TILES:
       if (value < 1) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: x6_min_tiles must be >= 1%s");
       ctx->opt_x6_min_tiles = (int)(value > 0x7fffffff ? 0x7fffffff : value);
@@ -196,7 +201,7 @@ bool x6_takes(acx_ctx* ctx, const TfWs& ws, int64_t M, int N, int K, int lda) {
 // kernel is then ONE contiguous 16 KB block (+5-6 % on the ViT products against row-major planes, profiles/r05_gemm_x6_notes.txt).
 int linear_x6(acx_ctx* ctx, const void* A3, int lda, int64_t a_rows, const void* W3, int64_t w_plane_bytes, int ldw, void* C,
               int ldc, int M, int N, int K, const float* bias, int act, const float* residual, hipStream_t s, int ldr = 0,
-              int c_dtype = ACX_F32, void* tail_ws = nullptr, size_t tail_bytes = 0) {
+              int c_dtype = ACX_F32, void* tail_ws = nullptr, size_t tail_bytes = 0, const acx_ln_job* ln = nullptr) {
   if (!W3) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
   acx_gemm_desc d;
   memset(&d, 0, sizeof(d));
@@ -209,7 +214,8 @@ int linear_x6(acx_ctx* ctx, const void* A3, int lda, int64_t a_rows, const void*
   d.panels = 3;
   // scratch for the K split of a partly filled last round of tiles (acx_gemm: row-major outputs only)
   d.workspace = tail_ws; d.workspace_bytes = tail_ws ? tail_bytes : 0;
-  return acx_gemm(ctx, &d, s);
+  // ln: the LayerNorm of the output rows follows (acx_gemm_ln: part of it rides in the product's last round)
+  return ln ? acx_gemm_ln(ctx, &d, ln, s) : acx_gemm(ctx, &d, s);
 }
 
 int linear1(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const float* Wf, const void* Wb, int ldw,
@@ -282,6 +288,10 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
   const int hdt = prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
   const size_t esz = prec == ACX_PREC_BF16 ? 2 : 4;
   int rc;
+  // ACX_PREC_F32X6: the LayerNorm behind a residual product (out-proj -> ln_2, c_proj -> the next layer's ln_1, K | V LayerNorm of the
+  // pruned last layer included) is handed to the product (acx_gemm_ln: the idle workgroups of its last round of tiles run part of it)
+  const bool ln_ride = pdt3 == ACX_BF16X3P;
+  bool ln1_done = false;                         // this layer's ln_1 planes were written behind the previous layer's c_proj
   for (int l = 0; l < layers; ++l) {
     const acx_block_weights& b = blk[l];
     if (cls_ws && l == layers - 1) {
@@ -295,7 +305,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
       if (kv_x6) {
         // LayerNorm writes the product's three planes itself (all rows) and the f32 rows of the CLS tokens (Q below reads only those)
         if (!b.in_proj_w_bf16) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
-        if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+        if (!ln1_done && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
         if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
         if ((rc = linear_x6(ctx, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
                             (float*)ws.qkv + W, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
@@ -324,8 +334,11 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     // the QuickGELU epilogue of c_fc -- only the attention output goes through acx_split_bf16x3)
     const bool x6_qkv = x6mode && x6_takes(ctx, ws, rows, 3 * W, W, W), x6_out = x6mode && x6_takes(ctx, ws, rows, W, W, W);
     const bool x6_fc = x6mode && x6_takes(ctx, ws, rows, 4 * W, W, W), x6_proj = x6mode && x6_takes(ctx, ws, rows, W, 4 * W, 4 * W);
+    bool ln2_done = false;
+    const bool ln1_had = ln1_done;
+    ln1_done = false;
     if (x6_qkv) {
-      if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+      if (!ln1_had && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
     } else
     if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
     // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
@@ -356,14 +369,16 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     if (x6_out) {
       if (!att_x3 && !att_p3 && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.att, W, ws.hp, (int64_t)rows * W * 2, rows, W, s))) return rc;
       // (ws.h is free here and at c_proj: LayerNorm's output has been consumed, or went to the planes)
+      const acx_ln_job ln2 = {b.ln2_w, b.ln2_b, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
+      ln2_done = ln_ride && x6_fc;
       if ((rc = linear_x6(ctx, ws.hp, W, rows, b.out_proj_w_bf16, (int64_t)W * W * 2, W, x, W, (int)rows, W, W, b.out_proj_b,
-                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4))) return rc;
+                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln2_done ? &ln2 : nullptr))) return rc;
     } else
     if ((rc = linear(ctx, prec, ws.att, qdt, W, b.out_proj_w, b.out_proj_w_bf16, W, x, ACX_F32, W, (int)rows, W, W,
                      b.out_proj_b, ACX_ACT_NONE, x, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
     // x = x + mlp(ln_2(x))                                           clip/model.py:216
     if (x6_fc) {
-      if ((rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+      if (!ln2_done && (rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
     } else
     if ((rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
     if (x6_fc) {
@@ -376,8 +391,14 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
                      ACX_ACT_QUICKGELU, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
     if (x6_proj) {
       if (!x6_fc && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, (int64_t)rows * 4 * W * 2, rows, 4 * W, s))) return rc;
+      // the next layer's ln_1 where it writes the planes of ws.hp: a whole layer with its in-projection on the plane kernel, or the
+      // pruned last layer's K | V product
+      const bool next_planes = l + 1 < layers && ((cls_ws && l + 1 == layers - 1) ? x6_takes(ctx, ws, rows, 2 * W, W, W) && blk[l + 1].in_proj_w_bf16 != nullptr
+                                                                                  : x6_qkv);
+      ln1_done = ln_ride && next_planes;
+      const acx_ln_job ln1 = {ln1_done ? blk[l + 1].ln1_w : nullptr, ln1_done ? blk[l + 1].ln1_b : nullptr, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};
       if ((rc = linear_x6(ctx, ws.mp, 4 * W, rows, b.proj_w_bf16, (int64_t)W * 4 * W * 2, 4 * W, x, W, (int)rows, W, 4 * W, b.proj_b,
-                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4))) return rc;
+                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln1_done ? &ln1 : nullptr))) return rc;
     } else
     if ((rc = linear(ctx, prec, ws.mlp, hdt, 4 * W, b.proj_w, b.proj_w_bf16, 4 * W, x, ACX_F32, W, (int)rows, W, 4 * W,
                      b.proj_b, ACX_ACT_NONE, x, s, 0, ws.splitk, ws.splitk_bytes))) return rc;

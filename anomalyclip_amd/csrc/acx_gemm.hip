@@ -40,6 +40,7 @@
 //   gemm_bf16_ring_kernel    _bf16.h     bf16, persistent 256x256 tiles for the large-M shapes
 //   gemm_tn_kernel / _w8     _tn.h       weight gradients C = A^T B (reduction over rows), split-M + reduce
 #include "acx_internal.h"
+#include "acx_ln_rows.h"     // LnRide, ln_ride_rows: the LayerNorm rider of gemm_x6_p4_kernel
 
 #include <stdlib.h>
 #include <type_traits>
@@ -76,6 +77,7 @@ struct Args {
   const float* zeros;      // acx_gemm_desc.zero_page (conv taps outside the grid on the LDS-DMA kernels)
   unsigned int* counters;  // acx_gemm_desc.counters (few-row kernel's cross-workgroup K split: one arrival counter per tile)
   int tile0, ntiles;       // gemm_x6_p4_kernel: the launch covers the full 256 x 256 tiles tile0 .. tile0 + ntiles (ntiles = 0: all)
+  LnRide ln;               // gemm_x6_p4_kernel<.., RIDE = 1>: the LayerNorm rows of the workgroups without a tile (last member: the offsets above stay)
 };
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -567,6 +569,35 @@ bool acx_gemm_takes_strip_stream(const acx_gemm_desc* d) {
 // at K = 3072), growing with the number of strips in flight; 64-column strips 0.29-0.33 (0.38-0.45).  Upper ends here: strips are
 // taken for rem <= CUs / 2 (64-column ones for rem <= CUs / 4), which is where every measured case gains.
 static inline double x6_strip_cost(int ni) { return ni == 2 ? 0.55 : 0.45; }
+// LayerNorm rows riding in a partly filled last round (acx_gemm_ln; gemm_x6_p4_kernel<.., RIDE = 1>).
+//   * duration of the last round: a round of whole tiles takes 2.7 + 4.16 us x K-steps (profiles/x6_mfma_shape_ab.txt, "round" column:
+//     0.1025 ms at K = 768, 0.4018 ms at K = 3072), what the 158 tiles of the bench shape's last round ADD to the four before it is
+//     0.8 of that (0.1940 - 0.1025 and 0.7267 - 0.4018 ms there); a round of strips x6_strip_cost of it.
+//   * rate of the riders, LayerNorm rows of 768 columns per us and rider CU (one 4-wave workgroup per CU beside the tail's tiles):
+//     profiles/ln_rider_gate.txt -- at K = 768 (98 riders beside 158 tiles) the pair product + LayerNorm is fastest with 43,648 rows
+//     riding (32,736 and 54,560 within 1 % of it; all 87,296 completed rows: slower than not riding), i.e. 4.9-5.4 rows per us and
+//     rider over the tail's ~85 us; at K = 3072 every completed row fits and riding all of them is fastest.  Wider rows in
+//     proportion.  The constant is below the measurement: a rider must not outlast the tail.
+static inline double x6_tail_us(int nks, int strip_ni) { return 0.8 * (2.7 + 4.16 * nks) * (strip_ni == 4 ? 1.0 : x6_strip_cost(strip_ni)); }
+constexpr double X6_RIDE_ROWS_PER_US_CU = 4.5;
+// rows (even) that ride: the smaller of the rows the full rounds completed (tiles 0 .. tile0_tail of `tiles_n` per row block)
+// and what `riders` workgroups finish within the tail at `rate` rows of 768 columns per us each (<= 0: the constant above)
+static inline long long x6_ride_rows(long long M, int N, int tiles_n, int tile0_tail, int riders, int nks, int strip_ni, double rate) {
+  if (riders <= 0 || tile0_tail <= 0 || tiles_n <= 0) return 0;
+  long long ready = (long long)(tile0_tail / tiles_n) * 256;
+  if (ready > M) ready = M;
+  if (rate <= 0.0) rate = X6_RIDE_ROWS_PER_US_CU;
+  const double cap = rate * (768.0 / (double)N) * riders * x6_tail_us(nks, strip_ni);
+  long long ride = cap < (double)ready ? (long long)cap : ready;
+  return ride > 0 ? ride & ~1ll : 0;
+}
+// the cheaper strip width (NI = 2 / 1) for a last round of `rem` whole tiles on ncu workgroups; *best = that round's cost in whole-tile rounds
+static inline int x6_strip_pick(int rem, int ncu, double* best) {
+  const double cost2 = (double)((2 * rem + ncu - 1) / ncu) * x6_strip_cost(2), cost1 = (double)((4 * rem + ncu - 1) / ncu) * x6_strip_cost(1);
+  *best = cost1 < cost2 ? cost1 : cost2;
+  return cost1 < cost2 ? 1 : 2;
+}
+constexpr double X6_STRIP_MAX_COST = 0.93;       // strips are taken when they shorten the last round to less than this
 static inline bool x6_strip_enabled(const acx_ctx* ctx) { return ACX_DBG_SWITCH("X6_STRIP", true) && (!ctx || ctx->opt_x6_strip); }
 
 // K split of the plane-reuse kernel: `tiles` output tiles of `nks` K-steps on ncu persistent workgroups.  Cost of s pieces =
@@ -586,7 +617,8 @@ static int x6_choose_split(int tiles, int nks, int ncu, size_t image_bytes, size
   return best;
 }
 
-extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
+// job != nullptr (acx_gemm_ln): *ridden = the rows 0 .. *ridden of the job's LayerNorm that rode in the product's last round (0: none)
+static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden) {
   if (!d || !d->A || !d->W || !d->C) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: null pointer%s");
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: empty shape%s");
   const int prec = d->prec;
@@ -672,8 +704,8 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
           dt.C = (char*)d->C + (d->c_dtype == ACX_BF16X3P ? (size_t)row0 * 32 * 2
                                                           : (size_t)row0 * d->ldc * (d->c_dtype == ACX_F32 ? 4 : 2));
           if (d->residual) dt.residual = d->residual + (size_t)row0 * d->ldr;
-          const int rc = acx_gemm(ctx, &dm, stream);
-          return rc ? rc : acx_gemm(ctx, &dt, stream);
+          const int rc = gemm_impl(ctx, &dm, stream, nullptr, nullptr);
+          return rc ? rc : gemm_impl(ctx, &dt, stream, nullptr, nullptr);
         }
       }
     }
@@ -691,6 +723,7 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
   dim3 grid((unsigned)(tiles_m * g.tiles_n)), block(NTHREADS);
   g.ksplit = 1; g.kchunk = 0; g.partial = nullptr; g.counters = nullptr;
   g.tile0 = 0; g.ntiles = 0;
+  memset(&g.ln, 0, sizeof(g.ln));
   g.zeros = (const float*)d->zero_page;
   const size_t lds = 4 * TILE_B;
   hipStream_t s = (hipStream_t)stream;
@@ -844,20 +877,45 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
       if (!conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && x6_strip_enabled(ctx)) {
         const int rounds = xt / ncu, rem = xt - rounds * ncu;
         if (rem > 0) {
-          const double c2 = x6_strip_cost(2), c1 = x6_strip_cost(1);
-          const double cost2 = (double)((2 * rem + ncu - 1) / ncu) * c2, cost1 = (double)((4 * rem + ncu - 1) / ncu) * c1;
-          const double best = cost1 < cost2 ? cost1 : cost2;
+          double best = 0.0;
+          const int pick = x6_strip_pick(rem, ncu, &best);
           const int force = ctx ? ctx->opt_x6_strip : 1;    // 2 / 3: always 128- / 64-column strips (measurements)
           const double strip_us = (rounds + best) * (nks + 4.0) * 3.0;
           if (force >= 2) { strip_ni = force == 2 ? 2 : 1; tile0_tail = rounds * ncu; rem_tail = rem; }
-          else if (best < 0.93 && (split == 1 || (strip_us < split_us && !(ctx && ctx->opt_x6_tail)))) { strip_ni = cost1 < cost2 ? 1 : 2; tile0_tail = rounds * ncu; rem_tail = rem; }
+          else if (best < X6_STRIP_MAX_COST && (split == 1 || (strip_us < split_us && !(ctx && ctx->opt_x6_tail)))) { strip_ni = pick; tile0_tail = rounds * ncu; rem_tail = rem; }
           if (strip_ni < 4) split = 1;
         }
       }
       g.ksplit = split; g.kchunk = (nks + split - 1) / split; g.partial = split > 1 ? (float*)d->workspace : nullptr;
-      const int items = (strip_ni < 4 ? tile0_tail : xt) * split;
+      // LayerNorm riders (acx_gemm_ln): the residual product's last round -- whole tiles or strips, fewer items than workgroups, no K
+      // split -- goes out as a launch of its own on ncu workgroups; those without an item normalise rows the full rounds completed
+      long long ride = 0;
+      int ride_tile0 = 0, ride_rem = 0;           // whole-tile last round of a riding launch (strip_ni == 4): tiles ride_tile0 .. + ride_rem
+      if (job && ridden && !conv && !x3 && split == 1 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
+          (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && job->y_dtype == ACX_BF16X3P && job->w && job->b && job->y &&
+          !((uintptr_t)job->y & 15) && !(((long long)d->M * d->N * 2) & 15) && ACX_DBG_SWITCH("LN_RIDER", true) && ctx && ctx->opt_ln_rider) {
+        const int rounds = xt / ncu, rem = xt - rounds * ncu;
+        const int t0 = strip_ni < 4 ? tile0_tail : rounds * ncu;
+        const int tail_items = strip_ni < 4 ? rem_tail * (4 / strip_ni) : rem;
+        if (rounds >= 1 && rem > 0 && tail_items < ncu) {
+          ride = x6_ride_rows(d->M, d->N, d->N / 256, t0, ncu - tail_items, nks, strip_ni, 0.0);
+          if (ctx->opt_ln_rider > 1) {             // (measurements: ride up to this many of the completed rows)
+            const long long ready = x6_ride_rows(d->M, d->N, d->N / 256, t0, ncu - tail_items, nks, strip_ni, 1e30);
+            ride = (ctx->opt_ln_rider < ready ? ctx->opt_ln_rider : ready) & ~1ll;
+          }
+          if (ride > 0 && strip_ni == 4) { ride_tile0 = t0; ride_rem = rem; }
+        }
+      }
+      if (ride > 0) {
+        g.ln.x = (const float*)d->C; g.ln.w = job->w; g.ln.b = job->b; g.ln.y = (u16*)job->y;
+        g.ln.ldx = d->ldc; g.ln.rows = d->M; g.ln.row0 = 0; g.ln.nrows = ride;
+        g.ln.eps = job->eps; g.ln.mode = job->mode; g.ln.vpl = d->N / 64;
+        *ridden = ride;
+      }
+      const int items = (strip_ni < 4 ? tile0_tail : ride_rem ? ride_tile0 : xt) * split;
       const dim3 xgrid((unsigned)(items < ncu ? items : ncu));
       if (strip_ni < 4) { g.tile0 = 0; g.ntiles = tile0_tail; }
+      else if (ride_rem) { g.tile0 = 0; g.ntiles = ride_tile0; }
 #define ACX_X6L_(CM, ACT, RES, CV, NI_, GRID)                                                        \
   do {                                                                                              \
     if constexpr ((CV) == 0 && (CM) != 1 && (ACT) != 2) {   /* (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual) */ \
@@ -890,6 +948,16 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
     }                                                                                               \
     hipLaunchKernelGGL((gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI_>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
   } while (0)
+#define ACX_X6R(NI_, GRID)                                                                           \
+  do {                                                                                              \
+    static bool attrr_dev_[64] = {}; bool& attrr_done = attrr_dev_[dev_slot];                       \
+    if (!attrr_done) {                                                                              \
+      (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI_, 0, 0, 1>,     \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);         \
+      attrr_done = true;                                                                            \
+    }                                                                                               \
+    hipLaunchKernelGGL((gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI_, 0, 0, 1>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
+  } while (0)
 #define ACX_X6L(CM, ACT, RES, CV) do { if (items > 0) ACX_X6L_(CM, ACT, RES, CV, 4, xgrid); } while (0)
 #define ACX_X6SEL(CV)                                                                               \
   do {                                                                                              \
@@ -909,7 +977,10 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
         // f32 with a residual / QuickGELU / plain) -- anything else keeps whole tiles (x6_strip_epilogue_ok)
         g.tile0 = tile0_tail * (4 / strip_ni); g.ntiles = rem_tail * (4 / strip_ni);   // (in the strips' own numbering: N % 256 == 0)
         const int sitems = rem_tail * (4 / strip_ni);
-        const dim3 sgrid((unsigned)(sitems < ncu ? sitems : ncu));
+        const dim3 sgrid((unsigned)(ride > 0 || sitems >= ncu ? ncu : sitems));
+        if (ride > 0) {                           // (eligibility above: the f32 residual epilogue)
+          if (strip_ni == 2) ACX_X6R(2, sgrid); else ACX_X6R(1, sgrid);
+        } else
 #define ACX_X6S(NI_)                                                                                 \
   do {                                                                                              \
     if (c_x3_) { if (d->act == ACX_ACT_QUICKGELU) ACX_X6L_(2, 1, 0, 0, NI_, sgrid); else ACX_X6L_(2, 0, 0, 0, NI_, sgrid); } \
@@ -919,7 +990,11 @@ extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
   } while (0)
         if (strip_ni == 2) ACX_X6S(2); else ACX_X6S(1);
 #undef ACX_X6S
+      } else if (ride_rem) {
+        g.tile0 = ride_tile0; g.ntiles = ride_rem;
+        ACX_X6R(4, dim3((unsigned)ncu));
       }
+#undef ACX_X6R
 #undef ACX_X6SEL
 #undef ACX_X6L
 #undef ACX_X6L_
@@ -1252,6 +1327,41 @@ static int tn_p256_splits(int64_t M, int64_t N1, int64_t N2, int ncu) {
 constexpr size_t TN_ZERO_B = 1024;               // zero page at the end of the workspace (the DMA kernel's padding source)
 
 // ---- grouped small weight gradients (identity row map, no conv): see gemm_tn_w8_group_kernel
+
+extern "C" int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) { return gemm_impl(ctx, d, stream, nullptr, nullptr); }
+
+// acx_gemm followed by the LayerNorm of its output rows (x = d->C, [M, N] f32 with ldc == N) into the next product's K-panel
+// planes.  A pairs = 6 residual product whose last round of tiles fills only part of the chip goes out as its full rounds, then its
+// last round with the idle workgroups normalising rows the full rounds completed, then acx_layernorm on the rows that did not
+// ride; every other problem is acx_gemm + acx_layernorm.  Same bits either way (one arithmetic: acx_ln_rows.h).
+extern "C" int acx_gemm_ln(acx_ctx* ctx, const acx_gemm_desc* d, const acx_ln_job* job, void* stream) {
+  if (!job || !job->w || !job->b || !job->y) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_ln: null pointer%s");
+  if (!d || d->c_dtype != ACX_F32) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_ln: the product's output must be f32%s");
+  long long ridden = 0;
+  int rc = gemm_impl(ctx, d, stream, job, &ridden);
+  if (rc) return rc;
+  if (ridden > 0)
+    return acx_layernorm_rows(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, d->M, ridden, d->N, job->eps, job->mode, stream);
+  return acx_layernorm(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, d->N, job->y_dtype, d->M, d->N, job->eps, job->mode, stream);
+}
+
+// The host-side plan of acx_gemm_ln for an eligible product (pairs = 6, f32 residual epilogue, identity rows, N = 768 or 1024, even
+// M) on `ncu` workgroups: returns the rows that ride (0: none), *rows_ready = rows the full rounds complete.  ksplit > 1 (a K
+// split: fewer tiles than workgroups) never rides; rate <= 0: the library's constant (rows of 768 columns per us and rider CU).
+extern "C" int64_t acx_gemm_ln_plan(int32_t M, int32_t N, int32_t K, int32_t ncu, int32_t ksplit, double rate, int64_t* rows_ready) {
+  if (rows_ready) *rows_ready = 0;
+  if (M <= 0 || N <= 0 || K <= 0 || ncu <= 0 || ksplit > 1 || N % 256 || (M & 1) || K % 32) return 0;
+  const int tiles_n = N / 256, xt = ((M + 255) / 256) * tiles_n, nks = K / 32;
+  const int rounds = xt / ncu, rem = xt - rounds * ncu;
+  if (rounds < 1 || rem == 0) return 0;
+  double best = 0.0;                              // (acx_gemm's strip choice at its defaults)
+  const int pick = x6_strip_pick(rem, ncu, &best), strip_ni = best < X6_STRIP_MAX_COST ? pick : 4;
+  const int tail_items = rem * (4 / strip_ni);
+  if (tail_items >= ncu) return 0;
+  if (rows_ready) *rows_ready = x6_ride_rows(M, N, tiles_n, rounds * ncu, ncu - tail_items, nks, strip_ni, 1e30);
+  return x6_ride_rows(M, N, tiles_n, rounds * ncu, ncu - tail_items, nks, strip_ni, rate);
+}
+
 extern "C" size_t acx_gemm_tn_group_workspace_bytes(int32_t nprob, const acx_tn_problem* probs) {
   size_t need = 0;
   for (int i = 0; i < nprob; ++i) {

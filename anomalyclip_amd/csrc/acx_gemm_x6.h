@@ -120,9 +120,16 @@ __device__ __forceinline__ T& x6_sel(T& a, T& b) {
   if constexpr (FIRST) return a; else return b;
 }
 
-template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0>
+// RIDE (NT six-product form with the f32 residual epilogue only; acx_gemm_ln): the launch is the LAST, partly filled round of a
+// product and its grid is the CU count -- the workgroups that draw no item normalise rows of the residual stream which the
+// launch before (the full rounds, same stream) completed, and write them as the NEXT product's K-panel planes (g.ln: acx_ln_rows.h,
+// the arithmetic of layernorm_panel2_kernel: a row's planes are bit-identical whichever kernel wrote them).  No workgroup waits for
+// another: the riders read rows no tile of this launch writes and write plane rows no tile of this launch reads.  The workgroups
+// with an item run exactly the code of the RIDE = 0 instantiation.
+template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0, int RIDE = 0>
 __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   static_assert(X3 == 0 || (CONV == 0 && TN == 0 && PLAIN == 0 && W14 == 0), "three-product mode: identity rows, NT");
+  static_assert(RIDE == 0 || (C_MODE == 0 && ACT == 0 && RES == 1 && CONV == 0 && TN == 0 && PLAIN == 0 && X3 == 0), "LayerNorm rider: the residual products");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const acx_gemm_desc& d = g.d;
   const int t = threadIdx.x, lane = t & 63;
@@ -141,6 +148,15 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
   const int b0 = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + ((int)blockIdx.x >> 3);
   const int my_items = b0 < nitems ? (nitems - b0 + G - 1) / G : 0;
+  if constexpr (RIDE != 0) {
+    if (my_items == 0) {                         // b0 - nitems: this workgroup's ordinal among the G - nitems riders
+      if (g.ln.nrows > 0) {
+        if (g.ln.vpl == 12) ln_ride_rows<12>(g.ln, b0 - nitems, G - nitems, wave, lane);
+        else ln_ride_rows<16>(g.ln, b0 - nitems, G - nitems, wave, lane);
+      }
+      return;
+    }
+  }
   if (my_items == 0) return;
   const int nks = PLAIN ? d.K / 64 : (d.K + 31) / 32;   // K-steps of a tile (TN: the last one may be ragged: zero page; PLAIN: super-steps)
   const int spi = (nks + ksplit - 1) / ksplit;   // K-steps per item; the last K range of a tile takes what is left (dispatch: > 0)

@@ -62,6 +62,7 @@ struct acx_ctx {
   int opt_x6_tail;          // ACX_OPT_X6_TAIL_SPLIT (0: off)
   int opt_x6_min_tiles;     // ACX_OPT_X6_MIN_TILES
   int opt_x6_strip;         // ACX_OPT_X6_STRIP_TAIL (1: by the cost model, 0: off, 2 / 3: always 128- / 64-column strips)
+  long long opt_ln_rider;   // ACX_OPT_LN_RIDER (1: rows by the cost model, 0: off, > 1: ride up to this many rows -- measurements)
   char err[512];
   bool prof_on;
   bool prof_gemm_only;   // acx_prof_enable(ctx, 2): event pairs around the GEMM launches only
@@ -121,6 +122,9 @@ static inline int acx_check_launch(acx_ctx* ctx, const char* name) {
 
 // acx_gemm.hip: true when acx_gemm runs `d` on the persistent strip-stream kernel (no partial last wave to split off)
 bool acx_gemm_takes_strip_stream(const acx_gemm_desc* d);
+// acx_norm.hip: LayerNorm of rows row0 .. rows (row0 even) into ACX_BF16X3P planes of `rows` rows -- what acx_gemm_ln's riders left
+int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
+                       int64_t row0, int32_t D, float eps, int32_t mode, void* stream);
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -6,27 +6,9 @@
 //   acx_cls_head   : mean of the two reversible streams + LayerNorm + Linear(E,1) + sigmoid
 //                    (classification_head.py:11-15), with the inverse test-mode tiling on store
 #include "acx_internal.h"
+#include "acx_ln_rows.h"     // normalize, ln_panel2_store: shared with the LayerNorm rider of the plane-reuse GEMM
 
 namespace {
-
-template <int VPL>
-__device__ __forceinline__ void normalize(float (&v)[VPL], float eps, int mode) {
-  constexpr float invD = 1.f / (64 * VPL);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) s += v[i];
-  const float mean = wave_sum(s) * invD;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    v[i] -= mean;
-    q += v[i] * v[i];
-  }
-  const float var = wave_sum(q) * invD;
-  const float scale = mode == ACX_NORM_LAYER ? 1.f / sqrtf(var + eps) : 1.f / (sqrtf(var) + eps);
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) v[i] *= scale;
-}
 
 // OUT_BF16 == 2: the row as THREE bf16 planes hi | mid | lo (x = hi + mid + lo to 24 bits: the A operand of acx_gemm_desc.pairs =
 // 6), plane p at y + p * plane elements
@@ -112,10 +94,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 template <int VPL, bool TWO = false, bool F16 = false>
 __global__ __launch_bounds__(256) void layernorm_panel2_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                                const float* __restrict__ b, u16* __restrict__ y, int64_t rows,
-                                                               float eps, int mode) {
+                                                               float eps, int mode, int64_t row0) {
   static_assert(VPL % 4 == 0, "16-byte row loads");
+  // row0 (even): the launch covers rows row0 .. rows of the planes (acx_gemm_ln: the rows before it rode in the product's last round)
   const int lane = threadIdx.x & 63;
-  const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;         // even: rows r0, r0 + 1 share a line in every panel
+  const int64_t r0 = row0 + ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;  // even: rows r0, r0 + 1 share a line in every panel
   if (r0 >= rows) return;
   const bool two = r0 + 1 < rows;
   float va[VPL], vb[VPL];
@@ -123,54 +106,9 @@ __global__ __launch_bounds__(256) void layernorm_panel2_kernel(const float* __re
   load_row<VPL>(x + (two ? r0 + 1 : r0) * ldx, lane, vb);
   normalize<VPL>(va, eps, mode);
   normalize<VPL>(vb, eps, mode);
-  const int64_t plane = rows * (int64_t)(64 * VPL);
-  const int odd = lane & 1;
-#pragma unroll
-  for (int i = 0; i < VPL / 4; ++i) {
-    const int e = 4 * lane + 256 * i;
-    const float4 ww = *reinterpret_cast<const float4*>(w + e);
-    const float4 bb = *reinterpret_cast<const float4*>(b + e);
-    float oa[4] = {va[4 * i] * ww.x + bb.x, va[4 * i + 1] * ww.y + bb.y, va[4 * i + 2] * ww.z + bb.z, va[4 * i + 3] * ww.w + bb.w};
-    float ob[4] = {vb[4 * i] * ww.x + bb.x, vb[4 * i + 1] * ww.y + bb.y, vb[4 * i + 2] * ww.z + bb.z, vb[4 * i + 3] * ww.w + bb.w};
-    // the pair (2 j, 2 j + 1) holds elements 8 j .. 8 j + 7 of both rows: even keeps row a (own four + the odd lane's four), odd row b
-    float o8[8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float give = odd ? oa[k] : ob[k];                                    // what the partner needs from this lane
-      const float got = __shfl_xor(give, 1, 64);
-      o8[k] = odd ? got : oa[k];                                                 // elements 8 j + k
-      o8[4 + k] = odd ? ob[k] : got;                                             // elements 8 j + 4 + k
-    }
-    u16 hh[8], mm[8], ll[8];
-    if constexpr (F16) {
-#pragma unroll
-      for (int k = 0; k < 8; k += 2) {
-        const uint32_t ph_ = f2h2(o8[k], o8[k + 1]);
-        const uint32_t pl_ = f2h2(o8[k] - h2f_lo(ph_), o8[k + 1] - h2f_hi(ph_));
-        hh[k] = (u16)(ph_ & 0xffffu); hh[k + 1] = (u16)(ph_ >> 16);
-        mm[k] = (u16)(pl_ & 0xffffu); mm[k + 1] = (u16)(pl_ >> 16);
-        ll[k] = ll[k + 1] = 0;
-      }
-    } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      hh[k] = f2bf(o8[k]);
-      const float r1 = o8[k] - bf2f(hh[k]);
-      mm[k] = f2bf(r1);
-      ll[k] = f2bf(r1 - bf2f(mm[k]));
-    }
-    }
-    const int e8 = 8 * (lane >> 1) + 256 * i;
-    const int64_t row = r0 + odd;
-    if (odd && !two) continue;
-    u16* dst = y + ((int64_t)(e8 >> 5) * rows + row) * 32 + (e8 & 31);
-#define LNP_PACK(a) make_uint4((uint32_t)a[0] | ((uint32_t)a[1] << 16), (uint32_t)a[2] | ((uint32_t)a[3] << 16), \
-                               (uint32_t)a[4] | ((uint32_t)a[5] << 16), (uint32_t)a[6] | ((uint32_t)a[7] << 16))
-    *reinterpret_cast<uint4*>(dst) = LNP_PACK(hh);
-    *reinterpret_cast<uint4*>(dst + plane) = LNP_PACK(mm);
-    if constexpr (!TWO) *reinterpret_cast<uint4*>(dst + 2 * plane) = LNP_PACK(ll);
-#undef LNP_PACK
-  }
+  float4 ww[VPL / 4], bb[VPL / 4];
+  ln_load_affine<VPL>(w, b, lane, ww, bb);
+  ln_panel2_store<VPL, TWO, F16>(va, vb, ww, bb, y, rows, r0, two, lane);
 }
 
 template <int VPL>
@@ -251,11 +189,14 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__
     default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,640,768,1024}", "", (long)(D)); \
   }
 
-extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
-                             void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
-                             int32_t mode, void* stream) {
+// row0 > 0 (acx_layernorm_rows; even, K-panel bf16 x 3 planes on the two-rows-per-wave kernel only): rows row0 .. rows
+static int layernorm_impl(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
+                          void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
+                          int32_t mode, void* stream, int64_t row0) {
   if (!x || !w || !b || !y) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm: null pointer%s");
-  if (rows <= 0) return ACX_OK;
+  if (rows <= 0 || row0 >= rows) return ACX_OK;
+  if (row0 && (row0 < 0 || (row0 & 1) || y_dtype != ACX_BF16X3P || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15)))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm_rows: an even first row, ACX_BF16X3P planes with 16-byte aligned planes%s");
   if (D % 64 || ldx % 4 || ldy % 4) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm: D%%64 / ld%%4%s");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)stream;
@@ -263,24 +204,24 @@ extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const fl
   if (y_dtype == ACX_F16X2P) {         // two fp16 planes in K-panel layout (the ViT width only: the ACX_PREC_F16X3 driver)
     if (ldy != D || D != 768 || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15))
       return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_F16X2P needs ldy == D == 768 and 16-byte aligned planes%s");
-    layernorm_panel2_kernel<12, true, true><<<dim3((unsigned)((rows + 7) / 8)), block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode);
+    layernorm_panel2_kernel<12, true, true><<<dim3((unsigned)((rows + 7) / 8)), block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, (int64_t)0);
     ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
     return ACX_OK;
   }
   if (y_dtype == ACX_BF16X3P || y_dtype == ACX_BF16X2P) {   // three planes in K-panel layout [D / 32][rows][32] each (ldy == D), y + p * rows * ldy
     if (ldy != D || D % 256) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm: ACX_BF16X3P needs ldy == D, D %% 256 == 0%s");
     if (!((uintptr_t)y & 15) && !((rows * (int64_t)D * 2) & 15)) {                // 16-byte stores: two rows per wave
-      const dim3 grid2((unsigned)((rows + 7) / 8));
+      const dim3 grid2((unsigned)((rows - row0 + 7) / 8));
       if (y_dtype == ACX_BF16X2P && D == 768) {                                   // (hi and mid planes only: the ViT width)
-        layernorm_panel2_kernel<12, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode);
+        layernorm_panel2_kernel<12, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, (int64_t)0);
         ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
         return ACX_OK;
       }
       switch (D / 64) {
-        case 4: layernorm_panel2_kernel<4><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode); break;
-        case 8: layernorm_panel2_kernel<8><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode); break;
-        case 12: layernorm_panel2_kernel<12><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode); break;
-        case 16: layernorm_panel2_kernel<16><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode); break;
+        case 4: layernorm_panel2_kernel<4><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
+        case 8: layernorm_panel2_kernel<8><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
+        case 12: layernorm_panel2_kernel<12><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
+        case 16: layernorm_panel2_kernel<16><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
         default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_BF16X3P needs D in {256, 512, 768, 1024}%s");
       }
     } else
@@ -294,6 +235,18 @@ extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const fl
   }
   ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
   return ACX_OK;
+}
+
+extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
+                             void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
+                             int32_t mode, void* stream) {
+  return layernorm_impl(ctx, x, ldx, w, b, y, ldy, y_dtype, rows, D, eps, mode, stream, 0);
+}
+
+// acx_gemm_ln's remainder: the LayerNorm of rows row0 .. rows into ACX_BF16X3P planes of `rows` rows (acx_internal.h)
+int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
+                       int64_t row0, int32_t D, float eps, int32_t mode, void* stream) {
+  return layernorm_impl(ctx, x, ldx, w, b, y, D, ACX_BF16X3P, rows, D, eps, mode, stream, row0);
 }
 
 extern "C" int acx_vit_embed(acx_ctx* ctx, const float* patch_out, const float* cls, const float* pos,

@@ -102,6 +102,22 @@ def set_x6_min_tiles(device_index: int, tiles: int) -> None:
     L.check(L.lib().acx_set_option(h, L.OPT_X6_MIN_TILES, int(tiles)), h)
 
 
+def set_ln_rider(device_index: int, mode: int) -> None:
+    """ACX_OPT_LN_RIDER: 1 (default) = acx_gemm_ln runs LayerNorm rows on the workgroups that have no tile in a residual product's
+    partly filled last round, as many as its cost model says fit; 0 = product, then LayerNorm; > 1 = up to that many rows
+    (measurements).  Bit-identical results for every value."""
+    h = L.ctx(device_index)
+    L.check(L.lib().acx_set_option(h, L.OPT_LN_RIDER, int(mode)), h)
+
+
+def ln_rider_plan(M: int, N: int, K: int, ncu: int, ksplit: int = 1, rate: float = 0.0):
+    """(rows that ride, rows the full rounds complete) of acx_gemm_ln for an eligible product on ncu workgroups -- host arithmetic,
+    no device; rate: LayerNorm rows of 768 columns per us and rider workgroup (<= 0: the library's constant)"""
+    ready = C.c_int64(0)
+    ride = L.lib().acx_gemm_ln_plan(int(M), int(N), int(K), int(ncu), int(ksplit), float(rate), C.byref(ready))
+    return int(ride), int(ready.value)
+
+
 _SPLITK_WS: dict = {}
 _SPLITK_RETIRED: list = []
 
@@ -293,12 +309,14 @@ def unpanel(planes: torch.Tensor) -> torch.Tensor:
 def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] = None, bias=None, act=L.ACT_NONE,
             residual=None, out_dtype=torch.float32, amap=L.AMAP_IDENTITY, gn=0, gl=0, cin=0, M: Optional[int] = None,
             planes_out: bool = False, split_k: bool = True, panels: int = 0, panel_out: bool = False, pairs: int = 6,
-            out_scale: float = 0.0) -> torch.Tensor:
+            out_scale: float = 0.0, ln=None) -> torch.Tensor:
     """out[M, N] = epilogue(amap(A) W^T) with A = sum of the three bf16 planes a3 [3, rows, Ka] and W = sum of w3 [3, N, K]
     (split_bf16x3): the six leading cross products on the bf16 matrix cores, f32 accumulation -- the accuracy of an f32
     product (acx_gemm_desc.pairs = 6; acx_gemm_x6.h).  amap = AMAP_CONV3X3: implicit 3x3 convolution over the (gn, gl) token
     grid (K = 9 cin, a3 [3, rows, cin]).  planes_out: the result as three bf16 planes [3, M, N] (the next product's A operand).
-    Few output tiles: K is split across workgroups (split_k, workspace owned by this module)."""
+    Few output tiles: K is split across workgroups (split_k, workspace owned by this module).
+    ln = (weight, bias, y): acx_gemm_ln -- the LayerNorm of the output rows into the K-panel planes y [3, M, N] follows the product
+    (rows of it ride in the product's partly filled last round of tiles; same bits as gemm_x6 + layernorm(panel_out=True))."""
     f16 = a3.dtype == torch.float16          # two fp16 planes per operand (split_f16x2): pairs = 3 only, out_scale undoes the planes' scales
     if f16:
         assert pairs == 3 and a3.shape[0] == 2 and w3.shape[0] == 2 and w3.dtype == torch.float16 and (panel_out or not planes_out)
@@ -348,6 +366,13 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
             ws = _splitk_workspace(a3.device, min(8, max(4, 2 * wgs // max(1, (tail_rows + 255) // 256 * tn))) * tail_rows * N * 4)
             d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     h = _h(a3)
+    if ln is not None:
+        lw, lb, ly = ln
+        assert not planes_out and out.dtype == torch.float32 and ly.dtype == _BF16 and ly.shape == (3, M, N) and ly.is_contiguous()
+        job = L.LnJob()
+        job.w, job.b, job.y, job.y_dtype, job.eps, job.mode = lw.data_ptr(), lb.data_ptr(), ly.data_ptr(), L.BF16X3P, 1e-5, L.NORM_LAYER
+        L.check(L.lib().acx_gemm_ln(h, C.byref(d), C.byref(job), _stream()), h)
+        return out
     L.check(L.lib().acx_gemm(h, C.byref(d), _stream()), h)
     return out
 

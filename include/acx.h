@@ -108,8 +108,12 @@ const char* acx_last_error(acx_ctx* ctx);
 /*   ACX_OPT_X6_MIN_TILES    ACX_PREC_F32X6 drivers (acx_vit_encode, acx_transformer_forward): a product with at least this many
  *                           256 x 256 output tiles runs as a pairs = 6 product, smaller ones on the f32 MFMA kernels (default 18:
  *                           the ViT from 8 frames per launch; measured crossover, profiles/r06_x6_strip_tail.txt). */
+/*   ACX_OPT_LN_RIDER        acx_gemm_ln (and the ACX_PREC_F32X6 drivers, which call it for out-proj -> ln_2 and c_proj -> the next ln_1):
+ *                           1 (default) = the workgroups that have no tile in a residual product's partly filled last round run
+ *                           LayerNorm rows beside it, as many as the cost model says fit; 0 = product, then LayerNorm; > 1 = ride up
+ *                           to this many of the completed rows (measurements).  Results are BIT-IDENTICAL for every value. */
 enum { ACX_OPT_RING_MIN_TILES = 1, ACX_OPT_SK_MAX_M = 2, ACX_OPT_TN_P256_MIN_ROWS = 3, ACX_OPT_X6_CUS = 4, ACX_OPT_X6_TAIL_SPLIT = 5,
-       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7 };
+       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8 };
 int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value);
 
 /* ------------------------------------------------------------------------------------------
@@ -191,6 +195,27 @@ typedef struct acx_gemm_desc {
                              / activation / residual (operand planes that were scaled by acx_split_f16x2); 0 = 1 */
 } acx_gemm_desc;
 int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream);
+
+/* acx_gemm_ln: acx_gemm(d) followed by the LayerNorm of ITS OUTPUT rows -- x = d->C ([M, N] f32, ldc == N), y = norm(x) * w + b as
+ * acx_layernorm(x, ldc, w, b, y, N, y_dtype, M, N, eps, mode) writes it -- with the same bits as those two calls.  A pairs = 6 product
+ * with the f32 residual epilogue (identity rows, N = 768 or 1024, even M, y_dtype = ACX_BF16X3P) whose last round of 256 x 256 tiles
+ * fills only part of the chip goes out as (1) its full rounds, (2) its last round -- whole tiles or strips -- on one workgroup per
+ * CU, where the workgroups without a tile normalise rows that (1) completed and write their planes, (3) acx_layernorm's kernel on
+ * the rows that did not ride.  No workgroup waits for another.  y may be the product's own A planes (the ViT's out-proj reads and
+ * ln_2 writes the same buffer): the riders write plane rows no tile of (2) reads.  ACX_OPT_LN_RIDER = 0: always the two calls. */
+typedef struct acx_ln_job {
+  const float* w;         /* [N] */
+  const float* b;         /* [N] */
+  void* y;                /* output of y_dtype (K-panel planes: [3][N / 32][M][32] bf16, 16-byte aligned) */
+  int32_t y_dtype;
+  float eps;
+  int32_t mode;           /* ACX_NORM_* */
+} acx_ln_job;
+int acx_gemm_ln(acx_ctx* ctx, const acx_gemm_desc* d, const acx_ln_job* job, void* stream);
+/* host-side plan of acx_gemm_ln for an eligible product on `ncu` workgroups (no device needed): returns the rows that ride (even;
+ * 0: none -- no partial round, a K split (ksplit > 1), or no workgroup without a tile), *rows_ready (may be NULL) = the rows the
+ * full rounds complete.  rate: LayerNorm rows of 768 columns per microsecond and rider workgroup, <= 0: the library's constant. */
+int64_t acx_gemm_ln_plan(int32_t M, int32_t N, int32_t K, int32_t ncu, int32_t ksplit, double rate, int64_t* rows_ready);
 
 /* ------------------------------------------------------------------------------------------
  * acx_layernorm: y[r,:] = norm(x[r,:]) * w + b     (HBM-bound; one wavefront per row)
