@@ -24,7 +24,7 @@ from torch import nn
 from .. import ops
 from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, RN50, RN101, RN50X4, RN50X16, RN50X64, TINY
 from .clip_resnet import ModifiedResNet, check_resnet_precision
-from .clip_vit import VisionTransformer, check_vit_precision
+from .clip_vit import VisionTransformer, check_head_geometry, check_vit_precision
 from .coop import PromptLearner
 from .selector_model import SelectorModel
 from .temporal_model import TemporalModel
@@ -146,6 +146,8 @@ class AnomalyCLIP(nn.Module):
             # significant bits per operand); the head keeps the default's arithmetic
             self.precision = "auto"
         head_precision = "f32" if self.precision == "auto" else self.precision      # text tower (too small for the bf16 x 6 kernel)
+        check_head_geometry(self.num_segments, self.seg_length, self.emb_size, self.heads, self.dim_heads, self.num_topk,
+                            self.num_bottomk)                                          # (before anything is allocated)
         geom = g("clip_geometry") or geometry_of_arch(self.arch)
         if isinstance(geom, dict):
             geom = ClipGeometry(**geom)

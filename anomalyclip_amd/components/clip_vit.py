@@ -52,6 +52,38 @@ def check_vit_precision(precision: str, tokens: int, width: int, arch: str, reso
         raise ValueError(f"{arch} has {tokens} tokens per frame: the attention kernels take at most 1024")
 
 
+HEAD_MAX_AXIS = 128                                    # acx_axial_attention: 1 <= axis length <= 128 on either axis
+HEAD_DIMS = (16, 32, 64)                               # ... and head dimension e (include/acx.h)
+LAYERNORM_WIDTHS = (64, 128, 256, 512, 640, 768, 1024)  # acx_layernorm / acx_cls_head row widths
+
+
+def check_head_geometry(num_segments, seg_length, emb_size, heads, dim_heads=None, num_topk=None, num_bottomk=None,
+                        kernel_widths: bool = True):
+    """A ValueError naming the offending `net.*` key, before anything is allocated, for a temporal-head geometry the kernels do not
+    take: an axis of the (num_segments, seg_length) grid outside 1 ... 128, a head dimension e = dim_heads or emb_size / heads
+    outside {16, 32, 64}, an emb_size that is not a LayerNorm width, num_topk / num_bottomk above num_segments.  Everything inside
+    runs: where a fused or plane kernel's own gate is not met the general launches are taken.
+    `kernel_widths=False` leaves the two width checks (e, emb_size) to the first forward: a stand-alone TemporalModel may be
+    constructed at any width to query x6_convs()."""
+    for key, v in (("num_segments", num_segments), ("seg_length", seg_length)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1 or v > HEAD_MAX_AXIS:
+            raise ValueError(f"{key}={v!r}: the axial attention kernels take an integer axis length of 1 ... {HEAD_MAX_AXIS}")
+    if not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"heads={heads!r}: need an integer >= 1")
+    if kernel_widths:
+        if emb_size not in LAYERNORM_WIDTHS:
+            raise ValueError(f"emb_size={emb_size!r}: the LayerNorm kernels take the widths {', '.join(map(str, LAYERNORM_WIDTHS))}")
+        if dim_heads:
+            if dim_heads not in HEAD_DIMS:
+                raise ValueError(f"dim_heads={dim_heads!r}: the attention kernels take a head dimension of 16, 32 or 64")
+        elif emb_size % heads or emb_size // heads not in HEAD_DIMS:
+            raise ValueError(f"heads={heads!r} with emb_size={emb_size}: the head dimension emb_size / heads = {emb_size / heads:g} must "
+                             "be 16, 32 or 64 (or set dim_heads)")
+    for key, v in (("num_topk", num_topk), ("num_bottomk", num_bottomk)):
+        if v is not None and v > num_segments:
+            raise ValueError(f"{key}={v} selects more segments than num_segments={num_segments}")
+
+
 class LayerNorm(nn.Module):
     def __init__(self, width: int):
         super().__init__()

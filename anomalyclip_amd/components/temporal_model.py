@@ -24,7 +24,7 @@ from torch import nn
 from .. import _lib as L
 from .. import ops
 from .classification_head import ClassificationHead
-from .clip_vit import LayerNorm, _Linear
+from .clip_vit import LayerNorm, _Linear, check_head_geometry
 
 
 class _SelfAttention(nn.Module):
@@ -115,6 +115,8 @@ class TemporalModel(nn.Module):
     def __init__(self, input_size: int, emb_size: int, output_size: int, heads: int, dim_heads: Optional[int],
                  depth: int, num_segments: int, seg_length: int):
         super().__init__()
+        # (the width checks wait for forward(): a stand-alone model may be built at any width to ask x6_convs())
+        check_head_geometry(num_segments, seg_length, emb_size, heads, dim_heads, kernel_widths=False)
         self.input_size, self.emb_size, self.output_size = input_size, emb_size, output_size
         self.heads, self.dim_heads, self.depth = heads, dim_heads, depth
         self.num_segments, self.seg_length = num_segments, seg_length
@@ -282,6 +284,7 @@ class TemporalModel(nn.Module):
         int32 [tiles, 2] on the device: base row, row stride between segments) replaces `segment_size` for a BATCH of videos
         with different segment sizes: tile t gathers rows base + n * stride + l and its scores are scattered back there."""
         from . import functional as Fn
+        check_head_geometry(self.num_segments, self.seg_length, self.emb_size, self.heads, self.dim_heads)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if test_mode:
                 # TemporalFn implements the TRAIN tiling "(b n l) d" only; the reference evaluates under Lightning's

@@ -1107,12 +1107,154 @@ __global__ __launch_bounds__(256) void axial_attn_fwd_mfma_kernel(const float* _
   }
 }
 
+// Axial attention forward for any axis length 1 <= T <= 128 and head dim 16 / 32 / 64 (the kernel above keeps T in {16, 32} with
+// e in {16, 32}).  T is padded to tt = ceil(T / 16) tiles of 16 inside the kernel.  A workgroup takes G (line, head) groups per
+// round (G = 4 / 2 / 1 at tt = 1 / 2 / more, so that four waves have a query tile each whenever there are four): K and V of the
+// G groups are staged ONCE in LDS by all 256 threads (rows t >= T written as zeros: P = 0 times an uninitialised V row would be
+// a NaN in the MFMA), then wave w takes the (group, query tile) items w, w + 4, ...  Q never passes through LDS: a lane's B
+// fragment of S^T = K Q^T is 16 contiguous bytes of its query's row.  Padded keys get a score of -inf before the softmax,
+// padded queries read the last real row and are not stored.  LDS = G * 2 * 16 tt * (E + 4) * 4 bytes: 69.6 KB at T = 128,
+// e = 64 (two workgroups per CU).  TTM is the compile-time bound of tt (register tiles are indexed statically).
+template <int TTM, int E>
+__global__ __launch_bounds__(256) void axial_attn_fwd_pad_kernel(const float* __restrict__ qkv, float* __restrict__ out, int gn,
+                                                                 int gl, int heads, int axis, float scale, int T, int tt, int G,
+                                                                 int64_t ngroups) {
+  constexpr int ES = E + 4;
+  constexpr int ET = E / 16, KS = E / 16, F4 = E / 4;
+  extern __shared__ __attribute__((aligned(16))) char smem_ap[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, kq = lane >> 4;
+  const int TP = 16 * tt;
+  float* sKV = reinterpret_cast<float*>(smem_ap);            // [G][K | V][TP][ES]
+  const int He = heads * E, ld = 3 * He;
+  const int other = axis == 0 ? gl : gn;
+  const int64_t rstep = axis == 0 ? gl : 1;
+  auto row0_of = [&](int64_t grp, int& h) -> int64_t {
+    const int64_t line = grp / heads;
+    h = (int)(grp - line * heads);
+    const int64_t tile = line / other;
+    const int o = (int)(line - tile * other);
+    return axis == 0 ? tile * gn * gl + o : (tile * gn + o) * gl;
+  };
+  const int64_t nrounds = (ngroups + G - 1) / G;
+  for (int64_t rnd = blockIdx.x; rnd < nrounds; rnd += gridDim.x) {
+    // ---- stage K and V of the round's groups (float4 per thread)
+    for (int idx = threadIdx.x; idx < G * TP * F4; idx += 256) {
+      const int c4 = idx % F4, tk = idx / F4;
+      const int g = tk / TP, t = tk - g * TP;
+      const int64_t grp = rnd * G + g;
+      float4 k4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = k4;
+      if (t < T && grp < ngroups) {
+        int h;
+        const int64_t row0 = row0_of(grp, h);
+        const float* p = qkv + (row0 + t * rstep) * ld + h * E + 4 * c4;
+        k4 = *reinterpret_cast<const float4*>(p + He);
+        v4 = *reinterpret_cast<const float4*>(p + 2 * He);
+      }
+      float* dk = sKV + ((size_t)(2 * g) * TP + t) * ES + 4 * c4;
+      *reinterpret_cast<float4*>(dk) = k4;
+      *reinterpret_cast<float4*>(dk + TP * ES) = v4;
+    }
+    __syncthreads();
+    for (int item = wave; item < G * tt; item += 4) {
+      const int g = item / tt, it = item - g * tt;
+      const int64_t grp = rnd * G + g;
+      if (grp >= ngroups) break;                               // (wave-uniform)
+      int h;
+      const int64_t row0 = row0_of(grp, h);
+      const float* sK = sKV + (size_t)(2 * g) * TP * ES;
+      const float* sV = sK + TP * ES;
+      const int qi = 16 * it + li;                             // this lane's query
+      const float* qp = qkv + (row0 + (qi < T ? qi : T - 1) * rstep) * ld + h * E + 4 * kq;
+      float4 q4[KS];
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) q4[ks] = *reinterpret_cast<const float4*>(qp + 16 * ks);
+      f32x4 st[TTM];                                           // [jt]: S^T tiles (rows = keys j, column = query)
+      float mx = -INFINITY;
+#pragma unroll
+      for (int jt = 0; jt < TTM; ++jt) {
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        if (jt < tt) {
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            const float4 k4 = *reinterpret_cast<const float4*>(sK + (16 * jt + li) * ES + 16 * ks + 4 * kq);
+            a = __builtin_amdgcn_mfma_f32_16x16x4f32(k4.x, q4[ks].x, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x4f32(k4.y, q4[ks].y, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x4f32(k4.z, q4[ks].z, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_16x16x4f32(k4.w, q4[ks].w, a, 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            a[r] = 16 * jt + 4 * kq + r < T ? a[r] * scale : -INFINITY;
+            mx = fmaxf(mx, a[r]);
+          }
+        }
+        st[jt] = a;
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                  // finite: key 0 is real
+      float sum = 0.f;
+#pragma unroll
+      for (int jt = 0; jt < TTM; ++jt)
+        if (jt < tt) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { st[jt][r] = __expf(st[jt][r] - mx); sum += st[jt][r]; }
+        }
+      sum += __shfl_xor(sum, 16, 64);
+      sum += __shfl_xor(sum, 32, 64);
+      const float inv = 1.f / sum;
+      // O^T[e][i] = sum_j V[j][e] P^T[j][i]: A = V^T (lane & 15 = e, step r <-> j = 4 kq + r), B = the P^T tiles
+#pragma unroll
+      for (int et = 0; et < ET; ++et) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int jt = 0; jt < TTM; ++jt)
+          if (jt < tt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sV[(16 * jt + 4 * kq + r) * ES + 16 * et + li], st[jt][r], acc, 0, 0, 0);
+          }
+        if (qi < T)
+          *reinterpret_cast<float4*>(out + (row0 + qi * rstep) * He + h * E + 16 * et + 4 * kq) =
+              make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
+      }
+    }
+    __syncthreads();                                           // every wave is done with sKV before the next round restages it
+  }
+}
+
 extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, int32_t tiles, int32_t gn, int32_t gl,
                                    int32_t heads, int32_t e, int32_t axis, void* stream) {
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
   if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_axial_attention: null pointer%s");
   if (tiles <= 0) return ACX_OK;
   const int T = axis == 0 ? gn : gl;
+  if (gn <= 0 || gl <= 0 || T > 128 || (e != 16 && e != 32 && e != 64) || heads <= 0)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_axial_attention: need 1 <= axis length <= 128, e in {16,32,64}, heads >= 1%s");
+  if (!((T == 16 || T == 32) && (e == 16 || e == 32))) {
+    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return acx_fail(ctx, ACX_E_BADARG, "acx_axial_attention: qkv / out must be 16-byte aligned%s");
+    const int64_t ngroups = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
+    const int tt = (T + 15) / 16;
+    const int G = tt == 1 ? 4 : tt == 2 ? 2 : 1;
+    const size_t ldsp = (size_t)G * 2 * 16 * tt * (e + 4) * sizeof(float);
+    int64_t nbp = (ngroups + G - 1) / G;
+    const int64_t capp = 4 * (int64_t)(ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256);
+    if (nbp > capp) nbp = capp;
+    const float scale = 1.f / sqrtf((float)e);
+    hipStream_t sp = (hipStream_t)stream;
+#define ACX_AXP(TTM_, EE_)                                                                                 \
+  do {                                                                                                     \
+    (void)hipFuncSetAttribute((const void*)axial_attn_fwd_pad_kernel<TTM_, EE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp); \
+    hipLaunchKernelGGL((axial_attn_fwd_pad_kernel<TTM_, EE_>), dim3((unsigned)nbp), dim3(256), ldsp, sp, qkv, out, gn, gl, heads, axis, \
+                       scale, T, tt, G, ngroups);                                                          \
+  } while (0)
+#define ACX_AXP_E(TTM_) do { if (e == 64) ACX_AXP(TTM_, 64); else if (e == 32) ACX_AXP(TTM_, 32); else ACX_AXP(TTM_, 16); } while (0)
+    if (tt <= 2) ACX_AXP_E(2); else if (tt <= 4) ACX_AXP_E(4); else ACX_AXP_E(8);
+#undef ACX_AXP_E
+#undef ACX_AXP
+    ACX_CHECK_LAUNCH(ctx, "acx_axial_attention(padded mfma)");
+    return ACX_OK;
+  }
   if ((T == 16 || T == 32) && (e == 16 || e == 32) && heads > 0 && !(((uintptr_t)qkv | (uintptr_t)out) & 15)) {
     const int64_t ngroups = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
     const size_t ldsm = (size_t)4 * 3 * T * (e + 4) * sizeof(float);

@@ -696,10 +696,14 @@ __global__ __launch_bounds__(512) void seq_attn_bwd_block_kernel(const float* __
 //   pass 2  S = Q K^T and dP = dO V^T (lane = key column) with the row statistics read back from LDS: the P and dS tiles are
 //           the A operand of dV = P^T dO and dK = dS^T Q as they stand.
 // 224 MFMAs of 16x16x4 per (T = 32, E = 32) group; exact f32 products, fixed summation order.
-template <int T, int E>
+// PAD: the sequence has tlen <= T real elements (T = tlen rounded up to 16, up to 64).  Rows t >= tlen of q, k, v, dO are
+// staged as zeros, padded keys get a score of -inf in pass 1 (P = dS = 0 there), padded queries have dO = 0 and so dS = 0 and
+// add nothing to dK / dV; pass 2's padded key columns only reach dK / dV rows that are not stored.  PAD = false is the
+// kernel of the shipped shapes as it was (tlen unused).
+template <int T, int E, bool PAD = false>
 __global__ __launch_bounds__(256) void axial_attn_bwd_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                   float* __restrict__ dqkv, int gn, int gl, int heads, int axis,
-                                                                  float scale, int64_t ngroups) {
+                                                                  float scale, int64_t ngroups, int tlen) {
   constexpr int ES = E + 4;                      // LDS row stride (floats)
   constexpr int TT = T / 16, ET = E / 16, KS = E / 16;
   constexpr int WF = 4 * T * ES + 4 * T;          // floats per wave: Q, K, V, dO, stats (m, inv, D, pad)
@@ -727,6 +731,16 @@ __global__ __launch_bounds__(256) void axial_attn_bwd_mfma_kernel(const float* _
       const int t = idx / (E / 4), c4 = idx - t * (E / 4);
       const int64_t r = row0 + t * rstep;
       const float* p = qkv + r * ld + h * E + 4 * c4;
+      if constexpr (PAD) {
+        if (t >= tlen) {
+          const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+          *reinterpret_cast<float4*>(sQ + t * ES + 4 * c4) = z;
+          *reinterpret_cast<float4*>(sK + t * ES + 4 * c4) = z;
+          *reinterpret_cast<float4*>(sV + t * ES + 4 * c4) = z;
+          *reinterpret_cast<float4*>(sO + t * ES + 4 * c4) = z;
+          continue;
+        }
+      }
       *reinterpret_cast<float4*>(sQ + t * ES + 4 * c4) = *reinterpret_cast<const float4*>(p);
       *reinterpret_cast<float4*>(sK + t * ES + 4 * c4) = *reinterpret_cast<const float4*>(p + He);
       *reinterpret_cast<float4*>(sV + t * ES + 4 * c4) = *reinterpret_cast<const float4*>(p + 2 * He);
@@ -763,7 +777,11 @@ __global__ __launch_bounds__(256) void axial_attn_bwd_mfma_kernel(const float* _
 #pragma unroll
       for (int jt = 0; jt < TT; ++jt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { st[jt][it][r] *= scale; mx = fmaxf(mx, st[jt][it][r]); }
+        for (int r = 0; r < 4; ++r) {
+          st[jt][it][r] *= scale;
+          if constexpr (PAD) { if (16 * jt + 4 * kq + r >= tlen) st[jt][it][r] = -INFINITY; }
+          mx = fmaxf(mx, st[jt][it][r]);
+        }
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
       float sum = 0.f;
@@ -796,8 +814,10 @@ __global__ __launch_bounds__(256) void axial_attn_bwd_mfma_kernel(const float* _
           for (int r = 0; r < 4; ++r)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dt[jt][it][r], sK[(16 * jt + 4 * kq + r) * ES + 16 * et + li], acc, 0, 0, 0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (PAD) { if (16 * it + 4 * kq + r >= tlen) continue; }
           dqkv[(row0 + (16 * it + 4 * kq + r) * rstep) * ld + h * E + 16 * et + li] = acc[r];
+        }
       }
     }
     // ---- pass 2: scores with lane column = key j; row statistics from LDS
@@ -844,6 +864,7 @@ __global__ __launch_bounds__(256) void axial_attn_bwd_mfma_kernel(const float* _
           }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+          if constexpr (PAD) { if (16 * jt + 4 * kq + r >= tlen) continue; }
           float* dst = dqkv + (row0 + (16 * jt + 4 * kq + r) * rstep) * ld + h * E + 16 * et + li;
           dst[He] = dk[r];
           dst[2 * He] = dv[r];
@@ -1947,7 +1968,7 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
   do {                                                                                                       \
     (void)hipFuncSetAttribute((const void*)axial_attn_bwd_mfma_kernel<TT_, EE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m); \
     hipLaunchKernelGGL((axial_attn_bwd_mfma_kernel<TT_, EE_>), dim3((unsigned)nbm), dim3(256), lds_m, sm, qkv, dout, dqkv, gn, gl, heads, \
-                       axis, scale_m, ngroups_m);                                                            \
+                       axis, scale_m, ngroups_m, T);                                                         \
   } while (0)
     if (T == 32) { if (e == 32) ACX_AXB(32, 32); else ACX_AXB(32, 16); }
     else { if (e == 32) ACX_AXB(16, 32); else ACX_AXB(16, 16); }
@@ -1955,8 +1976,32 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(axial mfma)");
     return ACX_OK;
   }
+  if (!causal && T >= 1 && T <= 64 && (e == 16 || e == 32) && ACX_DBG_SWITCH("AXB_MFMA", true)) {
+    // every other axis length up to 64: the same kernel on the sequence padded to a multiple of 16 (PAD = true)
+    const int64_t ngroups_p = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
+    hipStream_t sp = (hipStream_t)stream;
+    AcxProfScope profp__(ctx, ACX_K_ATTN, sp);
+    const float scale_p = 1.f / sqrtf((float)e);
+    const int TP = (T + 15) / 16 * 16;
+    const size_t lds_p = (size_t)4 * (4 * TP * (e + 4) + 4 * TP) * sizeof(float);       // 151.5 KB at TP = 64, e = 32
+    int64_t nbp = (ngroups_p + 3) / 4;
+    const int64_t capp = 2 * (int64_t)(ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256);
+    if (nbp > capp) nbp = capp;
+#define ACX_AXBP(TT_, EE_)                                                                                   \
+  do {                                                                                                       \
+    (void)hipFuncSetAttribute((const void*)axial_attn_bwd_mfma_kernel<TT_, EE_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p); \
+    hipLaunchKernelGGL((axial_attn_bwd_mfma_kernel<TT_, EE_, true>), dim3((unsigned)nbp), dim3(256), lds_p, sp, qkv, dout, dqkv, gn, gl, \
+                       heads, axis, scale_p, ngroups_p, T);                                                  \
+  } while (0)
+#define ACX_AXBP_E(TT_) do { if (e == 32) ACX_AXBP(TT_, 32); else ACX_AXBP(TT_, 16); } while (0)
+    if (TP == 16) ACX_AXBP_E(16); else if (TP == 32) ACX_AXBP_E(32); else if (TP == 48) ACX_AXBP_E(48); else ACX_AXBP_E(64);
+#undef ACX_AXBP_E
+#undef ACX_AXBP
+    ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(axial mfma, padded)");
+    return ACX_OK;
+  }
   if (T <= 0 || T > 256 || (e != 16 && e != 32 && e != 64))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_seq_attention_bwd: need sequence <= 256, head dim in {16,32,64}%s");
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_seq_attention_bwd: need 1 <= sequence <= 256, head dim in {16,32,64}%s");
   const int64_t nlines = (int64_t)tiles * (axis == 0 ? gl : gn);
   const int64_t ngroups = nlines * heads;
   int gpb = 256 / T;

@@ -436,7 +436,11 @@ int acx_selector_bn(acx_ctx* ctx, const float* raw, const float* mean, const flo
 
 /* acx_axial_attention: the softmax(q k^T e^-1/2) v core of axial_attention.SelfAttention along one
  * axis of the (tiles, gn, gl) token grid.  qkv [rows, 3*heads*e] = (q | k | v) per token, out
- * [rows, heads*e].  axis 0: attend along gn (tokens with equal (tile, l)); axis 1: along gl. */
+ * [rows, heads*e].  axis 0: attend along gn (tokens with equal (tile, l)); axis 1: along gl.
+ * Domain: 1 <= axis length T <= 128 (either axis, any integer), e in {16, 32, 64}, heads >= 1; anything else is
+ * ACX_E_UNSUPPORTED.  T in {16, 32} with e in {16, 32} runs one wave per (line, head) (q, k, v in a wave-private LDS
+ * slice); every other shape runs the padded kernel (T rounded up to 16 inside the kernel, K / V of a group staged once
+ * per workgroup, one query tile per wave; needs 16-byte aligned qkv / out).  Both on v_mfma_f32_16x16x4_f32. */
 int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, int32_t tiles, int32_t gn,
                         int32_t gl, int32_t heads, int32_t e, int32_t axis, void* stream);
 
@@ -576,7 +580,11 @@ int acx_transpose(acx_ctx* ctx, const float* in, float* out, int32_t R, int32_t 
 /* conv weight [Cout,Cin,3,3] -> [Cin][tap'][Cout] with flipped taps: the W operand of the dX implicit GEMM */
 int acx_conv_weight_dx(acx_ctx* ctx, const float* w, float* out, int32_t Cout, int32_t Cin, void* stream);
 /* backward of acx_axial_attention (axis 0/1 on the (tiles,gn,gl) grid) and of acx_attention (tiles=batch,
- * gn=1, gl=L, axis=1, e=64, causal as in the forward): dqkv [rows, 3*heads*e]. */
+ * gn=1, gl=L, axis=1, e=64, causal as in the forward): dqkv [rows, 3*heads*e].
+ * Domain: 1 <= sequence length T <= 256, e in {16, 32, 64} (ACX_E_UNSUPPORTED otherwise).  Non-causal T <= 64 with
+ * e in {16, 32} runs on the f32 MFMA, one wave per (line, head): T in {16, 32} unpadded, every other T padded to a
+ * multiple of 16 inside the kernel.  The text-tower shapes (gn = 1, e = 64) have their own kernels; everything else
+ * (T > 64, or e = 64 on a grid, or causal) runs the general thread-per-(group, row) kernel. */
 int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int32_t tiles,
                           int32_t gn, int32_t gl, int32_t heads, int32_t e, int32_t axis, int32_t causal,
                           float* stats_ws /* [rows*heads*3] floats or NULL */, void* stream);

@@ -5,6 +5,7 @@ the head -- text encoder + selector + axial temporal transformer + loss, forward
 (`head`, `dp_train`) inside the driver's command; this tool adds knobs for development:
 
     python tools/bench_head.py [--batch 64] [--steps 10] [--warmup 2]
+    python tools/bench_head.py --num-segments 24 --seg-length 10 --emb-size 256 --heads 4     # another segment grid / head geometry
     python -m torch.distributed.run --nproc-per-node N tools/bench_head.py --gpus N [--scaling strong|weak]
     python tools/bench_head.py --emulate-world 8      # ONE GPU: rank 0's share of an 8-rank strong-scaling step
                                                       # (8 videos, 2 of 14 text classes, collectives stubbed out):
@@ -93,6 +94,34 @@ def stub_collectives(world, net=None):
     parallel.is_distributed = lambda: True
 
 
+def build_grid_net(hc, precision, dev, cfg):
+    """bench.build_net for a head configuration other than the shipped one (bench.py keeps the shipped geometry)"""
+    from anomalyclip_amd import init_weights as IW
+    from anomalyclip_amd.components.anomaly_clip import AnomalyCLIP, lookup_prompts
+    toks = torch.tensor(lookup_prompts(key=cfg)["tokenized_prompts"], dtype=torch.int32)
+    net = AnomalyCLIP(arch="ViT-B/16", labels_key=cfg, emb_size=hc.emb_size, depth=hc.depth, heads=hc.heads, dim_heads=hc.dim_heads,
+                      num_segments=hc.num_segments, seg_length=hc.seg_length, concat_features=False, normal_id=hc.normal_id,
+                      stride=1, load_from_features=False, select_idx_dropout_topk=0.7, select_idx_dropout_bottomk=0.7,
+                      ncrops=1, num_topk=3, num_bottomk=3, n_ctx=8, shared_context=False, ctx_init="", precision=precision,
+                      vit_chunk=256)
+    sd = IW.init_anomalyclip_state_dict(IW.VIT_B16, hc, toks, seed=0)
+    net.load_state_dict(sd, strict=True)
+    return net.to(dev).eval(), sd, toks.argmax(-1), hc
+
+
+def grid_batch(B_global, world, rank, dev, rows, num_classes, normal_id, step_seed=1):
+    """bench.head_batch with `rows` = num_segments * seg_length features per video"""
+    from anomalyclip_amd import parallel
+    g = torch.Generator().manual_seed(step_seed)
+    feats = torch.randn(B_global, 1, rows, 512, generator=g) * 0.3
+    na = num_classes - 1
+    labels = torch.tensor([i % na + (1 if i % na >= normal_id else 0) for i in range(B_global // 2)] + [normal_id] * (B_global // 2))
+    idx = parallel.shard_videos(B_global, world, rank)
+    f_loc, l_loc = feats[idx].to(dev), labels[idx].to(dev)
+    h = len(idx) // 2
+    return ((f_loc[h:], l_loc[h:]), (f_loc[:h], l_loc[:h])), idx
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -109,6 +138,11 @@ def main():
     ap.add_argument("--x6-tail", action="store_true", help="ACX_OPT_X6_TAIL_SPLIT on (K-split a partly filled last round of tiles)")
     ap.add_argument("--precision", default="auto", choices=["auto", "f32"], help="auto: the convolutions as bf16 x 6 products (default)")
     ap.add_argument("--config", default="ucf", choices=["ucf", "xd"], help="head configuration (xd: E = 128, 7 classes, one crop)")
+    ap.add_argument("--num-segments", type=int, default=0, help="segments per video (default: the configuration's 32)")
+    ap.add_argument("--seg-length", type=int, default=0, help="frames per segment (default: 16)")
+    ap.add_argument("--emb-size", type=int, default=0, help="head width (default: the configuration's 256 / 128)")
+    ap.add_argument("--heads", type=int, default=0, help="attention heads (default: 8)")
+    ap.add_argument("--dim-heads", type=int, default=0, help="head dimension (default: emb_size / heads)")
     ap.add_argument("--extra-streams", type=int, default=0,
                     help="development probe: create (and use once) this many HIP streams BEFORE the step graph exists -- the streams of a "
                          "process share GPU_MAX_HW_QUEUES (default 4) hardware queues; a text stream that lands on the main stream's queue "
@@ -126,13 +160,23 @@ def main():
     from anomalyclip_amd.anomaly_clip_module import AnomalyCLIPModule
     from anomalyclip_amd.components.loss import ComputeLoss
 
-    net, sd, eot, hc = B.build_net(args.precision, dev, cfg=args.config)
+    if args.num_segments or args.seg_length or args.emb_size or args.heads or args.dim_heads:
+        import dataclasses
+        from anomalyclip_amd import init_weights as IW
+        base = {"ucf": IW.UCF_HEAD, "xd": dataclasses.replace(IW.XD_HEAD, ncrops=1)}[args.config]
+        hc = dataclasses.replace(base, num_segments=args.num_segments or base.num_segments, seg_length=args.seg_length or base.seg_length,
+                                 emb_size=args.emb_size or base.emb_size, heads=args.heads or base.heads,
+                                 dim_heads=args.dim_heads or base.dim_heads)
+        net, sd, eot, hc = build_grid_net(hc, args.precision, dev, args.config)
+    else:
+        net, sd, eot, hc = B.build_net(args.precision, dev, cfg=args.config)
+    N, Lg = hc.num_segments, hc.seg_length
     net.load_from_features = True
     net.text_class_parallel = not args.no_text_shard
     net.text_graph = bool(args.text_graph)
     net.temporal_model.graph = bool(args.temporal_graph)
     net.step_graph = not args.no_step_graph
-    crit = ComputeLoss(hc.normal_id, 3, 1.0, 1.0, 1.0, 1.0, 1.0, 8e-4, 8e-3, 16, 32)
+    crit = ComputeLoss(hc.normal_id, 3, 1.0, 1.0, 1.0, 1.0, 1.0, 8e-4, 8e-3, Lg, N)
     mod = AnomalyCLIPModule(net, None, None, crit, num_classes=hc.num_classes, solver={"lr": 1e-5}).to(dev)
     mod.ncentroid = torch.zeros(512, device=dev)
     opt = mod.configure_optimizers()["optimizer"]
@@ -144,7 +188,10 @@ def main():
         assert world == 1
         eff_world = args.emulate_world
     B_global = args.batch if args.scaling == "strong" else args.batch * eff_world
-    batch, idx = B.head_batch(B_global, eff_world, rank, dev, num_classes=hc.num_classes, normal_id=hc.normal_id)
+    if (N, Lg) == (32, 16):
+        batch, idx = B.head_batch(B_global, eff_world, rank, dev, num_classes=hc.num_classes, normal_id=hc.normal_id)
+    else:
+        batch, idx = grid_batch(B_global, eff_world, rank, dev, N * Lg, hc.num_classes, hc.normal_id)
     if args.emulate_world > 1:
         stub_collectives(eff_world, net)
 
@@ -178,7 +225,7 @@ def main():
         if len(loss_trace) < 4:
             loss_trace.append(mod.last_losses[0].detach().clone())
 
-    x = torch.cat((batch[1][0], batch[0][0]), 0).view(-1, 1, 512, 512)
+    x = torch.cat((batch[1][0], batch[0][0]), 0).view(-1, 1, N * Lg, 512)
 
     def fwd_step():
         with torch.no_grad():
@@ -214,7 +261,7 @@ def main():
     host_ms = (time.perf_counter() - t0) * 1e3
     torch.cuda.synchronize()
     if rank == 0:
-        feats_per_step = B_global * 512
+        feats_per_step = B_global * N * Lg
         print(json.dumps({
             "metric": "features/sec through the head (UCF-Crime shape, 512-d), train step = fwd+loss+bwd+AdamW",
             "train_features_per_s": round(feats_per_step * args.steps / dt_train, 1),
@@ -230,6 +277,8 @@ def main():
             "text_class_parallel": bool(net.text_class_parallel), "text_graph": bool(net.text_graph), "temporal_graph": bool(net.temporal_model.graph),
             "step_graph": bool(net.step_graph) and any(v is not None for v in mod.__dict__.get("_step_graphs", {}).values()),
             "step_graph_error": getattr(mod, "step_graph_error", None),
+            "num_segments": N, "seg_length": Lg, "emb_size": hc.emb_size, "heads": hc.heads, "head_dim": hc.e,
+            "x6_convs": bool(net.temporal_model.x6_convs()),
             "global_batch_videos": B_global, "scaling": args.scaling, "dtype": "f32",
             "loss": float(mod.last_losses[0].detach()), "first_losses": [round(float(v), 6) for v in loss_trace], "data": "synthetic"}))
     if world > 1:
