@@ -160,9 +160,11 @@ struct TfWs {   // transformer scratch carved from the caller's workspace
 
 // the plane modes of the drivers: ACX_PREC_F32X6 (six products: f32-accurate) and ACX_PREC_F32X3 (the three leading products)
 static inline bool is_xmode(int prec) { return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3; }
-static thread_local int tl_x_pairs = 6;          // acx_gemm_desc.pairs of the driver's plane products (set at the driver's entry)
-static thread_local bool tl_x_f16 = false;       // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
-static inline void set_xmode(int prec) { tl_x_pairs = (prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3) ? 3 : 6; tl_x_f16 = prec == ACX_PREC_F16X3; }
+struct XMode {
+  int pairs;                                     // acx_gemm_desc.pairs of the driver's plane products (and the attention's products)
+  bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
+};
+static inline XMode xmode_of(int prec) { return {(prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3) ? 3 : 6, prec == ACX_PREC_F16X3}; }
 
 TfWs carve_tf(char* base, int64_t rows, int W, int prec = ACX_PREC_F32) {
   TfWs w;
@@ -199,7 +201,7 @@ bool x6_takes(acx_ctx* ctx, const TfWs& ws, int64_t M, int N, int K, int lda) {
 // Both operands' planes are in K-PANEL layout (ACX_BF16X3P: the driver's producers -- LayerNorm, the attention, c_fc's epilogue,
 // acx_split_bf16x3_panel -- write it, the caller's weight planes come in it): a 256-row x 32-column unit of the plane-reuse
 // kernel is then ONE contiguous 16 KB block (+5-6 % on the ViT products against row-major planes, profiles/r05_gemm_x6_notes.txt).
-int linear_x6(acx_ctx* ctx, const void* A3, int lda, int64_t a_rows, const void* W3, int64_t w_plane_bytes, int ldw, void* C,
+int linear_x6(acx_ctx* ctx, XMode xm, const void* A3, int lda, int64_t a_rows, const void* W3, int64_t w_plane_bytes, int ldw, void* C,
               int ldc, int M, int N, int K, const float* bias, int act, const float* residual, hipStream_t s, int ldr = 0,
               int c_dtype = ACX_F32, void* tail_ws = nullptr, size_t tail_bytes = 0, const acx_ln_job* ln = nullptr) {
   if (!W3) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
@@ -207,10 +209,10 @@ int linear_x6(acx_ctx* ctx, const void* A3, int lda, int64_t a_rows, const void*
   memset(&d, 0, sizeof(d));
   d.A = A3; d.W = W3; d.C = C;
   d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldw = ldw; d.ldc = ldc;
-  d.a_dtype = tl_x_f16 ? ACX_F16 : ACX_BF16; d.c_dtype = (tl_x_f16 && c_dtype == ACX_BF16X3P) ? ACX_F16X2P : c_dtype; d.prec = ACX_PREC_BF16;
-  d.out_scale = tl_x_f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
+  d.a_dtype = xm.f16 ? ACX_F16 : ACX_BF16; d.c_dtype = (xm.f16 && c_dtype == ACX_BF16X3P) ? ACX_F16X2P : c_dtype; d.prec = ACX_PREC_BF16;
+  d.out_scale = xm.f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
   d.bias = bias; d.act = act; d.residual = residual; d.ldr = ldr ? ldr : ldc;
-  d.pairs = tl_x_pairs; d.a_plane_stride = a_rows * (int64_t)lda * 2; d.w_plane_stride = w_plane_bytes;
+  d.pairs = xm.pairs; d.a_plane_stride = a_rows * (int64_t)lda * 2; d.w_plane_stride = w_plane_bytes;
   d.panels = 3;
   // scratch for the K split of a partly filled last round of tiles (acx_gemm: row-major outputs only)
   d.workspace = tail_ws; d.workspace_bytes = tail_ws ? tail_bytes : 0;
@@ -282,8 +284,8 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
                        const acx_block_weights* blk, const TfWs& ws, hipStream_t s, float* cls_ws = nullptr) {
   const int64_t rows = (int64_t)batch * L;
   const bool x6mode = is_xmode(prec);
+  const XMode xm = xmode_of(prec);
   const int pdt3 = prec == ACX_PREC_F16X3 ? ACX_F16X2P : prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P;   // LayerNorm's plane output
-  const bool f16mode = prec == ACX_PREC_F16X3;
   if (x6mode) prec = ACX_PREC_F32;               // everything that is not one of the four large GEMMs runs as in f32 mode
   const int hdt = prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
   const size_t esz = prec == ACX_PREC_BF16 ? 2 : 4;
@@ -307,7 +309,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
         if (!b.in_proj_w_bf16) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
         if (!ln1_done && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
         if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-        if ((rc = linear_x6(ctx, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
+        if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
                             (float*)ws.qkv + W, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
       } else {
       if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
@@ -348,19 +350,19 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
     const bool att_p3 = x6_qkv && x6_out && ws.qkv3 && !causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
     if (x6_qkv) {
-      if ((rc = linear_x6(ctx, ws.hp, W, rows, b.in_proj_w_bf16, (int64_t)3 * W * W * 2, W, att_p3 ? (void*)ws.qkv3 : (void*)ws.qkv, 3 * W,
+      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.in_proj_w_bf16, (int64_t)3 * W * W * 2, W, att_p3 ? (void*)ws.qkv3 : (void*)ws.qkv, 3 * W,
                           (int)rows, 3 * W, W, b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, att_p3 ? ACX_BF16X3P : ACX_F32,
                           att_p3 ? ws.qkv : ws.h, att_p3 ? (size_t)rows * 3 * W * 4 : (size_t)rows * W * 4))) return rc;   // (free f32 buffers: tail scratch)
     } else
     if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, qdt, 3 * W, (int)rows, 3 * W, W,
                      b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
     const bool att_x3 = x6_out && !causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
-    if (f16mode && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
+    if (xm.f16 && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
       return acx_fail(ctx, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
     if (ab) {
       if ((rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s))) return rc;
     } else if (att_p3) {   // planes in, planes out
-      if ((rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, f16mode ? 103 : tl_x_pairs, s))) return rc;
+      if ((rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, xm.f16 ? 103 : xm.pairs, s))) return rc;
     } else if (att_x3) {   // the attention writes the out-projection's three planes itself
       if ((rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s))) return rc;
     } else {
@@ -371,7 +373,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
       // (ws.h is free here and at c_proj: LayerNorm's output has been consumed, or went to the planes)
       const acx_ln_job ln2 = {b.ln2_w, b.ln2_b, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
       ln2_done = ln_ride && x6_fc;
-      if ((rc = linear_x6(ctx, ws.hp, W, rows, b.out_proj_w_bf16, (int64_t)W * W * 2, W, x, W, (int)rows, W, W, b.out_proj_b,
+      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.out_proj_w_bf16, (int64_t)W * W * 2, W, x, W, (int)rows, W, W, b.out_proj_b,
                           ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln2_done ? &ln2 : nullptr))) return rc;
     } else
     if ((rc = linear(ctx, prec, ws.att, qdt, W, b.out_proj_w, b.out_proj_w_bf16, W, x, ACX_F32, W, (int)rows, W, W,
@@ -383,7 +385,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     if ((rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
     if (x6_fc) {
       // QuickGELU(c_fc) straight into the planes of c_proj's input when c_proj takes the x6 path too
-      if ((rc = linear_x6(ctx, ws.hp, W, rows, b.fc_w_bf16, (int64_t)4 * W * W * 2, W, x6_proj ? (void*)ws.mp : (void*)ws.mlp, 4 * W,
+      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.fc_w_bf16, (int64_t)4 * W * W * 2, W, x6_proj ? (void*)ws.mp : (void*)ws.mlp, 4 * W,
                           (int)rows, 4 * W, W, b.fc_b, ACX_ACT_QUICKGELU, nullptr, s, 0, x6_proj ? ACX_BF16X3P : ACX_F32,
                           x6_proj ? ws.mlp : ws.h, x6_proj ? (size_t)rows * 4 * W * 4 : (size_t)rows * W * 4))) return rc;
     } else
@@ -397,7 +399,7 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
                                                                                   : x6_qkv);
       ln1_done = ln_ride && next_planes;
       const acx_ln_job ln1 = {ln1_done ? blk[l + 1].ln1_w : nullptr, ln1_done ? blk[l + 1].ln1_b : nullptr, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};
-      if ((rc = linear_x6(ctx, ws.mp, 4 * W, rows, b.proj_w_bf16, (int64_t)W * 4 * W * 2, 4 * W, x, W, (int)rows, W, 4 * W, b.proj_b,
+      if ((rc = linear_x6(ctx, xm, ws.mp, 4 * W, rows, b.proj_w_bf16, (int64_t)W * 4 * W * 2, 4 * W, x, W, (int)rows, W, 4 * W, b.proj_b,
                           ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln1_done ? &ln1 : nullptr))) return rc;
     } else
     if ((rc = linear(ctx, prec, ws.mlp, hdt, 4 * W, b.proj_w, b.proj_w_bf16, 4 * W, x, ACX_F32, W, (int)rows, W, 4 * W,
@@ -425,7 +427,6 @@ extern "C" int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, in
   TfWs ws = carve_tf((char*)workspace, (int64_t)batch * L, width, prec);
   if (ws.total > workspace_bytes && is_xmode(prec)) ws = carve_tf((char*)workspace, (int64_t)batch * L, width);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_transformer_forward: workspace too small%s");
-  set_xmode(prec);
   return transformer_layers(ctx, x, batch, L, width, heads, layers, causal, prec, blocks, ws, (hipStream_t)stream);
 }
 
@@ -471,7 +472,7 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_vit_encode: workspace too small%s");
   hipStream_t s = (hipStream_t)stream;
   const int prec = is_xmode(d->prec) ? ACX_PREC_F32 : d->prec;   // final projection (and small launches): f32 kernels
-  set_xmode(d->prec);
+  const XMode xm = xmode_of(d->prec);
   const int pdt = prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
   int rc;
   // conv1 as GEMM over im2col'ed patches                               clip/model.py:267-269
@@ -481,7 +482,7 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
     // like the layers' GEMMs (conv1_w_bf16: the weight's three K-panel planes); scratch for a K-split tail: the f32 q | k | v buffer
     if ((rc = acx_vit_patches(ctx, frames, ws.patches, d->prec == ACX_PREC_F16X3 ? ACX_F16X2P : d->prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P,
                               F, d->resolution, d->patch, s))) return rc;
-    if ((rc = linear_x6(ctx, ws.patches, K, (int64_t)F * T, w->conv1_w_bf16, (int64_t)W * K * 2, K, ws.patch_out, W, F * T, W, K, nullptr,
+    if ((rc = linear_x6(ctx, xm, ws.patches, K, (int64_t)F * T, w->conv1_w_bf16, (int64_t)W * K * 2, K, ws.patch_out, W, F * T, W, K, nullptr,
                         ACX_ACT_NONE, nullptr, s, 0, ACX_F32, tf.qkv, (size_t)F * (T + 1) * 3 * W * 4))) return rc;
   } else {
   // a patch of 14 (K = 588: not a multiple of the bf16 kernels' 8) embeds on the f32 kernels in every mode: ~0.2 % of the MACs

@@ -604,16 +604,10 @@ static int attention_impl(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* 
   }
   if (x3) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_x3: the ViT kernel only (non-causal, 128 < L <= 1024, out 16-byte aligned)%s");
   if (L > 224) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: L > 224 needs the streaming kernel (out 16-byte aligned, ldo %% 4 == 0)%s");
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
 #define ACX_ATTN(NT, NW)                                                                           \
-  do {                                                                                             \
-    const size_t lds = (size_t)NT * 32 * (KROW + VROW) * 4 + NW * 32 * 4 + 16;                          \
-    static bool done = false;                                                                      \
-    if (!done) {                                                                                   \
-      (void)hipFuncSetAttribute((const void*)attn_kernel<NT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      done = true;                                                                                 \
-    }                                                                                              \
-    hipLaunchKernelGGL((attn_kernel<NT, NW>), grid, dim3(NW * 64), lds, s, qkv, ldqkv, out, ldo, L, heads, causal); \
-  } while (0)
+  acx_launch_lds<attn_kernel<NT, NW>>(dev_slot, grid, dim3(NW * 64), (size_t)NT * 32 * (KROW + VROW) * 4 + NW * 32 * 4 + 16, s, \
+                                      qkv, ldqkv, out, ldo, L, heads, causal)
   switch (nt) {
     // one wave per 32-query block where it fits; >4 blocks -> 8 waves (2 per SIMD: one wave's softmax and
     // LDS phases overlap the other's MFMAs)
@@ -982,27 +976,19 @@ extern "C" int acx_attention_p3n(acx_ctx* ctx, const void* qkv_planes, void* out
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_ATTN, s);
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
-  static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_p3_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AP3_LDS_B);
-    (void)hipFuncSetAttribute((const void*)attn_p3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AP3_LDS_B);
-    (void)hipFuncSetAttribute((const void*)attn_p3_kernel<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AP3_LDS_B);
-    attr_done = true;
-  }
 #if AP3_TRACE
   long long* trace_ = getenv("ACX_TRACE_PTR") ? (long long*)strtoull(getenv("ACX_TRACE_PTR"), nullptr, 0) : nullptr;
 #else
   long long* trace_ = nullptr;
 #endif
-  if (f16)
-    hipLaunchKernelGGL((attn_p3_kernel<3, 1>), dim3((unsigned)(nitems < ncu ? nitems : ncu)), dim3(512), (size_t)AP3_LDS_B, s, (const u16*)qkv_planes,
-                       rows * 3 * heads * 64, rows, (u16*)out_planes, rows * heads * 64, L, heads, nitems, trace_);
-  else if (products == 3)
-    hipLaunchKernelGGL(attn_p3_kernel<3>, dim3((unsigned)(nitems < ncu ? nitems : ncu)), dim3(512), (size_t)AP3_LDS_B, s, (const u16*)qkv_planes,
-                       rows * 3 * heads * 64, rows, (u16*)out_planes, rows * heads * 64, L, heads, nitems, trace_);
-  else
-  hipLaunchKernelGGL(attn_p3_kernel<6>, dim3((unsigned)(nitems < ncu ? nitems : ncu)), dim3(512), (size_t)AP3_LDS_B, s, (const u16*)qkv_planes,
-                     rows * 3 * heads * 64, rows, (u16*)out_planes, rows * heads * 64, L, heads, nitems, trace_);
+  const dim3 grid((unsigned)(nitems < ncu ? nitems : ncu));
+#define ACX_AP3(...)                                                                                                     \
+  acx_launch_lds<attn_p3_kernel<__VA_ARGS__>>(dev_slot, grid, dim3(512), (size_t)AP3_LDS_B, s, (const u16*)qkv_planes,   \
+                                              rows * 3 * heads * 64, rows, (u16*)out_planes, rows * heads * 64, L, heads, nitems, trace_)
+  if (f16) ACX_AP3(3, 1);
+  else if (products == 3) ACX_AP3(3);
+  else ACX_AP3(6);
+#undef ACX_AP3
   ACX_CHECK_LAUNCH(ctx, "acx_attention_p3");
   return ACX_OK;
 }
@@ -1203,16 +1189,10 @@ extern "C" int acx_attention_bf16(acx_ctx* ctx, const void* qkv, int64_t ldqkv, 
   const dim3 grid((unsigned)(batch * heads));
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
 #define ACX_ATTNB(NT)                                                                              \
-  do {                                                                                             \
-    const size_t lds = (size_t)NT * 32 * BK_ROWB + 2 * BV_PANEL_B;                                 \
-    static bool done = false;                                                                      \
-    if (!done) {                                                                                   \
-      (void)hipFuncSetAttribute((const void*)attn_bf16_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      done = true;                                                                                 \
-    }                                                                                              \
-    hipLaunchKernelGGL((attn_bf16_kernel<NT>), grid, dim3(256), lds, s, (const u16*)qkv, ldqkv, (u16*)out, ldo, L, heads); \
-  } while (0)
+  acx_launch_lds<attn_bf16_kernel<NT>>(dev_slot, grid, dim3(256), (size_t)NT * 32 * BK_ROWB + 2 * BV_PANEL_B, s, (const u16*)qkv, ldqkv, \
+                                       (u16*)out, ldo, L, heads)
   switch (nt) {
     case 1: ACX_ATTNB(1); break;
     case 2: ACX_ATTNB(2); break;

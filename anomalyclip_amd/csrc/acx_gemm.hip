@@ -33,12 +33,30 @@
 //   * XCD-aware 1-D grid: block b runs on XCD b%8; the bijective remap gives every XCD a
 //     contiguous run of tiles (n fastest) so the A tile of a row of tiles stays in that XCD's L2.
 //
-// Kernel families (all dispatched from acx_gemm / acx_gemm_tn at the bottom of this file):
-//   gemm_kernel<...>         this file   4 waves per tile: every precision / row map / epilogue, split-K
+// Kernel families:
+//   gemm_kernel<...>         this file   4 waves per 128x128 tile: every precision / row map / epilogue, K split over gridDim.y
+//   gemm_f32_s64_kernel      _w8.h       64x64 tiles, four blocks per CU: small branch-free f32 problems (text tower)
+//   gemm_f32_sk_kernel       _sk.h       32x32 tiles, K split over the waves: few-row f32 problems and their fusions
 //   gemm_f32_w8_kernel       _w8.h       8 waves per tile: branch-free f32 problems and the 3x3 convolutions
+//   gemm_f32_p256_kernel     _p256.h     persistent strip stream, one 1024-thread block per CU: big f32 problems without a residual
 //   gemm_bf16_dma_kernel     _bf16.h     bf16 operands, global->LDS DMA staging, 128x128, two blocks per CU
 //   gemm_bf16_ring_kernel    _bf16.h     bf16, persistent 256x256 tiles for the large-M shapes
-//   gemm_tn_kernel / _w8     _tn.h       weight gradients C = A^T B (reduction over rows), split-M + reduce
+//   gemm_bf16_p8_kernel      _p8.h       the ring kernel's tile stream on a phase-interleaved schedule
+//   gemm_x6_p4_kernel        _x6.h       pairs = 6 / 3: products of bf16 / fp16 planes, one wave per SIMD; also acx_gemm_tn_x6
+//   gemm_tn_kernel / _w8 / _p256 / _w8_group  _tn.h   weight gradients C = A^T B (reduction over rows), split-M + reduce
+// (+ the reduce launches of a K split: splitk_reduce_kernel, splitk_reduce4_kernel, tn_reduce_kernel)
+//
+// acx_gemm (gemm_impl below) validates the descriptor, then tries its routes in this order; the first that takes the problem launches:
+//   1. opt-in tail split of a pairs = 6 product (two acx_gemm calls)      route_x6_tail_split
+//   2. few-row f32 problems and the few-row fusions -> gemm_f32_sk_kernel  route_sk
+//   3. pairs = 6 / 3 -> gemm_x6_p4_kernel (plan: x6_plan)                  route_x6
+//   4. small branch-free f32 -> gemm_f32_s64_kernel                        route_s64
+//   5. the K split of the 128x128-tile kernels, decided once             generic_ksplit
+//   6. big f32, no residual, no K split -> gemm_f32_p256_kernel           route_p256
+//   7. f32 branch-free / 3x3 convolutions -> gemm_f32_w8_kernel           route_w8
+//   8. bf16 ring / p8, bf16 DMA convolution, bf16 DMA, gemm_kernel        route_ring, route_dma_conv, route_dma, route_gemm_kernel
+//   9. the reduce launch of a K split                                     splitk_reduce (from the route that split)
+// acx_gemm_tn* (weight gradients) are dispatched at the bottom of this file.
 #include "acx_internal.h"
 #include "acx_ln_rows.h"     // LnRide, ln_ride_rows: the LayerNorm rider of gemm_x6_p4_kernel
 
@@ -617,8 +635,8 @@ static int x6_choose_split(int tiles, int nks, int ncu, size_t image_bytes, size
   return best;
 }
 
-// job != nullptr (acx_gemm_ln): *ridden = the rows 0 .. *ridden of the job's LayerNorm that rode in the product's last round (0: none)
-static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden) {
+// What acx_gemm refuses before it looks for a route (the routes refuse what only they can know)
+static int gemm_validate(acx_ctx* ctx, const acx_gemm_desc* d) {
   if (!d || !d->A || !d->W || !d->C) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: null pointer%s");
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: empty shape%s");
   const int prec = d->prec;
@@ -663,633 +681,640 @@ static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const a
   if (d->act == ACX_ACT_RESRELU && !d->residual)
     return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: ACX_ACT_RESRELU needs a residual%s");
   if (d->act < ACX_ACT_NONE || d->act > ACX_ACT_RESRELU) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: unknown act%s");
+  return ACX_OK;
+}
 
-  // ---- pairs = 6, more 256 x 256 tiles than CUs, a last round that fills only part of the chip (the ViT's N = 768 products: 1182
-  // tiles = 4.6 rounds at 512 frames, 591 = 2.3 at 256): the whole tile rows of the full rounds go out as one launch, the rest
-  // as a second problem on its row range -- fewer tiles than CUs, so its K is split across workgroups and reduced by a launch
-  // that also applies the epilogue (below; plane outputs: acx_gemm_desc.c_plane_rows).  Identity rows, caller-provided workspace; taken when
-  // the split model says >= 1 % (x6_choose_split's units).  Opt-in (ACX_OPT_X6_TAIL_SPLIT): the tail rows sum K in another order than
-  // the rows before them, and the default keeps identical rows of one launch bit-identical.  Decided before the profiling scope:
-  // the two calls are two launches.
-  if (d->pairs == 6 && (d->amap == ACX_AMAP_IDENTITY || d->amap == ACX_AMAP_CONV3X3) && d->workspace && prec == ACX_PREC_BF16 && a_bf16 &&
-      !d->a_sub && !d->pos0 &&
-      d->K % 32 == 0 && ctx && ctx->opt_x6_tail) {
-    int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
-    if (ctx && ctx->opt_x6_cus > 0 && ctx->opt_x6_cus < ncu) ncu = ctx->opt_x6_cus;
-    const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256, xt = tm * tn, nks = d->K / 32;
-    const int rounds = xt / ncu, rem = xt - rounds * ncu;
-    if (rounds >= 1 && rem > 0) {
-      int tm_main = (rounds * ncu) / tn;
-      if (d->amap == ACX_AMAP_CONV3X3) {           // the tail must begin at a token-grid boundary (its taps never leave a grid)
-        const int grid_tiles = (d->gn * d->gl + 255) / 256;
-        tm_main = (d->gn * d->gl) % 256 == 0 ? tm_main / grid_tiles * grid_tiles : 0;
-      }
-      const int xtail = (tm - tm_main) * tn;
-      const int64_t row0 = (int64_t)tm_main * 256, m_tail = d->M - row0;
-      if (tm_main >= 1 && xtail < ncu && m_tail > 0) {
-        double tail_us = 0.0;
-        const int s_tail = x6_choose_split(xtail, nks, ncu, (size_t)m_tail * d->N * sizeof(float), d->workspace_bytes, 6, &tail_us);
-        const double now_us = (rounds + 1) * (nks + 7.0) * 3.0, new_us = rounds * (nks + 7.0) * 3.0 + tail_us + 6.0;
-#ifndef ACX_X6TAIL_THRESH
-#define ACX_X6TAIL_THRESH 0.99
-#endif
-        if (s_tail > 1 && new_us < ACX_X6TAIL_THRESH * now_us) {
-          acx_gemm_desc dm = *d, dt = *d;
-          dm.M = (int)row0; dm.workspace = nullptr; dm.workspace_bytes = 0;
-          const bool apanel = (d->panels & 1) != 0;
-          dt.M = (int)m_tail;
-          dt.A = (const char*)d->A + (apanel ? (size_t)row0 * 64 : (size_t)row0 * d->lda * 2);
-          const bool c_planes = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P;
-          if (c_planes) dm.c_plane_rows = dt.c_plane_rows = d->c_plane_rows ? d->c_plane_rows : (int64_t)d->M;
-          dt.C = (char*)d->C + (d->c_dtype == ACX_BF16X3P ? (size_t)row0 * 32 * 2
-                                                          : (size_t)row0 * d->ldc * (d->c_dtype == ACX_F32 ? 4 : 2));
-          if (d->residual) dt.residual = d->residual + (size_t)row0 * d->ldr;
-          const int rc = gemm_impl(ctx, &dm, stream, nullptr, nullptr);
-          return rc ? rc : gemm_impl(ctx, &dt, stream, nullptr, nullptr);
-        }
-      }
-    }
-  }
+// ---- acx_gemm's host side: gemm_validate, the per-call facts (GemmCall), then one function per kernel route, tried by gemm_impl
+// in the order of the file header.  A route answers ROUTE_NEXT (declined: nothing launched, nothing changed), ACX_OK (launched)
+// or a negative code (refused with acx_fail).  Routes get the launch arguments by value: none sees another's changes.
+constexpr int ROUTE_NEXT = 1;
 
+struct GemmCall {
+  acx_ctx* ctx;
+  const acx_gemm_desc* d;
+  hipStream_t s;
+  int prec;
+  bool a_bf16, a_f16, c_bf16;     // 16-bit A elements (bf16 or fp16 planes), fp16 planes, bf16 C
+  bool fast;                      // identity rows, no a_sub / positional epilogue, whole K-steps, no LeakyReLU: the branch-free kernels
+  bool relu_act;                  // ACX_ACT_RELU / ACX_ACT_RESRELU
+  int dev_slot;                   // index of the context's device in acx_launch_lds's per-device state
+  int ncu, ncu_x6;                // workgroups of a persistent launch; the plane kernel's (ACX_OPT_X6_CUS caps it)
+};
+
+static GemmCall gemm_call(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
+  GemmCall c;
+  c.ctx = ctx; c.d = d; c.s = (hipStream_t)stream;
+  c.prec = d->prec;
+  c.a_f16 = d->a_dtype == ACX_F16;
+  c.a_bf16 = d->a_dtype == ACX_BF16 || c.a_f16;
+  c.c_bf16 = d->c_dtype == ACX_BF16;
+  c.fast = d->amap == ACX_AMAP_IDENTITY && !d->a_sub && !d->pos0 && d->K % (c.prec == ACX_PREC_F32 ? 32 : 64) == 0 &&
+           d->act != ACX_ACT_LEAKYRELU;
+  c.relu_act = d->act == ACX_ACT_RELU || d->act == ACX_ACT_RESRELU;
+  c.dev_slot = (ctx ? ctx->device : 0) & 63;
+  c.ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
+  c.ncu_x6 = ctx && ctx->opt_x6_cus > 0 && ctx->opt_x6_cus < c.ncu ? ctx->opt_x6_cus : c.ncu;
+  return c;
+}
+
+static Args gemm_args(const GemmCall& c) {
   Args g;
-  g.d = *d;
-  const int tiles_m = (d->M + BM - 1) / BM;
-  g.tiles_n = (d->N + BN - 1) / BN;
+  g.d = *c.d;
+  g.tiles_n = (c.d->N + BN - 1) / BN;
 #if ACX_TRACE
   g.trace = getenv("ACX_TRACE_PTR") ? (long long*)strtoull(getenv("ACX_TRACE_PTR"), nullptr, 0) : nullptr;
 #else
   g.trace = nullptr;
 #endif
-  dim3 grid((unsigned)(tiles_m * g.tiles_n)), block(NTHREADS);
   g.ksplit = 1; g.kchunk = 0; g.partial = nullptr; g.counters = nullptr;
   g.tile0 = 0; g.ntiles = 0;
   memset(&g.ln, 0, sizeof(g.ln));
-  g.zeros = (const float*)d->zero_page;
-  const size_t lds = 4 * TILE_B;
-  hipStream_t s = (hipStream_t)stream;
-  AcxProfScope prof__(ctx, ACX_K_GEMM, (hipStream_t)stream);
-  if (ctx && ctx->prof_on) ctx->prof_gemm_flops += 2.0 * d->M * (double)d->N * d->K;
-  // hipFuncSetAttribute is a per-DEVICE setting: the "already done" flags of the launch macros below are indexed by the
-  // context's device, so one process may drive several GPUs
-  const int dev_slot = (ctx ? ctx->device : 0) & 63;
-#define ACX_LAUNCH(P, AB, CB, F, ACT, RES)                                                          \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_kernel<P, AB, CB, F, ACT, RES>,                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_kernel<P, AB, CB, F, ACT, RES>), grid, block, lds, s, g);              \
-  } while (0)
-  const int ke = prec == ACX_PREC_F32 ? 32 : 64;
-  const bool fast = d->amap == ACX_AMAP_IDENTITY && !d->a_sub && !d->pos0 && d->K % ke == 0 &&
-                    d->act != ACX_ACT_LEAKYRELU;
-  const int variant = (prec == ACX_PREC_F32 ? 0 : (a_bf16 ? 1 : 2)) * 2 + c_bf16;   // 0..5
-#define ACX_FAST(P, AB, CB)                                                           \
-  do {                                                                                \
-    if (d->act == ACX_ACT_QUICKGELU) {                                                \
-      if (d->residual) ACX_LAUNCH(P, AB, CB, 1, 1, 1); else ACX_LAUNCH(P, AB, CB, 1, 1, 0); \
-    } else {                                                                          \
-      if (d->residual) ACX_LAUNCH(P, AB, CB, 1, 0, 1); else ACX_LAUNCH(P, AB, CB, 1, 0, 0); \
-    }                                                                                 \
-  } while (0)
-  // few-row f32 problems (and every problem that asks for the few-row fusions): 32x32 tiles, K split over the waves
-  {
-    const bool a_norm = d->a_norm_w != nullptr;
-    const bool sk_fusion = d->a_act != ACX_ACT_NONE || d->gelu_grad_of != nullptr || a_norm;
-    const bool sk_ok = fast && prec == ACX_PREC_F32 && !c_bf16 && !a_bf16 && d->K % SK_CH == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 &&
-                       !((uintptr_t)d->C & 15) && (!d->residual || (d->ldr % 4 == 0 && !((uintptr_t)d->residual & 15))) &&
-                       (!d->gelu_grad_of || (d->ldg % 4 == 0 && !((uintptr_t)d->gelu_grad_of & 15) && !d->residual &&
-                                             d->act == ACX_ACT_NONE)) &&
-                       !(d->act == ACX_ACT_QUICKGELU && d->residual) && !relu_act &&
-                       (d->a_act == ACX_ACT_NONE || d->a_act == ACX_ACT_QUICKGELU) &&
-                       (size_t)d->M * d->lda < ((size_t)1 << 31) && (size_t)d->N * d->ldw < ((size_t)1 << 31);
-    if (sk_fusion && !sk_ok)
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_act / gelu_grad_of / a_norm need the few-row f32 kernel (see acx_gemm_desc)%s");
-    if (a_norm && (d->K != 512 || !d->a_norm_b || d->a_act != ACX_ACT_NONE || d->residual || d->gelu_grad_of || d->act != ACX_ACT_NONE ||
-                   (((uintptr_t)d->a_norm_w | (uintptr_t)d->a_norm_b) & 15)))
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_norm needs K == 512, weight and bias, and no other fusion%s");
-    // narrow outputs (N <= 512: out-proj, proj and the dX chain of the text tower) stay ahead of the 64x64-tile kernel up to
-    // ~1300 rows -- 17-34 row tiles x 16 column tiles fill the chip where 64x64 tiles leave half of it idle
-    // (profiles/r03_text_gemm.txt); wide outputs only up to the row limit
-    const int sk_max_m = ctx ? ctx->opt_sk_max_m : ACX_SK_MAX_M;
-    // ... except long K at more than ~770 rows when the caller brought a split-K workspace: the 64x64 kernel with K split 2-4
-    // ways is ahead there (1078 rows, N = 512: K = 2048 37.1 vs 43.5 us, K = 1536 30.0 vs 33.2 us; at 539 rows it is not)
-    const bool sk_narrow = sk_max_m > 0 && d->N <= 512 && d->M <= 4 * sk_max_m && !(d->workspace && d->M > 768 && d->K >= 1536);
-    if (sk_ok && (sk_fusion || d->M <= sk_max_m || sk_narrow)) {
-      dim3 kgrid((unsigned)(((d->M + 31) / 32) * ((d->N + 31) / 32)));
-      // long K on few tiles: pieces of two chunks (512 floats = resident in one DMA burst) across workgroups, when the caller
-      // brought the partial workspace and the arrival counters
-      g.counters = (unsigned int*)d->counters;
-      if (d->workspace && d->counters && d->K >= 1024 && d->K % 512 == 0) {
-        const int pieces = d->K / 512;
-        if ((int)kgrid.x * pieces <= 512 && (int)kgrid.x <= d->n_counters &&
-            (size_t)pieces * kgrid.x * 4096 <= d->workspace_bytes && !((uintptr_t)d->workspace & 15)) {
-          g.ksplit = pieces;
-          g.kchunk = 2;
-          g.partial = (float*)d->workspace;
-          kgrid.y = (unsigned)pieces;
-        }
-      }
-#define ACX_SKL(E, AG)                                                                              \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_f32_sk_kernel<E, AG>,                             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_LDS_B);         \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_f32_sk_kernel<E, AG>), kgrid, dim3(512), (size_t)SK_LDS_B, s, g);      \
-  } while (0)
-      if (a_norm) {
-        static bool attrn_dev_[64] = {}; bool& attrn_done = attrn_dev_[dev_slot];
-        if (!attrn_done) {
-          (void)hipFuncSetAttribute((const void*)gemm_f32_sk_kernel<SK_EPI_PLAIN, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)SK_LDS_B);
-          attrn_done = true;
-        }
-        hipLaunchKernelGGL((gemm_f32_sk_kernel<SK_EPI_PLAIN, 0, 1>), kgrid, dim3(512), (size_t)SK_LDS_B, s, g);
-        ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-        return ACX_OK;
-      }
-      const int epi = d->gelu_grad_of ? SK_EPI_GELUGRAD : d->residual ? SK_EPI_RES : d->act == ACX_ACT_QUICKGELU ? SK_EPI_QUICKGELU : SK_EPI_PLAIN;
-      if (d->a_act == ACX_ACT_QUICKGELU) {
-        switch (epi) {
-          case SK_EPI_PLAIN: ACX_SKL(SK_EPI_PLAIN, 1); break;
-          case SK_EPI_QUICKGELU: ACX_SKL(SK_EPI_QUICKGELU, 1); break;
-          case SK_EPI_RES: ACX_SKL(SK_EPI_RES, 1); break;
-          default: ACX_SKL(SK_EPI_GELUGRAD, 1); break;
-        }
-      } else {
-        switch (epi) {
-          case SK_EPI_PLAIN: ACX_SKL(SK_EPI_PLAIN, 0); break;
-          case SK_EPI_QUICKGELU: ACX_SKL(SK_EPI_QUICKGELU, 0); break;
-          case SK_EPI_RES: ACX_SKL(SK_EPI_RES, 0); break;
-          default: ACX_SKL(SK_EPI_GELUGRAD, 0); break;
-        }
-      }
-#undef ACX_SKL
-      ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-      return ACX_OK;
-    }
+  g.zeros = (const float*)c.d->zero_page;
+  return g;
+}
+
+// A K split over gridDim.y (or over the plane kernel's work items): pieces of `kchunk` K-steps, partial sums in `partial`
+struct KSplit {
+  int ksplit = 1, kchunk = 0;
+  float* partial = nullptr;
+  void into(Args& g) const { g.ksplit = ksplit; g.kchunk = kchunk; g.partial = partial; }
+};
+static KSplit ksplit_even(int nkt, int split, void* workspace) {
+  KSplit k;
+  k.kchunk = (nkt + split - 1) / split;
+  k.ksplit = (nkt + k.kchunk - 1) / k.kchunk;
+  k.partial = (float*)workspace;
+  return k;
+}
+
+// The launch that sums a K split's partial images in fixed order and applies the epilogue.  vec4: four columns per lane (the
+// plane kernel's outputs: N, ldc, ldr multiples of 4, 16-byte aligned bias / residual / C, no positional epilogue)
+static void splitk_reduce(const GemmCall& c, const float* partial, int ksplit, bool vec4) {
+  const acx_gemm_desc* d = c.d;
+  if (vec4) {
+    const int64_t total4 = (int64_t)d->M * (d->N / 4);
+    const dim3 rgrid((unsigned)((total4 + 255) / 256));
+    const bool c_x3 = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
+    if (c_x3) hipLaunchKernelGGL((splitk_reduce4_kernel<2>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+    else if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce4_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+    else hipLaunchKernelGGL((splitk_reduce4_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+    return;
   }
-  // ---- pairs = 6 (f32-accurate product from three bf16 planes per operand): the one-wave-per-SIMD plane-reuse kernel
-  // (acx_gemm_x6.h) -- identity rows or the implicit 3x3 convolution; K split across workgroups when the tiles alone
-  // would not fill the chip (caller-provided workspace)
-  if ((d->pairs == 6 || d->pairs == 3) && ACX_DBG_SWITCH("X6P4", true)) {
-    const bool conv = d->amap == ACX_AMAP_CONV3X3;
-    const bool x3 = d->pairs == 3;               // the three leading products only (acx_gemm_x6.h, X3): identity rows
-    if (x3 && (conv || c_bf16 || d->act == ACX_ACT_LEAKYRELU))
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 3 takes identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues%s");
-    const bool c_x3_ = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
-    if (a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P)
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: fp16 operand planes write fp16 output planes (ACX_F16X2P)%s");
-    const bool shape_ok = prec == ACX_PREC_BF16 && a_bf16 && (d->amap == ACX_AMAP_IDENTITY || conv) && !d->a_sub && !d->pos0 &&
-        d->K % 32 == 0 && d->lda % 8 == 0 && d->ldw % 8 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
-        !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && d->a_plane_stride > 0 && d->w_plane_stride > 0 &&
-        !((d->a_plane_stride | d->w_plane_stride) & 15) && (size_t)d->M * d->lda * 2 < ((size_t)1 << 32) &&
-        (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && !(d->act == ACX_ACT_QUICKGELU && d->residual) &&
-        !(d->act == ACX_ACT_LEAKYRELU && d->residual) && !(c_x3_ && (d->residual || d->N % 8 || d->ldc % 8)) && !(c_bf16 && d->residual) &&
-        (!d->panels || (!conv && d->K % 32 == 0 && d->lda == d->K && d->ldw == d->K)) && ((d->c_dtype != ACX_BF16X3P && d->c_dtype != ACX_F16X2P) || d->ldc == d->N) &&
-        (!conv || (d->zero_page && !((uintptr_t)d->zero_page & 15) && d->cin % 32 == 0 && !(d->gl & (d->gl - 1)) &&
-                   !(d->gn & (d->gn - 1)) && d->M % 256 == 0));
-    if (shape_ok) {
-      int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
-      if (ctx && ctx->opt_x6_cus > 0 && ctx->opt_x6_cus < ncu) ncu = ctx->opt_x6_cus;   // ACX_OPT_X6_CUS
-      // narrow convolution outputs (N <= 128: c2 and the input gradient of c1 in the XD-Violence head, E = 128): 256 x 128 tiles
-      // (the NI = 2 instantiation) instead of half-empty 256 x 256 ones; f32 outputs without an activation only (what the head asks for)
-      const bool narrow = conv && d->N <= 128 && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE;
-      const int xt = ((d->M + 255) / 256) * (narrow ? 1 : (d->N + 255) / 256);
-      const int nks = d->K / 32;
-      int split = 1;
-      double split_us = 0.0;
-      if (d->workspace && xt < ncu && !(a_f16 && c_x3_))   // (no reduce launch writes fp16 planes: such launches keep whole K per tile)
-        split = x6_choose_split(xt, nks, ncu, (size_t)d->M * d->N * sizeof(float), d->workspace_bytes, 6, &split_us);
-      // A partly filled LAST round of tiles (N = 768 at 256 frames: 591 tiles = 2.3 rounds of 256 CUs) is cut into column STRIPS:
-      // the full rounds go out as whole tiles, the remaining `rem` tiles as 2 rem strips of 128 columns or 4 rem strips of 64
-      // (the NI = 2 / 1 instantiations, acx_gemm_x6.h) when that makes the last round shorter.  Strips leave every row's K order
-      // and product order untouched -- results are bit-identical to whole tiles (test_gemm_x6_strip_tail_bit_identical) -- so
-      // identical rows of one launch stay identical wherever they sit, which the K split of the tail (ACX_OPT_X6_TAIL_SPLIT) gave up.
-      // Cost of a strip relative to a whole tile: measured (profiles/r06_x6_strip_tail.txt).  Fewer tiles than workgroups: strips
-      // compete with the K split by the same cost model (x6_choose_split's units).
-      int strip_ni = 4, tile0_tail = 0, rem_tail = 0;
-      if (!conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && x6_strip_enabled(ctx)) {
-        const int rounds = xt / ncu, rem = xt - rounds * ncu;
-        if (rem > 0) {
-          double best = 0.0;
-          const int pick = x6_strip_pick(rem, ncu, &best);
-          const int force = ctx ? ctx->opt_x6_strip : 1;    // 2 / 3: always 128- / 64-column strips (measurements)
-          const double strip_us = (rounds + best) * (nks + 4.0) * 3.0;
-          if (force >= 2) { strip_ni = force == 2 ? 2 : 1; tile0_tail = rounds * ncu; rem_tail = rem; }
-          else if (best < X6_STRIP_MAX_COST && (split == 1 || (strip_us < split_us && !(ctx && ctx->opt_x6_tail)))) { strip_ni = pick; tile0_tail = rounds * ncu; rem_tail = rem; }
-          if (strip_ni < 4) split = 1;
-        }
-      }
-      g.ksplit = split; g.kchunk = (nks + split - 1) / split; g.partial = split > 1 ? (float*)d->workspace : nullptr;
-      // LayerNorm riders (acx_gemm_ln): the residual product's last round -- whole tiles or strips, fewer items than workgroups, no K
-      // split -- goes out as a launch of its own on ncu workgroups; those without an item normalise rows the full rounds completed
-      long long ride = 0;
-      int ride_tile0 = 0, ride_rem = 0;           // whole-tile last round of a riding launch (strip_ni == 4): tiles ride_tile0 .. + ride_rem
-      if (job && ridden && !conv && !x3 && split == 1 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
-          (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && job->y_dtype == ACX_BF16X3P && job->w && job->b && job->y &&
-          !((uintptr_t)job->y & 15) && !(((long long)d->M * d->N * 2) & 15) && ACX_DBG_SWITCH("LN_RIDER", true) && ctx && ctx->opt_ln_rider) {
-        const int rounds = xt / ncu, rem = xt - rounds * ncu;
-        const int t0 = strip_ni < 4 ? tile0_tail : rounds * ncu;
-        const int tail_items = strip_ni < 4 ? rem_tail * (4 / strip_ni) : rem;
-        if (rounds >= 1 && rem > 0 && tail_items < ncu) {
-          ride = x6_ride_rows(d->M, d->N, d->N / 256, t0, ncu - tail_items, nks, strip_ni, 0.0);
-          if (ctx->opt_ln_rider > 1) {             // (measurements: ride up to this many of the completed rows)
-            const long long ready = x6_ride_rows(d->M, d->N, d->N / 256, t0, ncu - tail_items, nks, strip_ni, 1e30);
-            ride = (ctx->opt_ln_rider < ready ? ctx->opt_ln_rider : ready) & ~1ll;
-          }
-          if (ride > 0 && strip_ni == 4) { ride_tile0 = t0; ride_rem = rem; }
-        }
-      }
-      if (ride > 0) {
-        g.ln.x = (const float*)d->C; g.ln.w = job->w; g.ln.b = job->b; g.ln.y = (u16*)job->y;
-        g.ln.ldx = d->ldc; g.ln.rows = d->M; g.ln.row0 = 0; g.ln.nrows = ride;
-        g.ln.eps = job->eps; g.ln.mode = job->mode; g.ln.vpl = d->N / 64;
-        *ridden = ride;
-      }
-      const int items = (strip_ni < 4 ? tile0_tail : ride_rem ? ride_tile0 : xt) * split;
-      const dim3 xgrid((unsigned)(items < ncu ? items : ncu));
-      if (strip_ni < 4) { g.tile0 = 0; g.ntiles = tile0_tail; }
-      else if (ride_rem) { g.tile0 = 0; g.ntiles = ride_tile0; }
-#define ACX_X6L_(CM, ACT, RES, CV, NI_, GRID)                                                        \
-  do {                                                                                              \
-    if constexpr ((CV) == 0 && (CM) != 1 && (ACT) != 2) {   /* (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual) */ \
-      if (x3 && a_f16) {                                                                            \
-        static bool attr4_dev_[64] = {}; bool& attr4_done = attr4_dev_[dev_slot];                   \
-        if (!attr4_done) {                                                                          \
-          (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI_, 0, 2>, \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);     \
-          attr4_done = true;                                                                        \
-        }                                                                                           \
-        hipLaunchKernelGGL((gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI_, 0, 2>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
-        break;                                                                                      \
-      }                                                                                             \
-      if (x3) {                                                                                     \
-        static bool attr3_dev_[64] = {}; bool& attr3_done = attr3_dev_[dev_slot];                   \
-        if (!attr3_done) {                                                                          \
-          (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI_, 0, 1>, \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);     \
-          attr3_done = true;                                                                        \
-        }                                                                                           \
-        hipLaunchKernelGGL((gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI_, 0, 1>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
-        break;                                                                                      \
-      }                                                                                             \
-    }                                                                                               \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                          \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI_>,        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);         \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI_>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
-  } while (0)
-#define ACX_X6R(NI_, GRID)                                                                           \
-  do {                                                                                              \
-    static bool attrr_dev_[64] = {}; bool& attrr_done = attrr_dev_[dev_slot];                       \
-    if (!attrr_done) {                                                                              \
-      (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI_, 0, 0, 1>,     \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);         \
-      attrr_done = true;                                                                            \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI_, 0, 0, 1>), GRID, dim3(256), (size_t)X6_LDS_B, s, g); \
-  } while (0)
-#define ACX_X6L(CM, ACT, RES, CV) do { if (items > 0) ACX_X6L_(CM, ACT, RES, CV, 4, xgrid); } while (0)
-#define ACX_X6SEL(CV)                                                                               \
-  do {                                                                                              \
-    if (split > 1) ACX_X6L(0, 0, 0, CV);                                                            \
-    else if (c_x3_) { if (d->act == ACX_ACT_QUICKGELU) ACX_X6L(2, 1, 0, CV); else if (d->act == ACX_ACT_LEAKYRELU) ACX_X6L(2, 2, 0, CV); else ACX_X6L(2, 0, 0, CV); } \
-    else if (c_bf16) { if (d->act == ACX_ACT_QUICKGELU) ACX_X6L(1, 1, 0, CV); else if (d->act == ACX_ACT_LEAKYRELU) ACX_X6L(1, 2, 0, CV); else ACX_X6L(1, 0, 0, CV); } \
-    else if (d->residual) ACX_X6L(0, 0, 1, CV);                                                     \
-    else if (d->act == ACX_ACT_QUICKGELU) ACX_X6L(0, 1, 0, CV);                                     \
-    else if (d->act == ACX_ACT_LEAKYRELU) ACX_X6L(0, 2, 0, CV);                                     \
-    else ACX_X6L(0, 0, 0, CV);                                                                      \
-  } while (0)
-      if (narrow) { if (d->residual && split == 1) ACX_X6L_(0, 0, 1, 1, 2, xgrid); else ACX_X6L_(0, 0, 0, 1, 2, xgrid); }
-      else if (conv) ACX_X6SEL(1);
-      else ACX_X6SEL(0);
-      if (strip_ni < 4) {
-        // the strips of the last round: identity rows only; epilogues of the ViT's products (plane outputs with / without QuickGELU,
-        // f32 with a residual / QuickGELU / plain) -- anything else keeps whole tiles (x6_strip_epilogue_ok)
-        g.tile0 = tile0_tail * (4 / strip_ni); g.ntiles = rem_tail * (4 / strip_ni);   // (in the strips' own numbering: N % 256 == 0)
-        const int sitems = rem_tail * (4 / strip_ni);
-        const dim3 sgrid((unsigned)(ride > 0 || sitems >= ncu ? ncu : sitems));
-        if (ride > 0) {                           // (eligibility above: the f32 residual epilogue)
-          if (strip_ni == 2) ACX_X6R(2, sgrid); else ACX_X6R(1, sgrid);
-        } else
-#define ACX_X6S(NI_)                                                                                 \
-  do {                                                                                              \
-    if (c_x3_) { if (d->act == ACX_ACT_QUICKGELU) ACX_X6L_(2, 1, 0, 0, NI_, sgrid); else ACX_X6L_(2, 0, 0, 0, NI_, sgrid); } \
-    else if (d->residual) ACX_X6L_(0, 0, 1, 0, NI_, sgrid);                                         \
-    else if (d->act == ACX_ACT_QUICKGELU) ACX_X6L_(0, 1, 0, 0, NI_, sgrid);                         \
-    else ACX_X6L_(0, 0, 0, 0, NI_, sgrid);                                                          \
-  } while (0)
-        if (strip_ni == 2) ACX_X6S(2); else ACX_X6S(1);
-#undef ACX_X6S
-      } else if (ride_rem) {
-        g.tile0 = ride_tile0; g.ntiles = ride_rem;
-        ACX_X6R(4, dim3((unsigned)ncu));
-      }
-#undef ACX_X6R
-#undef ACX_X6SEL
-#undef ACX_X6L
-#undef ACX_X6L_
-      if (split > 1) {
-        // (shape_ok: N, ldc, ldr multiples of 4, 16-byte aligned bias / residual / C, no positional epilogue)
-        const int64_t total4 = (int64_t)d->M * (d->N / 4);
-        const dim3 rgrid((unsigned)((total4 + 255) / 256));
-        if (c_x3_) hipLaunchKernelGGL((splitk_reduce4_kernel<2>), rgrid, dim3(256), 0, s, (const float*)g.partial, split, *d);
-        else if (c_bf16) hipLaunchKernelGGL((splitk_reduce4_kernel<1>), rgrid, dim3(256), 0, s, (const float*)g.partial, split, *d);
-        else hipLaunchKernelGGL((splitk_reduce4_kernel<0>), rgrid, dim3(256), 0, s, (const float*)g.partial, split, *d);
-      }
-      ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-      return ACX_OK;
-    }
-    if (conv) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3 needs a power-of-two grid, cin %% 32 == 0, M %% 256 == 0, a zero page and 16-byte aligned planes%s");
+  const int64_t total = (int64_t)d->M * d->N;
+  const dim3 rgrid((unsigned)((total + 255) / 256));
+  if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+  else hipLaunchKernelGGL((splitk_reduce_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+}
+
+// ---- the plane kernel's plan (pairs = 6 / 3): a pure function of the shape, the workgroup count and what the call allows
+struct X6PlanIn {
+  int M, N, K, ncu;
+  bool narrow;                    // 256 x 128 tiles, one per row block (N <= 128)
+  bool may_split;                 // a K split across workgroups is possible (workspace; a reduce launch exists for the output)
+  size_t workspace_bytes;
+  bool may_strip;                 // column strips are possible (identity rows, N % 256 == 0, a strip epilogue, switch on)
+  int strip_force;                // ACX_OPT_X6_STRIP_TAIL: 2 / 3 = always 128- / 64-column strips (measurements)
+  bool tail_split_opt;            // ACX_OPT_X6_TAIL_SPLIT is on: a K split wins over strips
+  bool may_ride;                  // LayerNorm rows may ride in the last round (acx_gemm_ln's eligible products)
+  long long ride_cap;             // ACX_OPT_LN_RIDER: > 1 = ride up to this many of the completed rows (measurements)
+  double rate;                    // rows of 768 columns per us and rider (<= 0: X6_RIDE_ROWS_PER_US_CU)
+};
+struct X6Plan {
+  int xt, nks;                    // whole tiles, K-steps
+  int split;                      // K pieces per tile (1: none)
+  int strip_ni, tile0_tail, rem_tail;   // strip_ni < 4: tiles tile0_tail .. + rem_tail go out as strips of 64 strip_ni columns
+  long long ride, ready;          // LayerNorm rows that ride (0: none); rows the full rounds complete
+  int ride_tile0, ride_rem;       // whole-tile last round of a riding launch (strip_ni == 4): tiles ride_tile0 .. + ride_rem
+  int main_items, main_grid;      // first launch: work items (0: no such launch) and workgroups
+  int tail_items, tail_grid;      // second launch (strips, or the riding whole-tile round): the same
+};
+static X6Plan x6_plan(const X6PlanIn& in) {
+  X6Plan p = {};
+  const int ncu = in.ncu;
+  p.xt = ((in.M + 255) / 256) * (in.narrow ? 1 : (in.N + 255) / 256);
+  p.nks = in.K / 32;
+  p.split = 1;
+  double split_us = 0.0;
+  if (in.may_split && p.xt < ncu)
+    p.split = x6_choose_split(p.xt, p.nks, ncu, (size_t)in.M * in.N * sizeof(float), in.workspace_bytes, 6, &split_us);
+  const int rounds = p.xt / ncu, rem = p.xt - rounds * ncu;
+  // A partly filled LAST round of tiles (N = 768 at 256 frames: 591 tiles = 2.3 rounds of 256 CUs) is cut into column STRIPS:
+  // the full rounds go out as whole tiles, the remaining `rem` tiles as 2 rem strips of 128 columns or 4 rem strips of 64
+  // (the NI = 2 / 1 instantiations, acx_gemm_x6.h) when that makes the last round shorter.  Strips leave every row's K order
+  // and product order untouched -- results are bit-identical to whole tiles (test_gemm_x6_strip_tail_bit_identical) -- so
+  // identical rows of one launch stay identical wherever they sit, which the K split of the tail (ACX_OPT_X6_TAIL_SPLIT) gave up.
+  // Cost of a strip relative to a whole tile: measured (profiles/r06_x6_strip_tail.txt).  Fewer tiles than workgroups: strips
+  // compete with the K split by the same cost model (x6_choose_split's units).
+  p.strip_ni = 4;
+  if (in.may_strip && rem > 0) {
+    double best = 0.0;
+    const int pick = x6_strip_pick(rem, ncu, &best);
+    const double strip_us = (rounds + best) * (p.nks + 4.0) * 3.0;
+    if (in.strip_force >= 2) p.strip_ni = in.strip_force == 2 ? 2 : 1;
+    else if (best < X6_STRIP_MAX_COST && (p.split == 1 || (strip_us < split_us && !in.tail_split_opt))) p.strip_ni = pick;
+    if (p.strip_ni < 4) { p.tile0_tail = rounds * ncu; p.rem_tail = rem; p.split = 1; }
   }
-  const bool w8_conv = d->amap == ACX_AMAP_CONV3X3 && !d->a_sub && !d->pos0 && d->K % 32 == 0 && d->cin % 32 == 0 &&
-                       prec == ACX_PREC_F32 && !c_bf16 && !a_bf16;
-  // small branch-free f32 problems (text tower): 64x64 tiles, four blocks per CU, no split-K
-  const bool s64 = ACX_DBG_SWITCH("S64", true);
-  const int st_m = (d->M + 63) / 64, st_n = (d->N + 63) / 64;
-  if (s64 && fast && prec == ACX_PREC_F32 && !c_bf16 && !a_bf16 && tiles_m * g.tiles_n <= 256 && st_m * st_n >= 96) {
-    const size_t lds_s = 4 * TILE_S;
-    dim3 sgrid((unsigned)(st_m * st_n));
-    // long K on few tiles (text tower: N = 512, K = 1536 / 2048 at 539-1078 rows = 72-136 tiles of 48-64 serial K-steps):
-    // split K so that the launch covers the chip about twice, at least 16 K-steps per piece
-    if (d->workspace && st_m * st_n <= 256 && d->K >= 1024) {
-      int split = 1;
-      const int nkt = d->K / 32;
-      while (st_m * st_n * split * 2 <= 1100 && nkt / (split * 2) >= 12 && split < 8) split *= 2;
-      if (split > 1 && (size_t)split * d->M * d->N * sizeof(float) <= d->workspace_bytes) {
-        g.kchunk = (nkt + split - 1) / split;
-        g.ksplit = (nkt + g.kchunk - 1) / g.kchunk;
-        g.partial = (float*)d->workspace;
-        sgrid.y = (unsigned)g.ksplit;
-      }
-    }
-#define ACX_S64L(ACT, RES)                                                                          \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_f32_s64_kernel<ACT, RES>,                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);            \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_f32_s64_kernel<ACT, RES>), sgrid, dim3(256), lds_s, s, g);             \
-  } while (0)
-    if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_S64L(1, 1); else ACX_S64L(1, 0); }
-    else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_S64L(3, 1); else ACX_S64L(3, 0); }
-    else if (d->act == ACX_ACT_RESRELU) ACX_S64L(4, 1);
-    else { if (d->residual) ACX_S64L(0, 1); else ACX_S64L(0, 0); }
-#undef ACX_S64L
-    if (g.ksplit > 1) {
-      const int64_t total = (int64_t)d->M * d->N;
-      hipLaunchKernelGGL((splitk_reduce_kernel<0>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)g.partial,
-                         g.ksplit, *d);
-    }
-    ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-    return ACX_OK;
+  // LayerNorm riders (acx_gemm_ln): the residual product's last round -- whole tiles or strips, fewer items than workgroups, no K
+  // split -- goes out as a launch of its own on ncu workgroups; those without an item normalise rows the full rounds completed
+  const int last_items = p.strip_ni < 4 ? rem * (4 / p.strip_ni) : rem;
+  if (in.may_ride && p.split == 1 && rounds >= 1 && rem > 0 && last_items < ncu) {
+    const int t0 = rounds * ncu, tiles_n = in.N / 256;
+    p.ready = x6_ride_rows(in.M, in.N, tiles_n, t0, ncu - last_items, p.nks, p.strip_ni, 1e30);
+    p.ride = in.ride_cap > 1 ? (in.ride_cap < p.ready ? in.ride_cap : p.ready) & ~1ll
+                             : x6_ride_rows(in.M, in.N, tiles_n, t0, ncu - last_items, p.nks, p.strip_ni, in.rate);
+    if (p.ride > 0 && p.strip_ni == 4) { p.ride_tile0 = t0; p.ride_rem = rem; }
   }
-  const bool w8 = ACX_DBG_SWITCH("W8", true);   // ACX_W8=0 (debug builds) keeps the 4-wave kernels
-  // ... and f32 problems on the generic row-mapped path (a_sub / positional epilogue / test tilings: the temporal model's input
-  // projection, 64 tiles at a data-parallel rank's 4096 rows = a quarter of the chip for 59 us): same split, same reduce
-  const bool gen_split = !fast && prec == ACX_PREC_F32 && !a_bf16 && !c_bf16 && d->amap != ACX_AMAP_CONV3X3 && d->K % ke == 0 &&
-                         d->act != ACX_ACT_LEAKYRELU;
-  if ((fast || (w8_conv && w8) || gen_split) && d->workspace) {
-    // skinny problems (few tiles, long K): split K over gridDim.y so the chip is filled; partial sums are
-    // combined in fixed order by splitk_reduce_kernel together with the epilogue
-    const int tiles = tiles_m * g.tiles_n, nkt = d->K / ke;
-    int split = 1;
-    // bf16 pieces keep >= 8 K-steps: at the XD text tower's 539 rows x K = 512 a 2-way split + its 5 us reduce launch is
-    // slower than the unsplit launch (head step 1.64 -> 1.51 ms); 16 is worse again (1.59)
-    while (tiles * split * 2 <= 512 && nkt / (split * 2) >= (prec == ACX_PREC_BF16 ? 8 : 4) && split < 16) split *= 2;
-    if (split > 1 && (size_t)split * d->M * d->N * sizeof(float) <= d->workspace_bytes) {
-      g.ksplit = split;
-      g.kchunk = (nkt + split - 1) / split;
-      g.ksplit = (nkt + g.kchunk - 1) / g.kchunk;
+  p.main_items = (p.strip_ni < 4 ? p.tile0_tail : p.ride_rem ? p.ride_tile0 : p.xt) * p.split;
+  p.main_grid = p.main_items < ncu ? p.main_items : ncu;
+  p.tail_items = p.strip_ni < 4 ? last_items : p.ride_rem;
+  p.tail_grid = p.ride > 0 || p.tail_items >= ncu ? ncu : p.tail_items;
+  return p;
+}
+
+// What the plane kernel and the opt-in tail split both ask of the operands: bf16 / fp16 planes, identity or CONV3X3 rows, whole K-steps
+static bool x6_operands_ok(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  return c.prec == ACX_PREC_BF16 && c.a_bf16 && (d->amap == ACX_AMAP_IDENTITY || d->amap == ACX_AMAP_CONV3X3) && !d->a_sub && !d->pos0 &&
+         d->K % 32 == 0;
+}
+
+static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden);
+
+// ---- route 1, opt-in (ACX_OPT_X6_TAIL_SPLIT): pairs = 6, more 256 x 256 tiles than CUs, a last round that fills only part of
+// the chip (the ViT's N = 768 products: 1182 tiles = 4.6 rounds at 512 frames, 591 = 2.3 at 256): the whole tile rows of the full
+// rounds go out as one acx_gemm, the rest as a second one on its row range -- fewer tiles than CUs, so its K is split across
+// workgroups and reduced by a launch that also applies the epilogue (plane outputs: acx_gemm_desc.c_plane_rows).  Caller-provided
+// workspace; taken when the split model says >= 1 % (x6_choose_split's units).  Opt-in: the tail rows sum K in another order than
+// the rows before them, and the default keeps identical rows of one launch bit-identical.
+#ifndef ACX_X6TAIL_THRESH
+#define ACX_X6TAIL_THRESH 0.99
+#endif
+static int route_x6_tail_split(const GemmCall& c) {
+  acx_ctx* ctx = c.ctx;
+  const acx_gemm_desc* d = c.d;
+  if (!(d->pairs == 6 && d->workspace && ctx && ctx->opt_x6_tail && x6_operands_ok(c))) return ROUTE_NEXT;
+  const int ncu = c.ncu_x6;
+  const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256, xt = tm * tn, nks = d->K / 32;
+  const int rounds = xt / ncu, rem = xt - rounds * ncu;
+  if (rounds < 1 || rem == 0) return ROUTE_NEXT;
+  int tm_main = (rounds * ncu) / tn;
+  if (d->amap == ACX_AMAP_CONV3X3) {           // the tail must begin at a token-grid boundary (its taps never leave a grid)
+    const int grid_tiles = (d->gn * d->gl + 255) / 256;
+    tm_main = (d->gn * d->gl) % 256 == 0 ? tm_main / grid_tiles * grid_tiles : 0;
+  }
+  const int xtail = (tm - tm_main) * tn;
+  const int64_t row0 = (int64_t)tm_main * 256, m_tail = d->M - row0;
+  if (tm_main < 1 || xtail >= ncu || m_tail <= 0) return ROUTE_NEXT;
+  double tail_us = 0.0;
+  const int s_tail = x6_choose_split(xtail, nks, ncu, (size_t)m_tail * d->N * sizeof(float), d->workspace_bytes, 6, &tail_us);
+  const double now_us = (rounds + 1) * (nks + 7.0) * 3.0, new_us = rounds * (nks + 7.0) * 3.0 + tail_us + 6.0;
+  if (s_tail <= 1 || new_us >= ACX_X6TAIL_THRESH * now_us) return ROUTE_NEXT;
+  acx_gemm_desc dm = *d, dt = *d;
+  dm.M = (int)row0; dm.workspace = nullptr; dm.workspace_bytes = 0;
+  const bool apanel = (d->panels & 1) != 0;
+  dt.M = (int)m_tail;
+  dt.A = (const char*)d->A + (apanel ? (size_t)row0 * 64 : (size_t)row0 * d->lda * 2);
+  const bool c_planes = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P;
+  if (c_planes) dm.c_plane_rows = dt.c_plane_rows = d->c_plane_rows ? d->c_plane_rows : (int64_t)d->M;
+  dt.C = (char*)d->C + (d->c_dtype == ACX_BF16X3P ? (size_t)row0 * 32 * 2
+                                                  : (size_t)row0 * d->ldc * (d->c_dtype == ACX_F32 ? 4 : 2));
+  if (d->residual) dt.residual = d->residual + (size_t)row0 * d->ldr;
+  const int rc = gemm_impl(ctx, &dm, c.s, nullptr, nullptr);
+  return rc ? rc : gemm_impl(ctx, &dt, c.s, nullptr, nullptr);
+}
+
+// ---- route 2: few-row f32 problems (and every problem that asks for the few-row fusions): 32x32 tiles, K split over the waves
+template <int E, int AG, int AN = 0>
+static void sk_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_f32_sk_kernel<E, AG, AN>>(c.dev_slot, grid, dim3(512), (size_t)SK_LDS_B, c.s, g);
+}
+template <int AG>
+static void sk_launch_epi(const GemmCall& c, int epi, dim3 grid, const Args& g) {
+  switch (epi) {
+    case SK_EPI_PLAIN: sk_launch<SK_EPI_PLAIN, AG>(c, grid, g); break;
+    case SK_EPI_QUICKGELU: sk_launch<SK_EPI_QUICKGELU, AG>(c, grid, g); break;
+    case SK_EPI_RES: sk_launch<SK_EPI_RES, AG>(c, grid, g); break;
+    default: sk_launch<SK_EPI_GELUGRAD, AG>(c, grid, g); break;
+  }
+}
+static int route_sk(const GemmCall& c, const Args& base) {
+  acx_ctx* ctx = c.ctx;
+  const acx_gemm_desc* d = c.d;
+  const bool a_norm = d->a_norm_w != nullptr;
+  const bool sk_fusion = d->a_act != ACX_ACT_NONE || d->gelu_grad_of != nullptr || a_norm;
+  const bool sk_ok = c.fast && c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16 && d->K % SK_CH == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 &&
+                     !((uintptr_t)d->C & 15) && (!d->residual || (d->ldr % 4 == 0 && !((uintptr_t)d->residual & 15))) &&
+                     (!d->gelu_grad_of || (d->ldg % 4 == 0 && !((uintptr_t)d->gelu_grad_of & 15) && !d->residual &&
+                                           d->act == ACX_ACT_NONE)) &&
+                     !(d->act == ACX_ACT_QUICKGELU && d->residual) && !c.relu_act &&
+                     (d->a_act == ACX_ACT_NONE || d->a_act == ACX_ACT_QUICKGELU) &&
+                     (size_t)d->M * d->lda < ((size_t)1 << 31) && (size_t)d->N * d->ldw < ((size_t)1 << 31);
+  if (sk_fusion && !sk_ok)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_act / gelu_grad_of / a_norm need the few-row f32 kernel (see acx_gemm_desc)%s");
+  if (a_norm && (d->K != 512 || !d->a_norm_b || d->a_act != ACX_ACT_NONE || d->residual || d->gelu_grad_of || d->act != ACX_ACT_NONE ||
+                 (((uintptr_t)d->a_norm_w | (uintptr_t)d->a_norm_b) & 15)))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_norm needs K == 512, weight and bias, and no other fusion%s");
+  // narrow outputs (N <= 512: out-proj, proj and the dX chain of the text tower) stay ahead of the 64x64-tile kernel up to
+  // ~1300 rows -- 17-34 row tiles x 16 column tiles fill the chip where 64x64 tiles leave half of it idle
+  // (profiles/r03_text_gemm.txt); wide outputs only up to the row limit
+  const int sk_max_m = ctx ? ctx->opt_sk_max_m : ACX_SK_MAX_M;
+  // ... except long K at more than ~770 rows when the caller brought a split-K workspace: the 64x64 kernel with K split 2-4
+  // ways is ahead there (1078 rows, N = 512: K = 2048 37.1 vs 43.5 us, K = 1536 30.0 vs 33.2 us; at 539 rows it is not)
+  const bool sk_narrow = sk_max_m > 0 && d->N <= 512 && d->M <= 4 * sk_max_m && !(d->workspace && d->M > 768 && d->K >= 1536);
+  if (!(sk_ok && (sk_fusion || d->M <= sk_max_m || sk_narrow))) return ROUTE_NEXT;
+  Args g = base;
+  dim3 kgrid((unsigned)(((d->M + 31) / 32) * ((d->N + 31) / 32)));
+  // long K on few tiles: pieces of two chunks (512 floats = resident in one DMA burst) across workgroups, when the caller
+  // brought the partial workspace and the arrival counters
+  g.counters = (unsigned int*)d->counters;
+  if (d->workspace && d->counters && d->K >= 1024 && d->K % 512 == 0) {
+    const int pieces = d->K / 512;
+    if ((int)kgrid.x * pieces <= 512 && (int)kgrid.x <= d->n_counters &&
+        (size_t)pieces * kgrid.x * 4096 <= d->workspace_bytes && !((uintptr_t)d->workspace & 15)) {
+      g.ksplit = pieces;
+      g.kchunk = 2;
       g.partial = (float*)d->workspace;
-      grid.y = g.ksplit;
+      kgrid.y = (unsigned)pieces;
     }
   }
-  // f32 FAST problems without split-K: the 8-wave variant (ACX_W8=0 keeps the 4-wave kernel)
-  // (short split-K pieces of identity-map problems stay on the 4-wave kernel: no measurable difference)
-  if (g.ksplit == 1 && acx_gemm_takes_strip_stream(d)) {
-    // big f32 GEMMs without a residual: persistent strip-stream kernel, one 1024-thread block per CU (acx_gemm_p256.h)
-    const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
-    const dim3 pgrid((unsigned)ncu);                       // >= 1024 tiles of 128x128 => >= 8 strips per CU
-    const size_t plds = 2 * P2_STAGE_B;
-#define ACX_P2L(ACT, CV)                                                                            \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                          \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_f32_p256_kernel<ACT, 0, CV>,                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);             \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_f32_p256_kernel<ACT, 0, CV>), pgrid, dim3(1024), plds, s, g);          \
-  } while (0)
-    if (d->amap == ACX_AMAP_CONV3X3) {
-      if (d->act == ACX_ACT_LEAKYRELU) ACX_P2L(2, 1); else if (d->act == ACX_ACT_RELU) ACX_P2L(3, 1); else ACX_P2L(0, 1);
-    } else if (d->act == ACX_ACT_QUICKGELU) ACX_P2L(1, 0); else if (d->act == ACX_ACT_RELU) ACX_P2L(3, 0); else ACX_P2L(0, 0);
-#undef ACX_P2L
-    ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-    return ACX_OK;
-  }
-  if (w8 && (w8_conv || (fast && g.ksplit == 1)) && prec == ACX_PREC_F32 && !c_bf16 && !a_bf16) {
-#define ACX_W8L(ACT, RES, CV)                                                                       \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_f32_w8_kernel<ACT, RES, CV>,                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_f32_w8_kernel<ACT, RES, CV>), grid, dim3(512), lds, s, g);             \
-  } while (0)
-    // split pieces meet inside the kernel (last-arriver reduction) when the caller brought arrival counters; else a reduce launch
-    g.counters = (g.ksplit > 1 && d->counters && (int)grid.x <= d->n_counters) ? (unsigned int*)d->counters : nullptr;
-    if (w8_conv) {
-      if (d->act == ACX_ACT_LEAKYRELU) { if (d->residual) ACX_W8L(2, 1, 1); else ACX_W8L(2, 0, 1); }
-      else if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_W8L(1, 1, 1); else ACX_W8L(1, 0, 1); }
-      else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_W8L(3, 1, 1); else ACX_W8L(3, 0, 1); }
-      else if (d->act == ACX_ACT_RESRELU) ACX_W8L(4, 1, 1);
-      else { if (d->residual) ACX_W8L(0, 1, 1); else ACX_W8L(0, 0, 1); }
-    } else {
-      if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) ACX_W8L(1, 1, 0); else ACX_W8L(1, 0, 0); }
-      else if (d->act == ACX_ACT_RELU) { if (d->residual) ACX_W8L(3, 1, 0); else ACX_W8L(3, 0, 0); }
-      else if (d->act == ACX_ACT_RESRELU) ACX_W8L(4, 1, 0);
-      else { if (d->residual) ACX_W8L(0, 1, 0); else ACX_W8L(0, 0, 0); }
+  const int epi = d->gelu_grad_of ? SK_EPI_GELUGRAD : d->residual ? SK_EPI_RES : d->act == ACX_ACT_QUICKGELU ? SK_EPI_QUICKGELU : SK_EPI_PLAIN;
+  if (a_norm) sk_launch<SK_EPI_PLAIN, 0, 1>(c, kgrid, g);
+  else if (d->a_act == ACX_ACT_QUICKGELU) sk_launch_epi<1>(c, epi, kgrid, g);
+  else sk_launch_epi<0>(c, epi, kgrid, g);
+  ACX_CHECK_LAUNCH(ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- route 3: pairs = 6 (f32-accurate product from three bf16 planes per operand) and pairs = 3: the one-wave-per-SIMD
+// plane-reuse kernel (acx_gemm_x6.h) -- identity rows or the implicit 3x3 convolution; K split across workgroups when the tiles
+// alone would not fill the chip (caller-provided workspace)
+template <int CM, int ACT, int RES, int CV, int NI>
+static void x6_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  if constexpr (CV == 0 && CM != 1 && ACT != 2) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual)
+    if (c.d->pairs == 3) {                        // the three leading products only (acx_gemm_x6.h, X3); fp16 planes: X3 = 2
+      if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+      else acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+      return;
     }
-#undef ACX_W8L
-    if (g.ksplit > 1 && !g.counters) {
-      const int64_t total = (int64_t)d->M * d->N;
-      hipLaunchKernelGGL((splitk_reduce_kernel<0>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)g.partial,
-                         g.ksplit, *d);
-    }
-    ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-    return ACX_OK;
   }
-  // bf16 operands already in global memory, no split: the LDS-DMA kernels (ACX_NO_DMA=1 keeps the register-staged
-  // one, ACX_NO_RING=1 the 128x128 DMA kernel).  Large problems take the persistent 256x256 ring kernel.
-  const bool no_dma = !ACX_DBG_SWITCH("DMA", true);
-  const bool no_ring = !ACX_DBG_SWITCH("RING", true);
+  acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+}
+// whole 256 x 256 tiles: every epilogue (a K split leaves it to the reduce launch)
+template <int CV>
+static void x6_launch_tiles(const GemmCall& c, bool c_x3, int split, dim3 grid, const Args& g) {
+  const int act = c.d->act;
+  if (split > 1) x6_launch<0, 0, 0, CV, 4>(c, grid, g);
+  else if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<2, 2, 0, CV, 4>(c, grid, g); else x6_launch<2, 0, 0, CV, 4>(c, grid, g); }
+  else if (c.c_bf16) { if (act == ACX_ACT_QUICKGELU) x6_launch<1, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<1, 2, 0, CV, 4>(c, grid, g); else x6_launch<1, 0, 0, CV, 4>(c, grid, g); }
+  else if (c.d->residual) x6_launch<0, 0, 1, CV, 4>(c, grid, g);
+  else if (act == ACX_ACT_QUICKGELU) x6_launch<0, 1, 0, CV, 4>(c, grid, g);
+  else if (act == ACX_ACT_LEAKYRELU) x6_launch<0, 2, 0, CV, 4>(c, grid, g);
+  else x6_launch<0, 0, 0, CV, 4>(c, grid, g);
+}
+// the strips of the last round: identity rows only; epilogues of the ViT's products (plane outputs with / without QuickGELU,
+// f32 with a residual / QuickGELU / plain) -- anything else keeps whole tiles (X6PlanIn.may_strip)
+template <int NI>
+static void x6_launch_strips(const GemmCall& c, bool c_x3, dim3 grid, const Args& g) {
+  const int act = c.d->act;
+  if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, 0, NI>(c, grid, g); else x6_launch<2, 0, 0, 0, NI>(c, grid, g); }
+  else if (c.d->residual) x6_launch<0, 0, 1, 0, NI>(c, grid, g);
+  else if (act == ACX_ACT_QUICKGELU) x6_launch<0, 1, 0, 0, NI>(c, grid, g);
+  else x6_launch<0, 0, 0, 0, NI>(c, grid, g);
+}
+// a last round with LayerNorm riders (RIDE = 1: the f32 residual epilogue)
+template <int NI>
+static void x6_launch_ride(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI, 0, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+}
+// job != nullptr (acx_gemm_ln): *ridden = the rows 0 .. *ridden of the job's LayerNorm that rode in the product's last round (0: none)
+static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, long long* ridden) {
+  acx_ctx* ctx = c.ctx;
+  const acx_gemm_desc* d = c.d;
+  if (!((d->pairs == 6 || d->pairs == 3) && ACX_DBG_SWITCH("X6P4", true))) return ROUTE_NEXT;
+  const bool conv = d->amap == ACX_AMAP_CONV3X3, x3 = d->pairs == 3, c_bf16 = c.c_bf16;
+  if (x3 && (conv || c_bf16 || d->act == ACX_ACT_LEAKYRELU))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 3 takes identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues%s");
+  const bool c_x3_ = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
+  if (c.a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: fp16 operand planes write fp16 output planes (ACX_F16X2P)%s");
+  const bool shape_ok = x6_operands_ok(c) &&
+      d->lda % 8 == 0 && d->ldw % 8 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
+      !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && d->a_plane_stride > 0 && d->w_plane_stride > 0 &&
+      !((d->a_plane_stride | d->w_plane_stride) & 15) && (size_t)d->M * d->lda * 2 < ((size_t)1 << 32) &&
+      (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && !(d->act == ACX_ACT_QUICKGELU && d->residual) &&
+      !(d->act == ACX_ACT_LEAKYRELU && d->residual) && !(c_x3_ && (d->residual || d->N % 8 || d->ldc % 8)) && !(c_bf16 && d->residual) &&
+      (!d->panels || (!conv && d->K % 32 == 0 && d->lda == d->K && d->ldw == d->K)) && ((d->c_dtype != ACX_BF16X3P && d->c_dtype != ACX_F16X2P) || d->ldc == d->N) &&
+      (!conv || (d->zero_page && !((uintptr_t)d->zero_page & 15) && d->cin % 32 == 0 && !(d->gl & (d->gl - 1)) &&
+                 !(d->gn & (d->gn - 1)) && d->M % 256 == 0));
+  if (!shape_ok) {
+    if (conv) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3 needs a power-of-two grid, cin %% 32 == 0, M %% 256 == 0, a zero page and 16-byte aligned planes%s");
+    return ROUTE_NEXT;
+  }
+  X6PlanIn in = {};
+  in.M = d->M; in.N = d->N; in.K = d->K; in.ncu = c.ncu_x6;
+  // narrow convolution outputs (N <= 128: c2 and the input gradient of c1 in the XD-Violence head, E = 128): 256 x 128 tiles
+  // (the NI = 2 instantiation) instead of half-empty 256 x 256 ones; f32 outputs without an activation only (what the head asks for)
+  in.narrow = conv && d->N <= 128 && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE;
+  in.may_split = d->workspace && !(c.a_f16 && c_x3_);   // (no reduce launch writes fp16 planes: such launches keep whole K per tile)
+  in.workspace_bytes = d->workspace_bytes;
+  in.may_strip = !conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && x6_strip_enabled(ctx);
+  in.strip_force = ctx ? ctx->opt_x6_strip : 1;
+  in.tail_split_opt = ctx && ctx->opt_x6_tail;
+  in.may_ride = job && ridden && !conv && !x3 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
+      (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && job->y_dtype == ACX_BF16X3P && job->w && job->b && job->y &&
+      !((uintptr_t)job->y & 15) && !(((long long)d->M * d->N * 2) & 15) && ACX_DBG_SWITCH("LN_RIDER", true) && ctx && ctx->opt_ln_rider;
+  in.ride_cap = ctx ? ctx->opt_ln_rider : 0;
+  in.rate = 0.0;
+  const X6Plan p = x6_plan(in);
+
+  Args g = base;
+  g.ksplit = p.split; g.kchunk = (p.nks + p.split - 1) / p.split; g.partial = p.split > 1 ? (float*)d->workspace : nullptr;
+  if (p.ride > 0) {
+    g.ln.x = (const float*)d->C; g.ln.w = job->w; g.ln.b = job->b; g.ln.y = (u16*)job->y;
+    g.ln.ldx = d->ldc; g.ln.rows = d->M; g.ln.row0 = 0; g.ln.nrows = p.ride;
+    g.ln.eps = job->eps; g.ln.mode = job->mode; g.ln.vpl = d->N / 64;
+    *ridden = p.ride;
+  }
+  if (p.strip_ni < 4) g.ntiles = p.tile0_tail;          // (tile0 = 0) the full rounds only
+  else if (p.ride_rem) g.ntiles = p.ride_tile0;
+  if (p.main_items > 0) {
+    const dim3 xgrid((unsigned)p.main_grid);
+    if (in.narrow) { if (d->residual && p.split == 1) x6_launch<0, 0, 1, 1, 2>(c, xgrid, g); else x6_launch<0, 0, 0, 1, 2>(c, xgrid, g); }
+    else if (conv) x6_launch_tiles<1>(c, c_x3_, p.split, xgrid, g);
+    else x6_launch_tiles<0>(c, c_x3_, p.split, xgrid, g);
+  }
+  const dim3 tgrid((unsigned)p.tail_grid);
+  if (p.strip_ni < 4) {
+    g.tile0 = p.tile0_tail * (4 / p.strip_ni); g.ntiles = p.tail_items;   // (in the strips' own numbering: N % 256 == 0)
+    if (p.ride > 0) { if (p.strip_ni == 2) x6_launch_ride<2>(c, tgrid, g); else x6_launch_ride<1>(c, tgrid, g); }
+    else if (p.strip_ni == 2) x6_launch_strips<2>(c, c_x3_, tgrid, g);
+    else x6_launch_strips<1>(c, c_x3_, tgrid, g);
+  } else if (p.ride_rem) {
+    g.tile0 = p.ride_tile0; g.ntiles = p.ride_rem;
+    x6_launch_ride<4>(c, tgrid, g);
+  }
+  if (p.split > 1) splitk_reduce(c, g.partial, p.split, true);
+  ACX_CHECK_LAUNCH(ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- route 4: small branch-free f32 problems (text tower): 64x64 tiles, four blocks per CU
+template <int ACT, int RES>
+static void s64_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_f32_s64_kernel<ACT, RES>>(c.dev_slot, grid, dim3(256), (size_t)(4 * TILE_S), c.s, g);
+}
+static int route_s64(const GemmCall& c, const Args& base) {
+  const acx_gemm_desc* d = c.d;
+  const int tiles = ((d->M + BM - 1) / BM) * base.tiles_n, st_m = (d->M + 63) / 64, st_n = (d->N + 63) / 64;
+  if (!(ACX_DBG_SWITCH("S64", true) && c.fast && c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16 && tiles <= 256 && st_m * st_n >= 96))
+    return ROUTE_NEXT;
+  Args g = base;
+  dim3 sgrid((unsigned)(st_m * st_n));
+  // long K on few tiles (text tower: N = 512, K = 1536 / 2048 at 539-1078 rows = 72-136 tiles of 48-64 serial K-steps):
+  // split K so that the launch covers the chip about twice, at least 16 K-steps per piece
+  if (d->workspace && st_m * st_n <= 256 && d->K >= 1024) {
+    int split = 1;
+    const int nkt = d->K / 32;
+    while (st_m * st_n * split * 2 <= 1100 && nkt / (split * 2) >= 12 && split < 8) split *= 2;
+    if (split > 1 && (size_t)split * d->M * d->N * sizeof(float) <= d->workspace_bytes) {
+      ksplit_even(nkt, split, d->workspace).into(g);
+      sgrid.y = (unsigned)g.ksplit;
+    }
+  }
+  if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) s64_launch<1, 1>(c, sgrid, g); else s64_launch<1, 0>(c, sgrid, g); }
+  else if (d->act == ACX_ACT_RELU) { if (d->residual) s64_launch<3, 1>(c, sgrid, g); else s64_launch<3, 0>(c, sgrid, g); }
+  else if (d->act == ACX_ACT_RESRELU) s64_launch<4, 1>(c, sgrid, g);
+  else { if (d->residual) s64_launch<0, 1>(c, sgrid, g); else s64_launch<0, 0>(c, sgrid, g); }
+  if (g.ksplit > 1) splitk_reduce(c, g.partial, g.ksplit, false);
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- step 5: the K split of the 128x128-tile kernels, decided once for the routes below.  Skinny problems (few tiles, long K)
+// split K over gridDim.y so the chip is filled; the partial sums are combined in fixed order, together with the epilogue.  Taken
+// by branch-free problems, the 8-wave convolutions and f32 problems on the generic row-mapped path (a_sub / positional epilogue /
+// test tilings: the temporal model's input projection, 64 tiles at a data-parallel rank's 4096 rows = a quarter of the chip for
+// 59 us), when the caller brought a workspace
+static bool w8_takes_conv(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  return ACX_DBG_SWITCH("W8", true) && d->amap == ACX_AMAP_CONV3X3 && !d->a_sub && !d->pos0 && d->K % 32 == 0 && d->cin % 32 == 0 &&
+         c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16;
+}
+static KSplit generic_ksplit(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  const int ke = c.prec == ACX_PREC_F32 ? 32 : 64;
+  const bool gen_split = !c.fast && c.prec == ACX_PREC_F32 && !c.a_bf16 && !c.c_bf16 && d->amap != ACX_AMAP_CONV3X3 && d->K % ke == 0 &&
+                         d->act != ACX_ACT_LEAKYRELU;
+  if (!((c.fast || w8_takes_conv(c) || gen_split) && d->workspace)) return KSplit();
+  const int tiles = ((d->M + BM - 1) / BM) * ((d->N + BN - 1) / BN), nkt = d->K / ke;
+  int split = 1;
+  // bf16 pieces keep >= 8 K-steps: at the XD text tower's 539 rows x K = 512 a 2-way split + its 5 us reduce launch is
+  // slower than the unsplit launch (head step 1.64 -> 1.51 ms); 16 is worse again (1.59)
+  while (tiles * split * 2 <= 512 && nkt / (split * 2) >= (c.prec == ACX_PREC_BF16 ? 8 : 4) && split < 16) split *= 2;
+  if (split > 1 && (size_t)split * d->M * d->N * sizeof(float) <= d->workspace_bytes) return ksplit_even(nkt, split, d->workspace);
+  return KSplit();
+}
+
+// ---- route 6: big f32 GEMMs without a residual and no K split: the persistent strip-stream kernel, one 1024-thread block per CU
+// (acx_gemm_p256.h; acx_gemm_takes_strip_stream: >= 1024 tiles of 128x128 => >= 8 strips per CU)
+template <int ACT, int CV>
+static void p256_launch(const GemmCall& c, const Args& g) {
+  acx_launch_lds<gemm_f32_p256_kernel<ACT, 0, CV>>(c.dev_slot, dim3((unsigned)c.ncu), dim3(1024), (size_t)(2 * P2_STAGE_B), c.s, g);
+}
+static int route_p256(const GemmCall& c, const Args& g, const KSplit& ks) {
+  const acx_gemm_desc* d = c.d;
+  if (!(ks.ksplit == 1 && acx_gemm_takes_strip_stream(d))) return ROUTE_NEXT;
+  if (d->amap == ACX_AMAP_CONV3X3) {
+    if (d->act == ACX_ACT_LEAKYRELU) p256_launch<2, 1>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 1>(c, g); else p256_launch<0, 1>(c, g);
+  } else if (d->act == ACX_ACT_QUICKGELU) p256_launch<1, 0>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 0>(c, g); else p256_launch<0, 0>(c, g);
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- route 7: f32 branch-free problems without a K split, and the f32 3x3 convolutions with or without one: the 8-wave
+// variant (ACX_W8=0 in tools builds keeps the 4-wave kernel; short split-K pieces of identity-map problems stay on the 4-wave
+// kernel: no measurable difference)
+template <int ACT, int RES, int CV>
+static void w8_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_f32_w8_kernel<ACT, RES, CV>>(c.dev_slot, grid, dim3(512), (size_t)(4 * TILE_B), c.s, g);
+}
+template <int CV>
+static void w8_launch_epi(const GemmCall& c, dim3 grid, const Args& g) {
+  const acx_gemm_desc* d = c.d;
+  if constexpr (CV != 0) {                        // (LeakyReLU: the convolutions only -- `fast` excludes it)
+    if (d->act == ACX_ACT_LEAKYRELU) { if (d->residual) w8_launch<2, 1, CV>(c, grid, g); else w8_launch<2, 0, CV>(c, grid, g); return; }
+  }
+  if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) w8_launch<1, 1, CV>(c, grid, g); else w8_launch<1, 0, CV>(c, grid, g); }
+  else if (d->act == ACX_ACT_RELU) { if (d->residual) w8_launch<3, 1, CV>(c, grid, g); else w8_launch<3, 0, CV>(c, grid, g); }
+  else if (d->act == ACX_ACT_RESRELU) w8_launch<4, 1, CV>(c, grid, g);
+  else { if (d->residual) w8_launch<0, 1, CV>(c, grid, g); else w8_launch<0, 0, CV>(c, grid, g); }
+}
+static int route_w8(const GemmCall& c, const Args& base, dim3 grid, const KSplit& ks) {
+  const acx_gemm_desc* d = c.d;
+  const bool w8_conv = w8_takes_conv(c);
+  if (!(ACX_DBG_SWITCH("W8", true) && (w8_conv || (c.fast && ks.ksplit == 1)) && c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16))
+    return ROUTE_NEXT;
+  Args g = base;
+  ks.into(g);
+  // split pieces meet inside the kernel (last-arriver reduction) when the caller brought arrival counters; else a reduce launch
+  g.counters = (ks.ksplit > 1 && d->counters && (int)grid.x <= d->n_counters) ? (unsigned int*)d->counters : nullptr;
+  if (w8_conv) w8_launch_epi<1>(c, grid, g); else w8_launch_epi<0>(c, grid, g);
+  if (ks.ksplit > 1 && !g.counters) splitk_reduce(c, ks.partial, ks.ksplit, false);
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- route 8a: bf16 operands already in global memory, no split, many tiles: the persistent 256x256 kernels (ACX_NO_RING=1 /
+// ACX_NO_DMA=1 in tools builds keep the kernels below).  Even K-tile count and 32-bit operand byte offsets: the phase-interleaved
+// kernel (acx_gemm_p8.h); else the lock-step ring kernel.  What only these kernels can do is refused here when they cannot.
+template <int CB, int ACT, int RES>
+static void ring_launch(const GemmCall& c, bool p8, dim3 grid, const Args& g) {
+  if (p8) acx_launch_lds<gemm_bf16_p8_kernel<CB, ACT, RES>>(c.dev_slot, grid, dim3(512), (size_t)P8_LDS_B, c.s, g);
+  else acx_launch_lds<gemm_bf16_ring_kernel<CB, ACT, RES>>(c.dev_slot, grid, dim3(512), (size_t)(2 * RG_STAGE_B + 8 * 4096), c.s, g);
+}
+#ifdef ACX_DEBUG_SWITCHES
+template <int CM, int ACT, int RES>
+static void p4_plain_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+}
+#endif
+static int route_ring(const GemmCall& c, const Args& g, const KSplit& ks) {
+  acx_ctx* ctx = c.ctx;
+  const acx_gemm_desc* d = c.d;
+  const bool c_bf16 = c.c_bf16;
   const int rtiles = ((d->M + 255) / 256) * ((d->N + 255) / 256);
   const int ring_min = ctx ? ctx->opt_ring_min_tiles : 512;   // acx_set_option(ACX_OPT_RING_MIN_TILES); tests lower it
-  const bool ring_ok = fast && g.ksplit == 1 && prec == ACX_PREC_BF16 && a_bf16 && !no_dma && !no_ring && d->lda % 8 == 0 &&
+  const bool ring_ok = c.fast && ks.ksplit == 1 && c.prec == ACX_PREC_BF16 && c.a_bf16 && ACX_DBG_SWITCH("DMA", true) &&
+      ACX_DBG_SWITCH("RING", true) && d->lda % 8 == 0 &&
       d->ldw % 8 == 0 && d->K % 64 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
       !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && rtiles >= ring_min &&
       !(d->act == ACX_ACT_QUICKGELU && d->residual);
   const bool c_x3 = d->c_dtype == ACX_BF16X3;
   if (c_x3 && (!ring_ok || d->residual || ((d->K / 64) * (d->pairs > 1 ? d->pairs : 1)) % 2 || !ACX_DBG_SWITCH("P8", true)))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: c_dtype ACX_BF16X3 needs the persistent 256x256 bf16 kernel and no residual%s");
-  // (pairs = 6 problems were taken by the plane-reuse kernel above; the PAIRS instantiation of the kernel below -- round 4's route,
-  // six plain products one after the other -- is no longer built)
+  // (pairs = 6 / 3 problems were taken by the plane-reuse kernel above, or do not fit it)
   if (d->pairs == 3) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 3 needs bf16 planes, identity rows, K %% 32 == 0 (the plane-reuse kernel)%s");
   if (d->pairs > 1)
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 needs bf16 planes (16-byte aligned strides), K %% 32 == 0, N %% 4 == 0 (plane output: N %% 8 == 0), identity rows or CONV3X3 on a power-of-two grid%s");
-  if (ring_ok) {
-    const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
-    const dim3 rgrid((unsigned)(rtiles < ncu ? rtiles : ncu));
-    // even K-tile count and 32-bit operand byte offsets: the phase-interleaved kernel; else the lock-step ring kernel
-    const int npairs_ = d->pairs > 1 ? d->pairs : 1;
-    const bool p8 = ((d->K / 64) * npairs_) % 2 == 0 && (size_t)d->M * d->lda * 2 < ((size_t)1 << 32) &&
-                    (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && ACX_DBG_SWITCH("P8", true);
-    if ((d->pairs > 1 || c_x3) && !p8)
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 / ACX_BF16X3 output need the persistent 256x256 kernel%s");
+  if (!ring_ok) return ROUTE_NEXT;
+  const dim3 rgrid((unsigned)(rtiles < c.ncu ? rtiles : c.ncu));
+  const int npairs_ = d->pairs > 1 ? d->pairs : 1;
+  const bool p8 = ((d->K / 64) * npairs_) % 2 == 0 && (size_t)d->M * d->lda * 2 < ((size_t)1 << 32) &&
+                  (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && ACX_DBG_SWITCH("P8", true);
+  if ((d->pairs > 1 || c_x3) && !p8)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 / ACX_BF16X3 output need the persistent 256x256 kernel%s");
 #ifdef ACX_DEBUG_SWITCHES
-    // A/B only (tools build, ACX_P4=1): the one-wave-per-SIMD frame's PLAIN schedule (acx_gemm_x6.h: 64-k super-steps, 64 MFMAs per
-    // wave and barrier).  Measured equal to or 3-15 % behind the p8 kernel on the ViT shapes, its K loop alone (no DMA, no stores)
-    // at 0.46 of the bf16 roof (profiles/r05_gemm_plain_bf16_notes.txt): not a product route.
-    if (p8 && !c_x3 && !(c_bf16 && d->residual) && d->act != ACX_ACT_LEAKYRELU && ACX_DBG_SWITCH("P4", false)) {
-      g.d.panels = 0; g.ksplit = 1; g.partial = nullptr;
-#define ACX_P4L(CM, ACT, RES)                                                                       \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                          \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 1>,              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B);         \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 1>), rgrid, dim3(256), (size_t)X6_LDS_B, s, g); \
-  } while (0)
-      if (d->residual) ACX_P4L(0, 0, 1);
-      else if (d->act == ACX_ACT_QUICKGELU) { if (c_bf16) ACX_P4L(1, 1, 0); else ACX_P4L(0, 1, 0); }
-      else { if (c_bf16) ACX_P4L(1, 0, 0); else ACX_P4L(0, 0, 0); }
-#undef ACX_P4L
-      ACX_CHECK_LAUNCH(ctx, "acx_gemm");
-      return ACX_OK;
-    }
+  // A/B only (tools build, ACX_P4=1): the one-wave-per-SIMD frame's PLAIN schedule (acx_gemm_x6.h: 64-k super-steps, 64 MFMAs per
+  // wave and barrier).  Measured equal to or 3-15 % behind the p8 kernel on the ViT shapes, its K loop alone (no DMA, no stores)
+  // at 0.46 of the bf16 roof (profiles/r05_gemm_plain_bf16_notes.txt): not a product route.
+  if (p8 && !c_x3 && !(c_bf16 && d->residual) && d->act != ACX_ACT_LEAKYRELU && ACX_DBG_SWITCH("P4", false)) {
+    Args g4 = g;
+    g4.d.panels = 0;
+    if (d->residual) p4_plain_launch<0, 0, 1>(c, rgrid, g4);
+    else if (d->act == ACX_ACT_QUICKGELU) { if (c_bf16) p4_plain_launch<1, 1, 0>(c, rgrid, g4); else p4_plain_launch<0, 1, 0>(c, rgrid, g4); }
+    else { if (c_bf16) p4_plain_launch<1, 0, 0>(c, rgrid, g4); else p4_plain_launch<0, 0, 0>(c, rgrid, g4); }
+    ACX_CHECK_LAUNCH(ctx, "acx_gemm");
+    return ACX_OK;
+  }
 #endif
-#define ACX_RING_L(CB, ACT, RES)                                                                    \
-  do {                                                                                              \
-    if (p8) {                                                                                       \
-      static bool attr8_dev_[64] = {}; bool& attr8_done = attr8_dev_[dev_slot];                                                               \
-      if (!attr8_done) {                                                                            \
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_p8_kernel<CB, ACT, RES>,                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8_LDS_B);       \
-        attr8_done = true;                                                                          \
-      }                                                                                             \
-      hipLaunchKernelGGL((gemm_bf16_p8_kernel<CB, ACT, RES>), rgrid, dim3(512), (size_t)P8_LDS_B, s, g); \
-      break;                                                                                        \
-    }                                                                                               \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_ring_kernel<CB, ACT, RES>,                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * RG_STAGE_B + 8 * 4096)); \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_bf16_ring_kernel<CB, ACT, RES>), rgrid, dim3(512), (size_t)(2 * RG_STAGE_B + 8 * 4096), s, g); \
-  } while (0)
-#define ACX_RING_SEL()                                                                              \
-  do {                                                                                              \
-    if (c_x3) { if (d->act == ACX_ACT_QUICKGELU) ACX_RING_L(2, 1, 0); else ACX_RING_L(2, 0, 0); }   \
-    else if (d->residual) { if (c_bf16) ACX_RING_L(1, 0, 1); else ACX_RING_L(0, 0, 1); }            \
-    else if (d->act == ACX_ACT_QUICKGELU) { if (c_bf16) ACX_RING_L(1, 1, 0); else ACX_RING_L(0, 1, 0); } \
-    else { if (c_bf16) ACX_RING_L(1, 0, 0); else ACX_RING_L(0, 0, 0); }                             \
-  } while (0)
-    ACX_RING_SEL();
-#undef ACX_RING_SEL
-#undef ACX_RING_L
-  } else
-  if (prec == ACX_PREC_BF16 && a_bf16 && !no_dma && d->amap == ACX_AMAP_CONV3X3 && g.ksplit == 1 && d->zero_page &&
-      !((uintptr_t)d->zero_page & 15) && d->cin % 64 == 0 && d->M % 128 == 0 && d->lda % 8 == 0 && d->ldw % 8 == 0 && !d->a_sub &&
-      !d->pos0 && d->act != ACX_ACT_QUICKGELU && !(d->act == ACX_ACT_LEAKYRELU && d->residual)) {
-    // bf16 implicit-GEMM convolutions (the XD-Violence head): the 128x128 LDS-DMA kernel with a per-tap source row
-    const size_t dlds = 2 * DMA_STAGE_B;
-    g.zeros = (const float*)d->zero_page;
-#define ACX_DMAC(CB, ACT, RES)                                                                      \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_dma_kernel<CB, ACT, RES, 1>,                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds);             \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_bf16_dma_kernel<CB, ACT, RES, 1>), grid, block, dlds, s, g);           \
-  } while (0)
-    if (d->act == ACX_ACT_LEAKYRELU) { if (c_bf16) ACX_DMAC(1, 2, 0); else ACX_DMAC(0, 2, 0); }
-    else if (d->residual) { if (c_bf16) ACX_DMAC(1, 0, 1); else ACX_DMAC(0, 0, 1); }
-    else { if (c_bf16) ACX_DMAC(1, 0, 0); else ACX_DMAC(0, 0, 0); }
-#undef ACX_DMAC
-  } else
-  if (fast && g.ksplit == 1 && prec == ACX_PREC_BF16 && a_bf16 && !no_dma && d->lda % 8 == 0 && d->ldw % 8 == 0) {
-    const size_t dlds = 2 * DMA_STAGE_B;
-#define ACX_DMA(CB, ACT, RES)                                                                       \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                                                                 \
-    if (!attr_done) {                                                                               \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_dma_kernel<CB, ACT, RES>,                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds);             \
-      attr_done = true;                                                                             \
-    }                                                                                               \
-    hipLaunchKernelGGL((gemm_bf16_dma_kernel<CB, ACT, RES>), grid, block, dlds, s, g);              \
-  } while (0)
-    const int sel = (c_bf16 ? 4 : 0) + (d->act == ACX_ACT_QUICKGELU ? 2 : 0) + (d->residual ? 1 : 0);
-    switch (sel) {
-      case 0: ACX_DMA(0, 0, 0); break;
-      case 1: ACX_DMA(0, 0, 1); break;
-      case 2: ACX_DMA(0, 1, 0); break;
-      case 3: ACX_DMA(0, 1, 1); break;
-      case 4: ACX_DMA(1, 0, 0); break;
-      case 5: ACX_DMA(1, 0, 1); break;
-      case 6: ACX_DMA(1, 1, 0); break;
-      default: ACX_DMA(1, 1, 1); break;
-    }
-#undef ACX_DMA
-  } else if (fast && !relu_act) {          // (the ReLU epilogues take the generic instantiation's run-time act)
-    switch (variant) {
-      case 0: ACX_FAST(0, 0, 0); break;
-      case 1: ACX_FAST(0, 0, 1); break;
-      case 2: ACX_FAST(1, 1, 0); break;
-      case 3: ACX_FAST(1, 1, 1); break;
-      case 4: ACX_FAST(1, 0, 0); break;
-      default: ACX_FAST(1, 0, 1); break;
-    }
-  } else {
-    switch (variant) {
-      case 0: ACX_LAUNCH(0, 0, 0, 0, 0, 0); break;
-      case 1: ACX_LAUNCH(0, 0, 1, 0, 0, 0); break;
-      case 2: ACX_LAUNCH(1, 1, 0, 0, 0, 0); break;
-      case 3: ACX_LAUNCH(1, 1, 1, 0, 0, 0); break;
-      case 4: ACX_LAUNCH(1, 0, 0, 0, 0, 0); break;
-      default: ACX_LAUNCH(1, 0, 1, 0, 0, 0); break;
-    }
-  }
-#undef ACX_FAST
-#undef ACX_LAUNCH
-  if (g.ksplit > 1) {
-    const int64_t total = (int64_t)d->M * d->N;
-    const dim3 rgrid((unsigned)((total + 255) / 256));
-    if (c_bf16) hipLaunchKernelGGL((splitk_reduce_kernel<1>), rgrid, dim3(256), 0, s, (const float*)g.partial, g.ksplit, *d);
-    else hipLaunchKernelGGL((splitk_reduce_kernel<0>), rgrid, dim3(256), 0, s, (const float*)g.partial, g.ksplit, *d);
-  }
+  if (c_x3) { if (d->act == ACX_ACT_QUICKGELU) ring_launch<2, 1, 0>(c, p8, rgrid, g); else ring_launch<2, 0, 0>(c, p8, rgrid, g); }
+  else if (d->residual) { if (c_bf16) ring_launch<1, 0, 1>(c, p8, rgrid, g); else ring_launch<0, 0, 1>(c, p8, rgrid, g); }
+  else if (d->act == ACX_ACT_QUICKGELU) { if (c_bf16) ring_launch<1, 1, 0>(c, p8, rgrid, g); else ring_launch<0, 1, 0>(c, p8, rgrid, g); }
+  else { if (c_bf16) ring_launch<1, 0, 0>(c, p8, rgrid, g); else ring_launch<0, 0, 0>(c, p8, rgrid, g); }
   ACX_CHECK_LAUNCH(ctx, "acx_gemm");
   return ACX_OK;
+}
+
+// ---- routes 8b / 8c: bf16 operands, no split, 128x128 tiles staged by global->LDS DMA, two blocks per CU: the implicit-GEMM
+// convolutions of the XD-Violence head (a per-tap source row; taps outside the grid read the zero page), then identity rows
+template <int CB, int ACT, int RES, int CV>
+static void dma_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  if constexpr (CV) acx_launch_lds<gemm_bf16_dma_kernel<CB, ACT, RES, 1>>(c.dev_slot, grid, dim3(NTHREADS), (size_t)(2 * DMA_STAGE_B), c.s, g);
+  else acx_launch_lds<gemm_bf16_dma_kernel<CB, ACT, RES>>(c.dev_slot, grid, dim3(NTHREADS), (size_t)(2 * DMA_STAGE_B), c.s, g);
+}
+static int route_dma_conv(const GemmCall& c, const Args& g, dim3 grid, const KSplit& ks) {
+  const acx_gemm_desc* d = c.d;
+  const bool c_bf16 = c.c_bf16;
+  if (!(c.prec == ACX_PREC_BF16 && c.a_bf16 && ACX_DBG_SWITCH("DMA", true) && d->amap == ACX_AMAP_CONV3X3 && ks.ksplit == 1 && d->zero_page &&
+        !((uintptr_t)d->zero_page & 15) && d->cin % 64 == 0 && d->M % 128 == 0 && d->lda % 8 == 0 && d->ldw % 8 == 0 && !d->a_sub &&
+        !d->pos0 && d->act != ACX_ACT_QUICKGELU && !(d->act == ACX_ACT_LEAKYRELU && d->residual)))
+    return ROUTE_NEXT;
+  if (d->act == ACX_ACT_LEAKYRELU) { if (c_bf16) dma_launch<1, 2, 0, 1>(c, grid, g); else dma_launch<0, 2, 0, 1>(c, grid, g); }
+  else if (d->residual) { if (c_bf16) dma_launch<1, 0, 1, 1>(c, grid, g); else dma_launch<0, 0, 1, 1>(c, grid, g); }
+  else { if (c_bf16) dma_launch<1, 0, 0, 1>(c, grid, g); else dma_launch<0, 0, 0, 1>(c, grid, g); }
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+static int route_dma(const GemmCall& c, const Args& g, dim3 grid, const KSplit& ks) {
+  const acx_gemm_desc* d = c.d;
+  if (!(c.fast && ks.ksplit == 1 && c.prec == ACX_PREC_BF16 && c.a_bf16 && ACX_DBG_SWITCH("DMA", true) && d->lda % 8 == 0 && d->ldw % 8 == 0))
+    return ROUTE_NEXT;
+  switch ((c.c_bf16 ? 4 : 0) + (d->act == ACX_ACT_QUICKGELU ? 2 : 0) + (d->residual ? 1 : 0)) {
+    case 0: dma_launch<0, 0, 0, 0>(c, grid, g); break;
+    case 1: dma_launch<0, 0, 1, 0>(c, grid, g); break;
+    case 2: dma_launch<0, 1, 0, 0>(c, grid, g); break;
+    case 3: dma_launch<0, 1, 1, 0>(c, grid, g); break;
+    case 4: dma_launch<1, 0, 0, 0>(c, grid, g); break;
+    case 5: dma_launch<1, 0, 1, 0>(c, grid, g); break;
+    case 6: dma_launch<1, 1, 0, 0>(c, grid, g); break;
+    default: dma_launch<1, 1, 1, 0>(c, grid, g); break;
+  }
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+// ---- route 8d: gemm_kernel, which takes everything: the branch-free instantiations (compile-time epilogue) for `fast` problems,
+// the generic one otherwise (the ReLU epilogues too: its run-time act); both with or without the K split, then (9) its reduce launch
+template <int P, int AB, int CB, int F, int ACT, int RES>
+static void gemm_kernel_launch(const GemmCall& c, dim3 grid, const Args& g) {
+  acx_launch_lds<gemm_kernel<P, AB, CB, F, ACT, RES>>(c.dev_slot, grid, dim3(NTHREADS), (size_t)(4 * TILE_B), c.s, g);
+}
+template <int P, int AB, int CB>
+static void gemm_kernel_launch_epi(const GemmCall& c, dim3 grid, const Args& g) {
+  const acx_gemm_desc* d = c.d;
+  if (!(c.fast && !c.relu_act)) gemm_kernel_launch<P, AB, CB, 0, 0, 0>(c, grid, g);
+  else if (d->act == ACX_ACT_QUICKGELU) {
+    if (d->residual) gemm_kernel_launch<P, AB, CB, 1, 1, 1>(c, grid, g); else gemm_kernel_launch<P, AB, CB, 1, 1, 0>(c, grid, g);
+  } else {
+    if (d->residual) gemm_kernel_launch<P, AB, CB, 1, 0, 1>(c, grid, g); else gemm_kernel_launch<P, AB, CB, 1, 0, 0>(c, grid, g);
+  }
+}
+static int route_gemm_kernel(const GemmCall& c, const Args& base, dim3 grid, const KSplit& ks) {
+  Args g = base;
+  ks.into(g);
+  switch ((c.prec == ACX_PREC_F32 ? 0 : (c.a_bf16 ? 1 : 2)) * 2 + c.c_bf16) {
+    case 0: gemm_kernel_launch_epi<0, 0, 0>(c, grid, g); break;
+    case 1: gemm_kernel_launch_epi<0, 0, 1>(c, grid, g); break;
+    case 2: gemm_kernel_launch_epi<1, 1, 0>(c, grid, g); break;
+    case 3: gemm_kernel_launch_epi<1, 1, 1>(c, grid, g); break;
+    case 4: gemm_kernel_launch_epi<1, 0, 0>(c, grid, g); break;
+    default: gemm_kernel_launch_epi<1, 0, 1>(c, grid, g); break;
+  }
+  if (ks.ksplit > 1) splitk_reduce(c, ks.partial, ks.ksplit, false);
+  ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
+  return ACX_OK;
+}
+
+static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden) {
+  int rc = gemm_validate(ctx, d);
+  if (rc) return rc;
+  const GemmCall c = gemm_call(ctx, d, stream);
+  // (decided before the profiling scope: the two calls are two launches)
+  if ((rc = route_x6_tail_split(c)) != ROUTE_NEXT) return rc;
+  AcxProfScope prof__(ctx, ACX_K_GEMM, c.s);
+  if (ctx && ctx->prof_on) ctx->prof_gemm_flops += 2.0 * d->M * (double)d->N * d->K;
+  const Args g = gemm_args(c);
+  if ((rc = route_sk(c, g)) != ROUTE_NEXT) return rc;
+  if ((rc = route_x6(c, g, job, ridden)) != ROUTE_NEXT) return rc;
+  if ((rc = route_s64(c, g)) != ROUTE_NEXT) return rc;
+  const KSplit ks = generic_ksplit(c);
+  const dim3 grid((unsigned)(((d->M + BM - 1) / BM) * g.tiles_n), (unsigned)ks.ksplit);   // 128x128 tiles x K pieces
+  if ((rc = route_p256(c, g, ks)) != ROUTE_NEXT) return rc;
+  if ((rc = route_w8(c, g, grid, ks)) != ROUTE_NEXT) return rc;
+  if ((rc = route_ring(c, g, ks)) != ROUTE_NEXT) return rc;
+  if ((rc = route_dma_conv(c, g, grid, ks)) != ROUTE_NEXT) return rc;
+  if ((rc = route_dma(c, g, grid, ks)) != ROUTE_NEXT) return rc;
+  return route_gemm_kernel(c, g, grid, ks);
 }
 
 // Split count of the M reduction: a pure function of the shape (so results are run-to-run identical).
@@ -1351,15 +1376,13 @@ extern "C" int acx_gemm_ln(acx_ctx* ctx, const acx_gemm_desc* d, const acx_ln_jo
 extern "C" int64_t acx_gemm_ln_plan(int32_t M, int32_t N, int32_t K, int32_t ncu, int32_t ksplit, double rate, int64_t* rows_ready) {
   if (rows_ready) *rows_ready = 0;
   if (M <= 0 || N <= 0 || K <= 0 || ncu <= 0 || ksplit > 1 || N % 256 || (M & 1) || K % 32) return 0;
-  const int tiles_n = N / 256, xt = ((M + 255) / 256) * tiles_n, nks = K / 32;
-  const int rounds = xt / ncu, rem = xt - rounds * ncu;
-  if (rounds < 1 || rem == 0) return 0;
-  double best = 0.0;                              // (acx_gemm's strip choice at its defaults)
-  const int pick = x6_strip_pick(rem, ncu, &best), strip_ni = best < X6_STRIP_MAX_COST ? pick : 4;
-  const int tail_items = rem * (4 / strip_ni);
-  if (tail_items >= ncu) return 0;
-  if (rows_ready) *rows_ready = x6_ride_rows(M, N, tiles_n, rounds * ncu, ncu - tail_items, nks, strip_ni, 1e30);
-  return x6_ride_rows(M, N, tiles_n, rounds * ncu, ncu - tail_items, nks, strip_ni, rate);
+  X6PlanIn in = {};                               // (acx_gemm's plan at the options' defaults, without a workspace)
+  in.M = M; in.N = N; in.K = K; in.ncu = ncu;
+  in.may_strip = true; in.strip_force = 1;
+  in.may_ride = true; in.ride_cap = 1; in.rate = rate;
+  const X6Plan p = x6_plan(in);
+  if (rows_ready) *rows_ready = p.ready;
+  return p.ride;
 }
 
 extern "C" size_t acx_gemm_tn_group_workspace_bytes(int32_t nprob, const acx_tn_problem* probs) {
@@ -1378,11 +1401,6 @@ extern "C" int acx_gemm_tn_group(acx_ctx* ctx, int32_t nprob, const acx_tn_probl
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = 4 * 32 * TN_ROWF * sizeof(float);
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
-  static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_w8_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
   int i = 0;
   size_t woff = 0;
   while (i < nprob) {
@@ -1427,7 +1445,7 @@ extern "C" int acx_gemm_tn_group(acx_ctx* ctx, int32_t nprob, const acx_tn_probl
     R.blk0[nr] = rblocks; R.n = nr;
     AcxProfScope prof__(ctx, ACX_K_GEMM_TN, s);
     if (ctx && ctx->prof_on) { ctx->prof_gemm_flops += flops; ctx->prof_tn_flops += flops; }
-    hipLaunchKernelGGL(gemm_tn_w8_group_kernel, dim3((unsigned)blocks), dim3(512), lds, s, G);
+    acx_launch_lds<gemm_tn_w8_group_kernel>(dev_slot, dim3((unsigned)blocks), dim3(512), lds, s, G);
     if (nr > 0) hipLaunchKernelGGL(tn_reduce_group_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, R);
   }
   ACX_CHECK_LAUNCH(ctx, "acx_gemm_tn_group");
@@ -1460,6 +1478,10 @@ extern "C" size_t acx_gemm_tn_x6_workspace_bytes(int32_t M, int32_t N1, int32_t 
   if (s > 64) s = 64;
   return (size_t)s * N1 * N2 * sizeof(float);
 }
+template <int CV, int NI, int W14>
+static void tn_x6_launch(int dev_slot, dim3 grid, hipStream_t s, const Args& g) {
+  acx_launch_lds<gemm_x6_p4_kernel<0, 0, 0, CV, 1, 0, NI, W14>>(dev_slot, grid, dim3(256), (size_t)X6_LDS_B, s, g);
+}
 extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stride, int32_t lda, const void* B3, int64_t b_plane_stride,
                               int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N1, int32_t N2, int32_t conv, int32_t gn, int32_t gl,
                               int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream) {
@@ -1490,16 +1512,9 @@ extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stri
   AcxProfScope prof__(ctx, ACX_K_GEMM_TN, s);
   if (ctx && ctx->prof_on) { ctx->prof_gemm_flops += 2.0 * M * (double)N1 * N2; ctx->prof_tn_flops += 2.0 * M * (double)N1 * N2; }
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
-#define ACX_TNX6(CV, NI_, W14_)                                                                      \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];                          \
-    if (!attr_done) { (void)hipFuncSetAttribute((const void*)gemm_x6_p4_kernel<0, 0, 0, CV, 1, 0, NI_, W14_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)X6_LDS_B); attr_done = true; } \
-    hipLaunchKernelGGL((gemm_x6_p4_kernel<0, 0, 0, CV, 1, 0, NI_, W14_>), xgrid, dim3(256), (size_t)X6_LDS_B, s, g); \
-  } while (0)
-  if (mode == 1) { if (conv) ACX_TNX6(1, 4, 0); else ACX_TNX6(0, 4, 0); }
-  else if (mode == 2) { if (conv) ACX_TNX6(1, 2, 0); else ACX_TNX6(0, 2, 0); }
-  else { if (conv) ACX_TNX6(1, 2, 1); else ACX_TNX6(0, 2, 1); }
-#undef ACX_TNX6
+  if (mode == 1) { if (conv) tn_x6_launch<1, 4, 0>(dev_slot, xgrid, s, g); else tn_x6_launch<0, 4, 0>(dev_slot, xgrid, s, g); }
+  else if (mode == 2) { if (conv) tn_x6_launch<1, 2, 0>(dev_slot, xgrid, s, g); else tn_x6_launch<0, 2, 0>(dev_slot, xgrid, s, g); }
+  else { if (conv) tn_x6_launch<1, 2, 1>(dev_slot, xgrid, s, g); else tn_x6_launch<0, 2, 1>(dev_slot, xgrid, s, g); }
   if (split > 1) {
     const int64_t n4 = (int64_t)N1 * N2 / 4;
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)workspace, C, n4, split);
@@ -1578,14 +1593,8 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
         g.sh_gl = __builtin_ctz((unsigned)gl);
         g.sh_grid = __builtin_ctz((unsigned)(gn * gl));
       }
-      const int dev_slot = (ctx ? ctx->device : 0) & 63;
-      static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];
-      if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_p256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TP_LDS_B);
-        attr_done = true;
-      }
       const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
-      hipLaunchKernelGGL(gemm_tn_p256_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(1024), (size_t)TP_LDS_B, s, g, zeros);
+      acx_launch_lds<gemm_tn_p256_kernel>((ctx ? ctx->device : 0) & 63, dim3((unsigned)tiles, (unsigned)splits), dim3(1024), (size_t)TP_LDS_B, s, g, zeros);
       if (splits_out) *splits_out = splits;
       if (splits > 1 && !splits_out) {
         const int64_t n4 = (int64_t)N1 * N2 / 4;
@@ -1614,22 +1623,9 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_GEMM_TN, s);
   if (ctx && ctx->prof_on) { ctx->prof_gemm_flops += 2.0 * M * (double)N1 * N2; ctx->prof_tn_flops += 2.0 * M * (double)N1 * N2; }
-  const int dev_slot = (ctx ? ctx->device : 0) & 63;            // kernel attributes are per device
-  static bool attr_dev_[64] = {}; bool& attr_done = attr_dev_[dev_slot];
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  const bool tn_w8 = ACX_DBG_SWITCH("TN_W8", true);
-  if (tn_w8) {
-    static bool attr8_dev_[64] = {}; bool& attr8_done = attr8_dev_[dev_slot];
-    if (!attr8_done) {
-      (void)hipFuncSetAttribute((const void*)gemm_tn_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr8_done = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_w8_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(512), lds, s, g);
-  } else
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)tiles, (unsigned)splits), dim3(NTHREADS), lds, s, g);
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
+  if (ACX_DBG_SWITCH("TN_W8", true)) acx_launch_lds<gemm_tn_w8_kernel>(dev_slot, dim3((unsigned)tiles, (unsigned)splits), dim3(512), lds, s, g);
+  else acx_launch_lds<gemm_tn_kernel>(dev_slot, dim3((unsigned)tiles, (unsigned)splits), dim3(NTHREADS), lds, s, g);
   if (splits_out) *splits_out = splits;
   if (splits > 1 && !splits_out) {
     const int64_t n4 = (int64_t)N1 * N2 / 4;

@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256) void bn_wide_finalize_kernel(const double* __r
 
 // shared launcher: projection (+ optional fused batch statistics); returns false when the shape does not fit the MFMA kernel
 static bool launch_selector_mfma(const float* x, const float* nc, const float* dirs, float* raw, int64_t rows, int D, int C1,
-                                 double* part, int* nblocks, int ncu, hipStream_t s) {
+                                 double* part, int* nblocks, int ncu, int dev_slot, hipStream_t s) {
   const int NT = (C1 + 15) / 16;
   const size_t lds = ((size_t)16 * NT * (D + 4) + D) * 4;
   if ((D != 64 && D != 128 && D != 256 && D != 512 && D != 768 && D != 1024) || lds > 160 * 1024) return false;
@@ -799,15 +799,8 @@ static bool launch_selector_mfma(const float* x, const float* nc, const float* d
     const dim3 dgrid((unsigned)nbd), dblock(512);
 #define ACX_SELDMA(DD, N_)                                                                                                \
   do {                                                                                                                    \
-    if (part) {                                                                                                           \
-      (void)hipFuncSetAttribute((const void*)selector_project_dma_kernel<DD, N_, true>,                                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dma);                                \
-      hipLaunchKernelGGL((selector_project_dma_kernel<DD, N_, true>), dgrid, dblock, lds_dma, s, x, nc, dirs, raw, rows, C1, part); \
-    } else {                                                                                                              \
-      (void)hipFuncSetAttribute((const void*)selector_project_dma_kernel<DD, N_, false>,                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dma);                                \
-      hipLaunchKernelGGL((selector_project_dma_kernel<DD, N_, false>), dgrid, dblock, lds_dma, s, x, nc, dirs, raw, rows, C1, part); \
-    }                                                                                                                     \
+    if (part) acx_launch_lds<selector_project_dma_kernel<DD, N_, true>>(dev_slot, dgrid, dblock, lds_dma, s, x, nc, dirs, raw, rows, C1, part); \
+    else acx_launch_lds<selector_project_dma_kernel<DD, N_, false>>(dev_slot, dgrid, dblock, lds_dma, s, x, nc, dirs, raw, rows, C1, part); \
   } while (0)
 #define ACX_SELDMA_D(DD) do { if (NT == 1) ACX_SELDMA(DD, 1); else ACX_SELDMA(DD, 2); } while (0)
     switch (D) {
@@ -829,15 +822,8 @@ static bool launch_selector_mfma(const float* x, const float* nc, const float* d
   const dim3 grid((unsigned)nb), block(256);
 #define ACX_SELM(DD, N_)                                                                                                  \
   do {                                                                                                                    \
-    if (part) {                                                                                                           \
-      (void)hipFuncSetAttribute((const void*)selector_project_mfma_kernel<DD, N_, true>,                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-      hipLaunchKernelGGL((selector_project_mfma_kernel<DD, N_, true>), grid, block, lds, s, x, nc, dirs, raw, rows, C1, part); \
-    } else {                                                                                                              \
-      (void)hipFuncSetAttribute((const void*)selector_project_mfma_kernel<DD, N_, false>,                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                    \
-      hipLaunchKernelGGL((selector_project_mfma_kernel<DD, N_, false>), grid, block, lds, s, x, nc, dirs, raw, rows, C1, part); \
-    }                                                                                                                     \
+    if (part) acx_launch_lds<selector_project_mfma_kernel<DD, N_, true>>(dev_slot, grid, block, lds, s, x, nc, dirs, raw, rows, C1, part); \
+    else acx_launch_lds<selector_project_mfma_kernel<DD, N_, false>>(dev_slot, grid, block, lds, s, x, nc, dirs, raw, rows, C1, part); \
   } while (0)
 #define ACX_SELD(DD)                                                         \
   do {                                                                       \
@@ -874,7 +860,7 @@ extern "C" int acx_selector_project(acx_ctx* ctx, const float* x, const float* n
   hipStream_t s = (hipStream_t)stream;
   int nb_unused = 0;
   const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
-  if (launch_selector_mfma(x, ncentroid, dirs, raw, rows, D, C1, nullptr, &nb_unused, ncu, s)) {
+  if (launch_selector_mfma(x, ncentroid, dirs, raw, rows, D, C1, nullptr, &nb_unused, ncu, (ctx ? ctx->device : 0) & 63, s)) {
     ACX_CHECK_LAUNCH(ctx, "acx_selector_project");
     return ACX_OK;
   }
@@ -884,11 +870,7 @@ extern "C" int acx_selector_project(acx_ctx* ctx, const float* x, const float* n
   int64_t nb = (rows + 3) / 4;
   if (nb > 2048) nb = 2048;
   const dim3 grid((unsigned)nb), block(256);
-#define ACX_SEL(V)                                                                                         \
-  do {                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)selector_project_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((selector_project_kernel<V>), grid, block, lds, s, x, ncentroid, dirs, raw, rows, C1); \
-  } while (0)
+#define ACX_SEL(V) acx_launch_lds<selector_project_kernel<V>>((ctx ? ctx->device : 0) & 63, grid, block, lds, s, x, ncentroid, dirs, raw, rows, C1)
   switch (D / 64) {
     case 1: ACX_SEL(1); break;
     case 2: ACX_SEL(2); break;
@@ -997,7 +979,7 @@ extern "C" int acx_selector_project_stats(acx_ctx* ctx, const float* x, const fl
   int nb = 0;
   {
     AcxProfScope prof__(ctx, ACX_K_OTHER, s);
-    if (!launch_selector_mfma(x, ncentroid, dirs, raw, rows, D, C1, (double*)workspace, &nb, ncu, s)) {
+    if (!launch_selector_mfma(x, ncentroid, dirs, raw, rows, D, C1, (double*)workspace, &nb, ncu, (ctx ? ctx->device : 0) & 63, s)) {
       // shape outside the MFMA kernel: projection, then the stand-alone statistics
       int rc = acx_selector_project(ctx, x, ncentroid, dirs, raw, rows, D, C1, stream);
       if (rc != ACX_OK) return rc;
@@ -1229,6 +1211,7 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
   if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_axial_attention: null pointer%s");
   if (tiles <= 0) return ACX_OK;
   const int T = axis == 0 ? gn : gl;
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
   if (gn <= 0 || gl <= 0 || T > 128 || (e != 16 && e != 32 && e != 64) || heads <= 0)
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_axial_attention: need 1 <= axis length <= 128, e in {16,32,64}, heads >= 1%s");
   if (!((T == 16 || T == 32) && (e == 16 || e == 32))) {
@@ -1243,11 +1226,8 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
     const float scale = 1.f / sqrtf((float)e);
     hipStream_t sp = (hipStream_t)stream;
 #define ACX_AXP(TTM_, EE_)                                                                                 \
-  do {                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)axial_attn_fwd_pad_kernel<TTM_, EE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp); \
-    hipLaunchKernelGGL((axial_attn_fwd_pad_kernel<TTM_, EE_>), dim3((unsigned)nbp), dim3(256), ldsp, sp, qkv, out, gn, gl, heads, axis, \
-                       scale, T, tt, G, ngroups);                                                          \
-  } while (0)
+  acx_launch_lds<axial_attn_fwd_pad_kernel<TTM_, EE_>>(dev_slot, dim3((unsigned)nbp), dim3(256), ldsp, sp, qkv, out, gn, gl, heads, axis, \
+                                                       scale, T, tt, G, ngroups)
 #define ACX_AXP_E(TTM_) do { if (e == 64) ACX_AXP(TTM_, 64); else if (e == 32) ACX_AXP(TTM_, 32); else ACX_AXP(TTM_, 16); } while (0)
     if (tt <= 2) ACX_AXP_E(2); else if (tt <= 4) ACX_AXP_E(4); else ACX_AXP_E(8);
 #undef ACX_AXP_E
@@ -1264,11 +1244,8 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
     const float scale = 1.f / sqrtf((float)e);
     hipStream_t sm = (hipStream_t)stream;
 #define ACX_AXF(TT_, EE_)                                                                                  \
-  do {                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)axial_attn_fwd_mfma_kernel<TT_, EE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm); \
-    hipLaunchKernelGGL((axial_attn_fwd_mfma_kernel<TT_, EE_>), dim3((unsigned)nbm), dim3(256), ldsm, sm, qkv, out, gn, gl, heads, axis, \
-                       scale, ngroups);                                                                    \
-  } while (0)
+  acx_launch_lds<axial_attn_fwd_mfma_kernel<TT_, EE_>>(dev_slot, dim3((unsigned)nbm), dim3(256), ldsm, sm, qkv, out, gn, gl, heads, axis, \
+                                                       scale, ngroups)
     if (T == 32) { if (e == 32) ACX_AXF(32, 32); else ACX_AXF(32, 16); }
     else { if (e == 32) ACX_AXF(16, 32); else ACX_AXF(16, 16); }
 #undef ACX_AXF
@@ -1282,11 +1259,7 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
   const size_t lds = (size_t)lpb * T * heads * e * 2 * 4;
   const dim3 grid((unsigned)((nlines + lpb - 1) / lpb)), block(256);
   hipStream_t s = (hipStream_t)stream;
-#define ACX_AX(TT, EE)                                                                                     \
-  do {                                                                                                     \
-    (void)hipFuncSetAttribute((const void*)axial_attn_kernel<TT, EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((axial_attn_kernel<TT, EE>), grid, block, lds, s, qkv, out, tiles, gn, gl, heads, axis, nlines); \
-  } while (0)
+#define ACX_AX(TT, EE) acx_launch_lds<axial_attn_kernel<TT, EE>>(dev_slot, grid, block, lds, s, qkv, out, tiles, gn, gl, heads, axis, nlines)
   if (T == 32 && e == 32) ACX_AX(32, 32);
   else if (T == 32) ACX_AX(32, 16);
   else if (e == 32) ACX_AX(16, 32);
@@ -1702,26 +1675,18 @@ extern "C" int acx_preprocess_frames(acx_ctx* ctx, const unsigned char* frames, 
       const dim3 grid((unsigned)((orows + R - 1) / R), (unsigned)F);
       // every chunk of a band requested up front: at most four chunks of at most 1024 16-byte blocks
       const bool allin = (maxrows + cr - 1) / cr <= 4 && (size_t)cr * W * 3 + 32 <= 4 * 256 * 16;
-#define ACX_PPF(KS)                                                                                 \
-  do {                                                                                              \
-    static bool attr_dev_[64] = {}; int dv_ = 0; (void)hipGetDevice(&dv_); bool& done_ = attr_dev_[dv_ & 63]; \
-    if (!done_) {                                                                                   \
-      (void)hipFuncSetAttribute((const void*)preprocess_fused_kernel<KS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-      (void)hipFuncSetAttribute((const void*)preprocess_fused_kernel<KS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-      done_ = true;                                                                                 \
-    }                                                                                               \
-    if (allin)                                                                                      \
-      hipLaunchKernelGGL((preprocess_fused_kernel<KS, true>), grid, dim3(256), lds, s, frames, out, hbounds, hcoef, vbounds, vcoef, vksize, \
-                         H, W, orows, ocols, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);            \
-    else                                                                                            \
-      hipLaunchKernelGGL((preprocess_fused_kernel<KS, false>), grid, dim3(256), lds, s, frames, out, hbounds, hcoef, vbounds, vcoef, vksize, \
-                         H, W, orows, ocols, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);            \
-  } while (0)
+      int dev = ctx ? ctx->device : 0;                 // (a call without a context: the attribute goes to the current device)
+      if (!ctx) (void)hipGetDevice(&dev);
+#define ACX_PPF_(KS, ALLIN)                                                                         \
+  acx_launch_lds<preprocess_fused_kernel<KS, ALLIN>>(dev, grid, dim3(256), lds, s, frames, out, hbounds, hcoef, vbounds, vcoef, vksize, \
+                                                     H, W, orows, ocols, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2])
+#define ACX_PPF(KS) do { if (allin) ACX_PPF_(KS, true); else ACX_PPF_(KS, false); } while (0)
       switch (hksize) {
         case 5: ACX_PPF(5); break;   case 7: ACX_PPF(7); break;   case 9: ACX_PPF(9); break;
         case 11: ACX_PPF(11); break; case 13: ACX_PPF(13); break; default: ACX_PPF(15); break;
       }
 #undef ACX_PPF
+#undef ACX_PPF_
       ACX_CHECK_LAUNCH(ctx, "acx_preprocess_frames");
       return ACX_OK;
     }

@@ -120,6 +120,21 @@ static inline int acx_check_launch(acx_ctx* ctx, const char* name) {
     if (rc__ != ACX_OK) return rc__;             \
   } while (0)
 
+// Launch of a kernel with dynamic LDS.  A launch above 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize raised first, and
+// that attribute is a per-DEVICE setting: each kernel instantiation keeps the largest size it has asked for on each device
+// (dev_slot = acx_ctx.device, or hipGetDevice, & 63) and raises the attribute only when a launch wants more, so one process may
+// drive several GPUs and a kernel whose LDS size depends on the shape is covered too.
+template <auto Kernel, typename... T>
+static inline void acx_launch_lds(int dev_slot, dim3 grid, dim3 block, size_t lds, hipStream_t s, const T&... args) {
+  static size_t lds_set_[64] = {};
+  size_t& lds_set = lds_set_[dev_slot & 63];
+  if (lds > lds_set) {
+    (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    lds_set = lds;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
+
 // acx_gemm.hip: true when acx_gemm runs `d` on the persistent strip-stream kernel (no partial last wave to split off)
 bool acx_gemm_takes_strip_stream(const acx_gemm_desc* d);
 // acx_norm.hip: LayerNorm of rows row0 .. rows (row0 even) into ACX_BF16X3P planes of `rows` rows -- what acx_gemm_ln's riders left

@@ -1912,14 +1912,14 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
   if (!qkv || !dout || !dqkv) return acx_fail(ctx, ACX_E_BADARG, "acx_seq_attention_bwd: null pointer%s");
   if (tiles <= 0) return ACX_OK;
   const int T = axis == 0 ? gn : gl;
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
   const bool sab_rows = ACX_DBG_SWITCH("SAB_ROWS", false);    // keep the two-launch rows kernel (A/B, debug builds)
   if (e == 64 && gn == 1 && axis == 1 && T <= AB_TP && !sab_rows && ACX_DBG_SWITCH("SAB_MFMA", true)) {
     // text-tower shape up to 80 tokens: the five products on the f32 MFMA, one workgroup per (sequence, head)
     hipStream_t s4 = (hipStream_t)stream;
     AcxProfScope prof4__(ctx, ACX_K_ATTN, s4);
-    (void)hipFuncSetAttribute((const void*)seq_attn_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AB_LDS_B);
-    hipLaunchKernelGGL(seq_attn_bwd_mfma_kernel, dim3((unsigned)(tiles * heads)), dim3(512), (size_t)AB_LDS_B, s4, qkv, dout, dqkv, T,
-                       heads, causal, 0.125f);
+    acx_launch_lds<seq_attn_bwd_mfma_kernel>(dev_slot, dim3((unsigned)(tiles * heads)), dim3(512), (size_t)AB_LDS_B, s4, qkv, dout, dqkv, T,
+                                             heads, causal, 0.125f);
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(mfma)");
     return ACX_OK;
   }
@@ -1929,13 +1929,8 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     AcxProfScope prof3__(ctx, ACX_K_ATTN, s3);
     const size_t lds3 = ((size_t)4 * T * SB_ROWF + 3 * T + 4 + 8 * 2 * ((T + 3) & ~3)) * sizeof(float);
     const dim3 grid3((unsigned)(tiles * heads)), block3(512);
-    if (T <= 64) {
-      (void)hipFuncSetAttribute((const void*)seq_attn_bwd_block_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      hipLaunchKernelGGL((seq_attn_bwd_block_kernel<1>), grid3, block3, lds3, s3, qkv, dout, dqkv, T, heads, causal, 0.125f);
-    } else {
-      (void)hipFuncSetAttribute((const void*)seq_attn_bwd_block_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-      hipLaunchKernelGGL((seq_attn_bwd_block_kernel<2>), grid3, block3, lds3, s3, qkv, dout, dqkv, T, heads, causal, 0.125f);
-    }
+    if (T <= 64) acx_launch_lds<seq_attn_bwd_block_kernel<1>>(dev_slot, grid3, block3, lds3, s3, qkv, dout, dqkv, T, heads, causal, 0.125f);
+    else acx_launch_lds<seq_attn_bwd_block_kernel<2>>(dev_slot, grid3, block3, lds3, s3, qkv, dout, dqkv, T, heads, causal, 0.125f);
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(block)");
     return ACX_OK;
   }
@@ -1965,11 +1960,8 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     const int64_t capm = 2 * (int64_t)(ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256);
     if (nbm > capm) nbm = capm;
 #define ACX_AXB(TT_, EE_)                                                                                    \
-  do {                                                                                                       \
-    (void)hipFuncSetAttribute((const void*)axial_attn_bwd_mfma_kernel<TT_, EE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m); \
-    hipLaunchKernelGGL((axial_attn_bwd_mfma_kernel<TT_, EE_>), dim3((unsigned)nbm), dim3(256), lds_m, sm, qkv, dout, dqkv, gn, gl, heads, \
-                       axis, scale_m, ngroups_m, T);                                                         \
-  } while (0)
+  acx_launch_lds<axial_attn_bwd_mfma_kernel<TT_, EE_>>(dev_slot, dim3((unsigned)nbm), dim3(256), lds_m, sm, qkv, dout, dqkv, gn, gl, heads, \
+                                                       axis, scale_m, ngroups_m, T)
     if (T == 32) { if (e == 32) ACX_AXB(32, 32); else ACX_AXB(32, 16); }
     else { if (e == 32) ACX_AXB(16, 32); else ACX_AXB(16, 16); }
 #undef ACX_AXB
@@ -1988,11 +1980,8 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     const int64_t capp = 2 * (int64_t)(ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256);
     if (nbp > capp) nbp = capp;
 #define ACX_AXBP(TT_, EE_)                                                                                   \
-  do {                                                                                                       \
-    (void)hipFuncSetAttribute((const void*)axial_attn_bwd_mfma_kernel<TT_, EE_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p); \
-    hipLaunchKernelGGL((axial_attn_bwd_mfma_kernel<TT_, EE_, true>), dim3((unsigned)nbp), dim3(256), lds_p, sp, qkv, dout, dqkv, gn, gl, \
-                       heads, axis, scale_p, ngroups_p, T);                                                  \
-  } while (0)
+  acx_launch_lds<axial_attn_bwd_mfma_kernel<TT_, EE_, true>>(dev_slot, dim3((unsigned)nbp), dim3(256), lds_p, sp, qkv, dout, dqkv, gn, gl, \
+                                                             heads, axis, scale_p, ngroups_p, T)
 #define ACX_AXBP_E(TT_) do { if (e == 32) ACX_AXBP(TT_, 32); else ACX_AXBP(TT_, 16); } while (0)
     if (TP == 16) ACX_AXBP_E(16); else if (TP == 32) ACX_AXBP_E(32); else if (TP == 48) ACX_AXBP_E(48); else ACX_AXBP_E(64);
 #undef ACX_AXBP_E
@@ -2013,11 +2002,8 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
   AcxProfScope prof__(ctx, ACX_K_ATTN, s);
   const dim3 grid((unsigned)((ngroups + gpb - 1) / gpb)), block(256);
 #define ACX_SAB(EE)                                                                                          \
-  do {                                                                                                       \
-    (void)hipFuncSetAttribute((const void*)seq_attn_bwd_kernel<EE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((seq_attn_bwd_kernel<EE>), grid, block, lds, s, qkv, dout, dqkv, tiles, gn, gl, heads, axis, causal, \
-                       scale, T, gpb, ngroups);                                                              \
-  } while (0)
+  acx_launch_lds<seq_attn_bwd_kernel<EE>>(dev_slot, grid, block, lds, s, qkv, dout, dqkv, tiles, gn, gl, heads, axis, causal, \
+                                          scale, T, gpb, ngroups)
   if (e == 16) ACX_SAB(16); else if (e == 32) ACX_SAB(32); else ACX_SAB(64);
 #undef ACX_SAB
   ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd");
@@ -2237,13 +2223,7 @@ extern "C" int acx_selector_tail(acx_ctx* ctx, const float* raw, const float* ga
   a.B = B; a.N = N; a.Lg = Lg; a.C1 = C1; a.normal_id = normal_id; a.ktop = ktop; a.kbot = kbot; a.eps = eps;
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_OTHER, s);
-  const int dev_slot = (ctx ? ctx->device : 0) & 63;
-  static size_t attr_dev_[64] = {};
-  if (lds > 64 * 1024 && attr_dev_[dev_slot] < lds) {
-    (void)hipFuncSetAttribute((const void*)selector_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_dev_[dev_slot] = lds;
-  }
-  hipLaunchKernelGGL(selector_tail_kernel, dim3(B), dim3(256), lds, s, a);
+  acx_launch_lds<selector_tail_kernel>((ctx ? ctx->device : 0) & 63, dim3(B), dim3(256), lds, s, a);
   ACX_CHECK_LAUNCH(ctx, "acx_selector_tail");
   return ACX_OK;
 }

@@ -56,7 +56,7 @@ enum { ACX_PREC_F32 = 0, ACX_PREC_BF16 = 1,          /* MFMA arithmetic: exact f
        ACX_PREC_F32X3 = 3,    /* the same drivers and plane layouts with the THREE leading products only (acx_gemm_desc.pairs = 3:
                                  (mid, hi) (hi, mid) (hi, hi)): sixteen significant bits per operand -- an error of ~1e-5 of sum |a||w| per
                                  product, between TF32 and f32 -- at about twice the GEMM rate of ACX_PREC_F32X6.  NOT an f32-accurate
-                                 path: opt-in (precision "bf16x3"); the attention keeps its six-product form */
+                                 path: opt-in (precision "bf16x3"); the planes attention takes its three-product form too (acx_attention_p3n) */
        ACX_PREC_F16X3 = 4,    /* the same drivers with TWO fp16 planes per operand and the three products (lo,hi) (hi,lo) (hi,hi):
                                  the fp16 pair holds the f32 value to 2^-24 (lo normal), every product is exact in f32, the dropped
                                  (lo,lo) term is <= 2^-22: f32-MFMA-level results at the three-product rate, for operands inside fp16's
