@@ -1464,6 +1464,8 @@ extern "C" int acx_concat_features(acx_ctx* ctx, const float* logits, const floa
 // restricted to the rows/columns the centre crop keeps.  HBM-bound: one pass over the uint8 frames.
 namespace {
 
+struct crop_windows { int top[10], left[10], flip[10]; };      // acx_preprocess_crops: the windows of one call, a kernel argument
+
 __device__ __forceinline__ unsigned char clip8_22(int v) {
   v >>= 22;
   return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
@@ -1507,6 +1509,34 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const unsigned cha
   out[i] = (v - mean) / sd;
 }
 
+// the vertical pass of acx_preprocess_crops' two-kernel route: tmp holds ALL ow columns of the resized image (one horizontal pass
+// serves every crop of a frame, mirrored ones included), crop z reads its rows top .. and its columns left .. (right to left
+// when flipped):  out[f * ncrops + z][c][yo][xo] = norm(clip8(0.5 + sum_y tmp[f][ymin + y][xi][c] * k[top + yo][y]))
+__global__ __launch_bounds__(256) void resample_v_crops_kernel(const unsigned char* __restrict__ tmp, float* __restrict__ out,
+                                                               const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                               int ksize, int H, int ow, int crop, int ncrops, crop_windows win,
+                                                               float m0, float m1, float m2, float s0, float s1, float s2) {
+  const int img = blockIdx.y;                            // f * ncrops + z: one image per grid row, so the window is uniform
+  const int per = 3 * crop * crop;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= per) return;
+  const int xo = i % crop;
+  const int yo = (i / crop) % crop;
+  const int c = i / (crop * crop);
+  const int z = img % ncrops;
+  const int64_t f = img / ncrops;
+  const int top = win.top[z], left = win.left[z], flip = win.flip[z];
+  const int xi = left + (flip ? crop - 1 - xo : xo);
+  const int ymin = bounds[2 * (top + yo)], yn = bounds[2 * (top + yo) + 1];
+  const unsigned char* col = tmp + ((f * H + ymin) * ow + xi) * 3 + c;
+  const int* k = kk + (size_t)(top + yo) * ksize;
+  int ss = 1 << 21;
+  for (int y = 0; y < yn; ++y) ss += (int)col[(size_t)y * ow * 3] * k[y];
+  const float v = (float)clip8_22(ss) / 255.f;           // ToTensor: uint8 -> float32 / 255
+  const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+  out[(size_t)img * per + i] = (v - mean) / sd;
+}
+
 // ---- fused variant: one workgroup per (frame, band of R output rows).  Phase 1 resamples the input rows the band needs
 // horizontally into an 8-bit image in LDS (thread = output column: its KS coefficients live in registers; the input rows
 // pass through LDS in chunks), phase 2 resamples vertically out of LDS (thread = four pixels x three
@@ -1516,15 +1546,27 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const unsigned cha
 // registers per thread): the workgroup waits for HBM ONCE instead of once per chunk -- the chunk loop's arithmetic is ~0.3 us
 // per chunk against ~3 us of memory latency, so with sequential chunks a workgroup spent its life waiting (240 x 320 frames:
 // 168 us per 512 frames, 0.42 of the copy rate); the vertical pass's bounds / coefficients come out of LDS as well.
-template <int KS, bool ALLIN>
+// CROPS (acx_preprocess_crops): blockIdx.z = crop; the tables are those of the WHOLE resized image and (top, left, flip)[z]
+// picks the crop's rows top .. top + orows and its columns left .. left + ocols, read right to left when flip is set; the
+// output image is f * ncrops + z.  Without CROPS the tables are already the kept rows / columns and none of this is compiled in.
+template <int KS, bool ALLIN, bool CROPS = false>
 __global__ __launch_bounds__(256) void preprocess_fused_kernel(const unsigned char* __restrict__ in, float* __restrict__ out,
                                                                const int* __restrict__ hb, const int* __restrict__ hk,
                                                                const int* __restrict__ vb, const int* __restrict__ vk, int vks,
                                                                int H, int W, int orows, int ocols, int R, int maxrows, int cr,
-                                                               float m0, float m1, float m2, float s0, float s1, float s2) {
+                                                               float m0, float m1, float m2, float s0, float s1, float s2,
+                                                               crop_windows win, int ncrops) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ptmp[];
   __shared__ float lut[3][256];                  // (v / 255 - mean[c]) / std[c] for v = 0..255: the float tail, evaluated once
   const int f = blockIdx.y, yo0 = blockIdx.x * R, yo1 = min(orows, yo0 + R);
+  size_t oimg = (size_t)f;                                                // output image
+  int left = 0, flip = 0;
+  if constexpr (CROPS) {
+    const int z = blockIdx.z, top = win.top[z];
+    left = win.left[z]; flip = win.flip[z];
+    vb += 2 * top; vk += (size_t)top * vks;
+    oimg = (size_t)f * ncrops + z;
+  }
   const int y0 = vb[2 * yo0];
   const int nrows = min(vb[2 * (yo1 - 1)] + vb[2 * (yo1 - 1) + 1] - y0, maxrows);
   const int rowb = ocols * 3;
@@ -1543,9 +1585,10 @@ __global__ __launch_bounds__(256) void preprocess_fused_kernel(const unsigned ch
   const int xo = t;                                                       // ocols <= 256 (dispatch)
   int k[KS], px[KS];
   if (xo < ocols) {
-    const int xmin = hb[2 * xo];
+    const int xi = CROPS ? left + (flip ? ocols - 1 - xo : xo) : xo;     // column of the table
+    const int xmin = hb[2 * xi];
 #pragma unroll
-    for (int x = 0; x < KS; ++x) { k[x] = hk[(size_t)xo * KS + x]; px[x] = 3 * min(xmin + x, W - 1); }
+    for (int x = 0; x < KS; ++x) { k[x] = hk[(size_t)xi * KS + x]; px[x] = 3 * min(xmin + x, W - 1); }
   }
   const int roww = W * 3;
   __shared__ int svb[2 * 32], svk[32 * 15];      // the band's vertical bounds / coefficients (R <= 32 rows, <= 15 taps)
@@ -1645,7 +1688,7 @@ __global__ __launch_bounds__(256) void preprocess_fused_kernel(const unsigned ch
 #pragma unroll
     for (int e = 0; e < 12; ++e) v[e] = lut[e % 3][clip8_22(acc[e])];
     const size_t plane = (size_t)orows * ocols;
-    float* o = out + (size_t)f * 3 * plane + (size_t)yo * ocols + 4 * g;
+    float* o = out + oimg * 3 * plane + (size_t)yo * ocols + 4 * g;
     *reinterpret_cast<float4*>(o) = make_float4(v[0], v[3], v[6], v[9]);
     *reinterpret_cast<float4*>(o + plane) = make_float4(v[1], v[4], v[7], v[10]);
     *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(v[2], v[5], v[8], v[11]);
@@ -1679,7 +1722,7 @@ extern "C" int acx_preprocess_frames(acx_ctx* ctx, const unsigned char* frames, 
       if (!ctx) (void)hipGetDevice(&dev);
 #define ACX_PPF_(KS, ALLIN)                                                                         \
   acx_launch_lds<preprocess_fused_kernel<KS, ALLIN>>(dev, grid, dim3(256), lds, s, frames, out, hbounds, hcoef, vbounds, vcoef, vksize, \
-                                                     H, W, orows, ocols, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2])
+                                                     H, W, orows, ocols, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], crop_windows{}, 1)
 #define ACX_PPF(KS) do { if (allin) ACX_PPF_(KS, true); else ACX_PPF_(KS, false); } while (0)
       switch (hksize) {
         case 5: ACX_PPF(5); break;   case 7: ACX_PPF(7); break;   case 9: ACX_PPF(9); break;
@@ -1698,5 +1741,75 @@ extern "C" int acx_preprocess_frames(acx_ctx* ctx, const unsigned char* frames, 
   hipLaunchKernelGGL(resample_v_norm_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, (const unsigned char*)tmp, out,
                      vbounds, vcoef, vksize, t2, H, ocols, orows, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   ACX_CHECK_LAUNCH(ctx, "acx_preprocess_frames");
+  return ACX_OK;
+}
+
+// Multi-crop front end (GroupScale -> FiveCrop / TenCrop -> ToTensor -> Normalize; reference gtransforms.py:89-102, 449-477): the
+// tables describe the WHOLE resized image (oh rows, ow columns), every crop is a window of them -- read right to left for the crops
+// of the mirrored image -- and all crops of all frames go out in one launch sequence.  Fused LDS kernel where its limits hold (the
+// uint8 intermediate never reaches memory; a crop's workgroups resample only their own band and columns); otherwise ONE horizontal
+// pass over all ow columns per frame, shared by every crop, and one vertical pass over the crops.
+extern "C" int acx_preprocess_crops(acx_ctx* ctx, const unsigned char* frames, float* out, unsigned char* tmp,
+                                    const int32_t* hbounds, const int32_t* hcoef, int32_t hksize, const int32_t* vbounds,
+                                    const int32_t* vcoef, int32_t vksize, int32_t F, int32_t H, int32_t W, int32_t oh, int32_t ow,
+                                    int32_t crop, int32_t ncrops, const int32_t* windows, const float* mean3, const float* std3,
+                                    void* stream) {
+  AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
+  if (!frames || !out || !tmp || !hbounds || !hcoef || !vbounds || !vcoef || !windows || !mean3 || !std3)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_preprocess_crops: null pointer%s");
+  if (ncrops != 1 && ncrops != 5 && ncrops != 10) return acx_fail(ctx, ACX_E_BADARG, "acx_preprocess_crops: ncrops must be 1, 5 or 10%s");
+  if (crop <= 0 || H <= 0 || W <= 0 || hksize <= 0 || vksize <= 0) return acx_fail(ctx, ACX_E_BADARG, "acx_preprocess_crops: bad geometry%s");
+  if (oh < crop || ow < crop)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_preprocess_crops: scale_size < crop_size (the resized image is smaller than the crop)%s");
+  crop_windows win = {};
+  for (int z = 0; z < ncrops; ++z) {
+    win.top[z] = windows[3 * z]; win.left[z] = windows[3 * z + 1]; win.flip[z] = windows[3 * z + 2] != 0;
+    if (win.top[z] < 0 || win.top[z] > oh - crop || win.left[z] < 0 || win.left[z] > ow - crop)
+      return acx_fail(ctx, ACX_E_BADARG, "acx_preprocess_crops: window outside the resized image%s");
+  }
+  if (F <= 0) return ACX_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t img_in = (size_t)H * W * 3, img_out = (size_t)3 * crop * crop;
+  // the same limits as acx_preprocess_frames' fused path, on the crop's columns
+  if (ACX_DBG_SWITCH("PREPROCESS_FUSED", true) && hksize >= 5 && hksize <= 15 && (hksize & 1) && crop % 4 == 0 && !((uintptr_t)out & 15)) {
+    const int R = vksize <= 9 ? 32 : 16;
+    const int maxrows = (int)((R - 1) * ((vksize - 1) / 4.0) + vksize + 2);
+    const int cr = std::max(1, std::min(16, 12288 / (W * 3)));
+    const size_t lds = (size_t)maxrows * crop * 3 + (size_t)cr * W * 3 + 32;
+    if (lds <= 96 * 1024 && crop <= 256 && (maxrows * crop * 3) % 16 == 0 && vksize <= 15) {
+      const bool allin = (maxrows + cr - 1) / cr <= 4 && (size_t)cr * W * 3 + 32 <= 4 * 256 * 16;
+      int dev = ctx ? ctx->device : 0;
+      if (!ctx) (void)hipGetDevice(&dev);
+      for (int f0 = 0; f0 < F; f0 += 65535) {            // grid.y <= 65535 frames per launch
+        const dim3 grid((unsigned)((crop + R - 1) / R), (unsigned)std::min(65535, F - f0), (unsigned)ncrops);
+        const unsigned char* in_ = frames + (size_t)f0 * img_in;
+        float* out_ = out + (size_t)f0 * ncrops * img_out;
+#define ACX_PPC_(KS, ALLIN)                                                                         \
+  acx_launch_lds<preprocess_fused_kernel<KS, ALLIN, true>>(dev, grid, dim3(256), lds, s, in_, out_, hbounds, hcoef, vbounds, vcoef, vksize, \
+                                                           H, W, crop, crop, R, maxrows, cr, mean3[0], mean3[1], mean3[2], std3[0], std3[1], \
+                                                           std3[2], win, ncrops)
+#define ACX_PPC(KS) do { if (allin) ACX_PPC_(KS, true); else ACX_PPC_(KS, false); } while (0)
+        switch (hksize) {
+          case 5: ACX_PPC(5); break;   case 7: ACX_PPC(7); break;   case 9: ACX_PPC(9); break;
+          case 11: ACX_PPC(11); break; case 13: ACX_PPC(13); break; default: ACX_PPC(15); break;
+        }
+#undef ACX_PPC
+#undef ACX_PPC_
+      }
+      ACX_CHECK_LAUNCH(ctx, "acx_preprocess_crops");
+      return ACX_OK;
+    }
+  }
+  const int fmax = std::max(1, 65535 / ncrops);          // grid.y = images of a launch
+  for (int f0 = 0; f0 < F; f0 += fmax) {
+    const int nf = std::min(fmax, F - f0);
+    const int64_t t1 = (int64_t)nf * H * ow * 3;
+    hipLaunchKernelGGL(resample_h_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, s, frames + (size_t)f0 * img_in,
+                       tmp + (size_t)f0 * H * ow * 3, hbounds, hcoef, hksize, t1, H, W, ow);
+    hipLaunchKernelGGL(resample_v_crops_kernel, dim3((unsigned)((img_out + 255) / 256), (unsigned)(nf * ncrops)), dim3(256), 0, s,
+                       (const unsigned char*)(tmp + (size_t)f0 * H * ow * 3), out + (size_t)f0 * ncrops * img_out, vbounds, vcoef,
+                       vksize, H, ow, crop, ncrops, win, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  }
+  ACX_CHECK_LAUNCH(ctx, "acx_preprocess_crops");
   return ACX_OK;
 }

@@ -1,0 +1,366 @@
+"""Feature files from frame folders: `<frames_root>/<video>/{:06d}.jpg` -> `<out_root>/<video>.npy`, float32 `[T * ncrops, D]`,
+row `t * ncrops + c` = crop c of frame t -- the files `feature_stream.py`, `feature_index.py` and the reference's
+`data.load_from_features=True` route read (feature_dataset.py:326,347).
+
+Per video: frames are decoded on a thread pool into two pinned uint8 buffers in rotation (the reference's
+`Image.open(...).convert("RGB")`, video_dataset.py:204), copied to the device on a side stream, cropped and normalised by ONE
+`preprocess_crops` call per batch, encoded by the CLIP image encoder at its own precision, and the rows come back asynchronously
+into a pinned `[T * ncrops, D]` buffer.  A batch is `max(1, chunk // ncrops)` frames, i.e. one encoder launch of at most `chunk`
+rows; decoding batch k + 1 overlaps the GPU's work on batch k.
+
+    python -m anomalyclip_amd.extract --arch ViT-B/16 --weights last.ckpt --frames-root frames --out-root features --ncrops 5
+"""
+from __future__ import annotations
+
+import os
+import re
+import sys
+from concurrent.futures import ThreadPoolExecutor
+from typing import Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+TEMPLATE = "{:06d}.jpg"                # the reference's default imagefile_template (video_dataset.py:171)
+MAX_DECODE_THREADS = 16                # the decode pool never grows beyond this, whatever the machine has
+
+
+# ---------------------------------------------------------------------------------------------------------------- frames
+def read_annotations(path: str) -> List[Tuple[str, int, int]]:
+    """rows `path start end label...` (video_dataset.py:33-38: four or more fields) -> [(path, start, end)], end inclusive"""
+    out = []
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            row = line.strip().split()
+            if not row:
+                continue
+            if len(row) < 4:
+                raise ValueError(f"{path}:{n}: expected `path start end label...`, got {line.strip()!r}")
+            out.append((row[0], int(row[1]), int(row[2])))
+    return out
+
+
+def _template_regex(template: str):
+    """a regex whose group 1 is the frame number of a file name made by `template`"""
+    m = re.fullmatch(r"(.*)\{(?::0?(\d*)d?)?\}(.*)", template)
+    if m is None:
+        raise ValueError(f"imagefile template {template!r} needs exactly one integer field, like '{{:06d}}.jpg'")
+    return re.compile(re.escape(m.group(1)) + r"(\d+)" + re.escape(m.group(3)))
+
+
+class FrameFolderReader:
+    """The frames `start ... end` (inclusive) of `<frames_root>/<video>/<template>`; without a range, every file of the folder
+    that matches the template, in frame order.  `batches(n)` decodes n frames at a time on a thread pool into two uint8 buffers
+    in rotation (pinned when a GPU is there), one batch ahead of its consumer."""
+
+    def __init__(self, frames_root: str, video: str, start: Optional[int] = None, end: Optional[int] = None,
+                 template: str = TEMPLATE, threads: int = 8, pinned: Optional[bool] = None):
+        self.dir = os.path.join(frames_root, video)
+        self.template = template
+        if (start is None) != (end is None):
+            raise ValueError("start and end go together")
+        if start is None:
+            rx = _template_regex(template)
+            idx = []
+            for name in os.listdir(self.dir):
+                m = rx.fullmatch(name)
+                if m and template.format(int(m.group(1))) == name:
+                    idx.append(int(m.group(1)))
+            self.indices = sorted(idx)
+        else:
+            self.indices = list(range(int(start), int(end) + 1))
+        if not self.indices:
+            raise ValueError(f"{self.dir}: no frames ({template})")
+        self.threads = max(1, min(int(threads), MAX_DECODE_THREADS))
+        self.pinned = torch.cuda.is_available() if pinned is None else bool(pinned)
+        self._buf = [None, None]
+        self.copied = [None, None]      # per slot: the consumer's event after the copy that READ the buffer (set by the consumer)
+        self._pool = None
+        self._size = None
+
+    def __len__(self) -> int:
+        return len(self.indices)
+
+    def path(self, i: int) -> str:
+        return os.path.join(self.dir, self.template.format(self.indices[i]))
+
+    @property
+    def frame_size(self) -> Tuple[int, int]:
+        """(H, W) of the video: that of its first frame"""
+        if self._size is None:
+            from PIL import Image
+            with Image.open(self.path(0)) as im:
+                self._size = (im.size[1], im.size[0])
+        return self._size
+
+    def pool(self) -> ThreadPoolExecutor:
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=self.threads)
+        return self._pool
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def _decode(self, i: int, dst: np.ndarray):
+        from PIL import Image
+        p = self.path(i)
+        with Image.open(p) as im:
+            a = np.asarray(im.convert("RGB"))
+        if a.shape != dst.shape:
+            raise ValueError(f"{p}: frame is {a.shape[0]} x {a.shape[1]}, the video's first frame is {dst.shape[0]} x {dst.shape[1]}")
+        dst[...] = a
+
+    def _fill(self, i0: int, i1: int, slot: int) -> torch.Tensor:
+        H, W = self.frame_size
+        if self.copied[slot] is not None:             # the copy that read this buffer two batches ago must be over
+            self.copied[slot].synchronize()
+            self.copied[slot] = None
+        buf = self._buf[slot]
+        if buf is None or buf.shape[0] < i1 - i0:
+            buf = torch.empty(i1 - i0, H, W, 3, dtype=torch.uint8)
+            buf = buf.pin_memory() if self.pinned else buf
+            self._buf[slot] = buf
+        view = buf[: i1 - i0]
+        dst = view.numpy()
+        list(self.pool().map(lambda j: self._decode(i0 + j, dst[j]), range(i1 - i0)))
+        return view
+
+    def batches(self, n: int) -> Iterator[Tuple[int, torch.Tensor]]:
+        """(slot, uint8 [k, H, W, 3]) for consecutive groups of n frames; batch k + 1 is being decoded while k is consumed.  The
+        consumer of an asynchronous copy stores its event in `self.copied[slot]`: the slot is refilled only after it."""
+        T = len(self)
+        spans = [(i, min(T, i + n)) for i in range(0, T, n)]
+        with ThreadPoolExecutor(max_workers=1) as driver:
+            try:
+                fut = driver.submit(self._fill, *spans[0], 0)
+                for k in range(len(spans)):
+                    view = fut.result()
+                    fut = driver.submit(self._fill, *spans[k + 1], (k + 1) & 1) if k + 1 < len(spans) else None
+                    yield k & 1, view
+            finally:
+                self.close()
+
+
+class _ArrayFrames:
+    """decoded frames already in memory ([T, H, W, 3] uint8, pinned or not): the same interface, nothing to decode"""
+
+    def __init__(self, frames):
+        self.frames = torch.as_tensor(frames)
+        if self.frames.dtype != torch.uint8 or self.frames.dim() != 4 or self.frames.shape[-1] != 3:
+            raise ValueError("frames must be uint8 [T, H, W, 3]")
+        self.copied = [None, None]
+
+    def __len__(self):
+        return self.frames.shape[0]
+
+    def batches(self, n: int):
+        for k, i in enumerate(range(0, len(self), n)):
+            yield k & 1, self.frames[i:i + n]
+
+
+# ---------------------------------------------------------------------------------------------------------------- writer
+def feature_path(out_path: str) -> str:
+    return out_path if out_path.endswith(".npy") else out_path + ".npy"
+
+
+def is_complete(out_path: str, shape: Tuple[int, int]) -> bool:
+    """an existing feature file whose header states float32 `shape` (a leftover `.tmp` beside it does not count)"""
+    from .feature_stream import FeatureStream
+    p = feature_path(out_path)
+    if not os.path.isfile(p):
+        return False
+    try:
+        with open(p, "rb") as fh:
+            got, fortran, dtype = FeatureStream._npy_header(fh)
+    except Exception:
+        return False
+    return tuple(got) == tuple(shape) and not fortran and dtype == np.dtype("<f4")
+
+
+def write_features(out_path: str, rows: np.ndarray) -> str:
+    """np.save format, float32 [T * ncrops, D]: written beside its place as `<out>.npy.tmp` (a stale one is replaced), then moved
+    into place atomically -- a reader never sees a half-written file under the final name"""
+    p = feature_path(out_path)
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    assert rows.ndim == 2
+    os.makedirs(os.path.dirname(os.path.abspath(p)), exist_ok=True)
+    tmp = p + ".tmp"
+    with open(tmp, "wb") as fh:
+        np.save(fh, rows, allow_pickle=False)
+    os.replace(tmp, p)
+    return p
+
+
+# ---------------------------------------------------------------------------------------------------------------- extractor
+def _encoder_of(net_or_encoder):
+    return getattr(net_or_encoder, "image_encoder", net_or_encoder)
+
+
+def batch_frames(encoder, ncrops: int) -> int:
+    """frames per batch: one encoder launch of at most `encoder.chunk` rows"""
+    return max(1, int(encoder.chunk) // ncrops)
+
+
+def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False) -> dict:
+    """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
+    Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
+    from .preprocess import preprocess_crops
+    encoder = _encoder_of(encoder)
+    if encoder.training and any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in encoder.modules()):
+        raise ValueError(f"{getattr(encoder, 'arch', type(encoder).__name__)}: extraction needs eval mode (call .eval()): in "
+                         "training mode BatchNorm takes its statistics from each batch")
+    reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
+    T, D, R = len(reader), int(encoder.output_dim), int(encoder.input_resolution)
+    shape = (T * ncrops, D)
+    if not overwrite and is_complete(out_path, shape):
+        return {"written": False, "frames": T, "rows": shape[0]}
+    dev = next(encoder.parameters()).device
+    if dev.type != "cuda":
+        raise ValueError("the encoder must be on the GPU")
+    out = torch.empty(shape, dtype=torch.float32).pin_memory()
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(device=dev)
+    r0 = 0
+    with torch.no_grad():
+        for slot, view in reader.batches(batch_frames(encoder, ncrops)):
+            with torch.cuda.stream(side):
+                x8 = view.to(dev, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            reader.copied[slot] = ev
+            cur.wait_event(ev)
+            x8.record_stream(cur)
+            x = preprocess_crops(x8, R, scale_size, ncrops)
+            rows = encoder(x.view(-1, 3, R, R))
+            out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
+            r0 += rows.shape[0]
+    assert r0 == shape[0], (r0, shape)
+    cur.synchronize()
+    write_features(out_path, out.numpy())
+    return {"written": True, "frames": T, "rows": shape[0]}
+
+
+def list_videos(frames_root: str, template: str = TEMPLATE) -> List[str]:
+    """every folder under frames_root that holds a file matching the template, relative to it, sorted"""
+    rx = _template_regex(template)
+    out = []
+    for d, subdirs, files in os.walk(frames_root):
+        subdirs.sort()
+        if any(rx.fullmatch(f) for f in files):
+            out.append(os.path.relpath(d, frames_root))
+    return sorted(out)
+
+
+def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root: str, out_root: str, ncrops: int = 1,
+                    scale_size: Optional[int] = None, overwrite: bool = False, template: str = TEMPLATE,
+                    decode_threads: int = 8, log=None) -> dict:
+    """Every video of the annotation file (rows `path start end label...`; without one: every frame folder under frames_root)
+    -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  Returns {written, skipped, frames, rows}."""
+    encoder = _encoder_of(net_or_encoder)
+    if annotation_file:
+        videos = read_annotations(annotation_file)
+    else:
+        videos = [(v, None, None) for v in list_videos(frames_root, template)]
+    counts = {"written": 0, "skipped": 0, "frames": 0, "rows": 0}
+    for video, start, end in videos:
+        reader = FrameFolderReader(frames_root, video, start, end, template, decode_threads)
+        try:
+            r = extract_video(encoder, reader, os.path.join(out_root, video), ncrops, scale_size, overwrite)
+        finally:
+            reader.close()
+        counts["written" if r["written"] else "skipped"] += 1
+        if r["written"]:
+            counts["frames"] += r["frames"]
+            counts["rows"] += r["rows"]
+        if log:
+            log(f"{'wrote' if r['written'] else 'kept '} {feature_path(os.path.join(out_root, video))}  [{r['rows']} rows]")
+    return counts
+
+
+# ---------------------------------------------------------------------------------------------------------------- command line
+def build_image_encoder(arch: str, precision: str = "auto", chunk: int = 512):
+    """the CLIP image encoder of `arch`, as AnomalyCLIP builds it"""
+    from .components.anomaly_clip import geometry_of_arch
+    from .components.clip_resnet import ModifiedResNet
+    from .components.clip_vit import VisionTransformer
+    geom = geometry_of_arch(arch)
+    if geom.is_resnet:
+        return ModifiedResNet(geom.vision_layers, geom.embed_dim, geom.resnet_heads, geom.image_resolution, geom.vision_width,
+                              precision=precision, chunk=chunk, arch=arch)
+    return VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width, geom.vision_layers,
+                             geom.vision_heads, geom.embed_dim, precision=precision, chunk=chunk, arch=arch)
+
+
+def load_encoder_weights(encoder, arch: str, weights) -> None:
+    """weights: a Lightning .ckpt (`net.image_encoder.*`), a dict holding `state_dict`, an AnomalyCLIP state_dict
+    (`image_encoder.*`) or the encoder's own state_dict; a checkpoint of another backbone is a ValueError naming both."""
+    from .checkpoint import split_lightning_state_dict
+    from .components.anomaly_clip import _describe, geometry_from_state_dict, geometry_of_arch
+    ck = torch.load(weights, map_location="cpu", weights_only=False) if isinstance(weights, str) else weights
+    sd = split_lightning_state_dict(ck.get("state_dict", ck) if isinstance(ck, dict) else ck)
+    if not any(k.startswith("image_encoder.") for k in sd):
+        sd = {"image_encoder." + k: v for k, v in sd.items()}
+    theirs, mine = geometry_from_state_dict(sd), geometry_of_arch(arch)
+    vision = ("image_resolution", "vision_layers", "vision_width", "vision_patch_size", "embed_dim")
+    if theirs is not None and any(getattr(theirs, f) != getattr(mine, f) for f in vision):
+        raise ValueError(f"the weights do not match arch {arch!r}: they hold {_describe(theirs)}, {arch} is {_describe(mine)}")
+    encoder.load_state_dict({k[len("image_encoder."):]: v for k, v in sd.items() if k.startswith("image_encoder.")}, strict=True)
+
+
+def _parser():
+    import argparse
+    from .components.anomaly_clip import _ARCH
+    from .components.clip_vit import PRECISIONS
+    p = argparse.ArgumentParser(prog="python -m anomalyclip_amd.extract", description="CLIP feature files from frame folders")
+    p.add_argument("--arch", required=True, choices=sorted(_ARCH))
+    p.add_argument("--weights", required=True, help="Lightning .ckpt, AnomalyCLIP state_dict or image-encoder state_dict")
+    p.add_argument("--frames-root", required=True)
+    p.add_argument("--out-root", required=True)
+    p.add_argument("--annotations", default=None, help="rows `path start end label...`; default: every folder of --frames-root")
+    p.add_argument("--ncrops", type=int, default=1, choices=(1, 5, 10))
+    p.add_argument("--scale-size", type=int, default=None, help="shorter side before cropping (default: crop, or crop * 8 // 7)")
+    p.add_argument("--precision", default="auto", choices=sorted(PRECISIONS))
+    p.add_argument("--overwrite", action="store_true")
+    return p
+
+
+def parse_args(argv: Optional[Sequence[str]] = None):
+    """argparse's behaviour for unknown arguments (exit status 2, `unrecognized arguments: ...`), and the same exit for arguments
+    that contradict each other: a --scale-size below the arch's resolution, a --precision the arch's encoder does not run."""
+    from .components.anomaly_clip import geometry_of_arch
+    from .components.clip_resnet import check_resnet_precision
+    from .components.clip_vit import check_vit_precision
+    p = _parser()
+    a = p.parse_args(argv)
+    geom = geometry_of_arch(a.arch)
+    if a.scale_size is not None and a.scale_size < geom.image_resolution:
+        p.error(f"--scale-size {a.scale_size} conflicts with --arch {a.arch}: its crops are {geom.image_resolution} pixels")
+    try:
+        if geom.is_resnet:
+            check_resnet_precision(a.precision, a.arch, geom.vision_width)
+        else:
+            check_vit_precision(a.precision, geom.grid ** 2 + 1, geom.vision_width, a.arch, geom.image_resolution, geom.vision_patch_size)
+    except ValueError as e:
+        p.error(f"--precision {a.precision} conflicts with --arch {a.arch}: {e}")
+    for name, path in (("--weights", a.weights), ("--frames-root", a.frames_root), ("--annotations", a.annotations)):
+        if path is not None and not os.path.exists(path):
+            p.error(f"{name} {path}: no such file or directory")
+    return a
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    a = parse_args(argv)
+    enc = build_image_encoder(a.arch, a.precision)
+    load_encoder_weights(enc, a.arch, a.weights)
+    enc = enc.to(torch.device("cuda", torch.cuda.current_device())).eval()
+    counts = extract_dataset(enc, a.annotations, a.frames_root, a.out_root, a.ncrops, a.scale_size, a.overwrite,
+                             log=lambda s: print(s, file=sys.stderr))
+    import json
+    print(json.dumps(counts))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -96,3 +96,72 @@ def preprocess_frames(frames_u8: torch.Tensor, size: int = 224, mean=CLIP_MEAN, 
     L.check(L.lib().acx_preprocess_frames(h, frames_u8.data_ptr(), out.data_ptr(), tmp.data_ptr(), hb.data_ptr(), hk.data_ptr(),
                                           hks, vb.data_ptr(), vk.data_ptr(), vks, F, H, W, size, size, m, s, ops._stream()), h)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Multi-crop front end: GroupScale(scale_size) -> CenterCrop / FiveCrop / TenCrop(crop_size) -> ToTensor -> Normalize
+# (reference gtransforms.py:89-102, 449-477; the crops are torchvision's published five_crop / ten_crop).
+def scaled_size(h: int, w: int, scale_size: int):
+    """(oh, ow) of Resize(scale_size) on (h, w): the shorter side becomes scale_size, the other int(scale_size * long / short)"""
+    if w <= h:
+        return int(scale_size * h / w), scale_size
+    return scale_size, int(scale_size * w / h)
+
+
+def default_scale_size(crop_size: int, ncrops: int) -> int:
+    """one crop: the reference's transform (scale == crop); 5 / 10 crops: the usual 8 / 7 (256 for 224, 384 for 336)"""
+    return crop_size if ncrops == 1 else crop_size * 8 // 7
+
+
+def crop_windows(h: int, w: int, scale_size: int, crop_size: int, ncrops: int):
+    """The crops of an (h, w) frame as windows of its resized image: [(top, left, flip)] in output order, `top` / `left` in
+    rows / columns of the resized image.  flip: the crop belongs to the horizontally mirrored image -- its window (t, l) there is
+    columns ow - C - l .. of the unmirrored image, read right to left; `left` is already that unmirrored column.
+    1: centre.  5: tl, tr, bl, br, centre.  10: those five, then the same five of the mirrored image."""
+    if ncrops not in (1, 5, 10):
+        raise ValueError(f"ncrops must be 1, 5 or 10, not {ncrops!r}")
+    if scale_size < crop_size:
+        raise ValueError(f"scale_size {scale_size} is smaller than crop_size {crop_size}")
+    oh, ow = scaled_size(h, w, scale_size)
+    C_ = crop_size
+    centre = (int(round((oh - C_) / 2.0)), int(round((ow - C_) / 2.0)))
+    if ncrops == 1:
+        return [(centre[0], centre[1], False)]
+    five = [(0, 0), (0, ow - C_), (oh - C_, 0), (oh - C_, ow - C_), centre]
+    wins = [(t, l, False) for t, l in five]
+    if ncrops == 10:
+        wins += [(t, ow - C_ - l, True) for t, l in five]
+    return wins
+
+
+@lru_cache(maxsize=16)
+def _full_tables(h: int, w: int, scale_size: int, device_str: str):
+    """the tables of the WHOLE resized image (every crop is a window of them)"""
+    oh, ow = scaled_size(h, w, scale_size)
+    hb, hk, hks = _coeffs(w, ow)
+    vb, vk, vks = _coeffs(h, oh)
+    dev = torch.device(device_str)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return oh, ow, t(hb), t(hk), hks, t(vb), t(vk), vks
+
+
+def preprocess_crops(frames_u8: torch.Tensor, crop_size: int, scale_size=None, ncrops: int = 1, mean=CLIP_MEAN,
+                     std=CLIP_STD) -> torch.Tensor:
+    """frames_u8: [F, H, W, 3] uint8 on the device -> [F, ncrops, 3, crop_size, crop_size] float32: image f * ncrops + c is crop c
+    of frame f (the row order of a feature file).  One library call for all crops of all frames."""
+    assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[-1] == 3 and frames_u8.is_contiguous()
+    if scale_size is None:
+        scale_size = default_scale_size(crop_size, ncrops)
+    F, H, W, _ = frames_u8.shape
+    wins = crop_windows(H, W, scale_size, crop_size, ncrops)
+    oh, ow, hb, hk, hks, vb, vk, vks = _full_tables(H, W, scale_size, str(frames_u8.device))
+    out = torch.empty(F, ncrops, 3, crop_size, crop_size, dtype=torch.float32, device=frames_u8.device)
+    tmp = torch.empty(F, H, ow, 3, dtype=torch.uint8, device=frames_u8.device)
+    m = (C.c_float * 3)(*mean)
+    s = (C.c_float * 3)(*std)
+    wv = (C.c_int32 * (3 * ncrops))(*[int(v) for win in wins for v in win])
+    h = ops._h(frames_u8)
+    L.check(L.lib().acx_preprocess_crops(h, frames_u8.data_ptr(), out.data_ptr(), tmp.data_ptr(), hb.data_ptr(), hk.data_ptr(),
+                                         hks, vb.data_ptr(), vk.data_ptr(), vks, F, H, W, oh, ow, crop_size, ncrops, wv, m, s,
+                                         ops._stream()), h)
+    return out

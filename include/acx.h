@@ -491,6 +491,22 @@ int acx_preprocess_frames(acx_ctx* ctx, const unsigned char* frames, float* out,
                           const int32_t* vcoef, int32_t vksize, int32_t F, int32_t H, int32_t W, int32_t orows,
                           int32_t ocols, const float* mean3, const float* std3, void* stream);
 
+/* acx_preprocess_crops: decoded uint8 RGB frames [F,H,W,3] -> [F,ncrops,3,crop,crop] f32, the crop index minor to the
+ * frame index: GroupScale (shorter side -> scale_size, BICUBIC as PIL does it; reference gtransforms.py:89-102), then
+ * the 1 / 5 / 10 crops of torchvision's CenterCrop / FiveCrop / TenCrop (gtransforms.py:449-477: tl, tr, bl, br, centre,
+ * then the same five of the horizontally mirrored image), /255 and Normalize -- all crops of all frames in one launch
+ * sequence.  hbounds/hcoef ([ow,2] / [ow,hksize]) and vbounds/vcoef ([oh,2] / [oh,vksize]) are the tables of the WHOLE
+ * resized image (oh x ow); windows is a HOST array of ncrops x (top, left, flip): the crop is rows top..top+crop and
+ * columns left..left+crop of the resized image, read right to left when flip != 0 (a window (t, l) of the mirrored
+ * image is (t, ow - crop - l, 1) here).  tmp: [F,H,ow,3] uint8 scratch.  mean3/std3 are HOST pointers.
+ * ACX_E_BADARG: ncrops not 1, 5 or 10; oh or ow below crop (scale_size < crop_size); a window outside the image.
+ * F * ncrops beyond a launch's grid limits is split inside the call. */
+int acx_preprocess_crops(acx_ctx* ctx, const unsigned char* frames, float* out, unsigned char* tmp,
+                         const int32_t* hbounds, const int32_t* hcoef, int32_t hksize, const int32_t* vbounds,
+                         const int32_t* vcoef, int32_t vksize, int32_t F, int32_t H, int32_t W, int32_t oh, int32_t ow,
+                         int32_t crop, int32_t ncrops, const int32_t* windows, const float* mean3, const float* std3,
+                         void* stream);
+
 /* utility: x[rows, cols] (f32, leading dimension ld) -> three dense bf16 planes dst + p * plane_stride_bytes, [rows, cols] each:
  * hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (each subtraction exact in f32): the operands of
  * acx_gemm_desc.pairs = 6.  cols % 4 == 0, 16-byte aligned src rows / 8-byte aligned planes. */
