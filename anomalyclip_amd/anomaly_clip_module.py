@@ -250,12 +250,28 @@ class AnomalyCLIPModule(_Base):
                 f = self.net.image_encoder(feats.view(-1, c, h, w)[:n].to(dev))
             ops.colsum_(acc, f)
             count += f.shape[0]
-        cnt = torch.tensor([float(count)], device=dev)
+        return self._finish_ncentroid(acc, count)
+
+    def _finish_ncentroid(self, acc: torch.Tensor, count: int) -> torch.Tensor:
+        cnt = torch.tensor([float(count)], device=acc.device)
         if parallel.is_distributed():
             parallel.all_reduce_sum_(acc)
             parallel.all_reduce_sum_(cnt)
         self._set_ncentroid(acc / cnt)
         return self.ncentroid
+
+    @torch.no_grad()
+    def compute_ncentroid_resident(self, videos) -> torch.Tensor:
+        """compute_ncentroid over feature files that already sit in device memory: `videos` are the [T, D] row blocks of the
+        normal training videos in file order (AnomalyCLIPDataModule.resident_normal_videos: one crop, stride 1, where the
+        test-mode tile's first T rows ARE the file's rows).  The same rows go through the same per-video ops.colsum_ calls, so
+        the result is bit-identical to the loader path; no file is read a second time."""
+        acc = torch.zeros(self.net.embedding_dim, dtype=torch.float32, device=self.device)
+        count = 0
+        for f in videos:
+            ops.colsum_(acc, f)
+            count += f.shape[0]
+        return self._finish_ncentroid(acc, count)
 
     def _set_ncentroid(self, value: torch.Tensor):
         """ncentroid lives in ONE persistent device buffer: reloads copy into it, so its address -- part of the temporal
@@ -276,8 +292,12 @@ class AnomalyCLIPModule(_Base):
         dm = self._datamodule()
         if dm is None:
             raise RuntimeError(f"{f} does not exist and there is no trainer.datamodule to compute it from")
-        loader = dm.train_dataloader_test_mode()
-        self.compute_ncentroid(loader, bool(_get(_get(dm, "hparams"), "load_from_features", True)))
+        resident = dm.resident_normal_videos() if hasattr(dm, "resident_normal_videos") else None
+        if resident is not None:
+            self.compute_ncentroid_resident(resident)
+        else:
+            loader = dm.train_dataloader_test_mode()
+            self.compute_ncentroid(loader, bool(_get(_get(dm, "hparams"), "load_from_features", True)))
         if parallel.rank() == 0:                 # the reference lets every rank write the same file
             torch.save(self.ncentroid.cpu(), f)
 

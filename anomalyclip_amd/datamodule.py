@@ -1,0 +1,179 @@
+"""`AnomalyCLIPDataModule` for pre-extracted feature files (the reference's src/data/anomaly_clip_datamodule.py with
+`load_from_features: true`), without Lightning: same hyper-parameter keys, same loader methods, same batch tuples.
+
+Training batches come from a `FeatureBank` resident in device memory through two `ResidentTrainLoader`s (normal / abnormal
+videos, batch_size // 2 each: anomaly_clip_datamodule.py:144-163); the test-mode loaders stream the files through
+`FeatureStream` and add the per-frame labels of the temporal annotation file (feature_dataset.py:329-345)."""
+from __future__ import annotations
+
+import os
+from pathlib import Path
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .anomaly_clip_module import AttrDict
+from .feature_bank import FeatureBank, ResidentTrainLoader
+from .feature_stream import FeatureStream
+
+HPARAM_KEYS = ("frames_root", "annotation_file_normal", "annotation_file_anomaly", "annotation_file_test",
+               "annotation_file_temporal_test", "labels_file", "normal_id", "num_classes", "num_segments", "seg_length", "ncrops",
+               "stride", "batch_size", "batch_size_test", "load_from_features", "visualize", "image_tmpl")
+_DEFAULTS = dict(annotation_file_temporal_test=None, labels_file=None, num_segments=32, seg_length=16, ncrops=1, stride=1,
+                 batch_size=64, batch_size_test=1, load_from_features=True, visualize=False, image_tmpl="{:06d}.jpg")
+
+
+class VideoRecord:
+    """one annotation row `path start_frame end_frame label` (feature_dataset.py:42-95)"""
+
+    def __init__(self, row: Sequence[str], root: str, where: str):
+        if len(row) != 4:
+            raise ValueError(f"{where}: expected `path start_frame end_frame label`, got {' '.join(row)!r}")
+        self.path = os.path.join(root, row[0]) + ".npy"
+        self.start_frame, self.end_frame, self.label = int(row[1]), int(row[2]), int(row[3])
+
+    @property
+    def num_frames(self) -> int:
+        return self.end_frame - self.start_frame + 1            # the end frame is inclusive
+
+
+def read_annotation_file(path: str, root: str) -> List[VideoRecord]:
+    with open(path) as fh:
+        return [VideoRecord(line.strip().split(), root, f"{path}:{i + 1}") for i, line in enumerate(fh) if line.strip()]
+
+
+def read_temporal_annotations(path: Optional[str]) -> Dict[str, np.ndarray]:
+    """{video stem: int64 [pairs, 2] of (start, stop)}: key = stem of the first column, values = the fields from the third on"""
+    out: Dict[str, np.ndarray] = {}
+    if path:
+        with open(path) as fh:
+            for line in fh:
+                f = line.strip().split()
+                if f:
+                    v = np.asarray([int(x) for x in f[2:]], dtype=np.int64)
+                    out[str(Path(f[0]).stem)] = v[: len(v) // 2 * 2].reshape(-1, 2)
+    return out
+
+
+def frame_labels(frames: int, start_frame: int, label: int, normal_id: int, pairs: np.ndarray) -> np.ndarray:
+    """per-frame labels int64 [frames]: frame i carries `label` iff start <= i + start_frame <= stop for some (start, stop) pair,
+    else `normal_id` (a `-1 -1` pair matches nothing)"""
+    pos = np.arange(frames, dtype=np.int64) + start_frame
+    hit = ((pairs[:, :1] <= pos[None, :]) & (pos[None, :] <= pairs[:, 1:])).any(0) if len(pairs) else np.zeros(frames, dtype=bool)
+    return np.where(hit, np.int64(label), np.int64(normal_id))
+
+
+class StreamedTestLoader:
+    """The reference's test-mode dataset under DataLoader(batch_size=1, shuffle=False): yields
+    (features [1, ncrops, rows, D] on the device, labels [1, T] int64, label [1], segment_size [1], [path]).  The tile is sized by
+    the FILE's frame count (FeatureStream), which is the annotation row's in every list the reference ships."""
+
+    def __init__(self, records: List[VideoRecord], annotations: Optional[Dict[str, np.ndarray]], hp, device):
+        self.records, self.annotations, self.hp, self.device = records, annotations, hp, device
+
+    def __len__(self) -> int:
+        return len(self.records)
+
+    def frame_labels(self, i: int, frames: int) -> np.ndarray:
+        """per-frame labels int64 [frames] of record i, whose file holds `frames` frames"""
+        rec, hp = self.records[i], self.hp
+        pairs = np.zeros((0, 2), dtype=np.int64)
+        if self.annotations:
+            stem = Path(rec.path).stem
+            if stem not in self.annotations:
+                raise KeyError(f"{rec.path}: no row for {stem!r} in {hp.annotation_file_temporal_test}")
+            pairs = self.annotations[stem]
+        return frame_labels(frames, rec.start_frame, rec.label, int(hp.normal_id), pairs)
+
+    def __iter__(self):
+        hp = self.hp
+        stream = FeatureStream([r.path for r in self.records], int(hp.num_segments), int(hp.seg_length), int(hp.stride),
+                               int(hp.ncrops), device=self.device)
+        for i, (feats, T, S, path) in enumerate(stream):
+            lab = torch.from_numpy(self.frame_labels(i, T)).unsqueeze(0)
+            yield feats, lab, torch.tensor([self.records[i].label]), torch.tensor([S]), [path]
+
+
+class AnomalyCLIPDataModule:
+    def __init__(self, **hparams):
+        hp = dict(_DEFAULTS)
+        hp.update(hparams)                                        # unknown keys are kept, like save_hyperparameters does
+        missing = [k for k in HPARAM_KEYS if k not in hp]
+        if missing:
+            raise TypeError(f"AnomalyCLIPDataModule: missing hyper-parameters {missing}")
+        if not hp["load_from_features"]:
+            raise ValueError("AnomalyCLIPDataModule: load_from_features=False (training from frames) is not supported; extract the "
+                             "feature files first (anomalyclip_amd.extract)")
+        if int(hp["batch_size_test"]) != 1:
+            raise ValueError("AnomalyCLIPDataModule: batch_size_test must be 1 (videos differ in length)")
+        self.hparams = AttrDict(hp)
+        self.device: Optional[torch.device] = hp.get("device")
+        self.bank: Optional[FeatureBank] = None
+        self.normal: List[VideoRecord] = []
+        self.anomaly: List[VideoRecord] = []
+        self.test: List[VideoRecord] = []
+        self._annotations: Dict[str, np.ndarray] = {}
+        self._train_loaders = None
+
+    @property
+    def num_classes(self):
+        return self.hparams.num_classes
+
+    def prepare_data(self):
+        pass
+
+    def _read_lists(self):
+        hp = self.hparams
+        if not self.test and not self.normal:
+            self.normal = read_annotation_file(hp.annotation_file_normal, hp.frames_root)
+            self.anomaly = read_annotation_file(hp.annotation_file_anomaly, hp.frames_root)
+            self.test = read_annotation_file(hp.annotation_file_test, hp.frames_root)
+            self._annotations = read_temporal_annotations(hp.annotation_file_temporal_test)
+
+    def setup(self, stage: Optional[str] = None):
+        """reads the lists; for `fit` (or no stage) loads ONE bank over the normal and the abnormal training videos"""
+        self._read_lists()
+        if stage in (None, "fit") and self.bank is None:
+            hp = self.hparams
+            recs = self.normal + self.anomaly
+            self.bank = FeatureBank([r.path for r in recs], [r.num_frames for r in recs], [r.label for r in recs],
+                                    ncrops=int(hp.ncrops), device=self.device, max_bytes=hp.get("max_bytes"))
+
+    def train_dataloader(self):
+        if self.bank is None:
+            self.setup("fit")
+        if self._train_loaders is None:           # kept across epochs: pinned slots, shard seed and epoch counter live in them
+            hp, n = self.hparams, len(self.normal)
+            kw = dict(batch_size=int(hp.batch_size) // 2, num_segments=int(hp.num_segments), seg_length=int(hp.seg_length),
+                      stride=int(hp.stride), shuffle=True, drop_last=True)
+            self._train_loaders = [ResidentTrainLoader(self.bank, range(n), **kw),
+                                   ResidentTrainLoader(self.bank, range(n, n + len(self.anomaly)), **kw)]
+        return self._train_loaders
+
+    def val_dataloader(self):
+        self._read_lists()
+        return StreamedTestLoader(self.test, self._annotations, self.hparams, self.device)
+
+    def test_dataloader(self):
+        return self.val_dataloader()
+
+    def train_dataloader_test_mode(self):
+        self._read_lists()
+        return StreamedTestLoader(self.normal, None, self.hparams, self.device)       # (no temporal file: every frame normal_id)
+
+    def resident_normal_videos(self):
+        """the normal training videos' rows in the bank, in file order -- what `train_dataloader_test_mode()` would stream again
+        -- when a frame is one bank row and the test-mode tile keeps the file's order (one crop, stride 1); else None"""
+        if self.bank is None or int(self.hparams.ncrops) != 1 or int(self.hparams.stride) != 1:
+            return None
+        return [self.bank.video(v) for v in range(len(self.normal))]
+
+    def teardown(self, stage: Optional[str] = None):
+        pass
+
+    def state_dict(self):
+        return {}
+
+    def load_state_dict(self, state_dict):
+        pass

@@ -17,6 +17,28 @@ def test_start_indices(num_frames: int, num_segments: int, frames_per_segment: i
     return starts.astype(np.int64), len(starts) // num_segments
 
 
+def train_draw_range(num_frames: int, num_segments: int, frames_per_segment: int, stride: int = 1):
+    """-> (distance between segment starts, exclusive upper bound of the random offset) of a train-mode draw
+    (feature_dataset.py:260-276); a bound <= 0 is the video / grid pair the reference cannot sample."""
+    lower = num_segments * frames_per_segment * stride
+    span = num_frames if num_frames >= lower else lower
+    dist = (span - frames_per_segment + 1) // num_segments
+    return dist, dist + 2 - frames_per_segment
+
+
+def train_start_indices(num_frames: int, num_segments: int, frames_per_segment: int, stride: int = 1, rng=None) -> np.ndarray:
+    """Train-mode segment starts [num_segments] int64: evenly spaced segment origins plus ONE `rng.randint` call of
+    num_segments offsets per video -- the reference's draw order is the contract.  `num_frames` is the annotation row's
+    end - start + 1 (not the file's row count, which is what the frame index later wraps around).  `rng`: anything with
+    numpy's `randint(high, size=)`, by default the global `np.random` like the reference."""
+    dist, high = train_draw_range(num_frames, num_segments, frames_per_segment, stride)
+    if high <= 0:
+        raise ValueError(f"cannot draw train-mode starts for {num_frames} frames on a {num_segments} x {frames_per_segment} grid "
+                         f"(stride {stride}): offset range {high} <= 0")
+    rng = np.random if rng is None else rng
+    return np.arange(num_segments, dtype=np.int64) * dist + rng.randint(high, size=num_segments)
+
+
 def frame_index_table(start_indices: np.ndarray, frames_per_segment: int, stride: int, num_frames: int) -> np.ndarray:
     """flat list of source frame indices, wrapped modulo the video length (feature_dataset.py:362)."""
     off = np.arange(frames_per_segment, dtype=np.int64) * stride

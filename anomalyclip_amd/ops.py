@@ -628,6 +628,28 @@ def gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sample_segments(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Tensor, vid: torch.Tensor, starts: torch.Tensor,
+                    N: int, L: int, stride: int, ncrops: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One training batch out of a resident feature set (feature_bank.py): bank [rows, D] f32, row_off int64 [V], frames int32 [V],
+    vid int32 [B], starts int32 [B * N], all on the device -> out [B, ncrops, N * L, D] with
+    out[b, c, n*L + l] = bank[row_off[vid[b]] + ((starts[b*N + n] + l*stride) mod frames[vid[b]]) * ncrops + c].
+    One launch on the current stream, no host synchronisation (so `vid` values are the caller's to keep inside [0, V))."""
+    assert bank.dim() == 2 and bank.is_contiguous() and bank.dtype == torch.float32
+    assert row_off.dtype == torch.int64 and frames.dtype == torch.int32 and vid.dtype == torch.int32 and starts.dtype == torch.int32
+    assert all(t.is_cuda and t.is_contiguous() for t in (row_off, frames, vid, starts))
+    B, D = vid.numel(), bank.shape[1]
+    assert starts.numel() == B * N and row_off.numel() == frames.numel()
+    shape = (B, ncrops, N * L, D)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=bank.device)
+    assert out.shape == shape and out.is_contiguous() and out.dtype == torch.float32 and out.device == bank.device
+    h = _h(bank)
+    from . import _lib                       # (the parameter L, named as in the C entry point, hides this module's alias)
+    _lib.check(_lib.lib().acx_sample_segments(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), vid.data_ptr(),
+                                              starts.data_ptr(), out.data_ptr(), B, N, L, stride, ncrops, D, _stream()), h)
+    return out
+
+
 def add_bcast(x: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
     assert x.is_contiguous() and p.is_contiguous()
     out = torch.empty_like(x)

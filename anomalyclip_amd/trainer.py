@@ -76,6 +76,7 @@ class Trainer:
             return loader
         if not isinstance(loader, DataLoader):
             if getattr(loader, "already_sharded", False):       # opt-in: an iterable that yields THIS rank's shard
+                getattr(loader, "set_epoch", lambda e: None)(epoch)
                 return loader
             raise TypeError(f"data-parallel training needs torch DataLoaders to shard (got {type(loader).__name__}); "
                             f"an iterable that already yields this rank's shard may set `already_sharded = True`")

@@ -856,6 +856,19 @@ int acx_comm_info(acx_ctx* ctx, int32_t* rank, int32_t* world);   /* world = 0: 
 int acx_allreduce(acx_ctx* ctx, void* buf, int64_t count, int32_t dtype, int32_t op, void* stream);
 int acx_allgather(acx_ctx* ctx, const void* send, void* recv, int64_t count, int32_t dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training batches from a feature set resident in device memory (feature_dataset.py:347-380, train mode).  `bank` is the
+ * concatenation of every video's feature file as stored: [T_v * ncrops, D], frame t / crop c in row t * ncrops + c; row_off[v] is
+ * video v's first bank row and frames[v] its T_v.  One launch draws a whole batch:
+ *   out[b, c, n*L + l, :] = bank[row_off[vid[b]] + ((starts[b*N + n] + l*stride) mod frames[vid[b]]) * ncrops + c, :]
+ * with out [B, ncrops, N*L, D].  All five tables are DEVICE pointers (row_off int64 [V], frames int32 [V], vid int32 [B] with
+ * values in [0, V), starts int32 [B*N]); the modulus is a true modulus and every element offset is 64-bit.  A pure copy in
+ * 16-byte pieces: D % 4 == 0 and 16-byte aligned bank / out, else ACX_E_BADARG; so are null pointers and non-positive
+ * N / L / stride / ncrops / D.  B == 0 is ACX_OK without a launch.  The same video may appear several times in a batch. */
+int acx_sample_segments(acx_ctx* ctx, const float* bank, const int64_t* row_off, const int32_t* frames, const int32_t* vid,
+                        const int32_t* starts, float* out, int32_t B, int32_t N, int32_t L, int32_t stride, int32_t ncrops,
+                        int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
