@@ -9,11 +9,12 @@ Attributes the module reads: `datamodule`, `current_epoch`, `max_epochs`, `ckpt_
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Any, Optional
 
 import torch
 
-from . import checkpoint, parallel
+from . import checkpoint, ops, parallel
 
 
 def _to_device(x: Any, dev):
@@ -38,6 +39,7 @@ class Trainer:
         self.global_step = 0
         self.ckpt_path: Optional[str] = None
         self.callback_metrics: dict = {}
+        self._optimizer = self._scheduler = self._train_loaders = None     # what save_checkpoint writes beside the weights
 
     # ------------------------------------------------------------------------------------------------------
     def _attach(self, model, datamodule, stage):
@@ -56,13 +58,26 @@ class Trainer:
             self.callback_metrics.update({k: v for k, v in m.items() if isinstance(v, (int, float))})
 
     def save_checkpoint(self, model, path: str):
-        """Lightning-shaped `.ckpt` (configs/callbacks/default.yaml:8-14: save_last) on rank 0."""
+        """Lightning-shaped `.ckpt` (configs/callbacks/default.yaml:8-14: save_last) on rank 0: the weights, and -- inside
+        fit(), for an optimizer that has a state_dict -- what a resume needs (checkpoint.training_state).  Every rank calls
+        it: the ranks' generator states are gathered to rank 0.  Written to `<path>.tmp` and renamed over `path`."""
+        opt = self._optimizer
+        extra_ranks = None
+        if hasattr(opt, "state_dict"):
+            extra_ranks = [checkpoint.rng_state(getattr(model, "device", None))]
+            if parallel.is_distributed():
+                gathered = [None] * parallel.world_size()
+                parallel.dist.all_gather_object(gathered, extra_ranks[0])
+                extra_ranks = gathered
         if parallel.rank() != 0:
             return
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        torch.save({"state_dict": checkpoint.to_lightning_state_dict(model.net), "epoch": self.current_epoch,
-                    "global_step": self.global_step, "hyper_parameters": dict(getattr(model, "hparams", {}) or {}),
-                    "pytorch-lightning_version": "1.8.3"}, path)
+        ckpt = {"state_dict": checkpoint.to_lightning_state_dict(model.net), "epoch": self.current_epoch,
+                "global_step": self.global_step, "hyper_parameters": dict(getattr(model, "hparams", {}) or {}),
+                "pytorch-lightning_version": "1.8.3"}
+        if extra_ranks is not None:
+            ckpt.update(checkpoint.training_state(opt, self._scheduler, extra_ranks, self._train_loaders, parallel.world_size()))
+        checkpoint.save_atomic(ckpt, path)
 
     # ------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -135,20 +150,55 @@ class Trainer:
                 batch.append(b)
             yield tuple(batch)
 
+    @staticmethod
+    def _usable_resume_state(acx):
+        """the file's `acx_resume` if this run can continue its random streams: written by us, at this world size"""
+        why = None
+        if not isinstance(acx, dict) or not acx.get("rng"):
+            why = "the checkpoint holds no generator states (not written by this trainer)"
+        elif int(acx.get("world_size", -1)) != parallel.world_size() or len(acx["rng"]) != parallel.world_size():
+            why = f"the checkpoint was written at world size {acx.get('world_size')}, this run has {parallel.world_size()}"
+        if why is None:
+            return acx
+        warnings.warn(f"resume: {why}; weights, optimizer, schedule and epoch are restored, the random generators are left as "
+                      f"they are: the data order and the selector masks will not match an uninterrupted run")
+        return None
+
     def fit(self, model, datamodule=None, ckpt_path: Optional[str] = None):
         self._attach(model, datamodule, "fit")
         dev = model.device
+        ckpt = None
         if ckpt_path:
-            checkpoint.load_into(model.net, ckpt_path)
+            ckpt = checkpoint.read(ckpt_path)
+            checkpoint.load_into(model.net, ckpt)
+            ops.WEIGHT_EPOCH[0] += 1                            # caches of derived weights keyed by the epoch see the load
             self.ckpt_path = ckpt_path
         cfg = model.configure_optimizers()
         opt = cfg["optimizer"]
         sched = cfg.get("lr_scheduler", {}).get("scheduler") if isinstance(cfg.get("lr_scheduler"), dict) else None
+        self._optimizer, self._scheduler, self._train_loaders = opt, sched, None
+        # resume (src/train.py:94): a file saved at the end of epoch e continues at epoch e + 1; a weight-only file starts over
+        first_epoch, resume = 0, None
+        if ckpt is not None:
+            state = checkpoint.load_training_state(ckpt, opt, sched)
+            if state is not None:
+                first_epoch, self.global_step = state["epoch"] + 1, state["global_step"]
+                # the loop below sets current_epoch per epoch; a finished run (first_epoch >= max_epochs) trains nothing and
+                # reports the last epoch it has, max_epochs - 1, not one that never ran
+                self.current_epoch = min(first_epoch, max(self.max_epochs - 1, 0))
+                resume = self._usable_resume_state(state["acx_resume"])
+            del ckpt, state
         model.on_train_start()
-        for epoch in range(self.max_epochs):
+        for epoch in range(first_epoch, self.max_epochs):
             self.current_epoch = epoch
             model.net.train()
+            if resume is not None:      # after on_train_start: computing ncentroid must not disturb what the epoch draws from
+                checkpoint.set_rng_state(resume["rng"][parallel.rank()], dev)
             loaders = self.datamodule.train_dataloader()        # [normal loader, abnormal loader] (datamodule:144-163)
+            self._train_loaders = loaders
+            if resume is not None:
+                checkpoint.set_loader_state(loaders, resume.get("train_loaders"))
+                resume = None
             for i, batch in enumerate(self._train_batches(loaders, epoch)):
                 if self.limit_train_batches is not None and i >= self.limit_train_batches:
                     break
