@@ -297,7 +297,9 @@ class AnomalyCLIPModule(_Base):
             self.compute_ncentroid_resident(resident)
         else:
             loader = dm.train_dataloader_test_mode()
-            self.compute_ncentroid(loader, bool(_get(_get(dm, "hparams"), "load_from_features", True)))
+            # a datamodule that encodes frames itself says so (yields_features); else the reference's data key decides
+            feats = getattr(dm, "yields_features", None)
+            self.compute_ncentroid(loader, bool(_get(_get(dm, "hparams"), "load_from_features", True) if feats is None else feats))
         if parallel.rank() == 0:                 # the reference lets every rank write the same file
             torch.save(self.ncentroid.cpu(), f)
 
@@ -362,20 +364,34 @@ class AnomalyCLIPModule(_Base):
         post-processing launch sequence over all tiles, one text-tower evaluation, then split per video and truncated to the
         real frames like anomaly_clip_module.py:474-483.  -> list of (abnormal_scores, labels, class_probs)."""
         net = self.net
-        if len(batches) == 1 or not getattr(net, "load_from_features", True):
+        tiles = [b[0] for b in batches]
+        if len(batches) == 1 or any(torch.is_tensor(t) and t.dim() == 5 for t in tiles):        # (frames: one video per forward)
             return [self._score_video(b) for b in batches]
         dev = self.device
-        feats, rows_per_crop, segs, labs = [], [], [], []
-        for b in batches:
-            f, labels, S = b[0], b[1], int(b[3])
-            f = f.to(dev)
-            if f.dim() != 4 or f.shape[0] != 1 or f.shape[1] != net.ncrops:
+        from .feature_bank import BankTile
+        if all(isinstance(t, BankTile) for t in tiles):
+            # a group of tiles of one resident bank: ONE gather launch straight into the buffer forward_test_many takes
+            t0 = tiles[0]
+            bank = t0.bank
+            if (any(t.bank is not bank or (t.N, t.L, t.stride) != (t0.N, t0.L, t0.stride) for t in tiles) or bank.device != dev
+                    or bank.ncrops != net.ncrops or (t0.N, t0.L) != (net.num_segments, net.seg_length)):
                 return [self._score_video(bb) for bb in batches]
-            feats.append(f.reshape(-1, f.shape[-1]))
-            rows_per_crop.append(f.shape[2])
-            segs.append(S)
-            labs.append(torch.as_tensor(labels).squeeze(0).to(dev))
-        x = feats[0] if len(feats) == 1 else torch.cat(feats, 0)
+            x = ops.tile_videos(bank.bank, bank.row_off, bank.frames, [t.v for t in tiles], [t.S for t in tiles], t0.N, t0.L,
+                                t0.stride, bank.ncrops)
+            rows_per_crop, segs = [t.rows for t in tiles], [int(b[3]) for b in batches]
+            labs = [torch.as_tensor(b[1]).squeeze(0).to(dev) for b in batches]
+        else:
+            feats, rows_per_crop, segs, labs = [], [], [], []
+            for b in batches:
+                f, labels, S = b[0], b[1], int(b[3])
+                f = f.to(dev)
+                if f.dim() != 4 or f.shape[0] != 1 or f.shape[1] != net.ncrops:
+                    return [self._score_video(bb) for bb in batches]
+                feats.append(f.reshape(-1, f.shape[-1]))
+                rows_per_crop.append(f.shape[2])
+                segs.append(S)
+                labs.append(torch.as_tensor(labels).squeeze(0).to(dev))
+            x = feats[0] if len(feats) == 1 else torch.cat(feats, 0)
         with torch.no_grad():
             sim, sc = net.forward_test_many(x, rows_per_crop, segs, self.ncentroid)
             probs = ops.class_probs(sim.contiguous(), sc.contiguous())

@@ -343,7 +343,7 @@ class AnomalyCLIP(nn.Module):
         ncentroid = ncentroid.to(dev, torch.float32).contiguous()
         segment_size = int(segment_size)
         if test_mode:
-            if not self.load_from_features:
+            if not self.load_from_features and image_features.dim() == 5:      # (anything else is features already)
                 b, t, c, h, w = image_features.size()
                 f = self.image_encoder(image_features.view(-1, c, h, w))                # anomaly_clip.py:119-123
                 # "(b ncrops n s l) d -> b ncrops (n s l) d" is a pure view
@@ -370,8 +370,8 @@ class AnomalyCLIP(nn.Module):
         features: [sum_v ncrops * 512 * S_v, D] rows, video after video, each video crop-major in frame order (what the
         dataset's `(1, ncrops, 512 S, D)` tensor holds); rows_per_crop[v] = 512 * S_v; segment_sizes[v] = S_v.
         Returns (similarity [rows, C-1], scores [rows]) in the same row order (stride expansion is left to the caller)."""
-        if not self.load_from_features:
-            raise ValueError("forward_test_many takes pre-extracted features")
+        if features.dim() == 5:
+            raise ValueError("forward_test_many takes features, not frames")
         dev = features.device
         ncentroid = ncentroid.to(dev, torch.float32).contiguous()
         N, Lg = self.num_segments, self.seg_length

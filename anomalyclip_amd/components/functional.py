@@ -757,7 +757,7 @@ class MilLossFn(torch.autograd.Function):
 # ====================================================================================================== assembly
 def anomaly_clip_train_forward(net, image_features, labels, ncentroid, masks=None):
     """anomaly_clip.py:156-215."""
-    if not net.load_from_features:
+    if not net.load_from_features and image_features.dim() == 5:                   # (anything else is features already)
         b, t, c, h, w = image_features.size()
         f = net.image_encoder(image_features.view(-1, c, h, w))                    # frozen, forward only
         image_features = f.view(b, net.ncrops, -1, f.shape[-1])

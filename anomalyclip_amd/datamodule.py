@@ -1,9 +1,14 @@
-"""`AnomalyCLIPDataModule` for pre-extracted feature files (the reference's src/data/anomaly_clip_datamodule.py with
-`load_from_features: true`), without Lightning: same hyper-parameter keys, same loader methods, same batch tuples.
+"""`AnomalyCLIPDataModule` (the reference's src/data/anomaly_clip_datamodule.py), without Lightning: same hyper-parameter keys, same
+loader methods, same batch tuples.
 
-Training batches come from a `FeatureBank` resident in device memory through two `ResidentTrainLoader`s (normal / abnormal
-videos, batch_size // 2 each: anomaly_clip_datamodule.py:144-163); the test-mode loaders stream the files through
-`FeatureStream` and add the per-frame labels of the temporal annotation file (feature_dataset.py:329-345)."""
+`load_from_features: true`: training batches come from a `FeatureBank` of the feature files, resident in device memory, through two
+`ResidentTrainLoader`s (normal / abnormal videos, batch_size // 2 each: anomaly_clip_datamodule.py:144-163); the test-mode loaders
+stream the files through `FeatureStream` and add the per-frame labels of the temporal annotation file (feature_dataset.py:329-345).
+
+`load_from_features: false` with `encoder=`: the frame folders `<frames_root>/<video>/<image_tmpl>` are encoded ONCE by the frozen
+CLIP image encoder into such banks (`FeatureBank.from_frames`; the reference's frame transform is deterministic, so its per-step
+encoding gives the same rows) and every loader draws from a bank: `ResidentTrainLoader` as above, `ResidentTestLoader` for the
+test-mode tiles.  No feature file is written."""
 from __future__ import annotations
 
 import os
@@ -14,7 +19,7 @@ import numpy as np
 import torch
 
 from .anomaly_clip_module import AttrDict
-from .feature_bank import FeatureBank, ResidentTrainLoader
+from .feature_bank import BankTile, FeatureBank, ResidentTrainLoader
 from .feature_stream import FeatureStream
 
 HPARAM_KEYS = ("frames_root", "annotation_file_normal", "annotation_file_anomaly", "annotation_file_test",
@@ -30,6 +35,7 @@ class VideoRecord:
     def __init__(self, row: Sequence[str], root: str, where: str):
         if len(row) != 4:
             raise ValueError(f"{where}: expected `path start_frame end_frame label`, got {' '.join(row)!r}")
+        self.video = row[0]                                      # the frame folder under frames_root
         self.path = os.path.join(root, row[0]) + ".npy"
         self.start_frame, self.end_frame, self.label = int(row[1]), int(row[2]), int(row[3])
 
@@ -95,16 +101,42 @@ class StreamedTestLoader:
             yield feats, lab, torch.tensor([self.records[i].label]), torch.tensor([S]), [path]
 
 
+class ResidentTestLoader(StreamedTestLoader):
+    """The same 5-tuples over the first len(records) videos of a resident bank (`records[i]` is video i of `bank`: the normal list
+    heads the training bank): the features are a `BankTile`,
+    gathered on the device when the consumer asks (`.to(device)`, or a group at once in AnomalyCLIPModule.score_videos); `path`
+    is the bank's path of the video (the frame folder of a bank filled from frames)."""
+
+    def __init__(self, bank: FeatureBank, records: List[VideoRecord], annotations: Optional[Dict[str, np.ndarray]], hp):
+        super().__init__(records, annotations, hp, bank.device)
+        if len(records) > len(bank):
+            raise ValueError(f"ResidentTestLoader: {len(records)} records over a bank of {len(bank)} videos")
+        self.bank = bank
+
+    def __iter__(self):
+        hp, bank = self.hp, self.bank
+        for i, rec in enumerate(self.records):
+            tile = BankTile(bank, i, int(hp.num_segments), int(hp.seg_length), int(hp.stride))
+            lab = torch.from_numpy(self.frame_labels(i, bank.file_frames[i])).unsqueeze(0)
+            yield tile, lab, torch.tensor([rec.label]), torch.tensor([tile.S]), [bank.paths[i]]
+
+
 class AnomalyCLIPDataModule:
-    def __init__(self, **hparams):
+    def __init__(self, encoder=None, **hparams):
         hp = dict(_DEFAULTS)
         hp.update(hparams)                                        # unknown keys are kept, like save_hyperparameters does
         missing = [k for k in HPARAM_KEYS if k not in hp]
         if missing:
             raise TypeError(f"AnomalyCLIPDataModule: missing hyper-parameters {missing}")
         if not hp["load_from_features"]:
-            raise ValueError("AnomalyCLIPDataModule: load_from_features=False (training from frames) is not supported; extract the "
-                             "feature files first (anomalyclip_amd.extract)")
+            if encoder is None:
+                raise ValueError("AnomalyCLIPDataModule: load_from_features=False (training from frame folders) needs the CLIP image "
+                                 "encoder that turns the frames into features: pass encoder=<the AnomalyCLIP net or its "
+                                 "image_encoder>, or extract feature files first (anomalyclip_amd.extract)")
+            if int(hp["ncrops"]) not in (1, 5, 10):
+                raise ValueError(f"AnomalyCLIPDataModule: ncrops={hp['ncrops']} with load_from_features=False: frames are cropped 1, 5 "
+                                 f"or 10 times (anomalyclip_amd.extract)")
+        self.encoder = None if hp["load_from_features"] else getattr(encoder, "image_encoder", encoder)
         if int(hp["batch_size_test"]) != 1:
             raise ValueError("AnomalyCLIPDataModule: batch_size_test must be 1 (videos differ in length)")
         self.hparams = AttrDict(hp)
@@ -115,6 +147,13 @@ class AnomalyCLIPDataModule:
         self.test: List[VideoRecord] = []
         self._annotations: Dict[str, np.ndarray] = {}
         self._train_loaders = None
+        self._test_bank: Optional[FeatureBank] = None             # frames mode: the test list's bank ...
+        self._normal_bank: Optional[FeatureBank] = None           # ... and the normal list's, when no fit bank holds it
+
+    @property
+    def yields_features(self) -> bool:
+        """every loader yields FEATURES, whatever `load_from_features` says (frames are encoded into banks here)"""
+        return True
 
     @property
     def num_classes(self):
@@ -131,14 +170,30 @@ class AnomalyCLIPDataModule:
             self.test = read_annotation_file(hp.annotation_file_test, hp.frames_root)
             self._annotations = read_temporal_annotations(hp.annotation_file_temporal_test)
 
+    def _frames_bank(self, records: List[VideoRecord]) -> FeatureBank:
+        """frames mode: the bank of `records`, encoded now.  The encoder is put in eval mode for the pass (BatchNorm on running
+        statistics, as extraction demands) and left as it was."""
+        hp, enc = self.hparams, self.encoder
+        was_training = enc.training
+        enc.eval()
+        try:
+            return FeatureBank.from_frames(enc, records, hp.frames_root, hp.image_tmpl, int(hp.ncrops), hp.get("scale_size"),
+                                           int(hp.get("decode_threads", 8)), self.device, hp.get("max_bytes"), hp.get("log"))
+        finally:
+            enc.train(was_training)
+
     def setup(self, stage: Optional[str] = None):
-        """reads the lists; for `fit` (or no stage) loads ONE bank over the normal and the abnormal training videos"""
+        """reads the lists; for `fit` (or no stage) loads ONE bank over the normal and the abnormal training videos (frames mode:
+        encodes it; the test list's bank is encoded when its loader is first asked for)"""
         self._read_lists()
         if stage in (None, "fit") and self.bank is None:
             hp = self.hparams
             recs = self.normal + self.anomaly
-            self.bank = FeatureBank([r.path for r in recs], [r.num_frames for r in recs], [r.label for r in recs],
-                                    ncrops=int(hp.ncrops), device=self.device, max_bytes=hp.get("max_bytes"))
+            if self.encoder is not None:
+                self.bank = self._frames_bank(recs)
+            else:
+                self.bank = FeatureBank([r.path for r in recs], [r.num_frames for r in recs], [r.label for r in recs],
+                                        ncrops=int(hp.ncrops), device=self.device, max_bytes=hp.get("max_bytes"))
 
     def train_dataloader(self):
         if self.bank is None:
@@ -153,6 +208,10 @@ class AnomalyCLIPDataModule:
 
     def val_dataloader(self):
         self._read_lists()
+        if self.encoder is not None:
+            if self._test_bank is None:
+                self._test_bank = self._frames_bank(self.test)
+            return ResidentTestLoader(self._test_bank, self.test, self._annotations, self.hparams)
         return StreamedTestLoader(self.test, self._annotations, self.hparams, self.device)
 
     def test_dataloader(self):
@@ -160,6 +219,13 @@ class AnomalyCLIPDataModule:
 
     def train_dataloader_test_mode(self):
         self._read_lists()
+        if self.encoder is not None:
+            bank = self.bank                      # the fit bank's first len(normal) videos ARE the normal list
+            if bank is None:
+                if self._normal_bank is None:
+                    self._normal_bank = self._frames_bank(self.normal)
+                bank = self._normal_bank
+            return ResidentTestLoader(bank, self.normal, None, self.hparams)
         return StreamedTestLoader(self.normal, None, self.hparams, self.device)       # (no temporal file: every frame normal_id)
 
     def resident_normal_videos(self):

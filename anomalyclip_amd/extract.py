@@ -203,41 +203,64 @@ def batch_frames(encoder, ncrops: int) -> int:
     return max(1, int(encoder.chunk) // ncrops)
 
 
-def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False) -> dict:
-    """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
-    Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
-    from .preprocess import preprocess_crops
-    encoder = _encoder_of(encoder)
+def check_eval_mode(encoder) -> None:
     if encoder.training and any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in encoder.modules()):
         raise ValueError(f"{getattr(encoder, 'arch', type(encoder).__name__)}: extraction needs eval mode (call .eval()): in "
                          "training mode BatchNorm takes its statistics from each batch")
-    reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
-    T, D, R = len(reader), int(encoder.output_dim), int(encoder.input_resolution)
-    shape = (T * ncrops, D)
-    if not overwrite and is_complete(out_path, shape):
-        return {"written": False, "frames": T, "rows": shape[0]}
-    dev = next(encoder.parameters()).device
-    if dev.type != "cuda":
+
+
+def check_encoder(encoder) -> None:
+    """what the encode loop needs of the image encoder: eval mode where it has BatchNorm, and the GPU"""
+    check_eval_mode(encoder)
+    if next(encoder.parameters()).device.type != "cuda":
         raise ValueError("the encoder must be on the GPU")
-    out = torch.empty(shape, dtype=torch.float32).pin_memory()
+
+
+def encode_video(encoder, frames, ncrops: int = 1, scale_size: Optional[int] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+    """The encode loop of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]): yields (row0, rows) -- `rows`
+    float32 [k * ncrops, D] on the device, queued on the current stream, the rows row0 ... of the video's [T * ncrops, D] table.
+    `batch_frames(encoder, ncrops)` frames per encoder launch; the frames reach the device on a side stream.  The consumer copies
+    each block where it wants it (a pinned file buffer: extract_video; a slice of a resident bank: FeatureBank.from_frames)."""
+    from .preprocess import preprocess_crops
+    encoder = _encoder_of(encoder)
+    check_encoder(encoder)
+    reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
+    R = int(encoder.input_resolution)
+    dev = next(encoder.parameters()).device
     cur = torch.cuda.current_stream(dev)
     side = torch.cuda.Stream(device=dev)
     r0 = 0
-    with torch.no_grad():
-        for slot, view in reader.batches(batch_frames(encoder, ncrops)):
-            with torch.cuda.stream(side):
-                x8 = view.to(dev, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(side)
-            reader.copied[slot] = ev
-            cur.wait_event(ev)
-            x8.record_stream(cur)
+    for slot, view in reader.batches(batch_frames(encoder, ncrops)):
+        with torch.cuda.stream(side):
+            x8 = view.to(dev, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        reader.copied[slot] = ev
+        cur.wait_event(ev)
+        x8.record_stream(cur)
+        with torch.no_grad():                     # (per batch: a grad mode held across a yield would reach the consumer)
             x = preprocess_crops(x8, R, scale_size, ncrops)
             rows = encoder(x.view(-1, 3, R, R))
-            out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
-            r0 += rows.shape[0]
-    assert r0 == shape[0], (r0, shape)
-    cur.synchronize()
+        yield r0, rows
+        r0 += rows.shape[0]
+    assert r0 == len(reader) * ncrops, (r0, len(reader), ncrops)
+
+
+def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False) -> dict:
+    """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
+    Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
+    encoder = _encoder_of(encoder)
+    reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
+    T, D = len(reader), int(encoder.output_dim)
+    shape = (T * ncrops, D)
+    check_eval_mode(encoder)
+    if not overwrite and is_complete(out_path, shape):
+        return {"written": False, "frames": T, "rows": shape[0]}
+    check_encoder(encoder)
+    out = torch.empty(shape, dtype=torch.float32).pin_memory()
+    for r0, rows in encode_video(encoder, reader, ncrops, scale_size):
+        out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
+    torch.cuda.current_stream(next(encoder.parameters()).device).synchronize()
     write_features(out_path, out.numpy())
     return {"written": True, "frames": T, "rows": shape[0]}
 

@@ -5,7 +5,10 @@ time and the DataLoader then ships batch * N*L * D floats over PCIe for a step t
 fits in device memory (UCF-Crime: 1,610 training videos, ~25 GB), so here every `.npy` file is loaded once (`FeatureBank`)
 and a step moves a few hundred bytes of indices: the video ids and the segment starts, drawn on the host in the reference's
 order (`ResidentTrainLoader`: torch's sampler for the video order, one `randint` call per video for the starts), then
-`acx_sample_segments` copies the rows (ops.sample_segments)."""
+`acx_sample_segments` copies the rows (ops.sample_segments).
+
+`FeatureBank.from_frames` fills the same bank from frame folders through the CLIP image encoder (no feature files), and
+`BankTile` / `ops.tile_videos` draw the test-mode tiles out of a bank on the device."""
 from __future__ import annotations
 
 import os
@@ -54,6 +57,79 @@ class FeatureBank:
         self.row_off = torch.from_numpy(self.offsets[:-1].copy()).to(self.device)
         self.frames = torch.tensor(self.file_frames, dtype=torch.int32).to(self.device)
         self.labels = torch.from_numpy(self.labels_host).to(self.device)
+
+    @classmethod
+    def from_frames(cls, encoder, records, frames_root: str, image_tmpl: str = "{:06d}.jpg", ncrops: int = 1,
+                    scale_size: Optional[int] = None, decode_threads: int = 8, device: Optional[torch.device] = None,
+                    max_bytes: Optional[int] = None, log=None) -> "FeatureBank":
+        """The same bank, filled by the CLIP image encoder instead of from files: every frame an annotation row names
+        (`records`: objects with `video`, `start_frame`, `end_frame`, `label`; frame t of video v is
+        `<frames_root>/<video>/image_tmpl.format(t + start_frame)`, end inclusive) is decoded and encoded ONCE through
+        extract.encode_video -- the launches `extract_video` makes, so the rows are the rows of the file it would write -- and each
+        block of rows is copied from the encoder's output straight into its bank slice.  `paths` are the frame folders,
+        `file_frames == num_frames`.  The size follows from the rows and `encoder.output_dim` and is checked before any frame is
+        opened."""
+        from . import extract as X
+        encoder = X._encoder_of(encoder)
+        records = list(records)
+        self = cls.__new__(cls)
+        self.paths = [os.path.join(str(frames_root), r.video) for r in records]
+        self.num_frames = [int(r.end_frame) - int(r.start_frame) + 1 for r in records]
+        self.labels_host = np.asarray([int(r.label) for r in records], dtype=np.int64)
+        self.ncrops, self.D = int(ncrops), int(encoder.output_dim)
+        if self.ncrops not in (1, 5, 10):
+            raise ValueError(f"FeatureBank.from_frames: ncrops = {ncrops} (1, 5 or 10 crops, as anomalyclip_amd.extract takes them)")
+        if not records:
+            raise ValueError("FeatureBank.from_frames: no videos")
+        for p, n in zip(self.paths, self.num_frames):
+            if n <= 0:
+                raise ValueError(f"{p}: the annotation row holds {n} frames")
+        if self.D % 4:
+            raise ValueError(f"FeatureBank.from_frames: feature width {self.D} is not a multiple of 4")
+        self.file_frames = list(self.num_frames)
+        rows = [n * self.ncrops for n in self.num_frames]
+        self.offsets = np.concatenate([[0], np.cumsum(rows, dtype=np.int64)]).astype(np.int64)
+        need = int(self.offsets[-1]) * self.D * 4
+        if max_bytes is None:
+            with torch.cuda.device(next(encoder.parameters()).device):
+                max_bytes = int(torch.cuda.mem_get_info()[0] * 0.8)       # 80 % of what is free now, as for a bank of files
+        if need > max_bytes:
+            raise ValueError(f"FeatureBank: the {int(self.offsets[-1]) // self.ncrops} frames of {len(records)} videos need {need} "
+                             f"bytes of device memory at {self.ncrops} crop(s) x {self.D} floats, {int(max_bytes)} bytes are "
+                             f"available (banks larger than device memory are not supported; anomalyclip_amd.extract writes "
+                             f"the same rows to feature files instead)")
+        X.check_encoder(encoder)
+        self.device = next(encoder.parameters()).device          # the rows never leave the device they are computed on
+        if device is not None and (torch.device(device).type != "cuda" or torch.device(device).index not in (None, self.device.index)):
+            raise ValueError(f"FeatureBank.from_frames: the encoder is on {self.device}, the bank was asked for on {device}")
+        self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            for v, r in enumerate(records):
+                reader = X.FrameFolderReader(str(frames_root), r.video, int(r.start_frame), int(r.end_frame), image_tmpl, decode_threads)
+                try:
+                    self.fill_video(encoder, v, reader, scale_size)
+                except FileNotFoundError as e:
+                    raise FileNotFoundError(f"video {r.video!r}: frame file {e.filename} is missing (the annotation row names frames "
+                                            f"{int(r.start_frame)} ... {int(r.end_frame)})") from e
+                finally:
+                    reader.close()
+                if log:
+                    log(f"encoded {self.paths[v]}  [{rows[v]} rows]")
+            torch.cuda.current_stream().synchronize()           # the readers' pinned buffers are released on return
+        self.row_off = torch.from_numpy(self.offsets[:-1].copy()).to(self.device)
+        self.frames = torch.tensor(self.file_frames, dtype=torch.int32).to(self.device)
+        self.labels = torch.from_numpy(self.labels_host).to(self.device)
+        return self
+
+    def fill_video(self, encoder, v: int, frames, scale_size: Optional[int] = None) -> None:
+        """encodes the frames of video v (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into its bank rows: every
+        block of extract.encode_video is copied device to device into its slice, on the current stream"""
+        from . import extract as X
+        dst = self.video(v)
+        if len(frames) * self.ncrops != dst.shape[0]:
+            raise ValueError(f"{self.paths[v]}: {len(frames)} frames for {dst.shape[0] // self.ncrops} in the bank")
+        for r0, blk in X.encode_video(encoder, frames, self.ncrops, scale_size):
+            dst[r0:r0 + blk.shape[0]].copy_(blk)
 
     def __len__(self) -> int:
         return len(self.paths)
@@ -138,6 +214,33 @@ class FeatureBank:
                 ev.record()
                 copied[slot] = ev
             torch.cuda.current_stream().synchronize()          # the pinned slots are released on return
+
+
+class BankTile:
+    """The test-mode tile of video `v` of a bank, not yet gathered: `[1, ncrops, rows, D]` with rows = N * L * S, row r = frame
+    (r * stride) mod T (feature_index.test_start_indices).  `.to(device)` gathers it with one `acx_tile_videos` launch;
+    AnomalyCLIPModule.score_videos gathers a whole group of them in one launch instead."""
+
+    def __init__(self, bank: FeatureBank, v: int, num_segments: int, seg_length: int, stride: int = 1):
+        self.bank, self.v = bank, int(v)
+        self.N, self.L, self.stride = int(num_segments), int(seg_length), int(stride)
+        starts, self.S = FI.test_start_indices(bank.file_frames[self.v], self.N, self.L, self.stride)
+        self.rows = len(starts) * self.L
+        self.shape = torch.Size((1, bank.ncrops, self.rows, bank.D))
+
+    def dim(self) -> int:
+        return 4
+
+    def to(self, device=None, *unused, **unused_kw) -> torch.Tensor:
+        b = self.bank
+        if device is not None and torch.device(device).type != "cuda":
+            raise ValueError("a BankTile is gathered on the bank's device")
+        with torch.cuda.device(b.device):
+            x = ops.tile_videos(b.bank, b.row_off, b.frames, [self.v], [self.S], self.N, self.L, self.stride, b.ncrops)
+        return x.view(self.shape)
+
+    def reshape(self, *shape) -> torch.Tensor:
+        return self.to().reshape(*shape)
 
 
 class _Indices(torch.utils.data.Dataset):

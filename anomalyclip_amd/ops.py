@@ -6,7 +6,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import gc
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -647,6 +647,49 @@ def sample_segments(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Ten
     from . import _lib                       # (the parameter L, named as in the C entry point, hides this module's alias)
     _lib.check(_lib.lib().acx_sample_segments(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), vid.data_ptr(),
                                               starts.data_ptr(), out.data_ptr(), B, N, L, stride, ncrops, D, _stream()), h)
+    return out
+
+
+_TILE_TABLES: dict = {}       # tile_videos: (device, vids, segment sizes, N * L, ncrops) -> the four device tables of that group
+
+
+def tile_videos(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Tensor, vids: Sequence[int], segment_sizes: Sequence[int],
+                N: int, L: int, stride: int, ncrops: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The test-mode tiles of a group of videos out of a resident feature set, in one launch: bank / row_off / frames as for
+    `sample_segments`, `vids` the videos' indices into them and `segment_sizes` their S_j (host ints: the caller knows the frame
+    counts) -> out [sum_j ncrops * N * L * S_j, D], video after video, each crop-major, with
+    out[out_off[j] + c * rows_j + r] = bank[row_off[vids[j]] + ((r * stride) mod frames[vids[j]]) * ncrops + c].
+    The group's small index tables are built once per group geometry and kept on the device; no host synchronisation."""
+    assert bank.dim() == 2 and bank.is_contiguous() and bank.dtype == torch.float32
+    assert row_off.dtype == torch.int64 and frames.dtype == torch.int32 and row_off.numel() == frames.numel()
+    assert all(t.is_cuda and t.is_contiguous() for t in (row_off, frames))
+    vids, segs = [int(v) for v in vids], [int(s) for s in segment_sizes]
+    V, D, NL = len(vids), bank.shape[1], int(N) * int(L)
+    if len(segs) != V or any(s <= 0 for s in segs) or any(not 0 <= v < frames.numel() for v in vids):
+        raise ValueError("tile_videos: one positive segment size per video, and video indices inside the bank")
+    rows = [NL * s for s in segs]
+    total = ncrops * sum(rows)
+    if out is None:
+        out = torch.empty(total, D, dtype=torch.float32, device=bank.device)
+    assert out.numel() == total * D and out.is_contiguous() and out.dtype == torch.float32 and out.device == bank.device
+    if V == 0:
+        return out
+    key = (bank.device, tuple(vids), tuple(segs), NL, int(ncrops))
+    tab = _TILE_TABLES.get(key)
+    if tab is None:
+        import numpy as np
+        out_off = np.concatenate([[0], np.cumsum([ncrops * r for r in rows[:-1]], dtype=np.int64)]).astype(np.int64)
+        blk = np.repeat(np.arange(V, dtype=np.int32), [ncrops * s for s in segs])
+        host = np.concatenate([out_off.view(np.int32), np.asarray(vids, dtype=np.int32), np.asarray(rows, dtype=np.int32), blk])
+        dev = torch.from_numpy(host).pin_memory().to(bank.device, non_blocking=True)         # one copy: int64 part first (aligned)
+        if len(_TILE_TABLES) >= 256:
+            _TILE_TABLES.pop(next(iter(_TILE_TABLES)))
+        tab = _TILE_TABLES[key] = (dev[:2 * V].view(torch.int64), dev[2 * V:3 * V], dev[3 * V:4 * V], dev[4 * V:])
+    h = _h(bank)
+    from . import _lib                       # (the parameter L hides this module's alias)
+    _lib.check(_lib.lib().acx_tile_videos(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), tab[1].data_ptr(), tab[0].data_ptr(),
+                                          tab[2].data_ptr(), tab[3].data_ptr(), out.data_ptr(), V, total, N, L, stride, ncrops, D,
+                                          _stream()), h)
     return out
 
 

@@ -869,6 +869,20 @@ int acx_sample_segments(acx_ctx* ctx, const float* bank, const int64_t* row_off,
                         const int32_t* starts, float* out, int32_t B, int32_t N, int32_t L, int32_t stride, int32_t ncrops,
                         int32_t D, void* stream);
 
+/* Test-mode tiles of a group of V videos of such a bank in ONE launch (feature_dataset.py:347-376: start indices k * L * stride,
+ * so row r of a video's tile is frame (r * stride) mod T), written video after video, each crop-major -- the tensor
+ * AnomalyCLIP.forward_test_many takes:
+ *   out[out_off[j] + c * rows[j] + r, :] = bank[row_off[vid[j]] + ((r * stride) mod frames[vid[j]]) * ncrops + c, :]
+ * for j < V, c < ncrops, r < rows[j], with rows[j] = N * L * S_j a multiple of N * L, out_off[j] = ncrops * (rows[0] + ... +
+ * rows[j-1]) and total_rows = ncrops * (rows[0] + ... + rows[V-1]).  blk[total_rows / (N * L)] maps every block of N * L output
+ * rows to its j.  row_off, frames, vid (int32 [V], values inside the bank), out_off (int64 [V]), rows (int32 [V]) and blk (int32) are
+ * DEVICE pointers.  The same pure copy: D % 4 == 0 and 16-byte aligned bank / out, else ACX_E_BADARG; so are null pointers,
+ * non-positive sizes, a total_rows that is no multiple of N * L, and total_rows or total_rows * stride at or above 2^31.
+ * V == 0 is ACX_OK without a launch. */
+int acx_tile_videos(acx_ctx* ctx, const float* bank, const int64_t* row_off, const int32_t* frames, const int32_t* vid,
+                    const int64_t* out_off, const int32_t* rows, const int32_t* blk, float* out, int32_t V, int64_t total_rows,
+                    int32_t N, int32_t L, int32_t stride, int32_t ncrops, int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
