@@ -177,8 +177,9 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__
 }  // namespace
 
 #define COMMA ,
+// (a width that is no multiple of 64 takes the default: D / 64 alone would hand 96 or 130 to the 64- or 128-wide kernel)
 #define DISPATCH_VPL(D, CALL)                          \
-  switch ((D) / 64) {                                  \
+  switch ((D) % 64 ? 0 : (D) / 64) {                   \
     case 1: { constexpr int V = 1; CALL; } break;      \
     case 2: { constexpr int V = 2; CALL; } break;      \
     case 4: { constexpr int V = 4; CALL; } break;      \

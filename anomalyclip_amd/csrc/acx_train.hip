@@ -242,6 +242,9 @@ __global__ __launch_bounds__(256) void leaky_grad_planes_kernel(const u16* __res
   u16 h[4], m[4], l[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
+    // no contraction in this block: fused into the subtraction below (x * 0.01 - hi in ONE rounding) the product never exists as an
+    // f32 value, and the planes are not those of the value stored in `out` (HIP's __fmul_rn is a plain product: it contracts too)
+#pragma clang fp contract(off)
     gv[k] *= sv[k] > 0.f ? 1.f : 0.01f;
     h[k] = f2bf(gv[k]);
     const float r1 = gv[k] - bf2f(h[k]);
@@ -1792,8 +1795,9 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restri
 }  // namespace
 
 #define COMMA ,
+// (a width that is no multiple of 64 takes the default: D / 64 alone would hand 96 or 130 to the 64- or 128-wide kernel)
 #define DISPATCH_VPL(D, CALL)                          \
-  switch ((D) / 64) {                                  \
+  switch ((D) % 64 ? 0 : (D) / 64) {                   \
     case 1: { constexpr int V = 1; CALL; } break;      \
     case 2: { constexpr int V = 2; CALL; } break;      \
     case 4: { constexpr int V = 4; CALL; } break;      \
