@@ -6,6 +6,10 @@
 #include <new>
 #include <stdlib.h>
 
+#ifndef ACX_ATTN_F32IN_DEFAULT
+#define ACX_ATTN_F32IN_DEFAULT 1   // ACX_OPT_ATTN_F32IN as acx_create sets it (A/B builds of the other default: -DACX_ATTN_F32IN_DEFAULT=0)
+#endif
+
 thread_local char acx_tls_err[512] = {0};
 
 extern "C" int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch,
@@ -43,6 +47,7 @@ extern "C" int acx_create(acx_ctx** out, int device) {
   c->opt_x6_tail = 0;
   c->opt_x6_strip = 1;
   c->opt_ln_rider = 1;
+  c->opt_attn_f32in = ACX_ATTN_F32IN_DEFAULT;
   c->comm = nullptr; c->comm_rank = 0; c->comm_world = 0;
   c->opt_x6_min_tiles = 18;
   c->err[0] = 0;
@@ -127,6 +132,9 @@ extern "C" int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value) {
     case ACX_OPT_LN_RIDER:
       if (value < 0) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: ln_rider is 0 (off), 1 (cost model) or a row count%s");
       ctx->opt_ln_rider = (long long)value;
+      return ACX_OK;
+    case ACX_OPT_ATTN_F32IN:
+      ctx->opt_attn_f32in = value != 0;
       return ACX_OK;
     case ACX_OPT_X6_MIN_TILES:
       if (value < 1) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: x6_min_tiles must be >= 1%s");
@@ -349,10 +357,13 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     const int qdt = ab ? ACX_BF16 : ACX_F32;
     // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
     const bool att_p3 = x6_qkv && x6_out && ws.qkv3 && !causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
+    // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
+    const bool att_p3f = att_p3 && pdt3 == ACX_BF16X3P && ctx && ctx->opt_attn_f32in;
+    const bool qkv_planes = att_p3 && !att_p3f;
     if (x6_qkv) {
-      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.in_proj_w_bf16, (int64_t)3 * W * W * 2, W, att_p3 ? (void*)ws.qkv3 : (void*)ws.qkv, 3 * W,
-                          (int)rows, 3 * W, W, b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, att_p3 ? ACX_BF16X3P : ACX_F32,
-                          att_p3 ? ws.qkv : ws.h, att_p3 ? (size_t)rows * 3 * W * 4 : (size_t)rows * W * 4))) return rc;   // (free f32 buffers: tail scratch)
+      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.in_proj_w_bf16, (int64_t)3 * W * W * 2, W, qkv_planes ? (void*)ws.qkv3 : (void*)ws.qkv, 3 * W,
+                          (int)rows, 3 * W, W, b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, qkv_planes ? ACX_BF16X3P : ACX_F32,
+                          qkv_planes ? ws.qkv : ws.h, qkv_planes ? (size_t)rows * 3 * W * 4 : (size_t)rows * W * 4))) return rc;   // (free f32 buffers: tail scratch)
     } else
     if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, qdt, 3 * W, (int)rows, 3 * W, W,
                      b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
@@ -361,6 +372,8 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
       return acx_fail(ctx, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
     if (ab) {
       if ((rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s))) return rc;
+    } else if (att_p3f) {  // f32 rows in, planes out
+      if ((rc = acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s))) return rc;
     } else if (att_p3) {   // planes in, planes out
       if ((rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, xm.f16 ? 103 : xm.pairs, s))) return rc;
     } else if (att_x3) {   // the attention writes the out-projection's three planes itself

@@ -696,7 +696,92 @@ __device__ __forceinline__ f32x16 ap3_mfma(const bf16x8 a, const bf16x8 b, const
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
 }
-template <int NPROD, int F16 = 0>
+#ifndef AP3F_ABL
+#define AP3F_ABL 0   // timing ablations of the f32-input arm (wrong results): 1 no split of K / V, 2 no split of Q, 8 every wave-iteration loads rows 0..7
+#endif
+// the f32-input arm's staging task of a lane (attn_p3_kernel<6, 0, 1>) in wave-iteration wi of K (col0 = W + 64 h) or V (col0 = 2 W +
+// 64 h) of the item whose first row is row0: 8 consecutive d of key row 8 wi + ((lane >> 2) & 7), panel lane >> 5, chunk lane & 3
+__device__ __forceinline__ const float4* ap3f_src(const float* __restrict__ qkv, int64_t ld, int64_t row0, int col0, int L, int wi, int lane) {
+  int r_ = min(8 * wi + ((lane >> 2) & 7), L - 1);   // behind the sequence: a finite duplicate
+#if AP3F_ABL & 8
+  r_ = (lane >> 2) & 7;
+#endif
+  return reinterpret_cast<const float4*>(qkv + (row0 + r_) * ld + (col0 + (lane >> 5) * 32 + (lane & 3) * 8));
+}
+// ... split into the three planes (ap3_split8: the sequence of the in-projection's plane epilogue) and written to the LDS blocks
+// blk0 + 2 p + panel; SWZ: K's chunk swizzle, applied on the LDS side
+template <int SWZ>
+__device__ __forceinline__ void ap3f_put(char* smem, const float4 a, const float4 b, int blk0, int wi, int lane) {
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  bf16x8 hi, mid, lo;
+#if AP3F_ABL & 1
+  hi = __builtin_bit_cast(bf16x8, a); mid = __builtin_bit_cast(bf16x8, b); lo = hi;
+#else
+  ap3_split8<0>(v, hi, mid, lo);
+#endif
+  const int row = 8 * wi + ((lane >> 2) & 7), ch = lane & 3;
+  char* dst = smem + (blk0 + (lane >> 5)) * AP3_BLK_B + row * 64 + (SWZ ? (ch ^ ((row >> 2) & 3)) : ch) * 16;
+  *reinterpret_cast<bf16x8*>(dst) = hi;
+  *reinterpret_cast<bf16x8*>(dst + 2 * AP3_BLK_B) = mid;
+  *reinterpret_cast<bf16x8*>(dst + 4 * AP3_BLK_B) = lo;
+}
+// K of an item by one wave: a rolled loop of two batches of 13 wave-iterations, the batch's 26 loads in flight at once (this code
+// shares the kernel's register budget)
+__device__ __forceinline__ void ap3f_stage_k(char* smem, const float* __restrict__ qkv, int64_t ld, int64_t row0, int col0, int L, int lane) {
+#pragma unroll 1
+  for (int w0 = 0; w0 < 26; w0 += 13) {
+    float4 ka_[13], kb_[13];
+#pragma unroll
+    for (int j = 0; j < 13; ++j) { const float4* p_ = ap3f_src(qkv, ld, row0, col0, L, w0 + j, lane); ka_[j] = p_[0]; kb_[j] = p_[1]; }
+    __builtin_amdgcn_sched_barrier(0);                  // every load of the batch issued before the first split
+#pragma unroll
+    for (int j = 0; j < 13; ++j) ap3f_put<1>(smem, ka_[j], kb_[j], 0, w0 + j, lane);
+  }
+}
+
+// measured staging variants of the f32-input arm, none faster than the default (profiles/attn_f32in_ab.txt): AP3F_KPIPE = n: K(next)
+// in batches of n wave-iterations, the first loaded in front of B2 and each next one while its predecessor is split (n > 5 spills);
+// AP3F_VEARLY: a wave's V share split and written between phase A's key tiles; AP3F_QLATE: Q split behind B1
+#ifndef AP3F_KPIPE
+#define AP3F_KPIPE 0
+#endif
+#ifndef AP3F_VEARLY
+#define AP3F_VEARLY 0
+#endif
+#ifndef AP3F_QLATE
+#define AP3F_QLATE 0
+#endif
+// batches of NB wave-iterations for the stager's software pipeline: the loads of batch n + 1 fly while batch n is split and written
+template <int NB>
+__device__ __forceinline__ void ap3f_kload(float4 (&a)[NB], float4 (&b)[NB], const float* __restrict__ qkv, int64_t ld, int64_t row0, int col0,
+                                           int L, int w0, int lane) {
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (w0 + j < 26) { const float4* p_ = ap3f_src(qkv, ld, row0, col0, L, w0 + j, lane); a[j] = p_[0]; b[j] = p_[1]; }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int NB>
+__device__ __forceinline__ void ap3f_kput(char* smem, const float4 (&a)[NB], const float4 (&b)[NB], int w0, int lane) {
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (w0 + j < 26) {
+      ap3f_put<1>(smem, a[j], b[j], 0, w0 + j, lane);
+      __builtin_amdgcn_sched_barrier(0);                // (one task's planes live at a time)
+    }
+}
+
+// F32IN (with NPROD = 6, F16 = 0: acx_attention_p3f): q | k | v arrive as the in-projection's f32 rows -- `qkv3` is that [rows, ld] f32
+// matrix and `plane_elems` its leading dimension ld -- and the kernel splits them itself: the LDS image of K and V, phase A, the
+// softmax, phase B and the epilogue are the plane kernel's, only the producers of the image (and of the Q fragments) differ.
+//   * a staging task of a lane is 8 consecutive d of one key row: two 16-byte loads, ap3_split8 (the in-projection's plane
+//     epilogue sequence: the bits are the ones that epilogue would have written), three 16-byte LDS writes; a wave-iteration
+//     covers 8 key rows x 64 d (lanes 0..31: panel 0, lanes 32..63: panel 1 -- every 16 lanes write 256 contiguous bytes), 26
+//     wave-iterations per operand; rows behind the sequence are duplicates of row L - 1, K's swizzle is applied on the LDS side;
+//   * K(next item) by the stager during phase B: two batches of 13 iterations, the batch's 26 loads in flight at once;
+//   * V(item) dealt over all eight waves as in AP3_STAGE_SHARED: loads issued right behind B1, split and written behind the
+//     phase's MFMAs, every wave waits for its own LDS writes (lgkmcnt) in front of B2;
+//   * a query wave loads its Q fragments as f32 (8 x 16 B per lane) and splits them into qf[0..2][ks].
+template <int NPROD, int F16 = 0, int F32IN = 0>
 __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
                                                          u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
                                                          long long* __restrict__ trace) {
@@ -754,24 +839,72 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
     }                                                                                              \
   } while (0)
 
+  const float* qf32 = reinterpret_cast<const float*>(qkv3);   // F32IN: the f32 rows, leading dimension plane_elems
+
   int item = blockIdx.x;
   if (item >= nitems) return;
   const float sc = 0.125f * 1.44269504088896340736f;    // 1 / sqrt(64) and log2(e): p = exp2((s - max) sc)
   if (wave == 7) {
     // ================================================================ the stager
+    if constexpr (F32IN) ap3f_stage_k(smem, qf32, plane_elems, (int64_t)(item / heads) * L, W + (item % heads) * 64, L, lane); else
     AP3_STAGE(item, 1, 0, 1);                           // K of the first item
     for (; item < nitems; item += (int)gridDim.x) {
       AP3_STAMP(ord, 0);
+      if constexpr (F32IN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // K(item) written
+      else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // K(item) landed
       AP3_STAMP(ord, 1);
       __builtin_amdgcn_s_barrier();                     // B1: ... and everybody is done with V(previous item)
       AP3_STAMP(ord, 2);
+      constexpr int KNB = AP3F_KPIPE > 0 ? AP3F_KPIPE : 1, KNBATCH = (26 + KNB - 1) / KNB;
+      [[maybe_unused]] float4 pa_[2][KNB], pb_[2][KNB];
+      [[maybe_unused]] const int nxt_ = item + (int)gridDim.x;
+      [[maybe_unused]] const int64_t nrow0 = (int64_t)(nxt_ / heads) * L;
+      [[maybe_unused]] const int ncol0 = W + (nxt_ % heads) * 64;
+      if constexpr (F32IN) {
+        asm volatile("" ::: "memory");
+#if AP3F_KPIPE
+        float4 va_[3], vb_[3];
+#pragma unroll
+        for (int z = 0; z < 3; ++z) {
+          const float4* p_ = ap3f_src(qf32, plane_elems, (int64_t)(item / heads) * L, 2 * W + (item % heads) * 64, L, 7 + 8 * z, lane);
+          va_[z] = p_[0]; vb_[z] = p_[1];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // the first batch of K(next item): only its LDS writes have to wait for B2
+        if (nxt_ < nitems) ap3f_kload<KNB>(pa_[0], pb_[0], qf32, plane_elems, nrow0, ncol0, L, 0, lane);
+#pragma unroll
+        for (int z = 0; z < 3; ++z) ap3f_put<0>(smem, va_[z], vb_[z], 6, 7 + 8 * z, lane);
+#else
+#pragma unroll 1
+        for (int wi = 7; wi < 26; wi += 8) {
+          const float4* p_ = ap3f_src(qf32, plane_elems, (int64_t)(item / heads) * L, 2 * W + (item % heads) * 64, L, wi, lane);
+          ap3f_put<0>(smem, p_[0], p_[1], 6, wi, lane);
+        }
+#endif
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      } else {
       AP3_STAGE_SHARED(item, 2, 6, 0);                  // this wave's share of V(item): needed after phase A
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
       AP3_STAMP(ord, 3);
       __builtin_amdgcn_s_barrier();                     // B2: V(item) landed, everybody is done with K(item)
       AP3_STAMP(ord, 4);
       const int nxt = item + (int)gridDim.x;
+      if constexpr (F32IN) {
+        asm volatile("" ::: "memory");
+#if AP3F_KPIPE
+        if (nxt < nitems) {
+#pragma unroll
+          for (int bt = 0; bt < KNBATCH; ++bt) {
+            if (bt + 1 < KNBATCH) ap3f_kload<KNB>(pa_[(bt + 1) & 1], pb_[(bt + 1) & 1], qf32, plane_elems, nrow0, ncol0, L, (bt + 1) * KNB, lane);
+            ap3f_kput<KNB>(smem, pa_[bt & 1], pb_[bt & 1], bt * KNB, lane);
+          }
+        }
+#else
+        if (nxt < nitems) ap3f_stage_k(smem, qf32, plane_elems, (int64_t)(nxt / heads) * L, W + (nxt % heads) * 64, L, lane);
+#endif
+      } else
       if (nxt < nitems) AP3_STAGE(nxt, 1, 0, 1);        // K(next item) during this item's phase B
       AP3_STAMP(ord, 5);
       ++ord;
@@ -796,6 +929,25 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
     const int b = item / heads, h = item - b * heads;
     // ---------------------------------------------------------------- phase A: S^T = K Q^T
     bf16x8 qf[3][4];
+    if constexpr (F32IN) {                              // d = 16 ks + 8 hh .. + 7 of the query row
+      const float4* qp = reinterpret_cast<const float4*>(qf32 + ((int64_t)b * L + qrow) * plane_elems + (h * 64 + 8 * hh));
+      float4 qa[4], qb[4];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) { qa[ks] = qp[4 * ks]; qb[ks] = qp[4 * ks + 1]; }
+#if AP3F_ABL & 2
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) { qf[0][ks] = qf[2][ks] = __builtin_bit_cast(bf16x8, qa[ks]); qf[1][ks] = __builtin_bit_cast(bf16x8, qb[ks]); }
+#elif !AP3F_QLATE
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const float qv[8] = {qa[ks].x, qa[ks].y, qa[ks].z, qa[ks].w, qb[ks].x, qb[ks].y, qb[ks].z, qb[ks].w};
+        ap3_split8<0>(qv, qf[0][ks], qf[1][ks], qf[2][ks]);
+      }
+#else
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) { qf[0][ks] = __builtin_bit_cast(bf16x8, qa[ks]); qf[1][ks] = __builtin_bit_cast(bf16x8, qb[ks]); }
+#endif
+    } else
 #pragma unroll
     for (int p = 0; p < NPL; ++p)
 #pragma unroll
@@ -805,11 +957,36 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
     AP3_STAMP(ord, 0);
     __builtin_amdgcn_s_barrier();                       // B1
     AP3_STAMP(ord, 1);
+    float4 sva[4], svb[4];                              // F32IN: this wave's share of V(item): wave-iterations wave + 8 z < 26
+    if constexpr (F32IN) {
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int z = 0; z < 4; ++z) {
+        sva[z] = svb[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (z < 3 || wave < 2) {
+          const float4* p_ = ap3f_src(qf32, plane_elems, (int64_t)b * L, 2 * W + h * 64, L, wave + 8 * z, lane);
+          sva[z] = p_[0]; svb[z] = p_[1];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                // the loads fly during phase A
+#if AP3F_QLATE
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {                  // split in phase A's first scheduling region
+        const float4 qa_ = __builtin_bit_cast(float4, qf[0][ks]), qb_ = __builtin_bit_cast(float4, qf[1][ks]);
+        const float qv[8] = {qa_.x, qa_.y, qa_.z, qa_.w, qb_.x, qb_.y, qb_.z, qb_.w};
+        ap3_split8<0>(qv, qf[0][ks], qf[1][ks], qf[2][ks]);
+      }
+#endif
+    } else
     AP3_STAGE_SHARED(item, 2, 6, 0);                    // this wave's share of V(item)
     AP3_STAMP(ord, 2);
     f32x16 sacc[7];
 #pragma unroll
     for (int kt = 0; kt < 7; ++kt) {
+#if AP3F_VEARLY
+      if constexpr (F32IN)                              // this wave's V share, one wave-iteration per key tile from the fourth on
+        if (kt >= 3 && (kt < 6 || wave < 2)) ap3f_put<0>(smem, sva[kt - 3], svb[kt - 3], 6, wave + 8 * (kt - 3), lane);
+#endif
 #pragma unroll
       for (int e = 0; e < 16; ++e) sacc[kt][e] = 0.f;
 #pragma unroll
@@ -835,6 +1012,14 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
 #endif
     }
     AP3_STAMP(ord, 3);
+    if constexpr (F32IN) {
+#if !AP3F_VEARLY
+#pragma unroll
+      for (int z = 0; z < 4; ++z)
+        if (z < 3 || wave < 2) ap3f_put<0>(smem, sva[z], svb[z], 6, wave + 8 * z, lane);
+#endif
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's share of V(item) written
+    } else
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's share of V(item) landed
     __builtin_amdgcn_s_barrier();                       // B2
     AP3_STAMP(ord, 4);
@@ -990,6 +1175,32 @@ extern "C" int acx_attention_p3n(acx_ctx* ctx, const void* qkv_planes, void* out
   else ACX_AP3(6);
 #undef ACX_AP3
   ACX_CHECK_LAUNCH(ctx, "acx_attention_p3");
+  return ACX_OK;
+}
+
+// the six-product form fed with the in-projection's f32 rows: qkv [batch * L, 3 heads * 64] f32 (leading dimension ldqkv) -> the same
+// three output planes, bit for bit what acx_attention_p3 gives on acx_split_bf16x3_panel(qkv); same L gate
+extern "C" int acx_attention_p3f(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int32_t batch, int32_t L, int32_t heads,
+                                 void* stream) {
+  if (!qkv || !out_planes) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_p3f: null pointer%s");
+  if (batch <= 0) return ACX_OK;
+  if (L <= 192 || L > AP3_ROWS || heads <= 0 || ldqkv < (int64_t)3 * heads * 64 || (ldqkv & 3) || (((uintptr_t)qkv | (uintptr_t)out_planes) & 15))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3f: 192 < L <= 208, 16-byte aligned qkv and planes, ldqkv %% 4 == 0 and >= 3 heads * 64%s");
+  const int64_t rows = (int64_t)batch * L;
+  const int nitems = batch * heads;
+  const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
+  hipStream_t s = (hipStream_t)stream;
+  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
+#if AP3_TRACE
+  long long* trace_ = getenv("ACX_TRACE_PTR") ? (long long*)strtoull(getenv("ACX_TRACE_PTR"), nullptr, 0) : nullptr;
+#else
+  long long* trace_ = nullptr;
+#endif
+  const dim3 grid((unsigned)(nitems < ncu ? nitems : ncu));
+  acx_launch_lds<attn_p3_kernel<6, 0, 1>>(dev_slot, grid, dim3(512), (size_t)AP3_LDS_B, s, (const u16*)qkv, ldqkv, rows, (u16*)out_planes,
+                                          rows * heads * 64, L, heads, nitems, trace_);
+  ACX_CHECK_LAUNCH(ctx, "acx_attention_p3f");
   return ACX_OK;
 }
 

@@ -110,6 +110,16 @@ def set_ln_rider(device_index: int, mode: int) -> None:
     L.check(L.lib().acx_set_option(h, L.OPT_LN_RIDER, int(mode)), h)
 
 
+ATTN_F32IN_DEFAULT = True   # ACX_OPT_ATTN_F32IN as acx_create sets it (tests restore it)
+
+
+def set_attn_f32in(device_index: int, on: bool) -> None:
+    """ACX_OPT_ATTN_F32IN: 1 (default) = in the six-product ViT layers the in-projection writes f32 rows and the plane attention
+    splits q | k | v itself (acx_attention_p3f); 0 = q | k | v pass through memory as three bf16 planes.  Bit-identical results."""
+    h = L.ctx(device_index)
+    L.check(L.lib().acx_set_option(h, L.OPT_ATTN_F32IN, int(bool(on))), h)
+
+
 def ln_rider_plan(M: int, N: int, K: int, ncu: int, ksplit: int = 1, rate: float = 0.0):
     """(rows that ride, rows the full rounds complete) of acx_gemm_ln for an eligible product on ncu workgroups -- host arithmetic,
     no device; rate: LayerNorm rows of 768 columns per us and rider workgroup (<= 0: the library's constant)"""
@@ -482,6 +492,18 @@ def attention_p3(qkv3: torch.Tensor, batch: int, L_: int, heads: int, products: 
     out = (torch.zeros if products == 3 else torch.empty)(3, batch * L_, W, dtype=_BF16, device=qkv3.device)   # (3 products: lo plane unwritten)
     h = _h(qkv3)
     L.check(L.lib().acx_attention_p3n(h, qkv3.data_ptr(), out.data_ptr(), batch, L_, heads, int(products), _stream()), h)
+    return out
+
+
+def attention_p3_f32(qkv: torch.Tensor, batch: int, L_: int, heads: int) -> torch.Tensor:
+    """acx_attention_p3f: the six-product plane attention fed with f32 q | k | v [batch * L, 3 * heads * 64] (rows may be strided:
+    stride(0) % 4 == 0); returns the three output planes [3, batch * L, heads * 64] in K-panel memory order -- the bits
+    attention_p3(split_bf16x3(qkv, panel=True)) gives."""
+    W = heads * 64
+    assert qkv.dtype == torch.float32 and qkv.shape == (batch * L_, 3 * W) and qkv.stride(1) == 1
+    out = torch.empty(3, batch * L_, W, dtype=_BF16, device=qkv.device)
+    h = _h(qkv)
+    L.check(L.lib().acx_attention_p3f(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), batch, L_, heads, _stream()), h)
     return out
 
 

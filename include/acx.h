@@ -112,8 +112,12 @@ const char* acx_last_error(acx_ctx* ctx);
  *                           1 (default) = the workgroups that have no tile in a residual product's partly filled last round run
  *                           LayerNorm rows beside it, as many as the cost model says fit; 0 = product, then LayerNorm; > 1 = ride up
  *                           to this many of the completed rows (measurements).  Results are BIT-IDENTICAL for every value. */
+/*   ACX_OPT_ATTN_F32IN     ACX_PREC_F32X6 drivers, six-product mode, layers whose attention is acx_attention_p3: 1 (default) = the
+ *                           in-projection writes f32 rows and the attention splits q | k | v into planes itself (acx_attention_p3f:
+ *                           no plane round trip through memory); 0 = the in-projection's epilogue writes the three planes and
+ *                           acx_attention_p3 reads them.  Results are BIT-IDENTICAL for both values. */
 enum { ACX_OPT_RING_MIN_TILES = 1, ACX_OPT_SK_MAX_M = 2, ACX_OPT_TN_P256_MIN_ROWS = 3, ACX_OPT_X6_CUS = 4, ACX_OPT_X6_TAIL_SPLIT = 5,
-       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8 };
+       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8, ACX_OPT_ATTN_F32IN = 9 };
 int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value);
 
 /* ------------------------------------------------------------------------------------------
@@ -247,6 +251,11 @@ int acx_attention_p3(acx_ctx* ctx, const void* qkv_planes, void* out_planes, int
  * are not read, the output's lo plane is not written -- the ACX_PREC_F32X3 mode, not f32-accurate), or 103 = three products on TWO
  * fp16 planes per operand (ACX_F16X2P images of q | k | v in, of the output out: the ACX_PREC_F16X3 mode) */
 int acx_attention_p3n(acx_ctx* ctx, const void* qkv_planes, void* out_planes, int32_t batch, int32_t L, int32_t heads, int32_t products,
+                      void* stream);
+/* acx_attention_p3 fed with the in-projection's f32 rows: qkv [batch * L, 3 heads * 64] f32 (16-byte aligned, ldqkv % 4 == 0); the
+ * kernel splits q | k | v into the three planes as it stages them -- the same split, the same products in the same order: the
+ * output planes equal acx_attention_p3's on acx_split_bf16x3_panel(qkv) bit for bit.  Six products only; same L gate. */
+int acx_attention_p3f(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int32_t batch, int32_t L, int32_t heads,
                       void* stream);
 /* ... with the planes in K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo == heads * 64) */
 int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,

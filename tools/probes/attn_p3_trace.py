@@ -1,6 +1,7 @@
 """Development probe: phase timeline of attn_p3_kernel's workgroup 0 (needs a -DAP3_TRACE=1 build through ACX_LIB_PATH):
 per wave and item, s_memrealtime (100 MHz) stamps at  0 item start | 1 after B1 | 2 V share issued | 3 Q K^T done | 4 after B2 |
-5 softmax done | 6 P V done | 7 stores issued   (stager wave 7: 0 start | 1 K landed | 2 after B1 | 3 V share landed | 4 after B2 | 5 K(next) issued)."""
+5 softmax done | 6 P V done | 7 stores issued   (stager wave 7: 0 start | 1 K landed | 2 after B1 | 3 V share landed | 4 after B2 | 5 K(next) issued).
+    python tools/probes/attn_p3_trace.py [f32]     f32: the f32-input arm (acx_attention_p3f; the stager's point 5 is then K(next) WRITTEN)"""
 import os
 import sys
 
@@ -16,7 +17,10 @@ qkv = torch.randn(B * L_, 3 * H * 64, device="cuda")
 q3 = ops.split_bf16x3(qkv, panel=True)
 for _ in range(3):
     tr.zero_()
-    ops.attention_p3(q3, B, L_, H)
+    if "f32" in sys.argv[1:]:
+        ops.attention_p3_f32(qkv, B, L_, H)
+    else:
+        ops.attention_p3(q3, B, L_, H)
 torch.cuda.synchronize()
 t = tr.cpu().numpy().reshape(16, 8, 8).astype("float64") / 100.0        # us
 t0 = t[2, :7, 0].min()

@@ -25,6 +25,11 @@ if which in ("vit", "all"):
         t6 = _event_time(lambda: ops.gemm_x6(a3, w3, **kw), 8)
         fl = 2.0 * M * N * K
         print(f"{name:5s} x6 {t6 * 1e3:7.3f} ms {fl / t6 / 1e12:6.1f} TF-equiv ({6 * fl / t6 / 1e12:6.0f} bf16 TF)", flush=True)
+        if name == "qkv":   # the in-projection's other epilogue (ACX_OPT_ATTN_F32IN = 0: q | k | v leave as three bf16 planes)
+            op = torch.empty(3, M, N, dtype=torch.bfloat16, device=dev)
+            t6 = _event_time(lambda: ops.gemm_x6(a3, w3, bias=bias, out=op, planes_out=True), 8)
+            print(f"qkv->planes x6 {t6 * 1e3:7.3f} ms {fl / t6 / 1e12:6.1f} TF-equiv ({6 * fl / t6 / 1e12:6.0f} bf16 TF)", flush=True)
+            del op
         if name == "fc":
             op = torch.empty(3, M, N, dtype=torch.bfloat16, device=dev)
             t6 = _event_time(lambda: ops.gemm_x6(a3, w3, bias=bias, act=L.ACT_QUICKGELU, out=op, planes_out=True), 8)
