@@ -190,6 +190,36 @@ def gen_loss(seed=31):
          g_sim=s1.grad, g_sim_topk=s2.grad, g_scores=s3.grad)
 
 
+LOSS_WEIGHTED = dict(B=4, N=6, L=5, C1=6, K=2, normal_id=6, lambdas=(0.7, 1.3, 0.9, 1.7, 0.6, 3e-3, 5e-2))
+
+
+def gen_loss_weighted(seed=32):
+    """the loss at seven DISTINCT weights (every other fixture has the five leading ones at 1.0), on a grid that is not 32 x 16, with
+    normal_id the last class: pins which lambda multiplies which term"""
+    g = torch.Generator().manual_seed(seed)
+    B, N, L, C1, K, normal_id = (LOSS_WEIGHTED[k] for k in ("B", "N", "L", "C1", "K", "normal_id"))
+    sim = 3 * torch.randn(B * N * L, C1, generator=g)
+    scores = torch.rand(B * N * L, generator=g) * 0.98 + 0.01
+    labels = torch.tensor([5, 0, normal_id, normal_id])
+    ia = torch.stack([torch.randperm(N, generator=g)[:K] for _ in range(B // 2)])
+    in_ = torch.stack([torch.randperm(N, generator=g)[:K] for _ in range(B // 2)])
+    ba = torch.stack([torch.randperm(N, generator=g)[:K] for _ in range(B // 2)])
+    rows = ((torch.arange(B).view(B, 1) * N + torch.cat([ia, in_])).view(B, K, 1) * L + torch.arange(L)).reshape(-1)
+    sim_topk = sim[rows].clone()                                         # the top-k segments' rows, as the selector gathers them
+    crit = ns.loss.ComputeLoss(normal_id, K, *LOSS_WEIGHTED["lambdas"], L, N)
+    with torch.enable_grad():
+        s1 = sim.clone().requires_grad_(True)
+        s2 = sim_topk.clone().requires_grad_(True)
+        s3 = scores.clone().requires_grad_(True)
+        outs = crit(s1, s2, labels.clone(), s3, ia, in_, ba)
+        outs[0].backward()
+    print("loss_weighted:", [f"{float(o):.6f}" for o in outs])
+    save("loss_weighted", sim=sim, sim_topk=sim_topk, scores=scores, labels=labels, idx_topk_abn=ia, idx_topk_nor=in_,
+         idx_bottomk_abn=ba, losses=torch.stack([o.detach() for o in outs]), g_sim=s1.grad, g_sim_topk=s2.grad,
+         g_scores=s3.grad, lambdas=np.asarray(LOSS_WEIGHTED["lambdas"], dtype=np.float64),
+         shape=np.asarray([B, N, L, C1, K, normal_id], dtype=np.int64))
+
+
 # ---------------------------------------------------------------- 8. end-to-end (tiny geometry)
 def gen_e2e(table, seed=41):
     geom = IW.TINY
@@ -360,6 +390,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["config0"]:
         gen_config0(json.load(open(os.path.join(REPO, "anomalyclip_amd", "data", "prompts.json"))))
         sys.exit(0)
+    if sys.argv[1:] == ["loss_weighted"]:
+        gen_loss_weighted()
+        sys.exit(0)
     table = gen_prompts()
     gen_vit("vit_tiny", IW.TINY, seed=1, nframes=3, store_tokens=True)
     gen_vit("vit_b16", IW.VIT_B16, seed=2, nframes=2, store_tokens=False)
@@ -368,6 +401,7 @@ if __name__ == "__main__":
     gen_selector()
     gen_temporal()
     gen_loss()
+    gen_loss_weighted()
     gen_e2e(table)
     gen_tables()
     gen_config0(table)

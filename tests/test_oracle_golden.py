@@ -106,6 +106,28 @@ def test_loss(golden):
     close(s3.grad, g["g_scores"], rtol=1e-4, atol=1e-8)
 
 
+def test_loss_weighted(golden):
+    """the reference's ComputeLoss at seven distinct weights on a 6 x 5 grid with normal_id the last class: a lambda attached to the
+    wrong term of the oracle shows here (every other fixture has the five leading weights at 1.0)"""
+    g = golden("loss_weighted")
+    B, N, Lg, C1, K, nid = (int(v) for v in g["shape"])
+    lam = [float(v) for v in g["lambdas"]]
+    assert len(set(lam)) == 7
+    with torch.enable_grad():
+        s1 = T(g["sim"]).requires_grad_(True)
+        s2 = T(g["sim_topk"]).requires_grad_(True)
+        s3 = T(g["scores"]).requires_grad_(True)
+        outs = O.compute_loss(s1, s2, T(g["labels"]), s3, T(g["idx_topk_abn"]), T(g["idx_topk_nor"]),
+                              T(g["idx_bottomk_abn"]), normal_id=nid, num_topk=K, num_segments=N, frames_per_segment=Lg,
+                              lambda_dir_abn=lam[0], lambda_dir_nor=lam[1], lambda_topk_abn=lam[2], lambda_bottomk_abn=lam[3],
+                              lambda_topk_nor=lam[4], lambda_smooth=lam[5], lambda_sparse=lam[6])
+        outs[0].backward()
+    close(torch.stack([o.detach() for o in outs]), g["losses"], rtol=1e-5, atol=1e-6)
+    close(s1.grad, g["g_sim"], rtol=1e-4, atol=1e-8)
+    close(s2.grad, g["g_sim_topk"], rtol=1e-4, atol=1e-8)
+    close(s3.grad, g["g_scores"], rtol=1e-4, atol=1e-8)
+
+
 def test_e2e_tiny(golden, prompts_table):
     g = golden("e2e_tiny")
     seed = int(g["seed"])
