@@ -115,6 +115,15 @@ class ResnetDesc(C.Structure):          # == struct acx_resnet_desc
                 ("prec", c_int32)]
 
 
+class JpegInfo(C.Structure):            # == struct acx_jpeg_info
+    _fields_ = [(n, c_int32) for n in ("width", "height", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y", "restart_interval")] + \
+               [(n, c_int32 * 4) for n in ("comp_h", "comp_v", "comp_tq", "comp_td", "comp_ta", "comp_width", "comp_height",
+                                           "blocks_wide", "blocks_high")] + \
+               [("coef_offset", c_int64 * 4), ("coef_elems", c_int64), ("scan_offset", c_int64),
+                ("qtab", (C.c_uint16 * 64) * 4), ("qtab_present", C.c_uint8 * 4), ("huff_present", (C.c_uint8 * 4) * 2),
+                ("huff_bits", ((C.c_uint8 * 17) * 4) * 2), ("huff_vals", ((C.c_uint8 * 256) * 4) * 2)]
+
+
 _SIGS = {
     "acx_version": (C.c_int, []),
     "acx_create": (C.c_int, [C.POINTER(c_void_p), C.c_int]),
@@ -269,6 +278,9 @@ _SIGS = {
                                   c_void_p, c_void_p]),
     "acx_sample_segments": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),
     "acx_tile_videos": (C.c_int, [c_void_p] * 9 + [c_int32, c_int64] + [c_int32] * 5 + [c_void_p]),
+    "acx_jpeg_parse": (C.c_int, [c_void_p, c_size_t, c_void_p]),
+    "acx_jpeg_entropy_decode": (C.c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    "acx_jpeg_reconstruct": (C.c_int, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
 }
 
 # entry points added by later translation units register themselves here (name -> signature)

@@ -8,7 +8,8 @@ stream the files through `FeatureStream` and add the per-frame labels of the tem
 `load_from_features: false` with `encoder=`: the frame folders `<frames_root>/<video>/<image_tmpl>` are encoded ONCE by the frozen
 CLIP image encoder into such banks (`FeatureBank.from_frames`; the reference's frame transform is deterministic, so its per-step
 encoding gives the same rows) and every loader draws from a bank: `ResidentTrainLoader` as above, `ResidentTestLoader` for the
-test-mode tiles.  No feature file is written."""
+test-mode tiles.  No feature file is written.  `decode="gpu"` (a keyword beside `encoder=`, not one of the reference's keys) has the
+frames' baseline JPEG files reconstructed on the device (anomalyclip_amd/jpeg.py) instead of decoded by Pillow: the same banks."""
 from __future__ import annotations
 
 import os
@@ -122,7 +123,9 @@ class ResidentTestLoader(StreamedTestLoader):
 
 
 class AnomalyCLIPDataModule:
-    def __init__(self, encoder=None, **hparams):
+    def __init__(self, encoder=None, decode: str = "pil", **hparams):
+        from .jpeg import check_decode
+        self.decode = check_decode(decode)                        # frames mode: how the frame files are decoded (not a reference key)
         hp = dict(_DEFAULTS)
         hp.update(hparams)                                        # unknown keys are kept, like save_hyperparameters does
         missing = [k for k in HPARAM_KEYS if k not in hp]
@@ -178,7 +181,8 @@ class AnomalyCLIPDataModule:
         enc.eval()
         try:
             return FeatureBank.from_frames(enc, records, hp.frames_root, hp.image_tmpl, int(hp.ncrops), hp.get("scale_size"),
-                                           int(hp.get("decode_threads", 8)), self.device, hp.get("max_bytes"), hp.get("log"))
+                                           int(hp.get("decode_threads", 8)), self.device, hp.get("max_bytes"), hp.get("log"),
+                                           decode=self.decode)
         finally:
             enc.train(was_training)
 

@@ -6,7 +6,8 @@ Per video: frames are decoded on a thread pool into two pinned uint8 buffers in 
 `Image.open(...).convert("RGB")`, video_dataset.py:204), copied to the device on a side stream, cropped and normalised by ONE
 `preprocess_crops` call per batch, encoded by the CLIP image encoder at its own precision, and the rows come back asynchronously
 into a pinned `[T * ncrops, D]` buffer.  A batch is `max(1, chunk // ncrops)` frames, i.e. one encoder launch of at most `chunk`
-rows; decoding batch k + 1 overlaps the GPU's work on batch k.
+rows; decoding batch k + 1 overlaps the GPU's work on batch k.  `decode="gpu"` (`--decode gpu`) leaves only the Huffman decoding of
+baseline JPEG files on the host and reconstructs the frames on the device (anomalyclip_amd/jpeg.py): the same bytes, the same files.
 
     python -m anomalyclip_amd.extract --arch ViT-B/16 --weights last.ckpt --frames-root frames --out-root features --ncrops 5
 """
@@ -71,6 +72,10 @@ class FrameFolderReader:
             self.indices = list(range(int(start), int(end) + 1))
         if not self.indices:
             raise ValueError(f"{self.dir}: no frames ({template})")
+        self._init_reader(threads, pinned)
+
+    def _init_reader(self, threads: int, pinned: Optional[bool]):
+        """the reader's state beside `dir`, `template` and `indices` (also for a reader made from another's frames)"""
         self.threads = max(1, min(int(threads), MAX_DECODE_THREADS))
         self.pinned = torch.cuda.is_available() if pinned is None else bool(pinned)
         self._buf = [None, None]
@@ -126,6 +131,10 @@ class FrameFolderReader:
         dst = view.numpy()
         list(self.pool().map(lambda j: self._decode(i0 + j, dst[j]), range(i1 - i0)))
         return view
+
+    def decode_batch(self, i0: int, i1: int, slot: int) -> torch.Tensor:
+        """the host stage of one batch, on its own (measurements): frames i0 ... i1 - 1 decoded into the slot's buffer"""
+        return self._fill(i0, i1, slot)
 
     def batches(self, n: int) -> Iterator[Tuple[int, torch.Tensor]]:
         """(slot, uint8 [k, H, W, 3]) for consecutive groups of n frames; batch k + 1 is being decoded while k is consumed.  The
@@ -246,11 +255,17 @@ def encode_video(encoder, frames, ncrops: int = 1, scale_size: Optional[int] = N
     assert r0 == len(reader) * ncrops, (r0, len(reader), ncrops)
 
 
-def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False) -> dict:
+def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False,
+                  decode: str = "pil") -> dict:
     """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
+    decode="gpu": the frames of a FrameFolderReader are read by a jpeg.JpegFolderReader over the same files instead.
     Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
+    from . import jpeg
+    jpeg.check_decode(decode)
     encoder = _encoder_of(encoder)
     reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
+    if decode == "gpu" and isinstance(reader, FrameFolderReader) and not isinstance(reader, jpeg.JpegFolderReader):
+        reader = jpeg.JpegFolderReader.like(reader)
     T, D = len(reader), int(encoder.output_dim)
     shape = (T * ncrops, D)
     check_eval_mode(encoder)
@@ -278,9 +293,12 @@ def list_videos(frames_root: str, template: str = TEMPLATE) -> List[str]:
 
 def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root: str, out_root: str, ncrops: int = 1,
                     scale_size: Optional[int] = None, overwrite: bool = False, template: str = TEMPLATE,
-                    decode_threads: int = 8, log=None) -> dict:
+                    decode_threads: int = 8, log=None, decode: str = "pil") -> dict:
     """Every video of the annotation file (rows `path start end label...`; without one: every frame folder under frames_root)
-    -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  Returns {written, skipped, frames, rows}."""
+    -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  decode: "pil" (Pillow on the host) or "gpu" (baseline
+    JPEG reconstructed on the device; every other file through Pillow).  Returns {written, skipped, frames, rows}."""
+    from . import jpeg
+    jpeg.check_decode(decode)
     encoder = _encoder_of(net_or_encoder)
     if annotation_file:
         videos = read_annotations(annotation_file)
@@ -288,7 +306,7 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
         videos = [(v, None, None) for v in list_videos(frames_root, template)]
     counts = {"written": 0, "skipped": 0, "frames": 0, "rows": 0}
     for video, start, end in videos:
-        reader = FrameFolderReader(frames_root, video, start, end, template, decode_threads)
+        reader = jpeg.make_reader(decode, frames_root, video, start, end, template, decode_threads)
         try:
             r = extract_video(encoder, reader, os.path.join(out_root, video), ncrops, scale_size, overwrite)
         finally:
@@ -346,6 +364,8 @@ def _parser():
     p.add_argument("--scale-size", type=int, default=None, help="shorter side before cropping (default: crop, or crop * 8 // 7)")
     p.add_argument("--precision", default="auto", choices=sorted(PRECISIONS))
     p.add_argument("--overwrite", action="store_true")
+    p.add_argument("--decode", default="pil", choices=("pil", "gpu"),
+                   help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device")
     return p
 
 
@@ -379,7 +399,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     load_encoder_weights(enc, a.arch, a.weights)
     enc = enc.to(torch.device("cuda", torch.cuda.current_device())).eval()
     counts = extract_dataset(enc, a.annotations, a.frames_root, a.out_root, a.ncrops, a.scale_size, a.overwrite,
-                             log=lambda s: print(s, file=sys.stderr))
+                             log=lambda s: print(s, file=sys.stderr), decode=a.decode)
     import json
     print(json.dumps(counts))
     return 0

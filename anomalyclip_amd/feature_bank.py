@@ -61,15 +61,17 @@ class FeatureBank:
     @classmethod
     def from_frames(cls, encoder, records, frames_root: str, image_tmpl: str = "{:06d}.jpg", ncrops: int = 1,
                     scale_size: Optional[int] = None, decode_threads: int = 8, device: Optional[torch.device] = None,
-                    max_bytes: Optional[int] = None, log=None) -> "FeatureBank":
+                    max_bytes: Optional[int] = None, log=None, decode: str = "pil") -> "FeatureBank":
         """The same bank, filled by the CLIP image encoder instead of from files: every frame an annotation row names
         (`records`: objects with `video`, `start_frame`, `end_frame`, `label`; frame t of video v is
         `<frames_root>/<video>/image_tmpl.format(t + start_frame)`, end inclusive) is decoded and encoded ONCE through
         extract.encode_video -- the launches `extract_video` makes, so the rows are the rows of the file it would write -- and each
         block of rows is copied from the encoder's output straight into its bank slice.  `paths` are the frame folders,
         `file_frames == num_frames`.  The size follows from the rows and `encoder.output_dim` and is checked before any frame is
-        opened."""
+        opened.  decode: "pil" or "gpu", as extract.extract_dataset takes it."""
         from . import extract as X
+        from . import jpeg
+        jpeg.check_decode(decode)
         encoder = X._encoder_of(encoder)
         records = list(records)
         self = cls.__new__(cls)
@@ -105,7 +107,8 @@ class FeatureBank:
         self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             for v, r in enumerate(records):
-                reader = X.FrameFolderReader(str(frames_root), r.video, int(r.start_frame), int(r.end_frame), image_tmpl, decode_threads)
+                reader = jpeg.make_reader(decode, str(frames_root), r.video, int(r.start_frame), int(r.end_frame), image_tmpl,
+                                          decode_threads)
                 try:
                     self.fill_video(encoder, v, reader, scale_size)
                 except FileNotFoundError as e:

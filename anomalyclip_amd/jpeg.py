@@ -1,0 +1,204 @@
+"""Baseline JPEG frames decoded on the GPU, bit for bit Pillow's `Image.open(p).convert("RGB")`.
+
+The decoder is split where the work changes character.  Huffman decoding is sequential and driven by untrusted bytes: it runs on the
+host (`acx_jpeg_parse` + `acx_jpeg_entropy_decode`, called through ctypes with the GIL released, one frame per pool thread) and
+leaves every block's 64 coefficients, de-zigzagged and not dequantised, in a pinned buffer.  Dequantisation, the inverse DCT, chroma
+upsampling and the colour conversion are regular integer arithmetic over every sample: `ops.jpeg_reconstruct` does them on the
+device for a whole batch, into the uint8 [k, H, W, 3] tensor `preprocess_crops` takes.
+
+`JpegFolderReader` is `extract.FrameFolderReader` with that decoder: same folder conventions, same interface, but its batches are
+DEVICE tensors.  A file the host decoder does not take (progressive, CMYK, subsampled and at most 4 pixels wide, PNG under a `.jpg`
+template, damaged, of another sampling than the video's leading frames ...) is decoded by Pillow in the same worker and copied into its place, so every frame is
+Pillow's either way; `fallbacks` counts them."""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .extract import TEMPLATE, FrameFolderReader
+
+DECODERS = ("pil", "gpu")
+GEOMETRY_PROBES = 4                    # leading frames looked at for the video's sampling before the whole video goes to Pillow
+
+
+def check_decode(decode, key: str = "decode") -> str:
+    """the `decode` switch of extract / extract_dataset / FeatureBank.from_frames / AnomalyCLIPDataModule"""
+    if decode not in DECODERS:
+        raise ValueError(f"{key}={decode!r}: the frame decoder is 'pil' (Pillow on the host) or 'gpu' (baseline JPEG, reconstructed "
+                         f"on the device)")
+    return decode
+
+
+def make_reader(decode: str, frames_root: str, video: str, start=None, end=None, template: str = TEMPLATE, threads: int = 8):
+    """the frame reader of a video for `decode`: extract.FrameFolderReader ('pil') or JpegFolderReader ('gpu')"""
+    from . import extract as X
+    if check_decode(decode) == "gpu":
+        return JpegFolderReader(frames_root, video, start, end, template, threads)
+    return X.FrameFolderReader(frames_root, video, start, end, template, threads)
+
+
+def parse(data: bytes) -> Tuple[int, L.JpegInfo]:
+    """(return code, acx_jpeg_info) of a JPEG file's bytes"""
+    info = L.JpegInfo()
+    rc = L.lib().acx_jpeg_parse(data, len(data), C.byref(info))
+    return rc, info
+
+
+def geometry_of(info: L.JpegInfo) -> Tuple[int, int, int, int, int]:
+    """(H, W, ncomp, hs, vs): what frames must share to be reconstructed in one launch"""
+    return int(info.height), int(info.width), int(info.ncomp), int(info.comp_h[0]), int(info.comp_v[0])
+
+
+class JpegFolderReader(FrameFolderReader):
+    """`FrameFolderReader` whose `batches(n)` yields (slot, uint8 [k, H, W, 3]) DEVICE tensors: files are read and entropy-decoded
+    on the pool into two pinned coefficient buffers in rotation, one batch ahead of the consumer; the copy to the device and the
+    two reconstruction kernels run on a side stream, and the stream that is current when a batch is taken waits for them.  Every
+    batch is a fresh tensor (allocated on the side stream, `record_stream`ed for the consumer's), so the consumer holds no buffer of
+    the reader's: `copied` is kept for the interface only."""
+
+    def __init__(self, frames_root: str, video: str, start: Optional[int] = None, end: Optional[int] = None,
+                 template: str = TEMPLATE, threads: int = 8, device: Optional[torch.device] = None):
+        super().__init__(frames_root, video, start, end, template, threads, pinned=True)
+        self._init_state(device)
+
+    @classmethod
+    def like(cls, reader: FrameFolderReader, device=None) -> "JpegFolderReader":
+        """the frames of `reader` (a FrameFolderReader that has not been read yet), decoded this way"""
+        self = cls.__new__(cls)
+        self.dir, self.template, self.indices = reader.dir, reader.template, list(reader.indices)
+        self._init_reader(reader.threads, pinned=True)
+        self._init_state(device)
+        return self
+
+    def _init_state(self, device):
+        self.device = device
+        self.fallbacks = 0                 # frames Pillow decoded
+        self._geom = None                  # (H, W, ncomp, hs, vs) of the first of the video's leading frames the host decoder takes;
+                                           # False: it takes none of them
+        self._coef = [None, None]          # per slot: pinned int16 [n, coef_elems]
+        self._qt = [None, None]            # per slot: pinned int16 [n, ncomp, 64] (the bits of uint16)
+        self._rgb = [None, None]           # per slot: pinned uint8 [n, H, W, 3] for Pillow's frames, allocated at the first one
+        self._done = [None, None]          # per slot: the event after the copies that READ the pinned buffers
+        self._side = None
+        self._lock = threading.Lock()
+
+    # ------------------------------------------------------------------------------------------------------------ host
+    @property
+    def geometry(self):
+        """(H, W, ncomp, hs, vs) of the first of the video's GEOMETRY_PROBES leading frames that the host decoder takes and whose
+        size is the video's; None if there is none: every frame of such a video (PNG frames, all progressive) is Pillow's"""
+        if self._geom is None:
+            self._geom = False
+            size = self.frame_size
+            for i in range(min(len(self), GEOMETRY_PROBES)):
+                try:
+                    with open(self.path(i), "rb") as fh:
+                        rc, info = parse(fh.read())
+                except FileNotFoundError:
+                    continue
+                if rc == 0 and geometry_of(info)[:2] == size:
+                    self._geom = geometry_of(info)
+                    break
+        return self._geom or None
+
+    def _pillow(self, i: int, j: int, slot: int, n: int):
+        """frame i of the folder as Pillow decodes it, into place j of the slot's RGB buffer"""
+        H, W = self.frame_size
+        with self._lock:
+            if self._rgb[slot] is None or self._rgb[slot].shape[0] < n:
+                self._rgb[slot] = torch.empty(n, H, W, 3, dtype=torch.uint8).pin_memory()
+            self.fallbacks += 1
+        FrameFolderReader._decode(self, i, self._rgb[slot][j].numpy())
+
+    def _entropy(self, i: int, j: int, slot: int, n: int, coef: np.ndarray, qt: np.ndarray) -> bool:
+        """frame i into coef[j], qt[j]; False: Pillow decoded it instead"""
+        geom = self.geometry
+        if geom is not None:
+            with open(self.path(i), "rb") as fh:
+                data = fh.read()
+            rc, info = parse(data)
+            if rc == 0 and geometry_of(info) == geom:
+                row = coef[j]
+                row.fill(0)
+                rc = L.lib().acx_jpeg_entropy_decode(data, len(data), C.byref(info), row.ctypes.data, row.size)
+                if rc == 0:
+                    for c in range(geom[2]):
+                        qt[j, c] = np.ctypeslib.as_array(info.qtab[int(info.comp_tq[c])])
+                    return True
+        self._pillow(i, j, slot, n)
+        return False
+
+    def _fill(self, i0: int, i1: int, slot: int):
+        n = i1 - i0
+        if self._done[slot] is not None:              # the copies that read this slot's buffers two batches ago must be over
+            self._done[slot].synchronize()
+            self._done[slot] = None
+        geom = self.geometry
+        coef = qt = None
+        if geom is not None:
+            elems = ops.jpeg_coef_elems(*geom)
+            if self._coef[slot] is None or self._coef[slot].shape[0] < n:
+                self._coef[slot] = torch.empty(n, elems, dtype=torch.int16).pin_memory()
+                self._qt[slot] = torch.zeros(n, geom[2], 64, dtype=torch.int16).pin_memory()
+            coef, qt = self._coef[slot][:n].numpy(), self._qt[slot][:n].numpy().view(np.uint16)
+        ok = list(self.pool().map(lambda j: self._entropy(i0 + j, j, slot, n, coef, qt), range(n)))
+        return n, ok
+
+    def decode_batch(self, i0: int, i1: int, slot: int):
+        """the host stage of one batch, on its own (measurements): frames i0 ... i1 - 1 entropy-decoded into the slot's pinned
+        buffers -> (coef int16 [n, coef_elems], qtabs int16 [n, ncomp, 64], per frame: False where Pillow decoded it)"""
+        n, ok = self._fill(i0, i1, slot)
+        if self._coef[slot] is None:
+            return None, None, ok
+        return self._coef[slot][:n], self._qt[slot][:n], ok
+
+    # ------------------------------------------------------------------------------------------------------------ device
+    def _launch(self, slot: int, n: int, ok) -> torch.Tensor:
+        """the batch in the slot's pinned buffers -> uint8 [n, H, W, 3] on the device, ready for the current stream"""
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
+        H, W = self.frame_size
+        cur = torch.cuda.current_stream(dev)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=dev)
+        with torch.cuda.device(dev), torch.cuda.stream(self._side):
+            out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+            if any(ok):
+                coef = self._coef[slot][:n].to(dev, non_blocking=True)
+                qt = self._qt[slot][:n].to(dev, non_blocking=True)
+                ops.jpeg_reconstruct(coef, qt, *self.geometry, out=out)
+            for j in range(n):
+                if not ok[j]:                         # (after the kernels, which wrote this frame from whatever its row held)
+                    out[j].copy_(self._rgb[slot][j], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self._side)
+        self._done[slot] = ev
+        cur.wait_event(ev)
+        out.record_stream(cur)
+        return out
+
+    def batches(self, n: int) -> Iterator[Tuple[int, torch.Tensor]]:
+        """(slot, uint8 [k, H, W, 3] on the device) for consecutive groups of n frames; batch k + 1 is being entropy-decoded while
+        k is reconstructed and consumed"""
+        if not torch.cuda.is_available():
+            raise L.AcxError("JpegFolderReader reconstructs its frames on the GPU (no CPU fallback); decode='pil' reads them on the host")
+        T = len(self)
+        spans = [(i, min(T, i + n)) for i in range(0, T, n)]
+        with ThreadPoolExecutor(max_workers=1) as driver:
+            try:
+                fut = driver.submit(self._fill, *spans[0], 0)
+                for k in range(len(spans)):
+                    cnt, ok = fut.result()
+                    fut = driver.submit(self._fill, *spans[k + 1], (k + 1) & 1) if k + 1 < len(spans) else None
+                    yield k & 1, self._launch(k & 1, cnt, ok)
+            finally:
+                self.close()
+                for ev in self._done:                 # the pinned buffers go with the reader: not before their last copy
+                    if ev is not None:
+                        ev.synchronize()

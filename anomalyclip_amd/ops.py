@@ -1452,3 +1452,29 @@ def attnpool_tokens(x: torch.Tensor, pos: torch.Tensor, F: int, HW: int) -> torc
     h = _h(x)
     L.check(L.lib().acx_attnpool_tokens(h, x.data_ptr(), pos.data_ptr(), out.data_ptr(), F, HW, E, _stream()), h)
     return out
+
+
+# ---- baseline JPEG frames: the device half of the decoder (include/acx.h acx_jpeg_*; the host half: anomalyclip_amd/jpeg.py)
+def jpeg_coef_elems(H: int, W: int, ncomp: int, hs: int, vs: int) -> int:
+    """coefficients of one frame: every component's blocks, padded to whole MCUs (acx_jpeg_info.coef_elems)"""
+    mx, my = -(-W // (8 * hs)), -(-H // (8 * vs))
+    return (mx * hs * my * vs + (2 * mx * my if ncomp == 3 else 0)) * 64
+
+
+def jpeg_reconstruct(coef: torch.Tensor, qtabs: torch.Tensor, H: int, W: int, ncomp: int, hs: int, vs: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """coef int16 [F, coef_elems] (natural order, not dequantised, as acx_jpeg_entropy_decode writes them), qtabs [F, ncomp, 64]
+    (16-bit, each frame's table of each component, natural order) -> uint8 [F, H, W, 3], bit for bit Pillow's
+    `Image.open(...).convert("RGB")`.  ncomp 1 or 3; (hs, vs) the luma sampling factors."""
+    F = coef.shape[0]
+    n = jpeg_coef_elems(H, W, ncomp, hs, vs)
+    assert coef.dtype == torch.int16 and coef.shape == (F, n) and coef.is_contiguous()
+    assert qtabs.dtype in (torch.int16, torch.uint16) and qtabs.shape == (F, ncomp, 64) and qtabs.is_contiguous()
+    h = _h(coef)
+    if out is None:
+        out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=coef.device)
+    assert out.dtype == torch.uint8 and out.shape == (F, H, W, 3) and out.is_contiguous() and out.device == coef.device
+    planes = torch.empty(F, n, dtype=torch.uint8, device=coef.device)
+    L.check(L.lib().acx_jpeg_reconstruct(h, coef.data_ptr(), qtabs.data_ptr(), H, W, ncomp, hs, vs, F, planes.data_ptr(),
+                                         out.data_ptr(), _stream()), h)
+    return out

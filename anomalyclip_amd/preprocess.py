@@ -5,7 +5,7 @@ Reference: `get_augmentations` (src/utils/augmentations.py:21-34) = GroupScale(2
 Pillow's two-pass 8-bit resampler (horizontal then vertical, 22-bit fixed-point coefficients, 8-bit intermediate).
 The coefficient tables are computed here on the host in double precision exactly as Pillow's `precompute_coeffs` /
 `normalize_coeffs_8bpc` do (published algorithm of libImaging/Resample.c); the device kernels apply them.
-JPEG decoding stays on the host (out of scope)."""
+JPEG decoding is Pillow's on the host by default; anomalyclip_amd/jpeg.py moves all of it but the Huffman decoding to the device."""
 from __future__ import annotations
 
 import ctypes as C

@@ -892,6 +892,51 @@ int acx_tile_videos(acx_ctx* ctx, const float* bank, const int64_t* row_off, con
                     const int64_t* out_off, const int32_t* rows, const int32_t* blk, float* out, int32_t V, int64_t total_rows,
                     int32_t N, int32_t L, int32_t stride, int32_t ncrops, int32_t D, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG frames (the reference decodes with Pillow: video_dataset.py:204 `Image.open(...).convert("RGB")`): Huffman decoding
+ * on the host, everything after it on the device, bit for bit Pillow's RGB (libjpeg-turbo's defaults: the integer "islow" IDCT,
+ * "fancy" upsampling, the table-exact colour conversion).
+ *
+ * The supported set: 8-bit samples, SOF0 / SOF1, ONE interleaved scan with Ss = 0, Se = 63, Ah = Al = 0; one component, or three
+ * read as YCbCr with luma sampling 1x1, 2x1 or 2x2 and both chroma components 1x1.  Everything else a decoder may meet
+ * (progressive, arithmetic coding, 12 bits, four components, an Adobe segment with transform 0 or 2, other sampling factors,
+ * several scans, DNL, a downsampled chroma plane of one or two samples per row -- W <= 4: libjpeg replicates those instead of
+ * filtering them) is ACX_E_UNSUPPORTED; a malformed file is ACX_E_BADARG.  The two
+ * host functions take untrusted bytes, keep no state and allocate nothing: they may be called from many threads at once. */
+typedef struct acx_jpeg_info {
+  int32_t width, height, ncomp;
+  int32_t hmax, vmax;                      /* the largest sampling factors (the luma's) */
+  int32_t mcus_x, mcus_y;
+  int32_t restart_interval;                /* MCUs between restart markers, 0: none */
+  int32_t comp_h[4], comp_v[4];            /* sampling factors (a single component counts as 1 x 1) */
+  int32_t comp_tq[4], comp_td[4], comp_ta[4]; /* quantisation / DC / AC table of each component */
+  int32_t comp_width[4], comp_height[4];   /* real samples: ceil(width * h / hmax), ceil(height * v / vmax) */
+  int32_t blocks_wide[4], blocks_high[4];  /* MCUs * sampling factor: padded to whole MCUs */
+  int64_t coef_offset[4];                  /* first coefficient of each component, in elements */
+  int64_t coef_elems;                      /* coefficients of the frame */
+  int64_t scan_offset;                     /* offset of the entropy-coded data in the file */
+  uint16_t qtab[4][64];                    /* quantisation tables in NATURAL (row-major) order */
+  uint8_t qtab_present[4];
+  uint8_t huff_present[2][4];              /* [0: DC, 1: AC][table] */
+  uint8_t huff_bits[2][4][17];             /* codes of each length 1 .. 16 */
+  uint8_t huff_vals[2][4][256];
+} acx_jpeg_info;
+
+/* walks the markers up to the scan (SOI, APPn / COM skipped, DQT with 8- or 16-bit entries, DHT, SOF0 / SOF1, DRI, SOS) */
+int acx_jpeg_parse(const uint8_t* data, size_t n, acx_jpeg_info* info);
+/* every block's 64 coefficients in natural order, NOT dequantised, into the ZEROED buffer coef[coef_elems]: component after
+ * component, each [blocks_high][blocks_wide][64].  FF 00 stuffing; a restart marker re-aligns to a byte and resets the DC
+ * predictors.  A stream that ends early, a code no table holds, a run past the block's end: ACX_E_BADARG. */
+int acx_jpeg_entropy_decode(const uint8_t* data, size_t n, const acx_jpeg_info* info, int16_t* coef, size_t coef_elems);
+
+/* F frames of ONE geometry -> rgb uint8 [F,H,W,3] (the input of acx_preprocess_crops / acx_preprocess_frames).  coef: int16
+ * [F][coef_elems] as acx_jpeg_entropy_decode writes them; qtabs: uint16 [F][ncomp][64], each frame's table of each COMPONENT in
+ * natural order; ncomp 1 or 3, (hs, vs) the luma sampling factors (1,1), (2,1) or (2,2), W >= 5 where hs = 2.  planes: uint8 [F][coef_elems] scratch (the
+ * component planes, padded to whole blocks).  coef, qtabs and rgb 16-byte aligned, planes 8-byte aligned; F * H * W below 2^31.
+ * Two launches: dequantisation + inverse DCT into the planes, then upsampling + colour conversion + packing. */
+int acx_jpeg_reconstruct(acx_ctx* ctx, const int16_t* coef, const uint16_t* qtabs, int32_t H, int32_t W, int32_t ncomp, int32_t hs,
+                         int32_t vs, int32_t F, uint8_t* planes, uint8_t* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
