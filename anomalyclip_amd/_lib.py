@@ -17,7 +17,7 @@ ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
 OPT_RING_MIN_TILES, OPT_SK_MAX_M, OPT_TN_P256_MIN_ROWS, OPT_X6_CUS, OPT_X6_TAIL_SPLIT = 1, 2, 3, 4, 5
-OPT_X6_STRIP_TAIL, OPT_X6_MIN_TILES, OPT_LN_RIDER, OPT_ATTN_F32IN = 6, 7, 8, 9
+OPT_X6_STRIP_TAIL, OPT_X6_MIN_TILES, OPT_LN_RIDER, OPT_ATTN_F32IN, OPT_CLS_FOLD = 6, 7, 8, 9, 10
 ACX_F64, ACX_I64 = 16, 17                              # element types of the collectives only (acx_allreduce / acx_allgather)
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 COMM_ID_BYTES = 128
@@ -144,6 +144,9 @@ _SIGS = {
     "acx_attention_p3f": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3_panel": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_cls_fold_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "acx_attention_cls_fold": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                         c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "acx_vit_patches": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "acx_vit_embed": (C.c_int, [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_void_p]),
     "acx_resnet_stem_im2col": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

@@ -10,6 +10,10 @@
 #define ACX_ATTN_F32IN_DEFAULT 1   // ACX_OPT_ATTN_F32IN as acx_create sets it (A/B builds of the other default: -DACX_ATTN_F32IN_DEFAULT=0)
 #endif
 
+#ifndef ACX_CLS_FOLD_DEFAULT
+#define ACX_CLS_FOLD_DEFAULT 1     // ACX_OPT_CLS_FOLD as acx_create sets it
+#endif
+
 thread_local char acx_tls_err[512] = {0};
 
 extern "C" int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch,
@@ -48,6 +52,7 @@ extern "C" int acx_create(acx_ctx** out, int device) {
   c->opt_x6_strip = 1;
   c->opt_ln_rider = 1;
   c->opt_attn_f32in = ACX_ATTN_F32IN_DEFAULT;
+  c->opt_cls_fold = ACX_CLS_FOLD_DEFAULT;
   c->comm = nullptr; c->comm_rank = 0; c->comm_world = 0;
   c->opt_x6_min_tiles = 18;
   c->err[0] = 0;
@@ -135,6 +140,9 @@ extern "C" int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value) {
       return ACX_OK;
     case ACX_OPT_ATTN_F32IN:
       ctx->opt_attn_f32in = value != 0;
+      return ACX_OK;
+    case ACX_OPT_CLS_FOLD:
+      ctx->opt_cls_fold = value != 0;
       return ACX_OK;
     case ACX_OPT_X6_MIN_TILES:
       if (value < 1) return acx_fail(ctx, ACX_E_BADARG, "acx_set_option: x6_min_tiles must be >= 1%s");
@@ -288,6 +296,8 @@ int linear(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const fl
 // cls_ws != nullptr: the LAST layer is evaluated only where its output is consumed (token 0 of every sequence,
 // clip/model.py:285): K and V for all tokens, everything else for `batch` rows.  The final residual stream of
 // the CLS tokens is left COMPACT in cls_ws[0 .. batch*W) instead of x.
+// ACX_OPT_CLS_FOLD (every precision but bf16): not even K and V -- ln_1 and Q for the CLS rows, then acx_attention_cls_fold reads the
+// residual stream itself (u | z scratch: the f32 q | k | v buffer, free in that layer).
 int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int heads, int layers, int causal, int prec,
                        const acx_block_weights* blk, const TfWs& ws, hipStream_t s, float* cls_ws = nullptr) {
   const int64_t rows = (int64_t)batch * L;
@@ -302,6 +312,11 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
   // pruned last layer included) is handed to the product (acx_gemm_ln: the idle workgroups of its last round of tiles run part of it)
   const bool ln_ride = pdt3 == ACX_BF16X3P;
   bool ln1_done = false;                         // this layer's ln_1 planes were written behind the previous layer's c_proj
+  // The fold's u | z scratch (2 heads W floats per frame) lives in ws.qkv (3 L W floats per frame): a geometry with 2 heads > 3 L
+  // tokens (fewer than 11 tokens at 16 heads; no CLIP backbone) keeps the K | V path below, whatever the option says.
+  const size_t fold_ws_bytes = (size_t)rows * 3 * W * 4;                         // ws.qkv
+  const bool cls_fold = cls_ws && prec != ACX_PREC_BF16 && ctx && ctx->opt_cls_fold && L <= 1024 &&
+                        acx_attention_cls_fold_workspace_bytes(batch, heads) <= fold_ws_bytes;
   for (int l = 0; l < layers; ++l) {
     const acx_block_weights& b = blk[l];
     if (cls_ws && l == layers - 1) {
@@ -310,25 +325,34 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
       float* x1 = attc + (size_t)batch * W;      // [batch, W]
       char* hc = (char*)(x1 + (size_t)batch * W);          // [batch, W]   (f32 or bf16)
       char* mc = hc + (size_t)batch * W * 4;               // [batch, 4W]  (f32 or bf16)
-      const bool kv_x6 = x6mode && x6_takes(ctx, ws, rows, 2 * W, W, W);
-      // K | V for every token: rows [W, 3W) of in_proj
-      if (kv_x6) {
-        // LayerNorm writes the product's three planes itself (all rows) and the f32 rows of the CLS tokens (Q below reads only those)
-        if (!b.in_proj_w_bf16) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
-        if (!ln1_done && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-        if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-        if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
-                            (float*)ws.qkv + W, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
+      if (cls_fold) {
+        // ln_1 and Q for the CLS rows (hc and mc are free until ln_2 / c_fc), then the folded attention over the rows of x
+        float* qc = (float*)mc;                  // [batch, W]
+        if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, hc, W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+        if ((rc = linear(ctx, prec, hc, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, qc, ACX_F32, W, batch, W, W, b.in_proj_b, ACX_ACT_NONE,
+                         nullptr, s))) return rc;
+        if ((rc = acx_attention_cls_fold(ctx, x, b.ln1_w, b.ln1_b, 1e-5f, b.in_proj_w, b.in_proj_b, qc, W, attc, W, batch, L, W, heads,
+                                         ws.qkv, fold_ws_bytes, s))) return rc;
       } else {
-      if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-      if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w + (size_t)W * W,
-                       b.in_proj_w_bf16 ? (const char*)b.in_proj_w_bf16 + (size_t)W * W * 2 : nullptr, W,
-                       (float*)ws.qkv + W, ACX_F32, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
+        // K | V for every token: rows [W, 3W) of in_proj
+        if (x6mode && x6_takes(ctx, ws, rows, 2 * W, W, W)) {
+          // LayerNorm writes the product's three planes itself (all rows) and the f32 rows of the CLS tokens (Q below reads only those)
+          if (!b.in_proj_w_bf16) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
+          if (!ln1_done && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+          if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+          if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
+                              (float*)ws.qkv + W, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
+        } else {
+          if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
+          if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w + (size_t)W * W,
+                           b.in_proj_w_bf16 ? (const char*)b.in_proj_w_bf16 + (size_t)W * W * 2 : nullptr, W,
+                           (float*)ws.qkv + W, ACX_F32, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
+        }
+        // Q for the CLS rows only (A rows strided by one sequence)
+        if ((rc = linear(ctx, prec, ws.h, hdt, L * W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, ACX_F32, L * 3 * W, batch, W, W,
+                         b.in_proj_b, ACX_ACT_NONE, nullptr, s))) return rc;
+        if ((rc = acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, attc, W, batch, L, heads, s))) return rc;
       }
-      // Q for the CLS rows only (A rows strided by one sequence)
-      if ((rc = linear(ctx, prec, ws.h, hdt, L * W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, ACX_F32, L * 3 * W, batch, W, W,
-                       b.in_proj_b, ACX_ACT_NONE, nullptr, s))) return rc;
-      if ((rc = acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, attc, W, batch, L, heads, s))) return rc;
       if ((rc = linear(ctx, prec, attc, ACX_F32, W, b.out_proj_w, b.out_proj_w_bf16, W, x1, ACX_F32, W, batch, W, W,
                        b.out_proj_b, ACX_ACT_NONE, x, s, L * W))) return rc;
       if ((rc = acx_layernorm(ctx, x1, W, b.ln2_w, b.ln2_b, hc, W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
@@ -407,8 +431,8 @@ int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int head
     if (x6_proj) {
       if (!x6_fc && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, (int64_t)rows * 4 * W * 2, rows, 4 * W, s))) return rc;
       // the next layer's ln_1 where it writes the planes of ws.hp: a whole layer with its in-projection on the plane kernel, or the
-      // pruned last layer's K | V product
-      const bool next_planes = l + 1 < layers && ((cls_ws && l + 1 == layers - 1) ? x6_takes(ctx, ws, rows, 2 * W, W, W) && blk[l + 1].in_proj_w_bf16 != nullptr
+      // pruned last layer's K | V product (none under ACX_OPT_CLS_FOLD: that layer reads x itself)
+      const bool next_planes = l + 1 < layers && ((cls_ws && l + 1 == layers - 1) ? !cls_fold && x6_takes(ctx, ws, rows, 2 * W, W, W) && blk[l + 1].in_proj_w_bf16 != nullptr
                                                                                   : x6_qkv);
       ln1_done = ln_ride && next_planes;
       const acx_ln_job ln1 = {ln1_done ? blk[l + 1].ln1_w : nullptr, ln1_done ? blk[l + 1].ln1_b : nullptr, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};

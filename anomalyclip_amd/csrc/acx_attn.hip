@@ -1431,3 +1431,244 @@ extern "C" int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, 
   ACX_CHECK_LAUNCH(ctx, "acx_attention_cls");
   return ACX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// CLS-row attention of the pruned last ViT layer WITHOUT the K | V product (acx_attention_cls_fold).  With one query per
+// (frame, head) the projections fold into the query and the output:
+//   y_j = ln_1(x_j) = n_j * g + c,  n_j = (x_j - mean_j) rstd_j
+//   s_j = q_h . k_{j,h} / 8 = u_h . n_j + const,   u_h = g * W_{k,h}^T q_h / 8   (q_h . b_k and W_{k,h}^T q_h . c do not depend on j:
+//                                                                                  they cancel in the softmax)
+//   o_h = sum_j p_j v_{j,h} = W_{v,h} z_h + b_{v,h},  z_h = g * (sum_j p_j n_j) + c                         (sum_j p_j = 1)
+// Three launches: u for all frames (the K rows of in_proj read once per 16 frames), one workgroup per frame for scores, softmax
+// and z, then o for all frames (the V rows read once per 8 frames).  Every sum runs in a fixed order over one frame's data only: a
+// frame's result does not depend on the batch or on the frame's place in it.
+namespace {
+
+constexpr int CF_UF = 16;   // frames per workgroup of cls_fold_u_kernel
+constexpr int CF_OF = 8;    // frames per workgroup of cls_fold_o_kernel
+
+// u [batch, H, W]: grid (H, ceil(batch / CF_UF)); a thread owns columns c = tid + 256 i and sums the head's 64 rows of W_k in order
+__global__ __launch_bounds__(256) void cls_fold_u_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ wk,
+                                                         const float* __restrict__ lnw, float* __restrict__ u, int batch, int W) {
+  __shared__ __attribute__((aligned(16))) float qs[64][CF_UF];
+  const int h = blockIdx.x, H = gridDim.x, f0 = blockIdx.y * CF_UF;
+  for (int i = threadIdx.x; i < 64 * CF_UF; i += 256) {
+    const int f = i >> 6, d = i & 63;
+    const int fb = f0 + f < batch ? f0 + f : batch - 1;                          // (past the batch: a copy of its last frame, never stored)
+    qs[d][f] = q[(int64_t)fb * ldq + h * 64 + d];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < W; c += 256) {
+    float acc[CF_UF];
+#pragma unroll
+    for (int f = 0; f < CF_UF; ++f) acc[f] = 0.f;
+    const float* wp = wk + (int64_t)h * 64 * W + c;
+#pragma unroll 4
+    for (int d = 0; d < 64; ++d) {
+      const float w = wp[(int64_t)d * W];
+#pragma unroll
+      for (int f4 = 0; f4 < CF_UF / 4; ++f4) {
+        const float4 qv = *reinterpret_cast<const float4*>(&qs[d][4 * f4]);
+        acc[4 * f4] += qv.x * w; acc[4 * f4 + 1] += qv.y * w; acc[4 * f4 + 2] += qv.z * w; acc[4 * f4 + 3] += qv.w * w;
+      }
+    }
+    const float g = lnw[c] * 0.125f;
+#pragma unroll
+    for (int f = 0; f < CF_UF; ++f)
+      if (f0 + f < batch) u[((int64_t)(f0 + f) * H + h) * W + c] = acc[f] * g;
+  }
+}
+
+// One workgroup (4 waves) per frame.  Dynamic LDS: u [H][W] | scores, then softmax weights times rstd [L][HP] | (mean, rstd) [L].
+//   pass 1: a wave normalises R rows in registers (layernorm_kernel's row layout and sums) and writes their H scores
+//   softmax over L per head (one wave per head)
+//   pass 2: a thread owns columns c = tid + 256 k for all heads and sums the rows in order (re-read: L2 / MALL)
+template <int VPL>
+__global__ __launch_bounds__(256) void cls_fold_kernel(const float* __restrict__ x, const float* __restrict__ u,
+                                                       const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                       float* __restrict__ z, int L, float eps) {
+  constexpr int W = 64 * VPL, H = VPL, HP = (H + 3) & ~3, R = 4, CP = (VPL + 3) / 4;
+  constexpr float invD = 1.f / W;
+  extern __shared__ __attribute__((aligned(16))) float cf_smem[];
+  float* us = cf_smem;
+  float* sc = us + H * W;
+  float2* st = reinterpret_cast<float2*>(sc + (size_t)L * HP);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const float* xb = x + (int64_t)blockIdx.x * L * W;
+  const float* ub = u + (int64_t)blockIdx.x * H * W;
+  for (int i = 4 * tid; i < H * W; i += 1024) *reinterpret_cast<float4*>(us + i) = *reinterpret_cast<const float4*>(ub + i);
+  __syncthreads();
+
+  for (int j0 = wave * R; j0 < L; j0 += 4 * R) {
+    float v[R][VPL], rs[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) load_row<VPL>(xb + (int64_t)(j0 + r < L ? j0 + r : L - 1) * W, lane, v[r]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) s += v[r][i];
+      const float mean = wave_sum(s) * invD;
+      float qq = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        v[r][i] -= mean;
+        qq += v[r][i] * v[r][i];
+      }
+      rs[r] = 1.f / sqrtf(wave_sum(qq) * invD + eps);
+      if (lane == 0 && j0 + r < L) st[j0 + r] = make_float2(mean, rs[r]);
+    }
+#pragma unroll 1
+    for (int h = 0; h < H; ++h) {
+      float uu[VPL];
+      load_row<VPL>(us + h * W, lane, uu);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) d += v[r][i] * uu[i];
+        d = wave_sum(d) * rs[r];
+        if (lane == 0 && j0 + r < L) sc[(j0 + r) * HP + h] = d;
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int h = wave; h < H; h += 4) {
+    float m = -INFINITY;
+    for (int j = lane; j < L; j += 64) m = fmaxf(m, sc[j * HP + h]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int j = lane; j < L; j += 64) {
+      const float e = expf(sc[j * HP + h] - m);
+      sc[j * HP + h] = e;
+      s += e;
+    }
+    const float inv = 1.f / wave_sum(s);
+    for (int j = lane; j < L; j += 64) sc[j * HP + h] *= inv * st[j].y;
+  }
+  __syncthreads();
+
+  float acc[CP][H];
+#pragma unroll
+  for (int k = 0; k < CP; ++k)
+#pragma unroll
+    for (int h = 0; h < H; ++h) acc[k][h] = 0.f;
+#define CF_ROWS(NJ)                                                                                 \
+  {                                                                                                 \
+    float xv[NJ][CP];                                                                               \
+    _Pragma("unroll") for (int t = 0; t < NJ; ++t)                                                  \
+      _Pragma("unroll") for (int k = 0; k < CP; ++k)                                                \
+        xv[t][k] = tid + 256 * k < W ? xb[(int64_t)(j + t) * W + tid + 256 * k] : 0.f;              \
+    _Pragma("unroll") for (int t = 0; t < NJ; ++t) {                                                \
+      const float mean = st[j + t].x;                                                               \
+      float a[HP];                                                                                  \
+      _Pragma("unroll") for (int h4 = 0; h4 < HP / 4; ++h4) {                                       \
+        const float4 a4 = *reinterpret_cast<const float4*>(sc + (j + t) * HP + 4 * h4);             \
+        a[4 * h4] = a4.x; a[4 * h4 + 1] = a4.y; a[4 * h4 + 2] = a4.z; a[4 * h4 + 3] = a4.w;         \
+      }                                                                                             \
+      _Pragma("unroll") for (int k = 0; k < CP; ++k) {                                              \
+        const float d = xv[t][k] - mean;                                                            \
+        _Pragma("unroll") for (int h = 0; h < H; ++h) acc[k][h] += a[h] * d;                        \
+      }                                                                                             \
+    }                                                                                               \
+  }
+  int j = 0;
+  for (; j + 4 <= L; j += 4) CF_ROWS(4)
+  for (; j < L; ++j) CF_ROWS(1)
+#undef CF_ROWS
+  float* zb = z + (int64_t)blockIdx.x * H * W;
+#pragma unroll
+  for (int k = 0; k < CP; ++k) {
+    const int c = tid + 256 * k;
+    if (c < W) {
+      const float g = lnw[c], b0 = lnb[c];
+#pragma unroll
+      for (int h = 0; h < H; ++h) zb[h * W + c] = acc[k][h] * g + b0;
+    }
+  }
+}
+
+// out [batch, 64 H]: grid (H, ceil(batch / CF_OF)); a wave owns 16 of the head's 64 output elements, its lanes stride the columns
+__global__ __launch_bounds__(256) void cls_fold_o_kernel(const float* __restrict__ z, const float* __restrict__ wv,
+                                                         const float* __restrict__ bv, float* __restrict__ out, int64_t ldo,
+                                                         int batch, int W) {
+  __shared__ __attribute__((aligned(16))) float zs[CF_OF * 1024];
+  const int h = blockIdx.x, H = gridDim.x, f0 = blockIdx.y * CF_OF;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int f = 0; f < CF_OF; ++f) {
+    const int fb = f0 + f < batch ? f0 + f : batch - 1;
+    const float* zp = z + ((int64_t)fb * H + h) * W;
+    for (int c = threadIdx.x; c < W; c += 256) zs[f * W + c] = zp[c];
+  }
+  __syncthreads();
+  for (int e = wave; e < 64; e += 4) {
+    const float* wr = wv + (int64_t)(h * 64 + e) * W;
+    float acc[CF_OF];
+#pragma unroll
+    for (int f = 0; f < CF_OF; ++f) acc[f] = 0.f;
+    for (int c = lane; c < W; c += 64) {
+      const float w = wr[c];
+#pragma unroll
+      for (int f = 0; f < CF_OF; ++f) acc[f] += w * zs[f * W + c];
+    }
+    const float b0 = bv[h * 64 + e];
+#pragma unroll
+    for (int f = 0; f < CF_OF; ++f) {
+      const float o = wave_sum(acc[f]) + b0;
+      if (lane == f && f0 + f < batch) out[(int64_t)(f0 + f) * ldo + h * 64 + e] = o;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t acx_attention_cls_fold_workspace_bytes(int32_t batch, int32_t heads) {
+  if (batch <= 0 || heads <= 0) return 0;
+  return (size_t)2 * batch * heads * heads * 64 * sizeof(float);                 // u | z, [batch, heads, 64 heads] each
+}
+
+extern "C" int acx_attention_cls_fold(acx_ctx* ctx, const float* x, const float* ln_w, const float* ln_b, float eps,
+                                      const float* in_proj_w, const float* in_proj_b, const float* q, int64_t ldq, float* out,
+                                      int64_t ldo, int32_t batch, int32_t L, int32_t W, int32_t heads, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!x || !ln_w || !ln_b || !in_proj_w || !in_proj_b || !q || !out || !workspace)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls_fold: null pointer%s");
+  if (batch <= 0) return ACX_OK;
+  if (L <= 0 || L > 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls_fold: need 0 < L <= 1024%s");
+  if (heads <= 0 || W != heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls_fold: head dim must be 64%s");
+  switch (heads) {   // the LayerNorm widths
+    case 1: case 2: case 4: case 8: case 10: case 12: case 16: break;
+    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls_fold: width %s%ld not in {64,128,256,512,640,768,1024}", "", (long)W);
+  }
+  if (((uintptr_t)x & 15) || ((uintptr_t)workspace & 15)) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls_fold: x and workspace must be 16-byte aligned%s");
+  if (workspace_bytes < acx_attention_cls_fold_workspace_bytes(batch, heads))
+    return acx_fail(ctx, ACX_E_WORKSPACE, "acx_attention_cls_fold: workspace too small%s");
+  hipStream_t s = (hipStream_t)stream;
+  const int dev_slot = (ctx ? ctx->device : 0) & 63;
+  float* u = (float*)workspace;
+  float* z = u + (size_t)batch * heads * W;
+  const float* wk = in_proj_w + (size_t)W * W;
+  const float* wv = in_proj_w + (size_t)2 * W * W;
+  const int HP = (heads + 3) & ~3;
+  const size_t lds = ((size_t)heads * W + (size_t)L * HP) * 4 + (size_t)L * 8;   // <= 136 KB (W = 1024, L = 1024)
+  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+#define ACX_CLS_FOLD(V) \
+  acx_launch_lds<cls_fold_kernel<V>>(dev_slot, dim3((unsigned)batch), dim3(256), lds, s, x, (const float*)u, ln_w, ln_b, z, (int)L, eps)
+  hipLaunchKernelGGL(cls_fold_u_kernel, dim3((unsigned)heads, (unsigned)((batch + CF_UF - 1) / CF_UF)), dim3(256), 0, s, q, ldq, wk,
+                     ln_w, u, (int)batch, (int)W);
+  switch (heads) {
+    case 1: ACX_CLS_FOLD(1); break;
+    case 2: ACX_CLS_FOLD(2); break;
+    case 4: ACX_CLS_FOLD(4); break;
+    case 8: ACX_CLS_FOLD(8); break;
+    case 10: ACX_CLS_FOLD(10); break;
+    case 12: ACX_CLS_FOLD(12); break;
+    default: ACX_CLS_FOLD(16); break;
+  }
+#undef ACX_CLS_FOLD
+  hipLaunchKernelGGL(cls_fold_o_kernel, dim3((unsigned)heads, (unsigned)((batch + CF_OF - 1) / CF_OF)), dim3(256), 0, s, (const float*)z,
+                     wv, in_proj_b + 2 * W, out, ldo, (int)batch, (int)W);
+  ACX_CHECK_LAUNCH(ctx, "acx_attention_cls_fold");
+  return ACX_OK;
+}

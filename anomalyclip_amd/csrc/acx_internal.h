@@ -63,6 +63,7 @@ struct acx_ctx {
   int opt_x6_min_tiles;     // ACX_OPT_X6_MIN_TILES
   int opt_x6_strip;         // ACX_OPT_X6_STRIP_TAIL (1: by the cost model, 0: off, 2 / 3: always 128- / 64-column strips)
   int opt_attn_f32in;       // ACX_OPT_ATTN_F32IN (1: the plane attention of the six-product drivers reads f32 q | k | v)
+  int opt_cls_fold;         // ACX_OPT_CLS_FOLD (1: the pruned last ViT layer runs acx_attention_cls_fold instead of its K | V product)
   long long opt_ln_rider;   // ACX_OPT_LN_RIDER (1: rows by the cost model, 0: off, > 1: ride up to this many rows -- measurements)
   char err[512];
   bool prof_on;

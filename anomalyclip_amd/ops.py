@@ -120,6 +120,19 @@ def set_attn_f32in(device_index: int, on: bool) -> None:
     L.check(L.lib().acx_set_option(h, L.OPT_ATTN_F32IN, int(bool(on))), h)
 
 
+# ACX_OPT_CLS_FOLD as acx_create sets it in the default build (tests restore it).  The default is a compile-time constant of the library
+# (ACX_CLS_FOLD_DEFAULT) and the ABI has no getter: a library built with the other default (the A/B arm of tools/ab_cls_fold.py) is for
+# bench.py only -- the test suite is meant for the default build.
+CLS_FOLD_DEFAULT = True
+
+
+def set_cls_fold(device_index: int, on: bool) -> None:
+    """ACX_OPT_CLS_FOLD: 1 (default) = the pruned last ViT layer (every precision but bf16) runs without its K | V product
+    (acx_attention_cls_fold); 0 = ln_1 of all rows, the K | V product, acx_attention_cls.  Round-off apart, not bit-identical."""
+    h = L.ctx(device_index)
+    L.check(L.lib().acx_set_option(h, L.OPT_CLS_FOLD, int(bool(on))), h)
+
+
 def ln_rider_plan(M: int, N: int, K: int, ncu: int, ksplit: int = 1, rate: float = 0.0):
     """(rows that ride, rows the full rounds complete) of acx_gemm_ln for an eligible product on ncu workgroups -- host arithmetic,
     no device; rate: LayerNorm rows of 768 columns per us and rider workgroup (<= 0: the library's constant)"""
@@ -474,6 +487,23 @@ def attention(qkv: torch.Tensor, batch: int, L_: int, heads: int, causal: bool) 
     h = _h(qkv)
     L.check(L.lib().acx_attention(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), batch, L_, heads,
                                   int(causal), _stream()), h)
+    return out
+
+
+def attention_cls_fold(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, in_proj_w: torch.Tensor, in_proj_b: torch.Tensor,
+                       q: torch.Tensor, batch: int, L_: int, heads: int, eps: float = 1e-5) -> torch.Tensor:
+    """acx_attention_cls_fold: the CLS-row attention of a layer from its residual stream x [batch * L, W], ln_1, the f32
+    in-projection and the CLS queries q [batch, W] -- no K | V product.  Returns [batch, W]."""
+    W = heads * 64
+    assert x.is_contiguous() and x.shape == (batch * L_, W) and q.shape == (batch, W) and q.stride(1) == 1
+    assert in_proj_w.is_contiguous() and in_proj_w.shape == (3 * W, W) and in_proj_b.numel() == 3 * W
+    out = torch.empty(batch, W, dtype=torch.float32, device=x.device)
+    nbytes = L.lib().acx_attention_cls_fold_workspace_bytes(batch, heads)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    h = _h(x)
+    L.check(L.lib().acx_attention_cls_fold(h, x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), float(eps), in_proj_w.data_ptr(),
+                                           in_proj_b.data_ptr(), q.data_ptr(), q.stride(0), out.data_ptr(), out.stride(0), batch, L_,
+                                           W, heads, ws.data_ptr(), nbytes, _stream()), h)
     return out
 
 

@@ -116,8 +116,13 @@ const char* acx_last_error(acx_ctx* ctx);
  *                           in-projection writes f32 rows and the attention splits q | k | v into planes itself (acx_attention_p3f:
  *                           no plane round trip through memory); 0 = the in-projection's epilogue writes the three planes and
  *                           acx_attention_p3 reads them.  Results are BIT-IDENTICAL for both values. */
+/*   ACX_OPT_CLS_FOLD       acx_vit_encode, every precision but ACX_PREC_BF16: 1 (default) = the pruned last layer runs without its
+ *                           K | V product -- ln_1 and Q for the CLS rows, then acx_attention_cls_fold on the residual stream; 0 = ln_1
+ *                           of all rows, the K | V product and acx_attention_cls.  Both are f32-level evaluations of the same layer:
+ *                           the features differ by round-off (not bit-identical).  A geometry with 2 heads > 3 tokens per frame (the
+ *                           fold's scratch would not fit in the layer's free q | k | v buffer) runs the K | V path for both values. */
 enum { ACX_OPT_RING_MIN_TILES = 1, ACX_OPT_SK_MAX_M = 2, ACX_OPT_TN_P256_MIN_ROWS = 3, ACX_OPT_X6_CUS = 4, ACX_OPT_X6_TAIL_SPLIT = 5,
-       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8, ACX_OPT_ATTN_F32IN = 9 };
+       ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8, ACX_OPT_ATTN_F32IN = 9, ACX_OPT_CLS_FOLD = 10 };
 int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value);
 
 /* ------------------------------------------------------------------------------------------
@@ -269,6 +274,18 @@ int acx_attention_bf16(acx_ctx* ctx, const void* qkv, int64_t ldqkv, void* out, 
  * Used for the LAST ViT layer, whose output is consumed at the CLS token only (clip/model.py:285). */
 int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo,
                       int32_t batch, int32_t L, int32_t heads, void* stream);
+/* acx_attention_cls_fold: what ln_1 -> K | V rows of in_proj -> acx_attention_cls computes, WITHOUT the K | V product.  With one
+ * query per (frame, head) the key projection folds into the query (u_h = W_{k,h}^T q_h: q_h . b_k is the same for every key and
+ * cancels in the softmax) and the value projection into the output (o_h = W_{v,h} sum_j p_j ln_1(x_j) + b_{v,h}, since sum_j p_j = 1).
+ *   x [batch * L, W] f32 (dense, 16-byte aligned): the residual stream;  ln_w, ln_b [W], eps: ln_1;  in_proj_w [3 W, W], in_proj_b
+ *   [3 W]: the f32 in-projection (its K and V rows are read);  q [batch, ldq]: the CLS rows' queries (W_q ln_1(x_0) + b_q, unscaled);
+ *   out [batch, ldo] f32.  W = 64 heads, W in {64, 128, 256, 512, 640, 768, 1024} (the LayerNorm widths), 0 < L <= 1024.
+ * workspace: acx_attention_cls_fold_workspace_bytes(batch, heads) bytes, 16-byte aligned.  A frame's output is a function of that
+ * frame's rows alone: bit-identical for every batch size and position. */
+size_t acx_attention_cls_fold_workspace_bytes(int32_t batch, int32_t heads);
+int acx_attention_cls_fold(acx_ctx* ctx, const float* x, const float* ln_w, const float* ln_b, float eps, const float* in_proj_w,
+                           const float* in_proj_b, const float* q, int64_t ldq, float* out, int64_t ldo, int32_t batch, int32_t L,
+                           int32_t W, int32_t heads, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * acx_vit_patches: im2col of PxP/P patches, P even and R % P == 0 (P = 14 / 16 / 32: clip/model.py:246-252,267-269).
