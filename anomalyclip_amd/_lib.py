@@ -124,6 +124,11 @@ class JpegInfo(C.Structure):            # == struct acx_jpeg_info
                 ("huff_bits", ((C.c_uint8 * 17) * 4) * 2), ("huff_vals", ((C.c_uint8 * 256) * 4) * 2)]
 
 
+class JpegHuff(C.Structure):            # == struct acx_jpeg_huff
+    _fields_ = [("present", (C.c_uint8 * 4) * 2), ("bits", ((C.c_uint8 * 17) * 4) * 2), ("vals", ((C.c_uint8 * 256) * 4) * 2),
+                ("td", C.c_uint8 * 4), ("ta", C.c_uint8 * 4)]
+
+
 _SIGS = {
     "acx_version": (C.c_int, []),
     "acx_create": (C.c_int, [C.POINTER(c_void_p), C.c_int]),
@@ -283,6 +288,9 @@ _SIGS = {
     "acx_tile_videos": (C.c_int, [c_void_p] * 9 + [c_int32, c_int64] + [c_int32] * 5 + [c_void_p]),
     "acx_jpeg_parse": (C.c_int, [c_void_p, c_size_t, c_void_p]),
     "acx_jpeg_entropy_decode": (C.c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    "acx_jpeg_scan_pack": (C.c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "acx_jpeg_entropy_decode_dev": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int32] * 6 +
+                                    [c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "acx_jpeg_reconstruct": (C.c_int, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
 }
 

@@ -3,6 +3,7 @@
 // YCbCr -> RGB conversion, bit for bit what Pillow (libjpeg-turbo with its defaults) writes.
 #include "acx_internal.h"
 #include "acx_jpeg_host.h"
+#include "acx_jpeg_sync.h"
 
 extern "C" int acx_jpeg_parse(const uint8_t* data, size_t n, acx_jpeg_info* info) { return acx_jpeg::parse(data, n, info); }
 
@@ -215,5 +216,134 @@ extern "C" int acx_jpeg_reconstruct(acx_ctx* ctx, const int16_t* coef, const uin
   hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((pixels + 4095) / 4096)), dim3(256), 0, (hipStream_t)stream,
                      (const uint8_t*)planes, rgb, g, (uint32_t)pixels);
   ACX_CHECK_LAUNCH(ctx, "acx_jpeg_reconstruct (colour)");
+  return ACX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- entropy decoding
+extern "C" int acx_jpeg_scan_pack(const uint8_t* data, size_t n, const acx_jpeg_info* info, uint8_t* dst, size_t cap,
+                                  int64_t* payload_bytes, acx_jpeg_huff* huff) {
+  return acx_jpeg::scan_pack(data, n, info, dst, cap, payload_bytes, huff);
+}
+
+static_assert(sizeof(acx_jpeg_huff) == acx_jsync::kHuffBytes, "acx_jpeg_huff is the record acx_jpeg_sync.h reads");
+static_assert(ACX_JPEG_MAX_SUBSEQ == acx_jsync::kThreads, "one thread per subsequence");
+static_assert(sizeof(acx_jsync::Shared) <= 48 * 1024, "the tables and the records stay well inside the 64 KB a launch gets");
+
+// One workgroup per frame, thread t owns subsequence t: the phases of acx_jpeg_sync.h with the workgroup's barriers between them.
+// A frame whose scan, offset or tables are not usable is a status, decided by values every thread of the workgroup sees alike.
+__global__ __launch_bounds__(1024) void jpeg_entropy_kernel(const uint8_t* __restrict__ scans, int64_t scans_bytes,
+                                                            const int64_t* __restrict__ scan_off, const int32_t* __restrict__ scan_bits,
+                                                            const uint8_t* __restrict__ huff, acx_jsync::Geo g, uint32_t sub_arg,
+                                                            int16_t* __restrict__ coef, int32_t* __restrict__ status) {
+  using namespace acx_jsync;
+  __shared__ Shared S;
+  __shared__ int s_bad;
+  const uint32_t t = threadIdx.x, f = blockIdx.x;
+  const int64_t off = scan_off[f], bits64 = scan_bits[f];
+  const uint8_t* hf = huff + (size_t)f * kHuffBytes;
+  const uint32_t sub = sub_arg ? sub_arg : min_sub_bits(bits64 < 0 ? 0 : (uint64_t)bits64);
+  bool ok = bits64 >= 0 && off >= 0 && (off & 31) == 0 && (uint64_t)sub * kThreads >= (uint64_t)bits64 &&
+            (off >> 3) + (bits64 + 31) / 32 * 4 <= scans_bytes;
+  uint32_t used = 0, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+#pragma unroll
+  for (uint32_t c = 0; c < 3; ++c)
+    if (c < g.ncomp) {
+      td[c] = hf[kHuffTd + c];
+      ta[c] = hf[kHuffTa + c];
+      ok = ok && td[c] < 4 && ta[c] < 4;
+      td[c] &= 3;
+      ta[c] &= 3;
+      ok = ok && hf[kHuffPresent + td[c]] && hf[kHuffPresent + 4 + ta[c]];
+      used |= (1u << td[c]) | (16u << ta[c]);
+    }
+  if (!ok) {
+    if (t == 0) status[f] = kBad;
+    return;
+  }
+  const uint32_t bits = (uint32_t)bits64;
+  const uint32_t nsub = bits == 0 ? 1u : (bits + sub - 1) / sub;           // <= kThreads
+
+  for (uint32_t i = t; i < 8 * 512; i += kThreads) S.tab[i >> 9].look[i & 511] = 0;
+  for (uint32_t i = t; i < 8 * 256; i += kThreads) S.tab[i >> 8].vals[i & 255] = hf[kHuffVals + i];
+  if (t == 0) {
+    s_bad = 0;
+    S.err = S.done = 0;
+  }
+  if (t < 3) {
+    S.sel[0][t] = t == 0 ? td[0] : t == 1 ? td[1] : td[2];
+    S.sel[1][t] = 4 + (t == 0 ? ta[0] : t == 1 ? ta[1] : ta[2]);
+  }
+  S.pos[t] = 0;
+  S.bk[t] = 0;
+  S.nblk[t] = 0;
+  S.dc[0][t] = S.dc[1][t] = S.dc[2][t] = 0;
+  __syncthreads();
+  if (t < 8 && ((used >> t) & 1))
+    if (derive_codes(hf + kHuffBits + t * 17, &S.tab[t]) != 0) s_bad = 1;
+  __syncthreads();
+  if (s_bad) {
+    if (t == 0) status[f] = kBad;
+    return;
+  }
+
+  Scan sc;
+  scan_init(&sc, (const uint32_t*)(scans + (off >> 3)), bits);
+  State st = {0, 0, 0};
+  bool active = t < nsub;
+  if (active) phase_speculate(S, g, sc, t, sub, st);
+  __syncthreads();
+  for (uint32_t r = 1; r < nsub; ++r) {                                    // nsub is the workgroup's: every thread takes the barrier
+    const bool changed = phase_sync_round(S, g, sc, t, r, sub, nsub, st, active);
+    if (!__syncthreads_or(changed ? 1 : 0)) break;
+  }
+  __syncthreads();
+  for (uint32_t d = 1; d < kThreads; d <<= 1) {                            // inclusive scans of the counts over the records
+    uint32_t a = 0;
+    uint32_t b0 = 0, b1 = 0, b2 = 0;
+    if (t >= d) {
+      a = S.nblk[t - d];
+      b0 = S.dc[0][t - d];
+      b1 = S.dc[1][t - d];
+      b2 = S.dc[2][t - d];
+    }
+    __syncthreads();
+    S.nblk[t] += a;
+    S.dc[0][t] += b0;
+    S.dc[1][t] += b1;
+    S.dc[2][t] += b2;
+    __syncthreads();
+  }
+  if (t < nsub) phase_write(S, g, sc, t, sub, coef + (size_t)f * g.coef_elems);
+  __syncthreads();
+  if (t == 0) status[f] = (S.err || !S.done) ? kBad : 0;
+}
+
+extern "C" int acx_jpeg_entropy_decode_dev(acx_ctx* ctx, const uint8_t* scans, int64_t scans_bytes, const int64_t* scan_off,
+                                           const int32_t* scan_bits, const acx_jpeg_huff* huff, int32_t H, int32_t W, int32_t ncomp,
+                                           int32_t hs, int32_t vs, int32_t F, int64_t max_scan_bits, int32_t sub_bits, int16_t* coef,
+                                           int32_t* status, void* stream) {
+  AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
+  if (F == 0) return ACX_OK;
+  if (!scans || !scan_off || !scan_bits || !huff || !coef || !status)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: null pointer%s");
+  if (F < 0 || H < 1 || W < 1 || H > 65535 || W > 65535)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: F >= 0 and 1 <= H, W <= 65535%s");
+  if (!((ncomp == 1 && hs == 1 && vs == 1) || (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2))))))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_jpeg_entropy_decode_dev: 1 component, or 3 with luma sampling 1x1, 2x1 or 2x2%s");
+  acx_jsync::Geo g;
+  if (!acx_jsync::make_geo(H, W, ncomp, hs, vs, &g))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: a frame's coefficients must stay below 2^31%s");
+  if (scans_bytes < 0 || max_scan_bits < 0 || max_scan_bits > 0x7FFF0000ll || (max_scan_bits + 7) / 8 > scans_bytes)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: 0 <= max_scan_bits <= 8 * scans_bytes, below 2^31%s");
+  if (sub_bits < 0 || (sub_bits & 31))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: sub_bits is a multiple of 32, or 0 for each frame's smallest%s");
+  if (sub_bits && (int64_t)sub_bits * acx_jsync::kThreads < max_scan_bits)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: %ssub_bits %ld does not cover the longest scan with 1024 subsequences: needs %ld",
+                    "", (long)sub_bits, (long)acx_jsync::min_sub_bits((uint64_t)max_scan_bits));
+  if (((uintptr_t)scans & 3) || ((uintptr_t)scan_off & 7) || ((uintptr_t)scan_bits & 3) || ((uintptr_t)coef & 1) || ((uintptr_t)status & 3))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_jpeg_entropy_decode_dev: scans 4-byte aligned, the arrays aligned to their element%s");
+  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)F), dim3(acx_jsync::kThreads), 0, (hipStream_t)stream, scans, scans_bytes, scan_off,
+                     scan_bits, (const uint8_t*)huff, g, (uint32_t)sub_bits, coef, status);
+  ACX_CHECK_LAUNCH(ctx, "acx_jpeg_entropy_decode_dev");
   return ACX_OK;
 }

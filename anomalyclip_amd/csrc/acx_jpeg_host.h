@@ -383,6 +383,55 @@ static inline int entropy_decode(const uint8_t* d, size_t n, const acx_jpeg_info
   return ACX_OK;
 }
 
+// The scan un-stuffed for the device decoder: the bytes BitReader::fill would feed, in its order -- FF 00 is FF, an FF before an FF
+// is a fill byte, anything else after an FF (or an FF that ends the file) ends the stream -- then zero bytes up to a multiple of
+// ACX_JPEG_SCAN_ALIGN.  A restart interval is left to entropy_decode.
+static inline int scan_pack(const uint8_t* d, size_t n, const acx_jpeg_info* o, uint8_t* dst, size_t cap, int64_t* payload,
+                            acx_jpeg_huff* huff) {
+  if (!d || !o || !dst || !payload) return ACX_E_BADARG;
+  *payload = 0;
+  if (o->ncomp != 1 && o->ncomp != 3) return ACX_E_BADARG;
+  if (o->scan_offset < 2 || (uint64_t)o->scan_offset > n) return ACX_E_BADARG;
+  for (int c = 0; c < o->ncomp; ++c) {
+    if ((unsigned)o->comp_td[c] > 3 || (unsigned)o->comp_ta[c] > 3) return ACX_E_BADARG;
+    if (!o->huff_present[0][o->comp_td[c]] || !o->huff_present[1][o->comp_ta[c]]) return ACX_E_BADARG;
+  }
+  if (o->restart_interval != 0) return ACX_E_UNSUPPORTED;
+  size_t p = (size_t)o->scan_offset, len = 0;
+  while (p < n) {
+    const uint8_t b = d[p];
+    if (b != 0xFF) {
+      ++p;
+    } else if (p + 1 >= n) {
+      break;                                             // a lone FF at the end
+    } else if (d[p + 1] == 0) {
+      p += 2;
+    } else if (d[p + 1] == 0xFF) {
+      ++p;                                               // a fill byte
+      continue;
+    } else {
+      break;                                             // a marker
+    }
+    if (len >= cap) return ACX_E_BADARG;
+    dst[len++] = b;
+  }
+  const size_t padded = (len + ACX_JPEG_SCAN_ALIGN - 1) / ACX_JPEG_SCAN_ALIGN * ACX_JPEG_SCAN_ALIGN;
+  if (padded > cap) return ACX_E_BADARG;
+  memset(dst + len, 0, padded - len);
+  *payload = (int64_t)len;
+  if (huff) {
+    memset(huff, 0, sizeof(*huff));
+    memcpy(huff->present, o->huff_present, sizeof(huff->present));
+    memcpy(huff->bits, o->huff_bits, sizeof(huff->bits));
+    memcpy(huff->vals, o->huff_vals, sizeof(huff->vals));
+    for (int c = 0; c < o->ncomp; ++c) {
+      huff->td[c] = (uint8_t)o->comp_td[c];
+      huff->ta[c] = (uint8_t)o->comp_ta[c];
+    }
+  }
+  return ACX_OK;
+}
+
 }  // namespace acx_jpeg
 
 #endif  // ACX_JPEG_HOST_H_

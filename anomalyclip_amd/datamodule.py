@@ -9,7 +9,7 @@ stream the files through `FeatureStream` and add the per-frame labels of the tem
 CLIP image encoder into such banks (`FeatureBank.from_frames`; the reference's frame transform is deterministic, so its per-step
 encoding gives the same rows) and every loader draws from a bank: `ResidentTrainLoader` as above, `ResidentTestLoader` for the
 test-mode tiles.  No feature file is written.  `decode="gpu"` (a keyword beside `encoder=`, not one of the reference's keys) has the
-frames' baseline JPEG files reconstructed on the device (anomalyclip_amd/jpeg.py) instead of decoded by Pillow: the same banks."""
+frames' baseline JPEG files reconstructed on the device (anomalyclip_amd/jpeg.py) instead of decoded by Pillow, `decode="gpu_entropy"` their Huffman decoding too: the same banks."""
 from __future__ import annotations
 
 import os

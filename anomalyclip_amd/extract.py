@@ -258,14 +258,15 @@ def encode_video(encoder, frames, ncrops: int = 1, scale_size: Optional[int] = N
 def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False,
                   decode: str = "pil") -> dict:
     """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
-    decode="gpu": the frames of a FrameFolderReader are read by a jpeg.JpegFolderReader over the same files instead.
+    decode="gpu" / "gpu_entropy": the frames of a FrameFolderReader are read by a jpeg.JpegFolderReader /
+    jpeg.JpegEntropyFolderReader over the same files instead.
     Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
     from . import jpeg
     jpeg.check_decode(decode)
     encoder = _encoder_of(encoder)
     reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
-    if decode == "gpu" and isinstance(reader, FrameFolderReader) and not isinstance(reader, jpeg.JpegFolderReader):
-        reader = jpeg.JpegFolderReader.like(reader)
+    if decode != "pil" and isinstance(reader, FrameFolderReader) and not isinstance(reader, jpeg.JpegFolderReader):
+        reader = jpeg.READERS[decode].like(reader)
     T, D = len(reader), int(encoder.output_dim)
     shape = (T * ncrops, D)
     check_eval_mode(encoder)
@@ -295,8 +296,8 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
                     scale_size: Optional[int] = None, overwrite: bool = False, template: str = TEMPLATE,
                     decode_threads: int = 8, log=None, decode: str = "pil") -> dict:
     """Every video of the annotation file (rows `path start end label...`; without one: every frame folder under frames_root)
-    -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  decode: "pil" (Pillow on the host) or "gpu" (baseline
-    JPEG reconstructed on the device; every other file through Pillow).  Returns {written, skipped, frames, rows}."""
+    -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  decode: "pil" (Pillow on the host), "gpu" (baseline
+    JPEG reconstructed on the device; every other file through Pillow) or "gpu_entropy" (its Huffman decoding on the device too).  Returns {written, skipped, frames, rows}."""
     from . import jpeg
     jpeg.check_decode(decode)
     encoder = _encoder_of(net_or_encoder)
@@ -364,8 +365,9 @@ def _parser():
     p.add_argument("--scale-size", type=int, default=None, help="shorter side before cropping (default: crop, or crop * 8 // 7)")
     p.add_argument("--precision", default="auto", choices=sorted(PRECISIONS))
     p.add_argument("--overwrite", action="store_true")
-    p.add_argument("--decode", default="pil", choices=("pil", "gpu"),
-                   help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device")
+    p.add_argument("--decode", default="pil", choices=("pil", "gpu", "gpu_entropy"),
+                   help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device; "
+                        "gpu_entropy: the Huffman decoding on the device too")
     return p
 
 

@@ -68,7 +68,7 @@ class FeatureBank:
         extract.encode_video -- the launches `extract_video` makes, so the rows are the rows of the file it would write -- and each
         block of rows is copied from the encoder's output straight into its bank slice.  `paths` are the frame folders,
         `file_frames == num_frames`.  The size follows from the rows and `encoder.output_dim` and is checked before any frame is
-        opened.  decode: "pil" or "gpu", as extract.extract_dataset takes it."""
+        opened.  decode: "pil", "gpu" or "gpu_entropy", as extract.extract_dataset takes it."""
         from . import extract as X
         from . import jpeg
         jpeg.check_decode(decode)

@@ -1508,3 +1508,60 @@ def jpeg_reconstruct(coef: torch.Tensor, qtabs: torch.Tensor, H: int, W: int, nc
     L.check(L.lib().acx_jpeg_reconstruct(h, coef.data_ptr(), qtabs.data_ptr(), H, W, ncomp, hs, vs, F, planes.data_ptr(),
                                          out.data_ptr(), _stream()), h)
     return out
+
+
+JPEG_MAX_SUBSEQ = 1024                 # == ACX_JPEG_MAX_SUBSEQ: subsequences (threads of the one workgroup) per frame
+JPEG_SCAN_ALIGN = 4                    # == ACX_JPEG_SCAN_ALIGN
+JPEG_HUFF_BYTES = C.sizeof(L.JpegHuff)
+
+
+def jpeg_min_sub_bits(scan_bytes: int) -> int:
+    """the smallest `sub_bits` (bits per subsequence, a multiple of 32) with which JPEG_MAX_SUBSEQ subsequences cover an un-stuffed
+    scan of `scan_bytes` bytes: what jpeg_entropy_decode takes for a frame at sub_bits = 0"""
+    per = -(-(int(scan_bytes) * 8) // JPEG_MAX_SUBSEQ)
+    return max(32, -(-per // 32) * 32)
+
+
+def jpeg_scan_pack(data: bytes, info: "L.JpegInfo", dst, huff=None) -> tuple:
+    """the entropy-coded segment of a parsed file un-stuffed into `dst` (a writable uint8 numpy array or host tensor), zero-padded
+    to JPEG_SCAN_ALIGN -> (return code, payload bytes); `huff` (uint8, JPEG_HUFF_BYTES) receives the frame's Huffman record.
+    ACX_E_UNSUPPORTED: a restart interval (the host decoder's file); ACX_E_BADARG: `dst` is too small."""
+    import numpy as np
+    d = dst.numpy() if isinstance(dst, torch.Tensor) else dst
+    assert d.dtype == np.uint8 and d.flags.c_contiguous and d.flags.writeable
+    hp = None
+    if huff is not None:
+        h = huff.numpy() if isinstance(huff, torch.Tensor) else huff
+        assert h.dtype == np.uint8 and h.flags.c_contiguous and h.size == JPEG_HUFF_BYTES
+        hp = h.ctypes.data
+    n = C.c_int64(0)
+    rc = L.lib().acx_jpeg_scan_pack(data, len(data), C.byref(info), d.ctypes.data, d.size, C.byref(n), hp)
+    return rc, int(n.value)
+
+
+def jpeg_entropy_decode(scans: torch.Tensor, scan_off: torch.Tensor, scan_bits: torch.Tensor, huff: torch.Tensor, H: int, W: int,
+                        ncomp: int, hs: int, vs: int, max_scan_bits: int, sub_bits: int = 0, coef: Optional[torch.Tensor] = None,
+                        status: Optional[torch.Tensor] = None):
+    """Huffman decoding of F frames of one geometry on the device, one launch.  scans uint8 [n] (the packed scans), scan_off int64
+    [F] / scan_bits int32 [F] (each frame's first bit in `scans`, a multiple of 32, and its number of bits), huff uint8
+    [F, JPEG_HUFF_BYTES]; max_scan_bits: the longest scan (the host packed them).  sub_bits: bits per subsequence, or 0 for each
+    frame's jpeg_min_sub_bits.  -> (coef int16 [F, coef_elems] as acx_jpeg_entropy_decode writes it, status int32 [F]: 0 exactly
+    where the host decoder returns 0).  A `coef` passed in must be zeroed."""
+    F = scan_off.shape[0]
+    n = jpeg_coef_elems(H, W, ncomp, hs, vs)
+    dev = scans.device
+    assert scans.dtype == torch.uint8 and scans.dim() == 1 and scans.is_contiguous()
+    assert scan_off.dtype == torch.int64 and scan_off.shape == (F,) and scan_off.is_contiguous() and scan_off.device == dev
+    assert scan_bits.dtype == torch.int32 and scan_bits.shape == (F,) and scan_bits.is_contiguous() and scan_bits.device == dev
+    assert huff.dtype == torch.uint8 and huff.shape == (F, JPEG_HUFF_BYTES) and huff.is_contiguous() and huff.device == dev
+    h = _h(scans)
+    if coef is None:
+        coef = torch.zeros(F, n, dtype=torch.int16, device=dev)
+    if status is None:
+        status = torch.empty(F, dtype=torch.int32, device=dev)
+    assert coef.dtype == torch.int16 and coef.shape == (F, n) and coef.is_contiguous() and coef.device == dev
+    assert status.dtype == torch.int32 and status.shape == (F,) and status.is_contiguous() and status.device == dev
+    L.check(L.lib().acx_jpeg_entropy_decode_dev(h, scans.data_ptr(), scans.numel(), scan_off.data_ptr(), scan_bits.data_ptr(),
+                                                huff.data_ptr(), H, W, ncomp, hs, vs, F, int(max_scan_bits), int(sub_bits),
+                                                coef.data_ptr(), status.data_ptr(), _stream()), h)
+    return coef, status

@@ -954,6 +954,37 @@ int acx_jpeg_entropy_decode(const uint8_t* data, size_t n, const acx_jpeg_info* 
 int acx_jpeg_reconstruct(acx_ctx* ctx, const int16_t* coef, const uint16_t* qtabs, int32_t H, int32_t W, int32_t ncomp, int32_t hs,
                          int32_t vs, int32_t F, uint8_t* planes, uint8_t* rgb, void* stream);
 
+/* ---- Huffman decoding on the device: decode="gpu_entropy".  Only the marker walk and the byte un-stuffing stay on the host. */
+#define ACX_JPEG_SCAN_ALIGN 4            /* a packed scan is read as 32-bit words: its start and its padded length are multiples */
+#define ACX_JPEG_MAX_SUBSEQ 1024         /* subsequences (threads of the one workgroup) per frame */
+/* a frame's Huffman tables as they travel to the device: the huff_* fields of acx_jpeg_info and each component's table indices */
+typedef struct acx_jpeg_huff {
+  uint8_t present[2][4];                   /* [0: DC, 1: AC][table] */
+  uint8_t bits[2][4][17];
+  uint8_t vals[2][4][256];
+  uint8_t td[4], ta[4];                    /* DC / AC table of each component */
+} acx_jpeg_huff;                           /* 2200 bytes */
+
+/* Copies the entropy-coded segment at info->scan_offset into dst[cap] with every FF 00 replaced by FF (and fill FFs dropped), up to
+ * the first marker or the end of the file; *payload_bytes is the number of bytes copied, and dst is zero-padded up to the next
+ * multiple of ACX_JPEG_SCAN_ALIGN.  huff, if not null, receives the tables.  The contract of acx_jpeg_parse: untrusted bytes,
+ * every read and write bounded, no state, no allocation.  A file with a restart interval is ACX_E_UNSUPPORTED (the host decoder
+ * takes it); a dst too small, or an info the host decoder would refuse, is ACX_E_BADARG. */
+int acx_jpeg_scan_pack(const uint8_t* data, size_t n, const acx_jpeg_info* info, uint8_t* dst, size_t cap, int64_t* payload_bytes,
+                       acx_jpeg_huff* huff);
+
+/* Huffman-decodes F frames of ONE geometry in one launch, one workgroup of ACX_JPEG_MAX_SUBSEQ threads per frame (the
+ * self-synchronising parallel decode: anomalyclip_amd/csrc/acx_jpeg_sync.h).  DEVICE pointers: scans[scans_bytes], the packed
+ * scans; scan_off[F] / scan_bits[F], each frame's first bit (a multiple of 32) and number of bits in it; huff[F]; coef int16
+ * [F][coef_elems], ZEROED; status int32 [F].  max_scan_bits: the longest scan of the batch, known to the host that packed it.
+ * sub_bits: bits per subsequence, a multiple of 32, or 0 for each frame's smallest (ceil(bits / 1024) rounded up to 32); an
+ * explicit value with which 1024 subsequences do not cover max_scan_bits is ACX_E_BADARG before any launch, the needed value in
+ * acx_last_error.  coef is written exactly as acx_jpeg_entropy_decode writes it for the frames it accepts; status[f] is 0 exactly
+ * for those, and ACX_E_BADARG for the others (whose coefficients are unspecified, inside their frame). */
+int acx_jpeg_entropy_decode_dev(acx_ctx* ctx, const uint8_t* scans, int64_t scans_bytes, const int64_t* scan_off, const int32_t* scan_bits,
+                                const acx_jpeg_huff* huff, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int32_t F,
+                                int64_t max_scan_bits, int32_t sub_bits, int16_t* coef, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
