@@ -44,7 +44,11 @@ class GemmDesc(C.Structure):
     ]
 
 
-class LnJob(C.Structure):      # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
+class GemmScratch(C.Structure):   # acx_gemm_scratch_t: what acx_gemm_scratch tells the caller to bring
+    _fields_ = [("workspace_bytes", c_size_t), ("counters", c_int32)]
+
+
+class LnJob(C.Structure):     # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
     _fields_ = [("w", c_void_p), ("b", c_void_p), ("y", c_void_p), ("y_dtype", c_int32), ("eps", c_float), ("mode", c_int32)]
 
 
@@ -135,7 +139,9 @@ _SIGS = {
     "acx_destroy": (None, [c_void_p]),
     "acx_last_error": (C.c_char_p, [c_void_p]),
     "acx_set_option": (C.c_int, [c_void_p, c_int32, c_int64]),
+    "acx_get_option": (C.c_int, [c_void_p, c_int32, C.POINTER(c_int64)]),
     "acx_gemm": (C.c_int, [c_void_p, C.POINTER(GemmDesc), c_void_p]),
+    "acx_gemm_scratch": (C.c_int, [c_void_p, C.POINTER(GemmDesc), c_int32, C.POINTER(GemmScratch)]),
     "acx_gemm_ln": (C.c_int, [c_void_p, C.POINTER(GemmDesc), C.POINTER(LnJob), c_void_p]),
     "acx_gemm_ln_plan": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, C.c_double, C.POINTER(c_int64)]),
     "acx_layernorm": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,

@@ -26,6 +26,11 @@ def _parallel():
 
 
 # ====================================================================================================== text path
+def _few_row_limit(t: torch.Tensor) -> int:
+    """ACX_OPT_SK_MAX_M of the tensor's device: acx_gemm runs products with at most this many rows on the few-row kernel"""
+    return ops.get_option(t.device.index if t.device.index is not None else torch.cuda.current_device(), L.OPT_SK_MAX_M)
+
+
 def _text_forward_rows(net, ctx_param, text_projection, lo: int, hi: int, tf_out=None):
     """Text features of classes [lo, hi) (coop.py:74-90, text_encoder.py:14-25): prompt assembly, the 12 frozen CLIP
     text layers, EOT gather, ln_final, @ text_projection.  Returns (features [hi-lo, E], state for the backward).
@@ -43,7 +48,7 @@ def _text_forward_rows(net, ctx_param, text_projection, lo: int, hi: int, tf_out
     saved = []
     # few rows (a data-parallel rank's block of classes: 77 rows per class): acx_gemm runs the few-row kernel and the
     # activation / its derivative ride in its prologue / epilogue instead of separate launches
-    few = C * Lc <= ops.SK_MAX_ROWS and (4 * W) % 256 == 0 and W % 256 == 0
+    few = C * Lc <= _few_row_limit(x) and (4 * W) % 256 == 0 and W % 256 == 0
     # ... and the two LayerNorms of a block ride in the A prologue of the GEMM that consumes them (K == 512: the whole row is
     # resident in the kernel's two stages; LN(x) is never materialised -- the backward recomputes it from x anyway)
     norm_fused = few and W == 512
@@ -102,7 +107,7 @@ def _text_backward_rows(net, text_projection, state, d_tf, d_ctx_out=None, d_P_o
     d_eot, _, _ = ops.layernorm_bwd(eot, te.ln_final.weight, d_eln, need_params=False)
     d_x = ops.scatter_rows(d_eot, rows_idx, C * Lc)
     wt = _frozen_transposes(te)
-    few = C * Lc <= ops.SK_MAX_ROWS and (4 * W) % 256 == 0 and W % 256 == 0
+    few = C * Lc <= _few_row_limit(d_x) and (4 * W) % 256 == 0 and W % 256 == 0
     for li in range(len(saved) - 1, -1, -1):
         blk = te.transformer.resblocks[li]
         x, qkv, x_mid, pre = saved[li]

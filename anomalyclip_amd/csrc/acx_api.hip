@@ -161,6 +161,24 @@ extern "C" int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value) {
   }
 }
 
+extern "C" int acx_get_option(acx_ctx* ctx, int32_t option, int64_t* value) {
+  if (!ctx || !value) return acx_fail(ctx, ACX_E_BADARG, "acx_get_option: no context or no result pointer%s");
+  switch (option) {
+    case ACX_OPT_RING_MIN_TILES: *value = ctx->opt_ring_min_tiles; return ACX_OK;
+    case ACX_OPT_SK_MAX_M: *value = ctx->opt_sk_max_m; return ACX_OK;
+    case ACX_OPT_TN_P256_MIN_ROWS: *value = ctx->opt_tn_p256_min_rows; return ACX_OK;
+    case ACX_OPT_X6_CUS: *value = ctx->opt_x6_cus; return ACX_OK;
+    case ACX_OPT_X6_TAIL_SPLIT: *value = ctx->opt_x6_tail; return ACX_OK;
+    case ACX_OPT_X6_STRIP_TAIL: *value = ctx->opt_x6_strip; return ACX_OK;
+    case ACX_OPT_X6_MIN_TILES: *value = ctx->opt_x6_min_tiles; return ACX_OK;
+    case ACX_OPT_LN_RIDER: *value = ctx->opt_ln_rider; return ACX_OK;
+    case ACX_OPT_ATTN_F32IN: *value = ctx->opt_attn_f32in; return ACX_OK;
+    case ACX_OPT_CLS_FOLD: *value = ctx->opt_cls_fold; return ACX_OK;
+    default:
+      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_get_option: unknown option %s%ld", "", (long)option);
+  }
+}
+
 extern "C" const char* acx_last_error(acx_ctx* ctx) { return ctx ? ctx->err : acx_tls_err; }
 
 namespace {

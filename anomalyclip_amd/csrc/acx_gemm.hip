@@ -56,10 +56,13 @@
 //   7. f32 branch-free / 3x3 convolutions -> gemm_f32_w8_kernel           route_w8
 //   8. bf16 ring / p8, bf16 DMA convolution, bf16 DMA, gemm_kernel        route_ring, route_dma_conv, route_dma, route_gemm_kernel
 //   9. the reduce launch of a K split                                     splitk_reduce (from the route that split)
+// acx_gemm_scratch (behind gemm_impl) tells a caller what workspace and counters to bring: each splitting route is followed by the
+// rule that sizes its scratch (x6_tail_scratch_bytes, sk_scratch_bytes, x6_split_scratch_bytes, generic_scratch_bytes).
 // acx_gemm_tn* (weight gradients) are dispatched at the bottom of this file.
 #include "acx_internal.h"
 #include "acx_ln_rows.h"     // LnRide, ln_ride_rows: the LayerNorm rider of gemm_x6_p4_kernel
 
+#include <algorithm>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -635,6 +638,10 @@ static int x6_choose_split(int tiles, int nks, int ncu, size_t image_bytes, size
   return best;
 }
 
+// Scratch of that split as acx_gemm_scratch sizes it: from K = X6_SPLIT_MIN_K (two pieces of six whole K-steps; the model itself
+// would split K = 352), at most X6_SPLIT_PIECES_MAX partial images (the caller's cap: the model tries up to 64 and takes what fits)
+constexpr int X6_SPLIT_MIN_K = 384, X6_SPLIT_PIECES_MAX = 16;
+
 // What acx_gemm refuses before it looks for a route (the routes refuse what only they can know)
 static int gemm_validate(acx_ctx* ctx, const acx_gemm_desc* d) {
   if (!d || !d->A || !d->W || !d->C) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: null pointer%s");
@@ -849,6 +856,16 @@ static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const a
 #ifndef ACX_X6TAIL_THRESH
 #define ACX_X6TAIL_THRESH 0.99
 #endif
+// tile rows the full rounds of tiles cover on ncu workgroups; CONV3X3 on a token grid of whole tiles: down to a grid boundary
+static int x6_tail_tm_main(const acx_gemm_desc* d, int ncu) {
+  const int tn = (d->N + 255) / 256, xt = ((d->M + 255) / 256) * tn;
+  int tm_main = (xt / ncu * ncu) / tn;
+  if (d->amap == ACX_AMAP_CONV3X3 && (d->gn * d->gl) % 256 == 0) {
+    const int grid_tiles = d->gn * d->gl / 256;
+    tm_main = tm_main / grid_tiles * grid_tiles;
+  }
+  return tm_main;
+}
 static int route_x6_tail_split(const GemmCall& c) {
   acx_ctx* ctx = c.ctx;
   const acx_gemm_desc* d = c.d;
@@ -857,11 +874,9 @@ static int route_x6_tail_split(const GemmCall& c) {
   const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256, xt = tm * tn, nks = d->K / 32;
   const int rounds = xt / ncu, rem = xt - rounds * ncu;
   if (rounds < 1 || rem == 0) return ROUTE_NEXT;
-  int tm_main = (rounds * ncu) / tn;
-  if (d->amap == ACX_AMAP_CONV3X3) {           // the tail must begin at a token-grid boundary (its taps never leave a grid)
-    const int grid_tiles = (d->gn * d->gl + 255) / 256;
-    tm_main = (d->gn * d->gl) % 256 == 0 ? tm_main / grid_tiles * grid_tiles : 0;
-  }
+  // the tail must begin at a token-grid boundary (its taps never leave a grid)
+  if (d->amap == ACX_AMAP_CONV3X3 && (d->gn * d->gl) % 256) return ROUTE_NEXT;
+  const int tm_main = x6_tail_tm_main(d, ncu);
   const int xtail = (tm - tm_main) * tn;
   const int64_t row0 = (int64_t)tm_main * 256, m_tail = d->M - row0;
   if (tm_main < 1 || xtail >= ncu || m_tail <= 0) return ROUTE_NEXT;
@@ -882,6 +897,21 @@ static int route_x6_tail_split(const GemmCall& c) {
   const int rc = gemm_impl(ctx, &dm, c.s, nullptr, nullptr);
   return rc ? rc : gemm_impl(ctx, &dt, c.s, nullptr, nullptr);
 }
+// Scratch of this route (acx_gemm_scratch): partial images of the tail's rows, X6_TAIL_PIECES_MIN to _MAX of them (the caller's
+// caps: x6_choose_split takes what fits), more when the tail has few tiles.
+// Looser than the route: pairs = 3, a tail of >= ncu tiles and a CONV3X3 grid of less than a tile get scratch the route leaves unused.
+constexpr int X6_TAIL_PIECES_MIN = 4, X6_TAIL_PIECES_MAX = 8;
+static size_t x6_tail_scratch_bytes(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  if (!(c.ctx && c.ctx->opt_x6_tail && x6_operands_ok(c) && d->K >= X6_SPLIT_MIN_K)) return 0;
+  const int ncu = c.ncu_x6, tn = (d->N + 255) / 256, xt = ((d->M + 255) / 256) * tn;
+  if (xt < ncu || xt % ncu == 0) return 0;
+  const int64_t m_tail = d->M - (int64_t)x6_tail_tm_main(d, ncu) * 256;
+  if (m_tail <= 0) return 0;
+  const int xtail = (int)((m_tail + 255) / 256) * tn;
+  const int pieces = std::min(X6_TAIL_PIECES_MAX, std::max(X6_TAIL_PIECES_MIN, 2 * ncu / xtail));
+  return (size_t)pieces * m_tail * d->N * sizeof(float);
+}
 
 // ---- route 2: few-row f32 problems (and every problem that asks for the few-row fusions): 32x32 tiles, K split over the waves
 template <int E, int AG, int AN = 0>
@@ -897,6 +927,21 @@ static void sk_launch_epi(const GemmCall& c, int epi, dim3 grid, const Args& g) 
     default: sk_launch<SK_EPI_GELUGRAD, AG>(c, grid, g); break;
   }
 }
+// The rows the few-row kernel takes for their own sake (not for a fusion).  Narrow outputs (N <= 512: out-proj, proj and the dX
+// chain of the text tower) stay ahead of the 64x64-tile kernel up to ~1300 rows -- 17-34 row tiles x 16 column tiles fill the chip
+// where 64x64 tiles leave half of it idle (profiles/r03_text_gemm.txt); wide outputs only up to the row limit
+// ... except long K at more than ~770 rows when the caller brought a split-K workspace: the 64x64 kernel with K split 2-4
+// ways is ahead there (1078 rows, N = 512: K = 2048 37.1 vs 43.5 us, K = 1536 30.0 vs 33.2 us; at 539 rows it is not)
+static bool sk_takes_rows(const GemmCall& c, bool has_workspace) {
+  const acx_gemm_desc* d = c.d;
+  const int sk_max_m = c.ctx ? c.ctx->opt_sk_max_m : ACX_SK_MAX_M;
+  const bool sk_narrow = sk_max_m > 0 && d->N <= 512 && d->M <= 4 * sk_max_m && !(has_workspace && d->M > 768 && d->K >= 1536);
+  return d->M <= sk_max_m || sk_narrow;
+}
+// long K on few tiles: pieces of two chunks (512 floats = resident in one DMA burst) across workgroups, at most SK_PIECE_BLOCKS
+// workgroups in all, one 32 x 32 f32 partial tile each
+constexpr int SK_PIECE_K = 2 * SK_CH, SK_PIECE_BLOCKS = 512;
+constexpr size_t SK_PIECE_TILE_B = 32 * 32 * sizeof(float);
 static int route_sk(const GemmCall& c, const Args& base) {
   acx_ctx* ctx = c.ctx;
   const acx_gemm_desc* d = c.d;
@@ -914,23 +959,15 @@ static int route_sk(const GemmCall& c, const Args& base) {
   if (a_norm && (d->K != 512 || !d->a_norm_b || d->a_act != ACX_ACT_NONE || d->residual || d->gelu_grad_of || d->act != ACX_ACT_NONE ||
                  (((uintptr_t)d->a_norm_w | (uintptr_t)d->a_norm_b) & 15)))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_norm needs K == 512, weight and bias, and no other fusion%s");
-  // narrow outputs (N <= 512: out-proj, proj and the dX chain of the text tower) stay ahead of the 64x64-tile kernel up to
-  // ~1300 rows -- 17-34 row tiles x 16 column tiles fill the chip where 64x64 tiles leave half of it idle
-  // (profiles/r03_text_gemm.txt); wide outputs only up to the row limit
-  const int sk_max_m = ctx ? ctx->opt_sk_max_m : ACX_SK_MAX_M;
-  // ... except long K at more than ~770 rows when the caller brought a split-K workspace: the 64x64 kernel with K split 2-4
-  // ways is ahead there (1078 rows, N = 512: K = 2048 37.1 vs 43.5 us, K = 1536 30.0 vs 33.2 us; at 539 rows it is not)
-  const bool sk_narrow = sk_max_m > 0 && d->N <= 512 && d->M <= 4 * sk_max_m && !(d->workspace && d->M > 768 && d->K >= 1536);
-  if (!(sk_ok && (sk_fusion || d->M <= sk_max_m || sk_narrow))) return ROUTE_NEXT;
+  if (!(sk_ok && (sk_fusion || sk_takes_rows(c, d->workspace != nullptr)))) return ROUTE_NEXT;
   Args g = base;
   dim3 kgrid((unsigned)(((d->M + 31) / 32) * ((d->N + 31) / 32)));
-  // long K on few tiles: pieces of two chunks (512 floats = resident in one DMA burst) across workgroups, when the caller
-  // brought the partial workspace and the arrival counters
+  // the piece split, when the caller brought the partial workspace and the arrival counters
   g.counters = (unsigned int*)d->counters;
-  if (d->workspace && d->counters && d->K >= 1024 && d->K % 512 == 0) {
-    const int pieces = d->K / 512;
-    if ((int)kgrid.x * pieces <= 512 && (int)kgrid.x <= d->n_counters &&
-        (size_t)pieces * kgrid.x * 4096 <= d->workspace_bytes && !((uintptr_t)d->workspace & 15)) {
+  if (d->workspace && d->counters && d->K >= 2 * SK_PIECE_K && d->K % SK_PIECE_K == 0) {
+    const int pieces = d->K / SK_PIECE_K;
+    if ((int)kgrid.x * pieces <= SK_PIECE_BLOCKS && (int)kgrid.x <= d->n_counters &&
+        (size_t)pieces * kgrid.x * SK_PIECE_TILE_B <= d->workspace_bytes && !((uintptr_t)d->workspace & 15)) {
       g.ksplit = pieces;
       g.kchunk = 2;
       g.partial = (float*)d->workspace;
@@ -943,6 +980,19 @@ static int route_sk(const GemmCall& c, const Args& base) {
   else sk_launch_epi<0>(c, epi, kgrid, g);
   ACX_CHECK_LAUNCH(ctx, "acx_gemm");
   return ACX_OK;
+}
+
+// Scratch of this route (acx_gemm_scratch).  few rows: what the route takes from a caller that brings a workspace, by the caller's
+// looser rule -- it looks at neither N % 4, alignment and c_dtype nor the fusions (which take the route at any row count).
+static bool sk_scratch_few_rows(const GemmCall& c) {
+  return c.fast && c.prec == ACX_PREC_F32 && c.d->K % SK_CH == 0 && sk_takes_rows(c, true);
+}
+// the piece split's partial tiles (with the arrival counters), where the split can happen
+static size_t sk_scratch_bytes(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  if (!(sk_scratch_few_rows(c) && d->K >= 2 * SK_PIECE_K && d->K % SK_PIECE_K == 0)) return 0;
+  const int64_t tiles32 = (int64_t)((d->M + 31) / 32) * ((d->N + 31) / 32), pieces = d->K / SK_PIECE_K;
+  return tiles32 * pieces <= SK_PIECE_BLOCKS ? (size_t)(pieces * tiles32) * SK_PIECE_TILE_B : 0;
 }
 
 // ---- route 3: pairs = 6 (f32-accurate product from three bf16 planes per operand) and pairs = 3: the one-wave-per-SIMD
@@ -1058,6 +1108,16 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   return ACX_OK;
 }
 
+// Scratch of this route's K split (acx_gemm_scratch): fewer tiles than workgroups -- two partial images per idle round the split
+// can fill, 2 to X6_SPLIT_PIECES_MAX.  Looser than the route: fp16 operand planes with plane outputs never split (X6PlanIn.may_split).
+static size_t x6_split_scratch_bytes(const GemmCall& c) {
+  const acx_gemm_desc* d = c.d;
+  const int ncu = c.ncu_x6, xt = ((d->M + 255) / 256) * ((d->N + 255) / 256);
+  if (!(x6_operands_ok(c) && d->K >= X6_SPLIT_MIN_K && xt < ncu)) return 0;
+  const int pieces = std::min(X6_SPLIT_PIECES_MAX, std::max(2, 2 * ncu / xt));
+  return (size_t)pieces * d->M * d->N * sizeof(float);
+}
+
 // ---- route 4: small branch-free f32 problems (text tower): 64x64 tiles, four blocks per CU
 template <int ACT, int RES>
 static void s64_launch(const GemmCall& c, dim3 grid, const Args& g) {
@@ -1100,6 +1160,7 @@ static bool w8_takes_conv(const GemmCall& c) {
   return ACX_DBG_SWITCH("W8", true) && d->amap == ACX_AMAP_CONV3X3 && !d->a_sub && !d->pos0 && d->K % 32 == 0 && d->cin % 32 == 0 &&
          c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16;
 }
+constexpr int GEN_SPLIT_MAX = 16, GEN_SPLIT_BLOCKS = 512;   // at most this many pieces; tiles x pieces up to this many workgroups
 static KSplit generic_ksplit(const GemmCall& c) {
   const acx_gemm_desc* d = c.d;
   const int ke = c.prec == ACX_PREC_F32 ? 32 : 64;
@@ -1110,9 +1171,27 @@ static KSplit generic_ksplit(const GemmCall& c) {
   int split = 1;
   // bf16 pieces keep >= 8 K-steps: at the XD text tower's 539 rows x K = 512 a 2-way split + its 5 us reduce launch is
   // slower than the unsplit launch (head step 1.64 -> 1.51 ms); 16 is worse again (1.59)
-  while (tiles * split * 2 <= 512 && nkt / (split * 2) >= (c.prec == ACX_PREC_BF16 ? 8 : 4) && split < 16) split *= 2;
+  while (tiles * split * 2 <= GEN_SPLIT_BLOCKS && nkt / (split * 2) >= (c.prec == ACX_PREC_BF16 ? 8 : 4) && split < GEN_SPLIT_MAX) split *= 2;
   if (split > 1 && (size_t)split * d->M * d->N * sizeof(float) <= d->workspace_bytes) return ksplit_even(nkt, split, d->workspace);
   return KSplit();
+}
+
+// Scratch of this split and of route_s64's (acx_gemm_scratch): the partial images of the most pieces generic_ksplit can take for
+// the tile count; *counters = the f32 convolutions' pieces meet inside route_w8's kernel.  The gate is the caller's own: up to 128
+// tiles from K = 256, up to 256 tiles (the convolutions of a data-parallel rank's 4096 rows: 256 tiles = ONE 8-wave block per CU;
+// two K halves put two blocks on every CU for the price of a 12 us reduce) only from K = 1024 -- generic_ksplit would split those
+// from K = 256.  Looser than the routes in what it hands scratch to: bf16 convolutions and LeakyReLU on identity rows never split,
+// and the counters go to f32 convolutions with a bf16 output, which w8_takes_conv declines.
+static size_t generic_scratch_bytes(const GemmCall& c, int32_t* counters) {
+  const acx_gemm_desc* d = c.d;
+  const int64_t tiles = (int64_t)((d->M + BM - 1) / BM) * ((d->N + BN - 1) / BN);
+  const bool plain_rows = (d->amap == ACX_AMAP_IDENTITY || d->amap == ACX_AMAP_CONV3X3) && !d->a_sub && !d->pos0;
+  const bool mapped_rows = d->a_sub || d->pos0 || d->amap == ACX_AMAP_TESTTILE || d->amap == ACX_AMAP_TILETABLE;
+  const bool all_f32 = c.prec == ACX_PREC_F32 && d->a_dtype == ACX_F32 && d->c_dtype == ACX_F32;
+  if (!(((tiles <= 128 && d->K >= 256) || (tiles <= 256 && d->K >= 1024)) && !sk_scratch_few_rows(c) && (plain_rows || (mapped_rows && all_f32))))
+    return 0;
+  *counters = d->amap == ACX_AMAP_CONV3X3 && c.prec == ACX_PREC_F32;
+  return (size_t)std::min<int64_t>(GEN_SPLIT_MAX, GEN_SPLIT_BLOCKS / tiles) * d->M * d->N * sizeof(float);
 }
 
 // ---- route 6: big f32 GEMMs without a residual and no K split: the persistent strip-stream kernel, one 1024-thread block per CU
@@ -1315,6 +1394,29 @@ static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const a
   if ((rc = route_dma_conv(c, g, grid, ks)) != ROUTE_NEXT) return rc;
   if ((rc = route_dma(c, g, grid, ks)) != ROUTE_NEXT) return rc;
   return route_gemm_kernel(c, g, grid, ks);
+}
+
+// The scratch a caller should hand to acx_gemm / acx_gemm_ln for this descriptor: each rule stands behind the route it serves.
+// Host arithmetic on the shape fields, the options and whether the optional operands are there; d->workspace / d->counters are not
+// read.  The answer decides more than a size: the routes choose their K split from workspace_bytes, and route_sk's row gate from
+// whether there is a workspace at all.
+extern "C" int acx_gemm_scratch(const acx_ctx* ctx, const acx_gemm_desc* d, int32_t allow_split, acx_gemm_scratch_t* out) {
+  if (!d || !out || d->M <= 0 || d->N <= 0 || d->K <= 0) return ACX_E_BADARG;
+  out->workspace_bytes = 0;
+  out->counters = 0;
+  if (!allow_split) return ACX_OK;
+  const GemmCall c = gemm_call(const_cast<acx_ctx*>(ctx), d, nullptr);    // (the facts only: nothing is launched, nothing fails)
+  if (d->pairs == 6 || d->pairs == 3) {
+    out->workspace_bytes = x6_split_scratch_bytes(c);
+    if (!out->workspace_bytes) out->workspace_bytes = x6_tail_scratch_bytes(c);
+    return ACX_OK;
+  }
+  out->workspace_bytes = generic_scratch_bytes(c, &out->counters);
+  if (const size_t pieces_b = sk_scratch_bytes(c)) {
+    out->workspace_bytes = pieces_b;
+    out->counters = 1;
+  }
+  return ACX_OK;
 }
 
 // Split count of the M reduction: a pure function of the shape (so results are run-to-run identical).

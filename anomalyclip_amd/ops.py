@@ -6,6 +6,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import gc
+import threading
 from typing import Optional, Sequence
 
 import torch
@@ -44,16 +45,20 @@ def _dt(t: torch.Tensor) -> int:
     raise L.AcxError(f"unsupported dtype {t.dtype}")
 
 
-SK_MAX_ROWS = 320        # == the library's ACX_OPT_SK_MAX_M default: f32 GEMMs with at most this many rows run the few-row kernel
+def get_option(device_index: int, opt: int) -> int:
+    """acx_get_option: the ACX_OPT_* value (L.OPT_*) this device's context acts on -- as acx_create set it, or as last set by one of
+    the setters below or by acx_set_option directly.  The context is the only place the options live."""
+    h = L.ctx(device_index)
+    value = C.c_int64(0)
+    L.check(L.lib().acx_get_option(h, int(opt), C.byref(value)), h)
+    return int(value.value)
 
 
 def set_few_row_limit(device_index: int, rows: int) -> None:
-    """ACX_OPT_SK_MAX_M on this device's context and the wrapper's mirror of it (ops.gemm hands such problems no split-K
-    workspace, the text-tower glue picks the fused few-row launches below it)."""
-    global SK_MAX_ROWS
+    """ACX_OPT_SK_MAX_M: f32 GEMMs with at most this many rows run the few-row kernel (the text-tower glue picks the fused few-row
+    launches below it)."""
     h = L.ctx(device_index)
     L.check(L.lib().acx_set_option(h, L.OPT_SK_MAX_M, int(rows)), h)
-    SK_MAX_ROWS = int(rows)
 
 def set_x6_cus(device_index: int, cus: int) -> None:
     """ACX_OPT_X6_CUS: cap the persistent bf16 x 6 kernels' grid (0: every CU) so that other streams' kernels find free CUs while
@@ -61,22 +66,19 @@ def set_x6_cus(device_index: int, cus: int) -> None:
     the shape and of this value): set it BEFORE capturing graphs, and identically on every rank."""
     h = L.ctx(device_index)
     L.check(L.lib().acx_set_option(h, L.OPT_X6_CUS, int(cus)), h)
-    x6_options(device_index)["cus"] = int(cus)
-
-
-X6_MIN_TILES_DEFAULT = 18   # ACX_OPT_X6_MIN_TILES as acx_create sets it (tests restore it)
-_X6_OPTS: dict = {}     # device index -> {"cus": n, "tail_split": bool}: the wrapper's mirror of the context options it sizes scratch by
 
 
 def x6_options(device_index: int) -> dict:
-    return _X6_OPTS.setdefault(int(device_index), {"cus": 0, "tail_split": False})
+    """{"cus": ACX_OPT_X6_CUS, "tail_split": ACX_OPT_X6_TAIL_SPLIT} of this device's context: what the grid and the K split of a
+    captured bf16 x 6 launch depend on (the graph keys)."""
+    return {"cus": get_option(device_index, L.OPT_X6_CUS), "tail_split": bool(get_option(device_index, L.OPT_X6_TAIL_SPLIT))}
 
 
 def x6_workgroups(device_index: int) -> int:
     """Workgroups the persistent bf16 x 6 kernels launch on this device: its CU count, or ACX_OPT_X6_CUS when that is lower
-    (what acx_gemm's K-split model is evaluated for: the wrapper sizes the split workspace by the same number)."""
+    (what acx_gemm's K-split model is evaluated for)."""
     ncu = torch.cuda.get_device_properties(device_index).multi_processor_count
-    cap = x6_options(device_index)["cus"]
+    cap = get_option(device_index, L.OPT_X6_CUS)
     return min(ncu, cap) if cap > 0 else ncu
 
 
@@ -85,7 +87,6 @@ def set_x6_tail_split(device_index: int, on: bool) -> None:
     tail rows of a launch another summation order than the rows before them)."""
     h = L.ctx(device_index)
     L.check(L.lib().acx_set_option(h, L.OPT_X6_TAIL_SPLIT, int(bool(on))), h)
-    x6_options(device_index)["tail_split"] = bool(on)
 
 
 def set_x6_strip_tail(device_index: int, mode: int) -> None:
@@ -110,20 +111,11 @@ def set_ln_rider(device_index: int, mode: int) -> None:
     L.check(L.lib().acx_set_option(h, L.OPT_LN_RIDER, int(mode)), h)
 
 
-ATTN_F32IN_DEFAULT = True   # ACX_OPT_ATTN_F32IN as acx_create sets it (tests restore it)
-
-
 def set_attn_f32in(device_index: int, on: bool) -> None:
     """ACX_OPT_ATTN_F32IN: 1 (default) = in the six-product ViT layers the in-projection writes f32 rows and the plane attention
     splits q | k | v itself (acx_attention_p3f); 0 = q | k | v pass through memory as three bf16 planes.  Bit-identical results."""
     h = L.ctx(device_index)
     L.check(L.lib().acx_set_option(h, L.OPT_ATTN_F32IN, int(bool(on))), h)
-
-
-# ACX_OPT_CLS_FOLD as acx_create sets it in the default build (tests restore it).  The default is a compile-time constant of the library
-# (ACX_CLS_FOLD_DEFAULT) and the ABI has no getter: a library built with the other default (the A/B arm of tools/ab_cls_fold.py) is for
-# bench.py only -- the test suite is meant for the default build.
-CLS_FOLD_DEFAULT = True
 
 
 def set_cls_fold(device_index: int, on: bool) -> None:
@@ -194,7 +186,28 @@ def _colsum_counters(device) -> torch.Tensor:
     return c
 
 
-def runs_beside(main: "torch.cuda.Stream", cand: "torch.cuda.Stream", device, _big: Optional[torch.Tensor] = None) -> bool:
+_SCRATCH_ANSWER = threading.local()     # per thread: (acx_gemm_scratch_t, its byref) -- the query runs once per eager product
+
+
+def _bring_scratch(lib, h, d: "L.GemmDesc", pd, device, split_k: bool = True) -> None:
+    """What acx_gemm_scratch says this acx_gemm / acx_gemm_ln call should bring, into the descriptor d (pd = byref(d)): the stream's
+    split-K workspace (its whole size: the library chooses the K split from it) and the stream's arrival counters (all but the last
+    entry, which belongs to the loss kernel).  Which problems split, and into how many pieces, is the library's decision alone."""
+    try:
+        need, pneed = _SCRATCH_ANSWER.v
+    except AttributeError:
+        need = L.GemmScratch()
+        need, pneed = _SCRATCH_ANSWER.v = need, C.byref(need)
+    L.check(lib.acx_gemm_scratch(h, pd, 1 if split_k else 0, pneed), h)
+    if need.workspace_bytes:
+        ws = _splitk_workspace(device, need.workspace_bytes)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if need.counters:
+        ctr = _colsum_counters(device)
+        d.counters, d.n_counters = ctr.data_ptr(), _CTR_N - 1
+
+
+def runs_beside(main:"torch.cuda.Stream", cand: "torch.cuda.Stream", device, _big: Optional[torch.Tensor] = None) -> bool:
     """True when work on `cand` overtakes a long kernel on `main`, i.e. the two streams sit on DIFFERENT hardware queues.  The HIP
     streams of a process share GPU_MAX_HW_QUEUES (default 4) hardware queues per priority, a stream takes its queue at first use,
     and a queue runs its packets in order: two streams on one queue serialise.  Measured here (profiles/r06_stream_queues.txt): with
@@ -370,33 +383,16 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     d.amap, d.gn, d.gl, d.cin = amap, gn, gl, cin
     if amap == L.AMAP_CONV3X3:
         d.zero_page = _zero_page(a3.device).data_ptr()
-    tm, tn = (M + 255) // 256, (N + 255) // 256
-    tiles = tm * tn
-    dev_i = a3.device.index if a3.device.index is not None else torch.cuda.current_device()
-    wgs = x6_workgroups(dev_i)             # (the number acx_gemm evaluates its K-split model for: CUs, or ACX_OPT_X6_CUS)
-    ws = None
-    if split_k and tiles < wgs and K >= 384:
-        ws = _splitk_workspace(a3.device, min(16, max(2, 2 * wgs // tiles)) * M * N * 4)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    elif split_k and x6_options(dev_i)["tail_split"] and amap in (L.AMAP_IDENTITY, L.AMAP_CONV3X3) and K >= 384 and tiles % wgs:
-        # ACX_OPT_X6_TAIL_SPLIT only: scratch for the K split of a partly filled LAST round of tiles (acx_gemm splits the launch
-        # in two) -- sized from the tail's rows (the tile rows behind the full rounds), up to 4 pieces (8 when the tail is short)
-        tail_rows = M - min(M, (tiles // wgs * wgs) // tn * 256)
-        if amap == L.AMAP_CONV3X3 and (gn * gl) % 256 == 0:      # (the tail begins at a token-grid boundary)
-            gt = gn * gl // 256
-            tail_rows = M - min(M, ((tiles // wgs * wgs) // tn) // gt * gt * 256)
-        if tail_rows > 0:
-            ws = _splitk_workspace(a3.device, min(8, max(4, 2 * wgs // max(1, (tail_rows + 255) // 256 * tn))) * tail_rows * N * 4)
-            d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    h = _h(a3)
+    h, lib, pd = _h(a3), L.lib(), C.byref(d)
+    _bring_scratch(lib, h, d, pd, a3.device, split_k)
     if ln is not None:
         lw, lb, ly = ln
         assert not planes_out and out.dtype == torch.float32 and ly.dtype == _BF16 and ly.shape == (3, M, N) and ly.is_contiguous()
         job = L.LnJob()
         job.w, job.b, job.y, job.y_dtype, job.eps, job.mode = lw.data_ptr(), lb.data_ptr(), ly.data_ptr(), L.BF16X3P, 1e-5, L.NORM_LAYER
-        L.check(L.lib().acx_gemm_ln(h, C.byref(d), C.byref(job), _stream()), h)
+        L.check(lib.acx_gemm_ln(h, pd, C.byref(job), _stream()), h)
         return out
-    L.check(L.lib().acx_gemm(h, C.byref(d), _stream()), h)
+    L.check(lib.acx_gemm(h, pd, _stream()), h)
     return out
 
 
@@ -435,33 +431,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, out: Optional[torch.Tensor] = None
         assert tile_table is not None and tile_table.dtype == torch.int32 and tile_table.is_cuda and tile_table.is_contiguous()
         assert tile_table.numel() == 2 * (M // (gn * gl))
         d.tile_table = tile_table.data_ptr()
-    ws = None
-    tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    few_rows = ((M <= SK_MAX_ROWS or (N <= 512 and M <= 4 * SK_MAX_ROWS and not (M > 768 and K >= 1536)))
-                and K % 256 == 0 and prec == L.PREC_F32
-                and amap == L.AMAP_IDENTITY and a_sub is None and pos0 is None
-                and act != L.ACT_LEAKYRELU)                                   # acx_gemm takes the few-row kernel: no split-K
-    # split-K candidates: <= 128 output tiles, or up to 256 with a long K (the convolutions of a data-parallel rank's 4096
-    # rows: 256 tiles = ONE 8-wave block per CU; two K halves put two blocks on every CU for the price of a 12 us reduce)
-    generic_f32 = (a_sub is not None or pos0 is not None or amap in (L.AMAP_TESTTILE, L.AMAP_TILETABLE)) and prec == L.PREC_F32 \
-        and a.dtype == torch.float32 and out.dtype == torch.float32
-    if ((tiles <= 128 and K >= 256 or tiles <= 256 and K >= 1024) and not few_rows
-            and ((amap in (L.AMAP_IDENTITY, L.AMAP_CONV3X3) and a_sub is None and pos0 is None) or generic_f32)):
-        ws = _splitk_workspace(a.device, min(16, 512 // tiles) * M * N * 4)     # skinny problem: let the library split K
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        if amap == L.AMAP_CONV3X3 and prec == L.PREC_F32:
-            # f32 convolutions: the split pieces are reduced INSIDE the kernel (last-arriver, no second launch)
-            ctr = _colsum_counters(a.device)
-            d.counters, d.n_counters = ctr.data_ptr(), _CTR_N - 1
-    if few_rows and K >= 1024 and K % 512 == 0 and ((M + 31) // 32) * ((N + 31) // 32) * (K // 512) <= 512:
-        # long K on few tiles (the text tower's K = 2048 GEMMs): K split across workgroups, last-arriver reduction in-kernel
-        tiles32 = ((M + 31) // 32) * ((N + 31) // 32)
-        ws = _splitk_workspace(a.device, (K // 512) * tiles32 * 4096)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-        ctr = _colsum_counters(a.device)
-        d.counters, d.n_counters = ctr.data_ptr(), _CTR_N - 1               # the last entry belongs to the loss kernel
-    h = _h(a)
-    L.check(L.lib().acx_gemm(h, C.byref(d), _stream()), h)
+    h, lib, pd = _h(a), L.lib(), C.byref(d)
+    _bring_scratch(lib, h, d, pd, a.device)
+    L.check(lib.acx_gemm(h, pd, _stream()), h)
     return out
 
 

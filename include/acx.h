@@ -124,6 +124,9 @@ const char* acx_last_error(acx_ctx* ctx);
 enum { ACX_OPT_RING_MIN_TILES = 1, ACX_OPT_SK_MAX_M = 2, ACX_OPT_TN_P256_MIN_ROWS = 3, ACX_OPT_X6_CUS = 4, ACX_OPT_X6_TAIL_SPLIT = 5,
        ACX_OPT_X6_STRIP_TAIL = 6, ACX_OPT_X6_MIN_TILES = 7, ACX_OPT_LN_RIDER = 8, ACX_OPT_ATTN_F32IN = 9, ACX_OPT_CLS_FOLD = 10 };
 int acx_set_option(acx_ctx* ctx, int32_t option, int64_t value);
+/* *value = the option as acx_create set it or acx_set_option last stored it (what the library acts on: a value the setter clamps
+ * reads back clamped).  ACX_E_UNSUPPORTED for an unknown option, as the setter. */
+int acx_get_option(acx_ctx* ctx, int32_t option, int64_t* value);
 
 /* ------------------------------------------------------------------------------------------
  * acx_gemm: C[M,N] = epilogue( amap(A)[M,K] . W[N,K]^T )            (MFMA-bound workhorse)
@@ -156,7 +159,7 @@ typedef struct acx_gemm_desc {
   const float* pos0;      /* [gn, N] axial positional embedding param_0 (or NULL) */
   const float* pos1;      /* [gl, N] axial positional embedding param_1 (or NULL) */
   void* workspace;        /* optional: enables split-K for skinny problems (few output tiles, long K); */
-  size_t workspace_bytes; /* needs up to 16*M*N*4 bytes, less is fine (fewer splits or none)           */
+  size_t workspace_bytes; /* how much to bring: acx_gemm_scratch; less is fine (fewer splits or none)  */
   /* Few-row fusions of the text tower (clip/model.py:183-185,188-230 and its dX chain).  Both need the few-row f32
    * kernel: f32 operands, identity row map, K % 256 == 0, N % 4 == 0, 16-byte aligned C / residual / gelu_grad_of;
    * ACX_E_UNSUPPORTED otherwise. */
@@ -204,6 +207,19 @@ typedef struct acx_gemm_desc {
                              / activation / residual (operand planes that were scaled by acx_split_f16x2); 0 = 1 */
 } acx_gemm_desc;
 int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream);
+
+/* The scratch to hand to acx_gemm / acx_gemm_ln with this descriptor (the *_workspace_bytes query of acx_gemm): workspace_bytes of
+ * `workspace` (0: hand none -- a workspace can change the route as well as the split), counters != 0: hand the arrival-counter table
+ * too.  The routes choose their K split from the size they are given, so two callers that follow the query sum in the same order.
+ * Host arithmetic only, no device work: it reads the shape fields and tests residual, a_sub, pos0, zero_page, ... for NULL; no pointer
+ * of the descriptor is dereferenced, d->workspace and d->counters are ignored.  allow_split = 0: no K split across workgroups is
+ * wanted (nothing to bring).  ctx == NULL: 256 workgroups and the option values acx_create sets; else the context's CU count,
+ * ACX_OPT_SK_MAX_M, ACX_OPT_X6_CUS and ACX_OPT_X6_TAIL_SPLIT. */
+typedef struct acx_gemm_scratch_t {
+  size_t workspace_bytes;
+  int32_t counters;
+} acx_gemm_scratch_t;
+int acx_gemm_scratch(const acx_ctx* ctx, const acx_gemm_desc* d, int32_t allow_split, acx_gemm_scratch_t* out);
 
 /* acx_gemm_ln: acx_gemm(d) followed by the LayerNorm of ITS OUTPUT rows -- x = d->C ([M, N] f32, ldc == N), y = norm(x) * w + b as
  * acx_layernorm(x, ldc, w, b, y, N, y_dtype, M, N, eps, mode) writes it -- with the same bits as those two calls.  A pairs = 6 product

@@ -8,6 +8,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from anomalyclip_amd import _lib as L
 from anomalyclip_amd import init_weights as IW
 from anomalyclip_amd import ops
 from anomalyclip_amd.components.clip_vit import VisionTransformer
@@ -79,13 +80,14 @@ def _vit(name, precision, seed=3):
 def _on_off(vit, x):
     dev = torch.cuda.current_device()
     vit.chunk = x.shape[0]
+    before = ops.get_option(dev, L.OPT_ATTN_F32IN)
     try:
         ops.set_attn_f32in(dev, True)
         on = vit(x).clone()
         ops.set_attn_f32in(dev, False)
         off = vit(x).clone()
     finally:
-        ops.set_attn_f32in(dev, ops.ATTN_F32IN_DEFAULT)
+        ops.set_attn_f32in(dev, before)
     assert on.shape[0] == x.shape[0] and torch.isfinite(on).all()
     return on, off
 

@@ -126,11 +126,12 @@ def _vit(name, precision, seed=3):
 def _encode(vit, x, fold):
     dev = torch.cuda.current_device()
     vit.chunk = x.shape[0]
+    before = ops.get_option(dev, L.OPT_CLS_FOLD)
     try:
         ops.set_cls_fold(dev, fold)
         out = vit(x).clone()
     finally:
-        ops.set_cls_fold(dev, ops.CLS_FOLD_DEFAULT)
+        ops.set_cls_fold(dev, before)
     assert out.shape[0] == x.shape[0] and torch.isfinite(out).all()
     return out
 

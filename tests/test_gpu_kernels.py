@@ -106,11 +106,12 @@ def test_gemm_few_row_fusions_are_refused_elsewhere():
         ops.gemm(a, w, a_act=L.ACT_QUICKGELU)
     a, w = torch.randn(154, 512, generator=g).to(DEV), torch.randn(512, 512, generator=g).to(DEV)
     few = ops.gemm(a, w)
+    before = ops.get_option(torch.cuda.current_device(), L.OPT_SK_MAX_M)
     ops.set_few_row_limit(torch.cuda.current_device(), 0)
     try:
         tiles = ops.gemm(a, w)
     finally:
-        ops.set_few_row_limit(torch.cuda.current_device(), 320)
+        ops.set_few_row_limit(torch.cuda.current_device(), before)
     assert relerr(few, tiles) < 2e-6 and relerr(few, a.double().cpu() @ w.double().cpu().t()) < 2e-6
 
 
@@ -962,13 +963,14 @@ def test_gemm_x6_random_shapes_vs_fp64(seed):
     bound = 2.5e-6 * (A.abs() @ w.double().abs().t() + b.double().abs() + (r.double().abs() if res else 0)) + 1e-30
     dev = torch.device(DEV).index or 0
     outs = {}
+    before = ops.get_option(dev, L.OPT_X6_CUS)
     for split in (True, False):
         for cus in (0, 5):
             try:
                 ops.set_x6_cus(dev, cus)
                 y = ops.gemm_x6(a3, w3, split_k=split, **kw)
             finally:
-                ops.set_x6_cus(dev, 0)
+                ops.set_x6_cus(dev, before)
             e = (y.double() - ref).abs()
             assert bool((e <= bound).all()), (seed, M, N, K, conv, act, res, split, cus, float((e / bound).max()))
             outs[(split, cus)] = y
@@ -999,11 +1001,12 @@ def test_gemm_x6_partial_last_round_is_k_split(M, N, K):
     dev = torch.device(DEV).index or 0
     y2_off = ops.gemm_x6(a3, w3, bias=b, residual=r, split_k=True, panels=3)
     assert torch.equal(y2_off, y1)                                                       # opt-in: off by default
+    before = ops.get_option(dev, L.OPT_X6_TAIL_SPLIT)
     ops.set_x6_tail_split(dev, True)
     try:
         _partial_last_round_checks(M, N, K, a, w, b, r, x, a3, w3, y1)
     finally:
-        ops.set_x6_tail_split(dev, False)
+        ops.set_x6_tail_split(dev, before)
 
 
 def _partial_last_round_checks(M, N, K, a, w, b, r, x, a3, w3, y1):
@@ -1077,11 +1080,12 @@ def test_conv3x3_x6_partial_last_round_is_k_split():
     run = lambda: ops.gemm_x6(x3, w3, bias=b, act=L.ACT_LEAKYRELU, amap=L.AMAP_CONV3X3, gn=gn, gl=gl, cin=cin)
     y1 = run()
     dev = torch.device(DEV).index or 0
+    before = ops.get_option(dev, L.OPT_X6_TAIL_SPLIT)
     ops.set_x6_tail_split(dev, True)
     try:
         y2 = run()
     finally:
-        ops.set_x6_tail_split(dev, False)
+        ops.set_x6_tail_split(dev, before)
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
     row0 = (ncu // 2 * 2) * 256
     assert row0 < rows and torch.equal(y2[:row0], y1[:row0]) and not torch.equal(y2[row0:], y1[row0:])
@@ -1109,13 +1113,14 @@ def test_x6_cus_option_caps_the_grid_same_product():
     y0 = run()
     dev = torch.device(DEV).index or 0
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    before = ops.get_option(dev, L.OPT_X6_CUS)
     try:
         ops.set_x6_cus(dev, ncu - 32)
         y1, y1b = run(), run()
         ops.set_x6_cus(dev, 7)                                             # fewer workgroups than tiles x pieces: several items each
         y2 = run()
     finally:
-        ops.set_x6_cus(dev, 0)
+        ops.set_x6_cus(dev, before)
     y3 = run()
     assert torch.equal(y1, y1b) and torch.equal(y3, y0)
     xg = x.double().view(tiles, gn, gl, cin)

@@ -58,11 +58,12 @@ def test_vit_f32x6_small_launches_vs_reference(golden, which):
     vit, _ = make_vit(geom, int(g["seed"]), precision="f32x6")
     frames = torch.from_numpy(g["frames"]) if which == "vit_tiny" else R.vit_frames(int(g["seed"]), 2, 224)
     h = L.ctx(torch.cuda.current_device())
+    before = ops.get_option(torch.cuda.current_device(), L.OPT_X6_MIN_TILES)
     ops.set_x6_min_tiles(torch.cuda.current_device(), 1)
     try:
         out = vit(frames.to(DEV))
     finally:
-        ops.set_x6_min_tiles(torch.cuda.current_device(), ops.X6_MIN_TILES_DEFAULT)
+        ops.set_x6_min_tiles(torch.cuda.current_device(), before)
     assert relerr(out, g["out"]) < TOL and elem_ok(out, g["out"])
     vit32, _ = make_vit(geom, int(g["seed"]))
     assert relerr(out, vit32(frames.to(DEV))) < 5e-6                     # and round-off away from the f32 MFMA path

@@ -118,12 +118,13 @@ def test_gemm_tn_x6_random_shapes_vs_fp64(seed):
     ref = a.double().t() @ B
     bound = 2.5e-6 * (a.double().abs().t() @ B.abs()) + 1e-30
     dev = torch.device(DEV).index or 0
+    before = ops.get_option(dev, L.OPT_X6_CUS)
     for cus in (0, 37):
         try:
             ops.set_x6_cus(dev, cus)
             y = ops.gemm_tn_x6(a3, b3, conv=conv, gn=gn, gl=gl, cin=cin)
         finally:
-            ops.set_x6_cus(dev, 0)
+            ops.set_x6_cus(dev, before)
         e = (y.double() - ref).abs()
         assert bool((e <= bound).all()), (seed, M, N1, ncol, conv, gn, gl, cus, float((e / bound).max()))
 
@@ -765,6 +766,7 @@ def test_full_config_train_step_vs_oracle(prompts_table, cfg, B, precision):
     # filled last round of the convolutions' tiles K-split (AnomalyCLIPModule._x6_cu_reservation) -- the same options here
     dp2 = B == 32
     dev_i = torch.device(DEV).index or 0
+    before = ops.x6_options(dev_i)
     if dp2:
         ops.set_x6_cus(dev_i, torch.cuda.get_device_properties(dev_i).multi_processor_count - 32)
         ops.set_x6_tail_split(dev_i, True)
@@ -775,8 +777,8 @@ def test_full_config_train_step_vs_oracle(prompts_table, cfg, B, precision):
             losses[0].backward()
     finally:
         if dp2:
-            ops.set_x6_cus(dev_i, 0)
-            ops.set_x6_tail_split(dev_i, False)
+            ops.set_x6_cus(dev_i, before["cus"])
+            ops.set_x6_tail_split(dev_i, before["tail_split"])
     sides = _leaky_sides(tap, net.temporal_model, B)
     del net.temporal_model.__dict__["_act_tap"]
     names = [n for n, p in net.named_parameters() if p.requires_grad and n != "selector_model.logit_scale"]
