@@ -13,6 +13,7 @@ c_void_p, c_int32, c_int64, c_float, c_size_t = C.c_void_p, C.c_int32, C.c_int64
 ACX_F32, ACX_BF16, BF16X3, BF16X3P = 0, 1, 2, 3      # BF16X3 / BF16X3P: output only (three bf16 planes hi | mid | lo; P: K-panel layout)
 BF16X2P, ACX_F16, F16X2P = 4, 5, 6                     # hi + mid planes only; fp16 planes of the two-plane split (pairs = 3); their K-panel output
 PREC_F32, PREC_BF16, PREC_F32X6, PREC_F32X3, PREC_F16X3 = 0, 1, 2, 3, 4
+PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet encoder on the plane kernel (precision "bf16x6")
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
@@ -89,7 +90,7 @@ class VitDesc(C.Structure):
 
 
 class ResnetConv(C.Structure):          # == struct acx_resnet_conv
-    _fields_ = [("w", c_void_p), ("b", c_void_p)]
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("w3", c_void_p)]
 
 
 class ResnetBlock(C.Structure):         # == struct acx_resnet_block
@@ -98,7 +99,8 @@ class ResnetBlock(C.Structure):         # == struct acx_resnet_block
 
 class ResnetWeights(C.Structure):       # == struct acx_resnet_weights
     _fields_ = [("stem", ResnetConv * 3), ("blocks", C.POINTER(ResnetBlock)), ("positional_embedding", c_void_p),
-                ("q_w", c_void_p), ("q_b", c_void_p), ("kv_w", c_void_p), ("kv_b", c_void_p), ("c_w", c_void_p), ("c_b", c_void_p)]
+                ("q_w", c_void_p), ("q_b", c_void_p), ("kv_w", c_void_p), ("kv_b", c_void_p), ("c_w", c_void_p), ("c_b", c_void_p),
+                ("kv_w3", c_void_p)]
 
 
 class ResnetBn(C.Structure):            # == struct acx_resnet_bn

@@ -145,6 +145,10 @@ class AnomalyCLIP(nn.Module):
             # opt-in, NOT f32-accurate: the ViT's plane products with the three leading cross products only (ACX_PREC_F32X3: sixteen
             # significant bits per operand); the head keeps the default's arithmetic
             self.precision = "auto"
+        elif self.precision == "bf16x6":
+            # opt-in, f32-accurate: a ResNet image encoder on the plane kernel (ACX_PREC_BF16X6); the rest runs the default's
+            # arithmetic.  On a ViT arch it is refused below: "auto" already is that arithmetic there
+            self.precision = "auto"
         head_precision = "f32" if self.precision == "auto" else self.precision      # text tower (too small for the bf16 x 6 kernel)
         check_head_geometry(self.num_segments, self.seg_length, self.emb_size, self.heads, self.dim_heads, self.num_topk,
                             self.num_bottomk)                                          # (before anything is allocated)

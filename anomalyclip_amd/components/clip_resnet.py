@@ -23,8 +23,14 @@ from torch import nn
 from .. import _lib as L
 from .. import ops
 
-# "auto" (the default) and "f32" run the f32 MFMA kernels; "f32x6" is the older name of "auto"
-RESNET_PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "f32x6": L.PREC_F32X6}
+# "auto" (the default) and "f32" run the f32 MFMA kernels; "f32x6" is the older name of "auto".  "bf16x6" (opt-in, eval mode) runs
+# the convolutions as f32-accurate six-product GEMMs of bf16 planes (ACX_PREC_BF16X6); training mode stays on the f32 kernels.
+RESNET_PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "f32x6": L.PREC_F32X6, "bf16x6": L.PREC_BF16X6}
+
+
+def _routed(K: int, conv3x3: bool) -> bool:
+    """acx_resnet_encode's routing rule at ACX_PREC_BF16X6 (csrc/acx_resnet.hip rn_routed): the products that read w3 planes"""
+    return conv3x3 or K >= 64
 
 
 def check_resnet_precision(precision: str, arch: str, width: int = 64):
@@ -33,7 +39,7 @@ def check_resnet_precision(precision: str, arch: str, width: int = 64):
     if width % 8:
         raise ValueError(f"{arch}: width {width} is not a multiple of 8 (acx_resnet_encode)")
     if precision not in RESNET_PRECISIONS:
-        raise ValueError(f"precision {precision!r} is not available for {arch}: the ResNet encoders run 'auto' or 'f32'")
+        raise ValueError(f"precision {precision!r} is not available for {arch}: the ResNet encoders run 'auto', 'f32' or 'bf16x6'")
 
 
 def _cp(c: int) -> int:
@@ -142,18 +148,30 @@ class ModifiedResNet(nn.Module):
 
     def _weights(self, fold: bool = True):
         """The acx_resnet_weights table: BatchNorms folded (eval), or the raw convolution weights (training mode); cached by weight
-        epoch and the address / version of every parameter and buffer."""
-        key = (ops.WEIGHT_EPOCH[0],) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        epoch and the address / version of every parameter and buffer.  precision "bf16x6" (eval): plus the three bf16 planes of
+        every folded weight the driver routes to the plane kernel -- part of the same cache entry, which is keyed by the precision
+        as well (a table built for one precision is never handed to another)."""
+        x6 = fold and self.precision == "bf16x6"
+        key = (ops.WEIGHT_EPOCH[0], x6) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
         cache = self._wcache if fold else self._tcache
         if cache is not None and cache[0] == key:
             return cache[1]
         keep = []
+        split = []                                  # (f32 weight, its [3, Cout_p, K] bf16 planes): one launch at the end
         w = L.ResnetWeights()
+
+        def planes(wf):
+            w3 = torch.empty((3,) + tuple(wf.shape), dtype=torch.bfloat16, device=wf.device)
+            split.append((wf, w3))
+            keep.append(w3)
+            return w3.data_ptr()
 
         def put(dst, conv, bn, cin_p, stem=False):
             wf, bf = _fold(conv, bn if fold else None, cin_p, stem)
             keep.extend((wf, bf))
             dst.w, dst.b = wf.data_ptr(), bf.data_ptr()
+            if x6 and not stem and _routed(wf.shape[1], conv.kernel_size[0] == 3):
+                dst.w3 = planes(wf)
         put(w.stem[0], self.conv1, self.bn1, 32, stem=True)
         put(w.stem[1], self.conv2, self.bn2, _cp(self.width // 2))
         put(w.stem[2], self.conv3, self.bn3, _cp(self.width // 2))
@@ -174,6 +192,9 @@ class ModifiedResNet(nn.Module):
         w.positional_embedding = ap.positional_embedding.data_ptr()
         w.q_w, w.q_b = ap.q_proj.weight.data_ptr(), ap.q_proj.bias.data_ptr()
         w.kv_w, w.kv_b = kv_w.data_ptr(), kv_b.data_ptr()
+        if x6 and _routed(kv_w.shape[1], False):
+            w.kv_w3 = planes(kv_w)
+        ops.split_bf16x3_multi(split)
         w.c_w, w.c_b = ap.c_proj.weight.data_ptr(), ap.c_proj.bias.data_ptr()
         if fold:
             self._wcache = (key, (w, keep))

@@ -43,6 +43,9 @@ def check_vit_precision(precision: str, tokens: int, width: int, arch: str, reso
     accuracy is measured there only): they are refused for the ViT-B/32 / ViT-L/14 / ViT-L/14@336px geometries and for anything
     above 224 tokens (which no earlier release ran).  Other geometries keep what they did before (small ones, such as the test
     geometry, run those launches on the f32 kernels).  "auto", "f32" and "bf16" run every geometry up to 1024 tokens."""
+    if precision == "bf16x6":
+        raise ValueError(f"precision 'bf16x6' is a ResNet encoder precision: for {arch} 'auto' already is that arithmetic (every large "
+                         "product as an f32-accurate six-product GEMM of bf16 planes); use 'auto'")
     if precision not in PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}: one of {', '.join(PRECISIONS)}")
     if precision in ("bf16x3", "f16x3") and (tokens > 224 or (resolution, patch, width) in _NEW_ARCH_VISION):

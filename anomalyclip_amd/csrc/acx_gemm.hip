@@ -43,6 +43,7 @@
 //   gemm_bf16_ring_kernel    _bf16.h     bf16, persistent 256x256 tiles for the large-M shapes
 //   gemm_bf16_p8_kernel      _p8.h       the ring kernel's tile stream on a phase-interleaved schedule
 //   gemm_x6_p4_kernel        _x6.h       pairs = 6 / 3: products of bf16 / fp16 planes, one wave per SIMD; also acx_gemm_tn_x6
+//   gemm_x6_rn_kernel        _x6.h       the same body: the ReLU epilogues and the general 3x3 convolution map (ResNet encoder)
 //   gemm_tn_kernel / _w8 / _p256 / _w8_group  _tn.h   weight gradients C = A^T B (reduction over rows), split-M + reduce
 // (+ the reduce launches of a K split: splitk_reduce_kernel, splitk_reduce4_kernel, tn_reduce_kernel)
 //
@@ -465,6 +466,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
 #include "acx_gemm_bf16.h"   // gemm_bf16_dma_kernel, gemm_bf16_ring_kernel
 #include "acx_gemm_p8.h"     // gemm_bf16_p8_kernel: the ring kernel's tile stream on a phase-interleaved schedule
 #include "acx_gemm_x6.h"     // gemm_x6_p4_kernel: pairs = 6 products, one wave per SIMD, plane-reuse schedule
+#define X6_KERNEL gemm_x6_rn_kernel
+#include "acx_gemm_x6.h"     // gemm_x6_rn_kernel: the same text, the ResNet encoder's instantiations (ReLU epilogues, general conv map)
 #include "acx_gemm_tn.h"     // gemm_tn_kernel, gemm_tn_w8_kernel, tn_reduce_kernel
 
 template <int C_BF16>
@@ -680,11 +683,13 @@ static int gemm_validate(acx_ctx* ctx, const acx_gemm_desc* d) {
   }
   if ((d->pos0 != nullptr) != (d->pos1 != nullptr) || (d->pos0 && (d->gn <= 0 || d->gl <= 0)))
     return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: pos0/pos1 need both pointers and a grid%s");
-  // the ReLU epilogues (ResNet encoder): f32 products on the identity / CONV3X3 row maps only
+  // the ReLU epilogues (ResNet encoder): f32 products, or pairs = 6 products of bf16 planes (route_x6 says which combinations),
+  // on the identity / CONV3X3 row maps only
   const bool relu_act = d->act == ACX_ACT_RELU || d->act == ACX_ACT_RESRELU;
-  if (relu_act && (prec != ACX_PREC_F32 || d->pairs > 1 || c_bf16 || d->a_sub || d->pos0 || d->a_act != ACX_ACT_NONE ||
+  const bool relu_x6 = d->pairs == 6 && prec == ACX_PREC_BF16 && d->a_dtype == ACX_BF16;
+  if (relu_act && (((prec != ACX_PREC_F32 || d->pairs > 1) && !relu_x6) || c_bf16 || d->a_sub || d->pos0 || d->a_act != ACX_ACT_NONE ||
                    d->gelu_grad_of || d->a_norm_w || (d->amap != ACX_AMAP_IDENTITY && d->amap != ACX_AMAP_CONV3X3)))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_RELU / ACX_ACT_RESRELU need an f32 product on identity or CONV3X3 rows%s");
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_RELU / ACX_ACT_RESRELU need an f32 or a pairs = 6 product on identity or CONV3X3 rows%s");
   if (d->act == ACX_ACT_RESRELU && !d->residual)
     return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: ACX_ACT_RESRELU needs a residual%s");
   if (d->act < ACX_ACT_NONE || d->act > ACX_ACT_RESRELU) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: unknown act%s");
@@ -845,6 +850,16 @@ static bool x6_operands_ok(const GemmCall& c) {
          d->K % 32 == 0;
 }
 
+// CONV3X3 rows the shift map of the plane kernel cannot index: a grid that is not a power of two, or a last tile behind M
+static bool x6_conv_general(const acx_gemm_desc* d) {
+  return (d->gl & (d->gl - 1)) || (d->gn & (d->gn - 1)) || d->M % 256 != 0;
+}
+// products of the plane kernel that never split K across workgroups (route_x6, and so acx_gemm_scratch): the ReLU epilogues and the
+// general convolution map
+static bool x6_may_split(const GemmCall& c) {
+  return !c.relu_act && !(c.d->amap == ACX_AMAP_CONV3X3 && x6_conv_general(c.d));
+}
+
 static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden);
 
 // ---- route 1, opt-in (ACX_OPT_X6_TAIL_SPLIT): pairs = 6, more 256 x 256 tiles than CUs, a last round that fills only part of
@@ -869,7 +884,7 @@ static int x6_tail_tm_main(const acx_gemm_desc* d, int ncu) {
 static int route_x6_tail_split(const GemmCall& c) {
   acx_ctx* ctx = c.ctx;
   const acx_gemm_desc* d = c.d;
-  if (!(d->pairs == 6 && d->workspace && ctx && ctx->opt_x6_tail && x6_operands_ok(c))) return ROUTE_NEXT;
+  if (!(d->pairs == 6 && d->workspace && ctx && ctx->opt_x6_tail && x6_operands_ok(c) && x6_may_split(c))) return ROUTE_NEXT;
   const int ncu = c.ncu_x6;
   const int tm = (d->M + 255) / 256, tn = (d->N + 255) / 256, xt = tm * tn, nks = d->K / 32;
   const int rounds = xt / ncu, rem = xt - rounds * ncu;
@@ -903,7 +918,7 @@ static int route_x6_tail_split(const GemmCall& c) {
 constexpr int X6_TAIL_PIECES_MIN = 4, X6_TAIL_PIECES_MAX = 8;
 static size_t x6_tail_scratch_bytes(const GemmCall& c) {
   const acx_gemm_desc* d = c.d;
-  if (!(c.ctx && c.ctx->opt_x6_tail && x6_operands_ok(c) && d->K >= X6_SPLIT_MIN_K)) return 0;
+  if (!(c.ctx && c.ctx->opt_x6_tail && x6_operands_ok(c) && x6_may_split(c) && d->K >= X6_SPLIT_MIN_K)) return 0;
   const int ncu = c.ncu_x6, tn = (d->N + 255) / 256, xt = ((d->M + 255) / 256) * tn;
   if (xt < ncu || xt % ncu == 0) return 0;
   const int64_t m_tail = d->M - (int64_t)x6_tail_tm_main(d, ncu) * 256;
@@ -1000,19 +1015,29 @@ static size_t sk_scratch_bytes(const GemmCall& c) {
 // alone would not fill the chip (caller-provided workspace)
 template <int CM, int ACT, int RES, int CV, int NI>
 static void x6_launch(const GemmCall& c, dim3 grid, const Args& g) {
-  if constexpr (CV == 0 && CM != 1 && ACT != 2) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual)
+  if constexpr (CV == 0 && CM != 1 && ACT < 2) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual)
     if (c.d->pairs == 3) {                        // the three leading products only (acx_gemm_x6.h, X3); fp16 planes: X3 = 2
       if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       else acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       return;
     }
   }
-  acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  if constexpr (ACT >= ACX_ACT_RELU || CV == 2) {   // (the ResNet encoder's: whole tiles only)
+    static_assert(NI == 4, "gemm_x6_rn_kernel: whole tiles");
+    acx_launch_lds<gemm_x6_rn_kernel<CM, ACT, RES, CV, 0, 0, 4>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  } else {
+    acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  }
 }
 // whole 256 x 256 tiles: every epilogue (a K split leaves it to the reduce launch)
 template <int CV>
 static void x6_launch_tiles(const GemmCall& c, bool c_x3, int split, dim3 grid, const Args& g) {
   const int act = c.d->act;
+  // the ResNet encoder's epilogues (no K split): ReLU to planes or f32 on both row maps, ReLU after the residual on identity rows;
+  // the general convolution map (CV = 2) has these and the plain f32 output only (route_x6 refuses the rest)
+  if (act == ACX_ACT_RELU) { if (c_x3) x6_launch<2, 3, 0, CV, 4>(c, grid, g); else x6_launch<0, 3, 0, CV, 4>(c, grid, g); return; }
+  if constexpr (CV == 0) { if (act == ACX_ACT_RESRELU) { x6_launch<0, 4, 1, 0, 4>(c, grid, g); return; } }
+  if constexpr (CV == 2) { x6_launch<0, 0, 0, 2, 4>(c, grid, g); return; } else {
   if (split > 1) x6_launch<0, 0, 0, CV, 4>(c, grid, g);
   else if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<2, 2, 0, CV, 4>(c, grid, g); else x6_launch<2, 0, 0, CV, 4>(c, grid, g); }
   else if (c.c_bf16) { if (act == ACX_ACT_QUICKGELU) x6_launch<1, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<1, 2, 0, CV, 4>(c, grid, g); else x6_launch<1, 0, 0, CV, 4>(c, grid, g); }
@@ -1020,6 +1045,7 @@ static void x6_launch_tiles(const GemmCall& c, bool c_x3, int split, dim3 grid, 
   else if (act == ACX_ACT_QUICKGELU) x6_launch<0, 1, 0, CV, 4>(c, grid, g);
   else if (act == ACX_ACT_LEAKYRELU) x6_launch<0, 2, 0, CV, 4>(c, grid, g);
   else x6_launch<0, 0, 0, CV, 4>(c, grid, g);
+  }
 }
 // the strips of the last round: identity rows only; epilogues of the ViT's products (plane outputs with / without QuickGELU,
 // f32 with a residual / QuickGELU / plain) -- anything else keeps whole tiles (X6PlanIn.may_strip)
@@ -1042,7 +1068,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   const acx_gemm_desc* d = c.d;
   if (!((d->pairs == 6 || d->pairs == 3) && ACX_DBG_SWITCH("X6P4", true))) return ROUTE_NEXT;
   const bool conv = d->amap == ACX_AMAP_CONV3X3, x3 = d->pairs == 3, c_bf16 = c.c_bf16;
-  if (x3 && (conv || c_bf16 || d->act == ACX_ACT_LEAKYRELU))
+  if (x3 && (conv || c_bf16 || d->act == ACX_ACT_LEAKYRELU || c.relu_act))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 3 takes identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues%s");
   const bool c_x3_ = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
   if (c.a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P)
@@ -1054,20 +1080,30 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
       (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && !(d->act == ACX_ACT_QUICKGELU && d->residual) &&
       !(d->act == ACX_ACT_LEAKYRELU && d->residual) && !(c_x3_ && (d->residual || d->N % 8 || d->ldc % 8)) && !(c_bf16 && d->residual) &&
       (!d->panels || (!conv && d->K % 32 == 0 && d->lda == d->K && d->ldw == d->K)) && ((d->c_dtype != ACX_BF16X3P && d->c_dtype != ACX_F16X2P) || d->ldc == d->N) &&
-      (!conv || (d->zero_page && !((uintptr_t)d->zero_page & 15) && d->cin % 32 == 0 && !(d->gl & (d->gl - 1)) &&
-                 !(d->gn & (d->gn - 1)) && d->M % 256 == 0));
+      (!conv || (d->zero_page && !((uintptr_t)d->zero_page & 15) && d->cin % 32 == 0));
+  if (conv && d->lda > 0 && (size_t)d->M * d->lda * 2 >= ((size_t)1 << 32))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3: an A plane of 4 GiB or more is beyond the per-lane 32-bit byte offsets (fewer rows per call)%s");
   if (!shape_ok) {
-    if (conv) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3 needs a power-of-two grid, cin %% 32 == 0, M %% 256 == 0, a zero page and 16-byte aligned planes%s");
+    if (conv) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3 needs cin %% 32 == 0, N %% 4 == 0, a zero page and 16-byte aligned planes%s");
+    if (c.relu_act) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_RELU / ACX_ACT_RESRELU with pairs = 6 need K %% 32 == 0, N %% 4 == 0 and 16-byte aligned planes%s");
     return ROUTE_NEXT;
   }
+  // the general convolution row map (any grid, any M % (gn gl) == 0: acx_gemm_x6.h CONV = 2) where the shift map does not apply
+  const bool conv_any = conv && x6_conv_general(d);
+  if (conv_any && (d->residual || c_bf16 || (d->act != ACX_ACT_NONE && d->act != ACX_ACT_RELU) || (c_x3_ && d->act != ACX_ACT_RELU)))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 with CONV3X3 off a power-of-two grid of whole 256-row tiles writes f32 (bias, ReLU) or ReLU planes, no residual%s");
+  if (c.relu_act && ((d->act == ACX_ACT_RELU && d->residual) || (d->act == ACX_ACT_RESRELU && (conv || c_x3_))))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 takes ACX_ACT_RELU without a residual (f32 or plane output) and ACX_ACT_RESRELU on identity rows with f32 output%s");
   X6PlanIn in = {};
   in.M = d->M; in.N = d->N; in.K = d->K; in.ncu = c.ncu_x6;
   // narrow convolution outputs (N <= 128: c2 and the input gradient of c1 in the XD-Violence head, E = 128): 256 x 128 tiles
   // (the NI = 2 instantiation) instead of half-empty 256 x 256 ones; f32 outputs without an activation only (what the head asks for)
-  in.narrow = conv && d->N <= 128 && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE;
-  in.may_split = d->workspace && !(c.a_f16 && c_x3_);   // (no reduce launch writes fp16 planes: such launches keep whole K per tile)
+  in.narrow = conv && !conv_any && d->N <= 128 && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE;
+  // (no reduce launch writes fp16 planes: such launches keep whole K per tile; neither do the ResNet encoder's products -- the ReLU
+  // epilogues and the general convolution map -- split: every row of theirs sums K in one order whatever the launch's size)
+  in.may_split = d->workspace && !(c.a_f16 && c_x3_) && x6_may_split(c);
   in.workspace_bytes = d->workspace_bytes;
-  in.may_strip = !conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && x6_strip_enabled(ctx);
+  in.may_strip = !conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && !c.relu_act && x6_strip_enabled(ctx);
   in.strip_force = ctx ? ctx->opt_x6_strip : 1;
   in.tail_split_opt = ctx && ctx->opt_x6_tail;
   in.may_ride = job && ridden && !conv && !x3 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
@@ -1090,6 +1126,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   if (p.main_items > 0) {
     const dim3 xgrid((unsigned)p.main_grid);
     if (in.narrow) { if (d->residual && p.split == 1) x6_launch<0, 0, 1, 1, 2>(c, xgrid, g); else x6_launch<0, 0, 0, 1, 2>(c, xgrid, g); }
+    else if (conv_any) x6_launch_tiles<2>(c, c_x3_, p.split, xgrid, g);
     else if (conv) x6_launch_tiles<1>(c, c_x3_, p.split, xgrid, g);
     else x6_launch_tiles<0>(c, c_x3_, p.split, xgrid, g);
   }
@@ -1113,7 +1150,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
 static size_t x6_split_scratch_bytes(const GemmCall& c) {
   const acx_gemm_desc* d = c.d;
   const int ncu = c.ncu_x6, xt = ((d->M + 255) / 256) * ((d->N + 255) / 256);
-  if (!(x6_operands_ok(c) && d->K >= X6_SPLIT_MIN_K && xt < ncu)) return 0;
+  if (!(x6_operands_ok(c) && x6_may_split(c) && d->K >= X6_SPLIT_MIN_K && xt < ncu)) return 0;
   const int pieces = std::min(X6_SPLIT_PIECES_MAX, std::max(2, 2 * ncu / xt));
   return (size_t)pieces * d->M * d->N * sizeof(float);
 }

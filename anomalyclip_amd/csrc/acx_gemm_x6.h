@@ -26,8 +26,11 @@
 //     persistent kernels); an item is an output tile, or one K range of a tile when the launch splits K (few tiles: the
 //     head's convolutions at a data-parallel rank's rows) -- split items store raw f32 partial tiles, the epilogue is
 //     splitk_reduce_kernel's;
-//   * CONV: implicit-GEMM 3x3 convolution over the (gn, gl) token grid (power-of-two grid, cin % 32 == 0): the DMA source
-//     of an A row is the row shifted by the K-step's tap, or the caller's zero page outside the grid.
+//   * CONV: implicit-GEMM 3x3 convolution over the (gn, gl) token grid (cin % 32 == 0): the DMA source of an A row is the
+//     row shifted by the K-step's tap, or the caller's zero page outside the grid.  CONV = 1: power-of-two grid of whole
+//     256-row tiles (the row's grid position by shifts).  CONV = 2: ANY grid and any M % (gn gl) == 0 (the ResNets' 7, 14,
+//     28, 56 ... grids; a tile may straddle frames and end behind M): the position by division, once per work item where
+//     the row offsets are formed; rows at or behind M take every tap from the zero page (offset clamped) and are never stored.
 //   * MFMA SHAPE (ACX_X6_MFMA16, default 1; NT products -- not TN / PLAIN / X3): the half-steps run on
 //     v_mfma_f32_16x16x32_bf16, ONE instruction per (16-row block, 16-column block, product) and 32-wide K-step: 192 per wave and
 //     half-step, the same 3,072 MFMA cycles, the same 32 ds_read_b128 (X: 8 A.hi + 24 W fragments, Y: 8 A.mid + 8 A.lo + 16 W).
@@ -41,6 +44,8 @@
 //     description above (96 MFMAs of 32x32x16, two fragment sets of 16) is the whole kernel: the A/B arm.
 // Accumulation order differs from the p8 kernel's (all six products of a k range before the next range, smallest cross
 // terms first inside a range); the result is an f32 dot product's either way (tests hold both to the same bounds).
+#ifndef ACX_GEMM_X6_ONCE      // (constants, types and helpers: once; the kernel template below: once per name, see X6_KERNEL)
+#define ACX_GEMM_X6_ONCE
 #ifndef ACX_X6_ABL
 #define ACX_X6_ABL 0     // timing ablations (wrong results), bit mask: 1 no DMA in the K loop, 2 no vmcnt waits, 4 no epilogue stores, 8 every ds_read from one address
 #endif
@@ -126,9 +131,19 @@ __device__ __forceinline__ T& x6_sel(T& a, T& b) {
 // the arithmetic of layernorm_panel2_kernel: a row's planes are bit-identical whichever kernel wrote them).  No workgroup waits for
 // another: the riders read rows no tile of this launch writes and write plane rows no tile of this launch reads.  The workgroups
 // with an item run exactly the code of the RIDE = 0 instantiation.
+#endif  // ACX_GEMM_X6_ONCE
+// The kernel's NAME is a macro: acx_gemm.hip includes this file twice -- as gemm_x6_p4_kernel (the default: every instantiation the
+// ViTs, the head and the weight gradients run) and as gemm_x6_rn_kernel, the ResNet encoder's instantiations (the ReLU epilogues
+// ACT = ACX_ACT_RELU / ACX_ACT_RESRELU and the general convolution row map CONV = 2, whole tiles).  One text, two templates: the
+// first one's instantiations compile exactly as they did before the second existed.
+#ifndef X6_KERNEL
+#define X6_KERNEL gemm_x6_p4_kernel
+#endif
 template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0, int RIDE = 0>
-__global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
+__global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
   static_assert(X3 == 0 || (CONV == 0 && TN == 0 && PLAIN == 0 && W14 == 0), "three-product mode: identity rows, NT");
+  static_assert(CONV != 2 || (TN == 0 && PLAIN == 0 && NI == 4), "general convolution row map: NT products, whole tiles");
+  static_assert(ACT != ACX_ACT_RESRELU || (RES == 1 && C_MODE == 0 && CONV == 0), "ReLU after the residual: f32 output, identity rows");
   static_assert(RIDE == 0 || (C_MODE == 0 && ACT == 0 && RES == 1 && CONV == 0 && TN == 0 && PLAIN == 0 && X3 == 0), "LayerNorm rider: the residual products");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const acx_gemm_desc& d = g.d;
@@ -169,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
   // (S16: global chunk ^ ((row >> 1) & 3) -- the 16-row fragment read of that path is 2-way bank-conflicted under the other map)
   const int dc = ((lane & 3) ^ (S16 ? (lane >> 3) & 3 : (lane >> 4) & 3)) * 16;   // byte offset of its 16-byte piece inside the row's 64 B
   const char* zsrc = (CONV || TN) ? (const char*)g.zeros + (lane & 3) * 16 : nullptr;
-  const int sh_gl = CONV ? __builtin_ctz((unsigned)d.gl) : 0;
+  const int sh_gl = CONV == 1 ? __builtin_ctz((unsigned)d.gl) : 0;
   const int steps_per_tap = (CONV && !TN) ? d.cin / 32 : 1;
   // K-panel layout of the planes (acx_gemm_desc.panels; identity rows): plane = [K / 32][rows][32], a unit is one contiguous
   // 16 KB block -- the byte distance between K-steps is a whole panel (plane bytes / panels), rows are 64 B apart
@@ -200,13 +215,20 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
     if constexpr (TN == 0)                                                                         \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                \
       const int m_ = S.m0 + dr + 16 * i;                                                           \
-      RA[i] = (unsigned)(CONV ? m_ : min(m_, d.M - 1)) * (apanel ? 64u : (unsigned)d.lda * 2u) + (unsigned)dc; \
+      RA[i] = (unsigned)(CONV == 1 ? m_ : min(m_, d.M - 1)) * (apanel ? 64u : (unsigned)d.lda * 2u) + (unsigned)dc; \
       RW[i] = (unsigned)min(S.n0 + dwr + 16 * (i < NI ? i : 0), d.N - 1) * (wpanel ? 64u : (unsigned)d.ldw * 2u) + (unsigned)dc; \
       if constexpr (CONV != 0) {                                                                   \
-        const int n_ = (m_ >> sh_gl) & (d.gn - 1), l_c = m_ & (d.gl - 1);                          \
+        int n_, l_c;                                                                               \
+        if constexpr (CONV == 2) {   /* any grid: by division, once per work item */               \
+          const int r_ = min(m_, d.M - 1) % (d.gn * d.gl);                                         \
+          n_ = r_ / d.gl; l_c = r_ - n_ * d.gl;                                                    \
+        } else {                                                                                   \
+          n_ = (m_ >> sh_gl) & (d.gn - 1); l_c = m_ & (d.gl - 1);                                  \
+        }                                                                                          \
         const unsigned rn_ = (n_ > 0 ? 1u : 0u) | 2u | (n_ < d.gn - 1 ? 4u : 0u);   /* dn = -1, 0, +1 */ \
         const unsigned rl_ = (l_c > 0 ? 1u : 0u) | 2u | (l_c < d.gl - 1 ? 4u : 0u); /* dl = -1, 0, +1 */ \
         VM[i] = ((rn_ & 1u) ? rl_ : 0u) | ((rn_ & 2u) ? rl_ << 3 : 0u) | ((rn_ & 4u) ? rl_ << 6 : 0u); \
+        if constexpr (CONV == 2) { if (m_ >= d.M) VM[i] = 0u; }   /* rows behind M: every tap from the zero page */ \
       }                                                                                            \
     }                                                                                              \
   } while (0)
@@ -790,6 +812,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
         _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                            \
           if constexpr (ACT == ACX_ACT_QUICKGELU) ov[e] = acx_quickgelu(ov[e]);                    \
           else if constexpr (ACT == ACX_ACT_LEAKYRELU) ov[e] = ov[e] > 0.f ? ov[e] : 0.01f * ov[e]; \
+          else if constexpr (ACT == ACX_ACT_RELU) ov[e] = fmaxf(ov[e], 0.f);                       \
         }                                                                                          \
         /* three bf16 planes hi | mid | lo of the f32 value (ACX_BF16X3): the next pairs = 6 product's A operand */ \
         uint4 ph, pm, pl;                                                                          \
@@ -830,8 +853,13 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
       } else if constexpr (ACT == ACX_ACT_LEAKYRELU) {                                             \
         v.x = v.x > 0.f ? v.x : 0.01f * v.x; v.y = v.y > 0.f ? v.y : 0.01f * v.y;                  \
         v.z = v.z > 0.f ? v.z : 0.01f * v.z; v.w = v.w > 0.f ? v.w : 0.01f * v.w;                  \
+      } else if constexpr (ACT == ACX_ACT_RELU) {                                                  \
+        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); \
       }                                                                                            \
       if constexpr (RES != 0) { v.x += R[ps].x; v.y += R[ps].y; v.z += R[ps].z; v.w += R[ps].w; }  \
+      if constexpr (ACT == ACX_ACT_RESRELU) {   /* the ReLU AFTER the residual add */              \
+        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); \
+      }                                                                                            \
       const int row = roww + mi * 32 + 8 * ps;                                                     \
       if ((!(PRED) || (col < d.N && row < d.M)) && (!(ACX_X6_ABL & 4) || g.ksplit == 12345)) {     \
         if constexpr (C_MODE == 1) {                                                        \
@@ -925,3 +953,4 @@ __global__ __launch_bounds__(256, 1) void gemm_x6_p4_kernel(const Args g) {
 #undef X6_ADVANCE
 #undef X6_SET_ITEM
 }
+#undef X6_KERNEL

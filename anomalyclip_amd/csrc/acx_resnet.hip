@@ -214,10 +214,23 @@ int rn_batch(const RnGeom& g) {
 
 struct RnWs {
   float *cols, *x, *t1, *t2, *p, *ds, *tok, *qkv, *o;
+  // ACX_PREC_BF16X6 only: three buffers of three bf16 planes each (the A operands of the plane products) and the 256-byte zero
+  // page of the convolution taps outside a frame
+  char *pl0, *pl1, *pl2;
+  void* zero;
   size_t total;
 };
 
-RnWs rn_carve(char* base, const RnGeom& g, int fb) {
+// The routing rule of ACX_PREC_BF16X6: which products run as pairs = 6 products of bf16 planes (gemm_x6_p4_kernel).  A rule on
+// (K, N, convolution or not) ONLY -- never on the rows of a launch, so every internal batch and every frame count takes the same
+// kernels: every 3x3 convolution, and every 1x1 convolution / linear layer from K = 64 (the K = 32 stem product stays f32).  The
+// one-row-per-frame products of the attention pool (q of token 0, c_proj) are not asked: they stay on the few-row f32 kernel.
+inline bool rn_routed(int K, int N, bool conv) {
+  (void)N;
+  return conv || K >= 64;
+}
+
+RnWs rn_carve(char* base, const RnGeom& g, int fb, bool planes) {
   RnWs w;
   size_t off = 0;
   auto take = [&](size_t floats) { float* p = (float*)(base + off); off += rn_al(floats * 4); return p; };
@@ -230,6 +243,17 @@ RnWs rn_carve(char* base, const RnGeom& g, int fb) {
   w.tok = take((size_t)fb * (g.HW + 1) * g.E);
   w.qkv = take((size_t)fb * (g.HW + 1) * 3 * g.E);
   w.o = take((size_t)fb * g.E);
+  w.pl0 = w.pl1 = w.pl2 = nullptr;
+  w.zero = nullptr;
+  if (planes) {                                                  // (behind the f32 carve: that part is the same for every precision)
+    const size_t tok = (size_t)(g.HW + 1) * g.E;
+    const size_t el = (size_t)fb * ((size_t)g.max_act > tok ? (size_t)g.max_act : tok);
+    auto take_b = [&](size_t bytes) { char* p = base + off; off += rn_al(bytes); return p; };
+    w.pl0 = take_b(3 * el * 2);
+    w.pl1 = take_b(3 * el * 2);
+    w.pl2 = take_b(3 * el * 2);
+    w.zero = take_b(256);
+  }
   w.total = off;
   return w;
 }
@@ -248,14 +272,40 @@ int rn_gemm(acx_ctx* ctx, const float* A, int lda, const float* W, int N, int K,
   return acx_gemm(ctx, &d, s);
 }
 
+// ACX_PREC_BF16X6: the three bf16 planes of an f32 activation [rows][cols] (dense planes, plane stride rows * cols * 2 bytes)
+int rn_split(acx_ctx* ctx, const float* src, int cols, void* dst, int64_t rows, hipStream_t s) {
+  return acx_split_bf16x3(ctx, src, cols, dst, rows * cols * 2, rows, cols, s);
+}
+
+// one pairs = 6 product of the encoder: A3 = three dense bf16 planes [M][lda], W3 = three planes [N][K] of the folded weight; the
+// result as f32 rows (planes_out = false; ldc) or as the three planes of the next product's A operand (dense [M][N]).  No workspace:
+// whole tiles, whole K per tile -- a row's bits do not depend on where its frame sits in the launch.
+int rn_gemm6(acx_ctx* ctx, const void* A3, int lda, const void* W3, int N, int K, void* C, int ldc, bool planes_out, int64_t M,
+             const float* bias, int act, const float* residual, int gh, int gw, int cin, const void* zero, hipStream_t s) {
+  if (!W3) return acx_fail(ctx, ACX_E_BADARG, "acx_resnet_encode: ACX_PREC_BF16X6 needs the w3 planes of every routed convolution%s");
+  acx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = A3; d.W = W3; d.C = C;
+  d.M = (int32_t)M; d.N = N; d.K = K; d.lda = lda; d.ldw = K; d.ldc = planes_out ? N : ldc;
+  d.a_dtype = ACX_BF16; d.c_dtype = planes_out ? ACX_BF16X3 : ACX_F32; d.prec = ACX_PREC_BF16; d.pairs = 6;
+  d.a_plane_stride = M * lda * 2; d.w_plane_stride = (int64_t)N * K * 2;
+  d.bias = bias; d.act = act; d.residual = residual; d.ldr = ldc;
+  if (cin) { d.amap = ACX_AMAP_CONV3X3; d.gn = gh; d.gl = gw; d.cin = cin; d.zero_page = zero; }
+  return acx_gemm(ctx, &d, s);
+}
+
 // attention pool (:71-108) of n frames x [n HW][E]: tokens, k | v for every token into a [n (HW + 1)][3E] q | k | v buffer, q for
 // token 0 only, single-query attention per head (head dim 64, scale 64^-0.5), c_proj
 int rn_attnpool(acx_ctx* ctx, const acx_resnet_weights* w, const RnGeom& g, const RnWs& ws, const float* x, int n, float* features,
-                hipStream_t s) {
+                hipStream_t s, bool x6 = false) {
   int rc;
   const int E = g.E, L = g.HW + 1;
   if ((rc = acx_attnpool_tokens(ctx, x, w->positional_embedding, ws.tok, n, g.HW, E, s))) return rc;
-  if ((rc = rn_gemm(ctx, ws.tok, E, w->kv_w, 2 * E, E, ws.qkv + E, 3 * E, (int64_t)n * L, w->kv_b, ACX_ACT_NONE, nullptr, 0, 0, 0, s)))
+  if (x6 && rn_routed(E, 2 * E, false)) {                         // k | v of every token: planes of the tokens, f32 rows out
+    if ((rc = rn_split(ctx, ws.tok, E, ws.pl0, (int64_t)n * L, s))) return rc;
+    if ((rc = rn_gemm6(ctx, ws.pl0, E, w->kv_w3, 2 * E, E, ws.qkv + E, 3 * E, false, (int64_t)n * L, w->kv_b, ACX_ACT_NONE, nullptr,
+                       0, 0, 0, nullptr, s))) return rc;
+  } else if ((rc = rn_gemm(ctx, ws.tok, E, w->kv_w, 2 * E, E, ws.qkv + E, 3 * E, (int64_t)n * L, w->kv_b, ACX_ACT_NONE, nullptr, 0, 0, 0, s)))
     return rc;
   if ((rc = rn_gemm(ctx, ws.tok, L * E, w->q_w, E, E, ws.qkv, L * 3 * E, n, w->q_b, ACX_ACT_NONE, nullptr, 0, 0, 0, s))) return rc;
   if ((rc = acx_attention_cls(ctx, ws.qkv, 3 * E, ws.o, E, n, L, g.heads, s))) return rc;
@@ -312,6 +362,80 @@ int rn_encode_batch(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_wei
   return rn_attnpool(ctx, w, g, ws, ws.x, n, features, s);
 }
 
+// The same batch at ACX_PREC_BF16X6: every product rn_routed names runs on the plane kernel.  A product whose only consumer is the
+// next product writes that product's A planes itself (conv1 -> conv2, conv2 -> conv3 in a block without stride, the stem's conv2
+// -> conv3); a result that is also needed as f32 rows -- a block's output (the next identity, the average pools' input), a pooled
+// tensor, the stem's first product -- is split by acx_split_bf16x3.  Plane buffers: pl0 = the block input (then the pooled input
+// of a downsample), pl1 = conv1's output (then the pooled branch), pl2 = conv2's output.
+int rn_encode_batch_x6(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const RnGeom& g, const RnWs& ws,
+                       const float* frames, int n, float* features, hipStream_t s) {
+  int rc;
+  const int c1 = rn_cp(g.w / 2), c2 = rn_cp(g.w);
+  const int G = g.G1;
+  const int64_t M1 = (int64_t)n * G * G;
+  const void* Z = ws.zero;
+  // one product: planes in (a3) when routed, else the f32 rows (af); planes out (c3) when routed and asked for, else f32 rows (cf)
+  auto prod = [&](const float* af, const void* a3, int lda, const acx_resnet_conv& cv, int N, int K, float* cf, void* c3, int64_t M,
+                  int act, const float* res, int gh, int cin) -> int {
+    if (rn_routed(K, N, cin != 0))
+      return rn_gemm6(ctx, a3, lda, cv.w3, N, K, c3 ? c3 : (void*)cf, N, c3 != nullptr, M, cv.b, act, res, gh, gh, cin, Z, s);
+    int r = rn_gemm(ctx, af, lda, cv.w, N, K, cf, N, M, cv.b, act, res, gh, gh, cin, s);
+    if (!r && c3) r = rn_split(ctx, cf, N, c3, M, s);
+    return r;
+  };
+  if ((rc = acx_resnet_stem_im2col(ctx, frames, ws.cols, n, g.R, s))) return rc;
+  if ((rc = rn_gemm(ctx, ws.cols, 32, w->stem[0].w, c1, 32, ws.t1, c1, M1, w->stem[0].b, ACX_ACT_RELU, nullptr, 0, 0, 0, s))) return rc;
+  if ((rc = rn_split(ctx, ws.t1, c1, ws.pl0, M1, s))) return rc;
+  if ((rc = prod(ws.t1, ws.pl0, c1, w->stem[1], c1, 9 * c1, ws.t2, ws.pl1, M1, ACX_ACT_RELU, nullptr, G, c1))) return rc;
+  if ((rc = prod(ws.t2, ws.pl1, c1, w->stem[2], c2, 9 * c1, ws.t1, nullptr, M1, ACX_ACT_RELU, nullptr, G, c1))) return rc;
+  if ((rc = acx_avgpool2_nhwc(ctx, ws.t1, ws.x, n, G, G, c2, s))) return rc;
+  int H = G / 2, inpl = g.w, bi = 0;
+  for (int li = 0; li < 4; ++li) {
+    const int planes = g.w << li, pp = rn_cp(planes), cin = rn_cp(inpl), cout = 4 * planes;
+    for (int j = 0; j < d->layers[li]; ++j, ++bi) {
+      const acx_resnet_block& b = w->blocks[bi];
+      const bool stride = li > 0 && j == 0;
+      const int cin_b = j == 0 ? cin : cout;
+      const int64_t M = (int64_t)n * H * H;
+      const int Ho = stride ? H / 2 : H;
+      const int64_t Mo = (int64_t)n * Ho * Ho;
+      const bool r1 = rn_routed(cin_b, pp, false), r3 = rn_routed(pp, cout, false);
+      const bool rds = b.downsample.w && rn_routed(cin_b, cout, false);
+      // the block input's planes: conv1's A, and the downsample's in a block without stride
+      if (r1 || (rds && !stride)) { if ((rc = rn_split(ctx, ws.x, cin_b, ws.pl0, M, s))) return rc; }
+      if ((rc = prod(ws.x, ws.pl0, cin_b, b.conv1, pp, cin_b, ws.t1, ws.pl1, M, ACX_ACT_RELU, nullptr, 0, 0))) return rc;
+      // conv2: planes for conv3 directly, or f32 rows for the average pool of a block with stride
+      const bool direct = !stride && r3;
+      if ((rc = prod(ws.t1, ws.pl1, pp, b.conv2, pp, 9 * pp, ws.t2, direct ? ws.pl2 : nullptr, M, ACX_ACT_RELU, nullptr, H, pp))) return rc;
+      const float* a3f = ws.t2;
+      const void* a3p = ws.pl2;
+      const float* xin = ws.x;
+      const void* xinp = ws.pl0;
+      if (stride) {                                              // avgpool(stride) of the branch and of the identity's input
+        if ((rc = acx_avgpool2_nhwc(ctx, ws.t2, ws.t1, n, H, H, pp, s))) return rc;
+        if ((rc = acx_avgpool2_nhwc(ctx, ws.x, ws.p, n, H, H, cin_b, s))) return rc;
+        a3f = ws.t1; xin = ws.p;
+        if (r3) { if ((rc = rn_split(ctx, ws.t1, pp, ws.pl1, Mo, s))) return rc; }
+        a3p = ws.pl1;
+        if (rds) { if ((rc = rn_split(ctx, ws.p, cin_b, ws.pl0, Mo, s))) return rc; }
+      } else if (!r3) {
+        a3p = nullptr;
+      }
+      const float* ident = ws.x;
+      if (b.downsample.w) {
+        if ((rc = prod(xin, xinp, cin_b, b.downsample, cout, cin_b, ws.ds, nullptr, Mo, ACX_ACT_NONE, nullptr, 0, 0))) return rc;
+        ident = ws.ds;
+      } else if (stride || cin_b != cout) {
+        return acx_fail(ctx, ACX_E_BADARG, "acx_resnet_encode: a block that changes shape needs downsample weights%s");
+      }
+      if ((rc = prod(a3f, a3p, pp, b.conv3, cout, pp, ws.x, nullptr, Mo, ACX_ACT_RESRELU, ident, 0, 0))) return rc;
+      H = Ho;
+    }
+    inpl = 4 * planes;
+  }
+  return rn_attnpool(ctx, w, g, ws, ws.x, n, features, s, true);
+}
+
 int rn_check(acx_ctx* ctx, const acx_resnet_desc* d) {
   // width % 8: every block's 4 * planes output (and so the next block's input) is a multiple of 32 channels, unpadded
   if (d->resolution <= 0 || d->resolution % 32 || d->width <= 0 || d->width % 8 || d->output_dim <= 0 || d->output_dim % 4)
@@ -321,8 +445,9 @@ int rn_check(acx_ctx* ctx, const acx_resnet_desc* d) {
   if (d->width * 32 != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_resnet_encode: head dim must be 64 (heads = width / 2)%s");
   const int Hf = d->resolution / 32;
   if (Hf * Hf + 1 > 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_resnet_encode: more than 1024 attention-pool tokens%s");
-  if (d->prec != ACX_PREC_F32 && d->prec != ACX_PREC_F32X6)
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_resnet_encode: ACX_PREC_F32 / ACX_PREC_F32X6 only%s");
+  // (the training-mode pass takes the same values and runs the f32 kernels for all of them)
+  if (d->prec != ACX_PREC_F32 && d->prec != ACX_PREC_F32X6 && d->prec != ACX_PREC_BF16X6)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_resnet_encode: ACX_PREC_F32 / ACX_PREC_F32X6 / ACX_PREC_BF16X6 only%s");
   return ACX_OK;
 }
 
@@ -332,7 +457,7 @@ extern "C" size_t acx_resnet_workspace_bytes(const acx_resnet_desc* d, int32_t f
   if (!d || frames <= 0 || rn_check(nullptr, d)) return 0;
   const RnGeom g = rn_geom(d);
   const int fb = rn_batch(g);
-  return rn_carve(nullptr, g, frames < fb ? frames : fb).total;
+  return rn_carve(nullptr, g, frames < fb ? frames : fb, d->prec == ACX_PREC_BF16X6).total;
 }
 
 extern "C" int acx_resnet_encode(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const float* frames,
@@ -347,13 +472,20 @@ extern "C" int acx_resnet_encode(acx_ctx* ctx, const acx_resnet_desc* d, const a
   // batches of (nearly) equal size: ceil(nframes / fb) of them
   const int nb = (nframes + fb - 1) / fb;
   const int per = (nframes + nb - 1) / nb;
-  const RnWs ws = rn_carve((char*)workspace, g, per);
+  const bool x6 = d->prec == ACX_PREC_BF16X6;
+  const RnWs ws = rn_carve((char*)workspace, g, per, x6);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_resnet_encode: workspace too small (acx_resnet_workspace_bytes)%s");
+  if (x6) {                                                      // the workspace is the caller's and holds anything: the zero page, every call
+    if (((uintptr_t)workspace & 15)) return acx_fail(ctx, ACX_E_BADARG, "acx_resnet_encode: ACX_PREC_BF16X6 needs a 16-byte aligned workspace%s");
+    if (hipMemsetAsync(ws.zero, 0, 256, (hipStream_t)stream) != hipSuccess)
+      return acx_fail(ctx, ACX_E_HIP, "acx_resnet_encode: clearing the zero page failed%s");
+  }
   const int64_t fstride = (int64_t)3 * g.R * g.R;
   for (int f0 = 0; f0 < nframes; f0 += per) {
     const int n = nframes - f0 < per ? nframes - f0 : per;
-    if ((rc = rn_encode_batch(ctx, d, w, g, ws, frames + f0 * fstride, n, features + (int64_t)f0 * g.out, (hipStream_t)stream)))
-      return rc;
+    rc = x6 ? rn_encode_batch_x6(ctx, d, w, g, ws, frames + f0 * fstride, n, features + (int64_t)f0 * g.out, (hipStream_t)stream)
+            : rn_encode_batch(ctx, d, w, g, ws, frames + f0 * fstride, n, features + (int64_t)f0 * g.out, (hipStream_t)stream);
+    if (rc) return rc;
   }
   return ACX_OK;
 }
@@ -374,7 +506,7 @@ struct RnTrainWs {
 
 RnTrainWs rn_carve_train(char* base, const RnGeom& g, int F) {
   RnTrainWs t;
-  t.b = rn_carve(base, g, F);
+  t.b = rn_carve(base, g, F, false);
   size_t off = t.b.total;
   const int cmax = g.E;                                          // widest BatchNorm: layer4's 4 * 8 width = 32 width
   auto take = [&](size_t bytes) { char* p = base + off; off += rn_al(bytes); return p; };

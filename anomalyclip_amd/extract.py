@@ -354,6 +354,7 @@ def load_encoder_weights(encoder, arch: str, weights) -> None:
 def _parser():
     import argparse
     from .components.anomaly_clip import _ARCH
+    from .components.clip_resnet import RESNET_PRECISIONS
     from .components.clip_vit import PRECISIONS
     p = argparse.ArgumentParser(prog="python -m anomalyclip_amd.extract", description="CLIP feature files from frame folders")
     p.add_argument("--arch", required=True, choices=sorted(_ARCH))
@@ -363,7 +364,7 @@ def _parser():
     p.add_argument("--annotations", default=None, help="rows `path start end label...`; default: every folder of --frames-root")
     p.add_argument("--ncrops", type=int, default=1, choices=(1, 5, 10))
     p.add_argument("--scale-size", type=int, default=None, help="shorter side before cropping (default: crop, or crop * 8 // 7)")
-    p.add_argument("--precision", default="auto", choices=sorted(PRECISIONS))
+    p.add_argument("--precision", default="auto", choices=sorted(set(PRECISIONS) | set(RESNET_PRECISIONS)))
     p.add_argument("--overwrite", action="store_true")
     p.add_argument("--decode", default="pil", choices=("pil", "gpu", "gpu_entropy"),
                    help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device; "

@@ -64,13 +64,19 @@ enum { ACX_PREC_F32 = 0, ACX_PREC_BF16 = 1,          /* MFMA arithmetic: exact f
        ACX_PREC_F32X6 = 2 };  /* acx_vit_encode / acx_transformer_forward only: f32 everywhere, the four large GEMMs of a layer as
                                  f32-accurate bf16 x 6 products (acx_gemm_desc.pairs); the *_w_bf16 weight fields then hold THREE
                                  planes each (acx_split_bf16x3 of the f32 weight) */
+enum { ACX_PREC_BF16X6 = 5 }; /* acx_resnet_encode only: the ResNet encoder's products as pairs = 6 products of bf16 planes (f32-accurate:
+                                 the arithmetic ACX_PREC_F32X6 names in the ViT drivers).  A value of its own because ACX_PREC_F32X6 in
+                                 acx_resnet_desc.prec means -- and keeps meaning -- the f32 MFMA kernels.  Opt-in (precision "bf16x6") */
 #define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
 enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
        ACX_ACT_RELU = 3,      /* max(x, 0) in the activation slot (clip/model.py:18-22,122-130 ReLU after a folded BatchNorm) */
        ACX_ACT_RESRELU = 4 }; /* ReLU AFTER the residual add: C = max(residual + (acc + bias), 0) (clip/model.py:62-64, Bottleneck's
                                  `out += identity; relu3`); needs `residual`.  Both: f32 products (prec ACX_PREC_F32, pairs <= 1) on
-                                 the identity or CONV3X3 row maps, no a_sub / positional epilogue; ACX_E_UNSUPPORTED otherwise */
+                                 the identity or CONV3X3 row maps, no a_sub / positional epilogue; and pairs = 6 products: RELU on
+                                 identity or CONV3X3 rows to f32 or plane output (ACX_BF16X3[P]: the planes of the value AFTER the
+                                 ReLU), without a residual; RESRELU on identity rows to f32 output (whole tiles, no K split: both).
+                                 pairs = 3 takes neither; ACX_E_UNSUPPORTED otherwise */
 enum { ACX_AMAP_IDENTITY = 0, ACX_AMAP_CONV3X3 = 1, ACX_AMAP_TESTTILE = 2, ACX_AMAP_TILETABLE = 3 };
 enum { ACX_NORM_LAYER = 0, ACX_NORM_CHAN = 1 };     /* nn.LayerNorm vs axial_attention ChanLayerNorm (eps added to std) */
 
@@ -190,10 +196,14 @@ typedef struct acx_gemm_desc {
                              three dropped terms and the split remainders are <= 2^-23 of the product: the error is that of an
                              f32 dot product, at 6/16 of the f32 MFMA's cost (2.5 PFLOP/s bf16 against 157 TFLOP/s f32 on gfx950).
                              Kernel: gemm_x6_p4_kernel (csrc/acx_gemm_x6.h).  K % 32 == 0, N % 4 == 0, 16-byte aligned planes; row
-                             maps IDENTITY and CONV3X3 (power-of-two grid, cin % 32 == 0, M % 256 == 0, zero_page); epilogues bias,
-                             QuickGELU / LeakyReLU, residual (f32 C), c_dtype ACX_F32 / ACX_BF16 / ACX_BF16X3[P] (plane output:
-                             N % 8 == 0, no residual).  With `workspace`, launches of fewer output tiles than CUs split K across
-                             workgroups (fixed split per shape; partial tiles + the generic reduce launch).
+                             maps IDENTITY and CONV3X3 (cin % 32 == 0, zero_page, an A plane below 4 GiB); epilogues bias,
+                             QuickGELU / LeakyReLU / ReLU, residual (f32 C), c_dtype ACX_F32 / ACX_BF16 / ACX_BF16X3[P] (plane output:
+                             N % 8 == 0, no residual).  CONV3X3 on a power-of-two (gn, gl) grid with M % 256 == 0 takes every one of
+                             these; on ANY other grid or row count (gn, gl >= 1, M % (gn gl) == 0: a 256-row tile may straddle frames
+                             and end behind M) the row map works by division and the epilogues are bias / ReLU to f32 and ReLU to
+                             planes, without a residual or a K split.  With `workspace`, launches of fewer output tiles than CUs
+                             split K across workgroups (fixed split per shape; partial tiles + the generic reduce launch) -- except
+                             the ReLU epilogues and the general convolution map, which never split (acx_gemm_scratch answers 0).
                              3: the same planes and kernel with the THREE leading products only -- (mid,hi) (hi,mid) (hi,hi); the lo
                              planes are never read.  The dropped terms are <= 2^-16 of the leading one: NOT f32-accurate (about 1e-5 of
                              sum |a||w|).  Identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues. */
@@ -374,6 +384,9 @@ int acx_attnpool_tokens(acx_ctx* ctx, const float* x, const float* pos, float* t
 typedef struct acx_resnet_conv {
   const float* w;
   const float* b;
+  const void* w3;                           /* ACX_PREC_BF16X6: the three bf16 planes of w (acx_split_bf16x3: [3][Cout_p][K], plane stride
+                                               Cout_p * K * 2 bytes) for every convolution the driver routes to the plane kernel -- every
+                                               3x3, and every 1x1 with K >= 64 (not the stem's first); NULL / not read otherwise */
 } acx_resnet_conv;
 typedef struct acx_resnet_block {           /* Bottleneck (clip/model.py:10-68) */
   acx_resnet_conv conv1, conv2, conv3;
@@ -386,16 +399,22 @@ typedef struct acx_resnet_weights {
   const float *q_w, *q_b;                   /* q_proj [E, E], [E] */
   const float *kv_w, *kv_b;                 /* k_proj | v_proj stacked: [2E, E], [2E] */
   const float *c_w, *c_b;                   /* c_proj [output_dim, E], [output_dim] */
+  const void* kv_w3;                        /* ACX_PREC_BF16X6: the three bf16 planes of kv_w ([3][2E][E]); not read otherwise */
 } acx_resnet_weights;
 typedef struct acx_resnet_desc {
   int32_t resolution, width;
   int32_t layers[4];
   int32_t heads, output_dim;                /* heads = width * 32 / 64 (clip/model.py:314) */
-  int32_t prec;                             /* ACX_PREC_F32 or ACX_PREC_F32X6: both run the f32 MFMA kernels */
+  int32_t prec;                             /* ACX_PREC_F32 or ACX_PREC_F32X6: both run the f32 MFMA kernels; ACX_PREC_BF16X6: the plane
+                                               kernel for every product but the K = 32 stem product and the one-row-per-frame q / c_proj */
 } acx_resnet_desc;
 /* acx_resnet_encode: ModifiedResNet.forward in eval mode (clip/model.py:156-171): frames [F,3,R,R] f32 -> features
  * [F, output_dim] f32.  The frames run in internal batches whose largest activation stays below 2^31 bytes; workspace from
- * acx_resnet_workspace_bytes(desc, F) (0: the geometry is not supported).  R % 32 == 0, heads * 64 == 32 * width. */
+ * acx_resnet_workspace_bytes(desc, F) (0: the geometry is not supported).  R % 32 == 0, heads * 64 == 32 * width.
+ * ACX_PREC_BF16X6: the products run as pairs = 6 products of bf16 planes -- which ones is a rule on (K, N, convolution or not) alone,
+ * never on the frame count, so identical frames give bit-identical rows wherever they sit; a product whose only consumer is the next
+ * product writes its planes directly, an f32 result that feeds a product is split by acx_split_bf16x3.  The workspace (16-byte
+ * aligned) is larger by three plane buffers and a 256-byte zero page, which every call clears on its stream. */
 size_t acx_resnet_workspace_bytes(const acx_resnet_desc* d, int32_t frames);
 int acx_resnet_encode(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const float* frames, int32_t nframes,
                       float* features, void* workspace, size_t workspace_bytes, void* stream);
@@ -425,7 +444,8 @@ int acx_bn_apply_nhwc(acx_ctx* ctx, const float* x, const float* mean, const flo
 /* acx_resnet_encode_train: ModifiedResNet.forward with its BatchNorms in training mode (clip/model.py:156-171), layer by layer over
  * all F frames of the call (acx_bn_stats over each convolution's F * H * W rows).  w: the UNFOLDED convolution weights in the layouts
  * of acx_resnet_conv (the b fields are not read) and the attention pool; bn: every BatchNorm's parameters and buffers, which are
- * updated in place.  Workspace from acx_resnet_train_workspace_bytes(desc, F): every activation of all F frames. */
+ * updated in place.  Workspace from acx_resnet_train_workspace_bytes(desc, F): every activation of all F frames.
+ * A correctness path: it runs the f32 MFMA kernels for EVERY value of desc->prec, ACX_PREC_BF16X6 included (w3 / kv_w3 are not read). */
 size_t acx_resnet_train_workspace_bytes(const acx_resnet_desc* d, int32_t frames);
 int acx_resnet_encode_train(acx_ctx* ctx, const acx_resnet_desc* d, const acx_resnet_weights* w, const acx_resnet_train_bn* bn,
                             const float* frames, int32_t F, float* features, void* workspace, size_t workspace_bytes, void* stream);

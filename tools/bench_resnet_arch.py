@@ -2,12 +2,15 @@
 kernel times.
 
     python tools/bench_resnet_arch.py --arch RN50 --precision auto --frames 512 [--steps 5 --warmup 2]
+    python tools/bench_resnet_arch.py --arch RN50 --precision f32,bf16x6 --reps 2 --frames 512     (A/B in one process)
 
 One call of `--frames` frames (seeded random weights and frames) is timed with HIP events after the warm-up; a separate profiled
 pass (acx_prof_*: HIP-event pairs around every kernel, summed by kind) gives GEMM / attention / other times.  `gmac_per_frame`
 counts the multiply-adds of every convolution (unpadded channels), the attention pool's projections and its attention, from the
 shapes; `gemm_tflops` is what the profiled GEMMs executed (padded channels included) over their time, against the f32 MFMA roof
-(157.3 TFLOP/s: "auto" runs the f32 kernels for the ResNets).  Prints one JSON line."""
+(157.3 TFLOP/s: "auto" runs the f32 kernels for the ResNets; "bf16x6" runs most products on the bf16 matrix cores, so its fraction
+of that roof can exceed 1).  `--precision a,b --reps R`: the precisions ALTERNATE on one module in one process (a b a b ...), R
+repetitions each.  Prints one JSON line per measurement."""
 import argparse
 import ctypes
 import json
@@ -48,20 +51,34 @@ def macs_per_frame(g):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="RN50", choices=["RN50", "RN101", "RN50x4", "RN50x16", "RN50x64"])
-    ap.add_argument("--precision", default="auto", choices=["auto", "f32"])
+    ap.add_argument("--precision", default="auto", help="auto, f32 or bf16x6; two or more separated by commas alternate in this process")
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of every precision")
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     a = ap.parse_args()
+    precisions = a.precision.split(",")
+    for p in precisions:
+        if p not in ("auto", "f32", "bf16x6"):
+            ap.error(f"--precision {p}: one of auto, f32, bf16x6")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     g = geometry_of_arch(a.arch)
     with torch.device(dev):
         m = ModifiedResNet(g.vision_layers, g.embed_dim, g.resnet_heads, g.image_resolution, g.vision_width,
-                           precision=a.precision, chunk=a.frames, arch=a.arch)
+                           precision=precisions[0], chunk=a.frames, arch=a.arch)
     m.load_state_dict(IW.init_resnet_state_dict(g, 0, prefix=""), strict=True)
     m.eval()
     x = torch.randn(a.frames, 3, g.image_resolution, g.image_resolution, generator=torch.Generator().manual_seed(1)).to(dev)
+    for rep in range(a.reps):
+        for p in precisions:
+            m.precision = p
+            res = measure(a, g, m, x)
+            res["precision"], res["rep"] = p, rep
+            print(json.dumps(res), flush=True)
+
+
+def measure(a, g, m, x):
     t0 = time.time()
     for _ in range(a.warmup):
         m(x)
@@ -86,7 +103,7 @@ def main():
     kt = {k: round(tot[i], 3) for i, k in enumerate(kinds)}
     gemm_tflops = gf.value / 1e9 / tot[0] if tot[0] > 0 else None
     macs = macs_per_frame(g)
-    res = {"arch": a.arch, "precision": a.precision, "frames": a.frames, "steps": a.steps, "warmup": a.warmup, "frames_per_s": round(a.frames / (ms / 1e3), 1),
+    res = {"arch": a.arch, "precision": m.precision, "frames": a.frames, "steps": a.steps, "warmup": a.warmup, "frames_per_s": round(a.frames / (ms / 1e3), 1),
            "ms_per_call": round(ms, 3), "gmac_per_frame": round(macs / 1e9, 2),
            "model_tflops": round(2 * macs * a.frames / (ms / 1e3) / 1e12, 1),
            "kernel_ms": {"gemm": kt["gemm"], "attention": kt["attention"], "other": round(kt["norm"] + kt["other"], 3)},
@@ -94,7 +111,7 @@ def main():
            "gemm_tflops": round(gemm_tflops, 1) if gemm_tflops else None, "gemm_roof_tflops": F32_ROOF_TFLOPS,
            "gemm_frac_of_roof": round(gemm_tflops / F32_ROOF_TFLOPS, 4) if gemm_tflops else None,
            "finite": bool(torch.isfinite(out).all()), "wall_s": round(time.time() - t0, 1)}
-    print(json.dumps(res))
+    return res
 
 
 if __name__ == "__main__":
