@@ -22,6 +22,10 @@ OPT_X6_STRIP_TAIL, OPT_X6_MIN_TILES, OPT_LN_RIDER, OPT_ATTN_F32IN, OPT_CLS_FOLD 
 ACX_F64, ACX_I64 = 16, 17                              # element types of the collectives only (acx_allreduce / acx_allgather)
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 COMM_ID_BYTES = 128
+# acx_seq_attention_bwd_route / acx_axial_attention_route: the kernel route a shape takes (include/acx.h ACX_SAB_ROUTE_* / ACX_AXF_ROUTE_*)
+SAB_ROUTE_UNSUPPORTED, SAB_ROUTE_TEXT_MFMA, SAB_ROUTE_TEXT_BLOCK, SAB_ROUTE_TEXT_ROWS = 0, 1, 2, 3
+SAB_ROUTE_AXIAL_MFMA, SAB_ROUTE_AXIAL_MFMA_PADDED, SAB_ROUTE_GENERIC = 4, 5, 6
+AXF_ROUTE_UNSUPPORTED, AXF_ROUTE_PADDED_MFMA, AXF_ROUTE_EXACT_MFMA, AXF_ROUTE_THREAD_PER_ROW = 0, 1, 2, 3
 
 
 class GemmDesc(C.Structure):
@@ -202,6 +206,7 @@ _SIGS = {
                                   c_float, c_void_p]),
     "acx_axial_attention": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, c_void_p]),
+    "acx_axial_attention_route": (C.c_int, [c_void_p] + [c_int32] * 6),
     "acx_cls_head": (C.c_int, [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "acx_cls_head_tiles": (C.c_int, [c_void_p] * 8 + [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acx_class_probs": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
@@ -225,6 +230,7 @@ _SIGS = {
     "acx_transpose": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "acx_conv_weight_dx": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "acx_seq_attention_bwd": (C.c_int, [c_void_p] * 4 + [c_int32] * 7 + [c_void_p, c_void_p]),
+    "acx_seq_attention_bwd_route": (C.c_int, [c_void_p] + [c_int32] * 8),
     "acx_pos_grad": (C.c_int, [c_void_p] * 5 + [c_int32] * 4 + [c_void_p]),
     "acx_bn_bwd_stats": (C.c_int, [c_void_p] * 4 + [c_int64, c_int32, c_void_p, c_size_t, c_void_p]),
     "acx_bn_bwd_apply": (C.c_int, [c_void_p] * 6 + [c_int32, c_int64, c_int64, c_int32, c_float, c_void_p, c_void_p]),

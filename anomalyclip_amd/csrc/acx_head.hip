@@ -1205,6 +1205,18 @@ __global__ __launch_bounds__(256) void axial_attn_fwd_pad_kernel(const float* __
   }
 }
 
+// The dispatch rule of acx_axial_attention, first match wins; the dispatcher below switches on this answer.
+extern "C" int acx_axial_attention_route(const acx_ctx* ctx, int32_t gn, int32_t gl, int32_t heads, int32_t e, int32_t axis,
+                                         int32_t aligned) {
+  (void)ctx;
+  const int T = axis == 0 ? gn : gl;
+  if (gn <= 0 || gl <= 0 || T > 128 || (e != 16 && e != 32 && e != 64) || heads <= 0) return ACX_AXF_ROUTE_UNSUPPORTED;
+  if (!((T == 16 || T == 32) && (e == 16 || e == 32))) return ACX_AXF_ROUTE_PADDED_MFMA;      // (refuses a misaligned call)
+  if (aligned) return ACX_AXF_ROUTE_EXACT_MFMA;
+  if (256 % (T * heads)) return ACX_AXF_ROUTE_UNSUPPORTED;
+  return ACX_AXF_ROUTE_THREAD_PER_ROW;
+}
+
 extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, int32_t tiles, int32_t gn, int32_t gl,
                                    int32_t heads, int32_t e, int32_t axis, void* stream) {
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
@@ -1212,10 +1224,10 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
   if (tiles <= 0) return ACX_OK;
   const int T = axis == 0 ? gn : gl;
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
-  if (gn <= 0 || gl <= 0 || T > 128 || (e != 16 && e != 32 && e != 64) || heads <= 0)
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_axial_attention: need 1 <= axis length <= 128, e in {16,32,64}, heads >= 1%s");
-  if (!((T == 16 || T == 32) && (e == 16 || e == 32))) {
-    if (((uintptr_t)qkv | (uintptr_t)out) & 15) return acx_fail(ctx, ACX_E_BADARG, "acx_axial_attention: qkv / out must be 16-byte aligned%s");
+  const bool aligned = !(((uintptr_t)qkv | (uintptr_t)out) & 15);
+  switch (acx_axial_attention_route(ctx, gn, gl, heads, e, axis, aligned)) {
+  case ACX_AXF_ROUTE_PADDED_MFMA: {
+    if (!aligned) return acx_fail(ctx, ACX_E_BADARG, "acx_axial_attention: qkv / out must be 16-byte aligned%s");
     const int64_t ngroups = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
     const int tt = (T + 15) / 16;
     const int G = tt == 1 ? 4 : tt == 2 ? 2 : 1;
@@ -1235,7 +1247,7 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
     ACX_CHECK_LAUNCH(ctx, "acx_axial_attention(padded mfma)");
     return ACX_OK;
   }
-  if ((T == 16 || T == 32) && (e == 16 || e == 32) && heads > 0 && !(((uintptr_t)qkv | (uintptr_t)out) & 15)) {
+  case ACX_AXF_ROUTE_EXACT_MFMA: {
     const int64_t ngroups = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
     const size_t ldsm = (size_t)4 * 3 * T * (e + 4) * sizeof(float);
     int64_t nbm = (ngroups + 3) / 4;
@@ -1252,21 +1264,26 @@ extern "C" int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, i
     ACX_CHECK_LAUNCH(ctx, "acx_axial_attention(mfma)");
     return ACX_OK;
   }
-  if ((T != 16 && T != 32) || (e != 16 && e != 32) || heads <= 0 || 256 % (T * heads))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_axial_attention: need axis length in {16,32}, e in {16,32}, T*heads | 256%s");
-  const int lpb = 256 / (T * heads);
-  const int64_t nlines = (int64_t)tiles * (axis == 0 ? gl : gn);
-  const size_t lds = (size_t)lpb * T * heads * e * 2 * 4;
-  const dim3 grid((unsigned)((nlines + lpb - 1) / lpb)), block(256);
-  hipStream_t s = (hipStream_t)stream;
+  case ACX_AXF_ROUTE_THREAD_PER_ROW: {
+    const int lpb = 256 / (T * heads);
+    const int64_t nlines = (int64_t)tiles * (axis == 0 ? gl : gn);
+    const size_t lds = (size_t)lpb * T * heads * e * 2 * 4;
+    const dim3 grid((unsigned)((nlines + lpb - 1) / lpb)), block(256);
+    hipStream_t s = (hipStream_t)stream;
 #define ACX_AX(TT, EE) acx_launch_lds<axial_attn_kernel<TT, EE>>(dev_slot, grid, block, lds, s, qkv, out, tiles, gn, gl, heads, axis, nlines)
-  if (T == 32 && e == 32) ACX_AX(32, 32);
-  else if (T == 32) ACX_AX(32, 16);
-  else if (e == 32) ACX_AX(16, 32);
-  else ACX_AX(16, 16);
+    if (T == 32 && e == 32) ACX_AX(32, 32);
+    else if (T == 32) ACX_AX(32, 16);
+    else if (e == 32) ACX_AX(16, 32);
+    else ACX_AX(16, 16);
 #undef ACX_AX
-  ACX_CHECK_LAUNCH(ctx, "acx_axial_attention");
-  return ACX_OK;
+    ACX_CHECK_LAUNCH(ctx, "acx_axial_attention");
+    return ACX_OK;
+  }
+  default:
+    return acx_fail(ctx, ACX_E_UNSUPPORTED,
+                    "acx_axial_attention: need 1 <= axis length <= 128, e in {16,32,64}, heads >= 1; with a misaligned qkv / out, "
+                    "axis length in {16,32}, e in {16,32}, T*heads | 256%s");
+  }
 }
 
 extern "C" int acx_class_probs(acx_ctx* ctx, const float* sim, const float* scores, float* probs, int64_t rows,

@@ -1911,14 +1911,40 @@ extern "C" int acx_conv_weight_dx(acx_ctx* ctx, const float* w, float* out, int3
   return ACX_OK;
 }
 
+// groups per workgroup of seq_attn_bwd_kernel: 256 / T (one thread per (group, row)), fewer while K, V / Q, dO and the three
+// statistics of the groups exceed 96 KB of LDS
+static inline int sab_generic_gpb(int T, int e) {
+  int gpb = 256 / T;
+  while (gpb > 1 && (size_t)gpb * T * (2 * e + 3) * 4 > 96 * 1024) --gpb;
+  return gpb;
+}
+
+// The dispatch rule of acx_seq_attention_bwd, first match wins; the dispatcher below switches on this answer.
+extern "C" int acx_seq_attention_bwd_route(const acx_ctx* ctx, int32_t tiles, int32_t gn, int32_t gl, int32_t heads, int32_t e,
+                                           int32_t axis, int32_t causal, int32_t has_stats) {
+  (void)ctx; (void)tiles; (void)heads;
+  const int T = axis == 0 ? gn : gl;
+  const bool text = e == 64 && gn == 1 && axis == 1;          // the text tower's (batch, 1, L) grid
+  const bool sab_rows = ACX_DBG_SWITCH("SAB_ROWS", false);    // keep the two-launch rows kernel (A/B, debug builds)
+  if (text && T <= AB_TP && !sab_rows && ACX_DBG_SWITCH("SAB_MFMA", true)) return ACX_SAB_ROUTE_TEXT_MFMA;
+  if (text && T <= 128 && !sab_rows) return ACX_SAB_ROUTE_TEXT_BLOCK;
+  if (text && T <= 256 && has_stats) return ACX_SAB_ROUTE_TEXT_ROWS;
+  const bool axb = !causal && (e == 16 || e == 32) && ACX_DBG_SWITCH("AXB_MFMA", true);
+  if (axb && (T == 16 || T == 32)) return ACX_SAB_ROUTE_AXIAL_MFMA;
+  if (axb && T >= 1 && T <= 64) return ACX_SAB_ROUTE_AXIAL_MFMA_PADDED;
+  if (T <= 0 || T > 256 || (e != 16 && e != 32 && e != 64)) return ACX_SAB_ROUTE_UNSUPPORTED;
+  if ((size_t)sab_generic_gpb(T, e) * T * (2 * e + 3) * 4 > 160 * 1024) return ACX_SAB_ROUTE_UNSUPPORTED;
+  return ACX_SAB_ROUTE_GENERIC;
+}
+
 extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int32_t tiles, int32_t gn,
                                      int32_t gl, int32_t heads, int32_t e, int32_t axis, int32_t causal, float* stats_ws, void* stream) {
   if (!qkv || !dout || !dqkv) return acx_fail(ctx, ACX_E_BADARG, "acx_seq_attention_bwd: null pointer%s");
   if (tiles <= 0) return ACX_OK;
   const int T = axis == 0 ? gn : gl;
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
-  const bool sab_rows = ACX_DBG_SWITCH("SAB_ROWS", false);    // keep the two-launch rows kernel (A/B, debug builds)
-  if (e == 64 && gn == 1 && axis == 1 && T <= AB_TP && !sab_rows && ACX_DBG_SWITCH("SAB_MFMA", true)) {
+  switch (acx_seq_attention_bwd_route(ctx, tiles, gn, gl, heads, e, axis, causal, stats_ws != nullptr)) {
+  case ACX_SAB_ROUTE_TEXT_MFMA: {
     // text-tower shape up to 80 tokens: the five products on the f32 MFMA, one workgroup per (sequence, head)
     hipStream_t s4 = (hipStream_t)stream;
     AcxProfScope prof4__(ctx, ACX_K_ATTN, s4);
@@ -1927,7 +1953,7 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(mfma)");
     return ACX_OK;
   }
-  if (e == 64 && gn == 1 && axis == 1 && T <= 128 && !sab_rows) {
+  case ACX_SAB_ROUTE_TEXT_BLOCK: {
     // text-tower shape: one workgroup per (sequence, head), operands staged once in LDS, both passes in one launch
     hipStream_t s3 = (hipStream_t)stream;
     AcxProfScope prof3__(ctx, ACX_K_ATTN, s3);
@@ -1938,7 +1964,7 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(block)");
     return ACX_OK;
   }
-  if (e == 64 && gn == 1 && axis == 1 && T <= 256 && stats_ws) {
+  case ACX_SAB_ROUTE_TEXT_ROWS: {
     // text-tower shape: wave-per-row kernel (two launches: rows as queries, then rows as keys)
     hipStream_t s2 = (hipStream_t)stream;
     AcxProfScope prof2__(ctx, ACX_K_ATTN, s2);
@@ -1953,7 +1979,7 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(rows)");
     return ACX_OK;
   }
-  if (!causal && (T == 16 || T == 32) && (e == 16 || e == 32) && ACX_DBG_SWITCH("AXB_MFMA", true)) {
+  case ACX_SAB_ROUTE_AXIAL_MFMA: {
     // axial attention of the temporal model: one wave per (line, head) group on the f32 MFMA
     const int64_t ngroups_m = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
     hipStream_t sm = (hipStream_t)stream;
@@ -1972,7 +1998,7 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(axial mfma)");
     return ACX_OK;
   }
-  if (!causal && T >= 1 && T <= 64 && (e == 16 || e == 32) && ACX_DBG_SWITCH("AXB_MFMA", true)) {
+  case ACX_SAB_ROUTE_AXIAL_MFMA_PADDED: {
     // every other axis length up to 64: the same kernel on the sequence padded to a multiple of 16 (PAD = true)
     const int64_t ngroups_p = (int64_t)tiles * (axis == 0 ? gl : gn) * heads;
     hipStream_t sp = (hipStream_t)stream;
@@ -1993,25 +2019,27 @@ extern "C" int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float
     ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd(axial mfma, padded)");
     return ACX_OK;
   }
-  if (T <= 0 || T > 256 || (e != 16 && e != 32 && e != 64))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_seq_attention_bwd: need 1 <= sequence <= 256, head dim in {16,32,64}%s");
-  const int64_t nlines = (int64_t)tiles * (axis == 0 ? gl : gn);
-  const int64_t ngroups = nlines * heads;
-  int gpb = 256 / T;
-  while (gpb > 1 && (size_t)gpb * T * (2 * e + 3) * 4 > 96 * 1024) --gpb;
-  const size_t lds = (size_t)gpb * T * (2 * e + 3) * 4;
-  if (lds > 160 * 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_seq_attention_bwd: sequence too long for LDS%s");
-  const float scale = 1.f / sqrtf((float)e);
-  hipStream_t s = (hipStream_t)stream;
-  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
-  const dim3 grid((unsigned)((ngroups + gpb - 1) / gpb)), block(256);
+  case ACX_SAB_ROUTE_GENERIC: {
+    const int64_t nlines = (int64_t)tiles * (axis == 0 ? gl : gn);
+    const int64_t ngroups = nlines * heads;
+    const int gpb = sab_generic_gpb(T, e);
+    const size_t lds = (size_t)gpb * T * (2 * e + 3) * 4;
+    const float scale = 1.f / sqrtf((float)e);
+    hipStream_t s = (hipStream_t)stream;
+    AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+    const dim3 grid((unsigned)((ngroups + gpb - 1) / gpb)), block(256);
 #define ACX_SAB(EE)                                                                                          \
   acx_launch_lds<seq_attn_bwd_kernel<EE>>(dev_slot, grid, block, lds, s, qkv, dout, dqkv, tiles, gn, gl, heads, axis, causal, \
                                           scale, T, gpb, ngroups)
-  if (e == 16) ACX_SAB(16); else if (e == 32) ACX_SAB(32); else ACX_SAB(64);
+    if (e == 16) ACX_SAB(16); else if (e == 32) ACX_SAB(32); else ACX_SAB(64);
 #undef ACX_SAB
-  ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd");
-  return ACX_OK;
+    ACX_CHECK_LAUNCH(ctx, "acx_seq_attention_bwd");
+    return ACX_OK;
+  }
+  default:
+    return acx_fail(ctx, ACX_E_UNSUPPORTED,
+                    "acx_seq_attention_bwd: need 1 <= sequence <= 256, head dim in {16,32,64}, a group within 160 KB of LDS%s");
+  }
 }
 
 extern "C" int acx_pos_grad(acx_ctx* ctx, const float* dx, float* d0, float* d1, float* part, int32_t tiles, int32_t gn,

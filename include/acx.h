@@ -505,6 +505,13 @@ int acx_selector_bn(acx_ctx* ctx, const float* raw, const float* mean, const flo
  * per workgroup, one query tile per wave; needs 16-byte aligned qkv / out).  Both on v_mfma_f32_16x16x4_f32. */
 int acx_axial_attention(acx_ctx* ctx, const float* qkv, float* out, int32_t tiles, int32_t gn,
                         int32_t gl, int32_t heads, int32_t e, int32_t axis, void* stream);
+/* acx_axial_attention_route: which kernel acx_axial_attention runs a shape on -- the rule the dispatcher itself switches on.
+ * Arithmetic on the arguments: no device, nothing dereferenced, ctx may be NULL.  aligned: qkv and out are both 16-byte aligned.
+ * PADDED_MFMA with aligned == 0 is the shape whose call answers ACX_E_BADARG (that kernel needs the alignment); UNSUPPORTED is
+ * the call's ACX_E_UNSUPPORTED.  THREAD_PER_ROW (one thread per (line, head, query), K / V of the block's lines in LDS) is what a
+ * misaligned T in {16, 32}, e in {16, 32} call with T * heads | 256 falls back to. */
+enum { ACX_AXF_ROUTE_UNSUPPORTED = 0, ACX_AXF_ROUTE_PADDED_MFMA = 1, ACX_AXF_ROUTE_EXACT_MFMA = 2, ACX_AXF_ROUTE_THREAD_PER_ROW = 3 };
+int acx_axial_attention_route(const acx_ctx* ctx, int32_t gn, int32_t gl, int32_t heads, int32_t e, int32_t axis, int32_t aligned);
 
 /* acx_cls_head: score = sigmoid(LayerNorm((x1+x2)/2) . w + b) (ReversibleSequence mean +
  * classification_head.py:11-15); out_index maps row ((b s) n l) back to ((b n s l)) when seg > 0
@@ -666,6 +673,19 @@ int acx_conv_weight_dx(acx_ctx* ctx, const float* w, float* out, int32_t Cout, i
 int acx_seq_attention_bwd(acx_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int32_t tiles,
                           int32_t gn, int32_t gl, int32_t heads, int32_t e, int32_t axis, int32_t causal,
                           float* stats_ws /* [rows*heads*3] floats or NULL */, void* stream);
+/* acx_seq_attention_bwd_route: which kernel acx_seq_attention_bwd runs a shape on -- the rule the dispatcher itself switches
+ * on.  Arithmetic on the arguments: no device, nothing dereferenced, ctx may be NULL.  has_stats: stats_ws is not NULL.
+ *   TEXT_MFMA          gn = 1, axis 1, e = 64, T <= 80: one workgroup per (sequence, head) on the f32 MFMA
+ *   TEXT_BLOCK         the same shape, T 81..128: operands staged once in LDS, wave per row on the VALU
+ *   TEXT_ROWS          the same shape, T 129..256, with stats_ws: wave per row from L2, two launches
+ *   AXIAL_MFMA         non-causal T in {16, 32}, e in {16, 32}: one wave per (line, head) on the f32 MFMA
+ *   AXIAL_MFMA_PADDED  non-causal every other T <= 64, e in {16, 32}: the same kernel on T rounded up to 16
+ *   GENERIC            everything else in the domain: one thread per (group, row)
+ *   UNSUPPORTED        the call's ACX_E_UNSUPPORTED */
+enum { ACX_SAB_ROUTE_UNSUPPORTED = 0, ACX_SAB_ROUTE_TEXT_MFMA = 1, ACX_SAB_ROUTE_TEXT_BLOCK = 2, ACX_SAB_ROUTE_TEXT_ROWS = 3,
+       ACX_SAB_ROUTE_AXIAL_MFMA = 4, ACX_SAB_ROUTE_AXIAL_MFMA_PADDED = 5, ACX_SAB_ROUTE_GENERIC = 6 };
+int acx_seq_attention_bwd_route(const acx_ctx* ctx, int32_t tiles, int32_t gn, int32_t gl, int32_t heads, int32_t e, int32_t axis,
+                                int32_t causal, int32_t has_stats);
 /* gradients of the axial positional embeddings (pos0 [gn,E], pos1 [gl,E]) from dx [(tile,n,l), E]; `part` is a
  * scratch buffer of tiles*gn*E + tiles*ceil(gn/4)*gl*E floats (two-stage fixed-order reduction). */
 int acx_pos_grad(acx_ctx* ctx, const float* dx, float* d0, float* d1, float* part, int32_t tiles, int32_t gn,
