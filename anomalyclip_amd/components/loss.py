@@ -1,6 +1,6 @@
 """ComputeLoss -- drop-in for the reference's `src.models.components.loss.ComputeLoss` (loss.py:20-195):
 same constructor keys (configs/model/*.yaml `loss:` block), same call signature, same 8-tuple result.
-All seven terms and their gradients are evaluated by ONE libacx kernel pass (acx_mil_loss) instead of
+All seven terms and their gradients are evaluated by ONE libacx launch (acx_mil_loss_one) instead of
 the reference's Python loop over classes with `.nonzero()` host syncs."""
 from __future__ import annotations
 

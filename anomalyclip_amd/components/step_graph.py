@@ -366,10 +366,9 @@ class TrainStepGraph:
         raw, mean, var_b, var_u = ops.selector_project_stats(x, nc, dirs)
         total_rows = rows
         bn = sel.bn_layer
-        # the forward tail (BatchNorm, running statistics, picks, gather of the top-k segments) as ONE launch per step when a
-        # video's logits fit the LDS (acx_selector_tail: bit-identical to the separate launches below, which the autograd path uses)
-        fuse_tail = ((N * Lg * C1 + N * C1 + 2 * N + 2 * C1 + sel.num_topk + sel.num_bottomk) * 4 <= 160 * 1024 and C1 <= 64
-                     and not _UNFUSED)
+        # the forward tail (BatchNorm, running statistics, picks, gather of the top-k segments) as ONE launch per step where the
+        # library takes the shape (acx_selector_tail: bit-identical to the separate launches below, which the autograd path uses)
+        fuse_tail = ops.selector_tail_fits(B, N, Lg, C1, sel.num_topk, sel.num_bottomk) and not _UNFUSED
         if dist_on:                                                      # SyncBatchNorm (configs/trainer/ddp.yaml:9)
             ops.bn_pack(mean, var_b, rows, out=self.bn_local)
             pg.eager(lambda: par.all_gather_into(self.bn_gathered, self.bn_local))
@@ -399,8 +398,9 @@ class TrainStepGraph:
                    crit.lambda_topk_nor, crit.lambda_smooth, crit.lambda_sparse)
         # loss + `meter += losses` + the scatter of the top-k rows' gradient + the BatchNorm backward sums as ONE launch
         # (acx_mil_loss_bn: bit-identical to the four separate steps) when nothing sits between the loss and the selector's backward
-        fuse_loss = (not concat and rows % 256 == 0 and rows <= 131072 and C1 <= 64 and crit.num_segments == N
-                     and crit.frames_per_segment == Lg and crit.num_topk == sel.num_topk and not _UNFUSED)
+        # and the library takes the shape
+        fuse_loss = (not concat and crit.num_segments == N and crit.frames_per_segment == Lg and crit.num_topk == sel.num_topk
+                     and not _UNFUSED and ops.mil_loss_bn_fits(B, N, Lg, C1, crit.num_topk))
         bn_sums = None
         if fuse_loss:
             losses, dsim, dsc, bn_sums = ops.mil_loss_bn(logits, logits_topk, labels, scores, ia, in_, ba, crit.num_segments,

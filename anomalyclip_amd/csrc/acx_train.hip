@@ -1384,12 +1384,12 @@ struct LossArgs {
   float l_dir_abn, l_dir_nor, l_topk_abn, l_bottomk_abn, l_topk_nor, l_smooth, l_sparse;
   const float* gout_ptr;   // device scalar: upstream gradient of the total cost (NULL -> 1)
 };
-// thread per frame row; block partial sums of the 7 terms -> part[blk][8].  PUBLISH: the partials leave as agent-scope
-// (write-through) stores for the one-launch form, whose last-arriving block adds them up (see loss_fused_kernel)
+// thread per frame row; block partial sums of the 7 terms -> part[blk][8].  The partials leave as agent-scope (write-through)
+// stores: the last-arriving block of the launch adds them up (see loss_last_block_sums)
 // FOLD (acx_mil_loss_bn): the gradient of the gathered top-k rows (loss_topk_body's dsim_topk: the constant -l_dir_abn gout / RA in the
 // own-class column of an abnormal video's top-k segments, zero elsewhere) is added to this row's dsim HERE, after the row's own terms --
 // the value and the order of acx_scatter_segments(dsim, dsim_topk, idx_topk) -- and the finished row is mirrored into sdl [256][C1] (LDS)
-template <bool PUBLISH, bool FOLD = false>
+template <bool FOLD = false>
 __device__ __forceinline__ void loss_rows_body(const LossArgs& a, const int blk, float* red, float* sdl = nullptr) {
   const int64_t R = (int64_t)a.B * a.N * a.Lg;
   const int64_t r = (int64_t)blk * 256 + threadIdx.x;
@@ -1461,18 +1461,11 @@ __device__ __forceinline__ void loss_rows_body(const LossArgs& a, const int blk,
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     const float tot = block_sum(vals[k], red);
-    if (threadIdx.x == 0) {
-      if (PUBLISH) __hip_atomic_store(a.part + (size_t)blk * 8 + k, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else a.part[(size_t)blk * 8 + k] = tot;
-    }
+    if (threadIdx.x == 0) __hip_atomic_store(a.part + (size_t)blk * 8 + k, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-__global__ __launch_bounds__(256) void loss_rows_kernel(const LossArgs a) {
-  __shared__ float red[4];
-  loss_rows_body<false>(a, (int)blockIdx.x, red);
-}
 // thread per row of sim_topk (abnormal part only contributes): ldir_abn = -mean(own-class logit)
-template <bool PUBLISH, bool FOLD = false>
+template <bool FOLD = false>
 __device__ __forceinline__ void loss_topk_body(const LossArgs& a, float* __restrict__ part2, const int blk, float* red) {
   const int64_t RT = (int64_t)a.B * a.K * a.Lg;
   const int64_t RA = (int64_t)(a.B / 2) * a.K * a.Lg;
@@ -1491,37 +1484,11 @@ __device__ __forceinline__ void loss_topk_body(const LossArgs& a, float* __restr
     }
   }
   const float tot = block_sum(t, red);
-  if (threadIdx.x == 0) {
-    if (PUBLISH) __hip_atomic_store(part2 + blk, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else part2[blk] = tot;
-  }
-}
-__global__ __launch_bounds__(256) void loss_topk_kernel(const LossArgs a, float* __restrict__ part2) {
-  __shared__ float red[4];
-  loss_topk_body<false>(a, part2, (int)blockIdx.x, red);
-}
-// final: losses[8] = (cost, ldir_abn, ldir_nor, ltopk_abn, lbottomk_abn, ltopk_nor, lsmooth, lsparse)
-__global__ void loss_final_kernel(const LossArgs a, const float* __restrict__ part, int nparts, const float* __restrict__ part2,
-                                  int nparts2, float* __restrict__ losses) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  double t[6] = {0, 0, 0, 0, 0, 0}, d = 0;
-  for (int p = 0; p < nparts; ++p)
-    for (int k = 0; k < 6; ++k) t[k] += part[(size_t)p * 8 + k];
-  for (int p = 0; p < nparts2; ++p) d += part2[p];
-  const double per = (double)a.N * a.Lg, Bh = a.B / 2, Bn = a.B - a.B / 2;
-  const float ldir_abn = (float)(-a.l_dir_abn * d / (Bh * a.K * a.Lg));
-  const float ldir_nor = (float)(a.l_dir_nor * t[0] / (Bn * per));
-  const float ltopk_abn = (float)(a.l_topk_abn * t[1] / (Bh * a.K * a.Lg));
-  const float lbot_abn = (float)(a.l_bottomk_abn * t[2] / (Bh * a.K * a.Lg));
-  const float ltopk_nor = (float)(a.l_topk_nor * t[3] / (Bn * a.K * a.Lg));
-  const float lsmooth = (float)(a.l_smooth * t[4]);
-  const float lsparse = (float)(a.l_sparse * t[5] / (Bh * per));
-  losses[1] = ldir_abn; losses[2] = ldir_nor; losses[3] = ltopk_abn; losses[4] = lbot_abn;
-  losses[5] = ltopk_nor; losses[6] = lsmooth; losses[7] = lsparse;
-  losses[0] = ldir_abn + ldir_nor + ltopk_abn + lbot_abn + ltopk_nor + lsmooth + lsparse;
+  if (threadIdx.x == 0) __hip_atomic_store(part2 + blk, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the eight loss terms from the 7 x 32 lane sums of the last arriver (thread 0): a fixed tree; meter != nullptr: meter += losses
+// losses[8] = (cost, ldir_abn, ldir_nor, ltopk_abn, lbottomk_abn, ltopk_nor, lsmooth, lsparse)
 __device__ __forceinline__ void loss_terms_from_sums(const LossArgs& a, const double (*fin)[32], float* __restrict__ losses,
                                                      float* __restrict__ meter) {
   double t[7];
@@ -1549,25 +1516,18 @@ __device__ __forceinline__ void loss_terms_from_sums(const LossArgs& a, const do
   }
 }
 
-// The three launches above as ONE: blocks [0, np1) run the frame rows, blocks [np1, np1 + np2) the top-k rows; every block
-// publishes its partial sums write-through (no release fence: a device-scope fence would write back the whole L2 of its
-// XCD), bumps a relaxed arrival counter, and the last block to arrive forms the eight loss terms: 7 x 32 lanes add the parts
-// p = lane, lane + 32, ... in f64, the 32 lane sums of a term are added in lane order -- a fixed tree.
-__global__ __launch_bounds__(256) void loss_fused_kernel(const LossArgs a, float* __restrict__ part2, int np1, int np2,
-                                                         float* __restrict__ losses, unsigned int* __restrict__ counter) {
-  __shared__ float red[4];
-  __shared__ double fin[7][32];
-  __shared__ bool last;
-  const int b = (int)blockIdx.x;
-  if (b < np1) loss_rows_body<true>(a, b, red);
-  else loss_topk_body<true>(a, part2, b - np1, red);
+// What a block of either loss kernel does after its body.  Thread 0 waits for its published partials to leave, bumps the relaxed
+// arrival counter, and every block but the last to arrive is done (false: the kernel returns).  The last one adds the parts up:
+// 7 x 32 lanes add the parts p = lane, lane + 32, ... in f64 into fin; loss_terms_from_sums adds a term's 32 lane sums in lane order.
+__device__ __forceinline__ bool loss_last_block_sums(const LossArgs& a, const float* part2, int np1, int np2, unsigned int* counter,
+                                                     bool* last, double (*fin)[32]) {
   if (threadIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ACX_HANDOFF_RELEASE();
-    last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(np1 + np2) - 1;
+    *last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(np1 + np2) - 1;
   }
   __syncthreads();
-  if (!last) return;
+  if (!*last) return false;
   ACX_HANDOFF_ACQUIRE();
   const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
   if (k < 7) {
@@ -1581,6 +1541,21 @@ __global__ __launch_bounds__(256) void loss_fused_kernel(const LossArgs a, float
     fin[k][j] = acc;
   }
   __syncthreads();
+  return true;
+}
+
+// acx_mil_loss_one: blocks [0, np1) run the frame rows, blocks [np1, np1 + np2) the top-k rows; every block publishes its
+// partial sums write-through (no release fence: a device-scope fence would write back the whole L2 of its XCD), and the last
+// block to arrive forms the eight loss terms -- a fixed tree.
+__global__ __launch_bounds__(256) void loss_fused_kernel(const LossArgs a, float* __restrict__ part2, int np1, int np2,
+                                                         float* __restrict__ losses, unsigned int* __restrict__ counter) {
+  __shared__ float red[4];
+  __shared__ double fin[7][32];
+  __shared__ bool last;
+  const int b = (int)blockIdx.x;
+  if (b < np1) loss_rows_body(a, b, red);
+  else loss_topk_body(a, part2, b - np1, red);
+  if (!loss_last_block_sums(a, part2, np1, np2, counter, &last, fin)) return;
   if (threadIdx.x != 0) return;
   loss_terms_from_sums(a, fin, losses, nullptr);
   __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1606,7 +1581,7 @@ __global__ __launch_bounds__(256) void loss_bn_kernel(const LossArgs a, float* _
   const int b = (int)blockIdx.x, C1 = a.C1;
   constexpr int CP = 64;
   if (b < np1) {
-    loss_rows_body<true, true>(a, b, red, sdl);
+    loss_rows_body<true>(a, b, red, sdl);
     __syncthreads();
     const int RL = 256 / C1;
     const int c = threadIdx.x % C1, rl = threadIdx.x / C1;
@@ -1631,30 +1606,9 @@ __global__ __launch_bounds__(256) void loss_bn_kernel(const LossArgs a, float* _
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every lane's published partials have left before the barrier below
     __syncthreads();
   } else {
-    loss_topk_body<true, true>(a, part2, b - np1, red);
+    loss_topk_body<true>(a, part2, b - np1, red);
   }
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ACX_HANDOFF_RELEASE();
-    last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(np1 + np2) - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  ACX_HANDOFF_ACQUIRE();
-  {
-    const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
-    if (k < 7) {
-      double acc = 0.0;
-      if (k < 6) {
-        for (int p = j; p < np1; p += 32)
-          acc += (double)__hip_atomic_load(a.part + (size_t)p * 8 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        for (int p = j; p < np2; p += 32) acc += (double)__hip_atomic_load(part2 + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      fin[k][j] = acc;
-    }
-  }
-  __syncthreads();
+  if (!loss_last_block_sums(a, part2, np1, np2, counter, &last, fin)) return;
   const double tot = bn_pair_total<true>(bn_part, np1, CP, C1, &redd[0][0]);
   if ((int)threadIdx.x < 2 * C1) bn_sums[threadIdx.x] = (float)tot;
   if (threadIdx.x != 0) return;
@@ -2154,28 +2108,17 @@ extern "C" int acx_scatter_segments(acx_ctx* ctx, const float* dout, const int64
   return ACX_OK;
 }
 
-extern "C" int acx_mil_loss(acx_ctx* ctx, const float* sim, const float* sim_topk, const int64_t* labels, const float* scores,
-                            const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
-                            float* dsim, float* dsim_topk, float* dscores, float* losses, float* workspace,
-                            size_t workspace_floats, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K, int32_t normal_id,
-                            const float* lambdas /* [7] */, const float* gout, void* stream) {
-  return acx_mil_loss_one(ctx, sim, sim_topk, labels, scores, idx_topk_abn, idx_topk_nor, idx_bottomk_abn, dsim, dsim_topk, dscores,
-                          losses, workspace, workspace_floats, B, N, Lg, C1, K, normal_id, lambdas, gout, nullptr, stream);
-}
-
-extern "C" int acx_mil_loss_one(acx_ctx* ctx, const float* sim, const float* sim_topk, const int64_t* labels, const float* scores,
-                                const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
-                                float* dsim, float* dsim_topk, float* dscores, float* losses, float* workspace,
-                                size_t workspace_floats, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K, int32_t normal_id,
-                                const float* lambdas /* [7] */, const float* gout, uint32_t* counter, void* stream) {
-  if (!sim || !sim_topk || !labels || !scores || !idx_topk_abn || !idx_topk_nor || !idx_bottomk_abn || !dsim || !dsim_topk ||
-      !dscores || !losses || !workspace || !lambdas)
-    return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss: null pointer%s");
-  if (B <= 0 || B % 2 || C1 > 64) return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss: need even B, C-1 <= 64%s");
-  const int64_t R = (int64_t)B * N * Lg, RT = (int64_t)B * K * Lg;
-  const int np1 = (int)((R + 255) / 256), np2 = (int)((RT + 255) / 256);
-  if ((size_t)np1 * 8 + np2 > workspace_floats) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_mil_loss: workspace too small%s");
-  LossArgs a;
+// What the two loss entry points share in front of their launch: false when one of the pointers both need is NULL; else the kernel
+// arguments from the call's (dsim_topk may be NULL: acx_mil_loss_bn folds that gradient into dsim), the block counts of the frame
+// rows (np1) and of the gathered top-k rows (np2), and the workspace they need, in floats.
+static bool loss_prepare(LossArgs& a, int& np1, int& np2, size_t& need, const float* sim, const float* sim_topk, const int64_t* labels,
+                         const float* scores, const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
+                         float* dsim, float* dsim_topk, float* dscores, const float* losses, float* workspace, int32_t B, int32_t N,
+                         int32_t Lg, int32_t C1, int32_t K, int32_t normal_id, const float* lambdas, const float* gout,
+                         const uint32_t* counter) {
+  if (!sim || !sim_topk || !labels || !scores || !idx_topk_abn || !idx_topk_nor || !idx_bottomk_abn || !dsim || !dscores || !losses ||
+      !workspace || !lambdas || !counter)
+    return false;
   a.sim = sim; a.sim_topk = sim_topk; a.labels = labels; a.scores = scores;
   a.idx_topk_abn = idx_topk_abn; a.idx_topk_nor = idx_topk_nor; a.idx_bottomk_abn = idx_bottomk_abn;
   a.dsim = dsim; a.dsim_topk = dsim_topk; a.dscores = dscores; a.part = workspace;
@@ -2183,18 +2126,40 @@ extern "C" int acx_mil_loss_one(acx_ctx* ctx, const float* sim, const float* sim
   a.l_dir_abn = lambdas[0]; a.l_dir_nor = lambdas[1]; a.l_topk_abn = lambdas[2]; a.l_bottomk_abn = lambdas[3];
   a.l_topk_nor = lambdas[4]; a.l_smooth = lambdas[5]; a.l_sparse = lambdas[6];
   a.gout_ptr = gout;
+  const int64_t R = (int64_t)B * N * Lg, RT = (int64_t)B * K * Lg;
+  np1 = (int)((R + 255) / 256);
+  np2 = (int)((RT + 255) / 256);
+  need = (size_t)np1 * 8 + np2;
+  return true;
+}
+
+extern "C" int acx_mil_loss_one(acx_ctx* ctx, const float* sim, const float* sim_topk, const int64_t* labels, const float* scores,
+                                const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
+                                float* dsim, float* dsim_topk, float* dscores, float* losses, float* workspace,
+                                size_t workspace_floats, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K, int32_t normal_id,
+                                const float* lambdas /* [7] */, const float* gout, uint32_t* counter, void* stream) {
+  LossArgs a;
+  int np1, np2;
+  size_t need;
+  if (!dsim_topk || !loss_prepare(a, np1, np2, need, sim, sim_topk, labels, scores, idx_topk_abn, idx_topk_nor, idx_bottomk_abn, dsim,
+                                  dsim_topk, dscores, losses, workspace, B, N, Lg, C1, K, normal_id, lambdas, gout, counter))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss: null pointer%s");
+  if (B <= 0 || B % 2 || C1 > 64) return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss: need even B, C-1 <= 64%s");
+  if (need > workspace_floats) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_mil_loss: workspace too small%s");
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_OTHER, s);
-  float* part2 = workspace + (size_t)np1 * 8;
-  if (counter) {
-    hipLaunchKernelGGL(loss_fused_kernel, dim3(np1 + np2), dim3(256), 0, s, a, part2, np1, np2, losses, counter);
-    ACX_CHECK_LAUNCH(ctx, "acx_mil_loss");
-    return ACX_OK;
-  }
-  hipLaunchKernelGGL(loss_rows_kernel, dim3(np1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(loss_topk_kernel, dim3(np2), dim3(256), 0, s, a, part2);
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, a, (const float*)workspace, np1, (const float*)part2, np2, losses);
+  hipLaunchKernelGGL(loss_fused_kernel, dim3(np1 + np2), dim3(256), 0, s, a, workspace + (size_t)np1 * 8, np1, np2, losses, counter);
   ACX_CHECK_LAUNCH(ctx, "acx_mil_loss");
+  return ACX_OK;
+}
+
+// The shapes acx_mil_loss_bn takes.  A block of 256 frame rows must BE the slab of acx_bn_bwd_stats' stage 1 (bn_blocks:
+// ceil(rows / 256) blocks, at most 512), and a block's [256][C-1] dlogits are mirrored in LDS.
+extern "C" int acx_mil_loss_bn_fits(const acx_ctx* ctx, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K) {
+  (void)ctx; (void)K;
+  if (B <= 0 || B % 2 || C1 <= 0 || C1 > 64) return ACX_E_BADARG;
+  const int64_t R = (int64_t)B * N * Lg;
+  if (R % 256 || R / 256 > 512) return ACX_E_UNSUPPORTED;
   return ACX_OK;
 }
 
@@ -2204,30 +2169,39 @@ extern "C" int acx_mil_loss_bn(acx_ctx* ctx, const float* sim, const float* sim_
                                size_t workspace_floats, void* bn_workspace, size_t bn_workspace_bytes, int32_t B, int32_t N, int32_t Lg,
                                int32_t C1, int32_t K, int32_t normal_id, const float* lambdas /* [7] */, const float* gout,
                                uint32_t* counter, void* stream) {
-  if (!sim || !sim_topk || !labels || !scores || !idx_topk_abn || !idx_topk_nor || !idx_bottomk_abn || !dlogits || !dscores ||
-      !losses || !bn_sums || !workspace || !bn_workspace || !lambdas || !counter)
+  LossArgs a;
+  int np1, np2;
+  size_t need;
+  if (!bn_sums || !bn_workspace || !loss_prepare(a, np1, np2, need, sim, sim_topk, labels, scores, idx_topk_abn, idx_topk_nor,
+                                                 idx_bottomk_abn, dlogits, nullptr, dscores, losses, workspace, B, N, Lg, C1, K,
+                                                 normal_id, lambdas, gout, counter))
     return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss_bn: null pointer%s");
-  if (B <= 0 || B % 2 || C1 <= 0 || C1 > 64) return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss_bn: need even B, 1 <= C-1 <= 64%s");
-  const int64_t R = (int64_t)B * N * Lg, RT = (int64_t)B * K * Lg;
-  // the block of 256 frame rows must BE the slab of acx_bn_bwd_stats' stage 1 (bn_blocks: ceil(rows / 256) blocks, at most 512)
-  if (R % 256 || R / 256 > 512) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_mil_loss_bn: B N Lg must be a multiple of 256, at most 131072 rows%s");
-  const int np1 = (int)(R / 256), np2 = (int)((RT + 255) / 256);
-  if ((size_t)np1 * 8 + np2 > workspace_floats) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_mil_loss_bn: workspace too small%s");
+  switch (acx_mil_loss_bn_fits(ctx, B, N, Lg, C1, K)) {
+  case ACX_E_BADARG: return acx_fail(ctx, ACX_E_BADARG, "acx_mil_loss_bn: need even B, 1 <= C-1 <= 64%s");
+  case ACX_E_UNSUPPORTED: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_mil_loss_bn: B N Lg must be a multiple of 256, at most 131072 rows%s");
+  }
+  if (need > workspace_floats) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_mil_loss_bn: workspace too small%s");
   if (bn_workspace_bytes < (size_t)np1 * 2 * 64 * sizeof(double) || ((uintptr_t)bn_workspace & 7))
     return acx_fail(ctx, ACX_E_WORKSPACE, "acx_mil_loss_bn: BatchNorm workspace too small (acx_bn_workspace_bytes) or misaligned%s");
-  LossArgs a;
-  a.sim = sim; a.sim_topk = sim_topk; a.labels = labels; a.scores = scores;
-  a.idx_topk_abn = idx_topk_abn; a.idx_topk_nor = idx_topk_nor; a.idx_bottomk_abn = idx_bottomk_abn;
-  a.dsim = dlogits; a.dsim_topk = nullptr; a.dscores = dscores; a.part = workspace;
-  a.B = B; a.N = N; a.Lg = Lg; a.C1 = C1; a.K = K; a.normal_id = normal_id;
-  a.l_dir_abn = lambdas[0]; a.l_dir_nor = lambdas[1]; a.l_topk_abn = lambdas[2]; a.l_bottomk_abn = lambdas[3];
-  a.l_topk_nor = lambdas[4]; a.l_smooth = lambdas[5]; a.l_sparse = lambdas[6];
-  a.gout_ptr = gout;
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_OTHER, s);
   hipLaunchKernelGGL(loss_bn_kernel, dim3(np1 + np2), dim3(256), (size_t)256 * C1 * sizeof(float), s, a, workspace + (size_t)np1 * 8, np1,
                      np2, losses, meter, (double*)bn_workspace, bn_sums, counter);
   ACX_CHECK_LAUNCH(ctx, "acx_mil_loss_bn");
+  return ACX_OK;
+}
+
+// LDS of selector_tail_kernel, in bytes: a video's logits [N Lg][C-1], its segment sums [N][C-1], the two sort keys [N], mean and
+// variance [C-1] and the ktop + kbot picks
+static inline size_t selector_tail_lds(int N, int Lg, int C1, int ktop, int kbot) {
+  return ((size_t)N * Lg * C1 + (size_t)N * C1 + 2 * (size_t)N + 2 * (size_t)C1) * 4 + (size_t)(ktop + kbot) * 4;
+}
+
+// The shapes acx_selector_tail takes: a video's logits, masks and picks within the 160 KB of a workgroup's LDS.
+extern "C" int acx_selector_tail_fits(const acx_ctx* ctx, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t ktop, int32_t kbot) {
+  (void)ctx;
+  if (B <= 0 || B % 2 || ktop > N || kbot > N || ktop < 0 || kbot < 0 || C1 <= 0 || C1 > 64) return ACX_E_BADARG;
+  if (selector_tail_lds(N, Lg, C1, ktop, kbot) > 160 * 1024) return ACX_E_UNSUPPORTED;
   return ACX_OK;
 }
 
@@ -2242,10 +2216,11 @@ extern "C" int acx_selector_tail(acx_ctx* ctx, const float* raw, const float* ga
   if (gathered ? (!stat_out || ranks < 1) : (!mean || !var_biased || !var_unbiased))
     return acx_fail(ctx, ACX_E_BADARG, "acx_selector_tail: gathered statistics need stat_out and ranks >= 1, local ones mean / var%s");
   if ((running_mean == nullptr) != (running_var == nullptr)) return acx_fail(ctx, ACX_E_BADARG, "acx_selector_tail: running_mean and running_var come together%s");
-  if (B <= 0 || B % 2 || ktop > N || kbot > N || ktop < 0 || kbot < 0 || C1 <= 0 || C1 > 64 || ldl < C1)
+  const int fits = acx_selector_tail_fits(ctx, B, N, Lg, C1, ktop, kbot);
+  if (fits == ACX_E_BADARG || ldl < C1)
     return acx_fail(ctx, ACX_E_BADARG, "acx_selector_tail: need even B, k <= N, 1 <= C-1 <= 64, ldl >= C-1%s");
-  const size_t lds = ((size_t)N * Lg * C1 + (size_t)N * C1 + 2 * (size_t)N + 2 * (size_t)C1) * 4 + (size_t)(ktop + kbot) * 4;
-  if (lds > 160 * 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_selector_tail: a video's logits exceed the 160 KB of LDS%s");
+  if (fits != ACX_OK) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_selector_tail: a video's logits exceed the 160 KB of LDS%s");
+  const size_t lds = selector_tail_lds(N, Lg, C1, ktop, kbot);
   SelTailArgs a;
   a.raw = raw; a.gathered = gathered; a.R = ranks; a.mean_in = mean; a.var_b_in = var_biased; a.var_u_in = var_unbiased;
   a.stat_out = stat_out; a.rm = running_mean; a.rv = running_var; a.nbt = (long long*)num_batches_tracked;

@@ -1197,30 +1197,42 @@ def selector_tail(raw, labels, mask_top, mask_bot, N, Lg, normal_id, ktop, kbot,
     return logits, it, ib, topk, st
 
 
+def selector_tail_fits(B, N, Lg, C1, ktop, kbot) -> bool:
+    """whether acx_selector_tail takes the shape (the library's own shape checks: acx_selector_tail_fits)"""
+    return L.lib().acx_selector_tail_fits(None, B, N, Lg, C1, ktop, kbot) == 0
+
+
+def mil_loss_bn_fits(B, N, Lg, C1, K) -> bool:
+    """whether acx_mil_loss_bn takes the shape (the library's own shape checks: acx_mil_loss_bn_fits)"""
+    return L.lib().acx_mil_loss_bn_fits(None, B, N, Lg, C1, K) == 0
+
+
+def _mil_loss_common(sim, scores, B, N, Lg, K, lambdas):
+    """What mil_loss and mil_loss_bn both bring: (dsim, dscores, losses [8], workspace, its floats, lambdas as a C array, the
+    stream's loss counter)."""
+    import ctypes
+    dev = sim.device
+    nws = (B * N * Lg + 255) // 256 * 8 + (B * K * Lg + 255) // 256
+    return (torch.empty_like(sim), torch.empty_like(scores), torch.empty(8, dtype=torch.float32, device=dev),
+            torch.empty(nws, dtype=torch.float32, device=dev), nws, (ctypes.c_float * 7)(*[float(x) for x in lambdas]),
+            _colsum_counters(dev)[_CTR_N - 1:])            # the last arrival counter of the stream's table: the loss's own
+
+
 def mil_loss_bn(sim, sim_topk, labels, scores, idx_topk_abn, idx_topk_nor, idx_bottomk_abn, N, Lg, K, normal_id, lambdas,
                 meter: Optional[torch.Tensor] = None, gout: Optional[torch.Tensor] = None):
     """loss + its gradients + `meter += losses` + the scatter of the top-k rows' gradient + the selector BatchNorm's backward sums in
     ONE launch (acx_mil_loss_bn; bit-identical to mil_loss + axpby_ + scatter_segments_ + bn_bwd_stats).  Returns (losses [8],
-    dlogits, dscores, bn_sums [2 C1]); raises AcxError(ACX_E_UNSUPPORTED) when B N Lg is not a multiple of 256."""
-    import ctypes
+    dlogits, dscores, bn_sums [2 C1]); raises AcxError(ACX_E_UNSUPPORTED) where mil_loss_bn_fits says no."""
     B = labels.shape[0]
     C1 = sim.shape[1]
-    dev = sim.device
-    dl = torch.empty_like(sim)
-    dsc = torch.empty_like(scores)
-    losses = torch.empty(8, dtype=torch.float32, device=dev)
-    sums = torch.empty(2 * C1, dtype=torch.float32, device=dev)
-    nws = (B * N * Lg + 255) // 256 * 8 + (B * K * Lg + 255) // 256
-    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    dl, dsc, losses, ws, nws, lam, ctr = _mil_loss_common(sim, scores, B, N, Lg, K, lambdas)
+    sums = torch.empty(2 * C1, dtype=torch.float32, device=sim.device)
     bws = _bn_workspace(sim, sim.shape[0], C1)
-    lam = (ctypes.c_float * 7)(*[float(x) for x in lambdas])
     h = _h(sim)
-    ctr = _colsum_counters(dev)[_CTR_N - 1:]                # the last arrival counter of the stream's table: the loss's own
     L.check(L.lib().acx_mil_loss_bn(h, sim.data_ptr(), sim_topk.data_ptr(), labels.data_ptr(), scores.data_ptr(),
                                     idx_topk_abn.data_ptr(), idx_topk_nor.data_ptr(), idx_bottomk_abn.data_ptr(), dl.data_ptr(),
                                     dsc.data_ptr(), losses.data_ptr(), _ptr(meter), sums.data_ptr(), ws.data_ptr(), nws, bws.data_ptr(),
-                                    bws.numel() * 8, B, N, Lg, C1, K, normal_id, ctypes.cast(lam, ctypes.c_void_p), _ptr(gout),
-                                    ctr.data_ptr(), _stream()), h)
+                                    bws.numel() * 8, B, N, Lg, C1, K, normal_id, lam, _ptr(gout), ctr.data_ptr(), _stream()), h)
     return losses, dl, dsc, sums
 
 
@@ -1254,23 +1266,15 @@ def scatter_segments_(dlogits, dout, idx, N, Lg) -> None:
 def mil_loss(sim, sim_topk, labels, scores, idx_topk_abn, idx_topk_nor, idx_bottomk_abn, N, Lg, K, normal_id, lambdas,
              gout: Optional[torch.Tensor] = None):
     """returns (losses[8], dsim, dsim_topk, dscores)."""
-    import ctypes
     B = labels.shape[0]
     C1 = sim.shape[1]
-    dev = sim.device
-    dsim = torch.empty_like(sim)
+    dsim, dsc, losses, ws, nws, lam, ctr = _mil_loss_common(sim, scores, B, N, Lg, K, lambdas)
     dtopk = torch.empty_like(sim_topk)
-    dsc = torch.empty_like(scores)
-    losses = torch.empty(8, dtype=torch.float32, device=dev)
-    nws = (B * N * Lg + 255) // 256 * 8 + (B * K * Lg + 255) // 256
-    ws = torch.empty(nws, dtype=torch.float32, device=dev)
-    lam = (ctypes.c_float * 7)(*[float(x) for x in lambdas])
     h = _h(sim)
-    ctr = _colsum_counters(dev)[_CTR_N - 1:]                # the last arrival counter of the stream's table: the loss's own
     L.check(L.lib().acx_mil_loss_one(h, sim.data_ptr(), sim_topk.data_ptr(), labels.data_ptr(), scores.data_ptr(),
                                      idx_topk_abn.data_ptr(), idx_topk_nor.data_ptr(), idx_bottomk_abn.data_ptr(), dsim.data_ptr(),
                                      dtopk.data_ptr(), dsc.data_ptr(), losses.data_ptr(), ws.data_ptr(), nws, B, N, Lg, C1, K,
-                                     normal_id, ctypes.cast(lam, ctypes.c_void_p), _ptr(gout), ctr.data_ptr(), _stream()), h)
+                                     normal_id, lam, _ptr(gout), ctr.data_ptr(), _stream()), h)
     return losses, dsim, dtopk, dsc
 
 

@@ -717,18 +717,11 @@ int acx_gather_segments(acx_ctx* ctx, const float* logits, const int64_t* idx, f
                         int32_t Lg, int32_t C1, int32_t K, void* stream);
 int acx_scatter_segments(acx_ctx* ctx, const float* dout, const int64_t* idx, float* dlogits, int32_t B, int32_t N,
                          int32_t Lg, int32_t C1, int32_t K, void* stream);
-/* acx_mil_loss: ComputeLoss.__call__ (loss.py:51-195) forward AND backward in one pass.  losses[8] = (cost,
+/* acx_mil_loss_one: ComputeLoss.__call__ (loss.py:51-195) forward AND backward in ONE launch.  losses[8] = (cost,
  * ldir_abn, ldir_nor, ltopk_abn, lbottomk_abn, ltopk_nor, lsmooth, lsparse); dsim / dsim_topk / dscores are the
- * gradients of gout*cost.  lambdas[7] = (dir_abn, dir_nor, topk_abn, bottomk_abn, topk_nor, smooth, sparse).
- * workspace: ceil(B*N*Lg/256)*8 + ceil(B*K*Lg/256) floats. */
-int acx_mil_loss(acx_ctx* ctx, const float* sim, const float* sim_topk, const int64_t* labels, const float* scores,
-                 const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
-                 float* dsim, float* dsim_topk, float* dscores, float* losses, float* workspace,
-                 size_t workspace_floats, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K, int32_t normal_id,
-                 const float* lambdas, const float* gout /* device scalar or NULL (=1) */, void* stream);
-/* acx_mil_loss as ONE launch: `counter` = one uint32, zero before the first call and left zero by every call (caller-owned;
- * NULL = the three-launch form above).  The block partials are added in a different (fixed) order than the three-launch
- * form's serial sum, in f64 either way. */
+ * gradients of gout*cost (gout: device scalar or NULL = 1).  lambdas[7] = (dir_abn, dir_nor, topk_abn, bottomk_abn, topk_nor,
+ * smooth, sparse).  workspace: ceil(B*N*Lg/256)*8 + ceil(B*K*Lg/256) floats.  `counter` = one uint32, zero before the first call
+ * and left zero by every call (caller-owned; NULL is ACX_E_BADARG).  The block partials are added in a fixed order, in f64. */
 int acx_mil_loss_one(acx_ctx* ctx, const float* sim, const float* sim_topk, const int64_t* labels, const float* scores,
                  const int64_t* idx_topk_abn, const int64_t* idx_topk_nor, const int64_t* idx_bottomk_abn,
                  float* dsim, float* dsim_topk, float* dscores, float* losses, float* workspace,
@@ -745,6 +738,10 @@ int acx_mil_loss_bn(acx_ctx* ctx, const float* sim, const float* sim_topk, const
                     float* dscores, float* losses, float* meter, float* bn_sums, float* workspace, size_t workspace_floats,
                     void* bn_workspace, size_t bn_workspace_bytes, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K,
                     int32_t normal_id, const float* lambdas, const float* gout, uint32_t* counter, void* stream);
+/* acx_mil_loss_bn_fits: the code acx_mil_loss_bn's shape checks give a shape -- ACX_OK, ACX_E_BADARG (B odd or < 2, C1 outside
+ * 1..64) or ACX_E_UNSUPPORTED (B N Lg no multiple of 256, or more than 131072 rows); the entry point itself calls it.  Arithmetic
+ * on the arguments: no device, nothing dereferenced, ctx may be NULL, no error text. */
+int acx_mil_loss_bn_fits(const acx_ctx* ctx, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t K);
 /* The selector's forward tail as ONE launch, one workgroup per video (selector_model.py:60-99,119-225): [SyncBN combine of
  * `gathered` [ranks, 2 C1 + 1] -> stat_out [3 C1 + 1] = mean | biased var | unbiased var | total rows; gathered == NULL: the local
  * statistics mean / var_biased / var_unbiased] -> logits = BatchNorm(raw) [rows, ldl] -> [running statistics, NULL: none] ->
@@ -756,6 +753,10 @@ int acx_selector_tail(acx_ctx* ctx, const float* raw, const float* gathered, int
                       int64_t* num_batches_tracked, float momentum, float one_minus, float* logits, int64_t ldl, const int64_t* labels,
                       const float* mask_top, const float* mask_bot, int64_t* idx_top, int64_t* idx_bot, float* logits_topk, int32_t B,
                       int32_t N, int32_t Lg, int32_t C1, int32_t normal_id, int32_t ktop, int32_t kbot, float eps, void* stream);
+/* acx_selector_tail_fits: the code acx_selector_tail's shape checks give a shape -- ACX_OK, ACX_E_BADARG (B odd or < 2, a k
+ * outside 0..N, C1 outside 1..64) or ACX_E_UNSUPPORTED (a video's (N Lg C1 + N C1 + 2 N + 2 C1 + ktop + kbot) * 4 bytes exceed the
+ * 160 KB of LDS); the entry point itself calls it (and checks ldl).  Arithmetic on the arguments, as acx_mil_loss_bn_fits. */
+int acx_selector_tail_fits(const acx_ctx* ctx, int32_t B, int32_t N, int32_t Lg, int32_t C1, int32_t ktop, int32_t kbot);
 /* acx_text_directions_bwd with d_dirs given as the K-split partial images of the TN product that forms it (acx_gemm_tn_parts:
  * image s at ddirs_parts + s * part_stride floats, rows = direction index, row stride D), summed here in image order. */
 int acx_text_directions_bwd_parts(acx_ctx* ctx, const float* text, const float* ncentroid, const float* ddirs_parts, int32_t nparts,

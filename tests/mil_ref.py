@@ -43,6 +43,20 @@ def case_id(case):
     return "-".join(str(int(v)) for v in case)
 
 
+# ------------------------------------------------------------------------------------------------------------- the step graph's gates
+# The shapes the one-launch forms take, as the training step evaluated them itself before the library answered
+# (acx_selector_tail_fits / acx_mil_loss_bn_fits); frozen here, tests/test_cpu_mil_ref.py holds the queries to them.
+def selector_tail_gate(B, N, Lg, C1, ktop, kbot):
+    """a video's logits, segment sums, keys, statistics and picks within 160 KB of LDS, at most 64 directions"""
+    return (N * Lg * C1 + N * C1 + 2 * N + 2 * C1 + ktop + kbot) * 4 <= 160 * 1024 and C1 <= 64
+
+
+def mil_loss_bn_gate(B, N, Lg, C1, K):
+    """whole slabs of 256 frame rows, at most 512 of them, at most 64 directions"""
+    rows = B * N * Lg
+    return rows % 256 == 0 and rows <= 131072 and C1 <= 64
+
+
 # ------------------------------------------------------------------------------------------------------------- inputs
 def abnormal_labels(nv, C1, normal_id):
     """nv labels out of {0..C1} \\ {normal_id}: normal_id + 1, the largest class, normal_id - 1, the smallest, then the rest, in

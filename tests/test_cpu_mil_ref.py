@@ -1,7 +1,8 @@
 """No GPU: the reference side of tests/test_gpu_mil_chain.py and the host side of the chain's entry points.  The fp64 closed forms of
 mil_ref against torch's fp64 autograd of oracle.compute_loss / a plain BatchNorm expression / oracle.selector_directions (1e-12 * S);
 torch's fp32 evaluation of the same inside HALF the bound the kernels are held to (so the form of S, not a kernel, is what this
-file judges); the properties the seeded inputs promise; and the C ABI's refusal of odd B, k > N and C-1 = 65 before any launch."""
+file judges); the properties the seeded inputs promise; the C ABI's refusal of odd B, k > N and C-1 = 65 before any launch; and the
+two shape queries the training step asks (acx_selector_tail_fits, acx_mil_loss_bn_fits) on both sides of every boundary."""
 import ctypes as C
 
 import pytest
@@ -139,11 +140,8 @@ def test_chain_refuses_bad_arguments_before_any_launch():
     def select_idx(B=2, C1=3, ktop=K, kbot=K):
         return lib.acx_select_idx(None, p, p, p, p, p, p, B, N, Lg, C1, nid, ktop, kbot, None)
 
-    def mil_loss(B=2, C1=3):
-        return lib.acx_mil_loss(None, *[p] * 12, 8192, B, N, Lg, C1, K, nid, p, None, None)
-
-    def mil_loss_one(B=2, C1=3):
-        return lib.acx_mil_loss_one(None, *[p] * 12, 8192, B, N, Lg, C1, K, nid, p, None, p, None)
+    def mil_loss_one(B=2, C1=3, counter=p):
+        return lib.acx_mil_loss_one(None, *[p] * 12, 8192, B, N, Lg, C1, K, nid, p, None, counter, None)
 
     def mil_loss_bn(B=2, C1=3, N_=N):
         return lib.acx_mil_loss_bn(None, *[p] * 13, 8192, p, 8192 * 4, B, N_, Lg, C1, K, nid, p, None, p, None)
@@ -156,8 +154,8 @@ def test_chain_refuses_bad_arguments_before_any_launch():
     cases = [
         ("acx_select_idx", lambda: select_idx(B=3), BADARG), ("acx_select_idx", lambda: select_idx(ktop=N + 1), BADARG),
         ("acx_select_idx", lambda: select_idx(kbot=N + 1), BADARG),
-        ("acx_mil_loss", lambda: mil_loss(B=3), BADARG), ("acx_mil_loss", lambda: mil_loss(C1=65), BADARG),
         ("acx_mil_loss", lambda: mil_loss_one(B=3), BADARG), ("acx_mil_loss", lambda: mil_loss_one(C1=65), BADARG),
+        ("acx_mil_loss", lambda: mil_loss_one(counter=None), BADARG),
         ("acx_mil_loss_bn", lambda: mil_loss_bn(B=3), BADARG), ("acx_mil_loss_bn", lambda: mil_loss_bn(C1=65), BADARG),
         ("acx_mil_loss_bn", lambda: mil_loss_bn(), UNSUPPORTED), ("acx_mil_loss_bn", lambda: mil_loss_bn(N_=513 * 32), UNSUPPORTED),
         ("acx_selector_tail", lambda: selector_tail(B=3), BADARG), ("acx_selector_tail", lambda: selector_tail(C1=65), BADARG),
@@ -170,3 +168,51 @@ def test_chain_refuses_bad_arguments_before_any_launch():
         assert b"null" in lib.acx_last_error(None)
         assert call() == code, name
         assert lib.acx_last_error(None).startswith(name.encode() + b":"), (name, lib.acx_last_error(None))
+
+
+OK, BADARG, UNSUPPORTED = 0, -1, -2
+# (B, N, Lg, C1, ktop, kbot) -> the code of acx_selector_tail_fits and of acx_selector_tail's shape checks
+TAIL_BOUNDARIES = [
+    ((2, 2559, 13, 1, 7, 7), OK),                  # exactly 163,840 bytes of LDS
+    ((2, 2559, 13, 1, 7, 8), UNSUPPORTED),         # 163,844
+    ((2, 37, 16, 64, 3, 3), OK), ((2, 38, 16, 64, 3, 3), UNSUPPORTED),
+    ((2, 4, 4, 64, 2, 2), OK), ((2, 4, 4, 65, 2, 2), BADARG), ((2, 4, 4, 0, 2, 2), BADARG),
+    ((3, 4, 4, 3, 2, 2), BADARG),
+    ((2, 4, 4, 3, 5, 2), BADARG),                  # ktop = N + 1
+]
+# (B, N, Lg, C1, K) -> the code of acx_mil_loss_bn_fits and of acx_mil_loss_bn's shape checks
+LOSS_BN_BOUNDARIES = [
+    ((2, 8, 16, 3, 1), OK), ((2, 8, 15, 3, 1), UNSUPPORTED),                    # 256 rows, 240
+    ((2, 4096, 16, 3, 1), OK), ((2, 4104, 16, 3, 1), UNSUPPORTED),              # 131072 rows (512 slabs), 131328
+    ((2, 8, 16, 64, 1), OK), ((2, 8, 16, 65, 1), BADARG), ((2, 8, 16, 0, 1), BADARG),
+    ((3, 8, 16, 3, 1), BADARG),
+]
+
+
+def test_shape_queries_agree_with_the_gates_and_the_entry_points():
+    """acx_selector_tail_fits / acx_mil_loss_bn_fits through the C ABI with a null context: `== ACX_OK` equals the gate the training
+    step evaluated itself (mil_ref) over the loss sweep; the expected code on both sides of every boundary; and for every refused
+    shape the entry point (dummy pointers: it returns before any launch) gives the query's code."""
+    lib = L.lib()
+    for (B, N, Lg, C1, K, _) in LOSS_CASES:
+        assert (lib.acx_selector_tail_fits(None, B, N, Lg, C1, K, K) == OK) == MR.selector_tail_gate(B, N, Lg, C1, K, K), (B, N, Lg, C1, K)
+        assert (lib.acx_mil_loss_bn_fits(None, B, N, Lg, C1, K) == OK) == MR.mil_loss_bn_gate(B, N, Lg, C1, K), (B, N, Lg, C1, K)
+    gates = [MR.mil_loss_bn_gate(*c[:5]) for c in LOSS_CASES]
+    assert any(gates) and not all(gates)
+    buf = (C.c_float * 8192)()
+    p = C.addressof(buf)
+    for shape, code in TAIL_BOUNDARIES:
+        B, N, Lg, C1, ktop, kbot = shape
+        assert lib.acx_selector_tail_fits(None, *shape) == code, shape
+        assert code == BADARG or MR.selector_tail_gate(*shape) == (code == OK), shape      # (the gates never judged B or k)
+        if code != OK:
+            assert lib.acx_selector_tail(None, p, None, 0, p, p, p, None, None, None, None, 0.1, 0.9, p, C1, p, p, p, p, p, p, B, N, Lg,
+                                         C1, 0, ktop, kbot, 1e-5, None) == code, shape
+            assert lib.acx_last_error(None).startswith(b"acx_selector_tail:"), shape
+    for shape, code in LOSS_BN_BOUNDARIES:
+        B, N, Lg, C1, K = shape
+        assert lib.acx_mil_loss_bn_fits(None, *shape) == code, shape
+        assert code == BADARG or MR.mil_loss_bn_gate(*shape) == (code == OK), shape
+        if code != OK:
+            assert lib.acx_mil_loss_bn(None, *[p] * 13, 8192, p, 8192 * 4, B, N, Lg, C1, K, 0, p, None, p, None) == code, shape
+            assert lib.acx_last_error(None).startswith(b"acx_mil_loss_bn:"), shape
