@@ -26,6 +26,10 @@ COMM_ID_BYTES = 128
 SAB_ROUTE_UNSUPPORTED, SAB_ROUTE_TEXT_MFMA, SAB_ROUTE_TEXT_BLOCK, SAB_ROUTE_TEXT_ROWS = 0, 1, 2, 3
 SAB_ROUTE_AXIAL_MFMA, SAB_ROUTE_AXIAL_MFMA_PADDED, SAB_ROUTE_GENERIC = 4, 5, 6
 AXF_ROUTE_UNSUPPORTED, AXF_ROUTE_PADDED_MFMA, AXF_ROUTE_EXACT_MFMA, AXF_ROUTE_THREAD_PER_ROW = 0, 1, 2, 3
+# acx_gemm_route: the route function of csrc/acx_gemm.hip that takes a descriptor (include/acx.h ACX_GEMM_ROUTE_*)
+GEMM_ROUTE_NONE, GEMM_ROUTE_X6_TAIL_SPLIT, GEMM_ROUTE_SK, GEMM_ROUTE_X6, GEMM_ROUTE_S64, GEMM_ROUTE_P256, GEMM_ROUTE_W8 = 0, 1, 2, 3, 4, 5, 6
+GEMM_ROUTE_W8_CONV, GEMM_ROUTE_RING, GEMM_ROUTE_P8, GEMM_ROUTE_DMA_CONV, GEMM_ROUTE_DMA, GEMM_ROUTE_GENERIC = 7, 8, 9, 10, 11, 12
+GEMM_REDUCE_NONE, GEMM_REDUCE_LAUNCH, GEMM_REDUCE_COUNTERS = 0, 1, 2
 
 
 class GemmDesc(C.Structure):
@@ -51,6 +55,10 @@ class GemmDesc(C.Structure):
 
 class GemmScratch(C.Structure):   # acx_gemm_scratch_t: what acx_gemm_scratch tells the caller to bring
     _fields_ = [("workspace_bytes", c_size_t), ("counters", c_int32)]
+
+
+class GemmRoute(C.Structure):     # acx_gemm_route_t: the route acx_gemm takes, its K pieces, how they are summed, the launch's tiles
+    _fields_ = [("route", c_int32), ("ksplit", c_int32), ("reduce", c_int32), ("reserved", c_int32), ("tiles", c_int64)]
 
 
 class LnJob(C.Structure):     # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
@@ -148,6 +156,7 @@ _SIGS = {
     "acx_get_option": (C.c_int, [c_void_p, c_int32, C.POINTER(c_int64)]),
     "acx_gemm": (C.c_int, [c_void_p, C.POINTER(GemmDesc), c_void_p]),
     "acx_gemm_scratch": (C.c_int, [c_void_p, C.POINTER(GemmDesc), c_int32, C.POINTER(GemmScratch)]),
+    "acx_gemm_route": (C.c_int, [c_void_p, C.POINTER(GemmDesc), C.POINTER(GemmRoute)]),
     "acx_gemm_ln": (C.c_int, [c_void_p, C.POINTER(GemmDesc), C.POINTER(LnJob), c_void_p]),
     "acx_gemm_ln_plan": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, C.c_double, C.POINTER(c_int64)]),
     "acx_layernorm": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,

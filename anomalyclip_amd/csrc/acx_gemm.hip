@@ -711,11 +711,12 @@ struct GemmCall {
   bool relu_act;                  // ACX_ACT_RELU / ACX_ACT_RESRELU
   int dev_slot;                   // index of the context's device in acx_launch_lds's per-device state
   int ncu, ncu_x6;                // workgroups of a persistent launch; the plane kernel's (ACX_OPT_X6_CUS caps it)
+  acx_gemm_route_t* dry;          // acx_gemm_route: the route that takes the problem answers here INSTEAD of launching (nullptr: launch)
 };
 
-static GemmCall gemm_call(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
+static GemmCall gemm_call(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, acx_gemm_route_t* dry = nullptr) {
   GemmCall c;
-  c.ctx = ctx; c.d = d; c.s = (hipStream_t)stream;
+  c.ctx = ctx; c.d = d; c.s = (hipStream_t)stream; c.dry = dry;
   c.prec = d->prec;
   c.a_f16 = d->a_dtype == ACX_F16;
   c.a_bf16 = d->a_dtype == ACX_BF16 || c.a_f16;
@@ -727,6 +728,16 @@ static GemmCall gemm_call(acx_ctx* ctx, const acx_gemm_desc* d, void* stream) {
   c.ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
   c.ncu_x6 = ctx && ctx->opt_x6_cus > 0 && ctx->opt_x6_cus < c.ncu ? ctx->opt_x6_cus : c.ncu;
   return c;
+}
+
+// acx_gemm_route's answer, given by the route that would launch, at the point where it would: every gate above that point has run
+// exactly as it does for acx_gemm.  reduce: 0 no K split, 1 a reduce launch sums the pieces, 2 they meet through arrival counters
+static int route_dry(const GemmCall& c, int route, int ksplit, int reduce, long long tiles) {
+  c.dry->route = route;
+  c.dry->ksplit = ksplit;
+  c.dry->reduce = ksplit > 1 ? reduce : 0;
+  c.dry->tiles = tiles;
+  return ACX_OK;
 }
 
 static Args gemm_args(const GemmCall& c) {
@@ -860,7 +871,8 @@ static bool x6_may_split(const GemmCall& c) {
   return !c.relu_act && !(c.d->amap == ACX_AMAP_CONV3X3 && x6_conv_general(c.d));
 }
 
-static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden);
+static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden,
+                     acx_gemm_route_t* dry = nullptr);
 
 // ---- route 1, opt-in (ACX_OPT_X6_TAIL_SPLIT): pairs = 6, more 256 x 256 tiles than CUs, a last round that fills only part of
 // the chip (the ViT's N = 768 products: 1182 tiles = 4.6 rounds at 512 frames, 591 = 2.3 at 256): the whole tile rows of the full
@@ -899,6 +911,7 @@ static int route_x6_tail_split(const GemmCall& c) {
   const int s_tail = x6_choose_split(xtail, nks, ncu, (size_t)m_tail * d->N * sizeof(float), d->workspace_bytes, 6, &tail_us);
   const double now_us = (rounds + 1) * (nks + 7.0) * 3.0, new_us = rounds * (nks + 7.0) * 3.0 + tail_us + 6.0;
   if (s_tail <= 1 || new_us >= ACX_X6TAIL_THRESH * now_us) return ROUTE_NEXT;
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_X6_TAIL_SPLIT, s_tail, 1, xt);   // (the tail's pieces; all 256 x 256 tiles of both calls)
   acx_gemm_desc dm = *d, dt = *d;
   dm.M = (int)row0; dm.workspace = nullptr; dm.workspace_bytes = 0;
   const bool apanel = (d->panels & 1) != 0;
@@ -989,6 +1002,7 @@ static int route_sk(const GemmCall& c, const Args& base) {
       kgrid.y = (unsigned)pieces;
     }
   }
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_SK, g.ksplit, 2, kgrid.x);
   const int epi = d->gelu_grad_of ? SK_EPI_GELUGRAD : d->residual ? SK_EPI_RES : d->act == ACX_ACT_QUICKGELU ? SK_EPI_QUICKGELU : SK_EPI_PLAIN;
   if (a_norm) sk_launch<SK_EPI_PLAIN, 0, 1>(c, kgrid, g);
   else if (d->a_act == ACX_ACT_QUICKGELU) sk_launch_epi<1>(c, epi, kgrid, g);
@@ -1112,6 +1126,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   in.ride_cap = ctx ? ctx->opt_ln_rider : 0;
   in.rate = 0.0;
   const X6Plan p = x6_plan(in);
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_X6, p.split, 1, p.xt);
 
   Args g = base;
   g.ksplit = p.split; g.kchunk = (p.nks + p.split - 1) / p.split; g.partial = p.split > 1 ? (float*)d->workspace : nullptr;
@@ -1178,6 +1193,7 @@ static int route_s64(const GemmCall& c, const Args& base) {
       sgrid.y = (unsigned)g.ksplit;
     }
   }
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_S64, g.ksplit, 1, sgrid.x);
   if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) s64_launch<1, 1>(c, sgrid, g); else s64_launch<1, 0>(c, sgrid, g); }
   else if (d->act == ACX_ACT_RELU) { if (d->residual) s64_launch<3, 1>(c, sgrid, g); else s64_launch<3, 0>(c, sgrid, g); }
   else if (d->act == ACX_ACT_RESRELU) s64_launch<4, 1>(c, sgrid, g);
@@ -1240,6 +1256,7 @@ static void p256_launch(const GemmCall& c, const Args& g) {
 static int route_p256(const GemmCall& c, const Args& g, const KSplit& ks) {
   const acx_gemm_desc* d = c.d;
   if (!(ks.ksplit == 1 && acx_gemm_takes_strip_stream(d))) return ROUTE_NEXT;
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_P256, 1, 0, (long long)((d->M + BM - 1) / BM) * g.tiles_n);
   if (d->amap == ACX_AMAP_CONV3X3) {
     if (d->act == ACX_ACT_LEAKYRELU) p256_launch<2, 1>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 1>(c, g); else p256_launch<0, 1>(c, g);
   } else if (d->act == ACX_ACT_QUICKGELU) p256_launch<1, 0>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 0>(c, g); else p256_launch<0, 0>(c, g);
@@ -1274,6 +1291,7 @@ static int route_w8(const GemmCall& c, const Args& base, dim3 grid, const KSplit
   ks.into(g);
   // split pieces meet inside the kernel (last-arriver reduction) when the caller brought arrival counters; else a reduce launch
   g.counters = (ks.ksplit > 1 && d->counters && (int)grid.x <= d->n_counters) ? (unsigned int*)d->counters : nullptr;
+  if (c.dry) return route_dry(c, w8_conv ? ACX_GEMM_ROUTE_W8_CONV : ACX_GEMM_ROUTE_W8, ks.ksplit, g.counters ? 2 : 1, grid.x);
   if (w8_conv) w8_launch_epi<1>(c, grid, g); else w8_launch_epi<0>(c, grid, g);
   if (ks.ksplit > 1 && !g.counters) splitk_reduce(c, ks.partial, ks.ksplit, false);
   ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
@@ -1319,6 +1337,7 @@ static int route_ring(const GemmCall& c, const Args& g, const KSplit& ks) {
                   (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && ACX_DBG_SWITCH("P8", true);
   if ((d->pairs > 1 || c_x3) && !p8)
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 6 / ACX_BF16X3 output need the persistent 256x256 kernel%s");
+  if (c.dry) return route_dry(c, p8 ? ACX_GEMM_ROUTE_P8 : ACX_GEMM_ROUTE_RING, 1, 0, rtiles);
 #ifdef ACX_DEBUG_SWITCHES
   // A/B only (tools build, ACX_P4=1): the one-wave-per-SIMD frame's PLAIN schedule (acx_gemm_x6.h: 64-k super-steps, 64 MFMAs per
   // wave and barrier).  Measured equal to or 3-15 % behind the p8 kernel on the ViT shapes, its K loop alone (no DMA, no stores)
@@ -1355,6 +1374,7 @@ static int route_dma_conv(const GemmCall& c, const Args& g, dim3 grid, const KSp
         !((uintptr_t)d->zero_page & 15) && d->cin % 64 == 0 && d->M % 128 == 0 && d->lda % 8 == 0 && d->ldw % 8 == 0 && !d->a_sub &&
         !d->pos0 && d->act != ACX_ACT_QUICKGELU && !(d->act == ACX_ACT_LEAKYRELU && d->residual)))
     return ROUTE_NEXT;
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_DMA_CONV, 1, 0, grid.x);
   if (d->act == ACX_ACT_LEAKYRELU) { if (c_bf16) dma_launch<1, 2, 0, 1>(c, grid, g); else dma_launch<0, 2, 0, 1>(c, grid, g); }
   else if (d->residual) { if (c_bf16) dma_launch<1, 0, 1, 1>(c, grid, g); else dma_launch<0, 0, 1, 1>(c, grid, g); }
   else { if (c_bf16) dma_launch<1, 0, 0, 1>(c, grid, g); else dma_launch<0, 0, 0, 1>(c, grid, g); }
@@ -1365,6 +1385,7 @@ static int route_dma(const GemmCall& c, const Args& g, dim3 grid, const KSplit& 
   const acx_gemm_desc* d = c.d;
   if (!(c.fast && ks.ksplit == 1 && c.prec == ACX_PREC_BF16 && c.a_bf16 && ACX_DBG_SWITCH("DMA", true) && d->lda % 8 == 0 && d->ldw % 8 == 0))
     return ROUTE_NEXT;
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_DMA, 1, 0, grid.x);
   switch ((c.c_bf16 ? 4 : 0) + (d->act == ACX_ACT_QUICKGELU ? 2 : 0) + (d->residual ? 1 : 0)) {
     case 0: dma_launch<0, 0, 0, 0>(c, grid, g); break;
     case 1: dma_launch<0, 0, 1, 0>(c, grid, g); break;
@@ -1396,6 +1417,7 @@ static void gemm_kernel_launch_epi(const GemmCall& c, dim3 grid, const Args& g) 
   }
 }
 static int route_gemm_kernel(const GemmCall& c, const Args& base, dim3 grid, const KSplit& ks) {
+  if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_GENERIC, ks.ksplit, 1, grid.x);
   Args g = base;
   ks.into(g);
   switch ((c.prec == ACX_PREC_F32 ? 0 : (c.a_bf16 ? 1 : 2)) * 2 + c.c_bf16) {
@@ -1411,14 +1433,15 @@ static int route_gemm_kernel(const GemmCall& c, const Args& base, dim3 grid, con
   return ACX_OK;
 }
 
-static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden) {
+// dry != nullptr (acx_gemm_route): the same walk, and the route that takes the problem fills *dry where it would launch
+static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const acx_ln_job* job, long long* ridden, acx_gemm_route_t* dry) {
   int rc = gemm_validate(ctx, d);
   if (rc) return rc;
-  const GemmCall c = gemm_call(ctx, d, stream);
+  const GemmCall c = gemm_call(ctx, d, stream, dry);
   // (decided before the profiling scope: the two calls are two launches)
   if ((rc = route_x6_tail_split(c)) != ROUTE_NEXT) return rc;
-  AcxProfScope prof__(ctx, ACX_K_GEMM, c.s);
-  if (ctx && ctx->prof_on) ctx->prof_gemm_flops += 2.0 * d->M * (double)d->N * d->K;
+  AcxProfScope prof__(dry ? nullptr : ctx, ACX_K_GEMM, c.s);
+  if (ctx && ctx->prof_on && !dry) ctx->prof_gemm_flops += 2.0 * d->M * (double)d->N * d->K;
   const Args g = gemm_args(c);
   if ((rc = route_sk(c, g)) != ROUTE_NEXT) return rc;
   if ((rc = route_x6(c, g, job, ridden)) != ROUTE_NEXT) return rc;
@@ -1437,6 +1460,13 @@ static int gemm_impl(acx_ctx* ctx, const acx_gemm_desc* d, void* stream, const a
 // Host arithmetic on the shape fields, the options and whether the optional operands are there; d->workspace / d->counters are not
 // read.  The answer decides more than a size: the routes choose their K split from workspace_bytes, and route_sk's row gate from
 // whether there is a workspace at all.
+// Which route acx_gemm takes with this descriptor, by gemm_impl's own walk (no second copy of the gates): see include/acx.h
+extern "C" int acx_gemm_route(const acx_ctx* ctx, const acx_gemm_desc* d, acx_gemm_route_t* out) {
+  if (!out) return ACX_E_BADARG;
+  out->route = ACX_GEMM_ROUTE_NONE; out->ksplit = 1; out->reduce = 0; out->reserved = 0; out->tiles = 0;
+  return gemm_impl(const_cast<acx_ctx*>(ctx), d, nullptr, nullptr, nullptr, out);
+}
+
 extern "C" int acx_gemm_scratch(const acx_ctx* ctx, const acx_gemm_desc* d, int32_t allow_split, acx_gemm_scratch_t* out) {
   if (!d || !out || d->M <= 0 || d->N <= 0 || d->K <= 0) return ACX_E_BADARG;
   out->workspace_bytes = 0;

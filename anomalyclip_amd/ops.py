@@ -399,8 +399,9 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
 def gemm(a: torch.Tensor, w: torch.Tensor, *, out: Optional[torch.Tensor] = None, M: Optional[int] = None,
          bias=None, act=L.ACT_NONE, residual=None, a_sub=None, prec=L.PREC_F32, out_dtype=torch.float32,
          amap=L.AMAP_IDENTITY, gn=0, gl=0, cin=0, seg=0, pos0=None, pos1=None, a_act=L.ACT_NONE,
-         gelu_grad_of=None, tile_table=None, a_norm=None, a_norm_eps=1e-5) -> torch.Tensor:
-    """out[M,N] = epilogue(amap(a)[M,K] @ w[N,K]^T); see include/acx.h acx_gemm_desc."""
+         gelu_grad_of=None, tile_table=None, a_norm=None, a_norm_eps=1e-5, route: Optional["L.GemmRoute"] = None) -> torch.Tensor:
+    """out[M,N] = epilogue(amap(a)[M,K] @ w[N,K]^T); see include/acx.h acx_gemm_desc.
+    route: an L.GemmRoute that acx_gemm_route fills for this very descriptor, scratch included (the kernel tests name their kernel)."""
     assert a.dim() == 2 and w.dim() == 2 and a.is_contiguous() and w.is_contiguous()
     N, K = w.shape
     if M is None:
@@ -433,6 +434,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, out: Optional[torch.Tensor] = None
         d.tile_table = tile_table.data_ptr()
     h, lib, pd = _h(a), L.lib(), C.byref(d)
     _bring_scratch(lib, h, d, pd, a.device)
+    if route is not None:
+        L.check(lib.acx_gemm_route(h, pd, C.byref(route)), h)
     L.check(lib.acx_gemm(h, pd, _stream()), h)
     return out
 

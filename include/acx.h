@@ -231,6 +231,29 @@ typedef struct acx_gemm_scratch_t {
 } acx_gemm_scratch_t;
 int acx_gemm_scratch(const acx_ctx* ctx, const acx_gemm_desc* d, int32_t allow_split, acx_gemm_scratch_t* out);
 
+/* acx_gemm_route: which kernel route acx_gemm takes with this descriptor, and how it splits K -- answered by the dispatcher's own
+ * walk through its routes, which stops where the first launch would be (there is no second copy of the gates).  Host arithmetic, no
+ * device, nothing launched; no operand is dereferenced (A, W and C must be non-NULL and aligned as for acx_gemm: dummy addresses do).
+ * Unlike acx_gemm_scratch it READS workspace, workspace_bytes, counters and n_counters as values: the route and the split depend on
+ * them.  Returns what acx_gemm would return before its first launch: ACX_OK, or the refusal's ACX_E_* with the same text in
+ * acx_last_error (*out is then route = ACX_GEMM_ROUTE_NONE, ksplit = 1).  ctx == NULL: 256 workgroups and the option values
+ * acx_create sets.
+ *   route   ACX_GEMM_ROUTE_*, one per route function of csrc/acx_gemm.hip
+ *   ksplit  K pieces across workgroups (1: none); X6_TAIL_SPLIT: the pieces of the tail's rows
+ *   reduce  0 no split; 1 the pieces are summed by a reduce launch (which applies the epilogue); 2 they meet through the arrival
+ *           counters inside the kernel (no second launch)
+ *   tiles   output tiles of the launch in the route's own tile size: SK 32 x 32, S64 64 x 64, P256 / W8 / W8_CONV / DMA / DMA_CONV /
+ *           GENERIC 128 x 128, X6 / X6_TAIL_SPLIT / RING / P8 256 x 256 (persistent kernels: tiles, not workgroups) */
+enum { ACX_GEMM_ROUTE_NONE = 0, ACX_GEMM_ROUTE_X6_TAIL_SPLIT = 1, ACX_GEMM_ROUTE_SK = 2, ACX_GEMM_ROUTE_X6 = 3, ACX_GEMM_ROUTE_S64 = 4,
+       ACX_GEMM_ROUTE_P256 = 5, ACX_GEMM_ROUTE_W8 = 6, ACX_GEMM_ROUTE_W8_CONV = 7, ACX_GEMM_ROUTE_RING = 8, ACX_GEMM_ROUTE_P8 = 9,
+       ACX_GEMM_ROUTE_DMA_CONV = 10, ACX_GEMM_ROUTE_DMA = 11, ACX_GEMM_ROUTE_GENERIC = 12 };
+typedef struct acx_gemm_route_t {
+  int32_t route, ksplit, reduce;
+  int32_t reserved;
+  int64_t tiles;
+} acx_gemm_route_t;
+int acx_gemm_route(const acx_ctx* ctx, const acx_gemm_desc* d, acx_gemm_route_t* out);
+
 /* acx_gemm_ln: acx_gemm(d) followed by the LayerNorm of ITS OUTPUT rows -- x = d->C ([M, N] f32, ldc == N), y = norm(x) * w + b as
  * acx_layernorm(x, ldc, w, b, y, N, y_dtype, M, N, eps, mode) writes it -- with the same bits as those two calls.  A pairs = 6 product
  * with the f32 residual epilogue (identity rows, N = 768 or 1024, even M, y_dtype = ACX_BF16X3P) whose last round of 256 x 256 tiles

@@ -22,6 +22,15 @@ def relerr(a, b):
     return ((a - b).abs().max() / (b.abs().max() + 1e-30)).item()
 
 
+def gemm_on(route, *args, **kw):
+    """ops.gemm, with the kernel route a test's docstring names asserted through acx_gemm_route on the very descriptor that is launched
+    (scratch included); route: one L.GEMM_ROUTE_* or several.  Returns (output, the query's answer)."""
+    got = L.GemmRoute()
+    out = ops.gemm(*args, route=got, **kw)
+    assert got.route in (route if isinstance(route, tuple) else (route,)), (got.route, got.ksplit, got.reduce, got.tiles)
+    return out, got
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 32), (197 * 3, 2304, 768), (130, 70, 36), (1, 5, 4), (512, 256, 512)])
 def test_gemm_f32_plain(M, N, K):
     g = torch.Generator().manual_seed(M + N + K)
@@ -52,20 +61,23 @@ def test_gemm_few_rows_kernel(M, K, N):
 
     def ok(out, ref, scale=1.0):
         return bool(((out.cpu().double() - ref).abs() <= bound * scale).all())
-    assert ok(ops.gemm(ad, wd, bias=bd), lin)
-    assert ok(ops.gemm(ad, wd), lin - bias.double())
-    assert ok(ops.gemm(ad, wd, bias=bd, act=L.ACT_QUICKGELU), O.quick_gelu(lin), 1.5)
-    assert ok(ops.gemm(ad, wd, bias=bd, residual=rd), lin + res.double())
+
+    def sk(*args, **kw):                                                                  # every call here is the few-row kernel's
+        return gemm_on(L.GEMM_ROUTE_SK, *args, **kw)[0]
+    assert ok(sk(ad, wd, bias=bd), lin)
+    assert ok(sk(ad, wd), lin - bias.double())
+    assert ok(sk(ad, wd, bias=bd, act=L.ACT_QUICKGELU), O.quick_gelu(lin), 1.5)
+    assert ok(sk(ad, wd, bias=bd, residual=rd), lin + res.double())
     x = rd.clone()
-    ops.gemm(ad, wd, bias=bd, residual=x, out=x)                                          # C aliases the residual
+    sk(ad, wd, bias=bd, residual=x, out=x)                                                # C aliases the residual
     assert ok(x, lin + res.double())
     with torch.enable_grad():
         p64 = pre.double().requires_grad_(True)
         O.quick_gelu(p64).backward(torch.ones_like(p64))
-    assert ok(ops.gemm(ad, wd, gelu_grad_of=pd), (lin - bias.double()) * p64.grad, 2.0)
+    assert ok(sk(ad, wd, gelu_grad_of=pd), (lin - bias.double()) * p64.grad, 2.0)
     ga = O.quick_gelu(a64)
     bound_g = 2e-6 * (ga.abs() @ w64.abs().t() + bias.abs().double() + res.abs().double()) + 1e-30
-    out = ops.gemm(ad, wd, bias=bd, residual=rd, a_act=L.ACT_QUICKGELU)
+    out = sk(ad, wd, bias=bd, residual=rd, a_act=L.ACT_QUICKGELU)
     assert bool(((out.cpu().double() - (ga @ w64.t() + bias.double() + res.double())).abs() <= 2 * bound_g).all())
 
 
@@ -159,7 +171,8 @@ def test_gemm_small_tiles_split_k(M, N, K, res):
     w = (torch.randn(N, K, generator=g) * 0.05).to(DEV)
     b = torch.randn(N, generator=g).to(DEV)
     r = torch.randn(M, N, generator=g).to(DEV) if res else None
-    out = ops.gemm(a, w, bias=b, residual=r)
+    out, got = gemm_on(L.GEMM_ROUTE_S64, a, w, bias=b, residual=r)
+    assert got.ksplit == 4 and got.reduce == L.GEMM_REDUCE_LAUNCH                    # (four pieces at each of these shapes)
     ref = a.double() @ w.double().t() + b.double() + (r.double() if res else 0.0)
     assert relerr(out, ref) < 2e-6 * (K / 512) ** 0.5
     out2 = ops.gemm(a, w, bias=b, residual=r)
@@ -210,18 +223,21 @@ def test_gemm_bf16():
 @pytest.mark.parametrize("M,N,K,act,res", [(33001, 2300, 768, 1, 0), (33001, 2300, 768, 0, 1), (70000, 768, 3072, 0, 1),
                                            (100864, 768, 768, 1, 1), (20000, 3072, 768, 0, 0)])
 def test_gemm_f32_w8_benchmark_shapes(M, N, K, act, res):
-    """The kernel the frame benchmark spends 87 % of its time in -- gemm_f32_w8_kernel<ACT,RES,0> (8 waves, identity rows,
-    no split-K: > 256 output tiles, K % 32 == 0) -- at ViT-B/16 sizes with ragged M / N tails, every compile-time
-    epilogue, against an fp64 CPU product of the same operands.  (test_gemm_f32_plain's shapes dispatch to the
-    64x64-tile / 4-wave kernels.)  Element-wise check: |err| <= 2e-6 * (|a|.|w| + |bias| + |res|) row/col bound."""
+    """The kernels the f32 frame benchmark spends 87 % of its time in, at ViT-B/16 sizes with ragged M / N tails, against an fp64 CPU
+    product of the same operands: with a residual gemm_f32_w8_kernel<ACT,1,0> (8 waves, identity rows, no split-K: > 256 output
+    tiles, K % 32 == 0), without one -- these shapes have >= 1024 tiles -- the strip stream gemm_f32_p256_kernel<ACT,0,0>
+    (asserted below; the 8-wave kernel's epilogues without a residual run in tests/test_gpu_gemm_routes.py).
+    (test_gemm_f32_plain's shapes dispatch to the 8-wave, 64x64-tile, few-row and generic kernels.)  Element-wise check: |err| <= 2e-6 * (|a|.|w| + |bias| + |res|) row/col bound."""
     assert ((M + 127) // 128) * ((N + 127) // 128) > 256 and K % 32 == 0
     g = torch.Generator().manual_seed(M + N + K + act + 2 * res)
     a = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) * 0.05 + torch.arange(N).view(-1, 1) * 1e-4     # asymmetric (rule 16)
     bias = torch.randn(N, generator=g)
     r = torch.randn(M, N, generator=g) if res else None
-    out = ops.gemm(a.to(DEV), w.to(DEV), bias=bias.to(DEV), act=L.ACT_QUICKGELU if act else L.ACT_NONE,
-                   residual=r.to(DEV) if res else None).cpu()
+    out, got = gemm_on(L.GEMM_ROUTE_W8 if res else L.GEMM_ROUTE_P256, a.to(DEV), w.to(DEV), bias=bias.to(DEV),
+                       act=L.ACT_QUICKGELU if act else L.ACT_NONE, residual=r.to(DEV) if res else None)
+    assert got.ksplit == 1
+    out = out.cpu()
     pre = a.double() @ w.double().t() + bias.double()
     ref = O.quick_gelu(pre) if act else pre
     if res:
@@ -263,8 +279,9 @@ def test_gemm_conv3x3_benchmark_rows(cin, cout, act, res):
     if res:
         ref = ref + r.double()
     wk = w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous()
-    out = ops.gemm(x.reshape(-1, cin).to(DEV), wk.to(DEV), bias=b.to(DEV), act=act, residual=r.to(DEV) if res else None,
-                   amap=L.AMAP_CONV3X3, gn=N, gl=Lg, cin=cin)
+    out, got = gemm_on(L.GEMM_ROUTE_W8_CONV if res else L.GEMM_ROUTE_P256, x.reshape(-1, cin).to(DEV), wk.to(DEV), bias=b.to(DEV), act=act,
+                       residual=r.to(DEV) if res else None, amap=L.AMAP_CONV3X3, gn=N, gl=Lg, cin=cin)
+    assert got.ksplit == 1
     assert relerr(out, ref) < 3e-6
     assert bool(((out.cpu().double() - ref).abs() <= 3e-6 * (mag + (r.double().abs() if res else 0))).all())
 
@@ -282,9 +299,9 @@ def test_gemm_bf16_lds_dma_path(M, N, K, act, res, obf):
         ref = O.quick_gelu(ref)
     if res:
         ref = ref + r.double()
-    out = ops.gemm(ops.cast_bf16(a.to(DEV)), ops.cast_bf16(w.to(DEV)), bias=bias.to(DEV), prec=L.PREC_BF16,
-                   act=L.ACT_QUICKGELU if act else L.ACT_NONE, residual=r.to(DEV) if res else None,
-                   out_dtype=torch.bfloat16 if obf else torch.float32)
+    out, _ = gemm_on(L.GEMM_ROUTE_DMA, ops.cast_bf16(a.to(DEV)), ops.cast_bf16(w.to(DEV)), bias=bias.to(DEV), prec=L.PREC_BF16,
+                     act=L.ACT_QUICKGELU if act else L.ACT_NONE, residual=r.to(DEV) if res else None,
+                     out_dtype=torch.bfloat16 if obf else torch.float32)
     assert relerr(out.float(), ref) < (1e-2 if obf else 1e-5)
 
 
@@ -299,8 +316,11 @@ def ring_everywhere():
 @pytest.mark.parametrize("M,N,K,act,res,obf", [(3001, 600, 768, 0, 0, 0), (2500, 512, 128, 0, 1, 0), (5000, 300, 3072, 1, 0, 1),
                                                (777, 1000, 64, 0, 1, 1), (256, 256, 64, 0, 0, 0), (70000, 520, 192, 0, 1, 0)])
 def test_gemm_bf16_ring_kernel(M, N, K, act, res, obf, ring_everywhere):
-    """persistent 256x256 LDS-DMA kernel (normally only for >= 512 tiles; forced here): ragged tiles, tile counts
-    below / above the CU count (several tiles per block), single-step K, residual-as-accumulator-init."""
+    """the persistent 256x256 LDS-DMA kernels (normally only for >= 512 tiles; forced here) -- gemm_bf16_ring_kernel where K / 64 is
+    odd, gemm_bf16_p8_kernel where it is even: ragged tiles, tile counts below / above the CU count (several tiles per block),
+    single-step K, residual-as-accumulator-init.  (5000, 300, 3072) is NOT theirs: ops.gemm brings a workspace for its 120 tiles of
+    128 x 128, K splits four ways and gemm_kernel + splitk_reduce_kernel<1> run; the p8 kernel at that shape is a row of
+    tests/gemm_ref.py's table.)"""
     g = torch.Generator().manual_seed(M + K)
     a, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
     bias, r = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
@@ -309,23 +329,39 @@ def test_gemm_bf16_ring_kernel(M, N, K, act, res, obf, ring_everywhere):
         ref = O.quick_gelu(ref)
     if res:
         ref = ref + r.double()
-    out = ops.gemm(ops.cast_bf16(a.to(DEV)), ops.cast_bf16(w.to(DEV)), bias=bias.to(DEV), prec=L.PREC_BF16,
-                   act=L.ACT_QUICKGELU if act else L.ACT_NONE, residual=r.to(DEV) if res else None,
-                   out_dtype=torch.bfloat16 if obf else torch.float32)
+    want = L.GEMM_ROUTE_GENERIC if (M, K) == (5000, 3072) else L.GEMM_ROUTE_P8 if (K // 64) % 2 == 0 else L.GEMM_ROUTE_RING
+    out, got = gemm_on(want, ops.cast_bf16(a.to(DEV)), ops.cast_bf16(w.to(DEV)), bias=bias.to(DEV), prec=L.PREC_BF16,
+                       act=L.ACT_QUICKGELU if act else L.ACT_NONE, residual=r.to(DEV) if res else None,
+                       out_dtype=torch.bfloat16 if obf else torch.float32)
+    assert got.ksplit == (4 if want == L.GEMM_ROUTE_GENERIC else 1)
     assert relerr(out.float(), ref) < (1e-2 if obf else 1e-5)
 
 
 @pytest.mark.parametrize("M,N,K", [(1078, 1536, 512), (1078, 512, 2048), (64, 128, 4096), (300, 200, 1024)])
 def test_gemm_split_k_paths(M, N, K):
-    """skinny problems take the split-K path (workspace handed over by ops.gemm); epilogue applied after the reduce."""
+    """skinny problems with the workspace ops.gemm hands over; where K splits the epilogue is applied after the reduce.  By shape:
+    (1078, 1536, 512) the 64x64-tile kernel, unsplit (it splits from K = 1024); (1078, 512, 2048) the same kernel, four pieces and a
+    reduce launch; (64, 128, 4096) and (300, 200, 1024) with the residual alone the few-row kernel, 8 / 2 pieces meeting through
+    the arrival counters; with QuickGELU AND a residual (no few-row epilogue does both) a 128x128-tile kernel -- the scratch
+    acx_gemm_scratch asks for is the few-row pieces', too small for a 128x128-tile split, so in a fresh process the 8-wave kernel
+    runs unsplit; ops.gemm hands over the WHOLE cached workspace, though, and once an earlier product has grown it gemm_kernel
+    runs with K split 16 / 8 ways and a reduce launch.  Both are asserted as what they are."""
     g = torch.Generator().manual_seed(K)
     a, w = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
     bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
     ref = O.quick_gelu(a.double() @ w.double().t() + bias.double()) + res.double()
-    out = ops.gemm(a.to(DEV), w.to(DEV), bias=bias.to(DEV), act=L.ACT_QUICKGELU, residual=res.to(DEV))
+    s64 = M == 1078
+    out, got = gemm_on(L.GEMM_ROUTE_S64 if s64 else (L.GEMM_ROUTE_W8, L.GEMM_ROUTE_GENERIC), a.to(DEV), w.to(DEV), bias=bias.to(DEV),
+                       act=L.ACT_QUICKGELU, residual=res.to(DEV))
+    if s64:
+        assert (got.ksplit, got.reduce) == ((4, L.GEMM_REDUCE_LAUNCH) if K == 2048 else (1, 0))
+    else:
+        assert (got.route, got.ksplit, got.reduce) in ((L.GEMM_ROUTE_W8, 1, 0), (L.GEMM_ROUTE_GENERIC, 16 if K == 4096 else 8, L.GEMM_REDUCE_LAUNCH))
     assert relerr(out, ref) < 3e-6
     x = res.to(DEV).clone()
-    ops.gemm(a.to(DEV), w.to(DEV), bias=bias.to(DEV), residual=x, out=x)          # in place through the reduce kernel
+    _, got = gemm_on(L.GEMM_ROUTE_S64 if s64 else L.GEMM_ROUTE_SK, a.to(DEV), w.to(DEV), bias=bias.to(DEV), residual=x, out=x)   # in place
+    assert (got.ksplit, got.reduce) == {512: (1, 0), 2048: (4, L.GEMM_REDUCE_LAUNCH), 4096: (8, L.GEMM_REDUCE_COUNTERS),
+                                        1024: (2, L.GEMM_REDUCE_COUNTERS)}[K]
     assert relerr(x, a.double() @ w.double().t() + bias.double() + res.double()) < 3e-6
 
 
