@@ -30,6 +30,8 @@ AXF_ROUTE_UNSUPPORTED, AXF_ROUTE_PADDED_MFMA, AXF_ROUTE_EXACT_MFMA, AXF_ROUTE_TH
 GEMM_ROUTE_NONE, GEMM_ROUTE_X6_TAIL_SPLIT, GEMM_ROUTE_SK, GEMM_ROUTE_X6, GEMM_ROUTE_S64, GEMM_ROUTE_P256, GEMM_ROUTE_W8 = 0, 1, 2, 3, 4, 5, 6
 GEMM_ROUTE_W8_CONV, GEMM_ROUTE_RING, GEMM_ROUTE_P8, GEMM_ROUTE_DMA_CONV, GEMM_ROUTE_DMA, GEMM_ROUTE_GENERIC = 7, 8, 9, 10, 11, 12
 GEMM_REDUCE_NONE, GEMM_REDUCE_LAUNCH, GEMM_REDUCE_COUNTERS = 0, 1, 2
+# acx_gemm_tn_route / acx_gemm_tn_x6_route (include/acx.h ACX_TN_ROUTE_*); reduce: 0 none, 1 the reduce launch, 2 images for the caller
+TN_ROUTE_NONE, TN_ROUTE_W8, TN_ROUTE_P256, TN_ROUTE_X6_256x256, TN_ROUTE_X6_256x128, TN_ROUTE_X6_128x256 = 0, 1, 2, 3, 4, 5
 
 
 class GemmDesc(C.Structure):
@@ -59,6 +61,10 @@ class GemmScratch(C.Structure):   # acx_gemm_scratch_t: what acx_gemm_scratch te
 
 class GemmRoute(C.Structure):     # acx_gemm_route_t: the route acx_gemm takes, its K pieces, how they are summed, the launch's tiles
     _fields_ = [("route", c_int32), ("ksplit", c_int32), ("reduce", c_int32), ("reserved", c_int32), ("tiles", c_int64)]
+
+
+class GemmTnRoute(C.Structure):   # acx_gemm_tn_route_t: the kernel acx_gemm_tn* / acx_gemm_tn_x6 runs, its row ranges, who sums them
+    _fields_ = [(n, c_int32) for n in ("kernel", "splits", "rows_per_split", "tiles", "reduce", "clears_zero_page")]
 
 
 class LnJob(C.Structure):     # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
@@ -286,6 +292,8 @@ _SIGS = {
     "acx_gemm_tn_x6_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_gemm_tn_x6": (C.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_int32,
                                  c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "acx_gemm_tn_route": (C.c_int, [c_void_p] + [c_int32] * 12 + [c_size_t, c_int32, c_int32, C.POINTER(GemmTnRoute)]),
+    "acx_gemm_tn_x6_route": (C.c_int, [c_void_p] + [c_int32] * 11 + [c_size_t, c_int32, C.POINTER(GemmTnRoute)]),
     "acx_ctx_grad": (C.c_int, [c_void_p] * 3 + [c_int32] * 5 + [c_void_p]),
     "acx_scatter_rows": (C.c_int, [c_void_p] * 4 + [c_int64, c_int32, c_void_p]),
     "acx_preprocess_frames": (C.c_int, [c_void_p] * 6 + [c_int32, c_void_p, c_void_p, c_int32] + [c_int32] * 5 +

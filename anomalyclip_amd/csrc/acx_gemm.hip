@@ -1651,9 +1651,18 @@ template <int CV, int NI, int W14>
 static void tn_x6_launch(int dev_slot, dim3 grid, hipStream_t s, const Args& g) {
   acx_launch_lds<gemm_x6_p4_kernel<0, 0, 0, CV, 1, 0, NI, W14>>(dev_slot, grid, dim3(256), (size_t)X6_LDS_B, s, g);
 }
-extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stride, int32_t lda, const void* B3, int64_t b_plane_stride,
-                              int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N1, int32_t N2, int32_t conv, int32_t gn, int32_t gl,
-                              int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream) {
+// acx_gemm_tn_route / acx_gemm_tn_x6_route's answer, given where the first launch would be: every gate above that point has run
+// exactly as it does for the call itself.  reduce: 0 no split, 1 the reduce launch, 2 the images stay for the caller (_parts)
+static int tn_route_dry(acx_gemm_tn_route_t* dry, int kernel, int splits, int64_t rows_per_split, int tiles, int reduce, bool clears) {
+  dry->kernel = kernel; dry->splits = splits; dry->rows_per_split = (int32_t)rows_per_split; dry->tiles = tiles;
+  dry->reduce = splits > 1 ? reduce : 0; dry->clears_zero_page = clears ? 1 : 0;
+  return ACX_OK;
+}
+// dry != nullptr (acx_gemm_tn_x6_route): the same walk, answered in *dry where the launch would be
+static int gemm_tn_x6_impl(acx_ctx* ctx, const void* A3, int64_t a_plane_stride, int32_t lda, const void* B3, int64_t b_plane_stride,
+                           int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N1, int32_t N2, int32_t conv, int32_t gn, int32_t gl,
+                           int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream,
+                           acx_gemm_tn_route_t* dry) {
   if (!A3 || !B3 || !C || !zero_page) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_tn_x6: null pointer (the zero page is required)%s");
   if (M <= 0 || N1 <= 0 || N2 <= 0) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_tn_x6: empty shape%s");
   const int mode = tn_x6_mode(N1, N2, conv, cin);
@@ -1666,6 +1675,10 @@ extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stri
   if (ctx && ctx->opt_x6_cus > 0 && ctx->opt_x6_cus < ncu) ncu = ctx->opt_x6_cus;   // ACX_OPT_X6_CUS
   const int tiles = tn_x6_tiles(mode, N1, N2);
   const int split = workspace ? tn_x6_splits(tiles, M, N1, N2, ncu, workspace_bytes) : 1;
+  const int kchunk = ((int)((M + 31) / 32) + split - 1) / split;       // K-steps of 32 rows per piece
+  if (dry)
+    return tn_route_dry(dry, mode == 1 ? ACX_TN_ROUTE_X6_256x256 : mode == 2 ? ACX_TN_ROUTE_X6_256x128 : ACX_TN_ROUTE_X6_128x256, split,
+                        (int64_t)kchunk * 32, tiles, 1, false);
   Args g;
   memset(&g, 0, sizeof(g));
   g.d.A = A3; g.d.W = B3; g.d.C = C;
@@ -1673,7 +1686,7 @@ extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stri
   g.d.a_dtype = ACX_BF16; g.d.c_dtype = ACX_F32; g.d.prec = ACX_PREC_BF16; g.d.pairs = 6;
   g.d.a_plane_stride = a_plane_stride; g.d.w_plane_stride = b_plane_stride;
   g.d.amap = conv ? ACX_AMAP_CONV3X3 : ACX_AMAP_IDENTITY; g.d.gn = gn; g.d.gl = gl; g.d.cin = cin;
-  g.ksplit = split; g.kchunk = ((int)((M + 31) / 32) + split - 1) / split; g.partial = split > 1 ? (float*)workspace : nullptr;
+  g.ksplit = split; g.kchunk = kchunk; g.partial = split > 1 ? (float*)workspace : nullptr;
   g.zeros = (const float*)zero_page;
   const int items = tiles * split;
   const dim3 xgrid((unsigned)(items < ncu ? items : ncu));
@@ -1690,6 +1703,12 @@ extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stri
   }
   ACX_CHECK_LAUNCH(ctx, "acx_gemm_tn_x6");
   return ACX_OK;
+}
+extern "C" int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stride, int32_t lda, const void* B3, int64_t b_plane_stride,
+                              int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N1, int32_t N2, int32_t conv, int32_t gn, int32_t gl,
+                              int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream) {
+  return gemm_tn_x6_impl(ctx, A3, a_plane_stride, lda, B3, b_plane_stride, ldb, C, ldc, M, N1, N2, conv, gn, gl, cin, workspace,
+                         workspace_bytes, zero_page, stream, nullptr);
 }
 
 extern "C" size_t acx_gemm_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2) {
@@ -1713,7 +1732,8 @@ extern "C" int acx_gemm_tn(acx_ctx* ctx, const float* A, int32_t lda, const floa
 // `workspace` ([splits][N1][N2] f32, image order = tn_reduce_kernel's summation order); 1: C holds the result itself
 static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc,
                         int32_t M, int32_t N1, int32_t N2, const float* b_sub, int32_t conv, int32_t gn, int32_t gl,
-                        int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, int32_t* splits_out, void* stream);
+                        int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, int32_t* splits_out, void* stream,
+                        acx_gemm_tn_route_t* dry = nullptr);
 extern "C" int acx_gemm_tn_zp(acx_ctx* ctx, const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc,
                               int32_t M, int32_t N1, int32_t N2, const float* b_sub, int32_t conv, int32_t gn, int32_t gl,
                               int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream) {
@@ -1728,7 +1748,8 @@ extern "C" int acx_gemm_tn_parts(acx_ctx* ctx, const float* A, int32_t lda, cons
 }
 static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* B, int32_t ldb, float* C, int32_t ldc,
                         int32_t M, int32_t N1, int32_t N2, const float* b_sub, int32_t conv, int32_t gn, int32_t gl,
-                        int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, int32_t* splits_out, void* stream) {
+                        int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, int32_t* splits_out, void* stream,
+                        acx_gemm_tn_route_t* dry) {
   if (!A || !B || !C) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_tn: null pointer%s");
   if (M <= 0 || N1 <= 0 || N2 <= 0) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm_tn: empty shape%s");
   if (N1 % 4 || N2 % 4 || lda % 4 || ldb % 4 || ldc != N2 || (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15))
@@ -1744,6 +1765,9 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
     while (splits > 1 && (size_t)splits * part + ztail > workspace_bytes) --splits;
     const size_t zoff = splits > 1 ? (size_t)splits * part : 0;
     if (zoff + ztail <= workspace_bytes && !(zoff & 15) && !((uintptr_t)zero_page & 15)) {
+      const int m_per_split = ((M + splits - 1) / splits + 31) / 32 * 32;
+      const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
+      if (dry) return tn_route_dry(dry, ACX_TN_ROUTE_P256, splits, m_per_split, tiles, splits_out ? 2 : 1, !zero_page);
       hipStream_t s = (hipStream_t)stream;
       AcxProfScope prof__(ctx, ACX_K_GEMM_TN, s);
       if (ctx && ctx->prof_on) { ctx->prof_gemm_flops += 2.0 * M * (double)N1 * N2; ctx->prof_tn_flops += 2.0 * M * (double)N1 * N2; }
@@ -1756,13 +1780,12 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
       g.A = A; g.B = B; g.C = splits > 1 ? (float*)workspace : C;
       g.M = M; g.N1 = N1; g.N2 = N2; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
       g.b_sub = nullptr; g.conv = conv; g.gn = gn; g.gl = gl; g.cin = cin;
-      g.m_per_split = ((M + splits - 1) / splits + 31) / 32 * 32;
+      g.m_per_split = m_per_split;
       g.sh_gl = g.sh_grid = -1;
       if (conv && !(gl & (gl - 1)) && !((gn * gl) & (gn * gl - 1))) {
         g.sh_gl = __builtin_ctz((unsigned)gl);
         g.sh_grid = __builtin_ctz((unsigned)(gn * gl));
       }
-      const int tiles = ((N1 + 255) / 256) * ((N2 + 255) / 256);
       acx_launch_lds<gemm_tn_p256_kernel>((ctx ? ctx->device : 0) & 63, dim3((unsigned)tiles, (unsigned)splits), dim3(1024), (size_t)TP_LDS_B, s, g, zeros);
       if (splits_out) *splits_out = splits;
       if (splits > 1 && !splits_out) {
@@ -1778,11 +1801,14 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
   const int splits = tn_choose_splits(M, N1, N2);
   const size_t need = splits > 1 ? (size_t)splits * N1 * N2 * sizeof(float) : 0;
   if (need > workspace_bytes || (need && !workspace)) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_gemm_tn: workspace too small%s");
+  const int m_per_split = ((M + splits - 1) / splits + 31) / 32 * 32;
+  // (the 4-wave gemm_tn_kernel of a tools build's TN_W8=0 switch is outside the query)
+  if (dry) return tn_route_dry(dry, ACX_TN_ROUTE_W8, splits, m_per_split, tiles, splits_out ? 2 : 1, false);
   TnArgs g;
   g.A = A; g.B = B; g.C = splits > 1 ? (float*)workspace : C;
   g.M = M; g.N1 = N1; g.N2 = N2; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.b_sub = b_sub; g.conv = conv; g.gn = gn; g.gl = gl; g.cin = cin;
-  g.m_per_split = ((M + splits - 1) / splits + 31) / 32 * 32;
+  g.m_per_split = m_per_split;
   g.sh_gl = g.sh_grid = -1;
   if (conv && !(gl & (gl - 1)) && !((gn * gl) & (gn * gl - 1))) {
     g.sh_gl = __builtin_ctz((unsigned)gl);
@@ -1803,5 +1829,31 @@ static int gemm_tn_impl(acx_ctx* ctx, const float* A, int32_t lda, const float* 
   }
   ACX_CHECK_LAUNCH(ctx, "acx_gemm_tn");
   return ACX_OK;
+}
+
+// Which kernel acx_gemm_tn / _zp / _parts and acx_gemm_tn_x6 run a problem on, by their own walks (no second copy of the gates):
+// include/acx.h.  The operands stand in as aligned dummy addresses that nothing dereferences.
+static void tn_route_clear(acx_gemm_tn_route_t* out) {
+  out->kernel = ACX_TN_ROUTE_NONE; out->splits = 1; out->rows_per_split = 0; out->tiles = 0; out->reduce = 0; out->clears_zero_page = 0;
+}
+extern "C" int acx_gemm_tn_route(const acx_ctx* ctx, int32_t M, int32_t N1, int32_t N2, int32_t lda, int32_t ldb, int32_t ldc,
+                                 int32_t has_b_sub, int32_t conv, int32_t gn, int32_t gl, int32_t cin, int32_t has_workspace,
+                                 size_t workspace_bytes, int32_t has_zero_page, int32_t want_parts, acx_gemm_tn_route_t* out) {
+  if (!out) return ACX_E_BADARG;
+  tn_route_clear(out);
+  int32_t parts = 0;
+  const auto at = [](uintptr_t i) { return (float*)(i << 16); };
+  return gemm_tn_impl(const_cast<acx_ctx*>(ctx), at(1), lda, at(2), ldb, at(3), ldc, M, N1, N2, has_b_sub ? at(4) : nullptr, conv, gn, gl,
+                      cin, has_workspace ? at(5) : nullptr, workspace_bytes, has_zero_page ? at(6) : nullptr,
+                      want_parts ? &parts : nullptr, nullptr, out);
+}
+extern "C" int acx_gemm_tn_x6_route(const acx_ctx* ctx, int32_t M, int32_t N1, int32_t N2, int32_t lda, int32_t ldb, int32_t ldc,
+                                    int32_t conv, int32_t gn, int32_t gl, int32_t cin, int32_t has_workspace, size_t workspace_bytes,
+                                    int32_t has_zero_page, acx_gemm_tn_route_t* out) {
+  if (!out) return ACX_E_BADARG;
+  tn_route_clear(out);
+  const auto at = [](uintptr_t i) { return (float*)(i << 16); };
+  return gemm_tn_x6_impl(const_cast<acx_ctx*>(ctx), at(1), 0, lda, at(2), 0, ldb, at(3), ldc, M, N1, N2, conv, gn, gl, cin,
+                         has_workspace ? at(5) : nullptr, workspace_bytes, has_zero_page ? at(6) : nullptr, nullptr, out);
 }
 

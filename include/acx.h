@@ -664,6 +664,32 @@ size_t acx_gemm_tn_x6_workspace_bytes(int32_t M, int32_t N1, int32_t N2);
 int acx_gemm_tn_x6(acx_ctx* ctx, const void* A3, int64_t a_plane_stride, int32_t lda, const void* B3, int64_t b_plane_stride,
                    int32_t ldb, float* C, int32_t ldc, int32_t M, int32_t N1, int32_t N2, int32_t conv, int32_t gn, int32_t gl,
                    int32_t cin, void* workspace, size_t workspace_bytes, const void* zero_page, void* stream);
+/* acx_gemm_tn_route / acx_gemm_tn_x6_route: which kernel acx_gemm_tn / _zp / _parts (acx_gemm_tn_x6) runs a problem on and how it
+ * splits the rows -- answered by the entry points' own walk, which stops where the first launch would be (there is no second copy
+ * of the gates).  Host arithmetic, no device, nothing launched.  The operands stand in as aligned dummy addresses: has_b_sub /
+ * has_workspace / has_zero_page say which optional ones the caller brings, want_parts != 0 asks for acx_gemm_tn_parts.  The
+ * pointer (and plane stride) alignment refusals are therefore the real calls' alone.  Returns what the call would return before its
+ * first launch: ACX_OK, or the refusal's ACX_E_* with the same text in acx_last_error (*out is then kernel = ACX_TN_ROUTE_NONE,
+ * splits = 1).  ctx == NULL: 256 CUs and the option values acx_create sets.
+ *   kernel            ACX_TN_ROUTE_W8 (gemm_tn_w8_kernel, 128 x 128 tiles), _P256 (gemm_tn_p256_kernel, 256 x 256), _X6_* (the
+ *                     plane kernel's three tile geometries, N1 x N2).  The 4-wave gemm_tn_kernel behind a tools build's debug
+ *                     switch is not reported: such a build answers W8
+ *   splits            row ranges across workgroups (1: none; C is then written by the kernel itself)
+ *   rows_per_split    rows of a range (the last takes what is left; under P256 a trailing range can be empty and stores zeros)
+ *   tiles             output tiles in the kernel's tile size
+ *   reduce            0 no split; 1 a reduce launch sums the images in image order; 2 they stay in the workspace for the caller
+ *   clears_zero_page  1: P256 without a caller's zero page clears 1 KB behind the images in the workspace with a launch of its own */
+enum { ACX_TN_ROUTE_NONE = 0, ACX_TN_ROUTE_W8 = 1, ACX_TN_ROUTE_P256 = 2, ACX_TN_ROUTE_X6_256x256 = 3, ACX_TN_ROUTE_X6_256x128 = 4,
+       ACX_TN_ROUTE_X6_128x256 = 5 };
+typedef struct acx_gemm_tn_route_t {
+  int32_t kernel, splits, rows_per_split, tiles, reduce, clears_zero_page;
+} acx_gemm_tn_route_t;
+int acx_gemm_tn_route(const acx_ctx* ctx, int32_t M, int32_t N1, int32_t N2, int32_t lda, int32_t ldb, int32_t ldc, int32_t has_b_sub,
+                      int32_t conv, int32_t gn, int32_t gl, int32_t cin, int32_t has_workspace, size_t workspace_bytes,
+                      int32_t has_zero_page, int32_t want_parts, acx_gemm_tn_route_t* out);
+int acx_gemm_tn_x6_route(const acx_ctx* ctx, int32_t M, int32_t N1, int32_t N2, int32_t lda, int32_t ldb, int32_t ldc, int32_t conv,
+                         int32_t gn, int32_t gl, int32_t cin, int32_t has_workspace, size_t workspace_bytes, int32_t has_zero_page,
+                         acx_gemm_tn_route_t* out);
 int acx_reduce_rows(acx_ctx* ctx, const float* part, float* out, int32_t nparts, int32_t width, void* stream);
 /* LayerNorm / ChanLayerNorm backward.  dx (may be NULL) = [add +] dx_scale * dL/dx (add [rows, D] may be NULL: the
  * residual branch of a pre-norm block, clip/model.py:214-216, folded into the same pass); part (may be NULL)
