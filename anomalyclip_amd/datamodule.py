@@ -123,8 +123,9 @@ class ResidentTestLoader(StreamedTestLoader):
 
 
 class AnomalyCLIPDataModule:
-    def __init__(self, encoder=None, decode: str = "pil", **hparams):
+    def __init__(self, encoder=None, decode: str = "pil", pack: bool = False, **hparams):
         from .jpeg import check_decode
+        self.pack = bool(pack)                                    # frames mode: FeatureBank.from_frames(pack=...) (not a reference key)
         self.decode = check_decode(decode)                        # frames mode: how the frame files are decoded (not a reference key)
         hp = dict(_DEFAULTS)
         hp.update(hparams)                                        # unknown keys are kept, like save_hyperparameters does
@@ -182,7 +183,7 @@ class AnomalyCLIPDataModule:
         try:
             return FeatureBank.from_frames(enc, records, hp.frames_root, hp.image_tmpl, int(hp.ncrops), hp.get("scale_size"),
                                            int(hp.get("decode_threads", 8)), self.device, hp.get("max_bytes"), hp.get("log"),
-                                           decode=self.decode)
+                                           decode=self.decode, pack=self.pack)
         finally:
             enc.train(was_training)
 

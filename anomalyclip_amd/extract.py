@@ -9,15 +9,22 @@ into a pinned `[T * ncrops, D]` buffer.  A batch is `max(1, chunk // ncrops)` fr
 rows; decoding batch k + 1 overlaps the GPU's work on batch k.  `decode="gpu"` (`--decode gpu`) leaves only the Huffman decoding of
 baseline JPEG files on the host and reconstructs the frames on the device (anomalyclip_amd/jpeg.py): the same bytes, the same files.
 
+`pack=True` (`--pack`) is for datasets of many short clips: `encode_videos` cuts ALL videos' frames into full launches
+(`plan_launches`), decodes launch k + 1 while launch k is encoded whichever videos they belong to, and `extract_dataset` has a
+`FeatureWriter` thread write the files behind the encode loop.  Off by default; with it off every call runs the per-video loop above.
+
     python -m anomalyclip_amd.extract --arch ViT-B/16 --weights last.ckpt --frames-root frames --out-root features --ncrops 5
 """
 from __future__ import annotations
 
 import os
+import queue
 import re
 import sys
+import threading
+from collections import deque
 from concurrent.futures import ThreadPoolExecutor
-from typing import Iterator, List, Optional, Sequence, Tuple
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -81,6 +88,7 @@ class FrameFolderReader:
         self._buf = [None, None]
         self.copied = [None, None]      # per slot: the consumer's event after the copy that READ the buffer (set by the consumer)
         self._pool = None
+        self._borrowed = False
         self._size = None
 
     def __len__(self) -> int:
@@ -103,10 +111,16 @@ class FrameFolderReader:
             self._pool = ThreadPoolExecutor(max_workers=self.threads)
         return self._pool
 
+    def borrow(self, pool: ThreadPoolExecutor, side=None) -> None:
+        """decode on `pool`, which stays its owner's: `close()` leaves it running (encode_videos lends one pool to every reader
+        of a run).  `side`: the owner's copy stream, for the readers that put work on one"""
+        self.close()
+        self._pool, self._borrowed = pool, True
+
     def close(self):
-        if self._pool is not None:
+        if self._pool is not None and not self._borrowed:
             self._pool.shutdown(wait=True)
-            self._pool = None
+        self._pool, self._borrowed = None, False
 
     def _decode(self, i: int, dst: np.ndarray):
         from PIL import Image
@@ -135,6 +149,13 @@ class FrameFolderReader:
     def decode_batch(self, i0: int, i1: int, slot: int) -> torch.Tensor:
         """the host stage of one batch, on its own (measurements): frames i0 ... i1 - 1 decoded into the slot's buffer"""
         return self._fill(i0, i1, slot)
+
+    def decode_into(self, i0: int, i1: int, dst: np.ndarray) -> list:
+        """frames i0 ... i1 - 1 into the caller's uint8 [i1 - i0, H, W, 3] `dst`, on the pool: the futures, one per frame, so that
+        the caller can have several videos' frames decoded at once and wait for all of them"""
+        assert dst.shape == (i1 - i0, *self.frame_size, 3) and dst.dtype == np.uint8, (dst.shape, dst.dtype)
+        pool = self.pool()
+        return [pool.submit(self._decode, i0 + j, dst[j]) for j in range(i1 - i0)]
 
     def batches(self, n: int) -> Iterator[Tuple[int, torch.Tensor]]:
         """(slot, uint8 [k, H, W, 3]) for consecutive groups of n frames; batch k + 1 is being decoded while k is consumed.  The
@@ -200,6 +221,66 @@ def write_features(out_path: str, rows: np.ndarray) -> str:
         np.save(fh, rows, allow_pickle=False)
     os.replace(tmp, p)
     return p
+
+
+class FeatureWriter:
+    """One thread that writes feature files behind the encode loop (`extract_dataset(pack=True)`).  `acquire()` takes one of
+    `max_inflight` places for a video's row buffer and blocks while all are taken; `submit(event, rows, out_path)` hands the
+    filled buffer over: the thread waits for `event` (anything with `synchronize()`, or None), calls `write_features` and gives
+    the place back.  The first exception is kept: every job behind it is dropped unwritten (its place is still given back, so
+    the producer never waits for a dead writer), the `.npy.tmp` of the failed write is removed, and `check()` / `close()`
+    raise it in the caller's thread -- `close()` after the thread has been joined."""
+
+    def __init__(self, max_inflight: int = 4, done=None):
+        self.error = None
+        self._done = done                              # called in the writer thread after each file: done(tag)
+        self._places = threading.Semaphore(max(1, int(max_inflight)))
+        self._jobs = queue.SimpleQueue()
+        self._thread = threading.Thread(target=self._run, name="acx-feature-writer", daemon=True)
+        self._thread.start()
+
+    def acquire(self) -> None:
+        self._places.acquire()
+        self.check()
+
+    def submit(self, event, rows, out_path: str, tag=None) -> None:
+        self._jobs.put((event, rows, out_path, tag))
+
+    def check(self) -> None:
+        if self.error is not None:
+            raise self.error
+
+    def _run(self):
+        while True:
+            job = self._jobs.get()
+            if job is None:
+                return
+            event, rows, out_path, tag = job
+            try:
+                if self.error is None:
+                    if event is not None:
+                        event.synchronize()
+                    write_features(out_path, rows.numpy() if isinstance(rows, torch.Tensor) else rows)
+                    if self._done is not None:
+                        self._done(tag)
+            except BaseException as e:                  # (kept for the caller; the thread goes on giving places back)
+                self.error = e
+                try:
+                    os.remove(feature_path(out_path) + ".tmp")
+                except OSError:
+                    pass
+            finally:
+                del job, rows
+                self._places.release()
+
+    def close(self, check: bool = True) -> None:
+        """every job handed over so far is written (or dropped behind a failure), the thread is joined, then `check()`"""
+        if self._thread is not None:
+            self._jobs.put(None)
+            self._thread.join()
+            self._thread = None
+        if check:
+            self.check()
 
 
 # ---------------------------------------------------------------------------------------------------------------- extractor
@@ -281,6 +362,371 @@ def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: O
     return {"written": True, "frames": T, "rows": shape[0]}
 
 
+# ---------------------------------------------------------------------------------------------------------------- packed
+SLOT_ALIGN = 256        # a group's first byte in a launch's frame buffer: the crop kernel reads whole 16-byte blocks from its base
+
+
+def _iter_launches(lengths: Iterable[int], nb: int) -> Iterator[List[Tuple[int, int, int]]]:
+    """plan_launches' launches, made as the lengths arrive: the next video's length is asked for only once the launch being
+    filled has room for its first frame, so a full launch is out before the video behind it has to be opened"""
+    launch, room = [], nb
+    for v, T in enumerate(lengths):
+        i = 0
+        while i < T:
+            k = min(room, T - i)
+            launch.append((v, i, i + k))
+            i, room = i + k, room - k
+            if room == 0:
+                yield launch
+                launch, room = [], nb
+    if launch:
+        yield launch
+
+
+def plan_launches(lengths: Sequence[int], ncrops: int, chunk: int) -> List[List[Tuple[int, int, int]]]:
+    """The encoder launches of a packed run over videos of `lengths[v]` frames, in extraction order: each launch a list of pieces
+    (v, i0, i1) -- frames i0 ... i1 - 1 of video v -- in video order, then frame order.  Every frame is in exactly one piece; a
+    launch holds `max(1, chunk // ncrops)` frames (batch_frames), only the last one may hold fewer; a video without frames has no
+    piece.  For one video these are encode_video's batches."""
+    return list(_iter_launches([int(T) for T in lengths], max(1, int(chunk) // int(ncrops))))
+
+
+class _Opener:
+    """The run's readers, opened on the pool (listing a folder is host work like decoding) up to `lookahead` videos ahead of the
+    one being decoded.  The iterable is advanced by one pool task at a time: it may be a generator."""
+
+    def __init__(self, readers, pool: ThreadPoolExecutor, lookahead: int):
+        self.it, self.pool, self.lookahead = iter(readers), pool, max(0, int(lookahead))
+        self.ready, self.fut, self.exhausted = deque(), None, False
+
+    def _open(self, n: int):
+        got = []
+        for _ in range(n):
+            try:
+                got.append(next(self.it))
+            except StopIteration:
+                return got, None, True
+            except BaseException as e:                  # (what was opened before it is still handed over, then the error)
+                return got, e, True
+        return got, None, False
+
+    def _collect(self):
+        got, err, end = self.fut.result()
+        self.fut = None
+        self.ready.extend(got)
+        self.exhausted |= end
+        if err is not None:
+            self.error = err
+
+    error = None
+
+    def top_up(self):
+        if self.fut is not None and self.fut.done():
+            self._collect()
+        if self.fut is None and not self.exhausted and len(self.ready) < self.lookahead:
+            self.fut = self.pool.submit(self._open, self.lookahead - len(self.ready))
+
+    def next(self):
+        """the next (key, reader), or None after the last"""
+        while True:
+            if self.ready:
+                item = self.ready.popleft()
+                self.top_up()
+                return item
+            if self.fut is not None:
+                self._collect()
+            elif self.error is not None:
+                raise self.error
+            elif self.exhausted:
+                return None
+            else:
+                self.fut = self.pool.submit(self._open, max(1, self.lookahead))
+
+    def close(self):
+        if self.fut is not None:
+            self._collect()
+        for _, reader in self.ready:
+            reader.close()
+        self.ready.clear()
+
+
+class _Piece:
+    __slots__ = ("key", "reader", "i0", "i1", "off", "nbytes", "hw", "token")
+
+
+class _Launch:
+    __slots__ = ("slot", "host", "frames_dev", "pieces")
+
+
+class _LaunchFeeder(threading.Thread):
+    """The host side of encode_videos, one launch ahead of the encode: this thread opens the readers, cuts their frames into
+    launches (_iter_launches) and has every piece of a launch decoded on the shared pool -- a FrameFolderReader's into the
+    launch's slot of the pinned ring, a device reader's (jpeg.py) through its own pinned buffers into the launch's device frame
+    buffer.  It starts on launch k + 1 when the consumer takes launch k, whichever videos the two belong to."""
+
+    def __init__(self, readers, pool, lookahead: int, nb: int, dev, side):
+        super().__init__(name="acx-launch-feeder", daemon=True)
+        self.opener = _Opener(readers, pool, lookahead)
+        self.pool, self.nb, self.dev, self.side = pool, nb, dev, side
+        self.pinned = True
+        self.ring = [None, None, None]                 # the pinned uint8 ring: three slots of one launch's frames
+        self.copied = [None, None, None]               # per slot: the consumer's event after the copies that READ it
+        self.frame_bytes = 0                           # the largest frame met so far
+        self.active = []                               # v -> (key, reader), None once the video's last frame is decoded
+        self._out = queue.SimpleQueue()
+        self._credit = threading.Semaphore(1)
+        self._halt = False
+
+    # ------------------------------------------------------------------------------------------------------------ consumer
+    def take(self) -> Optional[_Launch]:
+        """the next decoded launch (None after the last; the feeder's exception is raised here), and leave to decode another"""
+        item = self._out.get()
+        if isinstance(item, BaseException):
+            raise item
+        self._credit.release()
+        return item
+
+    def stop(self):
+        self._halt = True
+        self._credit.release()
+        if self.is_alive():
+            self.join()
+        self.opener.close()
+        for kr in self.active:
+            if kr is not None:
+                kr[1].close()
+        self.active = []
+
+    # ------------------------------------------------------------------------------------------------------------ thread
+    def _lengths(self):
+        while True:
+            kr = self.opener.next()
+            if kr is None:
+                return
+            kr[1].borrow(self.pool, self.side)
+            self.active.append(kr)
+            yield len(kr[1])
+
+    def _slot(self, k: int) -> Tuple[int, torch.Tensor]:
+        s = k % 3
+        if self.copied[s] is not None:                 # the copies that read this slot three launches ago must be over
+            self.copied[s].synchronize()
+            self.copied[s] = None
+        need = self.nb * (-(-self.frame_bytes // SLOT_ALIGN) * SLOT_ALIGN + SLOT_ALIGN)
+        if self.ring[s] is None or self.ring[s].numel() < need:
+            buf = torch.empty(need, dtype=torch.uint8)
+            self.ring[s] = buf.pin_memory() if self.pinned else buf
+        return s, self.ring[s]
+
+    def _decode(self, k: int, plan) -> _Launch:
+        L = _Launch()
+        L.pieces, off, prev = [], 0, None
+        for v, i0, i1 in plan:
+            p = _Piece()
+            p.key, p.reader = self.active[v]
+            p.i0, p.i1, p.hw, p.token = i0, i1, tuple(p.reader.frame_size), None
+            kind = (p.hw, bool(getattr(p.reader, "device_frames", False)))
+            if kind != prev or kind[1]:                # a new group: host pieces of one geometry side by side are one block of
+                off = -(-off // SLOT_ALIGN) * SLOT_ALIGN    # frames; a device decoder's piece starts on a boundary of its own
+                prev = kind
+            p.off, p.nbytes = off, (i1 - i0) * p.hw[0] * p.hw[1] * 3
+            off += p.nbytes
+            self.frame_bytes = max(self.frame_bytes, p.hw[0] * p.hw[1] * 3)
+            L.pieces.append(p)
+        total = -(-off // SLOT_ALIGN) * SLOT_ALIGN
+        with torch.cuda.stream(self.side):
+            L.frames_dev = torch.empty(total, dtype=torch.uint8, device=self.dev)
+        L.slot, L.host = None, None
+        host = [p for p in L.pieces if not getattr(p.reader, "device_frames", False)]
+        futs = []
+        if host:
+            L.slot, ring = self._slot(k)
+            L.host = ring[:total]
+            flat = L.host.numpy()
+            for p in host:
+                dst = flat[p.off:p.off + p.nbytes].reshape(p.i1 - p.i0, p.hw[0], p.hw[1], 3)
+                futs += p.reader.decode_into(p.i0, p.i1, dst)
+        for p in L.pieces:
+            if p not in host:                          # (their frames are being decoded on the pool's other threads meanwhile)
+                dst = L.frames_dev[p.off:p.off + p.nbytes].view(p.i1 - p.i0, p.hw[0], p.hw[1], 3)
+                p.token = p.reader.decode_into(p.i0, p.i1, dst)
+        err = None
+        for f in futs:                                 # every frame is waited for: none is written after the launch is let go
+            try:
+                f.result()
+            except BaseException as e:
+                err = err or e
+        if err is not None:
+            raise err
+        for v, i0, i1 in plan:
+            if i1 == len(self.active[v][1]):
+                self.active[v] = None                  # (the pieces hold the reader until the consumer is through with them)
+        return L
+
+    def run(self):
+        try:
+            torch.cuda.set_device(self.dev)
+            plans = _iter_launches(self._lengths(), self.nb)
+            k = 0
+            while True:
+                self._credit.acquire()                 # (before the launch is planned: planning may open a reader)
+                if self._halt:
+                    return
+                plan = next(plans, None)
+                if plan is None:
+                    break
+                self.opener.top_up()
+                self._out.put(self._decode(k, plan))
+                k += 1
+            self._out.put(None)
+        except BaseException as e:
+            self._out.put(e)
+
+
+def encode_videos(encoder, readers, ncrops: int = 1, scale_size: Optional[int] = None, lookahead: int = 2,
+                  decode_threads: int = 8) -> Iterator[Tuple[object, int, torch.Tensor]]:
+    """encode_video over many videos with the encoder kept full across their boundaries.  `readers`: an iterable of
+    (key, reader), opened lazily (a generator: beside the readers of the launch being encoded and of the launch being decoded, at
+    most `lookahead` are open ahead of them, and a reader is closed after its last frame).  Yields (key, row0, rows): `rows` float32 [k * ncrops, D] on the device, queued on the current
+    stream, the rows row0 ... of video `key`'s [T * ncrops, D] table -- in video order, then row order.
+
+    The launches are plan_launches': every one but the last holds batch_frames(encoder, ncrops) frames, of as many videos as it
+    takes, and is ONE encoder call.  A launch's frames are decoded while the launch before it is encoded, by one pool of
+    `decode_threads` threads (at most MAX_DECODE_THREADS) that also opens the readers, into one pinned uint8 ring of three
+    slots that lasts the whole run (device readers: through their own pinned buffers).  Pieces of one frame size side by side
+    are one group: one copy (or the device decoder's launches) into the launch's frame buffer and one preprocess_crops call into
+    the group's slice of the launch's [rows, 3, R, R] input.  Ordering is by events only: nothing here synchronises the device."""
+    from .preprocess import preprocess_crops
+    encoder = _encoder_of(encoder)
+    check_encoder(encoder)
+    R = int(encoder.input_resolution)
+    dev = next(encoder.parameters()).device
+    cur = torch.cuda.current_stream(dev)
+    side = torch.cuda.Stream(device=dev)
+    pool = ThreadPoolExecutor(max_workers=max(1, min(int(decode_threads), MAX_DECODE_THREADS)), thread_name_prefix="acx-decode")
+    feeder = _LaunchFeeder(readers, pool, lookahead, batch_frames(encoder, ncrops), dev, side)
+    try:
+        feeder.start()
+        while True:
+            L = feeder.take()
+            if L is None:
+                break
+            groups = []                                # [off, frames, (H, W)]: runs of pieces in one block of the frame buffer
+            for p in L.pieces:
+                if groups and groups[-1][0] + groups[-1][1] * groups[-1][2][0] * groups[-1][2][1] * 3 == p.off and groups[-1][2] == p.hw:
+                    groups[-1][1] += p.i1 - p.i0
+                else:
+                    groups.append([p.off, p.i1 - p.i0, p.hw])
+            if L.host is not None:
+                with torch.cuda.stream(side):
+                    for p in L.pieces:
+                        if p.token is None:
+                            L.frames_dev[p.off:p.off + p.nbytes].copy_(L.host[p.off:p.off + p.nbytes], non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+                feeder.copied[L.slot] = ev
+                cur.wait_event(ev)
+            for p in L.pieces:
+                if p.token is not None:
+                    p.reader.finish_into(p.token)      # (makes the current stream wait for the piece's frames)
+            L.frames_dev.record_stream(cur)
+            nrows = sum(g[1] for g in groups) * ncrops
+            with torch.no_grad():                      # (per launch: a grad mode held across a yield would reach the consumer)
+                x = torch.empty(nrows, 3, R, R, dtype=torch.float32, device=dev)
+                r = 0
+                for off, n, (H, W) in groups:
+                    preprocess_crops(L.frames_dev[off:off + n * H * W * 3].view(n, H, W, 3), R, scale_size, ncrops,
+                                     out=x[r:r + n * ncrops])
+                    r += n * ncrops
+                rows = encoder(x)
+            assert rows.shape[0] == nrows, (rows.shape, nrows)
+            r = 0
+            for p in L.pieces:
+                n = (p.i1 - p.i0) * ncrops
+                yield p.key, p.i0 * ncrops, rows[r:r + n]
+                r += n
+                if p.i1 == len(p.reader):
+                    p.reader.close()
+    finally:
+        feeder.stop()
+        pool.shutdown(wait=True)
+
+
+class _InOrder:
+    """log lines that arrive in any order, from any thread, given to `log` in video order"""
+
+    def __init__(self, log):
+        self.log, self.pending, self.next, self.lock = log, {}, 0, threading.Lock()
+
+    def put(self, idx: int, line: str):
+        with self.lock:
+            self.pending[idx] = line
+            while self.next in self.pending:
+                line = self.pending.pop(self.next)
+                self.next += 1
+                if self.log:
+                    self.log(line)
+
+
+def _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scale_size, overwrite, template, decode_threads, log,
+                            decode, max_inflight) -> dict:
+    """extract_dataset(pack=True): encode_videos over the videos whose files are not complete; each video's rows are copied into a
+    pinned buffer of its own, at most `max_inflight` of them alive, and written by a FeatureWriter behind the encode loop"""
+    from . import jpeg
+    check_eval_mode(encoder)
+    D = int(encoder.output_dim)
+    todo, results, lines = {}, {}, _InOrder(log)
+
+    def line(idx, video):
+        written, _, rows = results[idx]
+        return f"{'wrote' if written else 'kept '} {feature_path(os.path.join(out_root, video))}  [{rows} rows]"
+
+    def readers():
+        for idx, (video, start, end) in enumerate(videos):
+            reader = jpeg.make_reader(decode, frames_root, video, start, end, template, decode_threads)
+            T, out_path = len(reader), os.path.join(out_root, video)
+            if not overwrite and is_complete(out_path, (T * ncrops, D)):
+                reader.close()
+                results[idx] = (False, T, T * ncrops)
+                lines.put(idx, line(idx, video))
+                continue
+            todo[idx] = (video, out_path, T)
+            yield idx, reader
+
+    def written(idx):
+        video, _, T = todo[idx]
+        results[idx] = (True, T, T * ncrops)
+        lines.put(idx, line(idx, video))
+
+    writer = FeatureWriter(max_inflight, done=written)
+    gen = encode_videos(encoder, readers(), ncrops, scale_size, decode_threads=decode_threads)
+    cur_idx, out = None, None
+    try:
+        for idx, r0, rows in gen:
+            _, out_path, T = todo[idx]
+            if idx != cur_idx:
+                writer.acquire()                       # (blocks while max_inflight videos' buffers are alive)
+                cur_idx, out = idx, torch.empty((T * ncrops, D), dtype=torch.float32).pin_memory()
+            out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
+            if r0 + rows.shape[0] == T * ncrops:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(rows.device))
+                writer.submit(ev, out, out_path, idx)
+                out = None
+    finally:
+        gen.close()
+        writer.close(check=False)
+    writer.check()
+    counts = {"written": 0, "skipped": 0, "frames": 0, "rows": 0}
+    for idx in sorted(results):
+        w, T, rows = results[idx]
+        counts["written" if w else "skipped"] += 1
+        if w:
+            counts["frames"] += T
+            counts["rows"] += rows
+    return counts
+
+
 def list_videos(frames_root: str, template: str = TEMPLATE) -> List[str]:
     """every folder under frames_root that holds a file matching the template, relative to it, sorted"""
     rx = _template_regex(template)
@@ -294,10 +740,14 @@ def list_videos(frames_root: str, template: str = TEMPLATE) -> List[str]:
 
 def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root: str, out_root: str, ncrops: int = 1,
                     scale_size: Optional[int] = None, overwrite: bool = False, template: str = TEMPLATE,
-                    decode_threads: int = 8, log=None, decode: str = "pil") -> dict:
+                    decode_threads: int = 8, log=None, decode: str = "pil", pack: bool = False, max_inflight: int = 4) -> dict:
     """Every video of the annotation file (rows `path start end label...`; without one: every frame folder under frames_root)
     -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  decode: "pil" (Pillow on the host), "gpu" (baseline
-    JPEG reconstructed on the device; every other file through Pillow) or "gpu_entropy" (its Huffman decoding on the device too).  Returns {written, skipped, frames, rows}."""
+    JPEG reconstructed on the device; every other file through Pillow) or "gpu_entropy" (its Huffman decoding on the device too).
+    pack: the videos share encoder launches (encode_videos: every launch but the last is full, and the next video is decoded
+    while this one is encoded) and the files are written by a thread behind the encode loop, at most `max_inflight` videos'
+    rows waiting for it; the same files to round-off, the same counts and log lines.
+    Returns {written, skipped, frames, rows}."""
     from . import jpeg
     jpeg.check_decode(decode)
     encoder = _encoder_of(net_or_encoder)
@@ -305,6 +755,9 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
         videos = read_annotations(annotation_file)
     else:
         videos = [(v, None, None) for v in list_videos(frames_root, template)]
+    if pack:
+        return _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scale_size, overwrite, template,
+                                       decode_threads, log, decode, max_inflight)
     counts = {"written": 0, "skipped": 0, "frames": 0, "rows": 0}
     for video, start, end in videos:
         reader = jpeg.make_reader(decode, frames_root, video, start, end, template, decode_threads)
@@ -369,6 +822,8 @@ def _parser():
     p.add_argument("--decode", default="pil", choices=("pil", "gpu", "gpu_entropy"),
                    help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device; "
                         "gpu_entropy: the Huffman decoding on the device too")
+    p.add_argument("--pack", action="store_true",
+                   help="share encoder launches between videos and write the files behind the encode loop (many short clips)")
     return p
 
 
@@ -402,7 +857,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     load_encoder_weights(enc, a.arch, a.weights)
     enc = enc.to(torch.device("cuda", torch.cuda.current_device())).eval()
     counts = extract_dataset(enc, a.annotations, a.frames_root, a.out_root, a.ncrops, a.scale_size, a.overwrite,
-                             log=lambda s: print(s, file=sys.stderr), decode=a.decode)
+                             log=lambda s: print(s, file=sys.stderr), decode=a.decode, pack=a.pack)
     import json
     print(json.dumps(counts))
     return 0

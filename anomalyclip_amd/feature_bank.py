@@ -61,14 +61,15 @@ class FeatureBank:
     @classmethod
     def from_frames(cls, encoder, records, frames_root: str, image_tmpl: str = "{:06d}.jpg", ncrops: int = 1,
                     scale_size: Optional[int] = None, decode_threads: int = 8, device: Optional[torch.device] = None,
-                    max_bytes: Optional[int] = None, log=None, decode: str = "pil") -> "FeatureBank":
+                    max_bytes: Optional[int] = None, log=None, decode: str = "pil", pack: bool = False) -> "FeatureBank":
         """The same bank, filled by the CLIP image encoder instead of from files: every frame an annotation row names
         (`records`: objects with `video`, `start_frame`, `end_frame`, `label`; frame t of video v is
         `<frames_root>/<video>/image_tmpl.format(t + start_frame)`, end inclusive) is decoded and encoded ONCE through
         extract.encode_video -- the launches `extract_video` makes, so the rows are the rows of the file it would write -- and each
         block of rows is copied from the encoder's output straight into its bank slice.  `paths` are the frame folders,
         `file_frames == num_frames`.  The size follows from the rows and `encoder.output_dim` and is checked before any frame is
-        opened.  decode: "pil", "gpu" or "gpu_entropy", as extract.extract_dataset takes it."""
+        opened.  decode: "pil", "gpu" or "gpu_entropy", as extract.extract_dataset takes it.  pack: the videos share encoder
+        launches (extract.encode_videos), each piece of rows copied into its video's bank slice: the same bank to round-off."""
         from . import extract as X
         from . import jpeg
         jpeg.check_decode(decode)
@@ -106,7 +107,9 @@ class FeatureBank:
             raise ValueError(f"FeatureBank.from_frames: the encoder is on {self.device}, the bank was asked for on {device}")
         self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            for v, r in enumerate(records):
+            if pack:
+                self._fill_packed(encoder, records, str(frames_root), image_tmpl, scale_size, decode_threads, decode, log, rows)
+            for v, r in enumerate(() if pack else records):
                 reader = jpeg.make_reader(decode, str(frames_root), r.video, int(r.start_frame), int(r.end_frame), image_tmpl,
                                           decode_threads)
                 try:
@@ -123,6 +126,28 @@ class FeatureBank:
         self.frames = torch.tensor(self.file_frames, dtype=torch.int32).to(self.device)
         self.labels = torch.from_numpy(self.labels_host).to(self.device)
         return self
+
+    def _fill_packed(self, encoder, records, frames_root, image_tmpl, scale_size, decode_threads, decode, log, rows) -> None:
+        """from_frames(pack=True): one extract.encode_videos run over every video; the bank's slices take the rows"""
+        from . import extract as X
+        from . import jpeg
+
+        def readers():
+            for v, r in enumerate(records):
+                yield v, jpeg.make_reader(decode, frames_root, r.video, int(r.start_frame), int(r.end_frame), image_tmpl,
+                                          decode_threads)
+
+        gen = X.encode_videos(encoder, readers(), self.ncrops, scale_size, decode_threads=decode_threads)
+        try:
+            for v, r0, blk in gen:
+                self.video(v)[r0:r0 + blk.shape[0]].copy_(blk)
+                if log and r0 + blk.shape[0] == rows[v]:
+                    log(f"encoded {self.paths[v]}  [{rows[v]} rows]")
+        except FileNotFoundError as e:
+            raise FileNotFoundError(f"frame file {e.filename} is missing (the annotation rows name every frame start ... end "
+                                    f"of their videos)") from e
+        finally:
+            gen.close()
 
     def fill_video(self, encoder, v: int, frames, scale_size: Optional[int] = None) -> None:
         """encodes the frames of video v (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into its bank rows: every

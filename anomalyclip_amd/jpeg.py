@@ -96,6 +96,15 @@ class JpegFolderReader(FrameFolderReader):
         self._done = [None, None]          # per slot: the event after the copies that READ the pinned buffers
         self._side = None
         self._lock = threading.Lock()
+        self._turn = 0                     # decode_into: the slot of the next piece
+
+    device_frames = True                   # decode_into / finish_into leave the frames in a DEVICE tensor of the caller's
+
+    def borrow(self, pool: ThreadPoolExecutor, side=None) -> None:
+        """FrameFolderReader.borrow; the copies and the decoder's kernels go on the lender's `side` stream"""
+        super().borrow(pool)
+        if side is not None:
+            self._side = side
 
     # ------------------------------------------------------------------------------------------------------------ host
     @property
@@ -167,16 +176,31 @@ class JpegFolderReader(FrameFolderReader):
             return None, None, ok
         return self._coef[slot][:n], self._qt[slot][:n], ok
 
+    def decode_into(self, i0: int, i1: int, dst: torch.Tensor):
+        """the host stage of frames i0 ... i1 - 1, meant for the caller's DEVICE uint8 [i1 - i0, H, W, 3] `dst` (a slice of a
+        launch that holds other videos' frames too): on the thread that decodes ahead, through this reader's two slots of
+        pinned buffers in rotation.  -> what finish_into takes, on the consumer's thread, at most one piece later"""
+        assert dst.is_cuda and dst.dtype == torch.uint8 and dst.shape == (i1 - i0, *self.frame_size, 3) and dst.is_contiguous()
+        slot, self._turn = self._turn, self._turn ^ 1
+        return (slot, dst) + tuple(self._fill(i0, i1, slot))
+
+    def finish_into(self, token) -> torch.Tensor:
+        """the device stage of decode_into's piece: its frames are in `dst` for the current stream"""
+        slot, dst, n, ok = token
+        return self._launch(slot, n, ok, out=dst)
+
     # ------------------------------------------------------------------------------------------------------------ device
-    def _launch(self, slot: int, n: int, ok) -> torch.Tensor:
-        """the batch in the slot's pinned buffers -> uint8 [n, H, W, 3] on the device, ready for the current stream"""
+    def _launch(self, slot: int, n: int, ok, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the batch in the slot's pinned buffers -> uint8 [n, H, W, 3] on the device (`out`, if the caller has a place for it),
+        ready for the current stream"""
         dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
         H, W = self.frame_size
         cur = torch.cuda.current_stream(dev)
         if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         with torch.cuda.device(dev), torch.cuda.stream(self._side):
-            out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+            if out is None:
+                out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
             if any(ok):
                 coef = self._coef[slot][:n].to(dev, non_blocking=True)
                 qt = self._qt[slot][:n].to(dev, non_blocking=True)
@@ -295,7 +319,16 @@ class JpegEntropyFolderReader(JpegFolderReader):
         return self._scan[slot][:total], tuple(m[:n] for m in self._meta[slot][:3]), how
 
     # ------------------------------------------------------------------------------------------------------------ device
-    def _fill(self, i0: int, i1: int, slot: int):
+    def decode_into(self, i0: int, i1: int, dst: torch.Tensor):
+        """JpegFolderReader.decode_into; here the thread that decodes ahead puts the piece's device work on the side stream too"""
+        assert dst.is_cuda and dst.dtype == torch.uint8 and dst.shape == (i1 - i0, *self.frame_size, 3) and dst.is_contiguous()
+        slot, self._turn = self._turn, self._turn ^ 1
+        return (slot,) + tuple(self._fill(i0, i1, slot, out=dst))
+
+    def finish_into(self, token) -> torch.Tensor:
+        return self._launch(*token)
+
+    def _fill(self, i0: int, i1: int, slot: int, out: Optional[torch.Tensor] = None):
         """on the driver thread: the host stage, then the batch's whole device work on the side stream -> (out, event)"""
         n, how, total = self._pack_batch(i0, i1, slot)
         dev = torch.device("cuda", torch.cuda.current_device()) if self.device is None else torch.device(self.device)
@@ -303,7 +336,8 @@ class JpegEntropyFolderReader(JpegFolderReader):
         if self._side is None:
             self._side = torch.cuda.Stream(device=dev)
         with torch.cuda.device(dev), torch.cuda.stream(self._side):
-            out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+            if out is None:
+                out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
             pillow = [j for j in range(n) if how[j] == 0]
             if any(how):
                 geom = self.geometry

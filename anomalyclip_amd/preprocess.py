@@ -146,16 +146,25 @@ def _full_tables(h: int, w: int, scale_size: int, device_str: str):
 
 
 def preprocess_crops(frames_u8: torch.Tensor, crop_size: int, scale_size=None, ncrops: int = 1, mean=CLIP_MEAN,
-                     std=CLIP_STD) -> torch.Tensor:
+                     std=CLIP_STD, out=None) -> torch.Tensor:
     """frames_u8: [F, H, W, 3] uint8 on the device -> [F, ncrops, 3, crop_size, crop_size] float32: image f * ncrops + c is crop c
-    of frame f (the row order of a feature file).  One library call for all crops of all frames."""
+    of frame f (the row order of a feature file).  One library call for all crops of all frames.  out: a contiguous float32
+    tensor of F * ncrops images of the same device to write them into (a slice of a larger input batch); it is returned viewed
+    as [F, ncrops, 3, crop_size, crop_size]."""
     assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[-1] == 3 and frames_u8.is_contiguous()
     if scale_size is None:
         scale_size = default_scale_size(crop_size, ncrops)
     F, H, W, _ = frames_u8.shape
     wins = crop_windows(H, W, scale_size, crop_size, ncrops)
     oh, ow, hb, hk, hks, vb, vk, vks = _full_tables(H, W, scale_size, str(frames_u8.device))
-    out = torch.empty(F, ncrops, 3, crop_size, crop_size, dtype=torch.float32, device=frames_u8.device)
+    if out is None:
+        out = torch.empty(F, ncrops, 3, crop_size, crop_size, dtype=torch.float32, device=frames_u8.device)
+    else:
+        if (out.dtype != torch.float32 or out.device != frames_u8.device or not out.is_contiguous()
+                or out.numel() != F * ncrops * 3 * crop_size * crop_size or out.data_ptr() % 16):
+            raise ValueError(f"preprocess_crops: out must be contiguous float32 on {frames_u8.device}, 16-byte aligned, of "
+                             f"{F * ncrops} images 3 x {crop_size} x {crop_size}; got {tuple(out.shape)} {out.dtype} on {out.device}")
+        out = out.view(F, ncrops, 3, crop_size, crop_size)
     tmp = torch.empty(F, H, ow, 3, dtype=torch.uint8, device=frames_u8.device)
     m = (C.c_float * 3)(*mean)
     s = (C.c_float * 3)(*std)
