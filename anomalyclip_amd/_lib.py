@@ -148,6 +148,11 @@ class JpegInfo(C.Structure):            # == struct acx_jpeg_info
                 ("huff_bits", ((C.c_uint8 * 17) * 4) * 2), ("huff_vals", ((C.c_uint8 * 256) * 4) * 2)]
 
 
+class VizGeom(C.Structure):             # == struct acx_viz_geom
+    _fields_ = [(n, c_int32) for n in ("Hc", "Wc", "H", "W", "fx", "fy", "fw", "fh", "border", "bx", "by", "bh", "bar_pitch", "bar_w",
+                                       "C1", "sx", "sy", "sw", "sh", "cursor_w", "T")] + [("threshold", c_float)]
+
+
 class JpegHuff(C.Structure):            # == struct acx_jpeg_huff
     _fields_ = [("present", (C.c_uint8 * 4) * 2), ("bits", ((C.c_uint8 * 17) * 4) * 2), ("vals", ((C.c_uint8 * 256) * 4) * 2),
                 ("td", C.c_uint8 * 4), ("ta", C.c_uint8 * 4)]
@@ -324,6 +329,10 @@ _SIGS = {
     "acx_jpeg_entropy_decode_dev": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int32] * 6 +
                                     [c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "acx_jpeg_reconstruct": (C.c_int, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
+    "acx_viz_compose": (C.c_int, [c_void_p] * 8 + [c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "acx_jpeg_forward": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "acx_jpeg_entropy_encode": (c_int64, [c_void_p, c_size_t, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "acx_jpeg_encode_bound": (c_int64, [c_int32, c_int32]),
 }
 
 # entry points added by later translation units register themselves here (name -> signature)

@@ -21,7 +21,8 @@ read through the same attributes: `trainer.datamodule` (`.train_dataloader_test_
 `trainer.ckpt_path`.
 
 The metric numbers (AUROC, AP, mAUC, mAP, top-1/5, optimal threshold; :339-404, :501-626) come from libacx's sort /
-scan kernels (metrics.py) instead of torchmetrics; plots and the Visualizer are out of scope.
+scan kernels (metrics.py) instead of torchmetrics; the four epilogue plots are not drawn; `data.visualize=True` renders the
+qualitative clips on the GPU (visualizer.py).
 The reference hard-codes /usr/src/app/logs/{train,eval}/runs/<run> (:409,:596); the same layout is used under
 `hparams.logs_root` (default "/usr/src/app/logs")."""
 from __future__ import annotations
@@ -348,7 +349,9 @@ class AnomalyCLIPModule(_Base):
         self._meters.reset()
 
     # ------------------------------------------------------------------ evaluation (:301-337, :458-498)
-    def _score_video(self, batch):
+    def _score_video(self, batch, with_softmax: bool = False):
+        """-> (abnormal_scores, labels, class_probs) of one video, truncated to its real frames; with_softmax: the truncated
+        softmax_similarity as a fourth item (the Visualizer's bars, :474-483)"""
         image_features, labels, segment_size = batch[0], batch[1], batch[3]        # 4-tuple (:302) or 5-tuple (:460)
         dev = self.device
         image_features = image_features.to(dev)
@@ -356,7 +359,11 @@ class AnomalyCLIPModule(_Base):
         with torch.no_grad():
             similarity, abnormal_scores = self.forward(image_features, labels, self.ncentroid, int(segment_size), test_mode=True)
             class_probs = ops.class_probs(similarity.contiguous(), abnormal_scores.contiguous())   # softmax * score
+            if with_softmax:                                                         # softmax * 1: the same kernel's softmax
+                softmax_similarity = ops.class_probs(similarity.contiguous(), torch.ones_like(abnormal_scores))
         n = labels.shape[0]                                                          # remove padded frames
+        if with_softmax:
+            return abnormal_scores[:n], labels, class_probs[:n], softmax_similarity[:n]
         return abnormal_scores[:n], labels, class_probs[:n]
 
     def score_videos(self, batches: List[Any]):
@@ -365,6 +372,8 @@ class AnomalyCLIPModule(_Base):
         real frames like anomaly_clip_module.py:474-483.  -> list of (abnormal_scores, labels, class_probs)."""
         net = self.net
         tiles = [b[0] for b in batches]
+        if getattr(self, "visualizer", None) is not None:                            # one video per forward, rendered as it is scored
+            return [self._score_and_render(b) for b in batches]
         if len(batches) == 1 or any(torch.is_tensor(t) and t.dim() == 5 for t in tiles):        # (frames: one video per forward)
             return [self._score_video(b) for b in batches]
         dev = self.device
@@ -471,13 +480,28 @@ class AnomalyCLIPModule(_Base):
     def on_test_start(self):
         self._load_or_compute_ncentroid(self._run_dir("train"))
         dm = self._datamodule()
-        if bool(_get(_get(dm, "hparams"), "visualize", False)):
-            raise NotImplementedError("data.visualize=True: the qualitative Visualizer is out of scope of this path")
-        self.visualizer = None
+        hp = _get(dm, "hparams")
+        if bool(_get(hp, "visualize", False)):                                       # :447-454
+            from .visualizer import Visualizer
+            extra = {"decode": dm.decode} if getattr(dm, "decode", None) else {}
+            # `visualizer`: the Visualizer's keyword extras (frames_root=, canvas=, quality= ...; not one of the reference's keys)
+            extra.update(dict(_get(hp, "visualizer", None) or {}))
+            self.visualizer = Visualizer(_get(hp, "normal_id"), _get(hp, "labels_file"), _get(hp, "image_tmpl", "{:06d}.jpg"),
+                                         self._run_dir("train"), self.device, **extra)
+        else:
+            self.visualizer = None
+
+    def _score_and_render(self, batch):
+        """_score_video, and the video's qualitative clip where a Visualizer is there (:485-492)"""
+        if getattr(self, "visualizer", None) is None:
+            return self._score_video(batch)
+        scores, labels, probs, softmax_similarity = self._score_video(batch, with_softmax=True)
+        self.visualizer.process_video(scores, probs, softmax_similarity, labels, batch[4])
+        return scores, labels, probs
 
     @parallel.rank_zero_only
     def test_step(self, batch: Any, batch_idx: int = 0):
-        scores, labels, probs = self._score_video(batch)
+        scores, labels, probs = self._score_and_render(batch)
         return {"abnormal_scores": scores, "labels": labels, "class_probs": probs}
 
     @parallel.rank_zero_only

@@ -1,7 +1,8 @@
 """Metrics epilogue on the GPU: the numbers `test_epoch_end` /
 `on_validation_epoch_end` write to metrics.json (reference anomaly_clip_module.py:339-404, 501-626), computed
 over all frames by libacx's sort / scan / count kernels instead of torchmetrics (==0.11.0 in the reference,
-not installed here).  Plots are out of scope.
+not installed here).  The four epilogue plots are not drawn (`evaluate(curves=True)` returns their points); the per-video
+qualitative clips are anomalyclip_amd/visualizer.py.
 
 Per curve (1 binary + C one-vs-rest): one stable radix sort of (score, label) pairs and one scan pass; the
 AUROC and the Youden-optimal threshold are exact integer arithmetic, AP a fixed-order f64 sum, so results are

@@ -1544,3 +1544,71 @@ def jpeg_entropy_decode(scans: torch.Tensor, scan_off: torch.Tensor, scan_bits: 
                                                 huff.data_ptr(), H, W, ncomp, hs, vs, F, int(max_scan_bits), int(sub_bits),
                                                 coef.data_ptr(), status.data_ptr(), _stream()), h)
     return coef, status
+
+
+# ---- qualitative videos: composition and the forward half of the JPEG encoder (include/acx.h acx_viz_compose, acx_jpeg_forward,
+# acx_jpeg_entropy_encode; the layout, the static layer and the container: anomalyclip_amd/visualizer.py)
+def viz_compose(static_layer: torch.Tensor, frames: torch.Tensor, scores: torch.Tensor, softmax: torch.Tensor, frame_idx: torch.Tensor,
+                tables, geom: "L.VizGeom", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """static_layer uint8 [Hc, Wc, 3], frames uint8 [B, H, W, 3], scores f32 [B], softmax f32 [B, C1], frame_idx int32 [B], all on
+    the device; tables: (hbounds, hcoef, hksize, vbounds, vcoef, vksize) of resample.coeffs(..., "bilinear") for the inner
+    rectangle, on the device -> the composed canvases uint8 [B, Hc, Wc, 3]"""
+    B, H, W, _ = frames.shape
+    dev = frames.device
+    hb, hk, hks, vb, vk, vks = tables
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.shape[3] == 3 and (H, W) == (geom.H, geom.W)
+    assert static_layer.dtype == torch.uint8 and static_layer.shape == (geom.Hc, geom.Wc, 3) and static_layer.is_contiguous()
+    assert scores.dtype == torch.float32 and scores.shape == (B,) and scores.is_contiguous()
+    assert softmax.dtype == torch.float32 and softmax.shape == (B, geom.C1) and softmax.is_contiguous()
+    assert frame_idx.dtype == torch.int32 and frame_idx.shape == (B,) and frame_idx.is_contiguous()
+    assert hb.shape == (geom.fw, 2) and hk.shape == (geom.fw, hks) and vb.shape == (geom.fh, 2) and vk.shape == (geom.fh, vks)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (hb, hk, vb, vk))
+    assert all(t.device == dev for t in (static_layer, scores, softmax, frame_idx, hb, hk, vb, vk))
+    if out is None:
+        out = torch.empty(B, geom.Hc, geom.Wc, 3, dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and out.shape == (B, geom.Hc, geom.Wc, 3) and out.is_contiguous() and out.device == dev
+    tmp = torch.empty(B, H, max(int(geom.fw), 1), 3, dtype=torch.uint8, device=dev)
+    h = _h(frames)
+    L.check(L.lib().acx_viz_compose(h, static_layer.data_ptr(), frames.data_ptr(), scores.data_ptr(), softmax.data_ptr(),
+                                    frame_idx.data_ptr(), hb.data_ptr(), hk.data_ptr(), hks, vb.data_ptr(), vk.data_ptr(), vks,
+                                    C.byref(geom), B, tmp.data_ptr(), out.data_ptr(), _stream()), h)
+    return out
+
+
+def jpeg_forward(canvases: torch.Tensor, qtabs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """canvases uint8 [B, Hc, Wc, 3] (Hc, Wc multiples of 16), qtabs [2, 64] 16-bit (luma, chroma; natural order) on the device ->
+    int16 [B, Hc * Wc * 3 / 2]: the quantised coefficients of baseline JPEG 4:2:0 in the layout jpeg_reconstruct(..., 3, 2, 2) reads"""
+    B, Hc, Wc, _ = canvases.shape
+    assert canvases.dtype == torch.uint8 and canvases.is_contiguous() and canvases.shape[3] == 3
+    assert qtabs.dtype in (torch.int16, torch.uint16) and qtabs.shape == (2, 64) and qtabs.is_contiguous() and qtabs.device == canvases.device
+    n = Hc * Wc * 3 // 2
+    if out is None:
+        out = torch.empty(B, n, dtype=torch.int16, device=canvases.device)
+    assert out.dtype == torch.int16 and out.shape == (B, n) and out.is_contiguous() and out.device == canvases.device
+    h = _h(canvases)
+    L.check(L.lib().acx_jpeg_forward(h, canvases.data_ptr(), qtabs.data_ptr(), Hc, Wc, B, out.data_ptr(), _stream()), h)
+    return out
+
+
+E_WORKSPACE = -4                       # ACX_E_WORKSPACE
+
+
+def jpeg_encode_bound(H: int, W: int) -> int:
+    """a buffer size jpeg_entropy_encode never exceeds for an H x W frame"""
+    n = int(L.lib().acx_jpeg_encode_bound(H, W))
+    if n < 0:
+        raise L.AcxError(f"acx_jpeg_encode_bound({H}, {W}): sizes are 1 .. 65535")
+    return n
+
+
+def jpeg_entropy_encode(coef, qtabs, H: int, W: int, dst) -> int:
+    """Host only (no GPU call; the GIL is released for its duration): one frame's coefficients (int16 numpy array or host tensor,
+    jpeg_coef_elems(H, W, 3, 2, 2) of them) and tables (uint16 [2, 64] numpy, natural order) -> a JFIF file in `dst` (writable
+    uint8 numpy array or host tensor).  Returns the bytes written, or a negative code: E_WORKSPACE when `dst` is too small."""
+    import numpy as np
+    c = coef.numpy() if isinstance(coef, torch.Tensor) else coef
+    d = dst.numpy() if isinstance(dst, torch.Tensor) else dst
+    assert c.dtype == np.int16 and c.flags.c_contiguous
+    assert qtabs.dtype == np.uint16 and qtabs.shape == (2, 64) and qtabs.flags.c_contiguous
+    assert d.dtype == np.uint8 and d.flags.c_contiguous and d.flags.writeable
+    return int(L.lib().acx_jpeg_entropy_encode(c.ctypes.data, c.size, qtabs.ctypes.data, H, W, d.ctypes.data, d.size))

@@ -9,7 +9,6 @@ JPEG decoding is Pillow's on the host by default; anomalyclip_amd/jpeg.py moves 
 from __future__ import annotations
 
 import ctypes as C
-import math
 from functools import lru_cache
 
 import numpy as np
@@ -17,48 +16,16 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import resample as _R
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # augmentations.py:23
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)      # augmentations.py:24
-_PRECISION_BITS = 32 - 8 - 2
-
-
-def _bicubic(x: float) -> float:
-    a = -0.5
-    x = abs(x)
-    if x < 1.0:
-        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
-    if x < 2.0:
-        return (((x - 5) * x + 8) * x - 4) * a
-    return 0.0
+_PRECISION_BITS = _R.PRECISION_BITS
 
 
 def _coeffs(in_size: int, out_size: int):
-    """Pillow precompute_coeffs(inSize, 0, inSize, outSize, BICUBIC) + normalize_coeffs_8bpc."""
-    scale = filterscale = in_size / out_size
-    if filterscale < 1.0:
-        filterscale = 1.0
-    support = 2.0 * filterscale
-    ksize = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), dtype=np.int32)
-    kk = np.zeros((out_size, ksize), dtype=np.int32)
-    ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = int(center - support + 0.5)
-        if xmin < 0:
-            xmin = 0
-        xmax = int(center + support + 0.5)
-        if xmax > in_size:
-            xmax = in_size
-        xmax -= xmin
-        w = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
-        ww = sum(w)
-        for x in range(xmax):
-            v = w[x] / ww if ww != 0.0 else w[x]
-            kk[xx, x] = int(-0.5 + v * (1 << _PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << _PRECISION_BITS))
-        bounds[xx] = (xmin, xmax)
-    return bounds, kk, ksize
+    """Pillow precompute_coeffs(inSize, 0, inSize, outSize, BICUBIC) + normalize_coeffs_8bpc (anomalyclip_amd/resample.py)."""
+    return _R.coeffs(in_size, out_size, "bicubic")
 
 
 def resize_geometry(h: int, w: int, size: int):

@@ -1091,6 +1091,59 @@ int acx_jpeg_entropy_decode_dev(acx_ctx* ctx, const uint8_t* scans, int64_t scan
                                 const acx_jpeg_huff* huff, int32_t H, int32_t W, int32_t ncomp, int32_t hs, int32_t vs, int32_t F,
                                 int64_t max_scan_bits, int32_t sub_bits, int16_t* coef, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Qualitative videos (data.visualize=True; the reference draws a matplotlib figure per frame: src/utils/visualizer.py): the
+ * per-frame picture composed on the device, then encoded as baseline JPEG -- the transform on the device, Huffman coding on the
+ * host.  anomalyclip_amd/visualizer.py lays the picture out and writes the Motion-JPEG file. */
+typedef struct acx_viz_geom {
+  int32_t Hc, Wc;                          /* the canvas */
+  int32_t H, W;                            /* the source frames */
+  int32_t fx, fy, fw, fh;                  /* the inner frame rectangle: the source resized to fw x fh */
+  int32_t border;                          /* width of the border around it */
+  int32_t bx, by, bh;                      /* bars: left edge of bar 0, top row of the panel, its height PH; a bar of height h
+                                              covers rows by + bh - h ... by + bh - 1 */
+  int32_t bar_pitch, bar_w;                /* bar k covers columns bx + k * bar_pitch ... + bar_w - 1 */
+  int32_t C1;                              /* bars: 1 .. 64 */
+  int32_t sx, sy, sw, sh;                  /* the score panel; sw is PW of the cursor's x = sx + (i * (sw - 1)) / T */
+  int32_t cursor_w;
+  int32_t T;                               /* frames of the video */
+  float threshold;
+} acx_viz_geom;
+
+/* acx_viz_compose: B canvases [B,Hc,Wc,3] uint8 in one launch sequence.  Every canvas starts as static_layer [Hc,Wc,3]; then, later
+ * items over earlier ones: frame b of frames [B,H,W,3] resized to the inner rectangle bit for bit as Pillow's
+ * Image.resize((fw, fh), BILINEAR) (hbounds/hcoef [fw,2] / [fw,hksize], vbounds/vcoef [fh,2] / [fh,vksize]: the tables of
+ * anomalyclip_amd/resample.py for the triangle filter; tmp: [B,H,fw,3] uint8 scratch), a border around it, (0,0,255) where
+ * scores[b] < threshold and (255,0,0) otherwise; C1 bars of height floor(softmax[b,k] * PH + 0.5) (float32, product and sum rounded
+ * separately; clipped to 0 .. PH) in (128,128,128), the three largest softmax[b,:] (the lower index wins a tie) in (255,0,0) where
+ * scores[b] >= threshold; a cursor of cursor_w columns in (255,0,0) over the score panel's height at frame_idx[b] (none for an
+ * index outside 0 .. T - 1).  All pointers but geom are DEVICE pointers.  ACX_E_BADARG: C1 outside 1 .. 64, or a rectangle that
+ * does not lie strictly inside the canvas (nothing is clipped). */
+int acx_viz_compose(acx_ctx* ctx, const uint8_t* static_layer, const uint8_t* frames, const float* scores, const float* softmax,
+                    const int32_t* frame_idx, const int32_t* hbounds, const int32_t* hcoef, int32_t hksize, const int32_t* vbounds,
+                    const int32_t* vcoef, int32_t vksize, const acx_viz_geom* geom, int32_t B, uint8_t* tmp, uint8_t* canvases,
+                    void* stream);
+
+/* acx_jpeg_forward: B canvases [B,Hc,Wc,3] uint8 -> the quantised coefficients of baseline JPEG, YCbCr 4:2:0, int16
+ * [B][Hc * Wc * 3 / 2] in the layout acx_jpeg_entropy_decode writes and acx_jpeg_reconstruct reads (luma sampling 2x2).  Integer
+ * arithmetic throughout ("Qualitative videos"): JFIF colour conversion in 16-bit fixed point, 2x2 chroma
+ * mean, level shift, samples with 6 fraction bits, the 8x8 orthonormal DCT as two passes of a 14-bit matrix, division by the
+ * table rounded half away from zero, clamped to +-1023 (what the Annex K tables code: AC category 10, DC differences category 11).
+ * qtabs: DEVICE uint16 [2][64], luma then chroma, natural order.  Hc and Wc multiples of 16 (ACX_E_BADARG otherwise); canvases,
+ * qtabs and coef 16-byte aligned. */
+int acx_jpeg_forward(acx_ctx* ctx, const uint8_t* canvases, const uint16_t* qtabs, int32_t Hc, int32_t Wc, int32_t B, int16_t* coef,
+                     void* stream);
+
+/* Host only, like acx_jpeg_parse: no context, no GPU call, no state, no allocation -- callable from many threads at once.
+ * One frame's coefficients (coef[coef_elems], the layout above for an H x W frame: blocks padded to whole 16 x 16 MCUs) and its
+ * tables (qtabs: HOST uint16 [2][64], natural order, entries 1 .. 255) -> a complete JFIF file in dst[cap]: APP0, two DQT, SOF0
+ * with luma sampling 2x2, four DHT with the Annex K tables, one interleaved scan with FF 00 stuffing, EOI.  Returns the number of
+ * bytes, or a negative code: ACX_E_WORKSPACE when cap is too small (nothing is written past dst + cap), ACX_E_BADARG for a
+ * coefficient those tables cannot code or a coef_elems that is not the frame's.  acx_jpeg_encode_bound(H, W) is always enough. */
+int64_t acx_jpeg_entropy_encode(const int16_t* coef, size_t coef_elems, const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst,
+                                size_t cap);
+int64_t acx_jpeg_encode_bound(int32_t H, int32_t W);
+
 #ifdef __cplusplus
 }
 #endif
