@@ -333,6 +333,10 @@ _SIGS = {
     "acx_jpeg_forward": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "acx_jpeg_entropy_encode": (c_int64, [c_void_p, c_size_t, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
     "acx_jpeg_encode_bound": (c_int64, [c_int32, c_int32]),
+    "acx_jpeg_encode_header": (c_int64, [c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "acx_jpeg_entropy_encode_dev_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "acx_jpeg_entropy_encode_dev": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # entry points added by later translation units register themselves here (name -> signature)

@@ -11,11 +11,11 @@
 namespace acx_jpeg {
 
 // ISO/IEC 10918-1 Annex K.3: the typical Huffman tables (codes of each length 1 .. 16, then the symbols)
-static const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-static const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-static const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-static const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
-static const uint8_t kAcLumaVals[162] = {
+static constexpr uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+static constexpr uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static constexpr uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static constexpr uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+static constexpr uint8_t kAcLumaVals[162] = {
     0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
@@ -24,8 +24,8 @@ static const uint8_t kAcLumaVals[162] = {
     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
-static const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
-static const uint8_t kAcChromaVals[162] = {
+static constexpr uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+static constexpr uint8_t kAcChromaVals[162] = {
     0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
@@ -105,25 +105,10 @@ static inline int64_t encode_bound(int32_t H, int32_t W) {
   return 1024 + mcus * 6 * 416;
 }
 
-// coef: [coef_elems] int16, the frame's blocks as entropy_decode writes them for 3 components with luma sampling 2x2;
-// qtabs: [2][64] in natural order (luma, chroma), entries 1 .. 255.  -> bytes written, or a negative ACX_E_* code.
-static inline int64_t entropy_encode(const int16_t* coef, size_t coef_elems, const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst,
-                                     size_t cap) {
-  if (!coef || !qtabs || (!dst && cap)) return ACX_E_BADARG;
-  if (H < 1 || W < 1 || H > 65535 || W > 65535) return ACX_E_BADARG;
-  for (int i = 0; i < 128; ++i)
-    if (qtabs[i] < 1 || qtabs[i] > 255) return ACX_E_BADARG;        // baseline: 8-bit tables
-  acx_jpeg_info g;
-  memset(&g, 0, sizeof(g));
-  g.width = W;
-  g.height = H;
-  g.ncomp = 3;
-  g.comp_h[0] = g.comp_v[0] = g.hmax = g.vmax = 2;
-  g.comp_h[1] = g.comp_v[1] = g.comp_h[2] = g.comp_v[2] = 1;
-  layout(&g);
-  if ((uint64_t)g.coef_elems != coef_elems) return ACX_E_BADARG;
-
-  BitWriter bw = {dst, cap, 0, 0, 0};
+// what stands before the scan: APP0, two DQT (entries in zigzag order), SOF0 with luma sampling 2x2, four DHT with the Annex K
+// tables, SOS -- kHeaderBytes of them for every size and every pair of tables
+constexpr int kHeaderBytes = 623;
+static inline void write_header(BitWriter& bw, const uint16_t* qtabs, int32_t H, int32_t W) {
   static const uint8_t app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
   bw.raw(app0, sizeof(app0));
   for (int t = 0; t < 2; ++t) {                                     // DQT: entries in zigzag order
@@ -143,7 +128,6 @@ static inline int64_t entropy_encode(const int16_t* coef, size_t coef_elems, con
   const uint8_t* hbits[4] = {kDcLumaBits, kAcLumaBits, kDcChromaBits, kAcChromaBits};
   const uint8_t* hvals[4] = {kDcVals, kAcLumaVals, kDcVals, kAcChromaVals};
   const uint8_t hid[4] = {0x00, 0x10, 0x01, 0x11};
-  EncTable tab[4];                                                  // DC luma, AC luma, DC chroma, AC chroma
   for (int t = 0; t < 4; ++t) {
     int cnt = 0;
     for (int i = 0; i < 16; ++i) cnt += hbits[t][i];
@@ -152,10 +136,52 @@ static inline int64_t entropy_encode(const int16_t* coef, size_t coef_elems, con
     bw.byte(hid[t]);
     bw.raw(hbits[t], 16);
     bw.raw(hvals[t], (size_t)cnt);
-    enc_derive(hbits[t], hvals[t], &tab[t]);
   }
   static const uint8_t sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
   bw.raw(sos, sizeof(sos));
+}
+
+static inline bool tables_are_baseline(const uint16_t* qtabs) {
+  for (int i = 0; i < 128; ++i)
+    if (qtabs[i] < 1 || qtabs[i] > 255) return false;                 // baseline: 8-bit tables
+  return true;
+}
+
+// the header alone, for a coder that writes the scan elsewhere: -> kHeaderBytes, or a negative ACX_E_* code
+static inline int64_t encode_header(const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst, size_t cap) {
+  if (!qtabs || (!dst && cap)) return ACX_E_BADARG;
+  if (H < 1 || W < 1 || H > 65535 || W > 65535) return ACX_E_BADARG;
+  if (!tables_are_baseline(qtabs)) return ACX_E_BADARG;
+  BitWriter bw = {dst, cap, 0, 0, 0};
+  write_header(bw, qtabs, H, W);
+  if (bw.n > cap) return ACX_E_WORKSPACE;
+  return (int64_t)bw.n;
+}
+
+// coef: [coef_elems] int16, the frame's blocks as entropy_decode writes them for 3 components with luma sampling 2x2;
+// qtabs: [2][64] in natural order (luma, chroma), entries 1 .. 255.  -> bytes written, or a negative ACX_E_* code.
+static inline int64_t entropy_encode(const int16_t* coef, size_t coef_elems, const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst,
+                                     size_t cap) {
+  if (!coef || !qtabs || (!dst && cap)) return ACX_E_BADARG;
+  if (H < 1 || W < 1 || H > 65535 || W > 65535) return ACX_E_BADARG;
+  if (!tables_are_baseline(qtabs)) return ACX_E_BADARG;
+  acx_jpeg_info g;
+  memset(&g, 0, sizeof(g));
+  g.width = W;
+  g.height = H;
+  g.ncomp = 3;
+  g.comp_h[0] = g.comp_v[0] = g.hmax = g.vmax = 2;
+  g.comp_h[1] = g.comp_v[1] = g.comp_h[2] = g.comp_v[2] = 1;
+  layout(&g);
+  if ((uint64_t)g.coef_elems != coef_elems) return ACX_E_BADARG;
+
+  BitWriter bw = {dst, cap, 0, 0, 0};
+  write_header(bw, qtabs, H, W);
+  EncTable tab[4];                                                  // DC luma, AC luma, DC chroma, AC chroma
+  enc_derive(kDcLumaBits, kDcVals, &tab[0]);
+  enc_derive(kAcLumaBits, kAcLumaVals, &tab[1]);
+  enc_derive(kDcChromaBits, kDcVals, &tab[2]);
+  enc_derive(kAcChromaBits, kAcChromaVals, &tab[3]);
 
   int pred[3] = {0, 0, 0};
   for (int my = 0; my < g.mcus_y; ++my)

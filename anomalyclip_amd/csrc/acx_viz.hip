@@ -1,6 +1,7 @@
 // The qualitative videos (data.visualize=True; reference src/utils/visualizer.py): the per-frame picture composed on the device, and
 // the forward half of a baseline JPEG encoder -- colour conversion, 2x2 chroma mean, forward DCT and quantisation into the
-// coefficient layout the decoder of acx_jpeg.hip reads.  Huffman coding is the host's (acx_jpeg_enc_host.h), behind the C ABI here.
+// coefficient layout the decoder of acx_jpeg.hip reads.  Huffman coding is the host's (acx_jpeg_enc_host.h), behind the C ABI here,
+// or the device's (acx_jpeg_enc.hip).
 #include "acx_internal.h"
 #include "acx_jpeg_enc_host.h"
 

@@ -1612,3 +1612,62 @@ def jpeg_entropy_encode(coef, qtabs, H: int, W: int, dst) -> int:
     assert qtabs.dtype == np.uint16 and qtabs.shape == (2, 64) and qtabs.flags.c_contiguous
     assert d.dtype == np.uint8 and d.flags.c_contiguous and d.flags.writeable
     return int(L.lib().acx_jpeg_entropy_encode(c.ctypes.data, c.size, qtabs.ctypes.data, H, W, d.ctypes.data, d.size))
+
+
+E_BADARG = -1                          # ACX_E_BADARG
+JPEG_HEADER_BYTES = 623                # what stands before the scan of a file jpeg_entropy_encode writes
+
+
+def jpeg_encode_header(qtabs, H: int, W: int):
+    """Host only: the JPEG_HEADER_BYTES bytes jpeg_entropy_encode writes before the scan of an H x W frame with the tables qtabs
+    (uint16 [2, 64] numpy, natural order) -- APP0, two DQT, SOF0, four DHT, SOS -> uint8 numpy [JPEG_HEADER_BYTES]"""
+    import numpy as np
+    assert qtabs.dtype == np.uint16 and qtabs.shape == (2, 64) and qtabs.flags.c_contiguous
+    dst = np.empty(JPEG_HEADER_BYTES, np.uint8)
+    n = int(L.lib().acx_jpeg_encode_header(qtabs.ctypes.data, H, W, dst.ctypes.data, dst.size))
+    if n != JPEG_HEADER_BYTES:
+        raise L.AcxError(f"acx_jpeg_encode_header({H}, {W}) failed [{n}]: sizes are 1 .. 65535, table entries 1 .. 255")
+    return dst
+
+
+def jpeg_entropy_encode_dev_workspace_bytes(H: int, W: int, B: int) -> int:
+    """bytes of the workspace jpeg_entropy_encode_dev needs for B frames of H x W"""
+    n = int(L.lib().acx_jpeg_entropy_encode_dev_workspace_bytes(H, W, B))
+    if n == 0:
+        raise L.AcxError(f"acx_jpeg_entropy_encode_dev_workspace_bytes({H}, {W}, {B}): B, H and W are 1 .. 65535 and the frame's "
+                         f"blocks x 1658 bits stay below 2^31")
+    return n
+
+
+def jpeg_entropy_encode_dev(coef: torch.Tensor, header: torch.Tensor, H: int, W: int, cap: Optional[int] = None,
+                            files: Optional[torch.Tensor] = None, nbytes: Optional[torch.Tensor] = None,
+                            status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """The Huffman coder of jpeg_entropy_encode on the device: coef int16 [B, jpeg_coef_elems(H, W, 3, 2, 2)] (as jpeg_forward
+    writes them) and header uint8 [n] (jpeg_encode_header, on the device) -> (files uint8 [B, cap], nbytes int32 [B], status int32
+    [B]): files[f, :nbytes[f]] is byte for byte the file jpeg_entropy_encode writes where status[f] is 0; E_WORKSPACE: the file
+    needs nbytes[f] > cap bytes; E_BADARG: a coefficient the tables cannot code.  cap: bytes per frame (default: files' row, or
+    jpeg_encode_bound); workspace: uint8, at least jpeg_entropy_encode_dev_workspace_bytes(H, W, B), reusable on one stream."""
+    B = coef.shape[0]
+    dev = coef.device
+    assert coef.dtype == torch.int16 and coef.shape == (B, jpeg_coef_elems(H, W, 3, 2, 2)) and coef.is_contiguous()
+    assert header.dtype == torch.uint8 and header.dim() == 1 and header.is_contiguous() and header.device == dev
+    if cap is None:
+        cap = files.shape[1] if files is not None else jpeg_encode_bound(H, W)
+    cap = int(cap)
+    if files is None:
+        files = torch.empty(B, cap, dtype=torch.uint8, device=dev)
+    if nbytes is None:
+        nbytes = torch.empty(B, dtype=torch.int32, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(jpeg_entropy_encode_dev_workspace_bytes(H, W, B), dtype=torch.uint8, device=dev)
+    assert files.dtype == torch.uint8 and files.is_contiguous() and files.device == dev and files.numel() >= B * cap
+    assert nbytes.dtype == torch.int32 and nbytes.numel() >= B and nbytes.is_contiguous() and nbytes.device == dev
+    assert status.dtype == torch.int32 and status.numel() >= B and status.is_contiguous() and status.device == dev
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev
+    h = _h(coef)
+    L.check(L.lib().acx_jpeg_entropy_encode_dev(h, coef.data_ptr(), header.data_ptr(), header.numel(), H, W, B, files.data_ptr(), cap,
+                                                nbytes.data_ptr(), status.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                                _stream()), h)
+    return files, nbytes, status

@@ -8,8 +8,9 @@ ground truth -- is drawn ONCE per video on the host with Pillow (`static_layer`)
 border, the bars, the cursor -- is composed on the device over a copy of that layer (`ops.viz_compose`), for a batch of frames per
 launch sequence, from the decoded frames `jpeg.make_reader` delivers and the scores `test_step` already holds there.  The canvases
 are turned into quantised JPEG coefficients on the device (`ops.jpeg_forward`), copied to pinned memory and Huffman-coded on a
-thread pool (`ops.jpeg_entropy_encode`) while the device works on the next batch.  `layout` returns every rectangle; both layers
-use it and nothing else knows a pixel position."""
+thread pool (`ops.jpeg_entropy_encode`) while the device works on the next batch.  With `entropy="gpu"` the Huffman coding runs on
+the device as well (`ops.jpeg_entropy_encode_dev`): no pool, and what is copied to the host is each frame's file, not its
+coefficients.  `layout` returns every rectangle; both layers use it and nothing else knows a pixel position."""
 from __future__ import annotations
 
 import csv
@@ -30,6 +31,13 @@ BORDER = 5                             # the reference's cv2.rectangle thickness
 CURSOR_W = 2
 CURVE_COLOUR, TRUTH_COLOUR = (0x4E, 0x79, 0xA7), (0xE1, 0x57, 0x59)
 MAX_THREADS = 16
+ENTROPY = ("host", "gpu")              # where the frames are Huffman-coded
+
+
+def check_entropy(entropy, key: str = "entropy") -> str:
+    if entropy not in ENTROPY:
+        raise ValueError(f"{key}={entropy!r}: one of {', '.join(repr(e) for e in ENTROPY)}")
+    return entropy
 
 # ISO/IEC 10918-1 Annex K.1 / K.2: the typical quantisation tables, natural (row-major) order
 _K1 = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -310,11 +318,13 @@ class Visualizer:
     threshold: of the border / bar colours (the reference's 0.5); canvas: (width, height), multiples of 16 -- the default is the
     reference's 12 x 8 inch figure at 100 dpi; frames_root: where the frame folders are when `path` names a feature file
     (`<frames_root>/<class>/<video>`; default: the reference's rule, path component [-3] -> `Anomaly-Frames`); batch: frames per
-    launch sequence; threads: Huffman-coding workers (at most 16); max_file_bytes: where a clip continues in a `.partN.avi`."""
+    launch sequence; threads: Huffman-coding workers (at most 16); max_file_bytes: where a clip continues in a `.partN.avi`;
+    entropy: where the frames are Huffman-coded -- 'host' (the thread pool) or 'gpu' (acx_jpeg_entropy_encode_dev: the same files
+    byte for byte, no pool; a frame whose file passes the per-frame slot goes through the host coder)."""
 
     def __init__(self, normal_idx, labels_csv_path, image_tmpl, save_dir, device, *, decode: str = "pil", quality: int = 90,
                  fps: float = 30, threshold: float = 0.5, canvas: Tuple[int, int] = (1200, 800), frames_root: Optional[str] = None,
-                 batch: int = 32, threads: int = 8, max_file_bytes: int = 1 << 30):
+                 batch: int = 32, threads: int = 8, max_file_bytes: int = 1 << 30, entropy: str = "host"):
         from .jpeg import check_decode
         self.normal_idx = int(normal_idx)
         self.labels_csv_path = labels_csv_path
@@ -322,6 +332,7 @@ class Visualizer:
         self.save_dir = Path(save_dir)
         self.device = torch.device(device)
         self.decode = check_decode(decode)
+        self.entropy = check_entropy(entropy)
         self.qtabs = quant_tables(quality)
         self.fps, self.threshold = float(fps), float(threshold)
         self.canvas = (int(canvas[0]), int(canvas[1]))
@@ -332,10 +343,13 @@ class Visualizer:
         self.threads = max(1, min(int(threads), MAX_THREADS))
         self.max_file_bytes = int(max_file_bytes)
         self.frames_written = 0        # of this object's life (measurements)
-        self._pin = [None, None]       # pinned int16 [batch, coef_elems], in rotation
+        self.bytes_to_host = 0         # of the frames' coefficients or files, likewise
+        self._pin = [None, None]       # pinned, in rotation: int16 [batch, coef_elems]; entropy="gpu": uint8 [batch, cap]
         self._out: list = []           # per frame of a batch: the worker's output buffer
         self._pool: Optional[ThreadPoolExecutor] = None
         self._qt_dev = None
+        self.cap = max(1 << 16, self.canvas[0] * self.canvas[1] * 3 // 4)      # bytes a frame's file rarely passes; then: a retry
+        self._dev: Optional[dict] = None                                        # entropy="gpu": the device side's buffers
 
     # ------------------------------------------------------------------------------------------------------------ where
     def setup_directories(self, path):
@@ -381,22 +395,47 @@ class Visualizer:
         writer.close()
 
     def _ensure(self, dev):
-        if self._pool is None:
-            self._pool = ThreadPoolExecutor(max_workers=self.threads)
         if self._qt_dev is None or self._qt_dev.device != dev:
             self._qt_dev = torch.from_numpy(self.qtabs.view(np.int16).copy()).to(dev)
         n = ops.jpeg_coef_elems(self.canvas[1], self.canvas[0], 3, 2, 2)
+        cap = self.cap                                                         # a frame rarely needs more; _encode retries
+        while len(self._out) < self.batch:
+            self._out.append(np.empty(cap, dtype=np.uint8))
+        if self.entropy == "gpu":
+            self._ensure_gpu(dev, n, cap)
+            return
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=self.threads)
         for s in (0, 1):
             if self._pin[s] is None:
                 self._pin[s] = torch.empty(self.batch, n, dtype=torch.int16).pin_memory()
-        cap = max(1 << 16, self.canvas[0] * self.canvas[1] * 3 // 4)           # a frame rarely needs more; _encode_one retries
-        while len(self._out) < self.batch:
-            self._out.append(np.empty(cap, dtype=np.uint8))
+
+    def _ensure_gpu(self, dev, n: int, cap: int):
+        """entropy="gpu": per slot the batch's coefficients, files, sizes and codes on the device and the files and sizes | codes in
+        pinned memory; one workspace (the batches follow each other on one stream); the stream of the copies to the host"""
+        d = self._dev
+        if d is not None and d["device"] == dev and d["cap"] == cap:
+            return
+        Wc, Hc = self.canvas
+        B = self.batch
+        u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
+        self._dev = {"device": dev, "cap": cap,
+                     "header": torch.from_numpy(ops.jpeg_encode_header(self.qtabs, Hc, Wc)).to(dev),
+                     "coef": [torch.empty(B, n, dtype=torch.int16, device=dev) for _ in (0, 1)],
+                     "files": [u8(B, cap) for _ in (0, 1)],
+                     "result": [torch.empty(2, B, dtype=torch.int32, device=dev) for _ in (0, 1)],      # sizes, codes
+                     "result_host": [torch.empty(2, B, dtype=torch.int32).pin_memory() for _ in (0, 1)],
+                     "workspace": u8(ops.jpeg_entropy_encode_dev_workspace_bytes(Hc, Wc, B)),
+                     "copies": torch.cuda.Stream(device=dev)}
+        self._pin = [torch.empty(B, cap, dtype=torch.uint8).pin_memory() for _ in (0, 1)]
 
     def _encode_one(self, slot: int, j: int):
         """frame j of the slot's pinned coefficients -> its JFIF bytes (a view of the worker's buffer)"""
+        return self._encode(self._pin[slot][j].numpy(), j)
+
+    def _encode(self, coef: np.ndarray, j: int):
+        """one frame's coefficients on the host -> its JFIF bytes (a view of buffer j)"""
         Wc, Hc = self.canvas
-        coef = self._pin[slot][j].numpy()
         n = ops.jpeg_entropy_encode(coef, self.qtabs, Hc, Wc, self._out[j])
         if n == ops.E_WORKSPACE:
             self._out[j] = np.empty(ops.jpeg_encode_bound(Hc, Wc), dtype=np.uint8)
@@ -407,19 +446,58 @@ class Visualizer:
 
     def _drain(self, pending, writer: AviWriter):
         slot, n, ev = pending
+        if self.entropy == "gpu":
+            return self._drain_gpu(slot, n, ev, writer)
         ev.synchronize()
+        self.bytes_to_host += n * self._pin[slot].shape[1] * 2
         for data in self._pool.map(lambda j: self._encode_one(slot, j), range(n)):     # in frame order
             writer.write(data)
         self.frames_written += n
 
-    def compose_batch(self, static_dev, frames, scores, softmax, idx, tables, geom):
-        """the device stage of one batch: canvases uint8 [k, Hc, Wc, 3] and their coefficients int16 [k, coef_elems]"""
+    def _code_batch(self, slot: int, n: int):
+        """entropy="gpu", after compose_batch wrote the slot's coefficients: the device coder, and its sizes and codes on their way"""
+        d = self._dev
+        Wc, Hc = self.canvas
+        res = d["result"][slot]
+        ops.jpeg_entropy_encode_dev(d["coef"][slot][:n], d["header"], Hc, Wc, cap=d["cap"], files=d["files"][slot], nbytes=res[0],
+                                    status=res[1], workspace=d["workspace"])
+        d["result_host"][slot].copy_(res, non_blocking=True)
+
+    def _drain_gpu(self, slot: int, n: int, ev, writer: AviWriter):
+        """the batch's event has the sizes and codes on the host: every frame's file, its bytes only, comes over on the copies'
+        stream (the main one is already busy with the next batch), then the frames are appended in order"""
+        d = self._dev
+        ev.synchronize()
+        res = d["result_host"][slot].numpy()
+        sizes, codes = res[0, :n].tolist(), res[1, :n].tolist()
+        for j, code in enumerate(codes):
+            if code not in (0, ops.E_WORKSPACE):
+                raise L.AcxError(f"acx_jpeg_entropy_encode failed [{code}] on frame {j} of a batch")
+        files, pin = d["files"][slot], self._pin[slot]
+        with torch.cuda.stream(d["copies"]):
+            for j in range(n):
+                if codes[j] == 0:
+                    pin[j, :sizes[j]].copy_(files[j, :sizes[j]], non_blocking=True)
+                    self.bytes_to_host += sizes[j]
+        d["copies"].synchronize()
+        for j in range(n):
+            if codes[j] == 0:
+                writer.write(pin[j, :sizes[j]].numpy())
+            else:                                          # the file passes the slot: the host coder's retry, from the coefficients
+                coef = d["coef"][slot][j].cpu().numpy()
+                self.bytes_to_host += coef.nbytes
+                writer.write(self._encode(coef, j))
+        self.frames_written += n
+
+    def compose_batch(self, static_dev, frames, scores, softmax, idx, tables, geom, out=None):
+        """the device stage of one batch: canvases uint8 [k, Hc, Wc, 3] and their coefficients int16 [k, coef_elems] (`out`, if given)"""
         canv = ops.viz_compose(static_dev, frames, scores, softmax, idx, tables, geom)
-        return canv, ops.jpeg_forward(canv, self._qt_dev)
+        return canv, ops.jpeg_forward(canv, self._qt_dev, out=out)
 
     def render(self, frame_dir: str, abnormal_scores, softmax_similarity, labels, title: str, writer: AviWriter):
         """the frames 0 ... T - 1 of `frame_dir` into `writer`: batch k + 1 is decoded, composed and transformed on the device
-        while batch k is Huffman-coded on the pool and appended"""
+        while batch k is Huffman-coded on the pool and appended (entropy="gpu": coded on the device too, while batch k's files are
+        copied and appended)"""
         from . import jpeg
         dev = self.device
         if dev.type != "cuda":
@@ -454,8 +532,13 @@ class Visualizer:
                     cur.wait_event(ev)
                     x8.record_stream(cur)
                 n = x8.shape[0]
-                _, coef = self.compose_batch(static_dev, x8, scores[i0:i0 + n], softmax[i0:i0 + n], idx[i0:i0 + n], tables, geom)
-                self._pin[k & 1][:n].copy_(coef, non_blocking=True)
+                part = (static_dev, x8, scores[i0:i0 + n], softmax[i0:i0 + n], idx[i0:i0 + n], tables, geom)
+                if self.entropy == "gpu":
+                    self.compose_batch(*part, out=self._dev["coef"][k & 1][:n])
+                    self._code_batch(k & 1, n)
+                else:
+                    _, coef = self.compose_batch(*part)
+                    self._pin[k & 1][:n].copy_(coef, non_blocking=True)
                 done = torch.cuda.Event()
                 done.record(cur)
                 if pending is not None:

@@ -1094,7 +1094,8 @@ int acx_jpeg_entropy_decode_dev(acx_ctx* ctx, const uint8_t* scans, int64_t scan
 /* ------------------------------------------------------------------------------------------
  * Qualitative videos (data.visualize=True; the reference draws a matplotlib figure per frame: src/utils/visualizer.py): the
  * per-frame picture composed on the device, then encoded as baseline JPEG -- the transform on the device, Huffman coding on the
- * host.  anomalyclip_amd/visualizer.py lays the picture out and writes the Motion-JPEG file. */
+ * host or (acx_jpeg_entropy_encode_dev) on the device.  anomalyclip_amd/visualizer.py lays the picture out and writes the
+ * Motion-JPEG file. */
 typedef struct acx_viz_geom {
   int32_t Hc, Wc;                          /* the canvas */
   int32_t H, W;                            /* the source frames */
@@ -1143,6 +1144,31 @@ int acx_jpeg_forward(acx_ctx* ctx, const uint8_t* canvases, const uint16_t* qtab
 int64_t acx_jpeg_entropy_encode(const int16_t* coef, size_t coef_elems, const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst,
                                 size_t cap);
 int64_t acx_jpeg_encode_bound(int32_t H, int32_t W);
+
+/* Host only, like acx_jpeg_entropy_encode: the 623 bytes that function writes before the scan of an H x W frame with the tables
+ * qtabs (HOST uint16 [2][64], natural order, entries 1 .. 255) -- APP0, two DQT, SOF0, four DHT, SOS -- into dst[cap].  Returns
+ * 623, or ACX_E_WORKSPACE when cap is smaller (nothing is written past dst + cap), or ACX_E_BADARG (null pointer, a size outside
+ * 1 .. 65535, a table entry outside 1 .. 255). */
+int64_t acx_jpeg_encode_header(const uint16_t* qtabs, int32_t H, int32_t W, uint8_t* dst, size_t cap);
+
+/* The Huffman coder of acx_jpeg_entropy_encode on the device, for B frames of one size in one launch sequence on `stream`
+ * (Visualizer(entropy="gpu"); the phases: anomalyclip_amd/csrc/acx_jpeg_enc_dev.h).  All pointers are DEVICE pointers.
+ * coef: int16 [B][coef_elems] as acx_jpeg_forward writes them (an H x W frame padded to whole 16 x 16 MCUs), 16-byte aligned; header: the
+ * header_bytes bytes every file begins with (acx_jpeg_encode_header).  Frame f's file -- byte for byte the one
+ * acx_jpeg_entropy_encode writes -- goes to files + f * cap; nbytes[f] is the size it needs, also when it does not fit;
+ * status[f] is that function's code for the frame: 0, ACX_E_WORKSPACE when nbytes[f] > cap (the slot then holds the file's first
+ * cap bytes), or ACX_E_BADARG for a coefficient the Annex K tables cannot code (a DC difference beyond category 11, |AC| > 1023;
+ * nbytes[f] is 0 and the slot is left as it was).  Nothing is written at or past files + (f + 1) * cap, and one frame's refusal
+ * leaves the other frames of the batch as they are without it.  The workspace (16-byte aligned, at least
+ * acx_jpeg_entropy_encode_dev_workspace_bytes(H, W, B) bytes) need not be cleared: the call zeroes what it merges into on the
+ * stream, so a workspace may be used again by the next call on the same stream.  Before any launch: ACX_E_BADARG for a null
+ * pointer or one not aligned, B < 1, B, H or W outside 1 .. 65535, header_bytes outside 1 .. 65535, cap < 0, or a size whose blocks x 1,658 bits (a
+ * block's longest code) reach 2^31 -- bit offsets are 32-bit; ACX_E_WORKSPACE for a workspace that is too small.
+ * acx_jpeg_entropy_encode_dev_workspace_bytes returns 0 for the arguments the call refuses. */
+size_t acx_jpeg_entropy_encode_dev_workspace_bytes(int32_t H, int32_t W, int32_t B);
+int acx_jpeg_entropy_encode_dev(acx_ctx* ctx, const int16_t* coef, const uint8_t* header, int32_t header_bytes, int32_t H, int32_t W,
+                                int32_t B, uint8_t* files, int64_t cap, int32_t* nbytes, int32_t* status, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

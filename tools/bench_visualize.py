@@ -7,7 +7,15 @@
   end_to_end_frames_per_s     Visualizer.process_video from the frame folder to the finished .avi (host clock around work that ends
                               in the file's rename), with --decode as the frame reader.
 The folder is written by Pillow (4:2:0, quality 75) into a temporary directory.  One JSON line; nothing is asserted.
-  python tools/bench_visualize.py --frames 512 --source 240x320 --decode gpu --quality 90 --threads 8"""
+  python tools/bench_visualize.py --frames 512 --source 240x320 --decode gpu --quality 90 --threads 8
+With --entropy host,gpu the two Huffman coders are compared in this one process, on the same folder, canvas and thread count:
+  entropy_dev_frames_per_s    acx_jpeg_entropy_encode_dev's launches on the batch entropy_frames_per_s codes (HIP events);
+  end_to_end                  per mode the --reps repetitions of Visualizer.process_video, the modes alternating (host, gpu, host,
+                              gpu ...), and the bytes copied to the host per frame;
+  gpu_not_slower              the condition stated before the run: the gpu mode's mean is not below the host mode's by more than
+                              the spread (largest - smallest) of the repetitions of either mode;
+  files_identical             the modes' .avi files are the same bytes.
+The line is also written to --out (default profiles/visualize_entropy_bench.json)."""
 import argparse, json, os, shutil, sys, tempfile, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -40,6 +48,9 @@ def main():
     ap.add_argument("--canvas", default="1200x800", help="WxH of the picture")
     ap.add_argument("--classes", type=int, default=13)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--entropy", default=None, help="host,gpu: compare the two Huffman coders end to end")
+    ap.add_argument("--reps", type=int, default=2, help="repetitions per mode of the comparison")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "visualize_entropy_bench.json"))
     args = ap.parse_args()
     from PIL import Image
     from anomalyclip_amd import ops
@@ -95,6 +106,45 @@ def main():
         out = os.path.join(root, "out", "qualitatives_var", "video0.avi")
         res["avi_bytes"] = os.path.getsize(out)
         viz.close()
+        if args.entropy:
+            modes = [V.check_entropy(m, "--entropy") for m in args.entropy.split(",")]
+            head = torch.from_numpy(ops.jpeg_encode_header(viz.qtabs, canvas[1], canvas[0])).to(dev)
+            ws = torch.empty(ops.jpeg_entropy_encode_dev_workspace_bytes(canvas[1], canvas[0], B), dtype=torch.uint8, device=dev)
+            files = torch.empty(B, viz.cap, dtype=torch.uint8, device=dev)
+            nb, st = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+            res["entropy_dev_frames_per_s"] = event_rate(lambda: ops.jpeg_entropy_encode_dev(
+                coef, head, canvas[1], canvas[0], cap=viz.cap, files=files, nbytes=nb, status=st, workspace=ws), B, args.iters)
+            res["entropy_dev_status"] = sorted(set(st.cpu().tolist()))
+            res["entropy_dev_workspace_bytes"] = ws.numel()
+            del ws, files
+            vs = {m: V.Visualizer(7, None, "{:06d}.jpg", os.path.join(root, "out_" + m), dev, decode=args.decode, quality=args.quality,
+                                  canvas=canvas, frames_root=os.path.join(root, "frames"), batch=B, threads=args.threads, entropy=m)
+                  for m in modes}
+            rates, data = {m: [] for m in modes}, {}
+            for r in range(args.reps + 1):                 # (the first round warms each mode's buffers up and is not counted)
+                for m in modes:
+                    avi = os.path.join(root, "out_" + m, "qualitatives_var", "video0.avi")
+                    if os.path.exists(avi):
+                        os.remove(avi)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    vs[m].process_video(scores, None, softmax, labels, path)
+                    dt = time.perf_counter() - t0
+                    if r:
+                        rates[m].append(T / dt)
+                    with open(avi, "rb") as fh:
+                        data[m] = fh.read()
+            res["end_to_end"] = {m: {"frames_per_s": rates[m], "mean_frames_per_s": float(np.mean(rates[m])),
+                                     "bytes_to_host_per_frame": vs[m].bytes_to_host / vs[m].frames_written} for m in modes}
+            for v in vs.values():
+                v.close()
+            res["files_identical"] = len({d for d in data.values()}) == 1
+            if "host" in rates and "gpu" in rates:
+                spread = max(max(v) - min(v) for v in rates.values())
+                res["spread_frames_per_s"] = spread
+                res["gpu_not_slower"] = bool(np.mean(rates["gpu"]) >= np.mean(rates["host"]) - spread)
+            with open(args.out, "w") as fh:
+                fh.write(json.dumps(res) + "\n")
         print(json.dumps(res))
     finally:
         shutil.rmtree(root, ignore_errors=True)
