@@ -323,6 +323,10 @@ _SIGS = {
                                   c_void_p, c_void_p]),
     "acx_sample_segments": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),
     "acx_tile_videos": (C.c_int, [c_void_p] * 9 + [c_int32, c_int64] + [c_int32] * 5 + [c_void_p]),
+    "acx_sample_segments_f16": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),
+    "acx_tile_videos_f16": (C.c_int, [c_void_p] * 9 + [c_int32, c_int64] + [c_int32] * 5 + [c_void_p]),
+    "acx_cast_rows_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p]),
+    "acx_expand_rows_f16": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "acx_jpeg_parse": (C.c_int, [c_void_p, c_size_t, c_void_p]),
     "acx_jpeg_entropy_decode": (C.c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
     "acx_jpeg_scan_pack": (C.c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),

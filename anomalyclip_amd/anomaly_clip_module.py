@@ -270,7 +270,8 @@ class AnomalyCLIPModule(_Base):
         acc = torch.zeros(self.net.embedding_dim, dtype=torch.float32, device=self.device)
         count = 0
         for f in videos:
-            ops.colsum_(acc, f)
+            # (a float16 bank: widened first, exactly, so the sums are those of a float32 bank holding the same values)
+            ops.colsum_(acc, f if f.dtype == torch.float32 else ops.expand_rows_f16(f))
             count += f.shape[0]
         return self._finish_ncentroid(acc, count)
 

@@ -123,8 +123,11 @@ class ResidentTestLoader(StreamedTestLoader):
 
 
 class AnomalyCLIPDataModule:
-    def __init__(self, encoder=None, decode: str = "pil", pack: bool = False, **hparams):
+    def __init__(self, encoder=None, decode: str = "pil", pack: bool = False, bank_dtype: str = "float32", **hparams):
+        from .feature_bank import check_bank_dtype
         from .jpeg import check_decode
+        check_bank_dtype(bank_dtype)
+        self.bank_dtype = bank_dtype                              # frames mode: the banks' element type (not a reference key)
         self.pack = bool(pack)                                    # frames mode: FeatureBank.from_frames(pack=...) (not a reference key)
         self.decode = check_decode(decode)                        # frames mode: how the frame files are decoded (not a reference key)
         hp = dict(_DEFAULTS)
@@ -183,7 +186,7 @@ class AnomalyCLIPDataModule:
         try:
             return FeatureBank.from_frames(enc, records, hp.frames_root, hp.image_tmpl, int(hp.ncrops), hp.get("scale_size"),
                                            int(hp.get("decode_threads", 8)), self.device, hp.get("max_bytes"), hp.get("log"),
-                                           decode=self.decode, pack=self.pack)
+                                           decode=self.decode, pack=self.pack, bank_dtype=self.bank_dtype)
         finally:
             enc.train(was_training)
 

@@ -13,6 +13,11 @@ baseline JPEG files on the host and reconstructs the frames on the device (anoma
 (`plan_launches`), decodes launch k + 1 while launch k is encoded whichever videos they belong to, and `extract_dataset` has a
 `FeatureWriter` thread write the files behind the encode loop.  Off by default; with it off every call runs the per-video loop above.
 
+`dtype="float16"` (`--dtype float16`) writes half-precision files (numpy's '<f2', the same shape): every block of encoder rows is
+rounded on the device (ops.cast_rows_f16: to nearest even, as numpy's astype rounds) before it is copied back, so the copy, the
+pinned buffers and the writer move half the bytes.  A feature that no half holds (|x| >= 65520) is a ValueError naming the video,
+and no file is left under the final name.  A present file of the OTHER dtype never counts as complete: it is rewritten.
+
     python -m anomalyclip_amd.extract --arch ViT-B/16 --weights last.ckpt --frames-root frames --out-root features --ncrops 5
 """
 from __future__ import annotations
@@ -31,6 +36,14 @@ import torch
 
 TEMPLATE = "{:06d}.jpg"                # the reference's default imagefile_template (video_dataset.py:171)
 MAX_DECODE_THREADS = 16                # the decode pool never grows beyond this, whatever the machine has
+DTYPES = ("float32", "float16")        # what a feature file may hold
+
+
+def check_dtype(dtype) -> str:
+    """dtype= of extract_video / extract_dataset: "float32" or "float16" """
+    if dtype not in DTYPES:
+        raise ValueError(f"dtype={dtype!r}: feature files are written as 'float32' or 'float16'")
+    return dtype
 
 
 # ---------------------------------------------------------------------------------------------------------------- frames
@@ -195,25 +208,26 @@ def feature_path(out_path: str) -> str:
     return out_path if out_path.endswith(".npy") else out_path + ".npy"
 
 
-def is_complete(out_path: str, shape: Tuple[int, int]) -> bool:
-    """an existing feature file whose header states float32 `shape` (a leftover `.tmp` beside it does not count)"""
+def is_complete(out_path: str, shape: Tuple[int, int], dtype: str = "float32") -> bool:
+    """an existing feature file whose header states `dtype` (float32, float16) and `shape`; a leftover `.tmp` beside it does not
+    count, and neither does a file of the other dtype: asking for float16 where float32 files lie rewrites them, and back"""
     from .feature_stream import FeatureStream
     p = feature_path(out_path)
     if not os.path.isfile(p):
         return False
     try:
         with open(p, "rb") as fh:
-            got, fortran, dtype = FeatureStream._npy_header(fh)
+            got, fortran, have = FeatureStream._npy_header(fh)
     except Exception:
         return False
-    return tuple(got) == tuple(shape) and not fortran and dtype == np.dtype("<f4")
+    return tuple(got) == tuple(shape) and not fortran and have == np.dtype("<f2" if dtype == "float16" else "<f4")
 
 
 def write_features(out_path: str, rows: np.ndarray) -> str:
-    """np.save format, float32 [T * ncrops, D]: written beside its place as `<out>.npy.tmp` (a stale one is replaced), then moved
-    into place atomically -- a reader never sees a half-written file under the final name"""
+    """np.save format, float32 [T * ncrops, D] (float16 rows stay float16): written beside its place as `<out>.npy.tmp` (a stale
+    one is replaced), then moved into place atomically -- a reader never sees a half-written file under the final name"""
     p = feature_path(out_path)
-    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    rows = np.ascontiguousarray(rows, dtype=np.float16 if np.asarray(rows).dtype == np.float16 else np.float32)
     assert rows.ndim == 2
     os.makedirs(os.path.dirname(os.path.abspath(p)), exist_ok=True)
     tmp = p + ".tmp"
@@ -227,7 +241,8 @@ class FeatureWriter:
     """One thread that writes feature files behind the encode loop (`extract_dataset(pack=True)`).  `acquire()` takes one of
     `max_inflight` places for a video's row buffer and blocks while all are taken; `submit(event, rows, out_path)` hands the
     filled buffer over: the thread waits for `event` (anything with `synchronize()`, or None), calls `write_features` and gives
-    the place back.  The first exception is kept: every job behind it is dropped unwritten (its place is still given back, so
+    the place back.  `overflow` (a pinned int64 [1] that the same event covers: float16 rows) is looked at before the write: non-zero
+    is a ValueError naming the file, and nothing is written.  The first exception is kept: every job behind it is dropped unwritten (its place is still given back, so
     the producer never waits for a dead writer), the `.npy.tmp` of the failed write is removed, and `check()` / `close()`
     raise it in the caller's thread -- `close()` after the thread has been joined."""
 
@@ -243,8 +258,8 @@ class FeatureWriter:
         self._places.acquire()
         self.check()
 
-    def submit(self, event, rows, out_path: str, tag=None) -> None:
-        self._jobs.put((event, rows, out_path, tag))
+    def submit(self, event, rows, out_path: str, tag=None, overflow=None) -> None:
+        self._jobs.put((event, rows, out_path, tag, overflow))
 
     def check(self) -> None:
         if self.error is not None:
@@ -255,11 +270,12 @@ class FeatureWriter:
             job = self._jobs.get()
             if job is None:
                 return
-            event, rows, out_path, tag = job
+            event, rows, out_path, tag, overflow = job
             try:
                 if self.error is None:
                     if event is not None:
                         event.synchronize()
+                    check_overflow(overflow, out_path)
                     write_features(out_path, rows.numpy() if isinstance(rows, torch.Tensor) else rows)
                     if self._done is not None:
                         self._done(tag)
@@ -284,6 +300,23 @@ class FeatureWriter:
 
 
 # ---------------------------------------------------------------------------------------------------------------- extractor
+def _half_buffer(shape: Tuple[int, int]):
+    """(rows, count): pinned float16 `shape` and, behind it in the same allocation, the int64 [1] that the overflow counter of the
+    casts is copied into"""
+    n = shape[0] * shape[1] * 2
+    pad = -n % 8
+    buf = torch.empty(n + pad + 8, dtype=torch.uint8).pin_memory()
+    return buf[:n].view(torch.float16).view(shape), buf[n + pad:].view(torch.int64)
+
+
+def check_overflow(count, out_path: str) -> None:
+    """count: the (synchronised) overflow counter of a video's casts, or None"""
+    n = 0 if count is None else int(count.reshape(-1)[0])
+    if n:
+        raise ValueError(f"{feature_path(out_path)}: {n} feature value(s) do not fit float16 (|x| >= 65520 rounds to infinity); "
+                         f"not written: extract this video with dtype='float32'")
+
+
 def _encoder_of(net_or_encoder):
     return getattr(net_or_encoder, "image_encoder", net_or_encoder)
 
@@ -337,12 +370,14 @@ def encode_video(encoder, frames, ncrops: int = 1, scale_size: Optional[int] = N
 
 
 def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: Optional[int] = None, overwrite: bool = False,
-                  decode: str = "pil") -> dict:
+                  decode: str = "pil", dtype: str = "float32") -> dict:
     """Encodes the frames of one video (a FrameFolderReader, or decoded uint8 frames [T, H, W, 3]) into `out_path` (.npy).
     decode="gpu" / "gpu_entropy": the frames of a FrameFolderReader are read by a jpeg.JpegFolderReader /
     jpeg.JpegEntropyFolderReader over the same files instead.
+    dtype: "float32", or "float16" (rounded on the device, block by block; ValueError and no file if a value does not fit).
     Returns {"written": bool, "frames": T, "rows": T * ncrops}."""
-    from . import jpeg
+    from . import jpeg, ops
+    check_dtype(dtype)
     jpeg.check_decode(decode)
     encoder = _encoder_of(encoder)
     reader = frames if hasattr(frames, "batches") else _ArrayFrames(frames)
@@ -351,13 +386,23 @@ def extract_video(encoder, frames, out_path: str, ncrops: int = 1, scale_size: O
     T, D = len(reader), int(encoder.output_dim)
     shape = (T * ncrops, D)
     check_eval_mode(encoder)
-    if not overwrite and is_complete(out_path, shape):
+    if not overwrite and is_complete(out_path, shape, dtype):
         return {"written": False, "frames": T, "rows": shape[0]}
     check_encoder(encoder)
-    out = torch.empty(shape, dtype=torch.float32).pin_memory()
+    dev = next(encoder.parameters()).device
+    if dtype == "float16":
+        out, count = _half_buffer(shape)
+        over = torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        out, count, over = torch.empty(shape, dtype=torch.float32).pin_memory(), None, None
     for r0, rows in encode_video(encoder, reader, ncrops, scale_size):
+        if over is not None:
+            rows = ops.cast_rows_f16(rows, over)
         out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
-    torch.cuda.current_stream(next(encoder.parameters()).device).synchronize()
+    if over is not None:
+        count.copy_(over, non_blocking=True)          # read once, behind the last block, by the synchronisation below
+    torch.cuda.current_stream(dev).synchronize()
+    check_overflow(count, out_path)
     write_features(out_path, out.numpy())
     return {"written": True, "frames": T, "rows": shape[0]}
 
@@ -669,13 +714,14 @@ class _InOrder:
 
 
 def _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scale_size, overwrite, template, decode_threads, log,
-                            decode, max_inflight) -> dict:
+                            decode, max_inflight, dtype="float32") -> dict:
     """extract_dataset(pack=True): encode_videos over the videos whose files are not complete; each video's rows are copied into a
     pinned buffer of its own, at most `max_inflight` of them alive, and written by a FeatureWriter behind the encode loop"""
-    from . import jpeg
+    from . import jpeg, ops
     check_eval_mode(encoder)
     D = int(encoder.output_dim)
     todo, results, lines = {}, {}, _InOrder(log)
+    half = dtype == "float16"
 
     def line(idx, video):
         written, _, rows = results[idx]
@@ -685,7 +731,7 @@ def _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scal
         for idx, (video, start, end) in enumerate(videos):
             reader = jpeg.make_reader(decode, frames_root, video, start, end, template, decode_threads)
             T, out_path = len(reader), os.path.join(out_root, video)
-            if not overwrite and is_complete(out_path, (T * ncrops, D)):
+            if not overwrite and is_complete(out_path, (T * ncrops, D), dtype):
                 reader.close()
                 results[idx] = (False, T, T * ncrops)
                 lines.put(idx, line(idx, video))
@@ -700,19 +746,28 @@ def _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scal
 
     writer = FeatureWriter(max_inflight, done=written)
     gen = encode_videos(encoder, readers(), ncrops, scale_size, decode_threads=decode_threads)
-    cur_idx, out = None, None
+    cur_idx, out, count, over = None, None, None, None
     try:
         for idx, r0, rows in gen:
             _, out_path, T = todo[idx]
             if idx != cur_idx:
                 writer.acquire()                       # (blocks while max_inflight videos' buffers are alive)
-                cur_idx, out = idx, torch.empty((T * ncrops, D), dtype=torch.float32).pin_memory()
+                cur_idx = idx
+                if half:                               # the video's own overflow counter: its casts add to it, the writer reads it
+                    out, count = _half_buffer((T * ncrops, D))
+                    over = torch.zeros(1, dtype=torch.int64, device=rows.device)
+                else:
+                    out = torch.empty((T * ncrops, D), dtype=torch.float32).pin_memory()
+            if half:
+                rows = ops.cast_rows_f16(rows, over)
             out[r0:r0 + rows.shape[0]].copy_(rows, non_blocking=True)
             if r0 + rows.shape[0] == T * ncrops:
+                if half:
+                    count.copy_(over, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(rows.device))
-                writer.submit(ev, out, out_path, idx)
-                out = None
+                writer.submit(ev, out, out_path, idx, count)
+                out, count, over = None, None, None
     finally:
         gen.close()
         writer.close(check=False)
@@ -740,15 +795,18 @@ def list_videos(frames_root: str, template: str = TEMPLATE) -> List[str]:
 
 def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root: str, out_root: str, ncrops: int = 1,
                     scale_size: Optional[int] = None, overwrite: bool = False, template: str = TEMPLATE,
-                    decode_threads: int = 8, log=None, decode: str = "pil", pack: bool = False, max_inflight: int = 4) -> dict:
+                    decode_threads: int = 8, log=None, decode: str = "pil", pack: bool = False, max_inflight: int = 4,
+                    dtype: str = "float32") -> dict:
     """Every video of the annotation file (rows `path start end label...`; without one: every frame folder under frames_root)
     -> `<out_root>/<path>.npy`.  Complete files are skipped unless overwrite.  decode: "pil" (Pillow on the host), "gpu" (baseline
     JPEG reconstructed on the device; every other file through Pillow) or "gpu_entropy" (its Huffman decoding on the device too).
     pack: the videos share encoder launches (encode_videos: every launch but the last is full, and the next video is decoded
     while this one is encoded) and the files are written by a thread behind the encode loop, at most `max_inflight` videos'
     rows waiting for it; the same files to round-off, the same counts and log lines.
+    dtype: "float32" or "float16" files (extract_video); a present file of the other dtype is rewritten, not kept.
     Returns {written, skipped, frames, rows}."""
     from . import jpeg
+    check_dtype(dtype)
     jpeg.check_decode(decode)
     encoder = _encoder_of(net_or_encoder)
     if annotation_file:
@@ -757,12 +815,12 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
         videos = [(v, None, None) for v in list_videos(frames_root, template)]
     if pack:
         return _extract_dataset_packed(encoder, videos, frames_root, out_root, ncrops, scale_size, overwrite, template,
-                                       decode_threads, log, decode, max_inflight)
+                                       decode_threads, log, decode, max_inflight, dtype)
     counts = {"written": 0, "skipped": 0, "frames": 0, "rows": 0}
     for video, start, end in videos:
         reader = jpeg.make_reader(decode, frames_root, video, start, end, template, decode_threads)
         try:
-            r = extract_video(encoder, reader, os.path.join(out_root, video), ncrops, scale_size, overwrite)
+            r = extract_video(encoder, reader, os.path.join(out_root, video), ncrops, scale_size, overwrite, dtype=dtype)
         finally:
             reader.close()
         counts["written" if r["written"] else "skipped"] += 1
@@ -822,6 +880,9 @@ def _parser():
     p.add_argument("--decode", default="pil", choices=("pil", "gpu", "gpu_entropy"),
                    help="pil: Pillow on the host; gpu: baseline JPEG, Huffman decoding on the host and the rest on the device; "
                         "gpu_entropy: the Huffman decoding on the device too")
+    p.add_argument("--dtype", default="float32", choices=DTYPES,
+                   help="element type of the files: float16 halves them (rounded to nearest even on the device; a value that does "
+                        "not fit is an error)")
     p.add_argument("--pack", action="store_true",
                    help="share encoder launches between videos and write the files behind the encode loop (many short clips)")
     return p
@@ -857,7 +918,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     load_encoder_weights(enc, a.arch, a.weights)
     enc = enc.to(torch.device("cuda", torch.cuda.current_device())).eval()
     counts = extract_dataset(enc, a.annotations, a.frames_root, a.out_root, a.ncrops, a.scale_size, a.overwrite,
-                             log=lambda s: print(s, file=sys.stderr), decode=a.decode, pack=a.pack)
+                             log=lambda s: print(s, file=sys.stderr), decode=a.decode, pack=a.pack, dtype=a.dtype)
     import json
     print(json.dumps(counts))
     return 0

@@ -22,11 +22,20 @@ from . import ops, parallel
 from .feature_stream import FeatureStream
 
 _STAGE_BYTES = 64 << 20          # pinned staging slot of the bank load (grown to the largest file)
+BANK_DTYPES = {"float32": torch.float32, "float16": torch.float16}
+
+
+def check_bank_dtype(bank_dtype) -> torch.dtype:
+    """bank_dtype= of FeatureBank.from_frames / AnomalyCLIPDataModule: "float32" or "float16" """
+    if bank_dtype not in BANK_DTYPES:
+        raise ValueError(f"bank_dtype={bank_dtype!r}: a feature bank is 'float32' or 'float16'")
+    return BANK_DTYPES[bank_dtype]
 
 
 class FeatureBank:
-    """Every feature file of `paths` in one device tensor `bank` [sum_v rows_v, D] float32, files in order and rows as stored
-    (frame t, crop c in row t * ncrops + c).  `row_off` int64 [V], `frames` int32 [V] (rows_v // ncrops: what a frame index wraps
+    """Every feature file of `paths` in one device tensor `bank` [sum_v rows_v, D], files in order and rows as stored
+    (frame t, crop c in row t * ncrops + c), in the files' element type `dtype`: float32, or float16 when every file is a
+    half-precision one (the gathers widen the rows on their way out: every loader still yields float32).  `row_off` int64 [V], `frames` int32 [V] (rows_v // ncrops: what a frame index wraps
     around) and `labels` int64 [V] live on the device; `paths`, `num_frames` (the annotation rows' end - start + 1: what the
     train-mode draw is sized by), `file_frames`, `offsets` and `labels_host` on the host.  Under data parallelism every rank
     holds the full bank."""
@@ -42,17 +51,17 @@ class FeatureBank:
         if self.ncrops <= 0:
             raise ValueError(f"FeatureBank: ncrops = {ncrops}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        rows, self.D = self._scan()
+        rows, self.D, dtype = self._scan()
         self.file_frames = [r // self.ncrops for r in rows]
         self.offsets = np.concatenate([[0], np.cumsum(rows, dtype=np.int64)]).astype(np.int64)       # [V + 1] bank rows
-        need = int(self.offsets[-1]) * self.D * 4
+        need = int(self.offsets[-1]) * self.D * dtype.itemsize
         if max_bytes is None:
             with torch.cuda.device(self.device):
                 max_bytes = int(torch.cuda.mem_get_info()[0] * 0.8)       # 80 % of what is free now: room left for the training step
         if need > max_bytes:
             raise ValueError(f"FeatureBank: {len(self.paths)} feature files need {need} bytes of device memory, "
                              f"{int(max_bytes)} bytes are available (banks larger than device memory are not supported)")
-        self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=torch.float32, device=self.device)
+        self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=dtype, device=self.device)
         self._load(rows, max(1, int(readers)))
         self.row_off = torch.from_numpy(self.offsets[:-1].copy()).to(self.device)
         self.frames = torch.tensor(self.file_frames, dtype=torch.int32).to(self.device)
@@ -61,7 +70,8 @@ class FeatureBank:
     @classmethod
     def from_frames(cls, encoder, records, frames_root: str, image_tmpl: str = "{:06d}.jpg", ncrops: int = 1,
                     scale_size: Optional[int] = None, decode_threads: int = 8, device: Optional[torch.device] = None,
-                    max_bytes: Optional[int] = None, log=None, decode: str = "pil", pack: bool = False) -> "FeatureBank":
+                    max_bytes: Optional[int] = None, log=None, decode: str = "pil", pack: bool = False,
+                    bank_dtype: str = "float32") -> "FeatureBank":
         """The same bank, filled by the CLIP image encoder instead of from files: every frame an annotation row names
         (`records`: objects with `video`, `start_frame`, `end_frame`, `label`; frame t of video v is
         `<frames_root>/<video>/image_tmpl.format(t + start_frame)`, end inclusive) is decoded and encoded ONCE through
@@ -69,10 +79,14 @@ class FeatureBank:
         block of rows is copied from the encoder's output straight into its bank slice.  `paths` are the frame folders,
         `file_frames == num_frames`.  The size follows from the rows and `encoder.output_dim` and is checked before any frame is
         opened.  decode: "pil", "gpu" or "gpu_entropy", as extract.extract_dataset takes it.  pack: the videos share encoder
-        launches (extract.encode_videos), each piece of rows copied into its video's bank slice: the same bank to round-off."""
+        launches (extract.encode_videos), each piece of rows copied into its video's bank slice: the same bank to round-off.
+        bank_dtype: "float16" keeps the rows as halves -- each block is rounded on the device (ops.cast_rows_f16: to nearest even,
+        as numpy rounds) on its way into the bank, half the memory; a feature too large for a half (|x| >= 65520) is a ValueError
+        naming the video once the bank is filled."""
         from . import extract as X
         from . import jpeg
         jpeg.check_decode(decode)
+        dtype = check_bank_dtype(bank_dtype)
         encoder = X._encoder_of(encoder)
         records = list(records)
         self = cls.__new__(cls)
@@ -92,20 +106,22 @@ class FeatureBank:
         self.file_frames = list(self.num_frames)
         rows = [n * self.ncrops for n in self.num_frames]
         self.offsets = np.concatenate([[0], np.cumsum(rows, dtype=np.int64)]).astype(np.int64)
-        need = int(self.offsets[-1]) * self.D * 4
+        need = int(self.offsets[-1]) * self.D * dtype.itemsize
         if max_bytes is None:
             with torch.cuda.device(next(encoder.parameters()).device):
                 max_bytes = int(torch.cuda.mem_get_info()[0] * 0.8)       # 80 % of what is free now, as for a bank of files
         if need > max_bytes:
             raise ValueError(f"FeatureBank: the {int(self.offsets[-1]) // self.ncrops} frames of {len(records)} videos need {need} "
-                             f"bytes of device memory at {self.ncrops} crop(s) x {self.D} floats, {int(max_bytes)} bytes are "
+                             f"bytes of device memory at {self.ncrops} crop(s) x {self.D} {bank_dtype} values, {int(max_bytes)} bytes are "
                              f"available (banks larger than device memory are not supported; anomalyclip_amd.extract writes "
                              f"the same rows to feature files instead)")
         X.check_encoder(encoder)
         self.device = next(encoder.parameters()).device          # the rows never leave the device they are computed on
         if device is not None and (torch.device(device).type != "cuda" or torch.device(device).index not in (None, self.device.index)):
             raise ValueError(f"FeatureBank.from_frames: the encoder is on {self.device}, the bank was asked for on {device}")
-        self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=torch.float32, device=self.device)
+        self.bank = torch.empty(int(self.offsets[-1]), self.D, dtype=dtype, device=self.device)
+        # float16: one overflow counter per video, added to by the casts and read once, after the synchronisation below
+        self._overflow = torch.zeros(len(records), dtype=torch.int64, device=self.device) if dtype == torch.float16 else None
         with torch.cuda.device(self.device):
             if pack:
                 self._fill_packed(encoder, records, str(frames_root), image_tmpl, scale_size, decode_threads, decode, log, rows)
@@ -122,6 +138,7 @@ class FeatureBank:
                 if log:
                     log(f"encoded {self.paths[v]}  [{rows[v]} rows]")
             torch.cuda.current_stream().synchronize()           # the readers' pinned buffers are released on return
+        self.check_overflow()
         self.row_off = torch.from_numpy(self.offsets[:-1].copy()).to(self.device)
         self.frames = torch.tensor(self.file_frames, dtype=torch.int32).to(self.device)
         self.labels = torch.from_numpy(self.labels_host).to(self.device)
@@ -140,7 +157,7 @@ class FeatureBank:
         gen = X.encode_videos(encoder, readers(), self.ncrops, scale_size, decode_threads=decode_threads)
         try:
             for v, r0, blk in gen:
-                self.video(v)[r0:r0 + blk.shape[0]].copy_(blk)
+                self._put(v, r0, blk)
                 if log and r0 + blk.shape[0] == rows[v]:
                     log(f"encoded {self.paths[v]}  [{rows[v]} rows]")
         except FileNotFoundError as e:
@@ -157,27 +174,61 @@ class FeatureBank:
         if len(frames) * self.ncrops != dst.shape[0]:
             raise ValueError(f"{self.paths[v]}: {len(frames)} frames for {dst.shape[0] // self.ncrops} in the bank")
         for r0, blk in X.encode_video(encoder, frames, self.ncrops, scale_size):
-            dst[r0:r0 + blk.shape[0]].copy_(blk)
+            self._put(v, r0, blk)
+
+    def _put(self, v: int, r0: int, blk: torch.Tensor) -> None:
+        """a block of encoder rows into rows r0 ... of video v: a device-to-device copy, or the cast of a float16 bank"""
+        dst = self.video(v)[r0:r0 + blk.shape[0]]
+        if dst.dtype == torch.float16:
+            if getattr(self, "_overflow", None) is None:
+                self._overflow = torch.zeros(len(self.paths), dtype=torch.int64, device=self.device)
+            ops.cast_rows_f16(blk, self._overflow[v:v + 1], out=dst)
+        else:
+            dst.copy_(blk)
+
+    def check_overflow(self) -> None:
+        """float16 bank filled from frames: raises ValueError for the first video with a feature that no half holds (the casts
+        counted them on the device; call after the stream that ran them is synchronised).  from_frames does; after fill_video
+        calls of one's own it is the caller's to call."""
+        over = getattr(self, "_overflow", None)
+        if over is None:
+            return
+        n = over.cpu().numpy()
+        bad = np.flatnonzero(n)
+        if bad.size:
+            v = int(bad[0])
+            raise ValueError(f"{self.paths[v]}: {int(n[v])} feature value(s) do not fit float16 (|x| >= 65520 rounds to infinity); "
+                             f"{bad.size} video(s) affected: use bank_dtype='float32'")
 
     def __len__(self) -> int:
         return len(self.paths)
 
     @property
+    def dtype(self) -> torch.dtype:
+        """the bank's element type: torch.float32, or torch.float16 (half-precision feature files, bank_dtype="float16")"""
+        return self.bank.dtype
+
+    @property
     def nbytes(self) -> int:
-        return self.bank.numel() * 4
+        return self.bank.numel() * self.bank.element_size()
 
     def video(self, v: int) -> torch.Tensor:
         """the rows of video v as stored in its file: a view of the bank"""
         return self.bank[int(self.offsets[v]): int(self.offsets[v + 1])]
 
-    def _scan(self) -> Tuple[List[int], int]:
-        rows, D = [], None
+    def _scan(self) -> Tuple[List[int], int, torch.dtype]:
+        rows, D, first = [], None, None
         for p in self.paths:
             with open(p, "rb") as fh:
                 shape, fortran, dtype = FeatureStream._npy_header(fh)
-            if len(shape) != 2 or fortran or dtype != np.dtype("<f4"):
-                raise ValueError(f"{p}: feature files must be C-ordered float32 with two dimensions "
+            if len(shape) != 2 or fortran or dtype not in (np.dtype("<f4"), np.dtype("<f2")):
+                raise ValueError(f"{p}: feature files must be C-ordered float32 (or float16) with two dimensions "
                                  f"(shape {tuple(shape)}, fortran_order {fortran}, dtype {dtype})")
+            if first is None:
+                first = (dtype, p)
+            if dtype != first[0]:
+                raise ValueError(f"{p}: dtype {dtype}, but {first[1]} and every file before this one hold {first[0]} (a bank has "
+                                 f"one element type: float32 files or float16 files, not both)")
             if shape[0] == 0 or shape[0] % self.ncrops:
                 raise ValueError(f"{p}: {shape[0]} rows are not a positive multiple of ncrops = {self.ncrops}")
             if D is None:
@@ -187,14 +238,14 @@ class FeatureBank:
             rows.append(int(shape[0]))
         if D is None:
             raise ValueError("FeatureBank: no feature files")
-        return rows, D
+        return rows, D, (torch.float16 if first[0] == np.dtype("<f2") else torch.float32)
 
     def _load(self, rows: List[int], readers: int) -> None:
         """files -> two pinned staging slots (filled by `readers` threads: file reads release the GIL) -> asynchronous copies into
         the bank; the files of a group are consecutive, so a group is ONE contiguous copy and the next group is read meanwhile."""
         from concurrent.futures import ThreadPoolExecutor
-        D = self.D
-        slot_elems = max(_STAGE_BYTES // 4, max(rows) * D)
+        D, esize = self.D, self.bank.element_size()              # (the slots hold the files' elements: halves stage half the bytes)
+        slot_elems = max(_STAGE_BYTES // esize, max(rows) * D)
         groups, cur, used = [], [], 0
         for v, r in enumerate(rows):
             if cur and used + r * D > slot_elems:
@@ -204,7 +255,7 @@ class FeatureBank:
             used += r * D
         groups.append(cur)
         slot_elems = min(slot_elems, max(sum(rows[v] for v in g) * D for g in groups))
-        pinned = [torch.empty(slot_elems, dtype=torch.float32).pin_memory() for _ in range(min(2, len(groups)))]
+        pinned = [torch.empty(slot_elems, dtype=self.bank.dtype).pin_memory() for _ in range(min(2, len(groups)))]
         copied: List[Optional[torch.cuda.Event]] = [None] * len(pinned)
         flat = self.bank.view(-1)
 
@@ -213,8 +264,8 @@ class FeatureBank:
             with open(self.paths[v], "rb") as fh:
                 FeatureStream._npy_header(fh)
                 got = fh.readinto(memoryview(dst).cast("B"))
-            if got != dst.size * 4:
-                raise IOError(f"{self.paths[v]}: short read ({got} of {dst.size * 4} bytes)")
+            if got != dst.size * esize:
+                raise IOError(f"{self.paths[v]}: short read ({got} of {dst.size * esize} bytes)")
 
         def fill(g, slot):
             if copied[slot] is not None:                      # the copy that last read this slot must be done before it is refilled

@@ -16,7 +16,11 @@ from . import feature_index as FI
 
 
 class FeatureStream:
-    """Iterates over videos: yields (features [1, ncrops, 512*S, D] on `device`, num_frames, segment_size, path)."""
+    """Iterates over videos: yields (features [1, ncrops, 512*S, D] on `device`, num_frames, segment_size, path).
+    The files are float32 or float16 `.npy`; a float16 file stays halves through the pinned slot and the upload and is widened on
+    the device (ops.expand_rows_f16, exact), so what is yielded is float32 either way."""
+
+    _FILE_DTYPES = (np.dtype("<f4"), np.dtype("<f2"))
 
     def __init__(self, paths: Sequence[str], num_segments: int = 32, seg_length: int = 16, stride: int = 1,
                  ncrops: int = 1, device: Optional[torch.device] = None, max_tiles: int = 64, readers: int = 4):
@@ -40,7 +44,7 @@ class FeatureStream:
             return NF.read_array_header_2_0(fh)
         return NF._read_array_header(fh, version=(major, minor))
 
-    def _slot_buffer(self, slot: int, need: int, D: int) -> torch.Tensor:
+    def _slot_buffer(self, slot: int, need: int, D: int, dtype=np.float32) -> torch.Tensor:
         # The pinned buffer of this slot was the source of an asynchronous copy two videos ago: that copy must have
         # finished reading it before the host overwrites it (the device-side wait_event in __iter__ orders the CONSUMER
         # stream only, not the host).
@@ -48,11 +52,15 @@ class FeatureStream:
             self._copied[slot].synchronize()
             self._copied[slot] = None
         buf = self._pinned[slot]
+        if np.dtype(dtype) == np.float16:
+            need = (need + 1) // 2
         if buf is None or buf.numel() < need:
             # pinning is slow (~1 GB/s): start at 16 tiles and grow by half so that a run re-pins a handful of times
             grown = 0 if buf is None else buf.numel() * 3 // 2
             buf = torch.empty(max(need, grown, self.ncrops * 16 * 512 * D), dtype=torch.float32).pin_memory()
             self._pinned[slot] = buf
+        if np.dtype(dtype) == np.float16:                # halves: the same slot, two to a float
+            return buf.view(torch.float16)
         return buf
 
     def _host_tile(self, path: str, slot: int):
@@ -63,15 +71,15 @@ class FeatureStream:
         if self.ncrops == 1 and self.stride == 1:
             with open(path, "rb") as fh:
                 shape, fortran, dtype = self._npy_header(fh)
-                if len(shape) == 2 and not fortran and dtype == np.dtype("<f4"):
+                if len(shape) == 2 and not fortran and dtype in self._FILE_DTYPES:
                     T, D = shape
                     starts, S = FI.test_start_indices(T, self.N, self.L, self.stride)
                     rows = len(starts) * self.L
-                    view = self._slot_buffer(slot, rows * D, D)[: rows * D].view(1, rows, D)
+                    view = self._slot_buffer(slot, rows * D, D, dtype)[: rows * D].view(1, rows, D)
                     dst = view.numpy()[0]
                     got = fh.readinto(memoryview(dst[:T]).cast("B"))
-                    if got != T * D * 4:
-                        raise IOError(f"{path}: short read ({got} of {T * D * 4} bytes)")
+                    if got != T * D * dtype.itemsize:
+                        raise IOError(f"{path}: short read ({got} of {T * D * dtype.itemsize} bytes)")
                     for r in range(T, rows, T):
                         n = min(T, rows - r)
                         dst[r:r + n] = dst[:n]
@@ -80,12 +88,13 @@ class FeatureStream:
         D = arr.shape[-1]
         T = arr.shape[0] // self.ncrops
         starts, S = FI.test_start_indices(T, self.N, self.L, self.stride)
-        if self.stride == 1 and arr.dtype == np.float32 and arr.ndim == 2 and arr.flags.c_contiguous:
+        held = arr.dtype if arr.dtype in self._FILE_DTYPES else np.dtype(np.float32)      # what the pinned slot holds
+        if self.stride == 1 and arr.dtype in self._FILE_DTYPES and arr.ndim == 2 and arr.flags.c_contiguous:
             # several crops, stride 1: crop c of the tile is rows c, c + ncrops, ... of the file in order, then its first rows
             # again -- one strided copy per crop straight out of the mapping into the pinned slot, no index gather
             rows = len(starts) * self.L
             need = self.ncrops * rows * D
-            view = self._slot_buffer(slot, need, D)[:need].view(self.ncrops, rows, D)
+            view = self._slot_buffer(slot, need, D, held)[:need].view(self.ncrops, rows, D)
             dst = view.numpy()
             src = arr.reshape(T, self.ncrops, D)
             for c in range(self.ncrops):
@@ -97,7 +106,7 @@ class FeatureStream:
         idx = FI.frame_index_table(starts, self.L, self.stride, T)
         rows = idx.shape[0]
         need = self.ncrops * rows * D
-        view = self._slot_buffer(slot, need, D)[:need].view(self.ncrops, rows, D)
+        view = self._slot_buffer(slot, need, D, held)[:need].view(self.ncrops, rows, D)
         src = np.asarray(arr).reshape(T, self.ncrops, D)
         np.take(src, idx, axis=0, out=view.numpy().transpose(1, 0, 2)) if self.ncrops == 1 else \
             view.numpy().__setitem__(slice(None), src[idx].transpose(1, 0, 2))
@@ -105,12 +114,12 @@ class FeatureStream:
 
     # ---- several videos per batch (AnomalyCLIP.forward_test_many / AnomalyCLIPModule.score_videos)
     def _geometry(self, path: str):
-        """(T, S, rows per crop, D) of a feature file from its header alone"""
+        """(T, S, rows per crop, D, dtype) of a feature file from its header alone"""
         with open(path, "rb") as fh:
             shape, fortran, dtype = self._npy_header(fh)
         T = shape[0] // self.ncrops
         starts, S = FI.test_start_indices(T, self.N, self.L, self.stride)
-        return T, S, len(starts) * self.L, shape[-1]
+        return T, S, len(starts) * self.L, shape[-1], dtype
 
     def _fill(self, path: str, dst: np.ndarray, T: int, rows: int):
         """test-mode tile of one video into dst [ncrops, rows, D] (pinned memory): same index semantics as _host_tile"""
@@ -119,16 +128,16 @@ class FeatureStream:
             if self.ncrops == 1:
                 with open(path, "rb") as fh:
                     shape, fortran, dtype = self._npy_header(fh)
-                    if len(shape) == 2 and not fortran and dtype == np.dtype("<f4"):
+                    if len(shape) == 2 and not fortran and dtype in self._FILE_DTYPES and dtype == dst.dtype:
                         got = fh.readinto(memoryview(dst[0, :T]).cast("B"))
-                        if got != T * D * 4:
-                            raise IOError(f"{path}: short read ({got} of {T * D * 4} bytes)")
+                        if got != T * D * dtype.itemsize:
+                            raise IOError(f"{path}: short read ({got} of {T * D * dtype.itemsize} bytes)")
                         for r in range(T, rows, T):
                             n = min(T, rows - r)
                             dst[0, r:r + n] = dst[0, :n]
                         return
             arr = np.load(path, mmap_mode="r", allow_pickle=False)
-            if arr.dtype == np.float32 and arr.ndim == 2 and arr.flags.c_contiguous:
+            if arr.dtype in self._FILE_DTYPES and arr.ndim == 2 and arr.flags.c_contiguous:       # (a half file into a float slot: widened here)
                 src = arr.reshape(T, self.ncrops, D)
                 for c in range(self.ncrops):
                     np.copyto(dst[c, :T], src[:, c, :])
@@ -146,9 +155,11 @@ class FeatureStream:
         geo = [self._geometry(p) for p in paths]
         D = geo[0][3]
         need = sum(self.ncrops * g[2] * D for g in geo)
-        flat = self._slot_buffer(slot, need, D)[:need]
+        # a group of float16 files stays halves up to the device; a mixed group is widened on the host, file by file
+        held = np.float16 if all(g[4] == np.dtype("<f2") for g in geo) else np.float32
+        flat = self._slot_buffer(slot, need, D, held)[:need]
         jobs, off = [], 0
-        for p, (T, S, rows, _) in zip(paths, geo):
+        for p, (T, S, rows, _, _) in zip(paths, geo):
             n = self.ncrops * rows * D
             jobs.append((p, flat[off:off + n].view(self.ncrops, rows, D).numpy(), T, rows))
             off += n
@@ -159,7 +170,15 @@ class FeatureStream:
         else:
             for j in jobs:
                 self._fill(*j)
-        return flat.view(-1, D), [(T, S, rows, p) for p, (T, S, rows, _) in zip(paths, geo)]
+        return flat.view(-1, D), [(T, S, rows, p) for p, (T, S, rows, _, _) in zip(paths, geo)]
+
+    def _upload(self, view: torch.Tensor) -> torch.Tensor:
+        """the pinned tile to the device on the current (copy) stream; halves are widened there, behind their copy"""
+        dev = view.to(self.device, non_blocking=True)
+        if dev.dtype == torch.float16:
+            from . import ops
+            dev = ops.expand_rows_f16(dev)
+        return dev
 
     def _fill_pool(self):
         pool = self.__dict__.get("_pool")
@@ -195,7 +214,7 @@ class FeatureStream:
                 view, meta = fut.result()
                 fut = pool.submit(self._host_group, groups[i + 1], (i + 1) & 1) if i + 1 < len(groups) else None
                 with torch.cuda.stream(self._copy_stream):
-                    dev = view.to(self.device, non_blocking=True)
+                    dev = self._upload(view)
                     ev = torch.cuda.Event()
                     ev.record(self._copy_stream)
                 self._copied[slot] = ev
@@ -216,7 +235,7 @@ class FeatureStream:
                 view, T, S = fut.result()
                 fut = pool.submit(self._host_tile, self.paths[i + 1], (i + 1) & 1) if i + 1 < len(self.paths) else None
                 with torch.cuda.stream(self._copy_stream):
-                    dev = view.to(self.device, non_blocking=True)
+                    dev = self._upload(view)
                     ev = torch.cuda.Event()
                     ev.record(self._copy_stream)
                 self._copied[slot] = ev

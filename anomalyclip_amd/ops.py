@@ -660,8 +660,11 @@ def sample_segments(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Ten
     """One training batch out of a resident feature set (feature_bank.py): bank [rows, D] f32, row_off int64 [V], frames int32 [V],
     vid int32 [B], starts int32 [B * N], all on the device -> out [B, ncrops, N * L, D] with
     out[b, c, n*L + l] = bank[row_off[vid[b]] + ((starts[b*N + n] + l*stride) mod frames[vid[b]]) * ncrops + c].
-    One launch on the current stream, no host synchronisation (so `vid` values are the caller's to keep inside [0, V))."""
-    assert bank.dim() == 2 and bank.is_contiguous() and bank.dtype == torch.float32
+    One launch on the current stream, no host synchronisation (so `vid` values are the caller's to keep inside [0, V)).
+    A float16 bank (half-precision feature files) goes through acx_sample_segments_f16: the same rows, widened exactly; out is
+    float32 either way.  Any other bank dtype is a TypeError."""
+    fn = _bank_entry(bank, "sample_segments")
+    assert bank.dim() == 2 and bank.is_contiguous()
     assert row_off.dtype == torch.int64 and frames.dtype == torch.int32 and vid.dtype == torch.int32 and starts.dtype == torch.int32
     assert all(t.is_cuda and t.is_contiguous() for t in (row_off, frames, vid, starts))
     B, D = vid.numel(), bank.shape[1]
@@ -672,8 +675,46 @@ def sample_segments(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Ten
     assert out.shape == shape and out.is_contiguous() and out.dtype == torch.float32 and out.device == bank.device
     h = _h(bank)
     from . import _lib                       # (the parameter L, named as in the C entry point, hides this module's alias)
-    _lib.check(_lib.lib().acx_sample_segments(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), vid.data_ptr(),
-                                              starts.data_ptr(), out.data_ptr(), B, N, L, stride, ncrops, D, _stream()), h)
+    _lib.check(getattr(_lib.lib(), fn)(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), vid.data_ptr(),
+                                       starts.data_ptr(), out.data_ptr(), B, N, L, stride, ncrops, D, _stream()), h)
+    return out
+
+
+def _bank_entry(bank: torch.Tensor, op: str) -> str:
+    """the C entry point of a gather for the bank's element type"""
+    if bank.dtype == torch.float32:
+        return "acx_" + op
+    if bank.dtype == torch.float16:
+        return "acx_" + op + "_f16"
+    raise TypeError(f"{op}: a feature bank is float32 or float16, got {bank.dtype}")
+
+
+def cast_rows_f16(src: torch.Tensor, overflow: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src f32 [rows, cols] (rows `src.stride(0)` floats apart) -> out f16 [rows, cols], rounded to nearest even with subnormal
+    halves: numpy's astype(float16) bit for bit.  Every finite value whose half is not finite (|x| >= 65520) is written as +-inf
+    and ADDED to `overflow` (int64 [1] on the device; the caller zeroes it and reads it when it next synchronises anyway).
+    One launch on the current stream, no host synchronisation."""
+    assert src.dim() == 2 and src.dtype == torch.float32 and src.is_cuda and (src.shape[0] == 0 or src.stride(1) == 1)
+    assert overflow.dtype == torch.int64 and overflow.numel() == 1 and overflow.device == src.device
+    rows, cols = src.shape
+    if out is None:
+        out = torch.empty(rows, cols, dtype=torch.float16, device=src.device)
+    assert out.shape == src.shape and out.dtype == torch.float16 and out.is_contiguous() and out.device == src.device
+    h = _h(src)
+    L.check(L.lib().acx_cast_rows_f16(h, src.data_ptr(), out.data_ptr(), rows, cols, src.stride(0) if rows else cols,
+                                      overflow.data_ptr(), _stream()), h)
+    return out
+
+
+def expand_rows_f16(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src f16 [..., D] contiguous -> out f32 of the same shape (exact): what the streamed test path runs on the halves it uploads"""
+    assert src.dtype == torch.float16 and src.is_cuda and src.is_contiguous() and src.dim() >= 1
+    if out is None:
+        out = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    assert out.shape == src.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == src.device
+    D = src.shape[-1]
+    h = _h(src)
+    L.check(L.lib().acx_expand_rows_f16(h, src.data_ptr(), out.data_ptr(), src.numel() // D if D else 0, D, _stream()), h)
     return out
 
 
@@ -686,8 +727,10 @@ def tile_videos(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Tensor,
     `sample_segments`, `vids` the videos' indices into them and `segment_sizes` their S_j (host ints: the caller knows the frame
     counts) -> out [sum_j ncrops * N * L * S_j, D], video after video, each crop-major, with
     out[out_off[j] + c * rows_j + r] = bank[row_off[vids[j]] + ((r * stride) mod frames[vids[j]]) * ncrops + c].
-    The group's small index tables are built once per group geometry and kept on the device; no host synchronisation."""
-    assert bank.dim() == 2 and bank.is_contiguous() and bank.dtype == torch.float32
+    The group's small index tables are built once per group geometry and kept on the device; no host synchronisation.
+    A float16 bank goes through acx_tile_videos_f16 (out stays float32); any other bank dtype is a TypeError."""
+    fn = _bank_entry(bank, "tile_videos")
+    assert bank.dim() == 2 and bank.is_contiguous()
     assert row_off.dtype == torch.int64 and frames.dtype == torch.int32 and row_off.numel() == frames.numel()
     assert all(t.is_cuda and t.is_contiguous() for t in (row_off, frames))
     vids, segs = [int(v) for v in vids], [int(s) for s in segment_sizes]
@@ -714,9 +757,9 @@ def tile_videos(bank: torch.Tensor, row_off: torch.Tensor, frames: torch.Tensor,
         tab = _TILE_TABLES[key] = (dev[:2 * V].view(torch.int64), dev[2 * V:3 * V], dev[3 * V:4 * V], dev[4 * V:])
     h = _h(bank)
     from . import _lib                       # (the parameter L hides this module's alias)
-    _lib.check(_lib.lib().acx_tile_videos(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), tab[1].data_ptr(), tab[0].data_ptr(),
-                                          tab[2].data_ptr(), tab[3].data_ptr(), out.data_ptr(), V, total, N, L, stride, ncrops, D,
-                                          _stream()), h)
+    _lib.check(getattr(_lib.lib(), fn)(h, bank.data_ptr(), row_off.data_ptr(), frames.data_ptr(), tab[1].data_ptr(), tab[0].data_ptr(),
+                                       tab[2].data_ptr(), tab[3].data_ptr(), out.data_ptr(), V, total, N, L, stride, ncrops, D,
+                                       _stream()), h)
     return out
 
 

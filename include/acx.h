@@ -1015,6 +1015,30 @@ int acx_tile_videos(acx_ctx* ctx, const float* bank, const int64_t* row_off, con
                     const int64_t* out_off, const int32_t* rows, const int32_t* blk, float* out, int32_t V, int64_t total_rows,
                     int32_t N, int32_t L, int32_t stride, int32_t ncrops, int32_t D, void* stream);
 
+/* Half-precision feature files: the same bank with float16 rows (IEEE binary16, numpy's '<f2').  acx_sample_segments_f16 and
+ * acx_tile_videos_f16 are the two gathers above on such a bank: the same tables, arguments, limits and formulas, `out` stays
+ * float32 (a half widens exactly).  A half row of D % 4 == 0 elements is 8-byte aligned only, so a lane loads 8 bytes and stores
+ * 16: D % 4 == 0, an 8-byte aligned bank and a 16-byte aligned out, else ACX_E_BADARG. */
+int acx_sample_segments_f16(acx_ctx* ctx, const void* bank, const int64_t* row_off, const int32_t* frames, const int32_t* vid,
+                            const int32_t* starts, float* out, int32_t B, int32_t N, int32_t L, int32_t stride, int32_t ncrops,
+                            int32_t D, void* stream);
+int acx_tile_videos_f16(acx_ctx* ctx, const void* bank, const int64_t* row_off, const int32_t* frames, const int32_t* vid,
+                        const int64_t* out_off, const int32_t* rows, const int32_t* blk, float* out, int32_t V, int64_t total_rows,
+                        int32_t N, int32_t L, int32_t stride, int32_t ncrops, int32_t D, void* stream);
+
+/* dst[r, c] = half(src[r * ld + c]) for r < rows, c < cols: float32 rows `ld` floats apart -> contiguous float16 rows, rounded to
+ * nearest even with subnormal halves (in integer arithmetic: numpy's astype(float16) bit for bit, NaN payloads included, under any
+ * denormal mode).  A finite input whose half is not finite (|x| >= 65520) is written as +-inf and counted: *overflow_count (DEVICE
+ * int64, the caller zeroes it) is increased by their number, one atomic add per workgroup that met any.  NaN and +-inf pass
+ * uncounted.  cols % 4 == 0, ld % 4 == 0, ld >= cols, a 16-byte aligned src and 8-byte aligned dst / overflow_count, else
+ * ACX_E_BADARG; rows == 0 is ACX_OK without a launch. */
+int acx_cast_rows_f16(acx_ctx* ctx, const float* src, void* dst, int64_t rows, int32_t cols, int64_t ld, int64_t* overflow_count,
+                      void* stream);
+
+/* dst[i] = float(src[i]) over rows * D contiguous float16 elements (exact): D % 4 == 0, an 8-byte aligned src and a 16-byte
+ * aligned dst, else ACX_E_BADARG; rows == 0 is ACX_OK without a launch. */
+int acx_expand_rows_f16(acx_ctx* ctx, const void* src, float* dst, int64_t rows, int32_t D, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Baseline JPEG frames (the reference decodes with Pillow: video_dataset.py:204 `Image.open(...).convert("RGB")`): Huffman decoding
  * on the host, everything after it on the device, bit for bit Pillow's RGB (libjpeg-turbo's defaults: the integer "islow" IDCT,

@@ -170,6 +170,8 @@ def main():
     ap.add_argument("--decode-threads", type=int, default=8)
     ap.add_argument("--kernel-only", action="store_true", help="time the crop kernel alone (no encoder is built)")
     ap.add_argument("--crop-size", type=int, default=224, help="--kernel-only: the crop size")
+    ap.add_argument("--dtype", default="float32", choices=("float32", "float16"),
+                    help="element type of the files written (legs b and c; not with --pack or --kernel-only)")
     ap.add_argument("--pack", action="store_true", help="pack off against pack on over 64 short clips (extract_pack_bench.jsonl)")
     ap.add_argument("--out", default=None, help="default: profiles/extract_bench.jsonl, with --pack profiles/extract_pack_bench.jsonl")
     args = ap.parse_args()
@@ -208,7 +210,7 @@ def main():
         nb = X.batch_frames(enc, args.ncrops)
         rows_total = args.frames * args.ncrops
         res.update({"arch": args.arch, "precision": args.precision, "frames": args.frames, "rows": rows_total, "crop": crop,
-                    "scale": scale, "rows_per_launch": nb * args.ncrops, "decode_threads": args.decode_threads})
+                    "scale": scale, "rows_per_launch": nb * args.ncrops, "decode_threads": args.decode_threads, "dtype": args.dtype})
         host = synthetic_frames(args.frames, H, W)
         # (a) the encoder alone: the launches extract_video makes (nb * ncrops rows each, the ragged last one included)
         x = torch.randn(nb * args.ncrops, 3, crop, crop, device=dev)
@@ -229,10 +231,11 @@ def main():
         try:
             # (b) pre-decoded frames in pinned memory
             pinned = torch.from_numpy(host).pin_memory()
-            X.extract_video(enc, pinned[:nb], os.path.join(tmp, "warm.npy"), args.ncrops, scale, overwrite=True)
+            X.extract_video(enc, pinned[:nb], os.path.join(tmp, "warm.npy"), args.ncrops, scale, overwrite=True, dtype=args.dtype)
             t0 = time.perf_counter()
-            X.extract_video(enc, pinned, os.path.join(tmp, "b.npy"), args.ncrops, scale, overwrite=True)
+            X.extract_video(enc, pinned, os.path.join(tmp, "b.npy"), args.ncrops, scale, overwrite=True, dtype=args.dtype)
             dt_b = time.perf_counter() - t0
+            res["b_file_bytes"] = os.path.getsize(os.path.join(tmp, "b.npy"))
             res["b_predecoded_rows_per_s"] = round(rows_total / dt_b, 1)
             res["b_over_a"] = round(dt_a / dt_b, 4)
             # (c) from JPEG folders
@@ -243,7 +246,7 @@ def main():
                 Image.fromarray(host[t]).save(os.path.join(vdir, X.TEMPLATE.format(t)), quality=90)
             t0 = time.perf_counter()
             counts = X.extract_dataset(enc, None, os.path.join(tmp, "frames"), os.path.join(tmp, "feats"), args.ncrops, scale,
-                                       decode_threads=args.decode_threads)
+                                       decode_threads=args.decode_threads, dtype=args.dtype)
             dt_c = time.perf_counter() - t0
             assert counts["rows"] == rows_total, counts
             res["c_jpeg_rows_per_s"] = round(rows_total / dt_c, 1)

@@ -7,7 +7,9 @@ Synthetic `.npy` files in a temporary directory (page cache, so the numbers are 
   2. steps/s of Trainer.fit on the UCF head fed (a) by AnomalyCLIPDataModule's resident loaders and (b) by a host loader --
      the files held in RAM, one numpy gather per video (feature_index) straight into pinned memory, `.to(device)` -- in the
      same run.  (b) is the best a user can write without the bank; the reference's per-frame Python loop is slower still.
-One JSON line.   python tools/bench_train_loader.py [--videos 256] [--frames 2000] [--batch 64] [--steps 40]"""
+--dtype float16 writes half-precision files: the bank holds halves and the gather widens them (part 2 then times the resident
+loaders only: the host loader of (b) gathers float32 rows).  tools/bench_feature_f16.py times both dtypes in one process.
+One JSON line.   python tools/bench_train_loader.py [--videos 256] [--frames 2000] [--batch 64] [--steps 40] [--dtype float16]"""
 import argparse, json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--steps", type=int, default=40, help="timed training steps per loader")
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--gather-reps", type=int, default=50)
+    ap.add_argument("--dtype", default="float32", choices=("float32", "float16"), help="element type of the feature files")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_train_loader.py measures on the GPU"
     import bench as B
@@ -73,7 +76,7 @@ def main():
         lists = {k: os.path.join(td, k + ".txt") for k in ("normal", "anomaly")}
         with open(lists["normal"], "w") as fn, open(lists["anomaly"], "w") as fa:
             for i, T in enumerate(lengths):
-                np.save(os.path.join(td, f"v{i}.npy"), (rng.standard_normal((T, D)) * 0.3).astype(np.float32))
+                np.save(os.path.join(td, f"v{i}.npy"), (rng.standard_normal((T, D)) * 0.3).astype(args.dtype))
                 (fn if i < V // 2 else fa).write(f"v{i} 0 {T - 1} {7 if i < V // 2 else i % 7}\n")
         hp = dict(frames_root=td, annotation_file_normal=lists["normal"], annotation_file_anomaly=lists["anomaly"],
                   annotation_file_test=lists["anomaly"], normal_id=7, num_classes=14, num_segments=N, seg_length=L, batch_size=args.batch,
@@ -92,7 +95,8 @@ def main():
         vid_d, starts_d = torch.from_numpy(vid).to(dev), torch.from_numpy(starts).to(dev)
         out = torch.empty(args.batch, 1, N * L, D, device=dev)
         dst = torch.empty_like(out)
-        moved = 2 * out.numel() * 4                                    # bytes read + bytes written, the same for both
+        moved = 2 * out.numel() * 4                                    # bytes read + bytes written by the copy ...
+        moved_g = out.numel() * (4 + bank.bank.element_size())         # ... and by the gather (a float16 bank: 2 read, 4 written)
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(2 * args.gather_reps)]
         for _ in range(5):
             ops.sample_segments(bank.bank, bank.row_off, bank.frames, vid_d, starts_d, N, L, 1, 1, out=out)
@@ -139,6 +143,15 @@ def main():
 
         mod = module()
         n_res, s_res = timed_fit(mod, dm)
+        if args.dtype != "float32":
+            print(json.dumps({
+                "row": "training batches from a resident feature set", "dtype": args.dtype, "videos": V, "frames_mean": args.frames,
+                "batch": args.batch, "bank": {"bytes": bank.nbytes, "load_s": round(load_s, 3), "GBps": round(bank.nbytes / load_s / 1e9, 2)},
+                "gather_one_batch": {"bytes_moved": moved_g, "ms_median": round(med(g_ms), 4), "ms_min": round(g_ms[0], 4),
+                                     "GBps": round(moved_g / med(g_ms) / 1e6, 1)},
+                "d2d_copy_same_rows_f32": {"ms_median": round(med(c_ms), 4), "ms_min": round(c_ms[0], 4)},
+                "fit_resident": {"steps": n_res, "steps_per_s": round(n_res / s_res, 2), "ms_per_step": round(s_res / n_res * 1e3, 3)}}))
+            return
         arrays = [np.load(r.path) for r in dm.normal + dm.anomaly]
         kw = dict(batch_size=half, num_segments=N, seg_length=L, stride=1)
         host_loaders = [HostTrainLoader(arrays, ResidentTrainLoader(bank, ids, **kw), N, L, 1) for ids in (range(V // 2), range(V // 2, V))]
