@@ -319,6 +319,9 @@ _SIGS = {
                                         C.POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "acx_clf_curve": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int64, c_void_p]),
+    "acx_curve_decimate_workspace_bytes": (c_int64, [c_int64]),
+    "acx_curve_decimate": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
     "acx_test_counts": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
     "acx_sample_segments": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),

@@ -21,8 +21,11 @@ read through the same attributes: `trainer.datamodule` (`.train_dataloader_test_
 `trainer.ckpt_path`.
 
 The metric numbers (AUROC, AP, mAUC, mAP, top-1/5, optimal threshold; :339-404, :501-626) come from libacx's sort /
-scan kernels (metrics.py) instead of torchmetrics; the four epilogue plots are not drawn; `data.visualize=True` renders the
-qualitative clips on the GPU (visualizer.py).
+scan kernels (metrics.py) instead of torchmetrics; `test_epoch_end` leaves the reference's four pictures (PR.png, ROC.png, F1.png,
+confusion_matrix.png; :621-691) beside metrics.json (figures.py: the two curves are reduced to the figure's pixel columns on the
+device and drawn with Pillow); `data.visualize=True` renders the qualitative clips on the GPU (visualizer.py).
+`hparams.figures` is not one of the reference's keys: `false` switches the four pictures off (no decimation launch, no file),
+a mapping may give `columns:` (the plot box's width in pixels, 1 ... 4096; default figures.DEFAULT_COLUMNS).
 The reference hard-codes /usr/src/app/logs/{train,eval}/runs/<run> (:409,:596); the same layout is used under
 `hparams.logs_root` (default "/usr/src/app/logs")."""
 from __future__ import annotations
@@ -440,12 +443,20 @@ class AnomalyCLIPModule(_Base):
         self.class_probs.append(probs)
         self.abnormal_scores.append(scores)
 
-    def _evaluate(self, scores, labels, probs, per_frame: bool):
+    def _figure_columns(self) -> Optional[int]:
+        """the plot box's width of the evaluation figures, None where `figures: false` switches them off"""
+        from . import figures
+        f = _get(self.hparams, "figures", True)
+        if f is None or f is False:
+            return None
+        return int((None if isinstance(f, bool) else _get(f, "columns", None)) or figures.DEFAULT_COLUMNS)
+
+    def _evaluate(self, scores, labels, probs, per_frame: bool, figure_columns: Optional[int] = None):
         from . import metrics as M
         dm = self._datamodule()
         C = int(_get(dm, "num_classes", None) or _get(self.hparams, "num_classes", probs.shape[1] + 1))
         normal_idx = int(_get(_get(dm, "hparams"), "normal_id", self.net.normal_id))
-        r = M.evaluate(scores, labels, probs, normal_idx, C, per_frame=per_frame)
+        r = M.evaluate(scores, labels, probs, normal_idx, C, per_frame=per_frame, figure_columns=figure_columns)
         self.last_metrics = r
         return r
 
@@ -508,14 +519,18 @@ class AnomalyCLIPModule(_Base):
     @parallel.rank_zero_only
     def test_epoch_end(self, outputs: List[Any]):
         outputs = [o for o in outputs if o is not None]
+        columns = self._figure_columns()
         r = self._evaluate(torch.cat([o["abnormal_scores"] for o in outputs]), torch.cat([o["labels"] for o in outputs]),
-                           torch.cat([o["class_probs"] for o in outputs]), True)
+                           torch.cat([o["class_probs"] for o in outputs]), True, figure_columns=columns)
         keys = ("auc_roc", "auc_pr", "mean_mc_auroc", "mean_mc_aupr", "mc_auroc", "mc_aupr", "top1_accuracy",
                 "top5_accuracy", "optimal_threshold")
         epoch = int(getattr(getattr(self, "trainer", None), "current_epoch", 0) or 0)
         metrics = {"epoch": epoch, **{k: r[k] for k in keys}}
         with open(self._run_dir("eval") / "metrics.json", "w") as fp:
             json.dump(metrics, fp, indent=4, sort_keys=True)
+        if columns is not None:                                                      # :621-691
+            from . import figures
+            figures.write_all(self._run_dir("eval"), r, _get(_get(self._datamodule(), "hparams"), "labels_file", None), columns)
         return metrics
 
     # ------------------------------------------------------------------ optimizer (:693-746)

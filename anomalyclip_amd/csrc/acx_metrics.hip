@@ -499,6 +499,196 @@ __global__ __launch_bounds__(256) void test_counts_kernel(const float* __restric
     if (lc[i]) atomicAdd(&counts[i], (unsigned long long)lc[i]);
 }
 
+// ------------------------------------------------------------------------------------------------ figure decimation
+// The curve's k points -> per pixel column of a figure the run's first / last / lowest / highest point (reference
+// anomaly_clip_module.py:523-530, 628-656 plots all k).  The column of a point is a cumulative count scaled by integer
+// division, so it never decreases with the index and a column's points are one contiguous index run.  The work is split
+// by POINTS: workgroup g walks a contiguous range of DC_CHUNK-point chunks, whatever columns they fall in.  A range is
+// summarised as a DecSpan: its first and its last column's records (the same record twice where it touches one column).
+// Joining two neighbouring ranges (dec_join) merges the records of a column both touch; a column that then lies strictly
+// inside the joined range can receive no further point and is written out at once by the ONE thread that joined -- every
+// join is made exactly once (thread fold, lane tree, waves 0..3, chunks in order, workgroups in order), so each column
+// has one writer and the result does not depend on timing.  The workgroups' spans are joined by a launch of their own.
+constexpr int DC_ITEMS = 8;
+constexpr int DC_WAVE_CHUNK = 64 * DC_ITEMS;              // 512 points per wave and step
+constexpr int DC_CHUNK = MT_THREADS * DC_ITEMS;           // 2048 points per workgroup and step
+constexpr int DC_MAX_GROUPS = 256;                        // workgroups of the partial launch == threads of the combine launch
+static_assert(DC_CHUNK == (MT_THREADS / 64) * DC_WAVE_CHUNK && MT_THREADS == 256 && DC_MAX_GROUPS % 64 == 0, "four waves per chunk");
+
+struct DecRec {          // one column's run so far; col < 0: none
+  int col;
+  int fi, li;            // first / last index
+  int ni, nt, nf;        // lowest y: index, tps, fps
+  int xi, xt, xf;        // highest y
+};
+struct DecSpan { DecRec h, t; };                          // first / last column of a range; h.col < 0: the range is empty
+
+__device__ __forceinline__ DecSpan dec_empty() {
+  DecSpan s = {};
+  s.h.col = -1; s.t.col = -1;
+  return s;
+}
+
+// y_a < y_b: ROC compares tps (tpr = tps / P), PR compares precision tps / (tps + fps) by cross-multiplication -- at most
+// (2^31 - 1) * (2^32 - 2) < 2^63
+__device__ __forceinline__ bool dec_less(int mode, int ta, int fa, int tb, int fb) {
+  if (mode == 0) return ta < tb;
+  return (long long)ta * ((long long)tb + fb) < (long long)tb * ((long long)ta + fa);
+}
+
+// a before b, same column; ties in y keep the lower index (a's)
+__device__ __forceinline__ DecRec dec_merge(const DecRec& a, const DecRec& b, int mode) {
+  DecRec r = a;
+  r.li = b.li;
+  if (dec_less(mode, b.nt, b.nf, a.nt, a.nf)) { r.ni = b.ni; r.nt = b.nt; r.nf = b.nf; }
+  if (dec_less(mode, a.xt, a.xf, b.xt, b.xf)) { r.xi = b.xi; r.xt = b.xt; r.xf = b.xf; }
+  return r;
+}
+
+// a finished column: its four (index, tps, fps) records
+__device__ __forceinline__ void dec_emit(const DecRec& r, const int* __restrict__ tps, const int* __restrict__ fps,
+                                         int* __restrict__ out) {
+  int* o = out + (size_t)r.col * 12;
+  o[0] = r.fi; o[1] = tps[r.fi]; o[2] = fps[r.fi];
+  o[3] = r.li; o[4] = tps[r.li]; o[5] = fps[r.li];
+  o[6] = r.ni; o[7] = r.nt; o[8] = r.nf;
+  o[9] = r.xi; o[10] = r.xt; o[11] = r.xf;
+}
+
+// a := a ++ b (b follows a in index order)
+__device__ __forceinline__ void dec_join(DecSpan& a, const DecSpan& b, int mode, const int* __restrict__ tps,
+                                         const int* __restrict__ fps, int* __restrict__ out) {
+  if (b.h.col < 0) return;
+  if (a.h.col < 0) { a = b; return; }
+  const bool a1 = a.h.col == a.t.col, b1 = b.h.col == b.t.col;
+  if (a.t.col == b.h.col) {
+    const DecRec m = dec_merge(a.t, b.h, mode);
+    if (!a1 && !b1) dec_emit(m, tps, fps, out);
+    if (a1) a.h = m;
+    a.t = b1 ? m : b.t;
+  } else {
+    if (!a1) dec_emit(a.t, tps, fps, out);
+    if (!b1) dec_emit(b.h, tps, fps, out);
+    a.t = b.t;
+  }
+}
+
+__device__ __forceinline__ DecRec dec_shfl_down(const DecRec& r, int off) {
+  DecRec o;
+  o.col = __shfl_down(r.col, off, 64);
+  o.fi = __shfl_down(r.fi, off, 64); o.li = __shfl_down(r.li, off, 64);
+  o.ni = __shfl_down(r.ni, off, 64); o.nt = __shfl_down(r.nt, off, 64); o.nf = __shfl_down(r.nf, off, 64);
+  o.xi = __shfl_down(r.xi, off, 64); o.xt = __shfl_down(r.xt, off, 64); o.xf = __shfl_down(r.xf, off, 64);
+  return o;
+}
+
+// lane 0 ends with the join of the wave's 64 spans in lane order; each pair is joined once, by the lower lane
+__device__ __forceinline__ void dec_wave_join(DecSpan& s, int lane, int mode, const int* __restrict__ tps,
+                                              const int* __restrict__ fps, int* __restrict__ out) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    DecSpan o;
+    o.h = dec_shfl_down(s.h, off);
+    o.t = dec_shfl_down(s.t, off);
+    if ((lane & (2 * off - 1)) == 0) dec_join(s, o, mode, tps, fps, out);
+  }
+}
+
+// the counts the device-side record holds -> k (clamped to the arrays' capacity; 0 where the curve is empty) and the x divisor
+__device__ __forceinline__ void dec_params(const CurveResultDev* __restrict__ res, long long capacity, int mode, int& k,
+                                           long long& den) {
+  long long kk = res->n_distinct;
+  kk = kk < 0 ? 0 : (kk > capacity ? capacity : kk);
+  den = mode == 0 ? res->n_neg : res->n_pos;
+  if (mode == 1 && den <= 0) kk = 0;                      // recall is NaN without positives: no curve
+  k = (int)kk;
+}
+
+__global__ __launch_bounds__(MT_THREADS) void curve_decimate_partial_kernel(const int* __restrict__ tps,
+                                                                             const int* __restrict__ fps, long long capacity,
+                                                                             const CurveResultDev* __restrict__ res, int mode,
+                                                                             int W, int vec, int* __restrict__ out,
+                                                                             DecSpan* __restrict__ ws) {
+  __shared__ DecSpan wsp[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int k;
+  long long den;
+  dec_params(res, capacity, mode, k, den);
+  const int nchunks = (k + DC_CHUNK - 1) / DC_CHUNK;
+  const int per = (nchunks + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min((int)blockIdx.x * per, nchunks), hi = min(lo + per, nchunks);
+  DecSpan carry = dec_empty();                            // thread 0: the workgroup's range so far
+  for (int c = lo; c < hi; ++c) {
+    const int i0 = c * DC_CHUNK + tid * DC_ITEMS;
+    int tp[DC_ITEMS], fp[DC_ITEMS];
+    if (vec && i0 + DC_ITEMS <= k) {
+      const int4 a = *(const int4*)(tps + i0), b = *(const int4*)(tps + i0 + 4);
+      const int4 e = *(const int4*)(fps + i0), f = *(const int4*)(fps + i0 + 4);
+      tp[0] = a.x; tp[1] = a.y; tp[2] = a.z; tp[3] = a.w; tp[4] = b.x; tp[5] = b.y; tp[6] = b.z; tp[7] = b.w;
+      fp[0] = e.x; fp[1] = e.y; fp[2] = e.z; fp[3] = e.w; fp[4] = f.x; fp[5] = f.y; fp[6] = f.z; fp[7] = f.w;
+    } else {
+#pragma unroll
+      for (int it = 0; it < DC_ITEMS; ++it) {
+        const bool valid = i0 + it < k;
+        tp[it] = valid ? tps[i0 + it] : 0;
+        fp[it] = valid ? fps[i0 + it] : 0;
+      }
+    }
+    DecSpan s = dec_empty();
+#pragma unroll
+    for (int it = 0; it < DC_ITEMS; ++it) {
+      if (i0 + it < k) {
+        const int x = mode == 0 ? fp[it] : tp[it];
+        int col = 0;
+        if (den > 0) {
+          const unsigned long long q = (unsigned long long)(unsigned)max(x, 0) * (unsigned)W / (unsigned long long)den;
+          col = q < (unsigned long long)W ? (int)q : W - 1;
+        }
+        DecSpan p = dec_empty();
+        p.h.col = col; p.h.fi = p.h.li = p.h.ni = p.h.xi = i0 + it;
+        p.h.nt = p.h.xt = tp[it]; p.h.nf = p.h.xf = fp[it];
+        p.t = p.h;
+        dec_join(s, p, mode, tps, fps, out);
+      }
+    }
+    dec_wave_join(s, lane, mode, tps, fps, out);
+    if (lane == 0) wsp[wave] = s;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 0; w < 4; ++w) {
+        const DecSpan o = wsp[w];
+        dec_join(carry, o, mode, tps, fps, out);
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) ws[blockIdx.x] = carry;
+}
+
+// one workgroup: the partial launch's `groups` (<= DC_MAX_GROUPS) spans joined in workgroup order, then what is left open
+__global__ __launch_bounds__(DC_MAX_GROUPS) void curve_decimate_combine_kernel(const int* __restrict__ tps,
+                                                                                const int* __restrict__ fps, int mode,
+                                                                                int* __restrict__ out,
+                                                                                const DecSpan* __restrict__ ws, int groups) {
+  __shared__ DecSpan wsp[DC_MAX_GROUPS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  DecSpan s = dec_empty();
+  if (tid < groups) s = ws[tid];
+  dec_wave_join(s, lane, mode, tps, fps, out);
+  if (lane == 0) wsp[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < DC_MAX_GROUPS / 64; ++w) {
+      const DecSpan o = wsp[w];
+      dec_join(s, o, mode, tps, fps, out);
+    }
+    if (s.h.col >= 0) {
+      dec_emit(s.h, tps, fps, out);
+      if (s.t.col != s.h.col) dec_emit(s.t, tps, fps, out);
+    }
+  }
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -620,6 +810,42 @@ extern "C" int acx_clf_curve(acx_ctx* ctx, const float* sorted_scores, const uin
   if (workspace_bytes < acx_clf_curve_workspace_bytes(n)) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_clf_curve: workspace too small");
   return acx_clf_curve_batched(ctx, sorted_scores, n, sorted_labels, n, n, 1, &cls, &negate, result, curve_tps, curve_fps,
                                curve_thresholds, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t acx_curve_decimate_workspace_bytes(int64_t capacity) {
+  if (capacity < 0) return -1;
+  const int64_t nb = (capacity + DC_CHUNK - 1) / DC_CHUNK;
+  return (nb < 1 ? 1 : (nb > DC_MAX_GROUPS ? DC_MAX_GROUPS : nb)) * (int64_t)sizeof(DecSpan);
+}
+
+// anomaly_clip_module.py:523-530, 628-656: the ROC / PR curve as a figure of `columns` pixel columns needs it.  3 launches: the
+// table's fill (index -1 everywhere), the partial launch over the points, the combine launch over the workgroups' spans.
+extern "C" int acx_curve_decimate(acx_ctx* ctx, const int32_t* curve_tps, const int32_t* curve_fps, int64_t capacity,
+                                  const acx_curve_result* result, int32_t mode, int32_t columns, int32_t* out, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  if (!ctx) return acx_fail(ctx, ACX_E_BADARG, "acx_curve_decimate: null context");
+  if (capacity < 0 || capacity >= (1ll << 31) - DC_CHUNK)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_curve_decimate: %scapacity=%ld out of range", "", (long)capacity);
+  if (mode != 0 && mode != 1) return acx_fail(ctx, ACX_E_BADARG, "acx_curve_decimate: %smode=%ld is neither 0 (ROC) nor 1 (PR)", "", (long)mode);
+  if (columns < 1 || columns > 4096) return acx_fail(ctx, ACX_E_BADARG, "acx_curve_decimate: %scolumns=%ld not in 1..4096", "", (long)columns);
+  if (!out || (capacity > 0 && (!curve_tps || !curve_fps || !result || !workspace)))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_curve_decimate: null buffer");
+  if (capacity > 0 && workspace_bytes < acx_curve_decimate_workspace_bytes(capacity))
+    return acx_fail(ctx, ACX_E_WORKSPACE, "acx_curve_decimate: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(out, 0xFF, (size_t)columns * 12 * sizeof(int32_t), st);      // (-1, -1, -1): an empty column
+  if (e != hipSuccess) return acx_fail(ctx, ACX_E_HIP, "acx_curve_decimate: memset: %s", hipGetErrorString(e));
+  if (capacity == 0) return ACX_OK;
+  const int groups = (int)(acx_curve_decimate_workspace_bytes(capacity) / (int64_t)sizeof(DecSpan));
+  const int vec = (((uintptr_t)curve_tps | (uintptr_t)curve_fps) & 15) == 0;
+  AcxProfScope prof(ctx, ACX_K_OTHER, st);
+  curve_decimate_partial_kernel<<<groups, MT_THREADS, 0, st>>>(curve_tps, curve_fps, (long long)capacity,
+                                                                (const CurveResultDev*)result, mode, columns, vec, out,
+                                                                (DecSpan*)workspace);
+  curve_decimate_combine_kernel<<<1, DC_MAX_GROUPS, 0, st>>>(curve_tps, curve_fps, mode, out, (const DecSpan*)workspace, groups);
+  e = hipGetLastError();
+  if (e != hipSuccess) return acx_fail(ctx, ACX_E_HIP, "acx_curve_decimate: %s", hipGetErrorString(e));
+  return ACX_OK;
 }
 
 extern "C" int acx_test_counts(acx_ctx* ctx, const float* scores, const float* probs, const int64_t* labels,

@@ -1463,6 +1463,31 @@ def clf_curve_batched(sorted_scores: torch.Tensor, sorted_labels: torch.Tensor, 
     return tps, fps, thr
 
 
+CURVE_DECIMATE_MAX_COLUMNS = 4096
+CURVE_DECIMATE_WAVE_CHUNK, CURVE_DECIMATE_CHUNK, CURVE_DECIMATE_MAX_GROUPS = 512, 2048, 256      # DC_* of csrc/acx_metrics.hip
+
+
+def curve_decimate(tps: torch.Tensor, fps: torch.Tensor, result: torch.Tensor, mode: int, columns: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The curve arrays of clf_curve (int32, capacity = numel; `result`: the uint8[56] device record with n_distinct / n_pos / n_neg
+    the curve launch wrote, never read on the host) -> int32 [columns, 4, 3] on the device: per pixel column of a `columns` wide
+    figure the (index, tps, fps) of the column's first, last, lowest and highest point; -1 in an empty column.  mode 0: ROC
+    (x = fps / N, y = tps / P), mode 1: PR (x = recall, y = precision).  include/acx.h acx_curve_decimate has the integer rules."""
+    assert tps.dtype == torch.int32 and fps.dtype == torch.int32 and tps.is_contiguous() and fps.is_contiguous()
+    assert tps.numel() == fps.numel() and result.dtype == torch.uint8 and result.numel() >= CURVE_RESULT_BYTES
+    cap, W = tps.numel(), int(columns)
+    dev = result.device
+    if out is None:
+        out = torch.empty(W, 4, 3, dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == W * 12
+    lib = L.lib()
+    ws = torch.empty(int(lib.acx_curve_decimate_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
+    h = _h(result)
+    L.check(lib.acx_curve_decimate(h, _ptr(tps) if cap else None, _ptr(fps) if cap else None, cap, result.data_ptr(), int(mode), W,
+                                   out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), h)
+    return out
+
+
 def eval_counts(scores, probs, labels, C: int, normal_idx: int, threshold_dev: torch.Tensor):
     """-> (y_pred int32 [n], counts int64 [3C + C*C + 30]); `threshold_dev` is a device f32 scalar view."""
     n = scores.numel()

@@ -924,6 +924,19 @@ int acx_clf_curve_batched(acx_ctx* ctx, const float* sorted_scores, int64_t scor
                           int64_t label_stride, int64_t n, int32_t batch, const int32_t* cls, const int32_t* negate,
                           acx_curve_result* results, int32_t* curve_tps, int32_t* curve_fps, float* curve_thresholds, void* workspace,
                           int64_t workspace_bytes, void* stream);
+/* anomaly_clip_module.py:523-530, 628-656 (the ROC and PR figures plot every point of the curve): the curve of acx_clf_curve
+ * (curve_tps / curve_fps, capacity entries, the first result->n_distinct valid) reduced to a figure's `columns` (1..4096) pixel
+ * columns, on the device.  `result` is the DEVICE record the curve launch wrote: k = n_distinct, P = n_pos and N = n_neg are read
+ * there, no host value depends on them.  Column of point j, by integer division: mode 0 (ROC) min(columns - 1, fps_j * columns / N),
+ * all 0 when N == 0; mode 1 (PR) min(columns - 1, tps_j * columns / P), and no point at all when P == 0 (recall is NaN).  Height:
+ * mode 0 tps_j; mode 1 the precision tps_j / (tps_j + fps_j), two of them compared as tps_a * (tps_b + fps_b) against
+ * tps_b * (tps_a + fps_a) in 64 bits.  out (device, int32 [columns][4][3]) receives per column the (index, tps, fps) of the run's
+ * first point, last point, lowest point and highest point (ties: the lowest index); an empty column holds (-1, -1, -1) four times.
+ * Exact integers, fixed-order joins, no atomics: run-to-run identical.  capacity == 0 and n_distinct == 0 are valid (all empty). */
+int64_t acx_curve_decimate_workspace_bytes(int64_t capacity);
+int acx_curve_decimate(acx_ctx* ctx, const int32_t* curve_tps, const int32_t* curve_fps, int64_t capacity,
+                       const acx_curve_result* result, int32_t mode, int32_t columns, int32_t* out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
 /* anomaly_clip_module.py:538-581, 621-626, 673: y_pred and the integer counters behind top-1 / top-5 accuracy,
  * the confusion matrix and F1@{0.1..1.0}.  probs [n, C-1] (class_probs without the normal column), labels int64,
  * threshold = DEVICE pointer to the optimal threshold (e.g. &result->opt_threshold).  counts (int64, device,
