@@ -324,6 +324,9 @@ _SIGS = {
                                      c_void_p]),
     "acx_test_counts": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "acx_score_events_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32]),
+    "acx_score_events": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_float, c_float,
+                                   c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "acx_sample_segments": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),
     "acx_tile_videos": (C.c_int, [c_void_p] * 9 + [c_int32, c_int64] + [c_int32] * 5 + [c_void_p]),
     "acx_sample_segments_f16": (C.c_int, [c_void_p] * 7 + [c_int32] * 6 + [c_void_p]),

@@ -13,6 +13,10 @@ hook signatures:
     test_epoch_end(self, outputs)           :501   @rank_zero_only, metrics.json under <logs>/eval/runs/<run>
     configure_optimizers(self)              :693   4 param groups, CosineAnnealingLR(T_max = trainer.max_epochs) successor
 
+Not in the reference (it only evaluates labeled videos): on_predict_start / predict_step / on_predict_epoch_end score the videos of
+`data.annotation_file_predict` without ground truth and leave their anomaly events (events.py) as events.json under
+<logs>/predict/runs/<run>; `hparams.predict` = {threshold, low, max_gap, min_len, max_events, save_scores}.
+
 `self.trainer` is whatever drives the module: pytorch_lightning's Trainer when that package is importable (the
 class then derives from LightningModule), otherwise anomalyclip_amd.trainer.Trainer -- a thin loop that calls
 exactly these hooks in Lightning's order (one process per GPU; gradients through parallel.GradBuckets).  Both are
@@ -481,12 +485,13 @@ class AnomalyCLIPModule(_Base):
         self.abnormal_scores.clear()
         return metrics
 
-    def _run_dir(self, kind: str) -> Path:
+    def _run_dir(self, kind: str, create: bool = True) -> Path:
         """<logs_root>/<kind>/runs/<name of the checkpoint's parent directory> (:407-409, :594-596)."""
         ckpt_path = Path(str(getattr(getattr(self, "trainer", None), "ckpt_path", None) or "ckpt/last.ckpt"))
         run = os.path.normpath(ckpt_path.parent).split(os.path.sep)[-1]
         d = Path(os.path.join(self._logs_root(), kind, "runs", str(run)))
-        d.mkdir(parents=True, exist_ok=True)
+        if create:
+            d.mkdir(parents=True, exist_ok=True)
         return d
 
     def on_test_start(self):
@@ -532,6 +537,83 @@ class AnomalyCLIPModule(_Base):
             from . import figures
             figures.write_all(self._run_dir("eval"), r, _get(_get(self._datamodule(), "hparams"), "labels_file", None), columns)
         return metrics
+
+    # ------------------------------------------------------------------ unlabeled videos (not in the reference: it only evaluates)
+    def _predict_params(self) -> dict:
+        """hparams.predict = {threshold, low, max_gap, min_len, max_events, save_scores}; defaults: low = threshold, no merging, no
+        length filter -- the events are then the maximal runs of the reference's y_pred != normal_idx (:537-547)"""
+        p = _get(self.hparams, "predict", None) or {}
+        thr = _get(p, "threshold", None)
+        low = _get(p, "low", None)
+        return {"threshold": None if thr is None else float(thr), "low": None if low is None else float(low),
+                "max_gap": int(_get(p, "max_gap", 0) or 0), "min_len": int(_get(p, "min_len", 1) or 1),
+                "max_events": int(_get(p, "max_events", 1024) or 1024), "save_scores": bool(_get(p, "save_scores", True))}
+
+    def on_predict_start(self):
+        """ncentroid as on_test_start; the threshold: hparams.predict.threshold, else the `optimal_threshold` the evaluation of
+        this run left in <logs_root>/eval/runs/<run>/metrics.json"""
+        self._load_or_compute_ncentroid(self._run_dir("train"))
+        self.visualizer = None                                                       # (clips shade the ground truth: test only)
+        p = self._predict_params()
+        if p["threshold"] is None:
+            f = self._run_dir("eval", create=False) / "metrics.json"
+            thr = None
+            if f.is_file():
+                with open(f) as fp:
+                    thr = json.load(fp).get("optimal_threshold")
+            if thr is None:
+                raise ValueError(f"predict: no threshold: {f} holds no `optimal_threshold` (run Trainer.test on this checkpoint "
+                                 f"first), and the module hyper-parameter `predict.threshold` is not set")
+            p["threshold"] = float(thr)
+        if p["low"] is None:
+            p["low"] = p["threshold"]
+        self.predict_params = p
+
+    @parallel.rank_zero_only
+    def predict_step_many(self, batches: List[Any], batch_idx: int = 0):
+        """the forward of test_step_many; the batches' label tensors only say how many frames are real"""
+        return [{"path": str(b[4][0]) if len(b) > 4 else str(batch_idx + i), "abnormal_scores": s, "class_probs": p}
+                for i, (b, (s, _, p)) in enumerate(zip(batches, self.score_videos(batches)))]
+
+    @parallel.rank_zero_only
+    def predict_step(self, batch: Any, batch_idx: int = 0):
+        return self.predict_step_many([batch], batch_idx)[0]
+
+    @parallel.rank_zero_only
+    def on_predict_epoch_end(self, outputs: List[Any]):
+        """every video's scores laid end to end on the device -> ONE events.find_events -> events.json (and scores/<video>.npy:
+        float32 [T, C], column 0 = p(A), columns 1 .. C - 1 = class_probs without the normal column) under
+        <logs_root>/predict/runs/<run>; -> the per-video dicts with `events` added"""
+        import numpy as np
+        from . import events as EV
+        from .figures import read_labels
+        outputs = [o for o in outputs if o is not None]
+        if not outputs:
+            return []
+        p = getattr(self, "predict_params", None)
+        if p is None:
+            raise RuntimeError("on_predict_epoch_end before on_predict_start: the threshold is not resolved")
+        dm = self._datamodule()
+        normal_idx = int(_get(_get(dm, "hparams"), "normal_id", self.net.normal_id))
+        scores = torch.cat([o["abnormal_scores"].reshape(-1) for o in outputs]).float().contiguous()
+        probs = torch.cat([o["class_probs"] for o in outputs]).float().contiguous()
+        lengths = [int(o["abnormal_scores"].numel()) for o in outputs]
+        row_off = torch.tensor([0] + lengths, dtype=torch.int64).cumsum(0)
+        found = EV.find_events(scores, probs, row_off, normal_idx, p["threshold"], p["low"], p["max_gap"], p["min_len"],
+                               p["max_events"])
+        out = self._run_dir("predict")
+        paths = [o["path"] for o in outputs]
+        echo = {**p, "normal_idx": normal_idx}
+        EV.write_events(out / "events.json", paths, found, echo, read_labels(_get(_get(dm, "hparams"), "labels_file", None)))
+        if p["save_scores"]:
+            (out / "scores").mkdir(exist_ok=True)
+            table = torch.cat([scores[:, None], probs], 1).cpu().numpy()             # one copy for all videos
+            seen: dict = {}
+            for o, a, b in zip(outputs, row_off[:-1].tolist(), row_off[1:].tolist()):
+                stem = Path(o["path"]).stem
+                k = seen[stem] = seen.get(stem, -1) + 1
+                np.save(out / "scores" / (stem if k == 0 else f"{stem}_{k}"), table[a:b])
+        return [{**o, "events": ev} for o, ev in zip(outputs, found)]
 
     # ------------------------------------------------------------------ optimizer (:693-746)
     def configure_optimizers(self):

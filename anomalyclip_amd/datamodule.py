@@ -9,7 +9,10 @@ stream the files through `FeatureStream` and add the per-frame labels of the tem
 CLIP image encoder into such banks (`FeatureBank.from_frames`; the reference's frame transform is deterministic, so its per-step
 encoding gives the same rows) and every loader draws from a bank: `ResidentTrainLoader` as above, `ResidentTestLoader` for the
 test-mode tiles.  No feature file is written.  `decode="gpu"` (a keyword beside `encoder=`, not one of the reference's keys) has the
-frames' baseline JPEG files reconstructed on the device (anomalyclip_amd/jpeg.py) instead of decoded by Pillow, `decode="gpu_entropy"` their Huffman decoding too: the same banks."""
+frames' baseline JPEG files reconstructed on the device (anomalyclip_amd/jpeg.py) instead of decoded by Pillow, `decode="gpu_entropy"` their Huffman decoding too: the same banks.
+
+`annotation_file_predict` (optional, not one of the reference's keys) lists videos WITHOUT ground truth, rows `path start_frame
+end_frame [label]`; `predict_dataloader()` yields the test-mode tuples for them in both modes (Trainer.predict)."""
 from __future__ import annotations
 
 import os
@@ -26,7 +29,7 @@ from .feature_stream import FeatureStream
 HPARAM_KEYS = ("frames_root", "annotation_file_normal", "annotation_file_anomaly", "annotation_file_test",
                "annotation_file_temporal_test", "labels_file", "normal_id", "num_classes", "num_segments", "seg_length", "ncrops",
                "stride", "batch_size", "batch_size_test", "load_from_features", "visualize", "image_tmpl")
-_DEFAULTS = dict(annotation_file_temporal_test=None, labels_file=None, num_segments=32, seg_length=16, ncrops=1, stride=1,
+_DEFAULTS = dict(annotation_file_temporal_test=None, annotation_file_predict=None, labels_file=None, num_segments=32, seg_length=16, ncrops=1, stride=1,
                  batch_size=64, batch_size_test=1, load_from_features=True, visualize=False, image_tmpl="{:06d}.jpg")
 
 
@@ -48,6 +51,21 @@ class VideoRecord:
 def read_annotation_file(path: str, root: str) -> List[VideoRecord]:
     with open(path) as fh:
         return [VideoRecord(line.strip().split(), root, f"{path}:{i + 1}") for i, line in enumerate(fh) if line.strip()]
+
+
+def read_predict_file(path: str, root: str, normal_id: int) -> List[VideoRecord]:
+    """the list of unlabeled videos (`annotation_file_predict`): rows `path start_frame end_frame [label]`; the label column is
+    optional and ignored (a row of one of the labeled lists can be used as it is): every record carries `normal_id`"""
+    out = []
+    with open(path) as fh:
+        for i, line in enumerate(fh):
+            row = line.strip().split()
+            if not row:
+                continue
+            if len(row) not in (3, 4):
+                raise ValueError(f"{path}:{i + 1}: expected `path start_frame end_frame [label]`, got {' '.join(row)!r}")
+            out.append(VideoRecord(row[:3] + [str(int(normal_id))], root, f"{path}:{i + 1}"))
+    return out
 
 
 def read_temporal_annotations(path: Optional[str]) -> Dict[str, np.ndarray]:
@@ -156,6 +174,8 @@ class AnomalyCLIPDataModule:
         self._train_loaders = None
         self._test_bank: Optional[FeatureBank] = None             # frames mode: the test list's bank ...
         self._normal_bank: Optional[FeatureBank] = None           # ... and the normal list's, when no fit bank holds it
+        self.predict: List[VideoRecord] = []                      # `annotation_file_predict`: videos without ground truth ...
+        self._predict_bank: Optional[FeatureBank] = None          # ... and, frames mode, their bank
 
     @property
     def yields_features(self) -> bool:
@@ -224,6 +244,21 @@ class AnomalyCLIPDataModule:
 
     def test_dataloader(self):
         return self.val_dataloader()
+
+    def predict_dataloader(self):
+        """the test-mode 5-tuples of the videos of `annotation_file_predict`, which need no annotation: the label tensor is
+        `normal_id` repeated T times and only its length means anything"""
+        hp = self.hparams
+        if not hp.get("annotation_file_predict"):
+            raise ValueError("AnomalyCLIPDataModule.predict_dataloader: the hyper-parameter `annotation_file_predict` (rows `path "
+                             "start_frame end_frame [label]`) is not set")
+        if not self.predict:
+            self.predict = read_predict_file(hp.annotation_file_predict, hp.frames_root, int(hp.normal_id))
+        if self.encoder is not None:
+            if self._predict_bank is None:
+                self._predict_bank = self._frames_bank(self.predict)
+            return ResidentTestLoader(self._predict_bank, self.predict, None, hp)
+        return StreamedTestLoader(self.predict, None, hp, self.device)
 
     def train_dataloader_test_mode(self):
         self._read_lists()

@@ -1500,6 +1500,34 @@ def eval_counts(scores, probs, labels, C: int, normal_idx: int, threshold_dev: t
     return y, counts
 
 
+SCORE_EVENTS_CHUNK = 1024                        # EV_CHUNK of csrc/acx_events.hip: frames per workgroup pass
+SCORE_EVENTS_MIN_C1, SCORE_EVENTS_MAX_C1 = 5, 63
+
+
+def score_events(scores: torch.Tensor, probs: torch.Tensor, row_off: torch.Tensor, normal_idx: int, hi: float, lo: float,
+                 max_gap: int, min_len: int, max_events: int):
+    """scores f32 [n], probs f32 [n, C1], row_off int64 [V + 1] (video v = rows row_off[v] .. row_off[v + 1] - 1), all on the device
+    -> (count int32 [V], events int32 [V, E, 6] = start, end, class, votes, hot_frames, peak_frame, stats f64 [V, E, 2] = peak, mean)
+    on the device; include/acx.h acx_score_events has the rules.  count[v] = -1: row_off is not monotone at video v."""
+    n, V, E = scores.numel(), row_off.numel() - 1, int(max_events)
+    assert scores.dtype == torch.float32 and probs.dtype == torch.float32 and row_off.dtype == torch.int64
+    assert scores.is_contiguous() and probs.is_contiguous() and row_off.is_contiguous() and V >= 0
+    assert probs.dim() == 2 and probs.shape[0] == n and probs.device == scores.device and row_off.device == scores.device
+    dev = scores.device
+    lib = L.lib()
+    h = _h(row_off)
+    nb = int(lib.acx_score_events_workspace_bytes(n, V, E))
+    ws = torch.empty(max(nb, 0), dtype=torch.uint8, device=dev)
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    events = torch.empty(V, max(E, 0), 6, dtype=torch.int32, device=dev)
+    stats = torch.empty(V, max(E, 0), 2, dtype=torch.float64, device=dev)
+    L.check(lib.acx_score_events(h, _ptr(scores) if n else None, _ptr(probs) if n else None, row_off.data_ptr(), n, V,
+                                 probs.shape[1], int(normal_idx), float(hi), float(lo), int(max_gap), int(min_len), E,
+                                 _ptr(count) if V else None, _ptr(events) if V else None, _ptr(stats) if V else None,
+                                 _ptr(ws) if nb > 0 else None, ws.numel(), _stream()), h)
+    return count, events, stats
+
+
 # ---- the CLIP ResNet encoders' own kernels (include/acx.h acx_resnet_*; the products are acx_gemm with ACX_ACT_RELU / RESRELU)
 def resnet_stem_im2col(frames: torch.Tensor) -> torch.Tensor:
     """frames [F,3,R,R] f32 -> [F * (R/2)^2, 32]: the stem's 3x3 stride-2 pad-1 columns (k = c * 9 + ky * 3 + kx, 27..31 zero)."""

@@ -214,31 +214,26 @@ class Trainer:
                 self.save_checkpoint(model, self.ckpt_path)
         return self.callback_metrics
 
-    def test(self, model, datamodule=None, ckpt_path: Optional[str] = None):
-        self._attach(model, datamodule, "test")
-        dev = model.device
-        if ckpt_path:
-            checkpoint.load_into(model.net, ckpt_path)
-            self.ckpt_path = ckpt_path
-        model.net.eval()
-        model.on_test_start()
-        # the reference scores one video per step (batch_size_test: 1); tiles of different videos are independent in
-        # evaluation, so `eval_batch_videos` consecutive test batches go through ONE forward (test_step_many) -- bounded by
-        # `eval_batch_tiles` 512-frame tiles so that a run of long videos does not blow up the activation memory
+    def _grouped_steps(self, model, loader, dev, step: str, many_step: str):
+        """The per-video outputs of `loader` (test-mode batches, one video each) through the module's `step` / `many_step` hooks.
+        The reference scores one video per step (batch_size_test: 1); tiles of different videos are independent in evaluation, so
+        `eval_batch_videos` consecutive batches go through ONE forward (`many_step`) -- bounded by `eval_batch_tiles` 512-frame
+        tiles so that a run of long videos does not blow up the activation memory."""
         outputs, group, tiles = [], [], 0
         kmax, tmax = int(getattr(self, "eval_batch_videos", 8)), int(getattr(self, "eval_batch_tiles", 96))
-        many = getattr(model, "test_step_many", None) if kmax > 1 else None
+        many = getattr(model, many_step, None) if kmax > 1 else None
+        one = getattr(model, step)
 
         def flush():
             if group:
                 res = many([_to_device(b, dev) for b in group], len(outputs))
                 outputs.extend(res if res is not None else [None] * len(group))
                 group.clear()
-        for i, batch in enumerate(self.datamodule.test_dataloader()):
+        for i, batch in enumerate(loader):
             if many is None or not isinstance(batch, (tuple, list)) or len(batch) < 4:
                 flush()
                 tiles = 0
-                outputs.append(model.test_step(_to_device(batch, dev), i))
+                outputs.append(one(_to_device(batch, dev), i))
                 continue
             t = int(batch[3])
             if group and (len(group) >= kmax or tiles + t > tmax):
@@ -247,5 +242,31 @@ class Trainer:
             group.append(batch)
             tiles += t
         flush()
+        return outputs
+
+    def test(self, model, datamodule=None, ckpt_path: Optional[str] = None):
+        self._attach(model, datamodule, "test")
+        dev = model.device
+        if ckpt_path:
+            checkpoint.load_into(model.net, ckpt_path)
+            self.ckpt_path = ckpt_path
+        model.net.eval()
+        model.on_test_start()
+        outputs = self._grouped_steps(model, self.datamodule.test_dataloader(), dev, "test_step", "test_step_many")
         m = model.test_epoch_end(outputs)
         return [m] if m is not None else []
+
+    def predict(self, model, datamodule=None, ckpt_path: Optional[str] = None):
+        """Scores the videos of `datamodule.predict_dataloader()` -- no ground truth is read -- and finds their anomaly events on
+        the device (AnomalyCLIPModule.on_predict_epoch_end: events.json, scores/<video>.npy).  Consecutive videos are grouped
+        exactly as in test().  -> one dict per video {path, abnormal_scores, class_probs, events}, on rank 0; [] elsewhere."""
+        self._attach(model, datamodule, "predict")
+        dev = model.device
+        if ckpt_path:
+            checkpoint.load_into(model.net, ckpt_path)
+            self.ckpt_path = ckpt_path
+        model.net.eval()
+        model.on_predict_start()
+        outputs = self._grouped_steps(model, self.datamodule.predict_dataloader(), dev, "predict_step", "predict_step_many")
+        res = model.on_predict_epoch_end(outputs)
+        return res if res is not None else []

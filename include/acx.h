@@ -945,6 +945,36 @@ int acx_curve_decimate(acx_ctx* ctx, const int32_t* curve_tps, const int32_t* cu
 int acx_test_counts(acx_ctx* ctx, const float* scores, const float* probs, const int64_t* labels, int64_t n,
                     int32_t C, int32_t normal_idx, const float* threshold, int32_t* y_pred, int64_t* counts,
                     void* stream);
+/* Anomaly events of unlabeled videos, on the device: only the event tables need to reach the host.  scores f32 [n]; probs f32
+ * [n, C1] (class_probs without the normal column, as acx_test_counts takes them: 5 <= C1 <= 63, 0 <= normal_idx <= C1); row_off
+ * int64 [videos + 1]: video v owns rows row_off[v] .. row_off[v + 1] - 1 (empty videos are allowed).  All three are DEVICE arrays.
+ * Rules (exact: tests/events_ref.py restates them entry for entry):
+ *   hot / warm  frame t is hot when !(s_t < hi), warm when !(s_t < lo) -- the reference's comparison (anomaly_clip_module.py:538),
+ *               so a NaN score is hot.
+ *   raw event   a maximal run of warm frames of one video that holds at least one hot frame (lo == hi: the maximal runs of the
+ *               reference's y_pred != normal_idx).
+ *   merging     consecutive raw events of a video are chained into one event while the gap between them is at most max_gap
+ *               frames; the gap frames belong to the event; nothing merges across a video boundary.
+ *   length      an event is kept when end - start + 1 >= min_len (start, end inclusive, relative to the video's first row);
+ *               merging comes first.
+ *   per event   over ALL its frames: peak = the largest non-NaN score (NaN when there is none), peak_frame = the first frame
+ *               that attains it (start when every score is NaN), mean = f64 sum of the non-NaN scores / their number (NaN when
+ *               there is none), hot_frames = the number of hot frames.
+ *   class       every hot frame votes for argmax_k probs[t, k] (strict >, from -inf: NaN never wins, ties and an all-NaN row go to
+ *               the lowest k); the event's class is the k with the most votes (ties: the lowest k), reported in the full label
+ *               space (k + 1 when k >= normal_idx); votes = the winner's count.
+ * Outputs (device): count int32 [videos] = ALL kept events of the video, also beyond max_events, or -1 for a video whose range
+ * is not 0 <= row_off[v] <= row_off[v + 1] <= n (its rows are not read); events int32 [videos][max_events][6] = start, end,
+ * class, votes, hot_frames, peak_frame; stats f64 [videos][max_events][2] = peak, mean.  Events in ascending start; the first
+ * min(count, max_events) slots are filled, every other slot holds -1 / NaN.
+ * Refused before any launch (ACX_E_BADARG): n or videos outside 0 .. 2^31 - 1, C1 / normal_idx out of domain, lo > hi or a NaN
+ * threshold, max_gap < 0, min_len < 1, max_events < 1, videos * max_events >= 2^31.  Two launches, no float atomics, fixed-order
+ * joins: run-to-run identical.  acx_score_events_workspace_bytes is host arithmetic (-1 for sizes the launch refuses); the present
+ * decomposition keeps its carry in registers and needs 0 bytes, workspace may then be NULL. */
+int64_t acx_score_events_workspace_bytes(int64_t n, int64_t videos, int32_t max_events);
+int acx_score_events(acx_ctx* ctx, const float* scores, const float* probs, const int64_t* row_off, int64_t n, int64_t videos,
+                     int32_t C1, int32_t normal_idx, float hi, float lo, int32_t max_gap, int32_t min_len, int32_t max_events,
+                     int32_t* count, int32_t* events, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* In-library launch timer used by bench.py's roofline leg: when enabled, every kernel launch is
  * bracketed by HIP events on the caller's stream.  kinds: 0 GEMM, 1 attention, 2 norm rows, 3 other.
