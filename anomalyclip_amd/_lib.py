@@ -32,6 +32,11 @@ GEMM_ROUTE_W8_CONV, GEMM_ROUTE_RING, GEMM_ROUTE_P8, GEMM_ROUTE_DMA_CONV, GEMM_RO
 GEMM_REDUCE_NONE, GEMM_REDUCE_LAUNCH, GEMM_REDUCE_COUNTERS = 0, 1, 2
 # acx_gemm_tn_route / acx_gemm_tn_x6_route (include/acx.h ACX_TN_ROUTE_*); reduce: 0 none, 1 the reduce launch, 2 images for the caller
 TN_ROUTE_NONE, TN_ROUTE_W8, TN_ROUTE_P256, TN_ROUTE_X6_256x256, TN_ROUTE_X6_256x128, TN_ROUTE_X6_128x256 = 0, 1, 2, 3, 4, 5
+# acx_transformer_plan: a layer's record (include/acx.h ACX_TF_LN_* / ACX_TF_GEMM_* / ACX_TF_BUF_* / ACX_TF_ATT_*)
+TF_LN_ROWS, TF_LN_PLANES, TF_LN_RIDDEN, TF_LN_CLS = 0, 1, 2, 3
+TF_GEMM_ROWS, TF_GEMM_X6 = 0, 1
+TF_BUF_NONE, TF_BUF_SPLITK, TF_BUF_H, TF_BUF_QKV, TF_BUF_MLP = 0, 1, 2, 3, 4
+TF_ATT_F32, TF_ATT_BF16, TF_ATT_X3_PANEL, TF_ATT_P3N, TF_ATT_P3F, TF_ATT_CLS, TF_ATT_CLS_FOLD = 0, 1, 2, 3, 4, 5, 6
 
 
 class GemmDesc(C.Structure):
@@ -67,7 +72,17 @@ class GemmTnRoute(C.Structure):   # acx_gemm_tn_route_t: the kernel acx_gemm_tn*
     _fields_ = [(n, c_int32) for n in ("kernel", "splits", "rows_per_split", "tiles", "reduce", "clears_zero_page")]
 
 
-class LnJob(C.Structure):     # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
+class TfProduct(C.Structure):     # acx_tf_product_t: one of a layer's four products as the transformer driver runs it
+    _fields_ = [(n, c_int32) for n in ("kernel", "c_dtype", "scratch", "ln_job")]
+
+
+class TfLayerPlan(C.Structure):   # acx_tf_layer_plan_t: what the transformer driver launches for one layer
+    _fields_ = [(n, c_int32) for n in ("ln1", "ln1_dtype", "ln2", "ln2_dtype")] + \
+               [(n, TfProduct) for n in ("in_proj", "out_proj", "fc", "proj")] + \
+               [(n, c_int32) for n in ("att", "att_products", "split_att", "split_mlp", "pruned", "reserved")]
+
+
+class LnJob(C.Structure):    # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
     _fields_ = [("w", c_void_p), ("b", c_void_p), ("y", c_void_p), ("y_dtype", c_int32), ("eps", c_float), ("mode", c_int32)]
 
 
@@ -204,6 +219,7 @@ _SIGS = {
     "acx_transformer_workspace_bytes_prec": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_transformer_forward": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, C.POINTER(BlockWeights), c_void_p, c_size_t, c_void_p]),
+    "acx_transformer_plan": (C.c_int, [c_void_p] + [c_int32] * 10 + [C.POINTER(TfLayerPlan)]),
     "acx_text_directions": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_selector_project": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                        c_void_p]),

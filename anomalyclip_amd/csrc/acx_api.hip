@@ -16,6 +16,21 @@
 
 thread_local char acx_tls_err[512] = {0};
 
+namespace {
+// The options the transformer driver's plan reads.  Filled in one place (tf_opts); acx_create takes its defaults from kCreateOpts.
+struct TfOpts {
+  int x6_min_tiles;                              // ACX_OPT_X6_MIN_TILES
+  bool attn_f32in, cls_fold;                     // ACX_OPT_ATTN_F32IN, ACX_OPT_CLS_FOLD
+};
+constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0};
+constexpr TfOpts kNoCtxOpts = {512, false, false};   // a driver called with ctx == NULL
+// query: acx_transformer_plan, which answers for a context as acx_create leaves it when it has none (like the other route queries)
+inline TfOpts tf_opts(const acx_ctx* ctx, bool query) {
+  if (!ctx) return query ? kCreateOpts : kNoCtxOpts;
+  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0};
+}
+}  // namespace
+
 extern "C" int acx_attention_cls(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch,
                                  int32_t L, int32_t heads, void* stream);
 
@@ -51,10 +66,10 @@ extern "C" int acx_create(acx_ctx** out, int device) {
   c->opt_x6_tail = 0;
   c->opt_x6_strip = 1;
   c->opt_ln_rider = 1;
-  c->opt_attn_f32in = ACX_ATTN_F32IN_DEFAULT;
-  c->opt_cls_fold = ACX_CLS_FOLD_DEFAULT;
+  c->opt_attn_f32in = kCreateOpts.attn_f32in;
+  c->opt_cls_fold = kCreateOpts.cls_fold;
   c->comm = nullptr; c->comm_rank = 0; c->comm_world = 0;
-  c->opt_x6_min_tiles = 18;
+  c->opt_x6_min_tiles = kCreateOpts.x6_min_tiles;
   c->err[0] = 0;
   c->prof_on = false;
   c->prof_gemm_only = false;
@@ -199,6 +214,8 @@ struct XMode {
   bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
 };
 static inline XMode xmode_of(int prec) { return {(prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3) ? 3 : 6, prec == ACX_PREC_F16X3}; }
+// what LayerNorm / acx_vit_patches write for the plane products of a mode
+static inline int plane_dtype_of(int prec) { return prec == ACX_PREC_F16X3 ? ACX_F16X2P : prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P; }
 
 TfWs carve_tf(char* base, int64_t rows, int W, int prec = ACX_PREC_F32) {
   TfWs w;
@@ -221,244 +238,393 @@ TfWs carve_tf(char* base, int64_t rows, int W, int prec = ACX_PREC_F32) {
   return w;
 }
 
+// The pruned last layer's scratch (acx_vit_encode's cls_ws): everything of that layer that exists for the CLS rows only.
+struct ClsWs {
+  float *xc, *attc, *x1;   // [batch, W] each: the final CLS residual stream, the attention output, the stream after out_proj
+  char *hc, *mc;           // [batch, W] LayerNorm output, [batch, 4W] MLP hidden (f32 or bf16; the fold's Q sits in mc before c_fc)
+};
+inline size_t cls_ws_bytes(int batch, int W) { return (size_t)8 * batch * W * 4; }   // xc, attc, x1, hc: W floats a row; mc: 4W
+ClsWs carve_cls(float* base, int batch, int W) {
+  const size_t n = (size_t)batch * W;
+  return {base, base + n, base + 2 * n, (char*)(base + 3 * n), (char*)(base + 4 * n)};
+}
+
 // ACX_PREC_F32X6: the large GEMMs of the ViT as f32-accurate products on the bf16 matrix cores (acx_gemm_desc.pairs = 6): the
 // f32 input is split into three bf16 planes (acx_split_bf16x3), the weights come as three planes from the caller.  A problem
-// the persistent 256x256 kernel does not take (few rows) stays on the f32 MFMA kernels.
-bool x6_takes(acx_ctx* ctx, const TfWs& ws, int64_t M, int N, int K, int lda) {
-  if (!ws.hp || !ACX_DBG_SWITCH("X6", true)) return false;
+// the persistent 256x256 kernel does not take (few rows) stays on the f32 MFMA kernels.  planes_ws: the workspace has the planes.
+bool x6_takes(const TfOpts& o, bool planes_ws, int64_t M, int N, int K, int lda) {
+  if (!planes_ws || !ACX_DBG_SWITCH("X6", true)) return false;
   const int64_t rtiles = ((M + 255) / 256) * ((N + 255) / 256);
-  const int x6_min = ctx ? ctx->opt_x6_min_tiles : 512;
-  return rtiles >= x6_min && K % 256 == 0 && N % 8 == 0 && (size_t)M * lda * 2 < ((size_t)1 << 32) &&
+  return rtiles >= o.x6_min_tiles && K % 256 == 0 && N % 8 == 0 && (size_t)M * lda * 2 < ((size_t)1 << 32) &&
          (size_t)N * K * 2 < ((size_t)1 << 32);
+}
+
+// One y = act(A W^T + bias) [+ residual] of the drivers.
+struct Product {
+  int kernel;                  // ACX_TF_GEMM_ROWS: A is rows of a_dtype, acx_gemm picks the kernel; ACX_TF_GEMM_X6: A and Wb are K-panel planes
+  const void* A; int a_dtype, lda;
+  const float* Wf;             // f32 weight [N, K]
+  const void* Wb;              // its bf16 copy (ACX_PREC_BF16) or its planes (plane modes)
+  int64_t w_plane_bytes;       // 0: N * K * 2 (a row range of a taller weight: that weight's)
+  int ldw, M, N, K;
+  const float* bias; int act;
+  const float* residual; int ldr;   // ldr 0: ldc
+  void* C; int c_dtype, ldc;
+  void* scratch; size_t scratch_bytes;   // for a K split, free while the product runs
+  const acx_ln_job* ln;        // plane kernel: the LayerNorm of the output rows follows (acx_gemm_ln: part of it rides in the last round)
+};
+
+struct TfMode {
+  int prec;                    // acx_gemm_desc.prec of the row products and everything small (plane modes: f32)
+  int hdt, pdt;                // what LayerNorm writes: rows of hdt (c_fc's hidden too), planes of pdt
+  XMode xm;
+};
+
+int missing_weights(acx_ctx* ctx, bool planes, int prec) {
+  if (planes) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
+  return acx_fail(ctx, ACX_E_BADARG, "driver: missing %s weight copy for the requested precision", prec == ACX_PREC_BF16 ? "bf16" : "f32");
+}
+
+acx_gemm_desc desc_of(const Product& p) {        // all of a descriptor but the weight, the arithmetic and the scratch
+  acx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = p.A; d.C = p.C;
+  d.M = p.M; d.N = p.N; d.K = p.K; d.lda = p.lda; d.ldw = p.ldw; d.ldc = p.ldc;
+  d.a_dtype = p.a_dtype; d.c_dtype = p.c_dtype;
+  d.bias = p.bias; d.act = p.act; d.residual = p.residual; d.ldr = p.ldr ? p.ldr : p.ldc;
+  return d;
 }
 
 // Both operands' planes are in K-PANEL layout (ACX_BF16X3P: the driver's producers -- LayerNorm, the attention, c_fc's epilogue,
 // acx_split_bf16x3_panel -- write it, the caller's weight planes come in it): a 256-row x 32-column unit of the plane-reuse
 // kernel is then ONE contiguous 16 KB block (+5-6 % on the ViT products against row-major planes, profiles/r05_gemm_x6_notes.txt).
-int linear_x6(acx_ctx* ctx, XMode xm, const void* A3, int lda, int64_t a_rows, const void* W3, int64_t w_plane_bytes, int ldw, void* C,
-              int ldc, int M, int N, int K, const float* bias, int act, const float* residual, hipStream_t s, int ldr = 0,
-              int c_dtype = ACX_F32, void* tail_ws = nullptr, size_t tail_bytes = 0, const acx_ln_job* ln = nullptr) {
-  if (!W3) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
-  acx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = A3; d.W = W3; d.C = C;
-  d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldw = ldw; d.ldc = ldc;
-  d.a_dtype = xm.f16 ? ACX_F16 : ACX_BF16; d.c_dtype = (xm.f16 && c_dtype == ACX_BF16X3P) ? ACX_F16X2P : c_dtype; d.prec = ACX_PREC_BF16;
+int run_x6(acx_ctx* ctx, XMode xm, const Product& p, hipStream_t s) {
+  acx_gemm_desc d = desc_of(p);
+  d.W = p.Wb;
+  d.a_dtype = xm.f16 ? ACX_F16 : ACX_BF16; d.prec = ACX_PREC_BF16; d.pairs = xm.pairs; d.panels = 3;
   d.out_scale = xm.f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
-  d.bias = bias; d.act = act; d.residual = residual; d.ldr = ldr ? ldr : ldc;
-  d.pairs = xm.pairs; d.a_plane_stride = a_rows * (int64_t)lda * 2; d.w_plane_stride = w_plane_bytes;
-  d.panels = 3;
+  d.a_plane_stride = (int64_t)p.M * p.lda * 2;
+  d.w_plane_stride = p.w_plane_bytes ? p.w_plane_bytes : (int64_t)p.N * p.K * 2;
   // scratch for the K split of a partly filled last round of tiles (acx_gemm: row-major outputs only)
-  d.workspace = tail_ws; d.workspace_bytes = tail_ws ? tail_bytes : 0;
-  // ln: the LayerNorm of the output rows follows (acx_gemm_ln: part of it rides in the product's last round)
-  return ln ? acx_gemm_ln(ctx, &d, ln, s) : acx_gemm(ctx, &d, s);
+  d.workspace = p.scratch; d.workspace_bytes = p.scratch ? p.scratch_bytes : 0;
+  return p.ln ? acx_gemm_ln(ctx, &d, p.ln, s) : acx_gemm(ctx, &d, s);
 }
 
-int linear1(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const float* Wf, const void* Wb, int ldw,
-            void* C, int c_dtype, int ldc, int M, int N, int K, const float* bias, int act, const float* residual,
-            hipStream_t s, int ldr, void* splitk_ws, size_t splitk_bytes) {
-  acx_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.A = A; d.C = C;
-  d.W = prec == ACX_PREC_BF16 ? Wb : (const void*)Wf;
-  if (!d.W) return acx_fail(ctx, ACX_E_BADARG, "driver: missing %s weight copy for the requested precision",
-                            prec == ACX_PREC_BF16 ? "bf16" : "f32");
-  d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldw = ldw; d.ldc = ldc;
-  d.a_dtype = a_dtype; d.c_dtype = c_dtype; d.prec = prec;
-  d.bias = bias; d.act = act; d.residual = residual; d.ldr = ldr ? ldr : ldc;
-  d.workspace = splitk_bytes ? splitk_ws : nullptr; d.workspace_bytes = splitk_bytes;
+int run_rows1(acx_ctx* ctx, int prec, const Product& p, hipStream_t s) {
+  acx_gemm_desc d = desc_of(p);
+  d.W = prec == ACX_PREC_BF16 ? p.Wb : (const void*)p.Wf;
+  if (!d.W) return missing_weights(ctx, false, prec);
+  d.prec = prec;
+  d.workspace = p.scratch_bytes ? p.scratch : nullptr; d.workspace_bytes = p.scratch_bytes;
   return acx_gemm(ctx, &d, s);
 }
 
-// Linear layer with tail handling: a grid of T tiles runs in ceil(T/512) waves of 128x128 tiles (2 per CU); when
+// Row product with tail handling: a grid of T tiles runs in ceil(T/512) waves of 128x128 tiles (2 per CU); when
 // the last wave would be mostly empty (e.g. N=768: 9.23 waves -> 10), the rows of that partial wave are issued as a
 // second launch that fills the chip (9 waves + ~1/3 wave): acx_gemm runs it on 64x64 tiles (f32, four blocks per CU)
-// or splits K over the workspace handed in here (other precisions).  The f32 tail gets no workspace: the 64x64 kernel would
+// or splits K over the scratch handed in here (other precisions).  The f32 tail gets no scratch: the 64x64 kernel would
 // split a K >= 1024 over it (ViT-L/14: 512 tail rows, K = 1024 / 4096), and the tail rows would then sum K in another order
 // than the head rows -- identical frames would no longer give identical rows across the launch.
-int linear(acx_ctx* ctx, int prec, const void* A, int a_dtype, int lda, const float* Wf, const void* Wb, int ldw,
-           void* C, int c_dtype, int ldc, int M, int N, int K, const float* bias, int act, const float* residual,
-           hipStream_t s, int ldr = 0, void* splitk_ws = nullptr, size_t splitk_bytes = 0) {
+int run_rows(acx_ctx* ctx, int prec, const Product& p, hipStream_t s) {
   bool tail_split = ACX_DBG_SWITCH("TAIL_SPLIT", true);
-  if (tail_split && !ldr) {   // the persistent strip-stream kernel balances its own tail
-    acx_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = M; d.N = N; d.K = K; d.lda = lda; d.ldw = ldw; d.ldc = ldc;
-    d.a_dtype = a_dtype; d.c_dtype = c_dtype; d.prec = prec; d.act = act; d.residual = residual;
+  if (tail_split && !p.ldr) {   // the persistent strip-stream kernel balances its own tail
+    acx_gemm_desc d = desc_of(p);
+    d.prec = prec;
     if (acx_gemm_takes_strip_stream(&d)) tail_split = false;
   }
-  const int tiles_n = (N + 127) / 128, tiles_m = (M + 127) / 128;
+  const int tiles_n = (p.N + 127) / 128, tiles_m = (p.M + 127) / 128;
   const long tiles = (long)tiles_m * tiles_n;
   const long full = tiles / 512;
   const long rem = tiles - full * 512;
-  if (tail_split && splitk_ws && full >= 2 && rem > 0 && rem <= 256 && !ldr) {
-    const int head_mt = (int)((full * 512) / tiles_n);
-    const int head_rows = head_mt * 128;
-    const int tail_rows = M - head_rows;
-    const size_t need = (size_t)4 * tail_rows * N * sizeof(float);
-    if (head_rows > 0 && tail_rows > 0 && need <= splitk_bytes) {
-      const size_t asz = a_dtype == ACX_BF16 ? 2 : 4, csz = c_dtype == ACX_BF16 ? 2 : 4;
-      int rc = linear1(ctx, prec, A, a_dtype, lda, Wf, Wb, ldw, C, c_dtype, ldc, head_rows, N, K, bias, act, residual, s, 0,
-                       nullptr, 0);
-      if (rc) return rc;
-      return linear1(ctx, prec, (const char*)A + (size_t)head_rows * lda * asz, a_dtype, lda, Wf, Wb, ldw,
-                     (char*)C + (size_t)head_rows * ldc * csz, c_dtype, ldc, tail_rows, N, K, bias, act,
-                     residual ? residual + (size_t)head_rows * ldc : nullptr, s, 0, prec == ACX_PREC_F32 ? nullptr : splitk_ws,
-                     prec == ACX_PREC_F32 ? 0 : splitk_bytes);
+  if (tail_split && p.scratch && full >= 2 && rem > 0 && rem <= 256 && !p.ldr) {
+    const int head_rows = (int)((full * 512) / tiles_n) * 128;
+    const int tail_rows = p.M - head_rows;
+    if (head_rows > 0 && tail_rows > 0 && (size_t)4 * tail_rows * p.N * sizeof(float) <= p.scratch_bytes) {
+      const size_t asz = p.a_dtype == ACX_BF16 ? 2 : 4, csz = p.c_dtype == ACX_BF16 ? 2 : 4;
+      Product head = p, tail = p;
+      head.M = head_rows; head.scratch = nullptr; head.scratch_bytes = 0;
+      tail.M = tail_rows;
+      tail.A = (const char*)p.A + (size_t)head_rows * p.lda * asz;
+      tail.C = (char*)p.C + (size_t)head_rows * p.ldc * csz;
+      if (p.residual) tail.residual = p.residual + (size_t)head_rows * p.ldc;
+      if (prec == ACX_PREC_F32) { tail.scratch = nullptr; tail.scratch_bytes = 0; }
+      const int rc = run_rows1(ctx, prec, head, s);
+      return rc ? rc : run_rows1(ctx, prec, tail, s);
     }
   }
-  return linear1(ctx, prec, A, a_dtype, lda, Wf, Wb, ldw, C, c_dtype, ldc, M, N, K, bias, act, residual, s, ldr, splitk_ws,
-                 splitk_bytes);
+  return run_rows1(ctx, prec, p, s);
 }
 
-// cls_ws != nullptr: the LAST layer is evaluated only where its output is consumed (token 0 of every sequence,
-// clip/model.py:285): K and V for all tokens, everything else for `batch` rows.  The final residual stream of
-// the CLS tokens is left COMPACT in cls_ws[0 .. batch*W) instead of x.
-// ACX_OPT_CLS_FOLD (every precision but bf16): not even K and V -- ln_1 and Q for the CLS rows, then acx_attention_cls_fold reads the
-// residual stream itself (u | z scratch: the f32 q | k | v buffer, free in that layer).
-int transformer_layers(acx_ctx* ctx, float* x, int batch, int L, int W, int heads, int layers, int causal, int prec,
-                       const acx_block_weights* blk, const TfWs& ws, hipStream_t s, float* cls_ws = nullptr) {
-  const int64_t rows = (int64_t)batch * L;
-  const bool x6mode = is_xmode(prec);
-  const XMode xm = xmode_of(prec);
-  const int pdt3 = prec == ACX_PREC_F16X3 ? ACX_F16X2P : prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P;   // LayerNorm's plane output
-  if (x6mode) prec = ACX_PREC_F32;               // everything that is not one of the four large GEMMs runs as in f32 mode
-  const int hdt = prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
-  const size_t esz = prec == ACX_PREC_BF16 ? 2 : 4;
-  int rc;
+int run(acx_ctx* ctx, const TfMode& m, const Product& p, hipStream_t s) {
+  return p.kernel == ACX_TF_GEMM_X6 ? run_x6(ctx, m.xm, p, s) : run_rows(ctx, m.prec, p, s);
+}
+
+// ---- the layer plan: every decision of the transformer drivers, taken once, before the first launch ----------------------------
+struct TfGeom {
+  int batch, L, W, heads, layers, causal, prec;
+  bool prune;                  // the LAST layer is evaluated only where its output is consumed: token 0 of every sequence (clip/model.py:285)
+  bool planes_ws;              // the workspace holds the planes of a plane mode (TfWs.hp)
+};
+struct TfHave { bool f32[4], alt[4]; };   // in_proj, out_proj, fc, proj of every block: the f32 weight, the *_w_bf16 copy / planes
+struct TfPlan {
+  TfMode mode;
+  acx_tf_layer_plan_t body, before_pruned, pruned;   // the three layer shapes (before_pruned: body with the pruned layer's ln_1 job)
+  bool prune;
+};
+
+// layer l's record: one of the three shapes; the first layer's ln_1 has no product before it, the last layer's proj no ln_1 behind it
+acx_tf_layer_plan_t tf_layer(const TfPlan& p, int l, int layers) {
+  acx_tf_layer_plan_t r = p.prune && l == layers - 1 ? p.pruned : p.prune && l == layers - 2 ? p.before_pruned : p.body;
+  if (l == 0 && r.ln1 == ACX_TF_LN_RIDDEN) r.ln1 = ACX_TF_LN_PLANES;
+  if (l == layers - 1) r.proj.ln_job = 0;
+  return r;
+}
+
+inline acx_tf_product_t tf_rows(int c_dtype, int scratch) { return {ACX_TF_GEMM_ROWS, c_dtype, scratch, 0}; }
+inline acx_tf_product_t tf_x6(int c_dtype, int scratch, bool ln_job) { return {ACX_TF_GEMM_X6, c_dtype, scratch, ln_job ? 1 : 0}; }
+
+// Pure host arithmetic on its arguments (err: where a refusal's text goes, nothing else).
+int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, TfPlan* p) {
+  memset(p, 0, sizeof(*p));
+  const int W = g.W, L = g.L;
+  const int64_t rows = (int64_t)g.batch * L;
+  const bool xmode = is_xmode(g.prec);
+  TfMode& m = p->mode;
+  m.xm = xmode_of(g.prec);
+  m.pdt = plane_dtype_of(g.prec);
+  m.prec = xmode ? ACX_PREC_F32 : g.prec;         // everything that is not one of the four large GEMMs runs as in f32 mode
+  m.hdt = m.prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
+  p->prune = g.prune;
+  const int cpl = m.xm.f16 ? ACX_F16X2P : ACX_BF16X3P;   // a plane product's plane output
+  auto x6 = [&](int N, int K) { return xmode && x6_takes(o, g.planes_ws, rows, N, K, K); };
+  const bool x6_qkv = x6(3 * W, W), x6_out = x6(W, W), x6_fc = x6(4 * W, W), x6_proj = x6(W, 4 * W), x6_kv = x6(2 * W, W);
   // ACX_PREC_F32X6: the LayerNorm behind a residual product (out-proj -> ln_2, c_proj -> the next layer's ln_1, K | V LayerNorm of the
   // pruned last layer included) is handed to the product (acx_gemm_ln: the idle workgroups of its last round of tiles run part of it)
-  const bool ln_ride = pdt3 == ACX_BF16X3P;
-  bool ln1_done = false;                         // this layer's ln_1 planes were written behind the previous layer's c_proj
-  // The fold's u | z scratch (2 heads W floats per frame) lives in ws.qkv (3 L W floats per frame): a geometry with 2 heads > 3 L
-  // tokens (fewer than 11 tokens at 16 heads; no CLIP backbone) keeps the K | V path below, whatever the option says.
-  const size_t fold_ws_bytes = (size_t)rows * 3 * W * 4;                         // ws.qkv
-  const bool cls_fold = cls_ws && prec != ACX_PREC_BF16 && ctx && ctx->opt_cls_fold && L <= 1024 &&
-                        acx_attention_cls_fold_workspace_bytes(batch, heads) <= fold_ws_bytes;
-  for (int l = 0; l < layers; ++l) {
-    const acx_block_weights& b = blk[l];
-    if (cls_ws && l == layers - 1) {
-      float* xc = cls_ws;                        // [batch, W]  final CLS residual stream
-      float* attc = cls_ws + (size_t)batch * W;  // [batch, W]
-      float* x1 = attc + (size_t)batch * W;      // [batch, W]
-      char* hc = (char*)(x1 + (size_t)batch * W);          // [batch, W]   (f32 or bf16)
-      char* mc = hc + (size_t)batch * W * 4;               // [batch, 4W]  (f32 or bf16)
-      if (cls_fold) {
-        // ln_1 and Q for the CLS rows (hc and mc are free until ln_2 / c_fc), then the folded attention over the rows of x
-        float* qc = (float*)mc;                  // [batch, W]
-        if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, hc, W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-        if ((rc = linear(ctx, prec, hc, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, qc, ACX_F32, W, batch, W, W, b.in_proj_b, ACX_ACT_NONE,
-                         nullptr, s))) return rc;
-        if ((rc = acx_attention_cls_fold(ctx, x, b.ln1_w, b.ln1_b, 1e-5f, b.in_proj_w, b.in_proj_b, qc, W, attc, W, batch, L, W, heads,
-                                         ws.qkv, fold_ws_bytes, s))) return rc;
-      } else {
-        // K | V for every token: rows [W, 3W) of in_proj
-        if (x6mode && x6_takes(ctx, ws, rows, 2 * W, W, W)) {
-          // LayerNorm writes the product's three planes itself (all rows) and the f32 rows of the CLS tokens (Q below reads only those)
-          if (!b.in_proj_w_bf16) return acx_fail(ctx, ACX_E_BADARG, "driver: missing bf16 x 3 weight planes for ACX_PREC_F32X6%s");
-          if (!ln1_done && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-          if ((rc = acx_layernorm(ctx, x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-          if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, (const char*)b.in_proj_w_bf16 + (size_t)W * 64 /* row W of every K-panel */, (int64_t)3 * W * W * 2, W,
-                              (float*)ws.qkv + W, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
-        } else {
-          if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-          if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w + (size_t)W * W,
-                           b.in_proj_w_bf16 ? (const char*)b.in_proj_w_bf16 + (size_t)W * W * 2 : nullptr, W,
-                           (float*)ws.qkv + W, ACX_F32, 3 * W, (int)rows, 2 * W, W, b.in_proj_b + W, ACX_ACT_NONE, nullptr, s))) return rc;
-        }
-        // Q for the CLS rows only (A rows strided by one sequence)
-        if ((rc = linear(ctx, prec, ws.h, hdt, L * W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, ACX_F32, L * 3 * W, batch, W, W,
-                         b.in_proj_b, ACX_ACT_NONE, nullptr, s))) return rc;
-        if ((rc = acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, attc, W, batch, L, heads, s))) return rc;
-      }
-      if ((rc = linear(ctx, prec, attc, ACX_F32, W, b.out_proj_w, b.out_proj_w_bf16, W, x1, ACX_F32, W, batch, W, W,
-                       b.out_proj_b, ACX_ACT_NONE, x, s, L * W))) return rc;
-      if ((rc = acx_layernorm(ctx, x1, W, b.ln2_w, b.ln2_b, hc, W, hdt, batch, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-      if ((rc = linear(ctx, prec, hc, hdt, W, b.fc_w, b.fc_w_bf16, W, mc, hdt, 4 * W, batch, 4 * W, W, b.fc_b,
-                       ACX_ACT_QUICKGELU, nullptr, s))) return rc;
-      if ((rc = linear(ctx, prec, mc, hdt, 4 * W, b.proj_w, b.proj_w_bf16, 4 * W, xc, ACX_F32, W, batch, W, 4 * W,
-                       b.proj_b, ACX_ACT_NONE, x1, s))) return rc;
-      (void)esz;
-      continue;
+  const bool ln_ride = m.pdt == ACX_BF16X3P;
+  // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
+  // QKV store traffic, bf16-MFMA attention, and a bf16 A operand (LDS-DMA kernels) for the out-projection
+  const bool ab = m.prec == ACX_PREC_BF16 && !g.causal && L <= 224 && ACX_DBG_SWITCH("ATTN_BF16", true);
+  // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
+  const bool att_p3 = x6_qkv && x6_out && !g.causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
+  // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
+  const bool att_p3f = att_p3 && ln_ride && o.attn_f32in;
+  const bool qkv_planes = att_p3 && !att_p3f;
+  // ... or on f32 rows, writing the out-projection's three planes itself
+  const bool att_x3 = x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
+  // ACX_OPT_CLS_FOLD (every precision but bf16): the pruned layer without K and V -- ln_1 and Q for the CLS rows, then
+  // acx_attention_cls_fold reads the residual stream itself.  Its u | z scratch (2 heads W floats per frame) lives in the f32 q | k | v
+  // buffer (3 L W floats per frame): a geometry with 2 heads > 3 L tokens (fewer than 11 tokens at 16 heads; no CLIP backbone) keeps
+  // the K | V path, whatever the option says.
+  const bool cls_fold = g.prune && m.prec != ACX_PREC_BF16 && o.cls_fold && L <= 1024 &&
+                        acx_attention_cls_fold_workspace_bytes(g.batch, g.heads) <= (size_t)rows * 3 * W * 4;
+  const bool kv_planes = g.prune && !cls_fold && x6_kv;   // the pruned layer's K | V product runs on the plane kernel
+
+  // refusals, in the order the walk meets them: in-projection, the fp16 gate, the other products, the pruned layer
+  auto need = [&](bool planes, int i) { return (planes || m.prec == ACX_PREC_BF16 ? have.alt[i] : have.f32[i]) ? 0 : missing_weights(err, planes, m.prec); };
+  int rc;
+  if (g.layers > (g.prune ? 1 : 0)) {
+    if ((rc = need(x6_qkv, 0))) return rc;
+    if (m.xm.f16 && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
+      return acx_fail(err, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
+    if ((rc = need(x6_out, 1)) || (rc = need(x6_fc, 2)) || (rc = need(x6_proj, 3))) return rc;
+  }
+  if (g.prune && g.layers > 0) {
+    if (kv_planes && (rc = need(true, 0))) return rc;
+    for (int i = 0; i < 4; ++i) if ((rc = need(false, i))) return rc;
+  }
+
+  // x = x + attn(ln_1(x)); x = x + mlp(ln_2(x))                      clip/model.py:215-216
+  // (plane modes: the producers of the four large GEMMs' inputs write the planes themselves -- LayerNorm, the plane attentions and
+  // the QuickGELU epilogue of c_fc; an f32 attention output or MLP hidden in front of a plane product goes through acx_split_bf16x3_panel.
+  // Scratch: a free f32 buffer -- ws.h at every plane product, LayerNorm's output went to the planes or has been consumed; ws.qkv /
+  // ws.mlp where the product writes the planes of that buffer's contents)
+  acx_tf_layer_plan_t& b = p->body;
+  b.ln1 = !x6_qkv ? ACX_TF_LN_ROWS : ln_ride && x6_proj ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
+  b.ln1_dtype = x6_qkv ? m.pdt : m.hdt;
+  b.in_proj = !x6_qkv ? tf_rows(ab ? ACX_BF16 : ACX_F32, ACX_TF_BUF_SPLITK)
+                      : qkv_planes ? tf_x6(cpl, ACX_TF_BUF_QKV, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
+  b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
+  b.att_products = b.att == ACX_TF_ATT_P3N ? (m.xm.f16 ? 103 : m.xm.pairs) : 0;
+  b.split_att = x6_out && !att_x3 && !att_p3;
+  b.out_proj = x6_out ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_fc) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
+  b.ln2 = !x6_fc ? ACX_TF_LN_ROWS : b.out_proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
+  b.ln2_dtype = x6_fc ? m.pdt : m.hdt;
+  // QuickGELU(c_fc) straight into the planes of c_proj's input when c_proj takes the plane kernel too
+  b.fc = !x6_fc ? tf_rows(m.hdt, ACX_TF_BUF_SPLITK) : x6_proj ? tf_x6(cpl, ACX_TF_BUF_MLP, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
+  b.split_mlp = x6_proj && !x6_fc;
+  // c_proj carries the next layer's ln_1 where that writes planes: a whole layer with its in-projection on the plane kernel ...
+  b.proj = x6_proj ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_qkv) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
+  // ... or the pruned last layer's K | V product (none under ACX_OPT_CLS_FOLD: that layer reads x itself)
+  p->before_pruned = b;
+  p->before_pruned.proj.ln_job = x6_proj && ln_ride && kv_planes;
+
+  // the pruned layer: K | V for all tokens (rows [W, 3W) of in_proj) or the fold; everything else for `batch` rows, on the row kernels
+  acx_tf_layer_plan_t& c = p->pruned;
+  c.pruned = 1;
+  c.ln1 = cls_fold ? ACX_TF_LN_CLS : !kv_planes ? ACX_TF_LN_ROWS : p->before_pruned.proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
+  c.ln1_dtype = kv_planes ? m.pdt : m.hdt;
+  c.in_proj = kv_planes ? tf_x6(ACX_F32, ACX_TF_BUF_NONE, false) : tf_rows(ACX_F32, ACX_TF_BUF_NONE);
+  c.att = cls_fold ? ACX_TF_ATT_CLS_FOLD : ACX_TF_ATT_CLS;
+  c.out_proj = c.proj = tf_rows(ACX_F32, ACX_TF_BUF_NONE);
+  c.ln2 = ACX_TF_LN_CLS;
+  c.ln2_dtype = m.hdt;
+  c.fc = tf_rows(m.hdt, ACX_TF_BUF_NONE);
+  return ACX_OK;
+}
+
+// the plan of a driver call: the options of its context, the weights its blocks carry
+int tf_plan_call(acx_ctx* ctx, const TfGeom& g, const acx_block_weights* blk, TfPlan* p) {
+  TfHave have;
+  for (int i = 0; i < 4; ++i) have.f32[i] = have.alt[i] = true;
+  for (int l = 0; l < g.layers; ++l) {
+    const void* f32[4] = {blk[l].in_proj_w, blk[l].out_proj_w, blk[l].fc_w, blk[l].proj_w};
+    const void* alt[4] = {blk[l].in_proj_w_bf16, blk[l].out_proj_w_bf16, blk[l].fc_w_bf16, blk[l].proj_w_bf16};
+    for (int i = 0; i < 4; ++i) { have.f32[i] &= f32[i] != nullptr; have.alt[i] &= alt[i] != nullptr; }
+  }
+  return tf_plan(ctx, g, have, tf_opts(ctx, false), p);
+}
+
+// ---- the executor: walks the layers and launches what the records say ----------------------------------------------------------
+struct TfRun {
+  acx_ctx* ctx; const TfGeom& g; const TfMode& m; const TfWs& ws; hipStream_t s;
+  int64_t rows() const { return (int64_t)g.batch * g.L; }
+
+  // product i (0 in_proj, 1 out_proj, 2 fc, 3 proj) of block b on M rows, run as r says; A, C and residual are the caller's to set
+  Product product(const acx_block_weights& b, int i, const acx_tf_product_t& r, int64_t M) const {
+    const int W = g.W;
+    Product p;
+    memset(&p, 0, sizeof(p));
+    p.kernel = r.kernel; p.c_dtype = r.c_dtype; p.M = (int)M;
+    switch (i) {
+      case 0: p.Wf = b.in_proj_w; p.Wb = b.in_proj_w_bf16; p.bias = b.in_proj_b; p.N = 3 * W; p.K = W; break;
+      case 1: p.Wf = b.out_proj_w; p.Wb = b.out_proj_w_bf16; p.bias = b.out_proj_b; p.N = W; p.K = W; break;
+      case 2: p.Wf = b.fc_w; p.Wb = b.fc_w_bf16; p.bias = b.fc_b; p.N = 4 * W; p.K = W; p.act = ACX_ACT_QUICKGELU; break;
+      default: p.Wf = b.proj_w; p.Wb = b.proj_w_bf16; p.bias = b.proj_b; p.N = W; p.K = 4 * W; break;
     }
-    // x = x + attn(ln_1(x))                                          clip/model.py:215
-    // (ACX_PREC_F32X6: the producers of the four large GEMMs' inputs write the three bf16 planes themselves -- LayerNorm and
-    // the QuickGELU epilogue of c_fc -- only the attention output goes through acx_split_bf16x3)
-    const bool x6_qkv = x6mode && x6_takes(ctx, ws, rows, 3 * W, W, W), x6_out = x6mode && x6_takes(ctx, ws, rows, W, W, W);
-    const bool x6_fc = x6mode && x6_takes(ctx, ws, rows, 4 * W, W, W), x6_proj = x6mode && x6_takes(ctx, ws, rows, W, 4 * W, 4 * W);
-    bool ln2_done = false;
-    const bool ln1_had = ln1_done;
-    ln1_done = false;
-    if (x6_qkv) {
-      if (!ln1_had && (rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-    } else
-    if ((rc = acx_layernorm(ctx, x, W, b.ln1_w, b.ln1_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-    // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
-    // QKV store traffic, bf16-MFMA attention, and a bf16 A operand (LDS-DMA kernels) for the out-projection
-    const bool ab = prec == ACX_PREC_BF16 && !causal && L <= 224 && ACX_DBG_SWITCH("ATTN_BF16", true);
-    const int qdt = ab ? ACX_BF16 : ACX_F32;
-    // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
-    const bool att_p3 = x6_qkv && x6_out && ws.qkv3 && !causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
-    // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
-    const bool att_p3f = att_p3 && pdt3 == ACX_BF16X3P && ctx && ctx->opt_attn_f32in;
-    const bool qkv_planes = att_p3 && !att_p3f;
-    if (x6_qkv) {
-      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.in_proj_w_bf16, (int64_t)3 * W * W * 2, W, qkv_planes ? (void*)ws.qkv3 : (void*)ws.qkv, 3 * W,
-                          (int)rows, 3 * W, W, b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, qkv_planes ? ACX_BF16X3P : ACX_F32,
-                          qkv_planes ? ws.qkv : ws.h, qkv_planes ? (size_t)rows * 3 * W * 4 : (size_t)rows * W * 4))) return rc;   // (free f32 buffers: tail scratch)
-    } else
-    if ((rc = linear(ctx, prec, ws.h, hdt, W, b.in_proj_w, b.in_proj_w_bf16, W, ws.qkv, qdt, 3 * W, (int)rows, 3 * W, W,
-                     b.in_proj_b, ACX_ACT_NONE, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
-    const bool att_x3 = x6_out && !causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
-    if (xm.f16 && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
-    if (ab) {
-      if ((rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s))) return rc;
-    } else if (att_p3f) {  // f32 rows in, planes out
-      if ((rc = acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s))) return rc;
-    } else if (att_p3) {   // planes in, planes out
-      if ((rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, xm.f16 ? 103 : xm.pairs, s))) return rc;
-    } else if (att_x3) {   // the attention writes the out-projection's three planes itself
-      if ((rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s))) return rc;
+    p.lda = p.ldw = p.K; p.ldc = p.N; p.a_dtype = m.hdt;
+    const size_t f = (size_t)rows() * W * 4;
+    switch (r.scratch) {
+      case ACX_TF_BUF_SPLITK: p.scratch = ws.splitk; p.scratch_bytes = ws.splitk_bytes; break;
+      case ACX_TF_BUF_H: p.scratch = ws.h; p.scratch_bytes = f; break;
+      case ACX_TF_BUF_QKV: p.scratch = ws.qkv; p.scratch_bytes = 3 * f; break;
+      case ACX_TF_BUF_MLP: p.scratch = ws.mlp; p.scratch_bytes = 4 * f; break;
+      default: break;
+    }
+    return p;
+  }
+  int norm(const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int dtype, int64_t n) const {
+    return acx_layernorm(ctx, x, ldx, w, b, y, ldy, dtype, n, g.W, 1e-5f, ACX_NORM_LAYER, s);
+  }
+  // ln_1 / ln_2 of all rows: to ws.h, to the planes of ws.hp, or already run behind the previous residual product
+  int norm_all(int kind, int dtype, const float* x, const float* w, const float* b) const {
+    if (kind == ACX_TF_LN_RIDDEN) return ACX_OK;
+    return norm(x, g.W, w, b, kind == ACX_TF_LN_PLANES ? ws.hp : ws.h, g.W, dtype, rows());
+  }
+  acx_ln_job job(const float* w, const float* b) const { return {w, b, ws.hp, m.pdt, 1e-5f, ACX_NORM_LAYER}; }
+  int go(const Product& p) const { return run(ctx, m, p, s); }
+
+  int body(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const acx_block_weights* next, float* x) const {
+    const int W = g.W, batch = g.batch, L = g.L, heads = g.heads;
+    auto planes = [](const acx_tf_product_t& q) { return q.c_dtype != ACX_F32 && q.c_dtype != ACX_BF16; };
+    int rc;
+    if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b))) return rc;
+    Product p = product(b, 0, r.in_proj, rows());
+    p.A = r.in_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
+    p.C = planes(r.in_proj) ? ws.qkv3 : ws.qkv;
+    if ((rc = go(p))) return rc;
+    switch (r.att) {
+      case ACX_TF_ATT_BF16: rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s); break;
+      case ACX_TF_ATT_P3F: rc = acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s); break;   // f32 rows in, planes out
+      case ACX_TF_ATT_P3N: rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, r.att_products, s); break;        // planes in, planes out
+      case ACX_TF_ATT_X3_PANEL: rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s); break;
+      default: rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, g.causal, s); break;
+    }
+    if (rc) return rc;
+    if (r.split_att && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.att, W, ws.hp, rows() * W * 2, rows(), W, s))) return rc;
+    const acx_ln_job ln2 = job(b.ln2_w, b.ln2_b);   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
+    p = product(b, 1, r.out_proj, rows());
+    p.A = r.out_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.att;
+    p.a_dtype = r.att == ACX_TF_ATT_BF16 ? ACX_BF16 : ACX_F32;
+    p.C = x; p.residual = x;
+    p.ln = r.out_proj.ln_job ? &ln2 : nullptr;
+    if ((rc = go(p))) return rc;
+    if ((rc = norm_all(r.ln2, r.ln2_dtype, x, b.ln2_w, b.ln2_b))) return rc;
+    p = product(b, 2, r.fc, rows());
+    p.A = r.fc.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
+    p.C = planes(r.fc) ? ws.mp : ws.mlp;
+    if ((rc = go(p))) return rc;
+    if (r.split_mlp && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, rows() * 4 * W * 2, rows(), 4 * W, s))) return rc;
+    const acx_ln_job ln1 = r.proj.ln_job ? job(next->ln1_w, next->ln1_b) : job(nullptr, nullptr);
+    p = product(b, 3, r.proj, rows());
+    p.A = r.proj.kernel == ACX_TF_GEMM_X6 ? ws.mp : ws.mlp;
+    p.C = x; p.residual = x;
+    p.ln = r.proj.ln_job ? &ln1 : nullptr;
+    return go(p);
+  }
+
+  // the final residual stream of the CLS tokens is left COMPACT in c.xc instead of x
+  int pruned(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const float* x, const ClsWs& c) const {
+    const int W = g.W, batch = g.batch, L = g.L;
+    int rc;
+    Product p = product(b, 0, r.in_proj, rows());
+    if (r.att == ACX_TF_ATT_CLS_FOLD) {
+      // ln_1 and Q for the CLS rows (hc and mc are free until ln_2 / c_fc), then the folded attention over the rows of x
+      if ((rc = norm(x, (int64_t)L * W, b.ln1_w, b.ln1_b, c.hc, W, r.ln1_dtype, batch))) return rc;
+      p.M = batch; p.N = W;
+      p.A = c.hc;
+      p.C = c.mc; p.ldc = W;
+      if ((rc = go(p))) return rc;
+      if ((rc = acx_attention_cls_fold(ctx, x, b.ln1_w, b.ln1_b, 1e-5f, b.in_proj_w, b.in_proj_b, (const float*)c.mc, W, c.attc, W, batch, L, W,
+                                       g.heads, ws.qkv, (size_t)rows() * 3 * W * 4, s))) return rc;
     } else {
-      if ((rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, causal, s))) return rc;
+      // K | V for every token: rows [W, 3W) of in_proj.  On the plane kernel LayerNorm writes the product's planes (all rows) and the
+      // f32 rows of the CLS tokens (Q below reads only those)
+      if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b))) return rc;
+      p.N = 2 * W; p.bias = b.in_proj_b + W;
+      p.C = (float*)ws.qkv + W; p.ldc = 3 * W;
+      if (r.in_proj.kernel == ACX_TF_GEMM_X6) {
+        if ((rc = norm(x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, m.hdt, batch))) return rc;
+        p.A = ws.hp;
+        p.Wb = (const char*)b.in_proj_w_bf16 + (size_t)W * 64;   // row W of every K-panel
+        p.w_plane_bytes = (int64_t)3 * W * W * 2;
+      } else {
+        p.A = ws.h;
+        p.Wf = b.in_proj_w + (size_t)W * W;
+        p.Wb = b.in_proj_w_bf16 ? (const char*)b.in_proj_w_bf16 + (size_t)W * W * 2 : nullptr;
+      }
+      if ((rc = go(p))) return rc;
+      // Q for the CLS rows only (A rows strided by one sequence)
+      Product q = product(b, 0, tf_rows(ACX_F32, ACX_TF_BUF_NONE), batch);
+      q.N = W;
+      q.A = ws.h; q.lda = L * W;
+      q.C = ws.qkv; q.ldc = L * 3 * W;
+      if ((rc = go(q))) return rc;
+      if ((rc = acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, c.attc, W, batch, L, g.heads, s))) return rc;
     }
-    if (x6_out) {
-      if (!att_x3 && !att_p3 && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.att, W, ws.hp, (int64_t)rows * W * 2, rows, W, s))) return rc;
-      // (ws.h is free here and at c_proj: LayerNorm's output has been consumed, or went to the planes)
-      const acx_ln_job ln2 = {b.ln2_w, b.ln2_b, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
-      ln2_done = ln_ride && x6_fc;
-      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.out_proj_w_bf16, (int64_t)W * W * 2, W, x, W, (int)rows, W, W, b.out_proj_b,
-                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln2_done ? &ln2 : nullptr))) return rc;
-    } else
-    if ((rc = linear(ctx, prec, ws.att, qdt, W, b.out_proj_w, b.out_proj_w_bf16, W, x, ACX_F32, W, (int)rows, W, W,
-                     b.out_proj_b, ACX_ACT_NONE, x, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
-    // x = x + mlp(ln_2(x))                                           clip/model.py:216
-    if (x6_fc) {
-      if (!ln2_done && (rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.hp, W, pdt3, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-    } else
-    if ((rc = acx_layernorm(ctx, x, W, b.ln2_w, b.ln2_b, ws.h, W, hdt, rows, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-    if (x6_fc) {
-      // QuickGELU(c_fc) straight into the planes of c_proj's input when c_proj takes the x6 path too
-      if ((rc = linear_x6(ctx, xm, ws.hp, W, rows, b.fc_w_bf16, (int64_t)4 * W * W * 2, W, x6_proj ? (void*)ws.mp : (void*)ws.mlp, 4 * W,
-                          (int)rows, 4 * W, W, b.fc_b, ACX_ACT_QUICKGELU, nullptr, s, 0, x6_proj ? ACX_BF16X3P : ACX_F32,
-                          x6_proj ? ws.mlp : ws.h, x6_proj ? (size_t)rows * 4 * W * 4 : (size_t)rows * W * 4))) return rc;
-    } else
-    if ((rc = linear(ctx, prec, ws.h, hdt, W, b.fc_w, b.fc_w_bf16, W, ws.mlp, hdt, 4 * W, (int)rows, 4 * W, W, b.fc_b,
-                     ACX_ACT_QUICKGELU, nullptr, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
-    if (x6_proj) {
-      if (!x6_fc && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, (int64_t)rows * 4 * W * 2, rows, 4 * W, s))) return rc;
-      // the next layer's ln_1 where it writes the planes of ws.hp: a whole layer with its in-projection on the plane kernel, or the
-      // pruned last layer's K | V product (none under ACX_OPT_CLS_FOLD: that layer reads x itself)
-      const bool next_planes = l + 1 < layers && ((cls_ws && l + 1 == layers - 1) ? !cls_fold && x6_takes(ctx, ws, rows, 2 * W, W, W) && blk[l + 1].in_proj_w_bf16 != nullptr
-                                                                                  : x6_qkv);
-      ln1_done = ln_ride && next_planes;
-      const acx_ln_job ln1 = {ln1_done ? blk[l + 1].ln1_w : nullptr, ln1_done ? blk[l + 1].ln1_b : nullptr, ws.hp, pdt3, 1e-5f, ACX_NORM_LAYER};
-      if ((rc = linear_x6(ctx, xm, ws.mp, 4 * W, rows, b.proj_w_bf16, (int64_t)W * 4 * W * 2, 4 * W, x, W, (int)rows, W, 4 * W, b.proj_b,
-                          ACX_ACT_NONE, x, s, 0, ACX_F32, ws.h, (size_t)rows * W * 4, ln1_done ? &ln1 : nullptr))) return rc;
-    } else
-    if ((rc = linear(ctx, prec, ws.mlp, hdt, 4 * W, b.proj_w, b.proj_w_bf16, 4 * W, x, ACX_F32, W, (int)rows, W, 4 * W,
-                     b.proj_b, ACX_ACT_NONE, x, s, 0, ws.splitk, ws.splitk_bytes))) return rc;
+    p = product(b, 1, r.out_proj, batch);
+    p.A = c.attc; p.a_dtype = ACX_F32;
+    p.C = c.x1; p.residual = x; p.ldr = L * W;
+    if ((rc = go(p))) return rc;
+    if ((rc = norm(c.x1, W, b.ln2_w, b.ln2_b, c.hc, W, r.ln2_dtype, batch))) return rc;
+    p = product(b, 2, r.fc, batch);
+    p.A = c.hc;
+    p.C = c.mc;
+    if ((rc = go(p))) return rc;
+    p = product(b, 3, r.proj, batch);
+    p.A = c.mc;
+    p.C = c.xc; p.residual = c.x1;
+    return go(p);
+  }
+};
+
+int transformer_layers(acx_ctx* ctx, float* x, const TfGeom& g, const TfPlan& plan, const acx_block_weights* blk, const TfWs& ws,
+                       hipStream_t s, float* cls_ws = nullptr) {
+  const TfRun exec = {ctx, g, plan.mode, ws, s};
+  for (int l = 0; l < g.layers; ++l) {
+    const acx_tf_layer_plan_t r = tf_layer(plan, l, g.layers);
+    const int rc = r.pruned ? exec.pruned(r, blk[l], x, carve_cls(cls_ws, g.batch, g.W))
+                            : exec.body(r, blk[l], l + 1 < g.layers ? &blk[l + 1] : nullptr, x);
+    if (rc) return rc;
   }
   return ACX_OK;
 }
@@ -472,6 +638,21 @@ extern "C" size_t acx_transformer_workspace_bytes_prec(int32_t width, int32_t ro
   return carve_tf(nullptr, rows, width, prec).total;
 }
 
+extern "C" int acx_transformer_plan(const acx_ctx* ctx, int32_t batch, int32_t L, int32_t width, int32_t heads, int32_t layers,
+                                    int32_t causal, int32_t prec, int32_t prune_last, int32_t has_weight_planes,
+                                    int32_t workspace_is_prec_sized, acx_tf_layer_plan_t* out) {
+  acx_ctx* err = const_cast<acx_ctx*>(ctx);      // (the refusal's text)
+  if (!out || batch <= 0 || L <= 0 || layers < 0) return acx_fail(err, ACX_E_BADARG, "acx_transformer_plan: no result array or an empty geometry%s");
+  memset(out, 0, sizeof(*out) * layers);
+  const TfGeom g = {batch, L, width, heads, layers, causal, prec, prune_last != 0, is_xmode(prec) && workspace_is_prec_sized};
+  const bool alt = has_weight_planes != 0;
+  const TfHave have = {{true, true, true, true}, {alt, alt, alt, alt}};
+  TfPlan plan;
+  const int rc = tf_plan(err, g, have, tf_opts(ctx, true), &plan);
+  for (int l = 0; !rc && l < layers; ++l) out[l] = tf_layer(plan, l, layers);
+  return rc;
+}
+
 extern "C" int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, int32_t width, int32_t heads,
                                        int32_t layers, int32_t causal, int32_t prec, const acx_block_weights* blocks,
                                        void* workspace, size_t workspace_bytes, void* stream) {
@@ -482,7 +663,10 @@ extern "C" int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, in
   TfWs ws = carve_tf((char*)workspace, (int64_t)batch * L, width, prec);
   if (ws.total > workspace_bytes && is_xmode(prec)) ws = carve_tf((char*)workspace, (int64_t)batch * L, width);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_transformer_forward: workspace too small%s");
-  return transformer_layers(ctx, x, batch, L, width, heads, layers, causal, prec, blocks, ws, (hipStream_t)stream);
+  const TfGeom g = {batch, L, width, heads, layers, causal, prec, false, ws.hp != nullptr};
+  TfPlan plan;
+  const int rc = tf_plan_call(ctx, g, blocks, &plan);
+  return rc ? rc : transformer_layers(ctx, x, g, plan, blocks, ws, (hipStream_t)stream);
 }
 
 namespace {
@@ -499,7 +683,7 @@ VitWs carve_vit(char* base, const acx_vit_desc* d, int F) {
   w.patch_out = base + off; off += al((size_t)F * T * W * 4);
   w.x = base + off;         off += al((size_t)F * (T + 1) * W * 4);
   w.cls = base + off;       off += al((size_t)F * W * 4);
-  w.cls_ws = base + off;    off += al((size_t)F * W * 4 * 8);      // xc, attc, x1, hc, mc(4W)
+  w.cls_ws = base + off;    off += al(cls_ws_bytes(F, W));
   w.tf_off = off;
   off += carve_tf(nullptr, (int64_t)F * (T + 1), W, d->prec).total;
   w.total = off;
@@ -526,35 +710,45 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
   const VitWs ws = carve_vit((char*)workspace, d, F);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_vit_encode: workspace too small%s");
   hipStream_t s = (hipStream_t)stream;
-  const int prec = is_xmode(d->prec) ? ACX_PREC_F32 : d->prec;   // final projection (and small launches): f32 kernels
-  const XMode xm = xmode_of(d->prec);
-  const int pdt = prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
-  int rc;
-  // conv1 as GEMM over im2col'ed patches                               clip/model.py:267-269
   const TfWs tf = carve_tf((char*)workspace + ws.tf_off, (int64_t)F * (T + 1), W, d->prec);
-  if (is_xmode(d->prec) && w->conv1_w_bf16 && K % 32 == 0 && x6_takes(ctx, tf, (int64_t)F * T, W, K, K)) {
-    // ACX_PREC_F32X6: im2col writes the three bf16 planes of the pixels (K-panel layout), the embedding is a pairs = 6 product
-    // like the layers' GEMMs (conv1_w_bf16: the weight's three K-panel planes); scratch for a K-split tail: the f32 q | k | v buffer
-    if ((rc = acx_vit_patches(ctx, frames, ws.patches, d->prec == ACX_PREC_F16X3 ? ACX_F16X2P : d->prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P,
-                              F, d->resolution, d->patch, s))) return rc;
-    if ((rc = linear_x6(ctx, xm, ws.patches, K, (int64_t)F * T, w->conv1_w_bf16, (int64_t)W * K * 2, K, ws.patch_out, W, F * T, W, K, nullptr,
-                        ACX_ACT_NONE, nullptr, s, 0, ACX_F32, tf.qkv, (size_t)F * (T + 1) * 3 * W * 4))) return rc;
+  const bool prune = ACX_DBG_SWITCH("VIT_PRUNE", true);
+  const TfGeom geom = {F, T + 1, W, d->heads, d->layers, 0, d->prec, prune, tf.hp != nullptr};
+  TfPlan plan;
+  int rc;
+  if ((rc = tf_plan_call(ctx, geom, w->blocks, &plan))) return rc;
+  const TfMode& m = plan.mode;                   // final projection (and small launches): f32 kernels in the plane modes
+  // conv1 as GEMM over im2col'ed patches                               clip/model.py:267-269
+  Product p;
+  memset(&p, 0, sizeof(p));
+  p.A = ws.patches; p.lda = K;
+  p.Wf = w->conv1_w; p.Wb = w->conv1_w_bf16; p.ldw = K;
+  p.M = F * T; p.N = W; p.K = K;
+  p.C = ws.patch_out; p.c_dtype = ACX_F32; p.ldc = W;
+  if (is_xmode(d->prec) && w->conv1_w_bf16 && K % 32 == 0 && x6_takes(tf_opts(ctx, false), tf.hp != nullptr, (int64_t)F * T, W, K, K)) {
+    // plane modes: im2col writes the planes of the pixels (K-panel layout), the embedding is a plane product like the layers' GEMMs
+    // (conv1_w_bf16: the weight's K-panel planes); scratch for a K-split tail: the f32 q | k | v buffer
+    p.kernel = ACX_TF_GEMM_X6;
+    p.a_dtype = m.pdt;
+    p.scratch = tf.qkv; p.scratch_bytes = (size_t)F * (T + 1) * 3 * W * 4;
   } else {
-  // a patch of 14 (K = 588: not a multiple of the bf16 kernels' 8) embeds on the f32 kernels in every mode: ~0.2 % of the MACs
-  const int pprec = d->patch % 4 ? ACX_PREC_F32 : prec, ppdt = d->patch % 4 ? ACX_F32 : pdt;
-  if ((rc = acx_vit_patches(ctx, frames, ws.patches, ppdt, F, d->resolution, d->patch, s))) return rc;
-  if ((rc = linear(ctx, pprec, ws.patches, ppdt, K, w->conv1_w, pprec == ACX_PREC_BF16 ? w->conv1_w_bf16 : nullptr, K, ws.patch_out, ACX_F32, W, F * T, W, K,
-                   nullptr, ACX_ACT_NONE, nullptr, s))) return rc;
+    // a patch of 14 (K = 588: not a multiple of the bf16 kernels' 8) embeds on the f32 kernels in every mode: ~0.2 % of the MACs
+    p.kernel = ACX_TF_GEMM_ROWS;
+    p.a_dtype = d->patch % 4 ? ACX_F32 : m.hdt;
   }
+  if ((rc = acx_vit_patches(ctx, frames, ws.patches, p.a_dtype, F, d->resolution, d->patch, s))) return rc;
+  if ((rc = p.kernel == ACX_TF_GEMM_X6 ? run_x6(ctx, m.xm, p, s) : run_rows(ctx, p.a_dtype == ACX_BF16 ? ACX_PREC_BF16 : ACX_PREC_F32, p, s))) return rc;
   // CLS + positional embedding + ln_pre                                :270-279
   if ((rc = acx_vit_embed(ctx, (const float*)ws.patch_out, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                           w->ln_pre_b, (float*)ws.x, F, T, W, s))) return rc;
-  const bool prune = ACX_DBG_SWITCH("VIT_PRUNE", true);
-  if ((rc = transformer_layers(ctx, (float*)ws.x, F, T + 1, W, d->heads, d->layers, 0, d->prec, w->blocks, tf, s,
-                               prune ? (float*)ws.cls_ws : nullptr))) return rc;
+  if ((rc = transformer_layers(ctx, (float*)ws.x, geom, plan, w->blocks, tf, s, (float*)ws.cls_ws))) return rc;
   // ln_post on the CLS rows, then @ proj                                :285-288
   if ((rc = acx_layernorm(ctx, prune ? (const float*)ws.cls_ws : (const float*)ws.x, prune ? (int64_t)W : (int64_t)(T + 1) * W,
                           w->ln_post_w, w->ln_post_b, ws.cls, W, ACX_F32, F, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
-  return linear(ctx, prec, ws.cls, ACX_F32, W, w->proj_t, w->proj_t_bf16, W, features, ACX_F32, d->embed_dim, F,
-                d->embed_dim, W, nullptr, ACX_ACT_NONE, nullptr, s);
+  memset(&p, 0, sizeof(p));
+  p.A = ws.cls; p.a_dtype = ACX_F32; p.lda = W;
+  p.Wf = w->proj_t; p.Wb = w->proj_t_bf16; p.ldw = W;
+  p.M = F; p.N = d->embed_dim; p.K = W;
+  p.C = features; p.c_dtype = ACX_F32; p.ldc = d->embed_dim;
+  return run_rows(ctx, m.prec, p, s);
 }
+

@@ -133,6 +133,23 @@ def ln_rider_plan(M: int, N: int, K: int, ncu: int, ksplit: int = 1, rate: float
     return int(ride), int(ready.value)
 
 
+def _struct_dict(s) -> dict:
+    return {n: (_struct_dict(v) if isinstance(v, C.Structure) else int(v)) for n, v in ((f[0], getattr(s, f[0])) for f in s._fields_)}
+
+
+def transformer_plan(batch: int, L_: int, width: int, heads: int, layers: int, *, causal: bool = False, prec: int = L.PREC_F32,
+                     prune_last: bool = False, has_weight_planes: bool = True, workspace_is_prec_sized: bool = True,
+                     device_index: Optional[int] = None) -> list:
+    """acx_transformer_plan: what acx_transformer_forward / acx_vit_encode (prune_last) launch for every layer, one dict per layer
+    with the fields of acx_tf_layer_plan_t (L.TF_* values; the four products as dicts) -- host arithmetic by the drivers' own plan
+    step, no device.  device_index None: the options acx_create sets, else that device's context.  A refusal raises L.AcxError."""
+    h = None if device_index is None else L.ctx(device_index)
+    out = (L.TfLayerPlan * max(1, layers))()
+    L.check(L.lib().acx_transformer_plan(h, int(batch), int(L_), int(width), int(heads), int(layers), int(causal), int(prec),
+                                         int(prune_last), int(has_weight_planes), int(workspace_is_prec_sized), out), h)
+    return [_struct_dict(out[l]) for l in range(layers)]
+
+
 _SPLITK_WS: dict = {}
 _SPLITK_RETIRED: list = []
 

@@ -482,6 +482,43 @@ int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, in
                             const acx_block_weights* blocks, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* acx_transformer_plan: what acx_transformer_forward / acx_vit_encode launch for every layer of a geometry -- answered by the plan
+ * step the drivers themselves execute (there is no second copy of the gates).  Host arithmetic, no device, nothing launched.
+ * prune_last: the last layer is evaluated for the CLS rows only (acx_vit_encode; acx_transformer_forward: 0).  has_weight_planes: the
+ * blocks carry their *_w_bf16 pointers (bf16 copies / weight planes; the f32 weights count as present).  workspace_is_prec_sized = 0:
+ * the plan of a plane mode that is handed an f32-sized workspace (acx_transformer_forward then runs the f32 kernels).  Returns what
+ * the driver returns before its first launch: ACX_OK, or the refusal's ACX_E_* with the same text in acx_last_error (the records are
+ * then cleared).  ctx == NULL: the option values acx_create sets.  out[l] is layer l's record:
+ *   ln1, ln2       ACX_TF_LN_*: ROWS own launch, f32 / bf16 rows; PLANES own launch, K-panel planes; RIDDEN handed to the previous
+ *                  residual product as its acx_ln_job (ln_1: the previous layer's proj; ln_2: out_proj); CLS the CLS rows only
+ *                  (pruned layer).  A pruned layer whose in_proj is ACX_TF_GEMM_X6 (the K | V product) adds the CLS rows' f32 launch
+ *                  to a PLANES / RIDDEN ln1: Q reads them.  ln1_dtype / ln2_dtype: the output's ACX_F32 / ACX_BF16 / plane dtype
+ *   in_proj .. proj  kernel ACX_TF_GEMM_ROWS (acx_gemm picks the kernel by its own routes) or ACX_TF_GEMM_X6 (plane kernel); c_dtype
+ *                  of its output (ACX_F32 / ACX_BF16 rows, ACX_BF16X3P / ACX_F16X2P planes); scratch ACX_TF_BUF_*: the buffer that is
+ *                  free at this product and serves its K split; ln_job 1: it carries the LayerNorm behind it (acx_gemm_ln).  A
+ *                  pruned layer's in_proj is the K | V product of all rows (or none: ACX_TF_ATT_CLS_FOLD); Q, for the CLS rows, is
+ *                  always a ROWS product
+ *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0)
+ *   split_att, split_mlp  1: acx_split_bf16x3_panel of the attention output / the MLP hidden is launched
+ *   pruned         1: the last layer, CLS rows only */
+enum { ACX_TF_LN_ROWS = 0, ACX_TF_LN_PLANES = 1, ACX_TF_LN_RIDDEN = 2, ACX_TF_LN_CLS = 3 };
+enum { ACX_TF_GEMM_ROWS = 0, ACX_TF_GEMM_X6 = 1 };
+enum { ACX_TF_BUF_NONE = 0, ACX_TF_BUF_SPLITK = 1, ACX_TF_BUF_H = 2, ACX_TF_BUF_QKV = 3, ACX_TF_BUF_MLP = 4 };
+enum { ACX_TF_ATT_F32 = 0, ACX_TF_ATT_BF16 = 1, ACX_TF_ATT_X3_PANEL = 2, ACX_TF_ATT_P3N = 3, ACX_TF_ATT_P3F = 4, ACX_TF_ATT_CLS = 5,
+       ACX_TF_ATT_CLS_FOLD = 6 };
+typedef struct acx_tf_product_t {
+  int32_t kernel, c_dtype, scratch, ln_job;
+} acx_tf_product_t;
+typedef struct acx_tf_layer_plan_t {
+  int32_t ln1, ln1_dtype, ln2, ln2_dtype;
+  acx_tf_product_t in_proj, out_proj, fc, proj;
+  int32_t att, att_products, split_att, split_mlp;
+  int32_t pruned, reserved;
+} acx_tf_layer_plan_t;
+int acx_transformer_plan(const acx_ctx* ctx, int32_t batch, int32_t L, int32_t width, int32_t heads, int32_t layers,
+                         int32_t causal, int32_t prec, int32_t prune_last, int32_t has_weight_planes,
+                         int32_t workspace_is_prec_sized, acx_tf_layer_plan_t* out /* [layers] */);
+
 /* ------------------------------------------------------------------------------------------
  * Head, forward (HBM-bound rows of SURVEY.md 8a). */
 
