@@ -14,6 +14,7 @@ ACX_F32, ACX_BF16, BF16X3, BF16X3P = 0, 1, 2, 3      # BF16X3 / BF16X3P: output 
 BF16X2P, ACX_F16, F16X2P = 4, 5, 6                     # hi + mid planes only; fp16 planes of the two-plane split (pairs = 3); their K-panel output
 PREC_F32, PREC_BF16, PREC_F32X6, PREC_F32X3, PREC_F16X3 = 0, 1, 2, 3, 4
 PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet encoder on the plane kernel (precision "bf16x6")
+PREC_F32X6_LN16 = 6                     # acx_vit_encode_ln16 only: PREC_F32X6 with the LayerNorm-fed products on fp16 planes (what "auto" resolves to)
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
@@ -83,7 +84,8 @@ class TfLayerPlan(C.Structure):   # acx_tf_layer_plan_t: what the transformer dr
 
 
 class LnJob(C.Structure):    # acx_ln_job: the LayerNorm acx_gemm_ln runs on the product's output rows
-    _fields_ = [("w", c_void_p), ("b", c_void_p), ("y", c_void_p), ("y_dtype", c_int32), ("eps", c_float), ("mode", c_int32)]
+    _fields_ = [("w", c_void_p), ("b", c_void_p), ("y", c_void_p), ("y_dtype", c_int32), ("eps", c_float), ("mode", c_int32),
+                ("y_scale", c_float)]
 
 
 class BlockWeights(C.Structure):
@@ -187,6 +189,8 @@ _SIGS = {
     "acx_gemm_ln_plan": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, C.c_double, C.POINTER(c_int64)]),
     "acx_layernorm": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int64, c_int32, c_float, c_int32, c_void_p]),
+    "acx_layernorm_scaled": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_int32,
+                                       c_float, c_void_p]),
     "acx_attention": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p]),
     "acx_attention_bf16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
@@ -215,6 +219,8 @@ _SIGS = {
     "acx_vit_workspace_bytes": (c_size_t, [C.POINTER(VitDesc), c_int32]),
     "acx_vit_encode": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_int32, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),
+    "acx_vit_encode_ln16": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_void_p, c_int32, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
     "acx_transformer_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "acx_transformer_workspace_bytes_prec": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_transformer_forward": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
@@ -425,6 +431,11 @@ def lib() -> C.CDLL:
                 fn.argtypes = args
             _lib = L
         return _lib
+
+
+def exports(name: str) -> bool:
+    """whether the loaded library has entry point `name` (an ACX_LIB_PATH library of another commit may not)"""
+    return isinstance(getattr(lib(), name, None), C._CFuncPtr)
 
 
 def ctx(device: int = 0) -> int:

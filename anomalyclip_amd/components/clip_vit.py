@@ -13,6 +13,7 @@ exists for it (no autograd through the ViT).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import List, Optional
 
 import torch
@@ -28,6 +29,10 @@ from .. import ops
 # kernels everywhere (v_mfma_f32_32x32x2_f32: an fmaf chain).  "bf16": bf16 operands, not a parity path.
 # "bf16x3" (opt-in, NOT f32-accurate): the plane kernels with the three leading cross products only (ACX_PREC_F32X3)
 # "f16x3" (opt-in): TWO fp16 planes per operand, three exact products -- f32-MFMA-level results for operands inside fp16's range
+# "auto" on the CLIP ViT widths (768, 1024) additionally runs the two LayerNorm-fed products of every body layer (in-projection, c_fc)
+# as three-product GEMMs of fp16 planes (ACX_PREC_F32X6_LN16) wherever they take the plane kernel, when ln16_scales() proves, from the
+# weights alone, that their operands stay inside fp16's range whatever the frames are; otherwise -- and always under "f32x6" -- six
+# products everywhere.
 PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32x6": L.PREC_F32X6, "bf16x3": L.PREC_F32X3,
               "f16x3": L.PREC_F16X3}
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
@@ -53,6 +58,53 @@ def check_vit_precision(precision: str, tokens: int, width: int, arch: str, reso
                          "ViT-B/16 geometry, whose planes attention (192 < tokens <= 208) it needs; use 'auto', 'f32' or 'bf16'")
     if tokens > 1024:
         raise ValueError(f"{arch} has {tokens} tokens per frame: the attention kernels take at most 1024")
+
+
+LN16_TARGET = 2.0 ** 14                                # s * (LayerNorm bound) <= 2^14: a factor 4 below fp16's largest number
+LN16_SCALE_RANGE = (2.0 ** -20, 2.0 ** 20)
+LN16_WEIGHT_MAX = 2.0 ** 15 / F16X3_WSCALE             # 2^10 max|w| <= 2^15
+
+
+def ln16_scale(bound: float) -> Optional[float]:
+    """The largest power of two s with s * bound <= 2^14, or None when bound is not a finite positive number or s leaves 2^-20 ... 2^20.
+    bound = max_i(|gamma_i| sqrt(D - 1) + |beta_i|) bounds every element of a LayerNorm output whatever its input row is."""
+    if not (math.isfinite(bound) and bound > 0.0):
+        return None
+    s = 2.0 ** (math.frexp(LN16_TARGET / bound)[1] - 1)
+    while s * bound > LN16_TARGET:                     # (the quotient's rounding; s * bound itself is exact)
+        s *= 0.5
+    return s if LN16_SCALE_RANGE[0] <= s <= LN16_SCALE_RANGE[1] else None
+
+
+@torch.no_grad()
+def ln16_scales(blocks, width: int) -> Optional[List[float]]:
+    """The weight-only proof behind ACX_PREC_F32X6_LN16 for a list of ResidualAttentionBlocks: [s(ln_1), s(ln_2)] per block (the
+    power-of-two scales of the LayerNorms' fp16 planes), or None when a condition fails -- a gamma, beta, in-projection or c_fc
+    weight that is not finite, a LayerNorm bound that is not > 0, a scale outside 2^-20 ... 2^20, or 2^10 max|w| > 2^15.  The frames play
+    no part: a LayerNorm output obeys |y_i| <= |gamma_i| sqrt(D - 1) + |beta_i| for every finite input row."""
+    vals = []
+    root = float(width - 1) ** 0.5
+    for b in blocks:
+        for ln in (b.ln_1, b.ln_2):
+            g, be = ln.weight.detach().double(), ln.bias.detach().double()
+            vals.append((g.abs() * root + be.abs()).max())                 # (max propagates NaN)
+            vals.append((g.abs() + be.abs()).sum())                        # finite iff every gamma and beta is
+        for wt in (b.attn.in_proj_weight, b.mlp.c_fc.weight):
+            vals.append(wt.detach().abs().max().double())
+            vals.append(wt.detach().double().abs().sum())
+    if not vals:
+        return None
+    v = torch.stack(vals).tolist()                                         # one transfer
+    out: List[float] = []
+    for i in range(0, len(v), 8):
+        b1, f1, b2, f2, w1, g1, w2, g2 = v[i:i + 8]
+        if not all(math.isfinite(t) for t in (f1, f2, g1, g2)) or not (w1 <= LN16_WEIGHT_MAX and w2 <= LN16_WEIGHT_MAX):
+            return None
+        s1, s2 = ln16_scale(b1), ln16_scale(b2)
+        if s1 is None or s2 is None:
+            return None
+        out += [s1, s2]
+    return out
 
 
 HEAD_MAX_AXIS = 128                                    # acx_axial_attention: 1 <= axis length <= 128 on either axis
@@ -150,8 +202,9 @@ class Transformer(nn.Module):
     def _key(self, prec):
         return (prec, ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def block_table(self, prec: int):
-        key = self._key(prec)
+    def block_table(self, prec: int, ln16_fc: bool = True):
+        """ln16_fc (PREC_F32X6_LN16 only): c_fc's weight as fp16 planes too (False: a library built to keep c_fc six-product)"""
+        key = self._key(prec) + (bool(ln16_fc),)
         if self._cache is not None and self._cache[0] == key:
             return self._cache[1]
         arr = (L.BlockWeights * self.layers)()
@@ -164,12 +217,14 @@ class Transformer(nn.Module):
             w.out_proj_w, w.out_proj_b = b.attn.out_proj.weight.data_ptr(), b.attn.out_proj.bias.data_ptr()
             w.fc_w, w.fc_b = b.mlp.c_fc.weight.data_ptr(), b.mlp.c_fc.bias.data_ptr()
             w.proj_w, w.proj_b = b.mlp.c_proj.weight.data_ptr(), b.mlp.c_proj.bias.data_ptr()
-            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3):
+            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16):
                 for name, p in (("in_proj_w_bf16", b.attn.in_proj_weight), ("out_proj_w_bf16", b.attn.out_proj.weight),
                                 ("fc_w_bf16", b.mlp.c_fc.weight), ("proj_w_bf16", b.mlp.c_proj.weight)):
                     # bf16 mode: one rounded copy; f32x6: the three planes hi | mid | lo of the f32 weight, each in K-panel
                     # layout [K / 32][N][32] (ACX_BF16X3P: what acx_transformer_forward's bf16 x 6 products read)
-                    if prec == L.PREC_F16X3:            # two fp16 planes of 2^10 w (K-panel layout)
+                    # PREC_F32X6_LN16: fp16 planes for the LayerNorm-fed products, the six-product planes for the other two
+                    if prec == L.PREC_F16X3 or (prec == L.PREC_F32X6_LN16 and (name == "in_proj_w_bf16" or (name == "fc_w_bf16" and ln16_fc))):
+                        # two fp16 planes of 2^10 w (K-panel layout)
                         t = ops.split_f16x2(p.detach(), panel=True, scale=F16X3_WSCALE)
                     else:
                         t = ops.cast_bf16(p.detach()) if prec == L.PREC_BF16 else ops.split_bf16x3(p.detach(), panel=True)
@@ -228,6 +283,7 @@ class VisionTransformer(nn.Module):
         # graph now picks a stream that runs beside its caller's -- ops.side_stream_beside, profiles/r06_stream_queues.txt).
         self.streams = streams
         self._wcache = None
+        self._ln16 = None                                  # (key, (scales, ctypes array, c_fc on fp16 planes) or None): "auto"'s resolution
         self._ws: Optional[torch.Tensor] = None
         self._ws2: Optional[torch.Tensor] = None
         self._side = None
@@ -266,8 +322,32 @@ class VisionTransformer(nn.Module):
         margin = min(lim / max(v, 1e-30) for v in worst.values())
         return {"bounds": worst, "fp16_max": lim, "margin": margin, "safe": margin > 1.0}
 
-    def _weights(self, prec: int):
-        key = (prec, ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+    def _ln16_bound(self):
+        """(scales, their ctypes array, whether c_fc's weight is bound as fp16 planes) or None, cached with the weights"""
+        key = (ops.WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self._ln16 is not None and self._ln16[0] == key:
+            return self._ln16[1]
+        res = None
+        if self.width in (768, 1024) and self.layers > 1 and L.exports("acx_vit_encode_ln16"):
+            scales = ln16_scales(self.transformer.resblocks, self.width)
+            if scales is not None:
+                # c_fc's weight format is a constant of the library's build (a tools build may keep c_fc six-product): its plan says which
+                # (asked at a shape whose c_fc is a plane product whatever this model's geometry is)
+                fc16 = ops.transformer_plan(64, 197, 768, 12, 2, prec=L.PREC_F32X6_LN16, prune_last=True)[0]["ln2_dtype"] == L.F16X2P
+                res = (scales, (C.c_float * len(scales))(*scales), fc16)
+        self._ln16 = (key, res)
+        return res
+
+    def ln16_resolution(self) -> Optional[List[float]]:
+        """What precision "auto" resolves to for the weights as they are: the LayerNorm plane scales of ACX_PREC_F32X6_LN16 when the
+        width is one the fp16 LayerNorm store is built for (768, 1024: every CLIP ViT) and ln16_scales' proof passes; None = six
+        products everywhere (ACX_PREC_F32X6).  Which launches then read fp16 planes is the driver's per-product rule: the in-projection
+        and c_fc wherever they take the plane kernel (small launches and small test geometries stay as they are)."""
+        res = self._ln16_bound()
+        return None if res is None else res[0]
+
+    def _weights(self, prec: int, ln16_fc: bool = True):
+        key = (prec, bool(ln16_fc), ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._wcache is not None and self._wcache[0] == key:
             return self._wcache[1]
         keep = []
@@ -280,7 +360,7 @@ class VisionTransformer(nn.Module):
             cb, pb = ops.cast_bf16(conv), ops.cast_bf16(proj_t)
             keep += [cb, pb]
             w.conv1_w_bf16, w.proj_t_bf16 = cb.data_ptr(), pb.data_ptr()
-        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3) and self.patch_size % 4 == 0:
+        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16) and self.patch_size % 4 == 0:
             # the patch embedding as a bf16 x 6 product: the weight's three planes in K-panel layout (ACX_BF16X3P; a patch of 14,
             # K = 588, is not a whole number of 32-column panels: acx_vit_encode embeds it on the f32 kernels)
             cb = ops.split_f16x2(conv, panel=True, scale=F16X3_WSCALE) if prec == L.PREC_F16X3 else ops.split_bf16x3(conv, panel=True)
@@ -290,7 +370,7 @@ class VisionTransformer(nn.Module):
         w.positional_embedding = self.positional_embedding.data_ptr()
         w.ln_pre_w, w.ln_pre_b = self.ln_pre.weight.data_ptr(), self.ln_pre.bias.data_ptr()
         w.ln_post_w, w.ln_post_b = self.ln_post.weight.data_ptr(), self.ln_post.bias.data_ptr()
-        arr, keep2 = self.transformer.block_table(prec)
+        arr, keep2 = self.transformer.block_table(prec, ln16_fc)
         w.blocks = C.cast(arr, C.POINTER(L.BlockWeights))
         keep += [arr, keep2]
         self._wcache = (key, (w, keep))
@@ -303,8 +383,16 @@ class VisionTransformer(nn.Module):
         x = x.contiguous().float()
         prec = PRECISIONS[self.precision]
         lib = L.lib()
+        bound = self._ln16_bound() if self.precision == "auto" and x.is_cuda else None
+        ln16_fc = True
+        if bound is not None:
+            prec = L.PREC_F32X6_LN16
+            _scales, sc, ln16_fc = bound
+            encode = lambda *a: lib.acx_vit_encode_ln16(a[0], a[1], a[2], sc, *a[3:])
+        else:
+            encode = lib.acx_vit_encode
         d = L.VitDesc(self.input_resolution, self.patch_size, self.width, self.layers, self.heads, self.output_dim, prec)
-        w, _keep = self._weights(prec)
+        w, _keep = self._weights(prec, ln16_fc)
         F = x.shape[0]
         out = torch.empty(F, self.output_dim, dtype=torch.float32, device=x.device)
         chunk = min(self.chunk, F)
@@ -313,16 +401,15 @@ class VisionTransformer(nn.Module):
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         h = ops._h(x)
         if self.streams == 2 and chunk >= 32 and x.is_cuda:
-            return self._forward_two_streams(x, out, d, w, chunk, nbytes, h)
+            return self._forward_two_streams(x, out, d, w, chunk, nbytes, h, encode)
         s = ops._stream()
         for f0 in range(0, F, chunk):
             n = min(chunk, F - f0)
-            L.check(lib.acx_vit_encode(h, C.byref(d), C.byref(w), x[f0:f0 + n].data_ptr(), n, out[f0:f0 + n].data_ptr(),
-                                       self._ws.data_ptr(), self._ws.numel(), s), h)
+            L.check(encode(h, C.byref(d), C.byref(w), x[f0:f0 + n].data_ptr(), n, out[f0:f0 + n].data_ptr(),
+                           self._ws.data_ptr(), self._ws.numel(), s), h)
         return out
 
-    def _forward_two_streams(self, x, out, d, w, chunk, nbytes, h):
-        lib = L.lib()
+    def _forward_two_streams(self, x, out, d, w, chunk, nbytes, h, encode):
         F = x.shape[0]
         half = (chunk + 1) // 2
         if self._ws2 is None or self._ws2.numel() < nbytes or self._ws2.device != x.device:
@@ -339,8 +426,8 @@ class VisionTransformer(nn.Module):
             n = min(half, F - f0)
             st, ws = self._side[k % 2], wss[k % 2]
             with torch.cuda.stream(st):
-                L.check(lib.acx_vit_encode(h, C.byref(d), C.byref(w), x[f0:f0 + n].data_ptr(), n, out[f0:f0 + n].data_ptr(),
-                                           ws.data_ptr(), ws.numel(), st.cuda_stream), h)
+                L.check(encode(h, C.byref(d), C.byref(w), x[f0:f0 + n].data_ptr(), n, out[f0:f0 + n].data_ptr(),
+                               ws.data_ptr(), ws.numel(), st.cuda_stream), h)
             k += 1
         for st in self._side:
             cur.wait_stream(st)

@@ -10,6 +10,10 @@
 #define ACX_ATTN_F32IN_DEFAULT 1   // ACX_OPT_ATTN_F32IN as acx_create sets it (A/B builds of the other default: -DACX_ATTN_F32IN_DEFAULT=0)
 #endif
 
+#ifndef ACX_LN16_FC_DEFAULT
+#define ACX_LN16_FC_DEFAULT 1      // ACX_PREC_F32X6_LN16: c_fc on fp16 planes as well as the in-projection (the A/B build that measures the in-projection alone: 0)
+#endif
+
 #ifndef ACX_CLS_FOLD_DEFAULT
 #define ACX_CLS_FOLD_DEFAULT 1     // ACX_OPT_CLS_FOLD as acx_create sets it
 #endif
@@ -21,13 +25,14 @@ namespace {
 struct TfOpts {
   int x6_min_tiles;                              // ACX_OPT_X6_MIN_TILES
   bool attn_f32in, cls_fold;                     // ACX_OPT_ATTN_F32IN, ACX_OPT_CLS_FOLD
+  bool ln16_fc;                                  // ACX_LN16_FC_DEFAULT (a build constant)
 };
-constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0};
-constexpr TfOpts kNoCtxOpts = {512, false, false};   // a driver called with ctx == NULL
+constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0, ACX_LN16_FC_DEFAULT != 0};
+constexpr TfOpts kNoCtxOpts = {512, false, false, ACX_LN16_FC_DEFAULT != 0};   // a driver called with ctx == NULL
 // query: acx_transformer_plan, which answers for a context as acx_create leaves it when it has none (like the other route queries)
 inline TfOpts tf_opts(const acx_ctx* ctx, bool query) {
   if (!ctx) return query ? kCreateOpts : kNoCtxOpts;
-  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0};
+  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0, kCreateOpts.ln16_fc};
 }
 }  // namespace
 
@@ -208,7 +213,9 @@ struct TfWs {   // transformer scratch carved from the caller's workspace
 };
 
 // the plane modes of the drivers: ACX_PREC_F32X6 (six products: f32-accurate) and ACX_PREC_F32X3 (the three leading products)
-static inline bool is_xmode(int prec) { return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3; }
+static inline bool is_xmode(int prec) {
+  return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3 || prec == ACX_PREC_F32X6_LN16;
+}
 struct XMode {
   int pairs;                                     // acx_gemm_desc.pairs of the driver's plane products (and the attention's products)
   bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
@@ -272,6 +279,8 @@ struct Product {
   void* C; int c_dtype, ldc;
   void* scratch; size_t scratch_bytes;   // for a K split, free while the product runs
   const acx_ln_job* ln;        // plane kernel: the LayerNorm of the output rows follows (acx_gemm_ln: part of it rides in the last round)
+  float a_scale;               // plane kernel, ACX_PREC_F32X6_LN16: > 0 = A is the fp16 pair planes of a_scale * (LayerNorm output), Wb the fp16
+                               // pair planes of 2^10 w: three products, the accumulator leaves multiplied by 2^-10 / a_scale.  0: the mode's planes
 };
 
 struct TfMode {
@@ -301,8 +310,9 @@ acx_gemm_desc desc_of(const Product& p) {        // all of a descriptor but the 
 int run_x6(acx_ctx* ctx, XMode xm, const Product& p, hipStream_t s) {
   acx_gemm_desc d = desc_of(p);
   d.W = p.Wb;
+  if (p.a_scale > 0.f) xm = {3, true};
   d.a_dtype = xm.f16 ? ACX_F16 : ACX_BF16; d.prec = ACX_PREC_BF16; d.pairs = xm.pairs; d.panels = 3;
-  d.out_scale = xm.f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
+  d.out_scale = p.a_scale > 0.f ? 1.f / (ACX_F16X3_WSCALE * p.a_scale) : xm.f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
   d.a_plane_stride = (int64_t)p.M * p.lda * 2;
   d.w_plane_stride = p.w_plane_bytes ? p.w_plane_bytes : (int64_t)p.N * p.K * 2;
   // scratch for the K split of a partly filled last round of tiles (acx_gemm: row-major outputs only)
@@ -368,6 +378,7 @@ struct TfGeom {
 struct TfHave { bool f32[4], alt[4]; };   // in_proj, out_proj, fc, proj of every block: the f32 weight, the *_w_bf16 copy / planes
 struct TfPlan {
   TfMode mode;
+  bool ln16_qkv, ln16_fc;      // ACX_PREC_F32X6_LN16: the in-projection / c_fc of the body layers run on fp16 planes (ln_1 / ln_2 write them)
   acx_tf_layer_plan_t body, before_pruned, pruned;   // the three layer shapes (before_pruned: body with the pruned layer's ln_1 job)
   bool prune;
 };
@@ -401,6 +412,12 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   // ACX_PREC_F32X6: the LayerNorm behind a residual product (out-proj -> ln_2, c_proj -> the next layer's ln_1, K | V LayerNorm of the
   // pruned last layer included) is handed to the product (acx_gemm_ln: the idle workgroups of its last round of tiles run part of it)
   const bool ln_ride = m.pdt == ACX_BF16X3P;
+  // ACX_PREC_F32X6_LN16: the plane-kernel in-projection and (ACX_LN16_FC_DEFAULT) c_fc read fp16 pair planes -- their weights come in that
+  // format, so the rule is per product and holds for every geometry; everything else is the six-product plan below, record for record
+  const bool ln16 = g.prec == ACX_PREC_F32X6_LN16;
+  if (ln16 && W != 768 && W != 1024) return acx_fail(err, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F32X6_LN16 is built for widths 768 and 1024%s");
+  p->ln16_qkv = ln16 && x6_qkv;
+  p->ln16_fc = ln16 && x6_fc && o.ln16_fc;
   // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
   // QKV store traffic, bf16-MFMA attention, and a bf16 A operand (LDS-DMA kernels) for the out-projection
   const bool ab = m.prec == ACX_PREC_BF16 && !g.causal && L <= 224 && ACX_DBG_SWITCH("ATTN_BF16", true);
@@ -440,7 +457,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   // ws.mlp where the product writes the planes of that buffer's contents)
   acx_tf_layer_plan_t& b = p->body;
   b.ln1 = !x6_qkv ? ACX_TF_LN_ROWS : ln_ride && x6_proj ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
-  b.ln1_dtype = x6_qkv ? m.pdt : m.hdt;
+  b.ln1_dtype = p->ln16_qkv ? ACX_F16X2P : x6_qkv ? m.pdt : m.hdt;
   b.in_proj = !x6_qkv ? tf_rows(ab ? ACX_BF16 : ACX_F32, ACX_TF_BUF_SPLITK)
                       : qkv_planes ? tf_x6(cpl, ACX_TF_BUF_QKV, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
   b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
@@ -448,7 +465,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   b.split_att = x6_out && !att_x3 && !att_p3;
   b.out_proj = x6_out ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_fc) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
   b.ln2 = !x6_fc ? ACX_TF_LN_ROWS : b.out_proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
-  b.ln2_dtype = x6_fc ? m.pdt : m.hdt;
+  b.ln2_dtype = p->ln16_fc ? ACX_F16X2P : x6_fc ? m.pdt : m.hdt;
   // QuickGELU(c_fc) straight into the planes of c_proj's input when c_proj takes the plane kernel too
   b.fc = !x6_fc ? tf_rows(m.hdt, ACX_TF_BUF_SPLITK) : x6_proj ? tf_x6(cpl, ACX_TF_BUF_MLP, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
   b.split_mlp = x6_proj && !x6_fc;
@@ -462,7 +479,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   acx_tf_layer_plan_t& c = p->pruned;
   c.pruned = 1;
   c.ln1 = cls_fold ? ACX_TF_LN_CLS : !kv_planes ? ACX_TF_LN_ROWS : p->before_pruned.proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
-  c.ln1_dtype = kv_planes ? m.pdt : m.hdt;
+  c.ln1_dtype = kv_planes ? (p->ln16_qkv ? ACX_F16X2P : m.pdt) : m.hdt;
   c.in_proj = kv_planes ? tf_x6(ACX_F32, ACX_TF_BUF_NONE, false) : tf_rows(ACX_F32, ACX_TF_BUF_NONE);
   c.att = cls_fold ? ACX_TF_ATT_CLS_FOLD : ACX_TF_ATT_CLS;
   c.out_proj = c.proj = tf_rows(ACX_F32, ACX_TF_BUF_NONE);
@@ -487,7 +504,10 @@ int tf_plan_call(acx_ctx* ctx, const TfGeom& g, const acx_block_weights* blk, Tf
 // ---- the executor: walks the layers and launches what the records say ----------------------------------------------------------
 struct TfRun {
   acx_ctx* ctx; const TfGeom& g; const TfMode& m; const TfWs& ws; hipStream_t s;
+  const float* ln_scales;      // ACX_PREC_F32X6_LN16: [2 layers] plane scales of ln_1, ln_2 (host)
   int64_t rows() const { return (int64_t)g.batch * g.L; }
+  // the scale of LayerNorm `which` (0 ln_1, 1 ln_2) of layer l where it writes ACX_PREC_F32X6_LN16's fp16 planes, else 0
+  float lnsc(int dtype, int l, int which) const { return g.prec == ACX_PREC_F32X6_LN16 && dtype == ACX_F16X2P ? ln_scales[2 * l + which] : 0.f; }
 
   // product i (0 in_proj, 1 out_proj, 2 fc, 3 proj) of block b on M rows, run as r says; A, C and residual are the caller's to set
   Product product(const acx_block_weights& b, int i, const acx_tf_product_t& r, int64_t M) const {
@@ -512,23 +532,30 @@ struct TfRun {
     }
     return p;
   }
-  int norm(const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int dtype, int64_t n) const {
+  int norm(const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t ldy, int dtype, int64_t n, float sc = 0.f) const {
+    if (sc > 0.f) return acx_layernorm_rows(ctx, x, ldx, w, b, y, dtype, sc, n, 0, g.W, 1e-5f, ACX_NORM_LAYER, s);   // fp16 planes of sc * y
     return acx_layernorm(ctx, x, ldx, w, b, y, ldy, dtype, n, g.W, 1e-5f, ACX_NORM_LAYER, s);
   }
   // ln_1 / ln_2 of all rows: to ws.h, to the planes of ws.hp, or already run behind the previous residual product
-  int norm_all(int kind, int dtype, const float* x, const float* w, const float* b) const {
+  int norm_all(int kind, int dtype, const float* x, const float* w, const float* b, float sc) const {
     if (kind == ACX_TF_LN_RIDDEN) return ACX_OK;
-    return norm(x, g.W, w, b, kind == ACX_TF_LN_PLANES ? ws.hp : ws.h, g.W, dtype, rows());
+    return norm(x, g.W, w, b, kind == ACX_TF_LN_PLANES ? ws.hp : ws.h, g.W, dtype, rows(), kind == ACX_TF_LN_PLANES ? sc : 0.f);
   }
-  acx_ln_job job(const float* w, const float* b) const { return {w, b, ws.hp, m.pdt, 1e-5f, ACX_NORM_LAYER}; }
+  // the LayerNorm a residual product carries: the planes of the mode, or (sc > 0) ACX_PREC_F32X6_LN16's fp16 planes of sc * y
+  acx_ln_job job(const float* w, const float* b, float sc = 0.f) const {
+    return {w, b, ws.hp, sc > 0.f ? ACX_F16X2P : m.pdt, 1e-5f, ACX_NORM_LAYER, sc};
+  }
   int go(const Product& p) const { return run(ctx, m, p, s); }
 
-  int body(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const acx_block_weights* next, float* x) const {
+  // l: the layer; next_ln1_dtype: what the NEXT layer's ln_1 writes (the job c_proj carries)
+  int body(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const acx_block_weights* next, float* x, int l, int next_ln1_dtype) const {
     const int W = g.W, batch = g.batch, L = g.L, heads = g.heads;
     auto planes = [](const acx_tf_product_t& q) { return q.c_dtype != ACX_F32 && q.c_dtype != ACX_BF16; };
+    const float sc1 = lnsc(r.ln1_dtype, l, 0), sc2 = lnsc(r.ln2_dtype, l, 1);
     int rc;
-    if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b))) return rc;
+    if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b, sc1))) return rc;
     Product p = product(b, 0, r.in_proj, rows());
+    p.a_scale = r.in_proj.kernel == ACX_TF_GEMM_X6 ? sc1 : 0.f;
     p.A = r.in_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
     p.C = planes(r.in_proj) ? ws.qkv3 : ws.qkv;
     if ((rc = go(p))) return rc;
@@ -541,20 +568,21 @@ struct TfRun {
     }
     if (rc) return rc;
     if (r.split_att && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.att, W, ws.hp, rows() * W * 2, rows(), W, s))) return rc;
-    const acx_ln_job ln2 = job(b.ln2_w, b.ln2_b);   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
+    const acx_ln_job ln2 = job(b.ln2_w, b.ln2_b, sc2);   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
     p = product(b, 1, r.out_proj, rows());
     p.A = r.out_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.att;
     p.a_dtype = r.att == ACX_TF_ATT_BF16 ? ACX_BF16 : ACX_F32;
     p.C = x; p.residual = x;
     p.ln = r.out_proj.ln_job ? &ln2 : nullptr;
     if ((rc = go(p))) return rc;
-    if ((rc = norm_all(r.ln2, r.ln2_dtype, x, b.ln2_w, b.ln2_b))) return rc;
+    if ((rc = norm_all(r.ln2, r.ln2_dtype, x, b.ln2_w, b.ln2_b, sc2))) return rc;
     p = product(b, 2, r.fc, rows());
+    p.a_scale = r.fc.kernel == ACX_TF_GEMM_X6 ? sc2 : 0.f;
     p.A = r.fc.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
     p.C = planes(r.fc) ? ws.mp : ws.mlp;
     if ((rc = go(p))) return rc;
     if (r.split_mlp && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, rows() * 4 * W * 2, rows(), 4 * W, s))) return rc;
-    const acx_ln_job ln1 = r.proj.ln_job ? job(next->ln1_w, next->ln1_b) : job(nullptr, nullptr);
+    const acx_ln_job ln1 = r.proj.ln_job ? job(next->ln1_w, next->ln1_b, lnsc(next_ln1_dtype, l + 1, 0)) : job(nullptr, nullptr);
     p = product(b, 3, r.proj, rows());
     p.A = r.proj.kernel == ACX_TF_GEMM_X6 ? ws.mp : ws.mlp;
     p.C = x; p.residual = x;
@@ -563,8 +591,9 @@ struct TfRun {
   }
 
   // the final residual stream of the CLS tokens is left COMPACT in c.xc instead of x
-  int pruned(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const float* x, const ClsWs& c) const {
+  int pruned(const acx_tf_layer_plan_t& r, const acx_block_weights& b, const float* x, const ClsWs& c, int l) const {
     const int W = g.W, batch = g.batch, L = g.L;
+    const float sc1 = lnsc(r.ln1_dtype, l, 0);     // (the K | V product on the plane kernel reads the in-projection's fp16 planes)
     int rc;
     Product p = product(b, 0, r.in_proj, rows());
     if (r.att == ACX_TF_ATT_CLS_FOLD) {
@@ -579,12 +608,12 @@ struct TfRun {
     } else {
       // K | V for every token: rows [W, 3W) of in_proj.  On the plane kernel LayerNorm writes the product's planes (all rows) and the
       // f32 rows of the CLS tokens (Q below reads only those)
-      if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b))) return rc;
+      if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b, sc1))) return rc;
       p.N = 2 * W; p.bias = b.in_proj_b + W;
       p.C = (float*)ws.qkv + W; p.ldc = 3 * W;
       if (r.in_proj.kernel == ACX_TF_GEMM_X6) {
         if ((rc = norm(x, (int64_t)L * W, b.ln1_w, b.ln1_b, ws.h, (int64_t)L * W, m.hdt, batch))) return rc;
-        p.A = ws.hp;
+        p.A = ws.hp; p.a_scale = sc1;
         p.Wb = (const char*)b.in_proj_w_bf16 + (size_t)W * 64;   // row W of every K-panel
         p.w_plane_bytes = (int64_t)3 * W * W * 2;
       } else {
@@ -618,12 +647,22 @@ struct TfRun {
 };
 
 int transformer_layers(acx_ctx* ctx, float* x, const TfGeom& g, const TfPlan& plan, const acx_block_weights* blk, const TfWs& ws,
-                       hipStream_t s, float* cls_ws = nullptr) {
-  const TfRun exec = {ctx, g, plan.mode, ws, s};
+                       hipStream_t s, float* cls_ws = nullptr, const float* ln_scales = nullptr) {
+  if (g.prec == ACX_PREC_F32X6_LN16) {
+    if (!ln_scales) return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_LN16 needs the LayerNorm plane scales (acx_vit_encode_ln16)%s");
+    for (int i = 0; i < 2 * g.layers; ++i) {
+      int e = 0;
+      const float sc = ln_scales[i];
+      if (!(sc >= 0x1p-20f && sc <= 0x1p20f) || frexpf(sc, &e) != 0.5f)
+        return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_LN16: a LayerNorm plane scale is not a power of two in [2^-20, 2^20]%s");
+    }
+  }
+  const TfRun exec = {ctx, g, plan.mode, ws, s, ln_scales};
   for (int l = 0; l < g.layers; ++l) {
     const acx_tf_layer_plan_t r = tf_layer(plan, l, g.layers);
-    const int rc = r.pruned ? exec.pruned(r, blk[l], x, carve_cls(cls_ws, g.batch, g.W))
-                            : exec.body(r, blk[l], l + 1 < g.layers ? &blk[l + 1] : nullptr, x);
+    const int next_ln1 = l + 1 < g.layers ? tf_layer(plan, l + 1, g.layers).ln1_dtype : 0;
+    const int rc = r.pruned ? exec.pruned(r, blk[l], x, carve_cls(cls_ws, g.batch, g.W), l)
+                            : exec.body(r, blk[l], l + 1 < g.layers ? &blk[l + 1] : nullptr, x, l, next_ln1);
     if (rc) return rc;
   }
   return ACX_OK;
@@ -696,9 +735,11 @@ extern "C" size_t acx_vit_workspace_bytes(const acx_vit_desc* d, int32_t frames)
   return carve_vit(nullptr, d, frames).total;
 }
 
-extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* frames,
-                              int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
+static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* ln_scales, const float* frames,
+                      int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d || !w || !frames || !features || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: null pointer%s");
+  if (d->prec == ACX_PREC_F32X6_LN16 && !ln_scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_LN16 needs the LayerNorm plane scales (acx_vit_encode_ln16)%s");
   if (nframes <= 0) return ACX_OK;
   if (d->width != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64%s");
   if (d->patch <= 0 || d->resolution % d->patch || d->patch % 2)
@@ -740,7 +781,7 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
   // CLS + positional embedding + ln_pre                                :270-279
   if ((rc = acx_vit_embed(ctx, (const float*)ws.patch_out, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                           w->ln_pre_b, (float*)ws.x, F, T, W, s))) return rc;
-  if ((rc = transformer_layers(ctx, (float*)ws.x, geom, plan, w->blocks, tf, s, (float*)ws.cls_ws))) return rc;
+  if ((rc = transformer_layers(ctx, (float*)ws.x, geom, plan, w->blocks, tf, s, (float*)ws.cls_ws, ln_scales))) return rc;
   // ln_post on the CLS rows, then @ proj                                :285-288
   if ((rc = acx_layernorm(ctx, prune ? (const float*)ws.cls_ws : (const float*)ws.x, prune ? (int64_t)W : (int64_t)(T + 1) * W,
                           w->ln_post_w, w->ln_post_b, ws.cls, W, ACX_F32, F, W, 1e-5f, ACX_NORM_LAYER, s))) return rc;
@@ -752,3 +793,15 @@ extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit
   return run_rows(ctx, m.prec, p, s);
 }
 
+
+extern "C" int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* frames,
+                              int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
+  return vit_encode(ctx, d, w, nullptr, frames, nframes, features, workspace, workspace_bytes, stream);
+}
+
+extern "C" int acx_vit_encode_ln16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* ln_scales, const float* frames,
+                                   int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!d || d->prec != ACX_PREC_F32X6_LN16 || !ln_scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode_ln16: needs desc->prec = ACX_PREC_F32X6_LN16 and the LayerNorm plane scales%s");
+  return vit_encode(ctx, d, w, ln_scales, frames, nframes, features, workspace, workspace_bytes, stream);
+}

@@ -468,6 +468,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
 #include "acx_gemm_x6.h"     // gemm_x6_p4_kernel: pairs = 6 products, one wave per SIMD, plane-reuse schedule
 #define X6_KERNEL gemm_x6_rn_kernel
 #include "acx_gemm_x6.h"     // gemm_x6_rn_kernel: the same text, the ResNet encoder's instantiations (ReLU epilogues, general conv map)
+#define X6_KERNEL gemm_x6_h3_kernel
+#define X6_F16_C_BF16X3 1
+#include "acx_gemm_x6.h"     // gemm_x6_h3_kernel: fp16 operand planes, three products, THREE bf16 output planes (ACX_PREC_F32X6_LN16's c_fc)
 #include "acx_gemm_tn.h"     // gemm_tn_kernel, gemm_tn_w8_kernel, tn_reduce_kernel
 
 template <int C_BF16>
@@ -1031,6 +1034,13 @@ template <int CM, int ACT, int RES, int CV, int NI>
 static void x6_launch(const GemmCall& c, dim3 grid, const Args& g) {
   if constexpr (CV == 0 && CM != 1 && ACT < 2) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual)
     if (c.d->pairs == 3) {                        // the three leading products only (acx_gemm_x6.h, X3); fp16 planes: X3 = 2
+      if constexpr (CM == 2) {                    // fp16 operands, bf16 x 3 output planes: the instantiations of gemm_x6_h3_kernel
+        static_assert(RES == 0, "plane outputs carry no residual (route_x6 refuses them)");
+        if (c.a_f16 && c.d->c_dtype == ACX_BF16X3P) {
+          acx_launch_lds<gemm_x6_h3_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          return;
+        }
+      }
       if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       else acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       return;
@@ -1085,8 +1095,8 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   if (x3 && (conv || c_bf16 || d->act == ACX_ACT_LEAKYRELU || c.relu_act))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: pairs = 3 takes identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues%s");
   const bool c_x3_ = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
-  if (c.a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P)
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: fp16 operand planes write fp16 output planes (ACX_F16X2P)%s");
+  if (c.a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P && d->c_dtype != ACX_BF16X3P)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: fp16 operand planes write fp16 output planes (ACX_F16X2P) or K-panel bf16 planes (ACX_BF16X3P)%s");
   const bool shape_ok = x6_operands_ok(c) &&
       d->lda % 8 == 0 && d->ldw % 8 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
       !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && d->a_plane_stride > 0 && d->w_plane_stride > 0 &&
@@ -1113,15 +1123,17 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   // narrow convolution outputs (N <= 128: c2 and the input gradient of c1 in the XD-Violence head, E = 128): 256 x 128 tiles
   // (the NI = 2 instantiation) instead of half-empty 256 x 256 ones; f32 outputs without an activation only (what the head asks for)
   in.narrow = conv && !conv_any && d->N <= 128 && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE;
-  // (no reduce launch writes fp16 planes: such launches keep whole K per tile; neither do the ResNet encoder's products -- the ReLU
+  // (no reduce launch writes fp16 planes: launches with ACX_F16X2P output keep whole K per tile -- fp16 operands with f32 or bf16 x 3 plane output split like
+  // the family: the raw partials carry out_scale; neither do the ResNet encoder's products -- the ReLU
   // epilogues and the general convolution map -- split: every row of theirs sums K in one order whatever the launch's size)
-  in.may_split = d->workspace && !(c.a_f16 && c_x3_) && x6_may_split(c);
+  in.may_split = d->workspace && !(c.a_f16 && d->c_dtype == ACX_F16X2P) && x6_may_split(c);
   in.workspace_bytes = d->workspace_bytes;
   in.may_strip = !conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && !c.relu_act && x6_strip_enabled(ctx);
   in.strip_force = ctx ? ctx->opt_x6_strip : 1;
   in.tail_split_opt = ctx && ctx->opt_x6_tail;
   in.may_ride = job && ridden && !conv && !x3 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
-      (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && job->y_dtype == ACX_BF16X3P && job->w && job->b && job->y &&
+      (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && (job->y_dtype == ACX_BF16X3P || job->y_dtype == ACX_F16X2P) &&
+      job->w && job->b && job->y &&
       !((uintptr_t)job->y & 15) && !(((long long)d->M * d->N * 2) & 15) && ACX_DBG_SWITCH("LN_RIDER", true) && ctx && ctx->opt_ln_rider;
   in.ride_cap = ctx ? ctx->opt_ln_rider : 0;
   in.rate = 0.0;
@@ -1134,6 +1146,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
     g.ln.x = (const float*)d->C; g.ln.w = job->w; g.ln.b = job->b; g.ln.y = (u16*)job->y;
     g.ln.ldx = d->ldc; g.ln.rows = d->M; g.ln.row0 = 0; g.ln.nrows = p.ride;
     g.ln.eps = job->eps; g.ln.mode = job->mode; g.ln.vpl = d->N / 64;
+    g.ln.f16 = job->y_dtype == ACX_F16X2P; g.ln.ysc = job->y_scale != 0.f ? job->y_scale : 1.f;   // (fp16 pair planes of ysc * y)
     *ridden = p.ride;
   }
   if (p.strip_ni < 4) g.ntiles = p.tile0_tail;          // (tile0 = 0) the full rounds only
@@ -1161,7 +1174,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
 }
 
 // Scratch of this route's K split (acx_gemm_scratch): fewer tiles than workgroups -- two partial images per idle round the split
-// can fill, 2 to X6_SPLIT_PIECES_MAX.  Looser than the route: fp16 operand planes with plane outputs never split (X6PlanIn.may_split).
+// can fill, 2 to X6_SPLIT_PIECES_MAX.  Looser than the route: fp16 operand planes with fp16 plane outputs (ACX_F16X2P) never split (X6PlanIn.may_split).
 static size_t x6_split_scratch_bytes(const GemmCall& c) {
   const acx_gemm_desc* d = c.d;
   const int ncu = c.ncu_x6, xt = ((d->M + 255) / 256) * ((d->N + 255) / 256);
@@ -1535,7 +1548,10 @@ extern "C" int acx_gemm_ln(acx_ctx* ctx, const acx_gemm_desc* d, const acx_ln_jo
   int rc = gemm_impl(ctx, d, stream, job, &ridden);
   if (rc) return rc;
   if (ridden > 0)
-    return acx_layernorm_rows(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, d->M, ridden, d->N, job->eps, job->mode, stream);
+    return acx_layernorm_rows(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, job->y_dtype, job->y_scale, d->M, ridden, d->N, job->eps,
+                              job->mode, stream);
+  if (job->y_dtype == ACX_F16X2P)
+    return acx_layernorm_rows(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, ACX_F16X2P, job->y_scale, d->M, 0, d->N, job->eps, job->mode, stream);
   return acx_layernorm(ctx, (const float*)d->C, d->ldc, job->w, job->b, job->y, d->N, job->y_dtype, d->M, d->N, job->eps, job->mode, stream);
 }
 

@@ -139,6 +139,12 @@ __device__ __forceinline__ T& x6_sel(T& a, T& b) {
 #ifndef X6_KERNEL
 #define X6_KERNEL gemm_x6_p4_kernel
 #endif
+// X6_F16_C_BF16X3 (a switch of the inclusion, like the name): 1 = the plane output (C_MODE = 2) of the fp16 three-product form (X3 = 2)
+// is the THREE bf16 planes of the f32 value (ACX_BF16X3P) instead of fp16 pairs -- gemm_x6_h3_kernel: c_fc of ACX_PREC_F32X6_LN16, whose
+// consumer c_proj is a six-product GEMM of bf16 planes.  0: every instantiation compiles to what it was.
+#ifndef X6_F16_C_BF16X3
+#define X6_F16_C_BF16X3 0
+#endif
 template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0, int RIDE = 0>
 __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
   static_assert(X3 == 0 || (CONV == 0 && TN == 0 && PLAIN == 0 && W14 == 0), "three-product mode: identity rows, NT");
@@ -817,7 +823,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
         /* three bf16 planes hi | mid | lo of the f32 value (ACX_BF16X3): the next pairs = 6 product's A operand */ \
         uint4 ph, pm, pl;                                                                          \
         float r1[8], r2[8];                                                                        \
-        constexpr int PF_ = (X3 == 2);             /* plane format: bf16 triples, or fp16 pairs (X3 = 2) */ \
+        constexpr int PF_ = (X3 == 2) && !(X6_F16_C_BF16X3);   /* plane format: bf16 triples, or fp16 pairs (X3 = 2) */ \
         ph.x = acx_pk2<PF_>(ov[0], ov[1]); ph.y = acx_pk2<PF_>(ov[2], ov[3]); ph.z = acx_pk2<PF_>(ov[4], ov[5]); ph.w = acx_pk2<PF_>(ov[6], ov[7]); \
         const unsigned hw_[4] = {ph.x, ph.y, ph.z, ph.w};                                          \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
@@ -837,7 +843,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
           u16* dst = (u16*)d.C + (cpanel ? ((size_t)(colq >> 5) * crows_ + row) * 32 + (colq & 31) : (size_t)row * d.ldc + colq); \
           __builtin_nontemporal_store(*reinterpret_cast<const u32x4_*>(&ph), reinterpret_cast<u32x4_*>(dst)); \
           __builtin_nontemporal_store(*reinterpret_cast<const u32x4_*>(&pm), reinterpret_cast<u32x4_*>(dst + pe)); \
-          if constexpr (X3 == 0)   /* (three-product mode: the consumer never reads the lo plane) */   \
+          if constexpr (X3 == 0 || (X6_F16_C_BF16X3))   /* (three-product mode: the consumer never reads the lo plane) */   \
           __builtin_nontemporal_store(*reinterpret_cast<const u32x4_*>(&pl), reinterpret_cast<u32x4_*>(dst + 2 * pe)); \
         }                                                                                          \
       }                                                                                            \
@@ -954,3 +960,4 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
 #undef X6_SET_ITEM
 }
 #undef X6_KERNEL
+#undef X6_F16_C_BF16X3

@@ -139,9 +139,10 @@ static inline void acx_launch_lds(int dev_slot, dim3 grid, dim3 block, size_t ld
 
 // acx_gemm.hip: true when acx_gemm runs `d` on the persistent strip-stream kernel (no partial last wave to split off)
 bool acx_gemm_takes_strip_stream(const acx_gemm_desc* d);
-// acx_norm.hip: LayerNorm of rows row0 .. rows (row0 even) into ACX_BF16X3P planes of `rows` rows -- what acx_gemm_ln's riders left
-int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
-                       int64_t row0, int32_t D, float eps, int32_t mode, void* stream);
+// acx_norm.hip: LayerNorm of rows row0 .. rows (row0 even) into ACX_BF16X3P planes of `rows` rows (or ACX_F16X2P planes of y_scale * y)
+// -- what acx_gemm_ln's riders left
+int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int32_t y_dtype, float y_scale,
+                       int64_t rows, int64_t row0, int32_t D, float eps, int32_t mode, void* stream);
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -39,11 +39,12 @@ __device__ __forceinline__ void ln_load_affine(const float* __restrict__ w, cons
 // with the same eight of row r0 + 1 -- so that eight lanes write the 128 contiguous bytes the two rows occupy in a panel with
 // 16-byte stores.  `rows` is the plane's TOTAL row count (element e of row r at ((e / 32) rows + r) 32 + e % 32, plane p at
 // y + p rows 64 VPL); two = false: row r0 + 1 does not exist (vb is a copy of va, nothing is stored for it).
-// TWO (ACX_BF16X2P): the hi and mid planes only;  F16 (ACX_F16X2P): two fp16 planes hi | lo instead of bf16 planes
+// TWO (ACX_BF16X2P): the hi and mid planes only;  F16 (ACX_F16X2P): two fp16 planes hi | lo instead of bf16 planes -- of sc * y,
+// sc a power of two (exact: the caller's proof that sc * y stays inside fp16's range; the bf16 planes do not read sc)
 template <int VPL, bool TWO, bool F16>
 __device__ __forceinline__ void ln_panel2_store(const float (&va)[VPL], const float (&vb)[VPL], const float4 (&wv)[VPL / 4],
                                                 const float4 (&bv)[VPL / 4], u16* __restrict__ y, int64_t rows, int64_t r0, bool two,
-                                                int lane) {
+                                                int lane, float sc = 1.f) {
   const int64_t plane = rows * (int64_t)(64 * VPL);
   const int odd = lane & 1;
 #pragma unroll
@@ -63,6 +64,8 @@ __device__ __forceinline__ void ln_panel2_store(const float (&va)[VPL], const fl
     }
     u16 hh[8], mm[8], ll[8];
     if constexpr (F16) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o8[k] *= sc;
 #pragma unroll
       for (int k = 0; k < 8; k += 2) {
         const uint32_t ph_ = f2h2(o8[k], o8[k + 1]);
@@ -94,13 +97,15 @@ __device__ __forceinline__ void ln_panel2_store(const float (&va)[VPL], const fl
 }
 
 // The LayerNorm job a pairs = 6 product carries for the workgroups of its last round that have no tile (acx_gemm_ln): rows
-// row0 .. row0 + nrows (both even) of x [*, 64 VPL] -> ACX_BF16X3P planes y of `rows` rows.
+// row0 .. row0 + nrows (both even) of x [*, 64 VPL] -> ACX_BF16X3P planes y of `rows` rows, or (f16 != 0) the two ACX_F16X2P
+// planes of ysc * y.
 struct LnRide {
   const float* x; const float* w; const float* b;
   u16* y;
   long long ldx, rows, row0, nrows;
   float eps;
   int mode, vpl;
+  float ysc; int f16;
 };
 
 // One rider workgroup (4 waves; ordinal `rider` of `nriders`): the job's row PAIRS are divided into contiguous ranges, one per
@@ -130,7 +135,8 @@ __device__ __forceinline__ void ln_ride_rows(const LnRide& j, int rider, int nri
       if (p + u < p1) {
         normalize<VPL>(cur[u][0], j.eps, j.mode);
         normalize<VPL>(cur[u][1], j.eps, j.mode);
-        ln_panel2_store<VPL, false, false>(cur[u][0], cur[u][1], ww, bb, j.y, j.rows, j.row0 + 2 * (p + u), true, lane);
+        if (j.f16) ln_panel2_store<VPL, true, true>(cur[u][0], cur[u][1], ww, bb, j.y, j.rows, j.row0 + 2 * (p + u), true, lane, j.ysc);
+        else ln_panel2_store<VPL, false, false>(cur[u][0], cur[u][1], ww, bb, j.y, j.rows, j.row0 + 2 * (p + u), true, lane);
       }
     }
 #pragma unroll

@@ -90,11 +90,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // halves -- the even lane of a pair ends up with eight consecutive elements of row r, the odd lane with the same eight of row r + 1
 // -- so that eight lanes write the 128 contiguous bytes rows r, r + 1 occupy in a panel with 16-byte stores.  Same arithmetic.
 // TWO (ACX_BF16X2P): the hi and mid planes only (the lo plane is left untouched: a pairs = 3 product does not read it)
-// F16 (ACX_F16X2P): two fp16 planes hi | lo (hi = fp16(y), lo = fp16(y - hi)) instead of bf16 planes
+// F16 (ACX_F16X2P): two fp16 planes hi | lo (hi = fp16(sc y), lo = fp16(sc y - hi)) instead of bf16 planes; sc: a power of two
 template <int VPL, bool TWO = false, bool F16 = false>
 __global__ __launch_bounds__(256) void layernorm_panel2_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                                const float* __restrict__ b, u16* __restrict__ y, int64_t rows,
-                                                               float eps, int mode, int64_t row0) {
+                                                               float eps, int mode, int64_t row0, float sc) {
   static_assert(VPL % 4 == 0, "16-byte row loads");
   // row0 (even): the launch covers rows row0 .. rows of the planes (acx_gemm_ln: the rows before it rode in the product's last round)
   const int lane = threadIdx.x & 63;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void layernorm_panel2_kernel(const float* __re
   normalize<VPL>(vb, eps, mode);
   float4 ww[VPL / 4], bb[VPL / 4];
   ln_load_affine<VPL>(w, b, lane, ww, bb);
-  ln_panel2_store<VPL, TWO, F16>(va, vb, ww, bb, y, rows, r0, two, lane);
+  ln_panel2_store<VPL, TWO, F16>(va, vb, ww, bb, y, rows, r0, two, lane, sc);
 }
 
 template <int VPL>
@@ -193,19 +193,21 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__
 // row0 > 0 (acx_layernorm_rows; even, K-panel bf16 x 3 planes on the two-rows-per-wave kernel only): rows row0 .. rows
 static int layernorm_impl(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
                           void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
-                          int32_t mode, void* stream, int64_t row0) {
+                          int32_t mode, void* stream, int64_t row0, float y_scale = 1.f) {
   if (!x || !w || !b || !y) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm: null pointer%s");
   if (rows <= 0 || row0 >= rows) return ACX_OK;
-  if (row0 && (row0 < 0 || (row0 & 1) || y_dtype != ACX_BF16X3P || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15)))
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm_rows: an even first row, ACX_BF16X3P planes with 16-byte aligned planes%s");
+  if (row0 && (row0 < 0 || (row0 & 1) || (y_dtype != ACX_BF16X3P && y_dtype != ACX_F16X2P) || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15)))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm_rows: an even first row, ACX_BF16X3P or ACX_F16X2P planes, 16-byte aligned%s");
   if (D % 64 || ldx % 4 || ldy % 4) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm: D%%64 / ld%%4%s");
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_NORM, s);
-  if (y_dtype == ACX_F16X2P) {         // two fp16 planes in K-panel layout (the ViT width only: the ACX_PREC_F16X3 driver)
-    if (ldy != D || D != 768 || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15))
-      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_F16X2P needs ldy == D == 768 and 16-byte aligned planes%s");
-    layernorm_panel2_kernel<12, true, true><<<dim3((unsigned)((rows + 7) / 8)), block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, (int64_t)0);
+  if (y_dtype == ACX_F16X2P) {         // two fp16 planes in K-panel layout (the ViT widths: the ACX_PREC_F16X3 / ACX_PREC_F32X6_LN16 drivers)
+    if (ldy != D || (D != 768 && D != 1024) || ((uintptr_t)y & 15) || ((rows * (int64_t)D * 2) & 15))
+      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_F16X2P needs ldy == D == 768 or 1024 and 16-byte aligned planes%s");
+    const dim3 grid2((unsigned)((rows - row0 + 7) / 8));
+    if (D == 768) layernorm_panel2_kernel<12, true, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, y_scale);
+    else layernorm_panel2_kernel<16, true, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, y_scale);
     ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
     return ACX_OK;
   }
@@ -214,15 +216,15 @@ static int layernorm_impl(acx_ctx* ctx, const float* x, int64_t ldx, const float
     if (!((uintptr_t)y & 15) && !((rows * (int64_t)D * 2) & 15)) {                // 16-byte stores: two rows per wave
       const dim3 grid2((unsigned)((rows - row0 + 7) / 8));
       if (y_dtype == ACX_BF16X2P && D == 768) {                                   // (hi and mid planes only: the ViT width)
-        layernorm_panel2_kernel<12, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, (int64_t)0);
+        layernorm_panel2_kernel<12, true><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, (int64_t)0, 1.f);
         ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
         return ACX_OK;
       }
       switch (D / 64) {
-        case 4: layernorm_panel2_kernel<4><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
-        case 8: layernorm_panel2_kernel<8><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
-        case 12: layernorm_panel2_kernel<12><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
-        case 16: layernorm_panel2_kernel<16><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0); break;
+        case 4: layernorm_panel2_kernel<4><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
+        case 8: layernorm_panel2_kernel<8><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
+        case 12: layernorm_panel2_kernel<12><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
+        case 16: layernorm_panel2_kernel<16><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
         default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_BF16X3P needs D in {256, 512, 768, 1024}%s");
       }
     } else
@@ -244,10 +246,20 @@ extern "C" int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const fl
   return layernorm_impl(ctx, x, ldx, w, b, y, ldy, y_dtype, rows, D, eps, mode, stream, 0);
 }
 
-// acx_gemm_ln's remainder: the LayerNorm of rows row0 .. rows into ACX_BF16X3P planes of `rows` rows (acx_internal.h)
-int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
-                       int64_t row0, int32_t D, float eps, int32_t mode, void* stream) {
-  return layernorm_impl(ctx, x, ldx, w, b, y, D, ACX_BF16X3P, rows, D, eps, mode, stream, row0);
+// a power of two (or 0: 1) as the F16X2P planes' scale
+static inline bool ln_scale_ok(float s) { int e; return s == 0.f || (s > 0.f && s <= 3.4e38f && frexpf(s, &e) == 0.5f); }
+
+extern "C" int acx_layernorm_scaled(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
+                                    int32_t D, float eps, int32_t mode, float y_scale, void* stream) {
+  if (!ln_scale_ok(y_scale)) return acx_fail(ctx, ACX_E_BADARG, "acx_layernorm_scaled: y_scale must be a power of two%s");
+  return layernorm_impl(ctx, x, ldx, w, b, y, D, ACX_F16X2P, rows, D, eps, mode, stream, 0, y_scale != 0.f ? y_scale : 1.f);
+}
+
+// acx_gemm_ln's remainder: the LayerNorm of rows row0 .. rows into ACX_BF16X3P planes of `rows` rows, or ACX_F16X2P planes of
+// y_scale * y (acx_internal.h)
+int acx_layernorm_rows(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int32_t y_dtype, float y_scale,
+                       int64_t rows, int64_t row0, int32_t D, float eps, int32_t mode, void* stream) {
+  return layernorm_impl(ctx, x, ldx, w, b, y, D, y_dtype, rows, D, eps, mode, stream, row0, y_scale != 0.f ? y_scale : 1.f);
 }
 
 extern "C" int acx_vit_embed(acx_ctx* ctx, const float* patch_out, const float* cls, const float* pos,

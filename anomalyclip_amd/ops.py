@@ -362,17 +362,21 @@ def unpanel(planes: torch.Tensor) -> torch.Tensor:
 def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] = None, bias=None, act=L.ACT_NONE,
             residual=None, out_dtype=torch.float32, amap=L.AMAP_IDENTITY, gn=0, gl=0, cin=0, M: Optional[int] = None,
             planes_out: bool = False, split_k: bool = True, panels: int = 0, panel_out: bool = False, pairs: int = 6,
-            out_scale: float = 0.0, ln=None) -> torch.Tensor:
+            out_scale: float = 0.0, ln=None, planes_bf16: bool = False) -> torch.Tensor:
     """out[M, N] = epilogue(amap(A) W^T) with A = sum of the three bf16 planes a3 [3, rows, Ka] and W = sum of w3 [3, N, K]
     (split_bf16x3): the six leading cross products on the bf16 matrix cores, f32 accumulation -- the accuracy of an f32
     product (acx_gemm_desc.pairs = 6; acx_gemm_x6.h).  amap = AMAP_CONV3X3: implicit 3x3 convolution over the (gn, gl) token
     grid (K = 9 cin, a3 [3, rows, cin]).  planes_out: the result as three bf16 planes [3, M, N] (the next product's A operand).
     Few output tiles: K is split across workgroups (split_k, workspace owned by this module).
     ln = (weight, bias, y): acx_gemm_ln -- the LayerNorm of the output rows into the K-panel planes y [3, M, N] follows the product
-    (rows of it ride in the product's partly filled last round of tiles; same bits as gemm_x6 + layernorm(panel_out=True))."""
+    (rows of it ride in the product's partly filled last round of tiles; same bits as gemm_x6 + layernorm(panel_out=True)); with a
+    fourth entry `scale` and y fp16 [2, M, N]: the two fp16 planes of scale * LayerNorm (layernorm_f16x2).
+    planes_bf16 (fp16 operands, planes_out, panel_out): the output planes are the THREE bf16 planes of the f32 value (ACX_BF16X3P) --
+    what a six-product GEMM reads -- instead of fp16 pairs."""
     f16 = a3.dtype == torch.float16          # two fp16 planes per operand (split_f16x2): pairs = 3 only, out_scale undoes the planes' scales
     if f16:
         assert pairs == 3 and a3.shape[0] == 2 and w3.shape[0] == 2 and w3.dtype == torch.float16 and (panel_out or not planes_out)
+        assert not planes_bf16 or planes_out
     else:
         assert a3.shape[0] == 3 and w3.shape[0] == 3 and a3.dtype == _BF16 and w3.dtype == _BF16
     assert a3.dim() == 3 and w3.dim() == 3 and a3.is_contiguous() and w3.is_contiguous()
@@ -385,13 +389,14 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     if M is None:
         M = rows
     if out is None:
-        out = torch.empty(((2 if f16 else 3), M, N) if planes_out else (M, N), dtype=(torch.float16 if f16 else _BF16) if planes_out else out_dtype,
+        f16_out = f16 and not planes_bf16
+        out = torch.empty(((2 if f16_out else 3), M, N) if planes_out else (M, N), dtype=(torch.float16 if f16_out else _BF16) if planes_out else out_dtype,
                           device=a3.device)
     d = L.GemmDesc()
     d.A, d.W, d.C = a3.data_ptr(), w3.data_ptr(), out.data_ptr()
     d.M, d.N, d.K = M, N, K
     d.lda, d.ldw, d.ldc = Ka, K, out.stride(-2)
-    d.a_dtype, d.c_dtype, d.prec = _dt(a3), ((L.F16X2P if f16 else L.BF16X3P if panel_out else L.BF16X3) if planes_out else _dt(out)), L.PREC_BF16
+    d.a_dtype, d.c_dtype, d.prec = _dt(a3), ((L.F16X2P if f16 and not planes_bf16 else L.BF16X3P if panel_out else L.BF16X3) if planes_out else _dt(out)), L.PREC_BF16
     d.out_scale = float(out_scale)
     d.bias, d.act = _ptr(bias), act
     d.residual, d.ldr = _ptr(residual), (residual.stride(0) if residual is not None else 0)
@@ -403,10 +408,14 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     h, lib, pd = _h(a3), L.lib(), C.byref(d)
     _bring_scratch(lib, h, d, pd, a3.device, split_k)
     if ln is not None:
-        lw, lb, ly = ln
-        assert not planes_out and out.dtype == torch.float32 and ly.dtype == _BF16 and ly.shape == (3, M, N) and ly.is_contiguous()
+        lw, lb, ly = ln[:3]
+        ln16 = len(ln) > 3
+        assert not planes_out and out.dtype == torch.float32 and ly.is_contiguous()
+        assert (ly.dtype == torch.float16 and ly.shape == (2, M, N)) if ln16 else (ly.dtype == _BF16 and ly.shape == (3, M, N))
         job = L.LnJob()
-        job.w, job.b, job.y, job.y_dtype, job.eps, job.mode = lw.data_ptr(), lb.data_ptr(), ly.data_ptr(), L.BF16X3P, 1e-5, L.NORM_LAYER
+        job.w, job.b, job.y, job.y_dtype, job.eps, job.mode = (lw.data_ptr(), lb.data_ptr(), ly.data_ptr(), L.F16X2P if ln16 else L.BF16X3P,
+                                                               1e-5, L.NORM_LAYER)
+        job.y_scale = float(ln[3]) if ln16 else 0.0
         L.check(lib.acx_gemm_ln(h, pd, C.byref(job), _stream()), h)
         return out
     L.check(lib.acx_gemm(h, pd, _stream()), h)
@@ -470,6 +479,18 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, *, eps=1e-5, mo
     h = _h(x)
     L.check(L.lib().acx_layernorm(h, x.data_ptr(), ldx, w.data_ptr(), b.data_ptr(), y.data_ptr(), D,
                                   (L.BF16X3P if panel_out else L.BF16X3) if planes_out else _dt(y), rows, D, eps, mode, _stream()), h)
+    return y
+
+
+def layernorm_f16x2(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, scale: float = 1.0, *, eps=1e-5, mode=L.NORM_LAYER) -> torch.Tensor:
+    """[2, rows, D] fp16 (D = 768 or 1024) in K-panel memory order: the planes hi = fp16(scale y), lo = fp16(scale y - hi) of y = LayerNorm(x) (ACX_F16X2P;
+    scale a power of two chosen so that scale * y stays inside fp16's range): the A operand of gemm_x6(..., pairs=3) on fp16 planes"""
+    D = w.numel()
+    rows = x.numel() // D
+    y = torch.empty(2, rows, D, dtype=torch.float16, device=x.device)
+    h = _h(x)
+    L.check(L.lib().acx_layernorm_scaled(h, x.data_ptr(), D, w.data_ptr(), b.data_ptr(), y.data_ptr(), rows, D, eps, mode, float(scale),
+                                         _stream()), h)
     return y
 
 

@@ -67,6 +67,16 @@ enum { ACX_PREC_F32 = 0, ACX_PREC_BF16 = 1,          /* MFMA arithmetic: exact f
 enum { ACX_PREC_BF16X6 = 5 }; /* acx_resnet_encode only: the ResNet encoder's products as pairs = 6 products of bf16 planes (f32-accurate:
                                  the arithmetic ACX_PREC_F32X6 names in the ViT drivers).  A value of its own because ACX_PREC_F32X6 in
                                  acx_resnet_desc.prec means -- and keeps meaning -- the f32 MFMA kernels.  Opt-in (precision "bf16x6") */
+enum { ACX_PREC_F32X6_LN16 = 6 }; /* acx_vit_encode_ln16 only: ACX_PREC_F32X6 with the two LayerNorm-fed products of a body layer -- the
+                                 in-projection and c_fc -- as three-product GEMMs of fp16 planes (the ACX_PREC_F16X3 arithmetic) wherever
+                                 they take the plane kernel.  ln_1 / ln_2 then write the two ACX_F16X2P planes of s * y, s a power of two
+                                 per LayerNorm which the CALLER proves safe from the weights alone (|y_i| <= |gamma_i| sqrt(D - 1) +
+                                 |beta_i| for any finite row); in_proj_w_bf16 / fc_w_bf16 hold two fp16 planes of 2^10 w
+                                 (acx_split_f16x2, K-panel layout), out_proj_w_bf16 / proj_w_bf16 the three bf16 planes.  Per A element
+                                 the planes' error is max(2^-22 |y|, 2^-25 / s).  Attention, out-proj, c_proj, the patch embedding and the
+                                 pruned last layer are ACX_PREC_F32X6's.  Widths 768 and 1024 (the fp16 LayerNorm store).  A tools build with
+                                 -DACX_LN16_FC_DEFAULT=0 keeps c_fc a six-product GEMM (fc_w_bf16: three bf16 planes; the A/B arm that
+                                 measures the in-projection alone): acx_transformer_plan's ln2_dtype tells the caller which it is */
 #define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
 enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
@@ -268,6 +278,9 @@ typedef struct acx_ln_job {
   int32_t y_dtype;
   float eps;
   int32_t mode;           /* ACX_NORM_* */
+  float y_scale;          /* y_dtype = ACX_F16X2P (N = 768 or 1024): the planes hold y_scale * y, a power of two; 0 = 1.  Not read otherwise.
+                             The struct GREW by this member with ACX_F16X2P jobs (a dtype acx_gemm_ln refused before): a caller built
+                             against the earlier header never names that dtype, and the member is read for it alone */
 } acx_ln_job;
 int acx_gemm_ln(acx_ctx* ctx, const acx_gemm_desc* d, const acx_ln_job* job, void* stream);
 /* host-side plan of acx_gemm_ln for an eligible product on `ncu` workgroups (no device needed): returns the rows that ride (even;
@@ -282,6 +295,10 @@ int64_t acx_gemm_ln_plan(int32_t M, int32_t N, int32_t K, int32_t ncu, int32_t k
 int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
                   void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
                   int32_t mode, void* stream);
+/* y_dtype = ACX_F16X2P (D = 768 or 1024, y dense and 16-byte aligned) with the planes of y_scale * y: y_scale a power of two (0 = 1), the
+ * multiply is exact.  The caller keeps |y_scale * y| inside fp16's range */
+int acx_layernorm_scaled(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b, void* y, int64_t rows,
+                         int32_t D, float eps, int32_t mode, float y_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * acx_attention: multi-head softmax(q k^T / sqrt(64)) v for head dim 64; causal L <= 224, non-causal L <= 1024
@@ -385,6 +402,12 @@ size_t acx_vit_workspace_bytes(const acx_vit_desc* d, int32_t frames);
 int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w,
                    const float* frames, int32_t nframes, float* features, void* workspace,
                    size_t workspace_bytes, void* stream);
+/* acx_vit_encode with desc->prec = ACX_PREC_F32X6_LN16: ln_scales [2 layers] (HOST array) = the power-of-two plane scales of
+ * ln_1 and ln_2 of every block (entries 2 l, 2 l + 1), each with s * max_i(|gamma_i| sqrt(width - 1) + |beta_i|) <= 2^14 and
+ * 2^-20 <= s <= 2^20 -- the caller's proof from the weights; the driver checks only that they are such powers of two.
+ * acx_vit_encode refuses that precision (it has no scales). */
+int acx_vit_encode_ln16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* ln_scales, const float* frames,
+                        int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The CLIP ResNet image encoders (RN50, RN101, RN50x4, RN50x16, RN50x64: ModifiedResNet, clip/model.py:111-171), eval mode.
