@@ -32,9 +32,6 @@
 // wait after an epilogue also waits for the 256 KB a CU just stored.  Rejected with numbers: de-synchronising the CUs
 // or the XCDs by start delays (no gain: the drain is not a chip-wide burst), write-back instead of streaming stores
 // (-3 %).
-#ifndef ACX_P8_ABL
-#define ACX_P8_ABL 0     // timing ablations (wrong results), bit mask: 1 no C stores, 2 no epilogue at all, 4 no DMA drain at the tile end
-#endif
 constexpr int P8_HALF_B = 128 * 128;            // half-tile: 128 rows x 64 bf16
 constexpr int P8_SLOT_B = 4 * P8_HALF_B;        // K-tile slot: AH0 | AH1 | BH0 | BH1
 constexpr int P8_LDS_B = 2 * P8_SLOT_B + 8 * 4096;   // + wave-private epilogue transposers
@@ -216,15 +213,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_p8_kernel(const Args g) {
     // ---- tile end: re-align the groups, complete the K-tile after next, drain the DMA queue, epilogue, split again
     if (wm == 0) __builtin_amdgcn_s_barrier();
     P8_DMA(c1, 3, 1); P8_DMA(c1, 1, 1);                          // BH1, AH1 of the next tile's second K-tile (slot 1 is free)
-    if (!(ACX_P8_ABL & 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((ACX_P8_ABL & 2) && g.ksplit != 12345) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
-    } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    {                                                            // the epilogue of tile L
       const int L = b0 + j * G;
       const int tm = L / tiles_n, tn = L - tm * tiles_n;
       const int m0 = tm * 256, n0 = tn * 256;
@@ -278,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_p8_kernel(const Args g) {
               }
               if constexpr (RES != 0) { v.x += res[u][ps].x; v.y += res[u][ps].y; v.z += res[u][ps].z; v.w += res[u][ps].w; }
               const int row = row0 + 8 * ps;
-              if (cok && row < d.M && (!(ACX_P8_ABL & 1) || g.ksplit == 12345)) {
+              if (cok && row < d.M) {
                 if constexpr (C_BF16 == 2) {
                   // three bf16 planes hi | mid | lo of the f32 value (ACX_BF16X3): the next pairs = 6 product's A operand
                   const float ov[4] = {v.x, v.y, v.z, v.w};

@@ -46,9 +46,6 @@
 // terms first inside a range); the result is an f32 dot product's either way (tests hold both to the same bounds).
 #ifndef ACX_GEMM_X6_ONCE      // (constants, types and helpers: once; the kernel template below: once per name, see X6_KERNEL)
 #define ACX_GEMM_X6_ONCE
-#ifndef ACX_X6_ABL
-#define ACX_X6_ABL 0     // timing ablations (wrong results), bit mask: 1 no DMA in the K loop, 2 no vmcnt waits, 4 no epilogue stores, 8 every ds_read from one address
-#endif
 #ifndef ACX_X6_MFMA16
 #define ACX_X6_MFMA16 1  // the NT plane-reuse path (TN = PLAIN = X3 = 0) on v_mfma_f32_16x16x32_bf16; 0: on v_mfma_f32_32x32x16_bf16 (the A/B arm)
 #endif
@@ -247,13 +244,11 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
   // restored: nothing else in this kernel reads it (ds_read / ds_write do not use M0 on gfx9+).
 #define X6_GLDS_S(base, voff, ldsaddr)                                                             \
   do {                                                                                             \
-    if ((ACX_X6_ABL & 1) && g.ksplit != 12345) break;                                              \
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"                   \
                  : : "v"(voff), "s"(ldsaddr), "s"(base) : "memory");                               \
   } while (0)
 #define X6_GLDS_V(gptr, ldsaddr)                                                                   \
   do {                                                                                             \
-    if ((ACX_X6_ABL & 1) && g.ksplit != 12345) break;                                              \
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"                  \
                  : : "v"(gptr), "s"(ldsaddr) : "memory");                                          \
   } while (0)
@@ -390,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) F1[q][e] = (__bf16)0.f;
 
-#define X6_FRAG(off) (*reinterpret_cast<const bf16x8*>(smem + (((ACX_X6_ABL & 8) && g.ksplit != 12345) ? 0 : (off))))
+#define X6_FRAG(off) (*reinterpret_cast<const bf16x8*>(smem + (off)))
   // fragment q (0..15) of substep s of an X / Y half-step; wpar = byte offset of this K-step's W.hi / W.mid slots
 #define X6_LOADF(dst, slotoff, TRX, fx0, fx1, blk, s)                                              \
   do {                                                                                             \
@@ -494,7 +489,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
         // ======================================================================= one K-step of the three-product mode (half-step Z)
         const int apar = wpar ? 2 * X6_UNIT_B : 0;                            // A.hi: AH / AM, A.mid: WL / AL by K-step parity
         const int sa_next = wpar ? X6_AH : X6_AM, sm_next = wpar ? X6_WL : X6_AL;
-        if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         X6_FENCE();
         __builtin_amdgcn_s_barrier();
         X6_FENCE();
@@ -570,7 +565,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
 #define X6_WX_LAST x6_sel<(NI == 1)>(WA, WB)
 #define X6_WY_FIRST x6_sel<(NI == 1)>(WB, WA)
         // ----------------------------------------------------------------------- half-step X
-        if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         X6_FENCE();
         __builtin_amdgcn_s_barrier();
         X6_FENCE();
@@ -624,7 +619,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
 #undef X6_H2
         }
         // ----------------------------------------------------------------------- half-step Y
-        if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(NI) : "memory");     // A.mid, A.lo landed (W.hi of the next K-step -- NI instructions -- may be in flight)
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(NI) : "memory");     // A.mid, A.lo landed (W.hi of the next K-step -- NI instructions -- may be in flight)
         X6_FENCE();
         __builtin_amdgcn_s_barrier();
         X6_FENCE();
@@ -662,7 +657,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
         continue;
       }
       // =========================================================================== half-step X
-      if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       X6_FENCE();
       __builtin_amdgcn_s_barrier();
       X6_FENCE();
@@ -693,7 +688,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
       X6_REP48(X6_B2_X)
 #undef X6_B2_X
       // =========================================================================== half-step Y
-      if (ACX_X6_ABL & 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(TN ? 4 : NI) : "memory");     // A.mid, A.lo landed (W.hi of the next K-step -- NI instructions -- may be in flight)
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" : : "n"(TN ? 4 : NI) : "memory");     // A.mid, A.lo landed (W.hi of the next K-step -- NI instructions -- may be in flight)
       X6_FENCE();
       __builtin_amdgcn_s_barrier();
       X6_FENCE();
@@ -836,7 +831,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
         }                                                                                          \
         pl.x = f2bf2(r2[0], r2[1]); pl.y = f2bf2(r2[2], r2[3]); pl.z = f2bf2(r2[4], r2[5]); pl.w = f2bf2(r2[6], r2[7]); \
         const int row = rowp + mi * 32 + 16 * ps, colq = colp + 32 * ni;                           \
-        if ((!(PRED) || (colq < d.N && row < d.M)) && (!(ACX_X6_ABL & 4) || g.ksplit == 12345)) {  \
+        if (!(PRED) || (colq < d.N && row < d.M)) {                                                \
           typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));                         \
           const size_t crows_ = d.c_plane_rows ? (size_t)d.c_plane_rows : (size_t)d.M;             \
           const size_t pe = crows_ * d.ldc;                                                        \
@@ -867,7 +862,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); \
       }                                                                                            \
       const int row = roww + mi * 32 + 8 * ps;                                                     \
-      if ((!(PRED) || (col < d.N && row < d.M)) && (!(ACX_X6_ABL & 4) || g.ksplit == 12345)) {     \
+      if (!(PRED) || (col < d.N && row < d.M)) {                                                   \
         if constexpr (C_MODE == 1) {                                                        \
           uint2 pk;                                                                                \
           pk.x = f2bf2(v.x, v.y);                                                                  \
