@@ -300,6 +300,12 @@ _SIGS = {
                                   C.POINTER(c_float)]),
     "acx_adamw_multi_dev": (C.c_int, [c_void_p, c_int32] + [C.POINTER(c_void_p)] * 4 + [C.POINTER(c_int64), c_void_p, c_float,
                                       C.c_double, C.c_double, C.c_double, c_void_p]),
+    "acx_grad_norm_workspace_bytes": (c_size_t, [c_int32, c_int64]),
+    "acx_grad_norm": (C.c_int, [c_void_p, c_int32, C.POINTER(c_void_p), C.POINTER(c_int64), c_float, c_float, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
+    "acx_adamw_multi_dev_clip": (C.c_int, [c_void_p, c_int32] + [C.POINTER(c_void_p)] * 4 + [C.POINTER(c_int64), c_void_p, c_float,
+                                           C.c_double, C.c_double, C.c_double, c_void_p, c_float, c_void_p]),
+    "acx_clip_grads": (C.c_int, [c_void_p, c_int32, C.POINTER(c_void_p), C.POINTER(c_int64), c_float, c_void_p, c_float, c_void_p]),
     "acx_bn_pack": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "acx_bn_running_update": (C.c_int, [c_void_p] * 6 + [c_int32, c_float, c_float, c_void_p]),
     "acx_fill_f32": (C.c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),

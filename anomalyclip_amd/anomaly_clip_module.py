@@ -214,6 +214,11 @@ class AnomalyCLIPModule(_Base):
         self.visualizer = None
         self.logged: dict = {}                    # last value per self.log() name (the fallback logger)
         self._buckets: Optional[parallel.GradBuckets] = None
+        # gradient clipping of the running step: (algorithm, value), (None, 0.0) = off (train_batch sets it); the device record
+        # [norm, coefficient, sum of the epoch's norms, -] and the number of norms in that sum
+        self._clip = (None, 0.0)
+        self._clip_rec: Optional[torch.Tensor] = None
+        self._clip_steps = 0
         if not _HAVE_LIGHTNING:
             object.__setattr__(self, "trainer", None)
 
@@ -225,6 +230,41 @@ class AnomalyCLIPModule(_Base):
 
         def log(self, name, value, **kw):
             self.logged[name] = value
+
+    # ------------------------------------------------------------------ gradient clipping (Trainer(gradient_clip_val=...))
+    def _clip_record(self) -> torch.Tensor:
+        """the device record acx_grad_norm writes; allocated once: captured launches point at it"""
+        if self._clip_rec is None:
+            self._clip_rec = torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=self.device)
+        return self._clip_rec
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """global L2 norm of the last step's (averaged) gradients before clipping, a 0-d device view: no synchronisation.
+        Computed under gradient_clip_algorithm "norm" only."""
+        return self._clip_record()[0]
+
+    @property
+    def last_clip_coef(self) -> torch.Tensor:
+        """the factor the last step's gradients were multiplied by (1 when the norm was below gradient_clip_val)"""
+        return self._clip_record()[1]
+
+    def grad_norm_epoch_mean(self) -> Optional[float]:
+        """mean pre-clip gradient norm of the steps since the last call (one host read), None if no step computed one; resets"""
+        if self._clip_steps == 0:
+            return None
+        rec = self._clip_record()
+        mean = float(rec[2].item()) / self._clip_steps
+        rec[2].zero_()
+        self._clip_steps = 0
+        return mean
+
+    def _clip_grad_list(self, buckets):
+        """the gradients the norm runs over, in the whole-step graph's order (text parameters first): both paths add the
+        same numbers in the same order"""
+        text = [self.net.prompt_learner.ctx, self.net.text_encoder.text_projection]
+        rest = [p for p in buckets.params if all(p is not q for q in text)]
+        return [p.grad for p in text + rest if p.grad is not None]
 
     def _datamodule(self):
         tr = getattr(self, "trainer", None)
@@ -710,11 +750,20 @@ class AnomalyCLIPModule(_Base):
         cache[key] = sg
         return sg
 
-    def train_batch(self, batch, optimizer, batch_idx: int = 0) -> torch.Tensor:
+    def train_batch(self, batch, optimizer, batch_idx: int = 0, gradient_clip_val=None, gradient_clip_algorithm=None) -> torch.Tensor:
         """forward, loss, backward (+ bucketed gradient all-reduce overlapped with it), AdamW: what Lightning's
         automatic optimisation + DDP do around `training_step` (configs/trainer/ddp.yaml).  Default: the whole step replayed
         from HIP graphs (step_graph.TrainStepGraph); automatic fallback: the autograd path below, itself with the text tower /
-        temporal model as replayed graphs where they capture, eager otherwise."""
+        temporal model as replayed graphs where they capture, eager otherwise.
+
+        Gradient clipping as Lightning's Trainer does it between backward and the optimizer step: gradient_clip_val /
+        gradient_clip_algorithm are read from `self.trainer`; the keyword arguments serve callers without a Trainer."""
+        if gradient_clip_val is None and gradient_clip_algorithm is None:
+            tr = getattr(self, "trainer", None)
+            gradient_clip_val = getattr(tr, "gradient_clip_val", None)
+            gradient_clip_algorithm = getattr(tr, "gradient_clip_algorithm", None)
+        from .optim import normalize_clip
+        self._clip = normalize_clip(gradient_clip_val, gradient_clip_algorithm)
         buckets = self._make_buckets()
         with self._x6_cu_reservation(batch):
             return self._train_batch(batch, optimizer, batch_idx, buckets)
@@ -774,6 +823,8 @@ class AnomalyCLIPModule(_Base):
                 self._meters.attach(sg.meter_sum)        # before the step: the graph adds this step's terms to it
             losses = sg.step()
             self._after_step_graph(sg, losses)
+            if self._clip[0] == "norm":
+                self._clip_steps += 1
             return losses[0].detach()
         tm = self.net.temporal_model
         tm.__dict__["_grad_sink"] = buckets        # graph-replayed temporal backward: one accumulate launch, this step only
@@ -786,7 +837,25 @@ class AnomalyCLIPModule(_Base):
         finally:
             tm.__dict__.pop("_grad_sink", None)
             buckets._armed = False
-        optimizer.step()
+        algo, value = self._clip
+        if algo is None:
+            optimizer.step()
+            return loss.detach()
+        # the whole-step graph's three steps: gradients final (and averaged), the norm over all of them, the clipped update
+        from .optim import AcxAdamW
+        grads = self._clip_grad_list(buckets)
+        rec = self._clip_record() if algo == "norm" else None
+        if algo == "norm":
+            ws = self.__dict__.get("_clip_ws")
+            if ws is None or ws[0] != tuple((g.data_ptr(), g.numel()) for g in grads):
+                ws = self.__dict__["_clip_ws"] = (tuple((g.data_ptr(), g.numel()) for g in grads), ops.grad_norm_workspace(grads))
+            ops.grad_norm_(grads, 1.0, value, rec, ws[1])
+            self._clip_steps += 1
+        if isinstance(optimizer, AcxAdamW):
+            optimizer.step(clip=(rec, value if algo == "value" else 0.0))
+        else:
+            ops.clip_grads_(grads, 1.0, rec, value if algo == "value" else 0.0)
+            optimizer.step()
         return loss.detach()
 
     def _after_step_graph(self, sg, losses):

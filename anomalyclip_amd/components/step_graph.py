@@ -220,7 +220,12 @@ class TrainStepGraph:
         self.tstream = (torch.cuda.Stream(device=dev, priority=-1) if _os.environ.get("ACX_STEP_PLAIN_TSTREAM") == "1"
                         else ops.side_stream_beside(torch.cuda.current_stream(), dev, priority=-1))
         self.ev_marks = [torch.cuda.Event() for _ in range(12)]
-        self.ev_x = {"text_fwd": torch.cuda.Event(), "text_params": torch.cuda.Event()}
+        self.ev_x = {"text_fwd": torch.cuda.Event(), "text_grads": torch.cuda.Event(), "text_params": torch.cuda.Event()}
+        # gradient clipping (Trainer(gradient_clip_val=...)): (algorithm, value) of the step this graph is built for; "norm"
+        # writes the module's device record [norm, coefficient, running sum] and needs a scratch for the partial sums
+        self.clip_algo, self.clip_value = getattr(module, "_clip", (None, 0.0))
+        self.clip_rec = module._clip_record() if self.clip_algo == "norm" else None
+        self.clip_ws = None
         self._text_state = None
         self.key = self.make_key(module, optimizer, n_abnormal, n_normal, frames)
         self.program = None
@@ -236,7 +241,8 @@ class TrainStepGraph:
                 int(x6["cus"]), bool(x6["tail_split"]),
                 None if nc is None else nc.data_ptr(), bool(net.concat_features), int(getattr(net, "text_len", 0)),
                 bool(getattr(net, "text_class_parallel", True)), torch.cuda.current_stream().cuda_stream,
-                net.eot_index.data_ptr(), net.eot_index._version) + tuple(      # the EOT row table is baked into the capture
+                net.eot_index.data_ptr(), net.eot_index._version,                 # the EOT row table is baked into the capture
+                tuple(getattr(module, "_clip", (None, 0.0)))) + tuple(             # so are the clip algorithm and its value
             p.data_ptr() for p in module._buckets.params)
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -308,7 +314,11 @@ class TrainStepGraph:
         so it is software-pipelined across steps: step k+1's text features are computed at the end of step k, right after the
         text parameters' own AdamW, beside step k's temporal backward -- the 340 latency-bound launches of a rank's text tower
         (1.3 ms at 2 classes) leave the critical path.  Same arithmetic in the same order; a prologue replays the text
-        forward at the start of a step whenever the pipelined features are not current (first step, parameters edited)."""
+        forward at the start of a step whenever the pipelined features are not current (first step, parameters edited).
+
+        Gradient clipping (Trainer(gradient_clip_val=...)): "value" clamps inside the two AdamW launches.  "norm" joins the chains
+        first: text backward [+ exchange] -> main exchange -> main waits for the text gradients -> ONE acx_grad_norm over every
+        gradient -> both AdamW launches read its coefficient, the text stream's after a mark behind the norm."""
         par = _par()
         mod, net = self.mod, self.net
         sel, tm, te, pl = net.selector_model, net.temporal_model, net.text_encoder, net.prompt_learner
@@ -470,10 +480,70 @@ class TrainStepGraph:
             nt = len(self.text_params)
             tms, tvs = ms[:nt], vs[:nt]
 
-        def text_adamw():
-            ops.adamw_multi_dev_(self.text_params, [self.gviews[p] for p in self.text_params], tms, tvs, self.hyper_dev[: 1 + 2 * nt],
-                                 gscale, betas[0], betas[1], eps)
+        # gradient clipping: "value" clamps inside both AdamW launches, the sequence keeps its shape; "norm" needs EVERY gradient
+        # final before ANY update -- the text AdamW moves behind a join with the main chain (see the tail below)
+        clip_norm = self.clip_algo == "norm"
+        clip_rec, clip_v = self.clip_rec, (self.clip_value if self.clip_algo == "value" else 0.0)
+        all_grads = [self.gviews[p] for p in self.opt_params]
+        if clip_norm and self.clip_ws is None:
+            self.clip_ws = ops.grad_norm_workspace(all_grads)
 
+        def adamw(params, pms, pvs, hyper):
+            gs = [self.gviews[p] for p in params]
+            if self.clip_algo is None:
+                ops.adamw_multi_dev_(params, gs, pms, pvs, hyper, gscale, betas[0], betas[1], eps)
+            else:
+                ops.adamw_multi_dev_clip_(params, gs, pms, pvs, hyper, gscale, betas[0], betas[1], eps, clip_rec, clip_v)
+
+        def text_adamw():
+            adamw(self.text_params, tms, tvs, self.hyper_dev[: 1 + 2 * nt])
+
+        def text_tail():
+            pg.x_mark("text_params")                                     # ctx / text_projection: gradients (and update) final
+            if pipelined:
+                if pg.mode == "capture":
+                    # the SAME graph / exchange items = next step's text forward, minus the prologue's leading (record, x_wait)
+                    # pair: here it follows the text AdamW in the text stream's own order and must NOT wait for the main stream
+                    pg.items.extend(pg.items[i0 + 2:i0 + self.n_prologue])
+                else:
+                    text_fwd_items()
+
+        def main_exchange(text_done: str):
+            """main stream: the temporal model's gradient exchange.  `text_done`: the point of the text stream at which the
+            text gradients are final"""
+            if dist_on:
+                if not self.in_graph_adamw:
+                    # finish(average=True) scales the WHOLE flat buffer, the [text_projection, ctx] bucket included: the text
+                    # stream's backward and its reduce_now must have completed first (with the in-graph AdamW nothing on the main
+                    # stream touches that bucket: the 1 / world factor is the update's own gscale)
+                    pg.main_wait(text_done)
+                pg.eager(lambda: (self._ready(list(tparams)), self.buckets.finish(average=not self.in_graph_adamw)))
+            else:
+                pg.host(lambda: (self._ready(list(tparams) + self.text_params), self.buckets.finish(average=False)))
+
+        if clip_norm:
+            pg.on_x(lambda: text_bwd(d_text), after=tok1)
+            if dist_on:
+                pg.x_eager(lambda: self.buckets.reduce_now(self.text_params))     # their own bucket, summed over ranks
+            pg.x_mark("text_grads")                                      # text gradients final, not yet applied
+            main_exchange("text_grads")
+            pg.main_wait("text_grads")
+            pg.begin()
+            # the norm of the AVERAGED gradients (what Lightning sees after DDP): the same number on every rank without another
+            # collective (finish(average=True) has divided the buffer already when the optimizer is not ours)
+            ops.grad_norm_(all_grads, gscale if self.in_graph_adamw else 1.0, self.clip_value, clip_rec, self.clip_ws)
+            if self.in_graph_adamw:
+                tokn = pg.mark()
+                pg.begin()
+                # enqueued BEFORE the text stream's items (the host walks their ~170 nodes), ordered after the same mark
+                adamw(self.main_params, ms[nt:], vs[nt:], self.hyper_dev[1 + 2 * nt:])
+                pg.on_x(text_adamw, after=tokn)
+            else:
+                ops.clip_grads_(all_grads, 1.0, clip_rec, 0.0)           # the optimizer steps after the replay
+            text_tail()
+            pg.main_wait("text_params")  # whoever follows on the main stream sees final text parameters / gradients
+            pg.end()
+            return
         if dist_on:
             pg.on_x(lambda: text_bwd(d_text), after=tok1)
             pg.x_eager(lambda: self.buckets.reduce_now(self.text_params))         # their own bucket, summed over ranks
@@ -483,29 +553,16 @@ class TrainStepGraph:
             pg.on_x(lambda: (text_bwd(d_text), text_adamw()), after=tok1)
         else:
             pg.on_x(lambda: text_bwd(d_text), after=tok1)
-        pg.x_mark("text_params")                                         # ctx / text_projection: gradients (and update) final
-        if pipelined:
-            if pg.mode == "capture":
-                # the SAME graph / exchange items = next step's text forward, minus the prologue's leading (record, x_wait) pair:
-                # here it follows the text AdamW in the text stream's own order and must NOT wait for the main stream
-                pg.items.extend(pg.items[i0 + 2:i0 + self.n_prologue])
-            else:
-                text_fwd_items()
+        text_tail()
         # ---- main tail: the temporal model's gradient exchange and optimizer step
-        if dist_on:
-            if not self.in_graph_adamw:
-                # finish(average=True) scales the WHOLE flat buffer, the [text_projection, ctx] bucket included: the text
-                # stream's backward and its reduce_now must have completed first (with the in-graph AdamW nothing on the main
-                # stream touches that bucket: the 1 / world factor is the update's own gscale)
-                pg.main_wait("text_params")
-            pg.eager(lambda: (self._ready(list(tparams)), self.buckets.finish(average=not self.in_graph_adamw)))
-        else:
-            pg.host(lambda: (self._ready(list(tparams) + self.text_params), self.buckets.finish(average=False)))
+        main_exchange("text_params")
         if self.in_graph_adamw:
             pg.begin()
-            ops.adamw_multi_dev_(self.main_params, [self.gviews[p] for p in self.main_params], ms[nt:], vs[nt:],
-                                 self.hyper_dev[1 + 2 * nt:], gscale, betas[0], betas[1], eps)
+            adamw(self.main_params, ms[nt:], vs[nt:], self.hyper_dev[1 + 2 * nt:])
         pg.main_wait("text_params")      # whoever follows on the main stream sees final text parameters / gradients
+        if self.clip_algo == "value" and not self.in_graph_adamw:
+            pg.begin()
+            ops.clip_grads_(all_grads, 1.0, None, clip_v)                # averaged by finish(); the optimizer steps after the replay
         pg.end()
 
     def _ready(self, params):
@@ -566,10 +623,10 @@ class TrainStepGraph:
             st.append((s.get("step", 0), None if "exp_avg" not in s else s["exp_avg"].clone(),
                        None if "exp_avg_sq" not in s else s["exp_avg_sq"].clone()))
         return (ps, st, bn.running_mean.clone(), bn.running_var.clone(), bn.num_batches_tracked.clone(), self.meter_sum.clone(),
-                ops.WEIGHT_EPOCH[0])
+                ops.WEIGHT_EPOCH[0], None if self.clip_rec is None else self.clip_rec.clone())
 
     def _restore(self, snap):
-        ps, st, rm, rv, nbt, ms, epoch = snap
+        ps, st, rm, rv, nbt, ms, epoch, clip_rec = snap
         bn = self.net.selector_model.bn_layer
         with torch.no_grad():
             for p, q in zip(self.opt_params, ps):
@@ -588,6 +645,8 @@ class TrainStepGraph:
             bn.running_var.copy_(rv)
             bn.num_batches_tracked.copy_(nbt)
             self.meter_sum.copy_(ms)
+            if clip_rec is not None:
+                self.clip_rec.copy_(clip_rec)
         ops.WEIGHT_EPOCH[0] = epoch + 1          # derived-weight caches keyed by the epoch must not survive the dry runs
 
     # ------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@
 //                           in ONE launch -- was ~20 copy / cat / transpose launches per step
 //   acx_adamw_multi_dev     multi-tensor AdamW whose per-tensor scalars (1 - lr wd, lr / bias correction) live in DEVICE
 //                           memory: lr schedules and the step count change without re-capturing the graph
+//   acx_grad_norm / acx_adamw_multi_dev_clip / acx_clip_grads   gradient clipping (Trainer(gradient_clip_val=...)): the global
+//                           norm in fp64 with a fixed order and no host read, AdamW on the scaled or clamped gradient
 //   acx_multi_copy          y_i = x_i for a list of tensors (gradients that cannot be produced in place -> flat buffer)
 //   acx_bn_pack / acx_bn_running_update / acx_fill_f32   the selector's BatchNorm bookkeeping without torch elementwise ops
 #include "acx_internal.h"
@@ -100,9 +102,25 @@ struct AdamwDevSegs {
 // hyper: [0] = sqrt(1 - beta2^step), then per tensor (decay = 1 - lr wd, step_size = lr / (1 - beta1^step)) pairs; the same
 // f32 values acx_adamw_multi forms on the host, so both entry points update bit-identically.  grad_scale multiplies every
 // gradient as it is read (1 / world size after a summing all-reduce; exactly 1.0f otherwise -- x * 1.0f == x).
-template <bool SCALE>
-__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const AdamwDevSegs t, const float* __restrict__ hyper, float b1, float b2,
-                                                              float omb1, float omb2, float eps, float grad_scale) {
+// Gradient clipping (what Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm) does between backward and optimizer.step():
+// torch.nn.utils.clip_grad_norm_ / clip_grad_value_ over every parameter's gradient).  MODE 1: g <- (g * grad_scale) * coef with the
+// coefficient read from the device record acx_grad_norm wrote; MODE 2: g * grad_scale clamped to [-v, v] by comparisons, so that a
+// NaN stays a NaN (torch.clamp).
+template <int MODE>
+__device__ __forceinline__ float clip_grad(float g, float grad_scale, float coef, float v) {
+  float x = g * grad_scale;
+  if (MODE == 1) x *= coef;
+  if (MODE == 2) x = x > v ? v : (x < -v ? -v : x);
+  return x;
+}
+
+// one block's 1024 elements of the update.  MODE 0: the gradient as it is (SCALE: times grad_scale, written back); MODE 1 / 2: the
+// clipped gradient (clip_grad), always written back -- the flat gradient buffer is left holding the clipped mean, as Lightning
+// leaves .grad
+template <bool SCALE, int MODE>
+__device__ __forceinline__ void adamw_dev_body(const AdamwDevSegs& t, const float* __restrict__ hyper, float b1, float b2, float omb1,
+                                               float omb2, float eps, float grad_scale, const float* __restrict__ clip,
+                                               float clip_value) {
   const int b = blockIdx.x;
   int lo = 0, hi = t.nseg - 1;
   while (lo < hi) {
@@ -117,12 +135,18 @@ __global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const AdamwDevSegs
   const long long n = t.n[sgi];
   const float bc2_sqrt = hyper[0];
   const float decay = hyper[1 + 2 * (t.seg_base + sgi)], step_size = hyper[2 + 2 * (t.seg_base + sgi)];
+  const float coef = MODE == 1 ? clip[1] : 1.f;
   const long long base = (long long)(b - t.chunk0[sgi]) * 1024 + threadIdx.x;
   float pi[4], gi[4], mi[4], vi[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const long long i = base + 256 * k;
-    if (i < n) { pi[k] = p[i]; gi[k] = SCALE ? g[i] * grad_scale : g[i]; mi[k] = m[i]; vi[k] = v[i]; }
+    if (i < n) {
+      pi[k] = p[i];
+      gi[k] = MODE ? clip_grad<MODE>(g[i], grad_scale, coef, clip_value) : (SCALE ? g[i] * grad_scale : g[i]);
+      mi[k] = m[i];
+      vi[k] = v[i];
+    }
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -134,8 +158,145 @@ __global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const AdamwDevSegs
       m[i] = mn;
       v[i] = vn;
       p[i] = pw - step_size * (mn / (sqrtf(vn) / bc2_sqrt + eps));
-      if (SCALE) g[i] = gi[k];         // the flat gradient buffer is left holding the MEAN, as DDP leaves .grad
+      if (SCALE || MODE) g[i] = gi[k];   // the flat gradient buffer is left holding the MEAN, as DDP leaves .grad
     }
+  }
+}
+
+template <bool SCALE>
+__global__ __launch_bounds__(256) void adamw_multi_dev_kernel(const AdamwDevSegs t, const float* __restrict__ hyper, float b1, float b2,
+                                                              float omb1, float omb2, float eps, float grad_scale) {
+  adamw_dev_body<SCALE, 0>(t, hyper, b1, b2, omb1, omb2, eps, grad_scale, nullptr, 0.f);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void adamw_multi_dev_clip_kernel(const AdamwDevSegs t, const float* __restrict__ hyper, float b1,
+                                                                   float b2, float omb1, float omb2, float eps, float grad_scale,
+                                                                   const float* __restrict__ clip, float clip_value) {
+  adamw_dev_body<true, MODE>(t, hyper, b1, b2, omb1, omb2, eps, grad_scale, clip, clip_value);
+}
+
+// ------------------------------------------------------------------------------------------------ gradient norm, in-place clipping
+// gradient tensors alone: the table of acx_grad_norm (chunks of GNORM_CHUNK elements) and acx_clip_grads (chunks of 1024)
+constexpr int GNORM_MAX_SEG = 48;
+constexpr int GNORM_CHUNK = 16384;                  // few partial sums: the last arriver walks them with latency-bound loads
+constexpr size_t GNORM_WS_HEAD = 64;                // the arrival counter's line, in front of the partial sums
+struct GradSegs {
+  float* g[GNORM_MAX_SEG];
+  long long n[GNORM_MAX_SEG];
+  int chunk0[GNORM_MAX_SEG + 1];
+  int nseg;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void clip_grads_kernel(const GradSegs t, float grad_scale, const float* __restrict__ clip,
+                                                         float clip_value) {
+  const int b = blockIdx.x;
+  int lo = 0, hi = t.nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (t.chunk0[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  float* __restrict__ g = t.g[lo];
+  const long long n = t.n[lo];
+  const float coef = MODE == 1 ? clip[1] : 1.f;
+  const long long base = (long long)(b - t.chunk0[lo]) * 1024 + threadIdx.x;
+  float gi[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long i = base + 256 * k;
+    if (i < n) gi[k] = g[i];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long i = base + 256 * k;
+    if (i < n) g[i] = clip_grad<MODE>(gi[k], grad_scale, coef, clip_value);
+  }
+}
+
+// sum of the 256 lanes' values in a FIXED tree: within a wave lane i += lane i + w (w = 32 ... 1; lane 0 ends with the wave's
+// sum), then the four waves' sums in wave order
+__device__ __forceinline__ double block_sum_f64(double s, double* red) {
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) s += __shfl_down(s, w);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const double tot = ((red[0] + red[1]) + red[2]) + red[3];
+  __syncthreads();
+  return tot;
+}
+
+// Global L2 norm of the gradients, squares and sums in fp64 (the square of an f32 is exact there; a sum of n non-negative
+// terms carries at most n 2^-53 relative error, so the f32-rounded norm is within one ulp of the exact one).  Order: block b of
+// the launch owns chunk b (GNORM_CHUNK elements of one tensor, tensors in table order): lane l adds elements l, l + 256, ...
+// of the chunk in order, the lanes are added by the fixed tree, the chunk's sum goes to part[part_base + b].  A call with
+// more tensors than one table holds is several launches; only the LAST one counts arrivals, and its last block to arrive
+// adds ALL the partial sums (earlier launches' included: they completed before this launch began) in chunk order -- lane l
+// chunks l, l + 256, ..., then the same tree -- and writes the record.  No floating-point atomics, no dependence on the
+// grid or on the arrival order.  The hand-off is colsum_fused_body's: agent-scope write-through stores of the partial sums,
+// s_waitcnt vmcnt(0), a relaxed agent-scope counter, agent-scope loads in the last arriver; the counter returns to zero.
+__global__ __launch_bounds__(256) void grad_norm_kernel(const GradSegs t, int nchunks, unsigned long long* __restrict__ part,
+                                                        int part_base, int total_parts, unsigned int* __restrict__ counter, int final_launch,
+                                                        float grad_scale, float max_norm, float* __restrict__ out) {
+  __shared__ double red[4];
+  __shared__ bool last;
+  const int b = blockIdx.x;
+  if (b < nchunks) {                                  // (a final launch without a chunk of its own is one block that only reduces)
+    int lo = 0, hi = t.nseg - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (t.chunk0[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    const float* __restrict__ g = t.g[lo];
+    const long long n = t.n[lo];
+    const long long base = (long long)(b - t.chunk0[lo]) * GNORM_CHUNK + threadIdx.x;
+    double s = 0.0;
+    for (int r = 0; r < GNORM_CHUNK / 4096; ++r) {    // sixteen loads in flight per lane, added in element order
+      float x[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const long long i = base + 4096 * r + 256 * k;
+        x[k] = i < n ? g[i] * grad_scale : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s += (double)x[k] * (double)x[k];
+    }
+    const double tot = block_sum_f64(s, red);
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(part + part_base + b, (unsigned long long)__double_as_longlong(tot), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  if (!final_launch) return;
+  if (threadIdx.x == 0) {
+    ACX_HANDOFF_RELEASE();
+    last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  ACX_HANDOFF_ACQUIRE();
+  double s = 0.0;
+  int p = threadIdx.x;
+  for (; p + 7 * 256 < total_parts; p += 8 * 256) {   // eight loads in flight per lane, added in chunk order
+    unsigned long long v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = __hip_atomic_load(part + p + 256 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += __longlong_as_double((long long)v[k]);
+  }
+  for (; p < total_parts; p += 256)
+    s += __longlong_as_double((long long)__hip_atomic_load(part + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  const double tot = block_sum_f64(s, red);
+  if (threadIdx.x == 0) {
+    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to at most 1 -- by a comparison,
+    // not fminf: torch.clamp(nan, max=1) is nan and the nan has to reach the update
+    const float norm = (float)sqrt(tot);
+    const float c = max_norm / (norm + 1e-6f);
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;
+    out[2] += norm;
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -442,12 +603,21 @@ extern "C" int acx_adamw_hyper(int32_t nseg, const double* lr, const double* wei
   return ACX_OK;
 }
 
-extern "C" int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, const void* const* g, void* const* m, void* const* v,
-                                   const int64_t* n, const float* hyper_dev, float grad_scale, double beta1, double beta2, double eps,
-                                   void* stream) {
+// which of the two clip arguments is on: 0 none, 1 the norm coefficient, 2 the clamp; -1 = bad arguments (message set)
+static int clip_mode(acx_ctx* ctx, const char* who, const float* clip_dev, float clip_value) {
+  if (clip_value != clip_value) { acx_fail(ctx, ACX_E_BADARG, "%s: clip_value is NaN", who); return -1; }
+  if (clip_dev && clip_value > 0.f) { acx_fail(ctx, ACX_E_BADARG, "%s: clip_dev and clip_value are exclusive", who); return -1; }
+  return clip_dev ? 1 : (clip_value > 0.f ? 2 : 0);
+}
+
+// the tables and launches of acx_adamw_multi_dev (mode 0) and acx_adamw_multi_dev_clip (mode 1: coefficient, 2: clamp)
+static int adamw_dev_launch(acx_ctx* ctx, const char* who, int32_t nseg, void* const* p, const void* const* g, void* const* m,
+                            void* const* v, const int64_t* n, const float* hyper_dev, float grad_scale, double beta1, double beta2,
+                            double eps, int mode, const float* clip_dev, float clip_value, void* stream) {
   if (nseg <= 0) return ACX_OK;
-  if (!p || !g || !m || !v || !n || !hyper_dev) return acx_fail(ctx, ACX_E_BADARG, "acx_adamw_multi_dev: null pointer%s");
+  if (!p || !g || !m || !v || !n || !hyper_dev) return acx_fail(ctx, ACX_E_BADARG, "%s: null pointer", who);
   hipStream_t s = (hipStream_t)stream;
+  const float b1 = (float)beta1, b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2), e = (float)eps;
   int i = 0;
   while (i < nseg) {
     AdamwDevSegs t;
@@ -457,8 +627,7 @@ extern "C" int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, c
     t.seg_base = i;
     for (; i < nseg && k < ADAMW_DEV_MAX_SEG; ++i) {
       // hyper is indexed by the CALLER's tensor index, so empty tensors are kept as zero-chunk segments, not skipped
-      if (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i]))
-        return acx_fail(ctx, ACX_E_BADARG, "acx_adamw_multi_dev: null tensor pointer%s");
+      if (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i])) return acx_fail(ctx, ACX_E_BADARG, "%s: null tensor pointer", who);
       t.p[k] = (float*)p[i]; t.g[k] = (const float*)g[i]; t.m[k] = (float*)m[i]; t.v[k] = (float*)v[i];
       t.n[k] = n[i] > 0 ? n[i] : 0;
       t.chunk0[k] = (int)chunks;
@@ -466,21 +635,133 @@ extern "C" int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, c
       ++k;
     }
     if (chunks == 0) continue;
-    if (chunks > 0x7fffffffLL) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_adamw_multi_dev: too many elements for one launch%s");
+    if (chunks > 0x7fffffffLL) return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: too many elements for one launch", who);
     // a zero-chunk segment shares its chunk0 with the next one: the search ("last segment with chunk0 <= b") then lands on the
     // LAST of the equal entries, which is the non-empty one -- unless the empty ones trail; cut those off
     while (k > 0 && t.n[k - 1] == 0) --k;
     t.chunk0[k] = (int)chunks;
     t.nseg = k;
     AcxProfScope prof__(ctx, ACX_K_OTHER, s);
-    if (grad_scale == 1.0f)
-      hipLaunchKernelGGL(adamw_multi_dev_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, s, t, hyper_dev, (float)beta1,
-                         (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, grad_scale);
+    const dim3 grid((unsigned)chunks), block(256);
+    if (mode == 1)
+      hipLaunchKernelGGL(adamw_multi_dev_clip_kernel<1>, grid, block, 0, s, t, hyper_dev, b1, b2, omb1, omb2, e, grad_scale, clip_dev,
+                         clip_value);
+    else if (mode == 2)
+      hipLaunchKernelGGL(adamw_multi_dev_clip_kernel<2>, grid, block, 0, s, t, hyper_dev, b1, b2, omb1, omb2, e, grad_scale, clip_dev,
+                         clip_value);
+    else if (grad_scale == 1.0f)
+      hipLaunchKernelGGL(adamw_multi_dev_kernel<false>, grid, block, 0, s, t, hyper_dev, b1, b2, omb1, omb2, e, grad_scale);
     else
-      hipLaunchKernelGGL(adamw_multi_dev_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, s, t, hyper_dev, (float)beta1,
-                         (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, grad_scale);
+      hipLaunchKernelGGL(adamw_multi_dev_kernel<true>, grid, block, 0, s, t, hyper_dev, b1, b2, omb1, omb2, e, grad_scale);
   }
-  ACX_CHECK_LAUNCH(ctx, "acx_adamw_multi_dev");
+  ACX_CHECK_LAUNCH(ctx, who);
+  return ACX_OK;
+}
+
+extern "C" int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, const void* const* g, void* const* m, void* const* v,
+                                   const int64_t* n, const float* hyper_dev, float grad_scale, double beta1, double beta2, double eps,
+                                   void* stream) {
+  return adamw_dev_launch(ctx, "acx_adamw_multi_dev", nseg, p, g, m, v, n, hyper_dev, grad_scale, beta1, beta2, eps, 0, nullptr, 0.f,
+                          stream);
+}
+
+extern "C" int acx_adamw_multi_dev_clip(acx_ctx* ctx, int32_t nseg, void* const* p, const void* const* g, void* const* m,
+                                        void* const* v, const int64_t* n, const float* hyper_dev, float grad_scale, double beta1,
+                                        double beta2, double eps, const float* clip_dev, float clip_value, void* stream) {
+  const int mode = clip_mode(ctx, "acx_adamw_multi_dev_clip", clip_dev, clip_value);
+  if (mode < 0) return ACX_E_BADARG;
+  return adamw_dev_launch(ctx, mode ? "acx_adamw_multi_dev_clip" : "acx_adamw_multi_dev", nseg, p, g, m, v, n, hyper_dev, grad_scale,
+                          beta1, beta2, eps, mode, clip_dev, clip_value, stream);
+}
+
+// argument checks shared by acx_grad_norm and acx_clip_grads; *chunks = the call's chunk count at `chunk` elements each
+static int grad_segs_check(acx_ctx* ctx, const char* who, int32_t nseg, const void* const* g, const int64_t* n, long long chunk,
+                           long long* chunks) {
+  if (nseg < 1) return acx_fail(ctx, ACX_E_BADARG, "%s: nseg must be at least 1", who);
+  if (!g || !n) return acx_fail(ctx, ACX_E_BADARG, "%s: null pointer", who);
+  long long c = 0;
+  for (int i = 0; i < nseg; ++i) {
+    if (n[i] < 0) return acx_fail(ctx, ACX_E_BADARG, "%s: negative tensor size", who);
+    if (n[i] > 0 && !g[i]) return acx_fail(ctx, ACX_E_BADARG, "%s: null tensor pointer", who);
+    c += (n[i] + chunk - 1) / chunk;
+  }
+  if (c > 0x7fffffffLL) return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: too many elements", who);
+  *chunks = c;
+  return ACX_OK;
+}
+// the next table of at most GNORM_MAX_SEG non-empty tensors, starting at tensor *i; -> its chunk count
+static int grad_segs_next(GradSegs* t, int* i, int32_t nseg, const void* const* g, const int64_t* n, long long chunk) {
+  memset(t, 0, sizeof(*t));
+  int k = 0, chunks = 0;
+  for (; *i < nseg && k < GNORM_MAX_SEG; ++*i) {
+    if (n[*i] == 0) continue;
+    t->g[k] = (float*)const_cast<void*>(g[*i]); t->n[k] = n[*i];
+    t->chunk0[k] = chunks;
+    chunks += (int)((n[*i] + chunk - 1) / chunk);
+    ++k;
+  }
+  t->chunk0[k] = chunks;
+  t->nseg = k;
+  return chunks;
+}
+
+extern "C" size_t acx_grad_norm_workspace_bytes(int32_t nseg, int64_t n) {
+  if (nseg < 1 || n < 0) return 0;
+  // every tensor ends with at most one partly filled chunk
+  return GNORM_WS_HEAD + sizeof(double) * (size_t)(n / GNORM_CHUNK + nseg);
+}
+
+extern "C" int acx_grad_norm(acx_ctx* ctx, int32_t nseg, const void* const* g, const int64_t* n, float grad_scale, float max_norm,
+                             float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  long long total = 0;
+  const int rc = grad_segs_check(ctx, "acx_grad_norm", nseg, g, n, GNORM_CHUNK, &total);
+  if (rc != ACX_OK) return rc;
+  if (!out || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_grad_norm: null pointer%s");
+  if (!(max_norm >= 0.f)) return acx_fail(ctx, ACX_E_BADARG, "acx_grad_norm: max_norm must be >= 0%s");
+  if ((uintptr_t)workspace & 15) return acx_fail(ctx, ACX_E_BADARG, "acx_grad_norm: 16-byte aligned workspace%s");
+  if (GNORM_WS_HEAD + sizeof(double) * (size_t)total > workspace_bytes)
+    return acx_fail(ctx, ACX_E_WORKSPACE, "acx_grad_norm: workspace too small (acx_grad_norm_workspace_bytes)%s");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned int* counter = (unsigned int*)workspace;
+  unsigned long long* part = (unsigned long long*)((char*)workspace + GNORM_WS_HEAD);
+  int i = 0, base = 0;
+  bool final_launch = false;
+  while (!final_launch) {
+    GradSegs t;
+    const int chunks = grad_segs_next(&t, &i, nseg, g, n, GNORM_CHUNK);
+    final_launch = base + chunks == (int)total;      // (what follows, if anything, is empty)
+    AcxProfScope prof__(ctx, ACX_K_OTHER, s);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3((unsigned)(chunks > 0 ? chunks : 1)), dim3(256), 0, s, t, chunks, part, base, (int)total,
+                       counter, final_launch ? 1 : 0, grad_scale, max_norm, out);
+    base += chunks;
+  }
+  ACX_CHECK_LAUNCH(ctx, "acx_grad_norm");
+  return ACX_OK;
+}
+
+extern "C" int acx_clip_grads(acx_ctx* ctx, int32_t nseg, void* const* g, const int64_t* n, float grad_scale, const float* clip_dev,
+                              float clip_value, void* stream) {
+  long long total = 0;
+  const int rc = grad_segs_check(ctx, "acx_clip_grads", nseg, (const void* const*)g, n, 1024, &total);
+  if (rc != ACX_OK) return rc;
+  const int mode = clip_mode(ctx, "acx_clip_grads", clip_dev, clip_value);
+  if (mode < 0) return ACX_E_BADARG;
+  if (mode == 0 && grad_scale == 1.0f) return ACX_OK;
+  hipStream_t s = (hipStream_t)stream;
+  int i = 0;
+  while (i < nseg) {
+    GradSegs t;
+    const int chunks = grad_segs_next(&t, &i, nseg, (const void* const*)g, n, 1024);
+    if (chunks == 0) continue;
+    AcxProfScope prof__(ctx, ACX_K_OTHER, s);
+    if (mode == 1)
+      hipLaunchKernelGGL(clip_grads_kernel<1>, dim3((unsigned)chunks), dim3(256), 0, s, t, grad_scale, clip_dev, clip_value);
+    else if (mode == 2)
+      hipLaunchKernelGGL(clip_grads_kernel<2>, dim3((unsigned)chunks), dim3(256), 0, s, t, grad_scale, clip_dev, clip_value);
+    else
+      hipLaunchKernelGGL(clip_grads_kernel<0>, dim3((unsigned)chunks), dim3(256), 0, s, t, grad_scale, clip_dev, clip_value);
+  }
+  ACX_CHECK_LAUNCH(ctx, "acx_clip_grads");
   return ACX_OK;
 }
 

@@ -1159,6 +1159,50 @@ def adamw_multi_dev_(ps, gs, ms, vs, hyper_dev: torch.Tensor, grad_scale: float,
                                         hyper_dev.data_ptr(), float(grad_scale), beta1, beta2, eps, _stream()), h)
 
 
+def grad_norm_workspace(gs) -> torch.Tensor:
+    """the zeroed scratch grad_norm_ needs for these gradient tensors (acx_grad_norm_workspace_bytes); reusable across calls"""
+    h = _h(gs[0])                                                            # (device tensors only)
+    nbytes = int(L.lib().acx_grad_norm_workspace_bytes(len(gs), sum(g.numel() for g in gs)))
+    return torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=gs[0].device)
+
+
+def grad_norm_(gs, grad_scale: float, max_norm: float, out: torch.Tensor, workspace: torch.Tensor) -> None:
+    """acx_grad_norm: out[0] = global L2 norm of the dense f32 tensors `gs` (each times grad_scale), out[1] = torch's clip
+    coefficient for max_norm, out[2] += out[0].  `out`: f32 [>= 3] on the device; nothing is read back."""
+    n = len(gs)
+    h = _h(gs[0])
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() >= 3 and out.is_contiguous()
+    assert all(g.dtype == torch.float32 for g in gs)
+    L.check(L.lib().acx_grad_norm(h, n, (C.c_void_p * n)(*[g.data_ptr() for g in gs]), (C.c_int64 * n)(*[g.numel() for g in gs]),
+                                  float(grad_scale), float(max_norm), out.data_ptr(), workspace.data_ptr(),
+                                  workspace.numel() * workspace.element_size(), _stream()), h)
+
+
+def adamw_multi_dev_clip_(ps, gs, ms, vs, hyper_dev: torch.Tensor, grad_scale: float, beta1, beta2, eps,
+                          clip_dev: Optional[torch.Tensor] = None, clip_value: float = 0.0) -> None:
+    """adamw_multi_dev_ on clipped gradients (acx_adamw_multi_dev_clip): `clip_dev` = the record grad_norm_ wrote (scale by its
+    coefficient), or `clip_value` > 0 (clamp); the gradient tensors are left holding the clipped gradient."""
+    n = len(ps)
+    if n == 0:
+        return
+    h = _h(ps[0])
+    assert hyper_dev.is_cuda and hyper_dev.dtype == torch.float32 and hyper_dev.numel() >= 1 + 2 * n
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])           # noqa: E731
+    L.check(L.lib().acx_adamw_multi_dev_clip(h, n, arr(ps), arr(gs), arr(ms), arr(vs), (C.c_int64 * n)(*[p.numel() for p in ps]),
+                                             hyper_dev.data_ptr(), float(grad_scale), beta1, beta2, eps, _ptr(clip_dev),
+                                             float(clip_value), _stream()), h)
+
+
+def clip_grads_(gs, grad_scale: float = 1.0, clip_dev: Optional[torch.Tensor] = None, clip_value: float = 0.0) -> None:
+    """the same clipping in place on the gradient tensors alone (acx_clip_grads): for an optimizer whose step is torch's"""
+    n = len(gs)
+    if n == 0:
+        return
+    h = _h(gs[0])
+    L.check(L.lib().acx_clip_grads(h, n, (C.c_void_p * n)(*[g.data_ptr() for g in gs]), (C.c_int64 * n)(*[g.numel() for g in gs]),
+                                   float(grad_scale), _ptr(clip_dev), float(clip_value), _stream()), h)
+
+
 def bn_pack(mean: torch.Tensor, var_b: torch.Tensor, rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     C1 = mean.numel()
     if out is None:

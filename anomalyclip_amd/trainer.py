@@ -27,13 +27,21 @@ def _to_device(x: Any, dev):
 
 class Trainer:
     def __init__(self, max_epochs: int = 50, min_epochs: int = 1, check_val_every_n_epoch: int = 1,
-                 default_root_dir: Optional[str] = None, limit_train_batches: Optional[int] = None, **ignored):
+                 default_root_dir: Optional[str] = None, limit_train_batches: Optional[int] = None,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = None, **ignored):
         # accepted and ignored like any Trainer kwarg that has no meaning here: accelerator, devices, strategy,
         # sync_batchnorm (always on under DP), num_sanity_val_steps, deterministic, callbacks, logger ...
         self.max_epochs, self.min_epochs = int(max_epochs), int(min_epochs)
         self.check_val_every_n_epoch = int(check_val_every_n_epoch)
         self.default_root_dir = default_root_dir
         self.limit_train_batches = limit_train_batches
+        # Lightning's meaning: None or 0 = off, the algorithm defaults to "norm"; the two Trainer arguments that change the
+        # arithmetic of a step (AnomalyCLIPModule.train_batch reads them).  Checked here: a typo must not train unclipped
+        from .optim import normalize_clip
+        normalize_clip(gradient_clip_val, gradient_clip_algorithm)
+        self.gradient_clip_val = gradient_clip_val
+        self.gradient_clip_algorithm = "norm" if gradient_clip_algorithm is None else str(
+            getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)).lower()
         self.datamodule = None
         self.current_epoch = 0
         self.global_step = 0
@@ -205,6 +213,10 @@ class Trainer:
                 model.train_batch(_to_device(batch, dev), opt, i)
                 self.global_step += 1
             model.on_train_epoch_end()
+            # the epoch's mean gradient norm before clipping (gradient_clip_algorithm "norm"): the one host read of the record
+            gn = getattr(model, "grad_norm_epoch_mean", lambda: None)()
+            if gn is not None:
+                self.callback_metrics["train/grad_norm"] = gn
             if sched is not None:
                 sched.step()
             if (epoch + 1) % self.check_val_every_n_epoch == 0 and hasattr(self.datamodule, "val_dataloader"):

@@ -913,6 +913,31 @@ int acx_adamw_hyper(int32_t nseg, const double* lr, const double* weight_decay, 
 int acx_adamw_multi_dev(acx_ctx* ctx, int32_t nseg, void* const* p, const void* const* g, void* const* m, void* const* v,
                         const int64_t* n, const float* hyper_dev, float grad_scale, double beta1, double beta2, double eps,
                         void* stream);
+/* ---- gradient clipping (configs/trainer/default.yaml:1 instantiates pytorch_lightning.Trainer, whose gradient_clip_val /
+ * gradient_clip_algorithm run torch.nn.utils.clip_grad_norm_ / clip_grad_value_ between backward and optimizer.step()).
+ * acx_grad_norm: global L2 norm of nseg f32 gradient tensors (host arrays of device pointers and element counts; 4-byte
+ * alignment suffices; any nseg >= 1, more tensors than one launch's table are several launches).  Every gradient is
+ * multiplied by grad_scale in f32 as it is read (1 / world size after a summing all-reduce, 1.0f otherwise); squares and
+ * sums are formed in fp64 in a fixed order (tensor order, then chunk order, then a fixed in-block tree; no floating-point
+ * atomics), so the result is bit-identical from call to call and the f32-rounded norm is within one ulp of the exact one.
+ * Writes the device record out[0] = norm, out[1] = clip coefficient, out[2] += norm (a running sum the caller zeroes).
+ * The coefficient is torch's, in f32: c = max_norm / (norm + 1e-6f), then c > 1 ? 1 : c (a NaN norm gives a NaN
+ * coefficient, a zero gradient 1).  workspace: acx_grad_norm_workspace_bytes(nseg, total elements) bytes, 16-byte aligned,
+ * caller-owned, ZERO before the first call and left reusable by every call (its arrival counter returns to zero).  No
+ * allocation, no host read, capturable. */
+size_t acx_grad_norm_workspace_bytes(int32_t nseg, int64_t n);
+int acx_grad_norm(acx_ctx* ctx, int32_t nseg, const void* const* g, const int64_t* n, float grad_scale, float max_norm,
+                  float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* acx_adamw_multi_dev on clipped gradients.  clip_dev (may be NULL): the record acx_grad_norm wrote, every gradient becomes
+ * (g * grad_scale) * clip_dev[1].  clip_value (<= 0: off): g * grad_scale is clamped to [-clip_value, clip_value], a NaN
+ * stays a NaN (clip_grad_value_).  At most one of the two.  The gradient tensors `g` are WRITTEN despite their const type (the
+ * signature mirrors acx_adamw_multi_dev's): they are left holding the clipped mean.  With both off this IS acx_adamw_multi_dev. */
+int acx_adamw_multi_dev_clip(acx_ctx* ctx, int32_t nseg, void* const* p, const void* const* g, void* const* m, void* const* v,
+                             const int64_t* n, const float* hyper_dev, float grad_scale, double beta1, double beta2, double eps,
+                             const float* clip_dev, float clip_value, void* stream);
+/* the same clipping applied in place to the gradient tensors alone (an optimizer whose step is not libacx's) */
+int acx_clip_grads(acx_ctx* ctx, int32_t nseg, void* const* g, const int64_t* n, float grad_scale, const float* clip_dev,
+                   float clip_value, void* stream);
 /* SyncBatchNorm payload of a rank (configs/trainer/ddp.yaml:9): out[2 C1 + 1] = [mean | biased var * rows | rows] */
 int acx_bn_pack(acx_ctx* ctx, const float* mean, const float* var_biased, int64_t rows, int32_t C1, float* out,
                 void* stream);

@@ -7,6 +7,9 @@ the head -- text encoder + selector + axial temporal transformer + loss, forward
     python tools/bench_head.py [--batch 64] [--steps 10] [--warmup 2]
     python tools/bench_head.py --num-segments 24 --seg-length 10 --emb-size 256 --heads 4     # another segment grid / head geometry
     python -m torch.distributed.run --nproc-per-node N tools/bench_head.py --gpus N [--scaling strong|weak]
+    python tools/bench_head.py --gradient-clip-val 1.0 [--gradient-clip-algorithm value]    # Trainer(gradient_clip_val=...)
+    python tools/bench_head.py --clip-study 3 [--emulate-world 8]    # clipping off / norm / value alternated in ONE process, three
+                                                      # repetitions each, + the norm launch and the text AdamW launch timed alone
     python tools/bench_head.py --emulate-world 8      # ONE GPU: rank 0's share of an 8-rank strong-scaling step
                                                       # (8 videos, 2 of 14 text classes, collectives stubbed out):
                                                       # per-rank compute + launch overhead = the efficiency ceiling
@@ -122,6 +125,76 @@ def grid_batch(B_global, world, rank, dev, rows, num_classes, normal_id, step_se
     return ((f_loc[h:], l_loc[h:]), (f_loc[:h], l_loc[:h])), idx
 
 
+def clip_study(args, mod, net, opt, timer, train_step, clip, eff_world, videos):
+    """Clipping off / "norm" / "value" alternated in this process (each has its own captured step graph), args.clip_study
+    repetitions of args.steps steps each; then, with HIP events, the launches the "norm" sequence can expose at worst -- the
+    acx_grad_norm launch over the step's gradients and the text parameters' AdamW launch -- and acx_probe_read of the same bytes."""
+    from anomalyclip_amd import _lib as L
+    from anomalyclip_amd import ops
+    val = args.gradient_clip_val if args.gradient_clip_val else 1.0
+    modes = {"off": (None, None), "norm": (val, "norm"), "value": (val, "value")}
+    ms = {k: [] for k in modes}
+    coef = {}
+    for k, (v, a) in modes.items():                      # capture + warm-up of every mode before any timing
+        clip.update(gradient_clip_val=v, gradient_clip_algorithm=a)
+        timer.run(train_step, 0, max(args.warmup, 2))
+    for _ in range(args.clip_study):
+        for k, (v, a) in modes.items():
+            clip.update(gradient_clip_val=v, gradient_clip_algorithm=a)
+            ms[k].append(round(timer.run(train_step, args.steps, 1) / args.steps * 1e3, 4))
+            if k == "norm":
+                coef[k] = float(mod.last_clip_coef)
+    sgs = [v for v in mod.__dict__.get("_step_graphs", {}).values() if v is not None]
+    sg = next((g for g in sgs if g.clip_algo == "norm"), None)
+    out = {"metric": "training step with gradient clipping, ms per step (one process, modes alternated)", "ms_per_step": ms,
+           "steps_per_repetition": args.steps, "clip_val": val, "last_clip_coef_norm": coef.get("norm"),
+           "emulated_world": args.emulate_world or None, "videos_this_rank": videos, "step_graphs": len(sgs),
+           "step_graph_error": getattr(mod, "step_graph_error", None)}
+    if sg is None:
+        return out
+
+    def event_ms(fn, n=50):
+        for _ in range(5):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+    grads = [sg.gviews[p] for p in sg.opt_params]
+    nbytes = 4 * sum(g.numel() for g in grads)
+    rec = torch.zeros(4, device=grads[0].device)
+    gscale = 1.0 / eff_world if eff_world > 1 else 1.0
+    norm_ms = event_ms(lambda: ops.grad_norm_(grads, gscale, val, rec, sg.clip_ws))
+    # the text AdamW launch on copies of the text parameters and moments (the timing must not train them)
+    tp = [p.detach().clone() for p in sg.text_params]
+    tg = [sg.gviews[p].clone() for p in sg.text_params]
+    tm, tv = [torch.zeros_like(p) for p in tp], [torch.zeros_like(p) for p in tp]
+    nt = len(tp)
+    adamw_ms = event_ms(lambda: ops.adamw_multi_dev_clip_(tp, tg, tm, tv, sg.hyper_dev[: 1 + 2 * nt], gscale, 0.9, 0.999, 1e-8, rec, 0.0))
+    flat = sg.buckets.flat
+    h = L.ctx(flat.device.index or 0)
+    sink = torch.zeros(64, device=flat.device)
+    st = torch.cuda.current_stream().cuda_stream
+    read_ms = event_ms(lambda: L.check(L.lib().acx_probe_read(h, flat.data_ptr(), min(nbytes, flat.numel() * 4) // 16 * 16, sink.data_ptr(), st), h))
+    off = ms["off"]
+    spread = max(off) - min(off)
+    base = sum(off) / len(off)
+    out.update({
+        "grad_norm_launch_ms": round(norm_ms, 5), "text_adamw_launch_ms": round(adamw_ms, 5), "gradient_bytes": nbytes,
+        "gradient_tensors": len(grads), "grad_norm_GBps": round(nbytes / norm_ms / 1e6, 1),
+        "probe_read_ms": round(read_ms, 5), "probe_read_GBps": round(nbytes / read_ms / 1e6, 1),
+        "off_mean_ms": round(base, 4), "off_spread_ms": round(spread, 4),
+        "norm_bound_ms": round(base + norm_ms + adamw_ms + spread, 4), "norm_mean_ms": round(sum(ms["norm"]) / len(ms["norm"]), 4),
+        "norm_within_bound": sum(ms["norm"]) / len(ms["norm"]) <= base + norm_ms + adamw_ms + spread,
+        "value_bound_ms": round(base + spread, 4), "value_mean_ms": round(sum(ms["value"]) / len(ms["value"]), 4),
+        "value_within_bound": sum(ms["value"]) / len(ms["value"]) <= base + spread})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -143,12 +216,20 @@ def main():
     ap.add_argument("--emb-size", type=int, default=0, help="head width (default: the configuration's 256 / 128)")
     ap.add_argument("--heads", type=int, default=0, help="attention heads (default: 8)")
     ap.add_argument("--dim-heads", type=int, default=0, help="head dimension (default: emb_size / heads)")
+    ap.add_argument("--gradient-clip-val", type=float, default=None, help="Trainer(gradient_clip_val=...): clip the step's gradients")
+    ap.add_argument("--gradient-clip-algorithm", default=None, choices=["norm", "value"], help="default: norm")
+    ap.add_argument("--clip-study", type=int, default=0, metavar="REPS",
+                    help="time the training step with clipping off, 'norm' and 'value' alternated REPS times in this process, and the "
+                         "acx_grad_norm launch, the text AdamW launch and acx_probe_read of the gradients' bytes with HIP events; "
+                         "prints one JSON line of its own and exits")
     ap.add_argument("--extra-streams", type=int, default=0,
                     help="development probe: create (and use once) this many HIP streams BEFORE the step graph exists -- the streams of a "
                          "process share GPU_MAX_HW_QUEUES (default 4) hardware queues; a text stream that lands on the main stream's queue "
                          "serialises the step's two chains")
     args = ap.parse_args()
     rank, local_rank, world = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("LOCAL_RANK", 0), ("WORLD_SIZE", 1)))
+    if args.clip_study and world > 1:
+        raise SystemExit("--clip-study is a one-process study: run it without torch.distributed.run (--emulate-world N for a rank's share)")
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dist = None
@@ -216,12 +297,14 @@ def main():
                  L_.ctx(local_rank))
     loss_trace = []
 
+    clip = {"gradient_clip_val": args.gradient_clip_val, "gradient_clip_algorithm": args.gradient_clip_algorithm}
+
     def train_step():
         torch.manual_seed(step_i[0])          # host mask RNG: the global batch's mask, this rank's rows
         step_i[0] += 1
         mt, mb = type(net.selector_model).generate_mask(net.selector_model, B_global)
         net.selector_model.generate_mask = lambda b, mt=mt[idx], mb=mb[idx]: (mt, mb)
-        mod.train_batch(batch, opt)
+        mod.train_batch(batch, opt, **clip)
         if len(loss_trace) < 4:
             loss_trace.append(mod.last_losses[0].detach().clone())
 
@@ -233,6 +316,10 @@ def main():
             net(x, None, mod.ncentroid, 1, True)
             net.train()
 
+    if args.clip_study:
+        if rank == 0:
+            print(json.dumps(clip_study(args, mod, net, opt, timer, train_step, clip, eff_world, len(idx))))
+        return
     if os.environ.get("ACX_CPROFILE"):
         # where the HOST spends a step (development aid): cumulative-time table of 20 steps to stderr
         import cProfile
@@ -280,6 +367,8 @@ def main():
             "num_segments": N, "seg_length": Lg, "emb_size": hc.emb_size, "heads": hc.heads, "head_dim": hc.e,
             "x6_convs": bool(net.temporal_model.x6_convs()),
             "global_batch_videos": B_global, "scaling": args.scaling, "dtype": "f32",
+            "gradient_clip_val": args.gradient_clip_val, "gradient_clip_algorithm": args.gradient_clip_algorithm,
+            "last_clip_coef": float(mod.last_clip_coef) if args.gradient_clip_val else None,
             "loss": float(mod.last_losses[0].detach()), "first_losses": [round(float(v), 6) for v in loss_trace], "data": "synthetic"}))
     if world > 1:
         dist.barrier()
