@@ -15,6 +15,7 @@ BF16X2P, ACX_F16, F16X2P = 4, 5, 6                     # hi + mid planes only; f
 PREC_F32, PREC_BF16, PREC_F32X6, PREC_F32X3, PREC_F16X3 = 0, 1, 2, 3, 4
 PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet encoder on the plane kernel (precision "bf16x6")
 PREC_F32X6_LN16 = 6                     # acx_vit_encode_ln16 only: PREC_F32X6 with the LayerNorm-fed products on fp16 planes (what "auto" resolves to)
+PREC_F32X6_R16 = 7                      # acx_vit_encode_r16 only: PREC_F32X6_LN16 with out-proj and c_proj on fp16 planes too ("auto", every proof passing)
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
@@ -57,7 +58,7 @@ class GemmDesc(C.Structure):
         ("counters", c_void_p), ("n_counters", c_int32),
         ("tile_table", c_void_p),
         ("pairs", c_int32), ("panels", c_int32), ("a_plane_stride", c_int64), ("w_plane_stride", c_int64),
-        ("c_plane_rows", c_int64), ("out_scale", c_float),
+        ("c_plane_rows", c_int64), ("out_scale", c_float), ("c_scale", c_float),
     ]
 
 
@@ -78,6 +79,8 @@ class TfProduct(C.Structure):     # acx_tf_product_t: one of a layer's four prod
 
 
 class TfLayerPlan(C.Structure):   # acx_tf_layer_plan_t: what the transformer driver launches for one layer
+    # (`reserved`: the record's last word under the name it had while it was always 0 -- acx_tf_layer_plan_t.att_out_dtype, F16X2P where
+    # the attention writes fp16 planes, PREC_F32X6_R16 only)
     _fields_ = [(n, c_int32) for n in ("ln1", "ln1_dtype", "ln2", "ln2_dtype")] + \
                [(n, TfProduct) for n in ("in_proj", "out_proj", "fc", "proj")] + \
                [(n, c_int32) for n in ("att", "att_products", "split_att", "split_mlp", "pruned", "reserved")]
@@ -198,6 +201,7 @@ _SIGS = {
     "acx_attention_p3": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3n": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3f": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_p3f16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3_panel": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls_fold_workspace_bytes": (c_size_t, [c_int32, c_int32]),
@@ -221,6 +225,8 @@ _SIGS = {
                                  c_void_p, c_size_t, c_void_p]),
     "acx_vit_encode_ln16": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_void_p, c_int32, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    "acx_vit_encode_r16": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
     "acx_transformer_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "acx_transformer_workspace_bytes_prec": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_transformer_forward": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -32,7 +32,8 @@ from .. import ops
 # "auto" on the CLIP ViT widths (768, 1024) additionally runs the two LayerNorm-fed products of every body layer (in-projection, c_fc)
 # as three-product GEMMs of fp16 planes (ACX_PREC_F32X6_LN16) wherever they take the plane kernel, when ln16_scales() proves, from the
 # weights alone, that their operands stay inside fp16's range whatever the frames are; otherwise -- and always under "f32x6" -- six
-# products everywhere.
+# products everywhere.  One step wider (ACX_PREC_F32X6_R16), when r16_scales() also proves the attention output and the MLP hidden inside
+# fp16's range from the weights: out-proj and c_proj read fp16 planes as well, written by the attention's and c_fc's epilogues.
 PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32x6": L.PREC_F32X6, "bf16x3": L.PREC_F32X3,
               "f16x3": L.PREC_F16X3}
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
@@ -77,13 +78,27 @@ def ln16_scale(bound: float) -> Optional[float]:
 
 
 @torch.no_grad()
-def ln16_scales(blocks, width: int) -> Optional[List[float]]:
-    """The weight-only proof behind ACX_PREC_F32X6_LN16 for a list of ResidualAttentionBlocks: [s(ln_1), s(ln_2)] per block (the
-    power-of-two scales of the LayerNorms' fp16 planes), or None when a condition fails -- a gamma, beta, in-projection or c_fc
-    weight that is not finite, a LayerNorm bound that is not > 0, a scale outside 2^-20 ... 2^20, or 2^10 max|w| > 2^15.  The frames play
-    no part: a LayerNorm output obeys |y_i| <= |gamma_i| sqrt(D - 1) + |beta_i| for every finite input row."""
+def r16_bounds(ln_w, ln_b, w, b):
+    """fp64 bound on |W_j . LayerNorm(x) + b_j| per output row j, for EVERY finite input row x: (L1, L2) -- both valid, r16_scales takes the
+    smaller one row by row.  With y = gamma o z + beta, z the normalised row (sum z = 0, ||z||_2^2 = D var / (var + eps) <= D, so also
+    |z_i| <= sqrt(D - 1)):
+      L1_j = max_i(|gamma_i| sqrt(D - 1) + |beta_i|) ||W_j||_1 + |b_j|           (Hoelder on |y_i| <= the LayerNorm bound)
+      L2_j = sqrt(D) ||W_j o gamma||_2 + |W_j . beta + b_j|                       (W_j . y + b_j = (W_j o gamma) . z + (W_j . beta + b_j);
+                                                                                  Cauchy-Schwarz on the first term with ||z||_2 <= sqrt(D))
+    L2 keeps the signs of beta and the spread of W_j o gamma over its D elements: typically 2^4 - 2^5 below L1."""
+    g, be, w64, b64 = ln_w.detach().double(), ln_b.detach().double(), w.detach().double(), b.detach().double()
+    D = g.numel()
+    l1 = (g.abs() * float(D - 1) ** 0.5 + be.abs()).max() * w64.abs().sum(1) + b64.abs()
+    l2 = float(D) ** 0.5 * (w64 * g).pow(2).sum(1).sqrt() + (w64 @ be + b64).abs()
+    return l1, l2
+
+
+@torch.no_grad()
+def _range_proofs(blocks, width: int):
+    """(ln16_scales, r16_scales) of a list of blocks from ONE device-to-host transfer; see the two functions"""
     vals = []
-    root = float(width - 1) ** 0.5
+    D = width
+    root = float(D - 1) ** 0.5
     for b in blocks:
         for ln in (b.ln_1, b.ln_2):
             g, be = ln.weight.detach().double(), ln.bias.detach().double()
@@ -92,19 +107,55 @@ def ln16_scales(blocks, width: int) -> Optional[List[float]]:
         for wt in (b.attn.in_proj_weight, b.mlp.c_fc.weight):
             vals.append(wt.detach().abs().max().double())
             vals.append(wt.detach().double().abs().sum())
+        # the operands of the two residual products: rows of V = W_v ln_1(x) + b_v, of the c_fc pre-activation W_fc ln_2(x) + b_fc
+        for ln, wt, bias in ((b.ln_1, b.attn.in_proj_weight[2 * D:], b.attn.in_proj_bias[2 * D:]), (b.ln_2, b.mlp.c_fc.weight, b.mlp.c_fc.bias)):
+            l1, l2 = r16_bounds(ln.weight, ln.bias, wt, bias)
+            vals.append(torch.minimum(l1, l2).max() + 0.0 * (l1.sum() + l2.sum()))   # (0 * inf = NaN: nothing non-finite hides behind the min)
+        for wt in (b.attn.out_proj.weight, b.mlp.c_proj.weight):
+            vals.append(wt.detach().abs().max().double())
+            vals.append(wt.detach().double().abs().sum())
     if not vals:
-        return None
+        return None, None
     v = torch.stack(vals).tolist()                                         # one transfer
-    out: List[float] = []
-    for i in range(0, len(v), 8):
-        b1, f1, b2, f2, w1, g1, w2, g2 = v[i:i + 8]
-        if not all(math.isfinite(t) for t in (f1, f2, g1, g2)) or not (w1 <= LN16_WEIGHT_MAX and w2 <= LN16_WEIGHT_MAX):
-            return None
-        s1, s2 = ln16_scale(b1), ln16_scale(b2)
-        if s1 is None or s2 is None:
-            return None
-        out += [s1, s2]
-    return out
+    ln16: Optional[List[float]] = []
+    r16: Optional[List[float]] = []
+    for i in range(0, len(v), 14):
+        b1, f1, b2, f2, w1, g1, w2, g2, ba, bh, w3, g3, w4, g4 = v[i:i + 14]
+        if ln16 is not None:
+            s1, s2 = ln16_scale(b1), ln16_scale(b2)
+            if not all(math.isfinite(t) for t in (f1, f2, g1, g2)) or not (w1 <= LN16_WEIGHT_MAX and w2 <= LN16_WEIGHT_MAX) or s1 is None or s2 is None:
+                ln16 = r16 = None
+            else:
+                ln16 += [s1, s2]
+        if r16 is not None:
+            sa, sh = ln16_scale(ba), ln16_scale(bh)
+            if not all(math.isfinite(t) for t in (g3, g4)) or not (w3 <= LN16_WEIGHT_MAX and w4 <= LN16_WEIGHT_MAX) or sa is None or sh is None:
+                r16 = None
+            else:
+                r16 += [sa, sh]
+    return ln16, r16
+
+
+def ln16_scales(blocks, width: int) -> Optional[List[float]]:
+    """The weight-only proof behind ACX_PREC_F32X6_LN16 for a list of ResidualAttentionBlocks: [s(ln_1), s(ln_2)] per block (the
+    power-of-two scales of the LayerNorms' fp16 planes), or None when a condition fails -- a gamma, beta, in-projection or c_fc
+    weight that is not finite, a LayerNorm bound that is not > 0, a scale outside 2^-20 ... 2^20, or 2^10 max|w| > 2^15.  The frames play
+    no part: a LayerNorm output obeys |y_i| <= |gamma_i| sqrt(D - 1) + |beta_i| for every finite input row."""
+    return _range_proofs(blocks, width)[0]
+
+
+def r16_scales(blocks, width: int) -> Optional[List[float]]:
+    """The weight-only proof behind ACX_PREC_F32X6_R16, on top of ln16_scales': [s_att, s_hid] per block -- the power-of-two scales of the
+    fp16 planes of the attention output (out-proj's A operand) and of the MLP hidden (c_proj's) -- or None when ln16_scales refuses or a
+    new condition fails: out_proj.weight or c_proj.weight not finite or 2^10 max|w| > 2^15, a bound that is not a finite positive number,
+    a scale outside 2^-20 ... 2^20.  The frames play no part:
+      * an attention output row is a convex combination (softmax weights) of V rows, so |o_j| <= max over tokens of |v_j|, and
+        v_j = W_v,j . ln_1(x) + b_v,j is bounded by r16_bounds;
+      * the hidden is QuickGELU(h), |h sigmoid(1.702 h)| <= |h|, and h_j = W_fc,j . ln_2(x) + b_fc,j is bounded by r16_bounds.
+    The bound of a block is max_j min(L1_j, L2_j); s is the largest power of two with s * bound <= 2^14 (ln16_scale).  A larger s matters:
+    an fp16 pair holds s * a only to an absolute 2^-25 once |s * a| < 2^-3, so s decides how small an element may be before it loses
+    relative accuracy."""
+    return _range_proofs(blocks, width)[1]
 
 
 HEAD_MAX_AXIS = 128                                    # acx_axial_attention: 1 <= axis length <= 128 on either axis
@@ -202,9 +253,10 @@ class Transformer(nn.Module):
     def _key(self, prec):
         return (prec, ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def block_table(self, prec: int, ln16_fc: bool = True):
-        """ln16_fc (PREC_F32X6_LN16 only): c_fc's weight as fp16 planes too (False: a library built to keep c_fc six-product)"""
-        key = self._key(prec) + (bool(ln16_fc),)
+    def block_table(self, prec: int, ln16_fc: bool = True, r16=(True, True)):
+        """ln16_fc (PREC_F32X6_LN16 / _R16): c_fc's weight as fp16 planes too (False: a library built to keep c_fc six-product);
+        r16 (PREC_F32X6_R16): (out_proj's, c_proj's) weight as fp16 planes -- what the driver's plan says for the geometry"""
+        key = self._key(prec) + (bool(ln16_fc), bool(r16[0]), bool(r16[1]))
         if self._cache is not None and self._cache[0] == key:
             return self._cache[1]
         arr = (L.BlockWeights * self.layers)()
@@ -217,13 +269,17 @@ class Transformer(nn.Module):
             w.out_proj_w, w.out_proj_b = b.attn.out_proj.weight.data_ptr(), b.attn.out_proj.bias.data_ptr()
             w.fc_w, w.fc_b = b.mlp.c_fc.weight.data_ptr(), b.mlp.c_fc.bias.data_ptr()
             w.proj_w, w.proj_b = b.mlp.c_proj.weight.data_ptr(), b.mlp.c_proj.bias.data_ptr()
-            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16):
+            mixed = prec in (L.PREC_F32X6_LN16, L.PREC_F32X6_R16)
+            f16w = {"in_proj_w_bf16": mixed, "fc_w_bf16": mixed and ln16_fc, "out_proj_w_bf16": prec == L.PREC_F32X6_R16 and r16[0],
+                    "proj_w_bf16": prec == L.PREC_F32X6_R16 and r16[1]}
+            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16, L.PREC_F32X6_R16):
                 for name, p in (("in_proj_w_bf16", b.attn.in_proj_weight), ("out_proj_w_bf16", b.attn.out_proj.weight),
                                 ("fc_w_bf16", b.mlp.c_fc.weight), ("proj_w_bf16", b.mlp.c_proj.weight)):
                     # bf16 mode: one rounded copy; f32x6: the three planes hi | mid | lo of the f32 weight, each in K-panel
                     # layout [K / 32][N][32] (ACX_BF16X3P: what acx_transformer_forward's bf16 x 6 products read)
                     # PREC_F32X6_LN16: fp16 planes for the LayerNorm-fed products, the six-product planes for the other two
-                    if prec == L.PREC_F16X3 or (prec == L.PREC_F32X6_LN16 and (name == "in_proj_w_bf16" or (name == "fc_w_bf16" and ln16_fc))):
+                    # PREC_F32X6_R16: fp16 planes for the residual products the plan moves as well
+                    if prec == L.PREC_F16X3 or f16w[name]:
                         # two fp16 planes of 2^10 w (K-panel layout)
                         t = ops.split_f16x2(p.detach(), panel=True, scale=F16X3_WSCALE)
                     else:
@@ -283,7 +339,7 @@ class VisionTransformer(nn.Module):
         # graph now picks a stream that runs beside its caller's -- ops.side_stream_beside, profiles/r06_stream_queues.txt).
         self.streams = streams
         self._wcache = None
-        self._ln16 = None                                  # (key, (scales, ctypes array, c_fc on fp16 planes) or None): "auto"'s resolution
+        self._ln16 = None                                  # (key, (scales, ctypes array, c_fc on fp16 planes, r16 or None) or None): "auto"'s resolution
         self._ws: Optional[torch.Tensor] = None
         self._ws2: Optional[torch.Tensor] = None
         self._side = None
@@ -323,18 +379,29 @@ class VisionTransformer(nn.Module):
         return {"bounds": worst, "fp16_max": lim, "margin": margin, "safe": margin > 1.0}
 
     def _ln16_bound(self):
-        """(scales, their ctypes array, whether c_fc's weight is bound as fp16 planes) or None, cached with the weights"""
+        """(scales, their ctypes array, whether c_fc's weight is bound as fp16 planes, r16) or None, cached with the weights; r16: None, or
+        ([ln_1, ln_2, att, hid] scales per layer, their ctypes array, (out_proj, c_proj) weights bound as fp16 planes) where the wider
+        proof passes too and the driver's plan moves at least one residual product of this geometry"""
         key = (ops.WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._ln16 is not None and self._ln16[0] == key:
             return self._ln16[1]
         res = None
         if self.width in (768, 1024) and self.layers > 1 and L.exports("acx_vit_encode_ln16"):
-            scales = ln16_scales(self.transformer.resblocks, self.width)
+            scales, wide = _range_proofs(self.transformer.resblocks, self.width)
             if scales is not None:
                 # c_fc's weight format is a constant of the library's build (a tools build may keep c_fc six-product): its plan says which
                 # (asked at a shape whose c_fc is a plane product whatever this model's geometry is)
                 fc16 = ops.transformer_plan(64, 197, 768, 12, 2, prec=L.PREC_F32X6_LN16, prune_last=True)[0]["ln2_dtype"] == L.F16X2P
-                res = (scales, (C.c_float * len(scales))(*scales), fc16)
+                r16 = None
+                if wide is not None and L.exports("acx_vit_encode_r16"):
+                    # which residual products read fp16 planes is the plan's answer for THIS geometry (out-proj: behind the planes
+                    # attention only; build constants); wherever such a product is a plane product the answer is the same at every batch
+                    rec = ops.transformer_plan(64, self.tokens, self.width, self.heads, 2, prec=L.PREC_F32X6_R16, prune_last=True)[0]
+                    fmt = (rec["reserved"] == L.F16X2P, rec["fc"]["c_dtype"] == L.F16X2P)
+                    if any(fmt):
+                        s4 = [t for l in range(self.layers) for t in (scales[2 * l], scales[2 * l + 1], wide[2 * l], wide[2 * l + 1])]
+                        r16 = (s4, (C.c_float * len(s4))(*s4), fmt)
+                res = (scales, (C.c_float * len(scales))(*scales), fc16, r16)
         self._ln16 = (key, res)
         return res
 
@@ -346,8 +413,15 @@ class VisionTransformer(nn.Module):
         res = self._ln16_bound()
         return None if res is None else res[0]
 
-    def _weights(self, prec: int, ln16_fc: bool = True):
-        key = (prec, bool(ln16_fc), ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+    def r16_resolution(self) -> Optional[List[float]]:
+        """The plane scales [ln_1, ln_2, att, hid] per layer of ACX_PREC_F32X6_R16 when "auto" resolves to it for the weights as they
+        are -- ln16_resolution's conditions, r16_scales' proof, and a geometry one of whose residual products the driver moves; None
+        otherwise (ln16_resolution then says whether it is ACX_PREC_F32X6_LN16 or six products everywhere)."""
+        res = self._ln16_bound()
+        return None if res is None or res[3] is None else res[3][0]
+
+    def _weights(self, prec: int, ln16_fc: bool = True, r16=(True, True)):
+        key = (prec, bool(ln16_fc), bool(r16[0]), bool(r16[1]), ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._wcache is not None and self._wcache[0] == key:
             return self._wcache[1]
         keep = []
@@ -360,7 +434,7 @@ class VisionTransformer(nn.Module):
             cb, pb = ops.cast_bf16(conv), ops.cast_bf16(proj_t)
             keep += [cb, pb]
             w.conv1_w_bf16, w.proj_t_bf16 = cb.data_ptr(), pb.data_ptr()
-        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16) and self.patch_size % 4 == 0:
+        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16, L.PREC_F32X6_R16) and self.patch_size % 4 == 0:
             # the patch embedding as a bf16 x 6 product: the weight's three planes in K-panel layout (ACX_BF16X3P; a patch of 14,
             # K = 588, is not a whole number of 32-column panels: acx_vit_encode embeds it on the f32 kernels)
             cb = ops.split_f16x2(conv, panel=True, scale=F16X3_WSCALE) if prec == L.PREC_F16X3 else ops.split_bf16x3(conv, panel=True)
@@ -370,7 +444,7 @@ class VisionTransformer(nn.Module):
         w.positional_embedding = self.positional_embedding.data_ptr()
         w.ln_pre_w, w.ln_pre_b = self.ln_pre.weight.data_ptr(), self.ln_pre.bias.data_ptr()
         w.ln_post_w, w.ln_post_b = self.ln_post.weight.data_ptr(), self.ln_post.bias.data_ptr()
-        arr, keep2 = self.transformer.block_table(prec, ln16_fc)
+        arr, keep2 = self.transformer.block_table(prec, ln16_fc, r16)
         w.blocks = C.cast(arr, C.POINTER(L.BlockWeights))
         keep += [arr, keep2]
         self._wcache = (key, (w, keep))
@@ -384,15 +458,20 @@ class VisionTransformer(nn.Module):
         prec = PRECISIONS[self.precision]
         lib = L.lib()
         bound = self._ln16_bound() if self.precision == "auto" and x.is_cuda else None
-        ln16_fc = True
-        if bound is not None:
+        ln16_fc, r16 = True, (True, True)
+        if bound is not None and bound[3] is not None:
+            prec = L.PREC_F32X6_R16
+            ln16_fc = bound[2]
+            _s4, sc4, r16 = bound[3]
+            encode = lambda *a: lib.acx_vit_encode_r16(a[0], a[1], a[2], sc4, *a[3:])
+        elif bound is not None:
             prec = L.PREC_F32X6_LN16
-            _scales, sc, ln16_fc = bound
+            _scales, sc, ln16_fc, _ = bound
             encode = lambda *a: lib.acx_vit_encode_ln16(a[0], a[1], a[2], sc, *a[3:])
         else:
             encode = lib.acx_vit_encode
         d = L.VitDesc(self.input_resolution, self.patch_size, self.width, self.layers, self.heads, self.output_dim, prec)
-        w, _keep = self._weights(prec, ln16_fc)
+        w, _keep = self._weights(prec, ln16_fc, r16)
         F = x.shape[0]
         out = torch.empty(F, self.output_dim, dtype=torch.float32, device=x.device)
         chunk = min(self.chunk, F)

@@ -14,6 +14,13 @@
 #define ACX_LN16_FC_DEFAULT 1      // ACX_PREC_F32X6_LN16: c_fc on fp16 planes as well as the in-projection (the A/B build that measures the in-projection alone: 0)
 #endif
 
+#ifndef ACX_R16_OUT_DEFAULT
+#define ACX_R16_OUT_DEFAULT 1      // ACX_PREC_F32X6_R16: out-proj on fp16 planes (the A/B build that measures c_proj alone: 0)
+#endif
+#ifndef ACX_R16_PROJ_DEFAULT
+#define ACX_R16_PROJ_DEFAULT 1     // ACX_PREC_F32X6_R16: c_proj on fp16 planes (the A/B build that measures out-proj alone: 0)
+#endif
+
 #ifndef ACX_CLS_FOLD_DEFAULT
 #define ACX_CLS_FOLD_DEFAULT 1     // ACX_OPT_CLS_FOLD as acx_create sets it
 #endif
@@ -26,13 +33,15 @@ struct TfOpts {
   int x6_min_tiles;                              // ACX_OPT_X6_MIN_TILES
   bool attn_f32in, cls_fold;                     // ACX_OPT_ATTN_F32IN, ACX_OPT_CLS_FOLD
   bool ln16_fc;                                  // ACX_LN16_FC_DEFAULT (a build constant)
+  bool r16_out, r16_proj;                        // ACX_R16_OUT_DEFAULT, ACX_R16_PROJ_DEFAULT (build constants)
 };
-constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0, ACX_LN16_FC_DEFAULT != 0};
-constexpr TfOpts kNoCtxOpts = {512, false, false, ACX_LN16_FC_DEFAULT != 0};   // a driver called with ctx == NULL
+constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0, ACX_LN16_FC_DEFAULT != 0, ACX_R16_OUT_DEFAULT != 0,
+                                ACX_R16_PROJ_DEFAULT != 0};
+constexpr TfOpts kNoCtxOpts = {512, false, false, ACX_LN16_FC_DEFAULT != 0, ACX_R16_OUT_DEFAULT != 0, ACX_R16_PROJ_DEFAULT != 0};   // a driver called with ctx == NULL
 // query: acx_transformer_plan, which answers for a context as acx_create leaves it when it has none (like the other route queries)
 inline TfOpts tf_opts(const acx_ctx* ctx, bool query) {
   if (!ctx) return query ? kCreateOpts : kNoCtxOpts;
-  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0, kCreateOpts.ln16_fc};
+  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0, kCreateOpts.ln16_fc, kCreateOpts.r16_out, kCreateOpts.r16_proj};
 }
 }  // namespace
 
@@ -214,8 +223,11 @@ struct TfWs {   // transformer scratch carved from the caller's workspace
 
 // the plane modes of the drivers: ACX_PREC_F32X6 (six products: f32-accurate) and ACX_PREC_F32X3 (the three leading products)
 static inline bool is_xmode(int prec) {
-  return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3 || prec == ACX_PREC_F32X6_LN16;
+  return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3 || prec == ACX_PREC_F32X6_LN16 ||
+         prec == ACX_PREC_F32X6_R16;
 }
+// the six-product modes whose LayerNorm-fed products read fp16 planes (ACX_PREC_F32X6_R16: the residual products too)
+static inline bool is_ln16(int prec) { return prec == ACX_PREC_F32X6_LN16 || prec == ACX_PREC_F32X6_R16; }
 struct XMode {
   int pairs;                                     // acx_gemm_desc.pairs of the driver's plane products (and the attention's products)
   bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
@@ -281,6 +293,8 @@ struct Product {
   const acx_ln_job* ln;        // plane kernel: the LayerNorm of the output rows follows (acx_gemm_ln: part of it rides in the last round)
   float a_scale;               // plane kernel, ACX_PREC_F32X6_LN16: > 0 = A is the fp16 pair planes of a_scale * (LayerNorm output), Wb the fp16
                                // pair planes of 2^10 w: three products, the accumulator leaves multiplied by 2^-10 / a_scale.  0: the mode's planes
+                               // (ACX_PREC_F32X6_R16: the same for the planes of a_scale * (attention output) / a_scale * (MLP hidden))
+  float c_scale;               // plane kernel, ACX_PREC_F32X6_R16's c_fc: > 0 = C is the fp16 pair planes of c_scale * value (acx_gemm_desc.c_scale)
 };
 
 struct TfMode {
@@ -313,6 +327,7 @@ int run_x6(acx_ctx* ctx, XMode xm, const Product& p, hipStream_t s) {
   if (p.a_scale > 0.f) xm = {3, true};
   d.a_dtype = xm.f16 ? ACX_F16 : ACX_BF16; d.prec = ACX_PREC_BF16; d.pairs = xm.pairs; d.panels = 3;
   d.out_scale = p.a_scale > 0.f ? 1.f / (ACX_F16X3_WSCALE * p.a_scale) : xm.f16 ? 1.f / ACX_F16X3_WSCALE : 0.f;
+  d.c_scale = p.c_scale;
   d.a_plane_stride = (int64_t)p.M * p.lda * 2;
   d.w_plane_stride = p.w_plane_bytes ? p.w_plane_bytes : (int64_t)p.N * p.K * 2;
   // scratch for the K split of a partly filled last round of tiles (acx_gemm: row-major outputs only)
@@ -379,6 +394,7 @@ struct TfHave { bool f32[4], alt[4]; };   // in_proj, out_proj, fc, proj of ever
 struct TfPlan {
   TfMode mode;
   bool ln16_qkv, ln16_fc;      // ACX_PREC_F32X6_LN16: the in-projection / c_fc of the body layers run on fp16 planes (ln_1 / ln_2 write them)
+  bool r16_out, r16_proj;      // ACX_PREC_F32X6_R16: out-proj / c_proj of the body layers run on fp16 planes (the attention / c_fc write them)
   acx_tf_layer_plan_t body, before_pruned, pruned;   // the three layer shapes (before_pruned: body with the pruned layer's ln_1 job)
   bool prune;
 };
@@ -414,8 +430,9 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   const bool ln_ride = m.pdt == ACX_BF16X3P;
   // ACX_PREC_F32X6_LN16: the plane-kernel in-projection and (ACX_LN16_FC_DEFAULT) c_fc read fp16 pair planes -- their weights come in that
   // format, so the rule is per product and holds for every geometry; everything else is the six-product plan below, record for record
-  const bool ln16 = g.prec == ACX_PREC_F32X6_LN16;
-  if (ln16 && W != 768 && W != 1024) return acx_fail(err, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F32X6_LN16 is built for widths 768 and 1024%s");
+  const bool ln16 = is_ln16(g.prec), r16 = g.prec == ACX_PREC_F32X6_R16;
+  if (ln16 && W != 768 && W != 1024)
+    return acx_fail(err, ACX_E_UNSUPPORTED, "driver: %s is built for widths 768 and 1024", r16 ? "ACX_PREC_F32X6_R16" : "ACX_PREC_F32X6_LN16");
   p->ln16_qkv = ln16 && x6_qkv;
   p->ln16_fc = ln16 && x6_fc && o.ln16_fc;
   // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
@@ -424,7 +441,13 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
   const bool att_p3 = x6_qkv && x6_out && !g.causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
   // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
-  const bool att_p3f = att_p3 && ln_ride && o.attn_f32in;
+  // ACX_PREC_F32X6_R16: a residual product goes fp16 only where it AND its producer take the plane kernels -- out-proj behind the planes
+  // attention (whose f32-rows arm writes the fp16 planes: taken whatever ACX_OPT_ATTN_F32IN says, out-proj's weights come as fp16 planes
+  // for this sequence length), c_proj behind a c_fc that itself reads fp16 planes.  The rule depends on the geometry's L and W and the
+  // build constants alone wherever the product is a plane product, so the caller binds the weights by one plan query.
+  p->r16_out = r16 && o.r16_out && att_p3;
+  p->r16_proj = r16 && o.r16_proj && p->ln16_fc && x6_proj;
+  const bool att_p3f = att_p3 && ln_ride && (o.attn_f32in || p->r16_out);
   const bool qkv_planes = att_p3 && !att_p3f;
   // ... or on f32 rows, writing the out-projection's three planes itself
   const bool att_x3 = x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
@@ -462,12 +485,13 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
                       : qkv_planes ? tf_x6(cpl, ACX_TF_BUF_QKV, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
   b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
   b.att_products = b.att == ACX_TF_ATT_P3N ? (m.xm.f16 ? 103 : m.xm.pairs) : 0;
+  b.att_out_dtype = p->r16_out ? ACX_F16X2P : 0;
   b.split_att = x6_out && !att_x3 && !att_p3;
   b.out_proj = x6_out ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_fc) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
   b.ln2 = !x6_fc ? ACX_TF_LN_ROWS : b.out_proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
   b.ln2_dtype = p->ln16_fc ? ACX_F16X2P : x6_fc ? m.pdt : m.hdt;
   // QuickGELU(c_fc) straight into the planes of c_proj's input when c_proj takes the plane kernel too
-  b.fc = !x6_fc ? tf_rows(m.hdt, ACX_TF_BUF_SPLITK) : x6_proj ? tf_x6(cpl, ACX_TF_BUF_MLP, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
+  b.fc = !x6_fc ? tf_rows(m.hdt, ACX_TF_BUF_SPLITK) : x6_proj ? tf_x6(p->r16_proj ? ACX_F16X2P : cpl, ACX_TF_BUF_MLP, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
   b.split_mlp = x6_proj && !x6_fc;
   // c_proj carries the next layer's ln_1 where that writes planes: a whole layer with its in-projection on the plane kernel ...
   b.proj = x6_proj ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_qkv) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
@@ -504,10 +528,13 @@ int tf_plan_call(acx_ctx* ctx, const TfGeom& g, const acx_block_weights* blk, Tf
 // ---- the executor: walks the layers and launches what the records say ----------------------------------------------------------
 struct TfRun {
   acx_ctx* ctx; const TfGeom& g; const TfMode& m; const TfWs& ws; hipStream_t s;
-  const float* ln_scales;      // ACX_PREC_F32X6_LN16: [2 layers] plane scales of ln_1, ln_2 (host)
+  const float* ln_scales;      // ACX_PREC_F32X6_LN16: [2 layers] plane scales of ln_1, ln_2; ACX_PREC_F32X6_R16: [4 layers] ln_1, ln_2, att, hid (host)
   int64_t rows() const { return (int64_t)g.batch * g.L; }
+  bool r16() const { return g.prec == ACX_PREC_F32X6_R16; }
   // the scale of LayerNorm `which` (0 ln_1, 1 ln_2) of layer l where it writes ACX_PREC_F32X6_LN16's fp16 planes, else 0
-  float lnsc(int dtype, int l, int which) const { return g.prec == ACX_PREC_F32X6_LN16 && dtype == ACX_F16X2P ? ln_scales[2 * l + which] : 0.f; }
+  float lnsc(int dtype, int l, int which) const { return is_ln16(g.prec) && dtype == ACX_F16X2P ? ln_scales[(r16() ? 4 : 2) * l + which] : 0.f; }
+  // ACX_PREC_F32X6_R16: the scale of layer l's attention output (which = 2) / MLP hidden (3) where `dtype` says it leaves as fp16 planes, else 0
+  float r16sc(int dtype, int l, int which) const { return r16() && dtype == ACX_F16X2P ? ln_scales[4 * l + which] : 0.f; }
 
   // product i (0 in_proj, 1 out_proj, 2 fc, 3 proj) of block b on M rows, run as r says; A, C and residual are the caller's to set
   Product product(const acx_block_weights& b, int i, const acx_tf_product_t& r, int64_t M) const {
@@ -552,6 +579,7 @@ struct TfRun {
     const int W = g.W, batch = g.batch, L = g.L, heads = g.heads;
     auto planes = [](const acx_tf_product_t& q) { return q.c_dtype != ACX_F32 && q.c_dtype != ACX_BF16; };
     const float sc1 = lnsc(r.ln1_dtype, l, 0), sc2 = lnsc(r.ln2_dtype, l, 1);
+    const float s_att = r16sc(r.att_out_dtype, l, 2), s_hid = r16sc(r.fc.c_dtype, l, 3);
     int rc;
     if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b, sc1))) return rc;
     Product p = product(b, 0, r.in_proj, rows());
@@ -561,15 +589,24 @@ struct TfRun {
     if ((rc = go(p))) return rc;
     switch (r.att) {
       case ACX_TF_ATT_BF16: rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s); break;
-      case ACX_TF_ATT_P3F: rc = acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s); break;   // f32 rows in, planes out
+      case ACX_TF_ATT_P3F:                                                                                               // f32 rows in, planes out
+        rc = s_att > 0.f ? acx_attention_p3f16(ctx, (const float*)ws.qkv, 3 * W, ws.hp, s_att, batch, L, heads, s)
+                         : acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s);
+        break;
       case ACX_TF_ATT_P3N: rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, r.att_products, s); break;        // planes in, planes out
       case ACX_TF_ATT_X3_PANEL: rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s); break;
       default: rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, g.causal, s); break;
     }
     if (rc) return rc;
     if (r.split_att && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.att, W, ws.hp, rows() * W * 2, rows(), W, s))) return rc;
-    const acx_ln_job ln2 = job(b.ln2_w, b.ln2_b, sc2);   // (ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln)
+    // ws.hp: out-proj's A planes AND ln_2's output -- disjoint rows, acx_gemm_ln.  ACX_PREC_F32X6_R16 (s_att > 0): A is TWO fp16 planes
+    // with the geometry of the two ln_2 writes (plane = [W / 32][rows][32] u16, N == K), so a rider's plane row r is exactly A's plane row
+    // r: the riders write rows below `ride` <= the rows the full rounds completed, the tiles of the last round read rows at or above
+    // them, and the full rounds -- which read every row -- are an earlier launch on the same stream.  The argument never used the
+    // planes' number format or count, only that row r of y and row r of A are the same bytes.
+    const acx_ln_job ln2 = job(b.ln2_w, b.ln2_b, sc2);
     p = product(b, 1, r.out_proj, rows());
+    p.a_scale = r.out_proj.kernel == ACX_TF_GEMM_X6 ? s_att : 0.f;
     p.A = r.out_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.att;
     p.a_dtype = r.att == ACX_TF_ATT_BF16 ? ACX_BF16 : ACX_F32;
     p.C = x; p.residual = x;
@@ -578,12 +615,14 @@ struct TfRun {
     if ((rc = norm_all(r.ln2, r.ln2_dtype, x, b.ln2_w, b.ln2_b, sc2))) return rc;
     p = product(b, 2, r.fc, rows());
     p.a_scale = r.fc.kernel == ACX_TF_GEMM_X6 ? sc2 : 0.f;
+    p.c_scale = s_hid;
     p.A = r.fc.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
     p.C = planes(r.fc) ? ws.mp : ws.mlp;
     if ((rc = go(p))) return rc;
     if (r.split_mlp && (rc = acx_split_bf16x3_panel(ctx, (const float*)ws.mlp, 4 * W, ws.mp, rows() * 4 * W * 2, rows(), 4 * W, s))) return rc;
     const acx_ln_job ln1 = r.proj.ln_job ? job(next->ln1_w, next->ln1_b, lnsc(next_ln1_dtype, l + 1, 0)) : job(nullptr, nullptr);
     p = product(b, 3, r.proj, rows());
+    p.a_scale = r.proj.kernel == ACX_TF_GEMM_X6 ? s_hid : 0.f;
     p.A = r.proj.kernel == ACX_TF_GEMM_X6 ? ws.mp : ws.mlp;
     p.C = x; p.residual = x;
     p.ln = r.proj.ln_job ? &ln1 : nullptr;
@@ -655,6 +694,15 @@ int transformer_layers(acx_ctx* ctx, float* x, const TfGeom& g, const TfPlan& pl
       const float sc = ln_scales[i];
       if (!(sc >= 0x1p-20f && sc <= 0x1p20f) || frexpf(sc, &e) != 0.5f)
         return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_LN16: a LayerNorm plane scale is not a power of two in [2^-20, 2^20]%s");
+    }
+  }
+  if (g.prec == ACX_PREC_F32X6_R16) {
+    if (!ln_scales) return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
+    for (int i = 0; i < 4 * g.layers; ++i) {
+      int e = 0;
+      const float sc = ln_scales[i];
+      if (!(sc >= 0x1p-20f && sc <= 0x1p20f) || frexpf(sc, &e) != 0.5f)
+        return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_R16: a plane scale is not a power of two in [2^-20, 2^20]%s");
     }
   }
   const TfRun exec = {ctx, g, plan.mode, ws, s, ln_scales};
@@ -740,6 +788,8 @@ static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights
   if (!d || !w || !frames || !features || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: null pointer%s");
   if (d->prec == ACX_PREC_F32X6_LN16 && !ln_scales)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_LN16 needs the LayerNorm plane scales (acx_vit_encode_ln16)%s");
+  if (d->prec == ACX_PREC_F32X6_R16 && !ln_scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
   if (nframes <= 0) return ACX_OK;
   if (d->width != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64%s");
   if (d->patch <= 0 || d->resolution % d->patch || d->patch % 2)
@@ -804,4 +854,11 @@ extern "C" int acx_vit_encode_ln16(acx_ctx* ctx, const acx_vit_desc* d, const ac
   if (!d || d->prec != ACX_PREC_F32X6_LN16 || !ln_scales)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode_ln16: needs desc->prec = ACX_PREC_F32X6_LN16 and the LayerNorm plane scales%s");
   return vit_encode(ctx, d, w, ln_scales, frames, nframes, features, workspace, workspace_bytes, stream);
+}
+
+extern "C" int acx_vit_encode_r16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* scales, const float* frames,
+                                  int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!d || d->prec != ACX_PREC_F32X6_R16 || !scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode_r16: needs desc->prec = ACX_PREC_F32X6_R16 and the plane scales%s");
+  return vit_encode(ctx, d, w, scales, frames, nframes, features, workspace, workspace_bytes, stream);
 }

@@ -76,10 +76,10 @@ extern "C" int acx_attention(acx_ctx* ctx, const float* qkv, int64_t ldqkv, floa
 }
 
 // The launch of attn_p3_kernel for acx_attention_p3n (form 6 / 3: products on bf16 planes, 103: three products on fp16 planes) and
-// acx_attention_p3f (form 0: `src` is the f32 matrix, ldqkv its leading dimension): persistent, one workgroup per CU; `name` is
-// the entry point's, for the launch check
+// acx_attention_p3f (form 0: `src` is the f32 matrix, ldqkv its leading dimension; form 16: acx_attention_p3f16, the same with the two
+// fp16 planes of oscale * o out): persistent, one workgroup per CU; `name` is the entry point's, for the launch check
 static int ap3_launch(acx_ctx* ctx, int form, const void* src, int64_t ldqkv, void* out_planes, int32_t batch, int32_t L, int32_t heads,
-                      void* stream, const char* name) {
+                      void* stream, const char* name, float oscale = 1.f) {
   const int64_t rows = (int64_t)batch * L;
   const int nitems = batch * heads;
   const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
@@ -98,6 +98,9 @@ static int ap3_launch(acx_ctx* ctx, int form, const void* src, int64_t ldqkv, vo
   if (form == 103) ACX_AP3(rows * 3 * heads * 64, 3, 1);
   else if (form == 3) ACX_AP3(rows * 3 * heads * 64, 3);
   else if (form == 6) ACX_AP3(rows * 3 * heads * 64, 6);
+  else if (form == 16)
+    acx_launch_lds<attn_p3_o16_kernel>(dev_slot, grid, dim3(512), (size_t)AP3_LDS_B, s, (const u16*)src, ldqkv, rows, (u16*)out_planes,
+                                       rows * heads * 64, L, heads, nitems, trace_, oscale);
   else ACX_AP3(ldqkv, 6, 0, 1);
 #undef ACX_AP3
   ACX_CHECK_LAUNCH(ctx, name);
@@ -133,6 +136,19 @@ extern "C" int acx_attention_p3f(acx_ctx* ctx, const float* qkv, int64_t ldqkv, 
   if (L <= 192 || L > AP3_ROWS || heads <= 0 || ldqkv < (int64_t)3 * heads * 64 || (ldqkv & 3) || (((uintptr_t)qkv | (uintptr_t)out_planes) & 15))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3f: 192 < L <= 208, 16-byte aligned qkv and planes, ldqkv %% 4 == 0 and >= 3 heads * 64%s");
   return ap3_launch(ctx, 0, qkv, ldqkv, out_planes, batch, L, heads, stream, "acx_attention_p3f");
+}
+
+// ... with the epilogue writing the two fp16 planes of out_scale * o (ACX_F16X2P): the out-projection's A operand in ACX_PREC_F32X6_R16
+extern "C" int acx_attention_p3f16(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, float out_scale, int32_t batch, int32_t L,
+                                   int32_t heads, void* stream) {
+  if (!qkv || !out_planes) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_p3f16: null pointer%s");
+  int e = 0;
+  if (!(out_scale >= 0x1p-20f && out_scale <= 0x1p20f) || frexpf(out_scale, &e) != 0.5f)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_attention_p3f16: out_scale must be a power of two in [2^-20, 2^20]%s");
+  if (batch <= 0) return ACX_OK;
+  if (L <= 192 || L > AP3_ROWS || heads <= 0 || ldqkv < (int64_t)3 * heads * 64 || (ldqkv & 3) || (((uintptr_t)qkv | (uintptr_t)out_planes) & 15))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3f16: 192 < L <= 208, 16-byte aligned qkv and planes, ldqkv %% 4 == 0 and >= 3 heads * 64%s");
+  return ap3_launch(ctx, 16, qkv, ldqkv, out_planes, batch, L, heads, stream, "acx_attention_p3f16", out_scale);
 }
 
 extern "C" int acx_attention_x3(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,

@@ -104,11 +104,18 @@ __device__ __forceinline__ void ap3f_stage_k(char* smem, const float* __restrict
 //   * V(item) dealt over all eight waves as in AP3_STAGE_SHARED: loads issued right behind B1, split and written behind the
 //     phase's MFMAs, every wave waits for its own LDS writes (lgkmcnt) in front of B2;
 //   * a query wave loads its Q fragments as f32 (8 x 16 B per lane) and splits them into qf[0..2][ks].
-template <int NPROD, int F16 = 0, int F32IN = 0>
-__global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
-                                                         u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
-                                                         long long* __restrict__ trace) {
+// O16 (with F32IN: attn_p3_o16_kernel, acx_attention_p3f16): the epilogue writes the TWO fp16 planes of oscale * o (ACX_F16X2P, the F16
+// arm's pack sequence) instead of the three bf16 planes of o; oscale, a power of two, folds into the normaliser -- exact.  Everything
+// before the epilogue is the F32IN arm's six-product bf16 code.  The body is shared and inlined into the two kernels below:
+// attn_p3_kernel keeps its name, its arguments and its code.
+template <int NPROD, int F16, int F32IN, int O16>
+__device__ __forceinline__ void attn_p3_body(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
+                                             u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
+                                             long long* __restrict__ trace, float oscale) {
+  static_assert(O16 == 0 || (F32IN != 0 && F16 == 0 && NPROD == 6), "fp16 output planes behind bf16 products: the f32-rows arm");
   constexpr int NPL = NPROD == 3 ? 2 : 3;               // planes of K / V / Q / the output in use
+  constexpr int OF = (F16 != 0 || O16 != 0) ? 1 : 0;    // the output planes' format: fp16 pairs or bf16 triples
+  constexpr int ONPL = O16 ? 2 : NPL;                   // ... and their number
   // development timeline (-DAP3_TRACE=1 builds + ACX_TRACE_PTR): workgroup 0's waves stamp s_memrealtime (100 MHz) at the phase
   // boundaries of their first AP3_TRACE_ITEMS items: trace[(item_ordinal * 8 + wave) * 8 + point]
 #if AP3_TRACE
@@ -355,7 +362,7 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
     // normalise, split into planes, store: lane (query li, hh) holds d = 32 dt + (e & 3) + 8 (e >> 2) + 4 hh, i.e. for every
     // group g4 of four registers an 8-byte piece of its row; v_permlane32_swap pairs the pieces of the two lane halves -- half
     // 0 ends up with d = 16 gp .. + 7, half 1 with d = 16 gp + 8 .. + 15 of the row: 16-byte stores, 12 per wave and item
-    const float inv = 1.f / sum;
+    const float inv = O16 ? (1.f / sum) * oscale : 1.f / sum;
     const int q = 32 * wave + li;
     const bool st_ok = q < L;
 #pragma unroll
@@ -368,16 +375,16 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
           const int g4 = 2 * gp + z;
           const float ov[4] = {oacc[dt][4 * g4] * inv, oacc[dt][4 * g4 + 1] * inv, oacc[dt][4 * g4 + 2] * inv, oacc[dt][4 * g4 + 3] * inv};
           uint2 ph2, pm2, pl2;
-          ph2.x = acx_pk2<F16>(ov[0], ov[1]); ph2.y = acx_pk2<F16>(ov[2], ov[3]);
-          const float r0 = ov[0] - acx_unpk_lo<F16>(ph2.x), r1 = ov[1] - acx_unpk_hi<F16>(ph2.x);
-          const float r2 = ov[2] - acx_unpk_lo<F16>(ph2.y), r3 = ov[3] - acx_unpk_hi<F16>(ph2.y);
-          pm2.x = acx_pk2<F16>(r0, r1); pm2.y = acx_pk2<F16>(r2, r3);
+          ph2.x = acx_pk2<OF>(ov[0], ov[1]); ph2.y = acx_pk2<OF>(ov[2], ov[3]);
+          const float r0 = ov[0] - acx_unpk_lo<OF>(ph2.x), r1 = ov[1] - acx_unpk_hi<OF>(ph2.x);
+          const float r2 = ov[2] - acx_unpk_lo<OF>(ph2.y), r3 = ov[3] - acx_unpk_hi<OF>(ph2.y);
+          pm2.x = acx_pk2<OF>(r0, r1); pm2.y = acx_pk2<OF>(r2, r3);
           pl2.x = f2bf2(r0 - __uint_as_float(pm2.x << 16), r1 - __uint_as_float(pm2.x & 0xffff0000u));
           pl2.y = f2bf2(r2 - __uint_as_float(pm2.y << 16), r3 - __uint_as_float(pm2.y & 0xffff0000u));
           pl_[z][0] = ph2; pl_[z][1] = pm2; pl_[z][2] = pl2;
         }
 #pragma unroll
-        for (int p = 0; p < NPL; ++p) {
+        for (int p = 0; p < ONPL; ++p) {
           // swap(X = piece of g4 = 2 gp, Y = piece of g4 = 2 gp + 1): half 0 gets (own X, partner's X), half 1 (partner's Y, own Y)
           typedef unsigned ap3_u2 __attribute__((ext_vector_type(2)));
           const ap3_u2 w0 = __builtin_amdgcn_permlane32_swap(pl_[0][p].x, pl_[1][p].x, false, false);
@@ -397,4 +404,18 @@ __global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__
 #undef AP3_STAGE_SHARED
 #undef AP3_STAGE
 #undef AP3_GLDS
+}
+
+template <int NPROD, int F16 = 0, int F32IN = 0>
+__global__ __launch_bounds__(512, 2) void attn_p3_kernel(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
+                                                         u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
+                                                         long long* __restrict__ trace) {
+  attn_p3_body<NPROD, F16, F32IN, 0>(qkv3, plane_elems, rows_total, out3, out_plane_elems, L, heads, nitems, trace, 1.f);
+}
+
+// f32 rows in, six bf16 products, the two fp16 planes of oscale * o out (O16)
+__global__ __launch_bounds__(512, 2) void attn_p3_o16_kernel(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
+                                                             u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
+                                                             long long* __restrict__ trace, float oscale) {
+  attn_p3_body<6, 0, 1, 1>(qkv3, plane_elems, rows_total, out3, out_plane_elems, L, heads, nitems, trace, oscale);
 }

@@ -471,6 +471,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
 #define X6_KERNEL gemm_x6_h3_kernel
 #define X6_F16_C_BF16X3 1
 #include "acx_gemm_x6.h"     // gemm_x6_h3_kernel: fp16 operand planes, three products, THREE bf16 output planes (ACX_PREC_F32X6_LN16's c_fc)
+#define X6_KERNEL gemm_x6_r16_kernel
+#define X6_R16 1
+#include "acx_gemm_x6.h"     // gemm_x6_r16_kernel: fp16 operand planes, three products -- scaled fp16 output planes, LayerNorm riders (ACX_PREC_F32X6_R16)
 #include "acx_gemm_tn.h"     // gemm_tn_kernel, gemm_tn_w8_kernel, tn_reduce_kernel
 
 template <int C_BF16>
@@ -605,16 +608,22 @@ static inline double x6_strip_cost(int ni) { return ni == 2 ? 0.55 : 0.45; }
 //     riding (32,736 and 54,560 within 1 % of it; all 87,296 completed rows: slower than not riding), i.e. 4.9-5.4 rows per us and
 //     rider over the tail's ~85 us; at K = 3072 every completed row fits and riding all of them is fastest.  Wider rows in
 //     proportion.  The constant is below the measurement: a rider must not outlast the tail.
-static inline double x6_tail_us(int nks, int strip_ni) { return 0.8 * (2.7 + 4.16 * nks) * (strip_ni == 4 ? 1.0 : x6_strip_cost(strip_ni)); }
+//   * three products (x3: the fp16 residual products of ACX_PREC_F32X6_R16): a K-step issues half the MFMAs, and the kernel can be no
+//     faster than that -- the K loop's term is halved, the epilogue's stays.  A LOWER bound of the tail (c_fc measured 0.66 of its
+//     six-product time): the riders get less than the tail gives, never more, so none outlasts the tiles.
+static inline double x6_tail_us(int nks, int strip_ni, bool x3 = false) {
+  return 0.8 * (2.7 + (x3 ? 2.08 : 4.16) * nks) * (strip_ni == 4 ? 1.0 : x6_strip_cost(strip_ni));
+}
 constexpr double X6_RIDE_ROWS_PER_US_CU = 4.5;
 // rows (even) that ride: the smaller of the rows the full rounds completed (tiles 0 .. tile0_tail of `tiles_n` per row block)
 // and what `riders` workgroups finish within the tail at `rate` rows of 768 columns per us each (<= 0: the constant above)
-static inline long long x6_ride_rows(long long M, int N, int tiles_n, int tile0_tail, int riders, int nks, int strip_ni, double rate) {
+static inline long long x6_ride_rows(long long M, int N, int tiles_n, int tile0_tail, int riders, int nks, int strip_ni, double rate,
+                                     bool x3 = false) {
   if (riders <= 0 || tile0_tail <= 0 || tiles_n <= 0) return 0;
   long long ready = (long long)(tile0_tail / tiles_n) * 256;
   if (ready > M) ready = M;
   if (rate <= 0.0) rate = X6_RIDE_ROWS_PER_US_CU;
-  const double cap = rate * (768.0 / (double)N) * riders * x6_tail_us(nks, strip_ni);
+  const double cap = rate * (768.0 / (double)N) * riders * x6_tail_us(nks, strip_ni, x3);
   long long ride = cap < (double)ready ? (long long)cap : ready;
   return ride > 0 ? ride & ~1ll : 0;
 }
@@ -804,6 +813,7 @@ struct X6PlanIn {
   bool may_ride;                  // LayerNorm rows may ride in the last round (acx_gemm_ln's eligible products)
   long long ride_cap;             // ACX_OPT_LN_RIDER: > 1 = ride up to this many of the completed rows (measurements)
   double rate;                    // rows of 768 columns per us and rider (<= 0: X6_RIDE_ROWS_PER_US_CU)
+  bool x3;                        // three products per K-step: the riders' time budget is the shorter tail's (x6_tail_us)
 };
 struct X6Plan {
   int xt, nks;                    // whole tiles, K-steps
@@ -847,7 +857,7 @@ static X6Plan x6_plan(const X6PlanIn& in) {
     const int t0 = rounds * ncu, tiles_n = in.N / 256;
     p.ready = x6_ride_rows(in.M, in.N, tiles_n, t0, ncu - last_items, p.nks, p.strip_ni, 1e30);
     p.ride = in.ride_cap > 1 ? (in.ride_cap < p.ready ? in.ride_cap : p.ready) & ~1ll
-                             : x6_ride_rows(in.M, in.N, tiles_n, t0, ncu - last_items, p.nks, p.strip_ni, in.rate);
+                             : x6_ride_rows(in.M, in.N, tiles_n, t0, ncu - last_items, p.nks, p.strip_ni, in.rate, in.x3);
     if (p.ride > 0 && p.strip_ni == 4) { p.ride_tile0 = t0; p.ride_rem = rem; }
   }
   p.main_items = (p.strip_ni < 4 ? p.tile0_tail : p.ride_rem ? p.ride_tile0 : p.xt) * p.split;
@@ -1040,6 +1050,10 @@ static void x6_launch(const GemmCall& c, dim3 grid, const Args& g) {
           acx_launch_lds<gemm_x6_h3_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
           return;
         }
+        if (c.a_f16 && c.d->c_scale != 0.f && c.d->c_scale != 1.f) {   // fp16 pair planes of c_scale * value: gemm_x6_r16_kernel
+          acx_launch_lds<gemm_x6_r16_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          return;
+        }
       }
       if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       else acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
@@ -1081,10 +1095,11 @@ static void x6_launch_strips(const GemmCall& c, bool c_x3, dim3 grid, const Args
   else if (act == ACX_ACT_QUICKGELU) x6_launch<0, 1, 0, 0, NI>(c, grid, g);
   else x6_launch<0, 0, 0, 0, NI>(c, grid, g);
 }
-// a last round with LayerNorm riders (RIDE = 1: the f32 residual epilogue)
+// a last round with LayerNorm riders (RIDE = 1: the f32 residual epilogue); three products of fp16 planes: gemm_x6_r16_kernel
 template <int NI>
 static void x6_launch_ride(const GemmCall& c, dim3 grid, const Args& g) {
-  acx_launch_lds<gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI, 0, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  if (c.d->pairs == 3) acx_launch_lds<gemm_x6_r16_kernel<0, 0, 1, 0, 0, 0, NI, 0, 2, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  else acx_launch_lds<gemm_x6_p4_kernel<0, 0, 1, 0, 0, 0, NI, 0, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
 }
 // job != nullptr (acx_gemm_ln): *ridden = the rows 0 .. *ridden of the job's LayerNorm that rode in the product's last round (0: none)
 static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, long long* ridden) {
@@ -1097,6 +1112,11 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   const bool c_x3_ = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
   if (c.a_f16 && c_x3_ && d->c_dtype != ACX_F16X2P && d->c_dtype != ACX_BF16X3P)
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: fp16 operand planes write fp16 output planes (ACX_F16X2P) or K-panel bf16 planes (ACX_BF16X3P)%s");
+  if (c.a_f16 && d->c_dtype == ACX_F16X2P && d->c_scale != 0.f) {
+    int e = 0;
+    if (!(d->c_scale >= 0x1p-20f && d->c_scale <= 0x1p20f) || frexpf(d->c_scale, &e) != 0.5f)
+      return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: c_scale must be a power of two in [2^-20, 2^20]%s");
+  }
   const bool shape_ok = x6_operands_ok(c) &&
       d->lda % 8 == 0 && d->ldw % 8 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
       !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && d->a_plane_stride > 0 && d->w_plane_stride > 0 &&
@@ -1131,12 +1151,14 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
   in.may_strip = !conv && d->N % 256 == 0 && !c_bf16 && d->act != ACX_ACT_LEAKYRELU && !c.relu_act && x6_strip_enabled(ctx);
   in.strip_force = ctx ? ctx->opt_x6_strip : 1;
   in.tail_split_opt = ctx && ctx->opt_x6_tail;
-  in.may_ride = job && ridden && !conv && !x3 && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
+  // (three products ride on fp16 planes only: the residual products of ACX_PREC_F32X6_R16)
+  in.may_ride = job && ridden && !conv && (!x3 || c.a_f16) && d->residual && !c_x3_ && !c_bf16 && d->act == ACX_ACT_NONE && d->N % 256 == 0 &&
       (d->N == 768 || d->N == 1024) && d->ldc == d->N && !(d->M & 1) && (job->y_dtype == ACX_BF16X3P || job->y_dtype == ACX_F16X2P) &&
       job->w && job->b && job->y &&
       !((uintptr_t)job->y & 15) && !(((long long)d->M * d->N * 2) & 15) && ACX_DBG_SWITCH("LN_RIDER", true) && ctx && ctx->opt_ln_rider;
   in.ride_cap = ctx ? ctx->opt_ln_rider : 0;
   in.rate = 0.0;
+  in.x3 = x3;
   const X6Plan p = x6_plan(in);
   if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_X6, p.split, 1, p.xt);
 

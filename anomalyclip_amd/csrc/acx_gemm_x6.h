@@ -142,12 +142,19 @@ __device__ __forceinline__ T& x6_sel(T& a, T& b) {
 #ifndef X6_F16_C_BF16X3
 #define X6_F16_C_BF16X3 0
 #endif
+// X6_R16 (a switch of the inclusion as well): 1 = gemm_x6_r16_kernel, the fp16 three-product form (X3 = 2) as ACX_PREC_F32X6_R16 runs it on
+// the products whose A operand is not a LayerNorm output -- (a) the fp16 pair planes a plane output (C_MODE = 2) writes hold
+// acx_gemm_desc.c_scale * value, one multiply by a power of two behind the activation (c_fc: the scale of c_proj's A operand); (b) the
+// f32 residual epilogue may carry LayerNorm riders (RIDE = 1: out-proj, c_proj).  0: every instantiation compiles to what it was.
+#ifndef X6_R16
+#define X6_R16 0
+#endif
 template <int C_MODE, int ACT, int RES, int CONV, int TN = 0, int PLAIN = 0, int NI = 4, int W14 = 0, int X3 = 0, int RIDE = 0>
 __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
   static_assert(X3 == 0 || (CONV == 0 && TN == 0 && PLAIN == 0 && W14 == 0), "three-product mode: identity rows, NT");
   static_assert(CONV != 2 || (TN == 0 && PLAIN == 0 && NI == 4), "general convolution row map: NT products, whole tiles");
   static_assert(ACT != ACX_ACT_RESRELU || (RES == 1 && C_MODE == 0 && CONV == 0), "ReLU after the residual: f32 output, identity rows");
-  static_assert(RIDE == 0 || (C_MODE == 0 && ACT == 0 && RES == 1 && CONV == 0 && TN == 0 && PLAIN == 0 && X3 == 0), "LayerNorm rider: the residual products");
+  static_assert(RIDE == 0 || (C_MODE == 0 && ACT == 0 && RES == 1 && CONV == 0 && TN == 0 && PLAIN == 0 && (X3 == 0 || (X6_R16 && X3 == 2))), "LayerNorm rider: the residual products");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const acx_gemm_desc& d = g.d;
   const int t = threadIdx.x, lane = t & 63;
@@ -751,6 +758,8 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
       char* scr = smem + 8 * X6_UNIT_B + wave * 4096;
       // fp16 planes (X3 = 2): the operands' power-of-two scales leave here; the other instantiations multiply by the CONSTANT 1 (no code)
       const float osc_ = (X3 == 2) ? (d.out_scale != 0.f ? d.out_scale : 1.f) : 1.f;
+      const float csc_ = (X6_R16 && X3 == 2 && C_MODE == 2) ? (d.c_scale != 0.f ? d.c_scale : 1.f) : 1.f;   // (X6_R16: the output planes' scale)
+      (void)csc_;
       const int rl = lane >> 3, cj = lane & 7;
       const int colw = n0 + wn * 32 * NI + 4 * cj;   // + 32 ni
       const int roww = m0 + wm * 128 + rl;       // + 32 mi + 8 ps
@@ -814,6 +823,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
           if constexpr (ACT == ACX_ACT_QUICKGELU) ov[e] = acx_quickgelu(ov[e]);                    \
           else if constexpr (ACT == ACX_ACT_LEAKYRELU) ov[e] = ov[e] > 0.f ? ov[e] : 0.01f * ov[e]; \
           else if constexpr (ACT == ACX_ACT_RELU) ov[e] = fmaxf(ov[e], 0.f);                       \
+          if constexpr (X6_R16 != 0 && X3 == 2) ov[e] *= csc_;   /* exact: a power of two */       \
         }                                                                                          \
         /* three bf16 planes hi | mid | lo of the f32 value (ACX_BF16X3): the next pairs = 6 product's A operand */ \
         uint4 ph, pm, pl;                                                                          \
@@ -956,3 +966,4 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
 }
 #undef X6_KERNEL
 #undef X6_F16_C_BF16X3
+#undef X6_R16

@@ -362,7 +362,7 @@ def unpanel(planes: torch.Tensor) -> torch.Tensor:
 def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] = None, bias=None, act=L.ACT_NONE,
             residual=None, out_dtype=torch.float32, amap=L.AMAP_IDENTITY, gn=0, gl=0, cin=0, M: Optional[int] = None,
             planes_out: bool = False, split_k: bool = True, panels: int = 0, panel_out: bool = False, pairs: int = 6,
-            out_scale: float = 0.0, ln=None, planes_bf16: bool = False) -> torch.Tensor:
+            out_scale: float = 0.0, ln=None, planes_bf16: bool = False, c_scale: float = 0.0) -> torch.Tensor:
     """out[M, N] = epilogue(amap(A) W^T) with A = sum of the three bf16 planes a3 [3, rows, Ka] and W = sum of w3 [3, N, K]
     (split_bf16x3): the six leading cross products on the bf16 matrix cores, f32 accumulation -- the accuracy of an f32
     product (acx_gemm_desc.pairs = 6; acx_gemm_x6.h).  amap = AMAP_CONV3X3: implicit 3x3 convolution over the (gn, gl) token
@@ -372,7 +372,8 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     (rows of it ride in the product's partly filled last round of tiles; same bits as gemm_x6 + layernorm(panel_out=True)); with a
     fourth entry `scale` and y fp16 [2, M, N]: the two fp16 planes of scale * LayerNorm (layernorm_f16x2).
     planes_bf16 (fp16 operands, planes_out, panel_out): the output planes are the THREE bf16 planes of the f32 value (ACX_BF16X3P) --
-    what a six-product GEMM reads -- instead of fp16 pairs."""
+    what a six-product GEMM reads -- instead of fp16 pairs.
+    c_scale (fp16 operands, fp16 planes out): the output planes hold c_scale * value, a power of two (acx_gemm_desc.c_scale)."""
     f16 = a3.dtype == torch.float16          # two fp16 planes per operand (split_f16x2): pairs = 3 only, out_scale undoes the planes' scales
     if f16:
         assert pairs == 3 and a3.shape[0] == 2 and w3.shape[0] == 2 and w3.dtype == torch.float16 and (panel_out or not planes_out)
@@ -398,6 +399,7 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     d.lda, d.ldw, d.ldc = Ka, K, out.stride(-2)
     d.a_dtype, d.c_dtype, d.prec = _dt(a3), ((L.F16X2P if f16 and not planes_bf16 else L.BF16X3P if panel_out else L.BF16X3) if planes_out else _dt(out)), L.PREC_BF16
     d.out_scale = float(out_scale)
+    d.c_scale = float(c_scale)
     d.bias, d.act = _ptr(bias), act
     d.residual, d.ldr = _ptr(residual), (residual.stride(0) if residual is not None else 0)
     d.pairs, d.a_plane_stride, d.w_plane_stride = int(pairs), rows * Ka * 2, N * K * 2      # (pairs = 3: the three leading products only)
@@ -547,6 +549,17 @@ def attention_p3_f32(qkv: torch.Tensor, batch: int, L_: int, heads: int) -> torc
     out = torch.empty(3, batch * L_, W, dtype=_BF16, device=qkv.device)
     h = _h(qkv)
     L.check(L.lib().acx_attention_p3f(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), batch, L_, heads, _stream()), h)
+    return out
+
+
+def attention_p3_f32_f16(qkv: torch.Tensor, batch: int, L_: int, heads: int, scale: float = 1.0) -> torch.Tensor:
+    """acx_attention_p3f16: attention_p3_f32 with the output as the two fp16 planes of scale * o, [2, batch * L, heads * 64] in K-panel
+    memory order (ACX_F16X2P): the bits split_f16x2(scale * o, panel=True) gives for the f32 o whose planes attention_p3_f32 writes."""
+    W = heads * 64
+    assert qkv.dtype == torch.float32 and qkv.shape == (batch * L_, 3 * W) and qkv.stride(1) == 1
+    out = torch.empty(2, batch * L_, W, dtype=torch.float16, device=qkv.device)
+    h = _h(qkv)
+    L.check(L.lib().acx_attention_p3f16(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), float(scale), batch, L_, heads, _stream()), h)
     return out
 
 

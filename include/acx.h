@@ -77,6 +77,13 @@ enum { ACX_PREC_F32X6_LN16 = 6 }; /* acx_vit_encode_ln16 only: ACX_PREC_F32X6 wi
                                  pruned last layer are ACX_PREC_F32X6's.  Widths 768 and 1024 (the fp16 LayerNorm store).  A tools build with
                                  -DACX_LN16_FC_DEFAULT=0 keeps c_fc a six-product GEMM (fc_w_bf16: three bf16 planes; the A/B arm that
                                  measures the in-projection alone): acx_transformer_plan's ln2_dtype tells the caller which it is */
+enum { ACX_PREC_F32X6_R16 = 7 };  /* acx_vit_encode_r16 only: ACX_PREC_F32X6_LN16 one step wider -- in every body layer the two residual
+                                 products (out-proj, c_proj) read fp16 pair planes as well, where they and their producers take the plane
+                                 kernels: the planes attention (acx_attention_p3f16) writes the two planes of s_att * o, c_fc's QuickGELU
+                                 epilogue those of s_hid * hidden (acx_gemm_desc.c_scale); the weights come as acx_split_f16x2(2^10 w).
+                                 s_att and s_hid are per-layer powers of two the CALLER proves from the weights alone (|o| is a convex
+                                 combination of V rows; |QuickGELU(x)| <= |x|).  Everything else is ACX_PREC_F32X6_LN16's plan, record for
+                                 record.  Tools builds: -DACX_R16_OUT_DEFAULT=0 / -DACX_R16_PROJ_DEFAULT=0 keep that product six-product */
 #define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
 enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
@@ -225,6 +232,9 @@ typedef struct acx_gemm_desc {
                              0: M.  acx_gemm uses it itself when it splits a launch into full rounds of tiles + a K-split tail. */
   float out_scale;        /* pairs = 3 with fp16 planes (a_dtype = ACX_F16): the accumulator is multiplied by this power of two before bias
                              / activation / residual (operand planes that were scaled by acx_split_f16x2); 0 = 1 */
+  float c_scale;          /* pairs = 3 with fp16 planes and c_dtype = ACX_F16X2P: the output planes hold c_scale * value -- one multiply by
+                             this power of two behind the activation (the next product's A operand, whose out_scale undoes it); 0 = 1.
+                             Not read otherwise.  (It fills the padding behind out_scale: the descriptor's size is what it was.) */
 } acx_gemm_desc;
 int acx_gemm(acx_ctx* ctx, const acx_gemm_desc* d, void* stream);
 
@@ -328,6 +338,12 @@ int acx_attention_p3n(acx_ctx* ctx, const void* qkv_planes, void* out_planes, in
  * output planes equal acx_attention_p3's on acx_split_bf16x3_panel(qkv) bit for bit.  Six products only; same L gate. */
 int acx_attention_p3f(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int32_t batch, int32_t L, int32_t heads,
                       void* stream);
+/* acx_attention_p3f with the output as the TWO fp16 planes of out_scale * o in K-panel layout (ACX_F16X2P): q | k | v, both
+ * contractions and the softmax are acx_attention_p3f's six-product bf16 arithmetic, only the epilogue differs -- the planes equal
+ * acx_split_f16x2(out_scale * o, panel) of the f32 value o whose three bf16 planes acx_attention_p3f writes, bit for bit.  out_scale: a
+ * power of two in [2^-20, 2^20]; the caller keeps |out_scale * o| inside fp16's range (|o| <= max |v|). */
+int acx_attention_p3f16(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, float out_scale, int32_t batch, int32_t L,
+                        int32_t heads, void* stream);
 /* ... with the planes in K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo == heads * 64) */
 int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
                            int32_t batch, int32_t L, int32_t heads, void* stream);
@@ -408,6 +424,11 @@ int acx_vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w
  * acx_vit_encode refuses that precision (it has no scales). */
 int acx_vit_encode_ln16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* ln_scales, const float* frames,
                         int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream);
+/* acx_vit_encode with desc->prec = ACX_PREC_F32X6_R16: scales [4 layers] (HOST array), layer l at 4 l: the plane scales of ln_1, ln_2 (as
+ * acx_vit_encode_ln16), of the attention output (s_att) and of the MLP hidden (s_hid) -- powers of two in [2^-20, 2^20] with s * bound <=
+ * 2^14 for a bound the caller proves from the weights; the driver checks only that they are such powers of two. */
+int acx_vit_encode_r16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* scales, const float* frames,
+                       int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The CLIP ResNet image encoders (RN50, RN101, RN50x4, RN50x16, RN50x64: ModifiedResNet, clip/model.py:111-171), eval mode.
@@ -521,7 +542,8 @@ int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, in
  *                  free at this product and serves its K split; ln_job 1: it carries the LayerNorm behind it (acx_gemm_ln).  A
  *                  pruned layer's in_proj is the K | V product of all rows (or none: ACX_TF_ATT_CLS_FOLD); Q, for the CLS rows, is
  *                  always a ROWS product
- *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0)
+ *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0);
+ *                  att_out_dtype: ACX_F16X2P where ACX_TF_ATT_P3F goes out as acx_attention_p3f16, else 0
  *   split_att, split_mlp  1: acx_split_bf16x3_panel of the attention output / the MLP hidden is launched
  *   pruned         1: the last layer, CLS rows only */
 enum { ACX_TF_LN_ROWS = 0, ACX_TF_LN_PLANES = 1, ACX_TF_LN_RIDDEN = 2, ACX_TF_LN_CLS = 3 };
@@ -536,7 +558,10 @@ typedef struct acx_tf_layer_plan_t {
   int32_t ln1, ln1_dtype, ln2, ln2_dtype;
   acx_tf_product_t in_proj, out_proj, fc, proj;
   int32_t att, att_products, split_att, split_mlp;
-  int32_t pruned, reserved;
+  int32_t pruned;
+  int32_t att_out_dtype;  /* the record's last word (the `reserved` word of earlier headers, 0 in every plan they describe):
+                             ACX_F16X2P = the attention writes the two fp16 planes of s_att * o (ACX_PREC_F32X6_R16 with out-proj on fp16
+                             planes: acx_attention_p3f16); 0 = the planes of the mode */
 } acx_tf_layer_plan_t;
 int acx_transformer_plan(const acx_ctx* ctx, int32_t batch, int32_t L, int32_t width, int32_t heads, int32_t layers,
                          int32_t causal, int32_t prec, int32_t prune_last, int32_t has_weight_planes,
