@@ -17,6 +17,7 @@ PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet 
 PREC_F32X6_LN16 = 6                     # acx_vit_encode_ln16 only: PREC_F32X6 with the LayerNorm-fed products on fp16 planes (what "auto" resolves to)
 PREC_F32X6_R16 = 7                      # acx_vit_encode_r16 only: PREC_F32X6_LN16 with out-proj and c_proj on fp16 planes too ("auto", every proof passing)
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
+ACT_GELU = 5                            # the exact GELU 0.5 x (1 + erf(x / sqrt 2)): CLIP checkpoints not trained with QuickGELU
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
 NORM_LAYER, NORM_CHAN = 0, 1
 OPT_RING_MIN_TILES, OPT_SK_MAX_M, OPT_TN_P256_MIN_ROWS, OPT_X6_CUS, OPT_X6_TAIL_SPLIT = 1, 2, 3, 4, 5
@@ -123,8 +124,8 @@ class PrepSeg(C.Structure):            # == struct acx_prep_seg
                 ("dst_ld", c_int32), ("transpose", c_int32), ("reserved", c_int32)]
 
 
-class VitDesc(C.Structure):
-    _fields_ = [(n, c_int32) for n in ("resolution", "patch", "width", "layers", "heads", "embed_dim", "prec")]
+class VitDesc(C.Structure):            # == struct acx_vit_desc (act: 0 / ACT_QUICKGELU or ACT_GELU; ctypes zeroes what is not given)
+    _fields_ = [(n, c_int32) for n in ("resolution", "patch", "width", "layers", "heads", "embed_dim", "prec", "act")]
 
 
 class ResnetConv(C.Structure):          # == struct acx_resnet_conv
@@ -231,6 +232,8 @@ _SIGS = {
     "acx_transformer_workspace_bytes_prec": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_transformer_forward": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, C.POINTER(BlockWeights), c_void_p, c_size_t, c_void_p]),
+    "acx_transformer_forward_act": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                              c_int32, c_int32, C.POINTER(BlockWeights), c_void_p, c_size_t, c_void_p]),
     "acx_transformer_plan": (C.c_int, [c_void_p] + [c_int32] * 10 + [C.POINTER(TfLayerPlan)]),
     "acx_text_directions": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_selector_project": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,

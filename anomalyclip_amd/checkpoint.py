@@ -30,11 +30,48 @@ def split_lightning_state_dict(sd: Mapping[str, torch.Tensor]) -> Dict[str, torc
     return out
 
 
+_CLIP_TEXT_KEYS = ("transformer.", "positional_embedding", "ln_final.", "text_projection")
+_CLIP_DROPPED = ("logit_scale", "input_resolution", "context_length", "vocab_size", "attn_mask")
+
+
+def is_clip_state_dict(sd) -> bool:
+    """a plain CLIP state_dict (OpenAI's non-JIT model.state_dict(), open_clip's open_clip_pytorch_model.bin): it has `visual.` keys"""
+    return isinstance(sd, Mapping) and any(isinstance(k, str) and k.startswith("visual.") for k in sd)
+
+
+def from_clip_state_dict(sd: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A plain CLIP state_dict -> AnomalyCLIP.state_dict() keys: `visual.*` -> `image_encoder.*`; `transformer.*`,
+    `positional_embedding`, `ln_final.*`, `text_projection` -> `text_encoder.*`; `token_embedding.weight` stays; `logit_scale` and
+    the JIT archives' `input_resolution` / `context_length` / `vocab_size` (and open_clip's `attn_mask` buffer) are dropped.  Half
+    tensors are widened to float32.  Any other key is a ValueError: this is not the CLIP module tree the mirrors have.
+    The dict does not say which activation the weights were trained with (OpenAI: "quick_gelu"; open_clip configs without
+    `quick_gelu: true`: "gelu"): that is the caller's `act`."""
+    out = {}
+    for k, v in sd.items():
+        if k in _CLIP_DROPPED:
+            continue
+        if k.startswith("visual."):
+            nk = "image_encoder." + k[len("visual."):]
+        elif k.startswith(_CLIP_TEXT_KEYS):
+            nk = "text_encoder." + k
+        elif k == "token_embedding.weight":
+            nk = k
+        else:
+            raise ValueError(f"not a CLIP state_dict key: {k!r} (expected visual.*, transformer.*, positional_embedding, ln_final.*, "
+                             "text_projection, token_embedding.weight, logit_scale)")
+        out[nk] = v.float() if torch.is_tensor(v) and v.is_floating_point() else v
+    return out
+
+
 def load_into(net: torch.nn.Module, ckpt, strict: bool = True) -> Tuple[list, list]:
-    """ckpt: path to a Lightning .ckpt, the loaded dict, or a bare state_dict."""
+    """ckpt: path to a Lightning .ckpt, the loaded dict, a bare state_dict, or a plain CLIP state_dict (`visual.*` keys: it fills the
+    two CLIP towers and the token embedding, AnomalyCLIP.load_state_dict; `strict` then covers those alone)."""
     if isinstance(ckpt, str):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=False)
     sd = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+    if is_clip_state_dict(sd):
+        missing, unexpected = net.load_state_dict(sd, strict=strict)
+        return list(missing), list(unexpected)
     sd = split_lightning_state_dict(sd)
     missing, unexpected = net.load_state_dict(sd, strict=False)
     # buffers the reference recomputes from the class names are allowed to differ in presence only

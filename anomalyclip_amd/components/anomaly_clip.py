@@ -24,7 +24,7 @@ from torch import nn
 from .. import ops
 from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, RN50, RN101, RN50X4, RN50X16, RN50X64, TINY
 from .clip_resnet import ModifiedResNet, check_resnet_precision
-from .clip_vit import VisionTransformer, check_head_geometry, check_vit_precision
+from .clip_vit import VisionTransformer, check_act, check_head_geometry, check_vit_precision
 from .coop import PromptLearner
 from .selector_model import SelectorModel
 from .temporal_model import TemporalModel
@@ -156,6 +156,10 @@ class AnomalyCLIP(nn.Module):
         if isinstance(geom, dict):
             geom = ClipGeometry(**geom)
         self.geometry = geom
+        # net.act: the activation of BOTH CLIP towers' MLPs, "quick_gelu" (default: OpenAI's checkpoints) or "gelu" (open_clip's LAION-2B /
+        # DataComp checkpoints); not a reference key, like `precision`.  The weights do not say which
+        self.act = g("act") or getattr(geom, "act", "quick_gelu")
+        check_act(self.act, vit_precision if vit_precision == "bf16" else None, self.arch if geom.is_resnet else None, key="net.act")
         if geom.is_resnet:
             check_resnet_precision(vit_precision, self.arch, geom.vision_width)      # (before anything is allocated)
             if geom.embed_dim != geom.transformer_width:
@@ -203,14 +207,14 @@ class AnomalyCLIP(nn.Module):
         full = int(tokenized.shape[-1])
         self.text_len = min(full, (int(tokenized.argmax(dim=-1).max()) + 1 + 3) // 4 * 4) if bool(g("text_truncate", True)) else full
         self.text_encoder = TextEncoder(geom.context_length, geom.transformer_width, geom.transformer_heads,
-                                        geom.transformer_layers, geom.embed_dim, head_precision)
+                                        geom.transformer_layers, geom.embed_dim, head_precision, act=self.act)
         if geom.is_resnet:
             self.image_encoder = ModifiedResNet(geom.vision_layers, geom.embed_dim, geom.resnet_heads, geom.image_resolution,
                                                 geom.vision_width, precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
         else:
             self.image_encoder = VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width,
                                                    geom.vision_layers, geom.vision_heads, geom.embed_dim,
-                                                   precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch)
+                                                   precision=vit_precision, chunk=g("vit_chunk", 512), arch=self.arch, act=self.act)
         self.selector_model = SelectorModel(classnames, self.normal_id, nn.Parameter(torch.tensor(2.6592601)),
                                             self.num_segments, self.seg_length, self.select_idx_dropout_topk,
                                             self.select_idx_dropout_bottomk, self.num_topk, self.num_bottomk)
@@ -237,7 +241,14 @@ class AnomalyCLIP(nn.Module):
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         """nn.Module.load_state_dict, after checking that the image_encoder.* / text_encoder.* tensors of `state_dict` have the
-        shapes of this module's `arch`: a checkpoint of another backbone raises a ValueError naming both geometries."""
+        shapes of this module's `arch`: a checkpoint of another backbone raises a ValueError naming both geometries.
+        A plain CLIP state_dict (`visual.*` keys: checkpoint.from_clip_state_dict) fills the two towers and the token embedding --
+        the prompt learner's frozen prefix / suffix embeddings are taken again from the new table -- and leaves the head as it is;
+        strict then means: every tensor of the towers is there and nothing else is."""
+        from ..checkpoint import from_clip_state_dict, is_clip_state_dict
+        clip = is_clip_state_dict(state_dict)
+        if clip:
+            state_dict = from_clip_state_dict(state_dict)
         mine = self.state_dict()
         bad = [k for k, v in state_dict.items() if k.startswith(("image_encoder.", "text_encoder.")) and torch.is_tensor(v)
                and k in mine and tuple(v.shape) != tuple(mine[k].shape)]
@@ -249,6 +260,19 @@ class AnomalyCLIP(nn.Module):
             raise ValueError(f"the checkpoint's CLIP encoders do not match arch {self.arch!r}: the checkpoint holds "
                              f"{_describe(theirs) if theirs is not None else 'another geometry'}, this module is "
                              f"{_describe(self.geometry)} (first differing tensor: {bad[0]})")
+        if clip:
+            strict = kwargs.pop("strict", args[0] if args else True)
+            res = super().load_state_dict(state_dict, strict=False, **kwargs)
+            towers = ("image_encoder.", "text_encoder.", "token_embedding.")
+            missing = [k for k in res.missing_keys if k.startswith(towers)]
+            if strict and (missing or res.unexpected_keys):
+                raise RuntimeError(f"the CLIP state_dict does not match the module tree: missing={missing} unexpected={list(res.unexpected_keys)}")
+            with torch.no_grad():                              # coop.py:57-66 with the loaded table
+                pl = self.prompt_learner
+                emb = self.token_embedding.weight[pl.tokenized_prompts.long().to(self.token_embedding.weight.device)]
+                pl.token_prefix.copy_(emb[:, :1, :])
+                pl.token_suffix.copy_(emb[:, 1 + pl.n_ctx:, :])
+            return res                                          # (missing_keys: the head's and the prompt learner's, left as they were)
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------------------------------

@@ -37,6 +37,23 @@ from .. import ops
 PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32x6": L.PREC_F32X6, "bf16x3": L.PREC_F32X3,
               "f16x3": L.PREC_F16X3}
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
+# The MLP's activation.  "quick_gelu" (the default): x sigmoid(1.702 x), what OpenAI's checkpoints were trained with.  "gelu": nn.GELU,
+# 0.5 x (1 + erf(x / sqrt 2)), what open_clip's LAION-2B / DataComp checkpoints of the same architectures were trained with (configs
+# without `quick_gelu: true`).  The weights do not say which: the two differ by up to 2e-2 per element and nothing else reports it.
+ACTS = {"quick_gelu": L.ACT_QUICKGELU, "gelu": L.ACT_GELU}
+
+
+def check_act(act, precision: Optional[str] = None, arch: Optional[str] = None, key: str = "act") -> int:
+    """The ACX_ACT_* value of an activation name; a ValueError naming `key` for an unknown one, and one naming both sides for
+    "gelu" with precision "bf16" (the bf16 MFMA routes are no parity path and have no exact-GELU epilogue) or with a ResNet arch
+    (ModifiedResNet has no GELU)."""
+    if act not in ACTS:
+        raise ValueError(f"{key}={act!r}: one of {', '.join(ACTS)}")
+    if act == "gelu" and precision == "bf16":
+        raise ValueError(f"{key}='gelu' with precision='bf16': the exact GELU runs on the f32-accurate paths only ('auto', 'f32', 'f32x6', 'f16x3')")
+    if act == "gelu" and arch is not None and str(arch).startswith("RN"):
+        raise ValueError(f"{key}='gelu' with arch={arch!r}: the CLIP ResNet encoders have no GELU (the activation is the ViT MLP's)")
+    return ACTS[act]
 
 
 # vision geometries (resolution, patch, width) of the backbones added beside ViT-B/16: ViT-B/32, ViT-L/14, ViT-L/14@336px
@@ -151,7 +168,8 @@ def r16_scales(blocks, width: int) -> Optional[List[float]]:
     a scale outside 2^-20 ... 2^20.  The frames play no part:
       * an attention output row is a convex combination (softmax weights) of V rows, so |o_j| <= max over tokens of |v_j|, and
         v_j = W_v,j . ln_1(x) + b_v,j is bounded by r16_bounds;
-      * the hidden is QuickGELU(h), |h sigmoid(1.702 h)| <= |h|, and h_j = W_fc,j . ln_2(x) + b_fc,j is bounded by r16_bounds.
+      * the hidden is act(h) with |act(h)| <= |h| for both activations -- QuickGELU h sigmoid(1.702 h) and the exact GELU h Phi(h)
+        are h times a factor in [0, 1] -- and h_j = W_fc,j . ln_2(x) + b_fc,j is bounded by r16_bounds.
     The bound of a block is max_j min(L1_j, L2_j); s is the largest power of two with s * bound <= 2^14 (ln16_scale).  A larger s matters:
     an fp16 pair holds s * a only to an absolute 2^-25 once |s * a| < 2^-3, so s decides how small an element may be before it loses
     relative accuracy."""
@@ -241,11 +259,13 @@ class ResidualAttentionBlock(nn.Module):
 class Transformer(nn.Module):
     """Holds `resblocks`; executes through acx_transformer_forward (in place on a [rows, W] f32 buffer)."""
 
-    def __init__(self, width: int, layers: int, heads: int, causal: bool = False):
+    def __init__(self, width: int, layers: int, heads: int, causal: bool = False, act: str = "quick_gelu"):
         super().__init__()
         if width != heads * 64:
             raise ValueError("libacx attention kernels are built for head dim 64 (every CLIP ViT/text tower)")
         self.width, self.layers, self.heads, self.causal = width, layers, heads, causal
+        check_act(act)
+        self.act = act
         self.resblocks = nn.ModuleList([ResidualAttentionBlock(width, heads) for _ in range(layers)])
         self._cache = None
 
@@ -297,8 +317,8 @@ class Transformer(nn.Module):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         arr, _keep = self.block_table(prec)
         h = ops._h(x)
-        L.check(lib.acx_transformer_forward(h, x.data_ptr(), batch, seq, self.width, self.heads, self.layers,
-                                            int(self.causal), prec, arr, ws.data_ptr(), nbytes, ops._stream()), h)
+        L.check(lib.acx_transformer_forward_act(h, x.data_ptr(), batch, seq, self.width, self.heads, self.layers,
+                                                int(self.causal), prec, ACTS[self.act], arr, ws.data_ptr(), nbytes, ops._stream()), h)
         return x
 
 
@@ -314,9 +334,12 @@ class VisionTransformer(nn.Module):
     chunks of `chunk` frames (workspace is allocated once per chunk size and reused)."""
 
     def __init__(self, input_resolution: int, patch_size: int, width: int, layers: int, heads: int,
-                 output_dim: int, precision: str = "auto", chunk: int = 512, streams: int = 1, arch: Optional[str] = None):
+                 output_dim: int, precision: str = "auto", chunk: int = 512, streams: int = 1, arch: Optional[str] = None,
+                 act: str = "quick_gelu"):
         super().__init__()
         self.arch = arch or f"ViT(width {width}, patch {patch_size}, resolution {input_resolution})"      # (for messages)
+        check_act(act, precision)
+        self.act = act
         self.input_resolution, self.patch_size, self.output_dim = input_resolution, patch_size, output_dim
         self.width, self.layers, self.heads = width, layers, heads
         self.conv1 = _Conv(width, patch_size)
@@ -324,7 +347,7 @@ class VisionTransformer(nn.Module):
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn((input_resolution // patch_size) ** 2 + 1, width))
         self.ln_pre = LayerNorm(width)
-        self.transformer = Transformer(width, layers, heads)
+        self.transformer = Transformer(width, layers, heads, act=act)
         self.ln_post = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self.precision = precision
@@ -350,6 +373,7 @@ class VisionTransformer(nn.Module):
 
     def check_precision(self):
         check_vit_precision(self.precision, self.tokens, self.width, self.arch, self.input_resolution, self.patch_size)
+        check_act(self.act, self.precision)
 
     @torch.no_grad()
     def f16x3_range_report(self) -> dict:
@@ -357,7 +381,7 @@ class VisionTransformer(nn.Module):
         (whatever the frames are, the patch embedding excepted: its A operand is the pixels themselves):
           LayerNorm outputs   |y_i| <= |gamma_i| sqrt(D - 1) + |beta_i|          (a unit-variance row has no element above sqrt(D - 1))
           attention outputs   convex combinations of V rows: |v_j| <= ln1_bound * ||W_v,j||_1 + |b_v,j|
-          QuickGELU hiddens   |x sigmoid(1.702 x)| <= |x| <= ln2_bound * ||W_fc,j||_1 + |b_fc,j|
+          MLP hiddens         |x sigmoid(1.702 x)| <= |x| and |x Phi(x)| <= |x| (QuickGELU, exact GELU) <= ln2_bound * ||W_fc,j||_1 + |b_fc,j|
           weight planes       2^10 |w|
         against fp16's largest finite number 65504.  `safe` says every bound is below it; `margin` is the smallest ratio 65504 / bound."""
         D = self.width
@@ -470,7 +494,7 @@ class VisionTransformer(nn.Module):
             encode = lambda *a: lib.acx_vit_encode_ln16(a[0], a[1], a[2], sc, *a[3:])
         else:
             encode = lib.acx_vit_encode
-        d = L.VitDesc(self.input_resolution, self.patch_size, self.width, self.layers, self.heads, self.output_dim, prec)
+        d = L.VitDesc(self.input_resolution, self.patch_size, self.width, self.layers, self.heads, self.output_dim, prec, ACTS[self.act])
         w, _keep = self._weights(prec, ln16_fc, r16)
         F = x.shape[0]
         out = torch.empty(F, self.output_dim, dtype=torch.float32, device=x.device)

@@ -46,6 +46,7 @@ def _text_forward_rows(net, ctx_param, text_projection, lo: int, hi: int, tf_out
     C = x0.shape[0]
     x = x0.view(C * Lc, W)
     saved = []
+    gelu = getattr(tr, "act", "quick_gelu") == "gelu"     # the tower's activation: the exact GELU, or QuickGELU (clip_vit.ACTS)
     # few rows (a data-parallel rank's block of classes: 77 rows per class): acx_gemm runs the few-row kernel and the
     # activation / its derivative ride in its prologue / epilogue instead of separate launches
     few = C * Lc <= _few_row_limit(x) and (4 * W) % 256 == 0 and W % 256 == 0
@@ -67,11 +68,11 @@ def _text_forward_rows(net, ctx_param, text_projection, lo: int, hi: int, tf_out
         else:
             h2 = ops.layernorm(x_mid, blk.ln_2.weight, blk.ln_2.bias)
             pre = ops.gemm(h2, blk.mlp.c_fc.weight.detach(), bias=blk.mlp.c_fc.bias.detach())
-        if few:                                       # QuickGELU applied as the few-row GEMM reads its A operand
+        if few:                                       # the activation applied as the few-row GEMM reads its A operand
             x_next = ops.gemm(pre, blk.mlp.c_proj.weight.detach(), bias=blk.mlp.c_proj.bias.detach(), residual=x_mid,
-                              a_act=L.ACT_QUICKGELU)
+                              a_act=L.ACT_GELU if gelu else L.ACT_QUICKGELU)
         else:
-            act = ops.act(pre, None, 2)
+            act = ops.act(pre, None, 4 if gelu else 2)
             x_next = ops.gemm(act, blk.mlp.c_proj.weight.detach(), bias=blk.mlp.c_proj.bias.detach(), residual=x_mid)
         saved.append((x, qkv, x_mid, pre))
         x = x_next
@@ -108,15 +109,17 @@ def _text_backward_rows(net, text_projection, state, d_tf, d_ctx_out=None, d_P_o
     d_x = ops.scatter_rows(d_eot, rows_idx, C * Lc)
     wt = _frozen_transposes(te)
     few = C * Lc <= _few_row_limit(d_x) and (4 * W) % 256 == 0 and W % 256 == 0
+    gelu = getattr(te.transformer, "act", "quick_gelu") == "gelu"
     for li in range(len(saved) - 1, -1, -1):
         blk = te.transformer.resblocks[li]
         x, qkv, x_mid, pre = saved[li]
         t_in, t_out, t_fc, t_proj = wt[li]
         if few:
-            d_pre = ops.gemm(d_x, t_proj, gelu_grad_of=pre)                  # (d_x @ proj_w) * gelu'(pre) in the epilogue
+            # (d_x @ proj_w) * act'(pre) in the epilogue: act = ACT_GELU names the exact GELU's derivative, 0 QuickGELU's
+            d_pre = ops.gemm(d_x, t_proj, gelu_grad_of=pre, act=L.ACT_GELU if gelu else L.ACT_NONE)
         else:
             d_act = ops.gemm(d_x, t_proj)                                    # [rows,4W] = d_x @ proj_w
-            d_pre = ops.act(pre, d_act, 1)
+            d_pre = ops.act(pre, d_act, 3 if gelu else 1)
         d_h2 = ops.gemm(d_pre, t_fc)                                         # [rows,W]
         d_x_mid, _, _ = ops.layernorm_bwd(x_mid, blk.ln_2.weight, d_h2, need_params=False, add=d_x)   # d_x + LN2'
         d_att = ops.gemm(d_x_mid, t_out)

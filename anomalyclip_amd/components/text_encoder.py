@@ -13,9 +13,9 @@ from .clip_vit import LayerNorm, Transformer, PRECISIONS
 
 class TextEncoder(nn.Module):
     def __init__(self, context_length: int, width: int, heads: int, layers: int, embed_dim: int,
-                 precision: str = "f32"):
+                 precision: str = "f32", act: str = "quick_gelu"):
         super().__init__()
-        self.transformer = Transformer(width, layers, heads, causal=True)   # clip/model.py:333-338,386-392
+        self.transformer = Transformer(width, layers, heads, causal=True, act=act)   # clip/model.py:333-338,386-392
         self.positional_embedding = nn.Parameter(torch.empty(context_length, width).normal_(std=0.01))
         self.ln_final = LayerNorm(width)
         self.text_projection = nn.Parameter(torch.empty(width, embed_dim).normal_(std=width ** -0.5))

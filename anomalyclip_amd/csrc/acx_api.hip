@@ -389,7 +389,18 @@ struct TfGeom {
   int batch, L, W, heads, layers, causal, prec;
   bool prune;                  // the LAST layer is evaluated only where its output is consumed: token 0 of every sequence (clip/model.py:285)
   bool planes_ws;              // the workspace holds the planes of a plane mode (TfWs.hp)
+  int act;                     // c_fc's activation, ACX_ACT_QUICKGELU or ACX_ACT_GELU (the executor's alone: tf_plan never reads it)
 };
+
+// the MLP activation a driver was handed: 0 means QuickGELU (callers of the headers before ACX_ACT_GELU); *act = the epilogue's value
+int tf_act(acx_ctx* ctx, const char* who, int32_t given, int prec, int* act) {
+  if (given != 0 && given != ACX_ACT_QUICKGELU && given != ACX_ACT_GELU)
+    return acx_fail(ctx, ACX_E_BADARG, "%s: act must be 0 / ACX_ACT_QUICKGELU or ACX_ACT_GELU", who);
+  if (given == ACX_ACT_GELU && prec == ACX_PREC_BF16)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: ACX_ACT_GELU with ACX_PREC_BF16 (the bf16 MFMA routes are no parity path)", who);
+  *act = given == ACX_ACT_GELU ? ACX_ACT_GELU : ACX_ACT_QUICKGELU;
+  return ACX_OK;
+}
 struct TfHave { bool f32[4], alt[4]; };   // in_proj, out_proj, fc, proj of every block: the f32 weight, the *_w_bf16 copy / planes
 struct TfPlan {
   TfMode mode;
@@ -545,7 +556,7 @@ struct TfRun {
     switch (i) {
       case 0: p.Wf = b.in_proj_w; p.Wb = b.in_proj_w_bf16; p.bias = b.in_proj_b; p.N = 3 * W; p.K = W; break;
       case 1: p.Wf = b.out_proj_w; p.Wb = b.out_proj_w_bf16; p.bias = b.out_proj_b; p.N = W; p.K = W; break;
-      case 2: p.Wf = b.fc_w; p.Wb = b.fc_w_bf16; p.bias = b.fc_b; p.N = 4 * W; p.K = W; p.act = ACX_ACT_QUICKGELU; break;
+      case 2: p.Wf = b.fc_w; p.Wb = b.fc_w_bf16; p.bias = b.fc_b; p.N = 4 * W; p.K = W; p.act = g.act; break;
       default: p.Wf = b.proj_w; p.Wb = b.proj_w_bf16; p.bias = b.proj_b; p.N = W; p.K = 4 * W; break;
     }
     p.lda = p.ldw = p.K; p.ldc = p.N; p.a_dtype = m.hdt;
@@ -731,7 +742,7 @@ extern "C" int acx_transformer_plan(const acx_ctx* ctx, int32_t batch, int32_t L
   acx_ctx* err = const_cast<acx_ctx*>(ctx);      // (the refusal's text)
   if (!out || batch <= 0 || L <= 0 || layers < 0) return acx_fail(err, ACX_E_BADARG, "acx_transformer_plan: no result array or an empty geometry%s");
   memset(out, 0, sizeof(*out) * layers);
-  const TfGeom g = {batch, L, width, heads, layers, causal, prec, prune_last != 0, is_xmode(prec) && workspace_is_prec_sized};
+  const TfGeom g = {batch, L, width, heads, layers, causal, prec, prune_last != 0, is_xmode(prec) && workspace_is_prec_sized, ACX_ACT_QUICKGELU};
   const bool alt = has_weight_planes != 0;
   const TfHave have = {{true, true, true, true}, {alt, alt, alt, alt}};
   TfPlan plan;
@@ -743,14 +754,22 @@ extern "C" int acx_transformer_plan(const acx_ctx* ctx, int32_t batch, int32_t L
 extern "C" int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, int32_t width, int32_t heads,
                                        int32_t layers, int32_t causal, int32_t prec, const acx_block_weights* blocks,
                                        void* workspace, size_t workspace_bytes, void* stream) {
+  return acx_transformer_forward_act(ctx, x, batch, L, width, heads, layers, causal, prec, ACX_ACT_QUICKGELU, blocks, workspace, workspace_bytes, stream);
+}
+
+extern "C" int acx_transformer_forward_act(acx_ctx* ctx, float* x, int32_t batch, int32_t L, int32_t width, int32_t heads,
+                                           int32_t layers, int32_t causal, int32_t prec, int32_t act, const acx_block_weights* blocks,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !blocks || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_transformer_forward: null pointer%s");
+  int mlp_act = 0, rc0;
+  if ((rc0 = tf_act(ctx, "acx_transformer_forward", act, prec, &mlp_act))) return rc0;
   if (width != heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_transformer_forward: head dim must be 64%s");
   // ACX_PREC_F32X6 with a workspace sized for it (acx_transformer_workspace_bytes_prec); a smaller (f32-sized) workspace runs
   // the f32 kernels
   TfWs ws = carve_tf((char*)workspace, (int64_t)batch * L, width, prec);
   if (ws.total > workspace_bytes && is_xmode(prec)) ws = carve_tf((char*)workspace, (int64_t)batch * L, width);
   if (ws.total > workspace_bytes) return acx_fail(ctx, ACX_E_WORKSPACE, "acx_transformer_forward: workspace too small%s");
-  const TfGeom g = {batch, L, width, heads, layers, causal, prec, false, ws.hp != nullptr};
+  const TfGeom g = {batch, L, width, heads, layers, causal, prec, false, ws.hp != nullptr, mlp_act};
   TfPlan plan;
   const int rc = tf_plan_call(ctx, g, blocks, &plan);
   return rc ? rc : transformer_layers(ctx, x, g, plan, blocks, ws, (hipStream_t)stream);
@@ -790,6 +809,8 @@ static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_LN16 needs the LayerNorm plane scales (acx_vit_encode_ln16)%s");
   if (d->prec == ACX_PREC_F32X6_R16 && !ln_scales)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
+  int mlp_act = 0, rc0;
+  if ((rc0 = tf_act(ctx, "acx_vit_encode", d->act, d->prec, &mlp_act))) return rc0;
   if (nframes <= 0) return ACX_OK;
   if (d->width != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64%s");
   if (d->patch <= 0 || d->resolution % d->patch || d->patch % 2)
@@ -803,7 +824,7 @@ static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights
   hipStream_t s = (hipStream_t)stream;
   const TfWs tf = carve_tf((char*)workspace + ws.tf_off, (int64_t)F * (T + 1), W, d->prec);
   const bool prune = ACX_DBG_SWITCH("VIT_PRUNE", true);
-  const TfGeom geom = {F, T + 1, W, d->heads, d->layers, 0, d->prec, prune, tf.hp != nullptr};
+  const TfGeom geom = {F, T + 1, W, d->heads, d->layers, 0, d->prec, prune, tf.hp != nullptr, mlp_act};
   TfPlan plan;
   int rc;
   if ((rc = tf_plan_call(ctx, geom, w->blocks, &plan))) return rc;

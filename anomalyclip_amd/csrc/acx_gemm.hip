@@ -28,7 +28,7 @@
 //   * A-operand prologue fused into the staging pass: f32->bf16 conversion, re-centring
 //     (a - ncentroid[k]), the 3x3-conv row gather (implicit GEMM over the (gn,gl) token grid,
 //     zero padding) and the reference's test-mode tiling gather.
-//   * epilogue fused: bias, QuickGELU / LeakyReLU, axial positional embedding, residual add,
+//   * epilogue fused: bias, QuickGELU / exact GELU / LeakyReLU / ReLU, axial positional embedding, residual add,
 //     f32 or bf16 store.
 //   * XCD-aware 1-D grid: block b runs on XCD b%8; the bijective remap gives every XCD a
 //     contiguous run of tiles (n fastest) so the A tile of a row of tiles stays in that XCD's L2.
@@ -44,6 +44,7 @@
 //   gemm_bf16_p8_kernel      _p8.h       the ring kernel's tile stream on a phase-interleaved schedule
 //   gemm_x6_p4_kernel        _x6.h       pairs = 6 / 3: products of bf16 / fp16 planes, one wave per SIMD; also acx_gemm_tn_x6
 //   gemm_x6_rn_kernel        _x6.h       the same body: the ReLU epilogues and the general 3x3 convolution map (ResNet encoder)
+//   gemm_x6_gelu_kernel, gemm_x6_h3_gelu_kernel, gemm_x6_r16_gelu_kernel   _x6.h   the same body again: the exact-GELU epilogues (ACX_ACT_GELU) of those three
 //   gemm_tn_kernel / _w8 / _p256 / _w8_group  _tn.h   weight gradients C = A^T B (reduction over rows), split-M + reduce
 // (+ the reduce launches of a K split: splitk_reduce_kernel, splitk_reduce4_kernel, tn_reduce_kernel)
 //
@@ -62,6 +63,7 @@
 // acx_gemm_tn* (weight gradients) are dispatched at the bottom of this file.
 #include "acx_internal.h"
 #include "acx_ln_rows.h"     // LnRide, ln_ride_rows: the LayerNorm rider of gemm_x6_p4_kernel
+#include "acx_gelu.h"        // acx_gelu_erf, acx_gelu_erf_grad: the exact GELU
 
 #include <algorithm>
 #include <stdlib.h>
@@ -83,6 +85,16 @@ __device__ __forceinline__ float acx_quickgelu(float v) {
   asm volatile("" : "+v"(r));
   return r;
 }
+
+// The exact GELU of the epilogues (ACX_ACT_GELU: its own template value everywhere, never a branch inside a QuickGELU instantiation);
+// pinned for the plane epilogues as above
+__device__ __forceinline__ float acx_gelu(float v) {
+  float r = acx_gelu_erf(v);
+  asm volatile("" : "+v"(r));
+  return r;
+}
+// the two GELUs take the same routes: a gate that names QuickGELU means either
+static inline bool acx_is_gelu(int act) { return act == ACX_ACT_QUICKGELU || act == ACX_ACT_GELU; }
 
 constexpr int BM = 128, BN = 128;
 constexpr int ROWB = 144;                // LDS row stride in bytes (128 data + 16 pad)
@@ -426,7 +438,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
       for (int r = 0; r < 16; ++r) {
         float v = acc[mi][ni][r] + bias;
         const int act = FAST ? ACT : d.act;
-        if (act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
+        if constexpr (ACT == ACX_ACT_GELU) v = acx_gelu(v);     // (FAST == 0 too: the generic path's instantiation for this activation)
+        else if (act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
         else if (act == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
         else if (act == ACX_ACT_RELU) v = fmaxf(v, 0.f);
         outv[r] += v;
@@ -474,10 +487,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const Args g) {
 #define X6_KERNEL gemm_x6_r16_kernel
 #define X6_R16 1
 #include "acx_gemm_x6.h"     // gemm_x6_r16_kernel: fp16 operand planes, three products -- scaled fp16 output planes, LayerNorm riders (ACX_PREC_F32X6_R16)
+// the exact-GELU epilogues (ACT = ACX_ACT_GELU) of the three kernels above, under names of their own: the instantiation sets of
+// gemm_x6_p4_kernel / _h3_ / _r16_ stay the ones their register tests list
+#define X6_KERNEL gemm_x6_gelu_kernel
+#include "acx_gemm_x6.h"
+#define X6_KERNEL gemm_x6_h3_gelu_kernel
+#define X6_F16_C_BF16X3 1
+#include "acx_gemm_x6.h"
+#define X6_KERNEL gemm_x6_r16_gelu_kernel
+#define X6_R16 1
+#include "acx_gemm_x6.h"
 #include "acx_gemm_tn.h"     // gemm_tn_kernel, gemm_tn_w8_kernel, tn_reduce_kernel
 
-template <int C_BF16>
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+// (GELU = 1: the exact GELU in the activation slot -- the *_gelu_kernel wrappers below; the kernels the other activations launch
+// are the GELU = 0 bodies, unchanged)
+template <int C_BF16, int GELU>
+__device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ part, int splits, const acx_gemm_desc& d) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total = (int64_t)d.M * d.N;
   if (i >= total) return;
@@ -485,7 +510,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   float v = 0.f;
   for (int s = 0; s < splits; ++s) v += part[(size_t)s * total + i];
   if (d.bias) v += d.bias[col];
-  if (d.act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
+  if constexpr (GELU != 0) v = acx_gelu(v);
+  else if (d.act == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
   else if (d.act == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
   else if (d.act == ACX_ACT_RELU) v = fmaxf(v, 0.f);
   // same order as the unsplit kernel's epilogue: (residual + (pos0 + pos1)) + activation(acc + bias)
@@ -505,13 +531,21 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   } else if constexpr (C_BF16 == 1) ((u16*)d.C)[(size_t)row * d.ldc + col] = f2bf(o);
   else ((float*)d.C)[(size_t)row * d.ldc + col] = o;
 }
+template <int C_BF16>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+  splitk_reduce_body<C_BF16, 0>(part, splits, d);
+}
+template <int C_BF16>
+__global__ __launch_bounds__(256) void splitk_reduce_gelu_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+  splitk_reduce_body<C_BF16, 1>(part, splits, d);
+}
 
 // The same, four consecutive columns per lane (N, ldc, ldr multiples of 4, 16-byte aligned bias / residual, no positional
 // epilogue): 16-byte loads of the pieces, 16- / 8-byte stores -- the pairs = 6 kernel's K split at a data-parallel rank's 4096
 // rows pays this launch after every convolution (one column per lane: 24-28 us for 3 x 16.8 MB in, three planes out).
 // OUT: 0 f32, 1 bf16, 2 three bf16 planes (ACX_BF16X3, or ACX_BF16X3P: K-panel layout).  Same arithmetic, same order.
-template <int OUT>
-__global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+template <int OUT, int GELU>
+__device__ __forceinline__ void splitk_reduce4_body(const float* __restrict__ part, int splits, const acx_gemm_desc& d) {
   const int n4 = d.N >> 2;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t total4 = (int64_t)d.M * n4;
@@ -535,7 +569,8 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __rest
   if (d.bias) { const float4 b4 = *reinterpret_cast<const float4*>(d.bias + col); v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w; }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    if (d.act == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);
+    if constexpr (GELU != 0) v[e] = acx_gelu(v[e]);
+    else if (d.act == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);
     else if (d.act == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
     else if (d.act == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
   }
@@ -568,6 +603,14 @@ __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __rest
   } else {
     *reinterpret_cast<float4*>((float*)d.C + (size_t)row * d.ldc + col) = make_float4(o[0], o[1], o[2], o[3]);
   }
+}
+template <int OUT>
+__global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+  splitk_reduce4_body<OUT, 0>(part, splits, d);
+}
+template <int OUT>
+__global__ __launch_bounds__(256) void splitk_reduce4_gelu_kernel(const float* __restrict__ part, int splits, acx_gemm_desc d) {
+  splitk_reduce4_body<OUT, 1>(part, splits, d);
 }
 
 }  // namespace
@@ -704,7 +747,16 @@ static int gemm_validate(acx_ctx* ctx, const acx_gemm_desc* d) {
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_RELU / ACX_ACT_RESRELU need an f32 or a pairs = 6 product on identity or CONV3X3 rows%s");
   if (d->act == ACX_ACT_RESRELU && !d->residual)
     return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: ACX_ACT_RESRELU needs a residual%s");
-  if (d->act < ACX_ACT_NONE || d->act > ACX_ACT_RESRELU) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: unknown act%s");
+  if (d->act < ACX_ACT_NONE || d->act > ACX_ACT_GELU) return acx_fail(ctx, ACX_E_BADARG, "acx_gemm: unknown act%s");
+  // the exact GELU: the routes the two CLIP towers take -- f32 products and the plane kernel (pairs = 6 / 3) on identity rows
+  if (d->act == ACX_ACT_GELU || d->a_act == ACX_ACT_GELU) {
+    if (prec == ACX_PREC_BF16 && d->pairs != 6 && d->pairs != 3)
+      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_GELU needs an f32 product or a pairs = 6 / 3 product of planes (the bf16 MFMA routes are no parity path)%s");
+    if (prec == ACX_PREC_F32 && c_bf16)
+      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_GELU on an f32 product writes f32%s");
+    if (d->amap != ACX_AMAP_IDENTITY)
+      return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: ACX_ACT_GELU runs on identity rows (no CLIP tower has a GELU behind a convolution or a tile map)%s");
+  }
   return ACX_OK;
 }
 
@@ -790,14 +842,22 @@ static void splitk_reduce(const GemmCall& c, const float* partial, int ksplit, b
     const int64_t total4 = (int64_t)d->M * (d->N / 4);
     const dim3 rgrid((unsigned)((total4 + 255) / 256));
     const bool c_x3 = d->c_dtype == ACX_BF16X3 || d->c_dtype == ACX_BF16X3P || d->c_dtype == ACX_F16X2P;
-    if (c_x3) hipLaunchKernelGGL((splitk_reduce4_kernel<2>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+    if (d->act == ACX_ACT_GELU) {
+      if (c_x3) hipLaunchKernelGGL((splitk_reduce4_gelu_kernel<2>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+      else if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce4_gelu_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+      else hipLaunchKernelGGL((splitk_reduce4_gelu_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+    }
+    else if (c_x3) hipLaunchKernelGGL((splitk_reduce4_kernel<2>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
     else if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce4_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
     else hipLaunchKernelGGL((splitk_reduce4_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
     return;
   }
   const int64_t total = (int64_t)d->M * d->N;
   const dim3 rgrid((unsigned)((total + 255) / 256));
-  if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+  if (d->act == ACX_ACT_GELU) {    // (f32 routes only: gemm_validate refuses the exact GELU on the bf16 ones)
+    hipLaunchKernelGGL((splitk_reduce_gelu_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
+  }
+  else if (c.c_bf16) hipLaunchKernelGGL((splitk_reduce_kernel<1>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
   else hipLaunchKernelGGL((splitk_reduce_kernel<0>), rgrid, dim3(256), 0, c.s, partial, ksplit, *d);
 }
 
@@ -965,6 +1025,8 @@ static void sk_launch_epi(const GemmCall& c, int epi, dim3 grid, const Args& g) 
     case SK_EPI_PLAIN: sk_launch<SK_EPI_PLAIN, AG>(c, grid, g); break;
     case SK_EPI_QUICKGELU: sk_launch<SK_EPI_QUICKGELU, AG>(c, grid, g); break;
     case SK_EPI_RES: sk_launch<SK_EPI_RES, AG>(c, grid, g); break;
+    case SK_EPI_GELU: sk_launch<SK_EPI_GELU, AG>(c, grid, g); break;
+    case SK_EPI_GELUGRAD_ERF: sk_launch<SK_EPI_GELUGRAD_ERF, AG>(c, grid, g); break;
     default: sk_launch<SK_EPI_GELUGRAD, AG>(c, grid, g); break;
   }
 }
@@ -991,9 +1053,9 @@ static int route_sk(const GemmCall& c, const Args& base) {
   const bool sk_ok = c.fast && c.prec == ACX_PREC_F32 && !c.c_bf16 && !c.a_bf16 && d->K % SK_CH == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 &&
                      !((uintptr_t)d->C & 15) && (!d->residual || (d->ldr % 4 == 0 && !((uintptr_t)d->residual & 15))) &&
                      (!d->gelu_grad_of || (d->ldg % 4 == 0 && !((uintptr_t)d->gelu_grad_of & 15) && !d->residual &&
-                                           d->act == ACX_ACT_NONE)) &&
-                     !(d->act == ACX_ACT_QUICKGELU && d->residual) && !c.relu_act &&
-                     (d->a_act == ACX_ACT_NONE || d->a_act == ACX_ACT_QUICKGELU) &&
+                                           (d->act == ACX_ACT_NONE || d->act == ACX_ACT_GELU))) &&   // (ACX_ACT_GELU: WHICH derivative)
+                     !(acx_is_gelu(d->act) && d->residual) && !c.relu_act &&
+                     (d->a_act == ACX_ACT_NONE || acx_is_gelu(d->a_act)) &&
                      (size_t)d->M * d->lda < ((size_t)1 << 31) && (size_t)d->N * d->ldw < ((size_t)1 << 31);
   if (sk_fusion && !sk_ok)
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_gemm: a_act / gelu_grad_of / a_norm need the few-row f32 kernel (see acx_gemm_desc)%s");
@@ -1016,9 +1078,11 @@ static int route_sk(const GemmCall& c, const Args& base) {
     }
   }
   if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_SK, g.ksplit, 2, kgrid.x);
-  const int epi = d->gelu_grad_of ? SK_EPI_GELUGRAD : d->residual ? SK_EPI_RES : d->act == ACX_ACT_QUICKGELU ? SK_EPI_QUICKGELU : SK_EPI_PLAIN;
+  const int epi = d->gelu_grad_of ? (d->act == ACX_ACT_GELU ? SK_EPI_GELUGRAD_ERF : SK_EPI_GELUGRAD) : d->residual ? SK_EPI_RES
+                  : d->act == ACX_ACT_QUICKGELU ? SK_EPI_QUICKGELU : d->act == ACX_ACT_GELU ? SK_EPI_GELU : SK_EPI_PLAIN;
   if (a_norm) sk_launch<SK_EPI_PLAIN, 0, 1>(c, kgrid, g);
   else if (d->a_act == ACX_ACT_QUICKGELU) sk_launch_epi<1>(c, epi, kgrid, g);
+  else if (d->a_act == ACX_ACT_GELU) sk_launch_epi<2>(c, epi, kgrid, g);
   else sk_launch_epi<0>(c, epi, kgrid, g);
   ACX_CHECK_LAUNCH(ctx, "acx_gemm");
   return ACX_OK;
@@ -1042,27 +1106,35 @@ static size_t sk_scratch_bytes(const GemmCall& c) {
 // alone would not fill the chip (caller-provided workspace)
 template <int CM, int ACT, int RES, int CV, int NI>
 static void x6_launch(const GemmCall& c, dim3 grid, const Args& g) {
-  if constexpr (CV == 0 && CM != 1 && ACT < 2) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU, residual)
+  if constexpr (CV == 0 && CM != 1 && (ACT < 2 || ACT == ACX_ACT_GELU)) {   // (the ViT's epilogues: f32 / plane outputs, bias, QuickGELU / GELU, residual)
     if (c.d->pairs == 3) {                        // the three leading products only (acx_gemm_x6.h, X3); fp16 planes: X3 = 2
       if constexpr (CM == 2) {                    // fp16 operands, bf16 x 3 output planes: the instantiations of gemm_x6_h3_kernel
         static_assert(RES == 0, "plane outputs carry no residual (route_x6 refuses them)");
         if (c.a_f16 && c.d->c_dtype == ACX_BF16X3P) {
-          acx_launch_lds<gemm_x6_h3_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          if constexpr (ACT == ACX_ACT_GELU) acx_launch_lds<gemm_x6_h3_gelu_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          else acx_launch_lds<gemm_x6_h3_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
           return;
         }
         if (c.a_f16 && c.d->c_scale != 0.f && c.d->c_scale != 1.f) {   // fp16 pair planes of c_scale * value: gemm_x6_r16_kernel
-          acx_launch_lds<gemm_x6_r16_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          if constexpr (ACT == ACX_ACT_GELU) acx_launch_lds<gemm_x6_r16_gelu_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+          else acx_launch_lds<gemm_x6_r16_kernel<2, ACT, 0, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
           return;
         }
       }
-      if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+      if constexpr (ACT == ACX_ACT_GELU) {
+        if (c.a_f16) acx_launch_lds<gemm_x6_gelu_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+        else acx_launch_lds<gemm_x6_gelu_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+      }
+      else if (c.a_f16) acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 2>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       else acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, 0, 0, 0, NI, 0, 1>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
       return;
     }
   }
-  if constexpr (ACT >= ACX_ACT_RELU || CV == 2) {   // (the ResNet encoder's: whole tiles only)
+  if constexpr (ACT == ACX_ACT_RELU || ACT == ACX_ACT_RESRELU || CV == 2) {   // (the ResNet encoder's: whole tiles only)
     static_assert(NI == 4, "gemm_x6_rn_kernel: whole tiles");
     acx_launch_lds<gemm_x6_rn_kernel<CM, ACT, RES, CV, 0, 0, 4>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
+  } else if constexpr (ACT == ACX_ACT_GELU) {
+    acx_launch_lds<gemm_x6_gelu_kernel<CM, ACT, RES, CV, 0, 0, NI>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
   } else {
     acx_launch_lds<gemm_x6_p4_kernel<CM, ACT, RES, CV, 0, 0, NI>>(c.dev_slot, grid, dim3(256), (size_t)X6_LDS_B, c.s, g);
   }
@@ -1077,6 +1149,9 @@ static void x6_launch_tiles(const GemmCall& c, bool c_x3, int split, dim3 grid, 
   if constexpr (CV == 0) { if (act == ACX_ACT_RESRELU) { x6_launch<0, 4, 1, 0, 4>(c, grid, g); return; } }
   if constexpr (CV == 2) { x6_launch<0, 0, 0, 2, 4>(c, grid, g); return; } else {
   if (split > 1) x6_launch<0, 0, 0, CV, 4>(c, grid, g);
+  else if (CV == 0 && act == ACX_ACT_GELU) {      // the exact GELU: identity rows, no residual (gemm_validate, route_x6)
+    if constexpr (CV == 0) { if (c_x3) x6_launch<2, 5, 0, 0, 4>(c, grid, g); else if (c.c_bf16) x6_launch<1, 5, 0, 0, 4>(c, grid, g); else x6_launch<0, 5, 0, 0, 4>(c, grid, g); }
+  }
   else if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<2, 2, 0, CV, 4>(c, grid, g); else x6_launch<2, 0, 0, CV, 4>(c, grid, g); }
   else if (c.c_bf16) { if (act == ACX_ACT_QUICKGELU) x6_launch<1, 1, 0, CV, 4>(c, grid, g); else if (act == ACX_ACT_LEAKYRELU) x6_launch<1, 2, 0, CV, 4>(c, grid, g); else x6_launch<1, 0, 0, CV, 4>(c, grid, g); }
   else if (c.d->residual) x6_launch<0, 0, 1, CV, 4>(c, grid, g);
@@ -1090,9 +1165,10 @@ static void x6_launch_tiles(const GemmCall& c, bool c_x3, int split, dim3 grid, 
 template <int NI>
 static void x6_launch_strips(const GemmCall& c, bool c_x3, dim3 grid, const Args& g) {
   const int act = c.d->act;
-  if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, 0, NI>(c, grid, g); else x6_launch<2, 0, 0, 0, NI>(c, grid, g); }
+  if (c_x3) { if (act == ACX_ACT_QUICKGELU) x6_launch<2, 1, 0, 0, NI>(c, grid, g); else if (act == ACX_ACT_GELU) x6_launch<2, 5, 0, 0, NI>(c, grid, g); else x6_launch<2, 0, 0, 0, NI>(c, grid, g); }
   else if (c.d->residual) x6_launch<0, 0, 1, 0, NI>(c, grid, g);
   else if (act == ACX_ACT_QUICKGELU) x6_launch<0, 1, 0, 0, NI>(c, grid, g);
+  else if (act == ACX_ACT_GELU) x6_launch<0, 5, 0, 0, NI>(c, grid, g);
   else x6_launch<0, 0, 0, 0, NI>(c, grid, g);
 }
 // a last round with LayerNorm riders (RIDE = 1: the f32 residual epilogue); three products of fp16 planes: gemm_x6_r16_kernel
@@ -1121,7 +1197,7 @@ static int route_x6(const GemmCall& c, const Args& base, const acx_ln_job* job, 
       d->lda % 8 == 0 && d->ldw % 8 == 0 && d->N % 4 == 0 && d->ldc % 4 == 0 && (!d->residual || d->ldr % 4 == 0) &&
       !(((uintptr_t)d->C | (uintptr_t)d->residual | (uintptr_t)d->bias) & 15) && d->a_plane_stride > 0 && d->w_plane_stride > 0 &&
       !((d->a_plane_stride | d->w_plane_stride) & 15) && (size_t)d->M * d->lda * 2 < ((size_t)1 << 32) &&
-      (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && !(d->act == ACX_ACT_QUICKGELU && d->residual) &&
+      (size_t)d->N * d->ldw * 2 < ((size_t)1 << 32) && !(acx_is_gelu(d->act) && d->residual) &&
       !(d->act == ACX_ACT_LEAKYRELU && d->residual) && !(c_x3_ && (d->residual || d->N % 8 || d->ldc % 8)) && !(c_bf16 && d->residual) &&
       (!d->panels || (!conv && d->K % 32 == 0 && d->lda == d->K && d->ldw == d->K)) && ((d->c_dtype != ACX_BF16X3P && d->c_dtype != ACX_F16X2P) || d->ldc == d->N) &&
       (!conv || (d->zero_page && !((uintptr_t)d->zero_page & 15) && d->cin % 32 == 0));
@@ -1230,6 +1306,7 @@ static int route_s64(const GemmCall& c, const Args& base) {
   }
   if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_S64, g.ksplit, 1, sgrid.x);
   if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) s64_launch<1, 1>(c, sgrid, g); else s64_launch<1, 0>(c, sgrid, g); }
+  else if (d->act == ACX_ACT_GELU) { if (d->residual) s64_launch<5, 1>(c, sgrid, g); else s64_launch<5, 0>(c, sgrid, g); }
   else if (d->act == ACX_ACT_RELU) { if (d->residual) s64_launch<3, 1>(c, sgrid, g); else s64_launch<3, 0>(c, sgrid, g); }
   else if (d->act == ACX_ACT_RESRELU) s64_launch<4, 1>(c, sgrid, g);
   else { if (d->residual) s64_launch<0, 1>(c, sgrid, g); else s64_launch<0, 0>(c, sgrid, g); }
@@ -1294,7 +1371,8 @@ static int route_p256(const GemmCall& c, const Args& g, const KSplit& ks) {
   if (c.dry) return route_dry(c, ACX_GEMM_ROUTE_P256, 1, 0, (long long)((d->M + BM - 1) / BM) * g.tiles_n);
   if (d->amap == ACX_AMAP_CONV3X3) {
     if (d->act == ACX_ACT_LEAKYRELU) p256_launch<2, 1>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 1>(c, g); else p256_launch<0, 1>(c, g);
-  } else if (d->act == ACX_ACT_QUICKGELU) p256_launch<1, 0>(c, g); else if (d->act == ACX_ACT_RELU) p256_launch<3, 0>(c, g); else p256_launch<0, 0>(c, g);
+  } else if (d->act == ACX_ACT_QUICKGELU) p256_launch<1, 0>(c, g); else if (d->act == ACX_ACT_GELU) p256_launch<5, 0>(c, g);
+  else if (d->act == ACX_ACT_RELU) p256_launch<3, 0>(c, g); else p256_launch<0, 0>(c, g);
   ACX_CHECK_LAUNCH(c.ctx, "acx_gemm");
   return ACX_OK;
 }
@@ -1311,6 +1389,9 @@ static void w8_launch_epi(const GemmCall& c, dim3 grid, const Args& g) {
   const acx_gemm_desc* d = c.d;
   if constexpr (CV != 0) {                        // (LeakyReLU: the convolutions only -- `fast` excludes it)
     if (d->act == ACX_ACT_LEAKYRELU) { if (d->residual) w8_launch<2, 1, CV>(c, grid, g); else w8_launch<2, 0, CV>(c, grid, g); return; }
+  }
+  if constexpr (CV == 0) {                        // (the exact GELU: identity rows only -- gemm_validate)
+    if (d->act == ACX_ACT_GELU) { if (d->residual) w8_launch<5, 1, 0>(c, grid, g); else w8_launch<5, 0, 0>(c, grid, g); return; }
   }
   if (d->act == ACX_ACT_QUICKGELU) { if (d->residual) w8_launch<1, 1, CV>(c, grid, g); else w8_launch<1, 0, CV>(c, grid, g); }
   else if (d->act == ACX_ACT_RELU) { if (d->residual) w8_launch<3, 1, CV>(c, grid, g); else w8_launch<3, 0, CV>(c, grid, g); }
@@ -1444,6 +1525,14 @@ static void gemm_kernel_launch(const GemmCall& c, dim3 grid, const Args& g) {
 template <int P, int AB, int CB>
 static void gemm_kernel_launch_epi(const GemmCall& c, dim3 grid, const Args& g) {
   const acx_gemm_desc* d = c.d;
+  if constexpr (P == 0 && AB == 0 && CB == 0) {   // (the exact GELU: all-f32 products only -- gemm_validate)
+    if (d->act == ACX_ACT_GELU) {
+      if (!c.fast) gemm_kernel_launch<0, 0, 0, 0, 5, 0>(c, grid, g);
+      else if (d->residual) gemm_kernel_launch<0, 0, 0, 1, 5, 1>(c, grid, g);
+      else gemm_kernel_launch<0, 0, 0, 1, 5, 0>(c, grid, g);
+      return;
+    }
+  }
   if (!(c.fast && !c.relu_act)) gemm_kernel_launch<P, AB, CB, 0, 0, 0>(c, grid, g);
   else if (d->act == ACX_ACT_QUICKGELU) {
     if (d->residual) gemm_kernel_launch<P, AB, CB, 1, 1, 1>(c, grid, g); else gemm_kernel_launch<P, AB, CB, 1, 1, 0>(c, grid, g);

@@ -249,6 +249,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_f32_p256_kernel(const Args g) {
         float v[4] = {a4.x + b4.x, a4.y + b4.y, a4.z + b4.z, a4.w + b4.w};                         \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                            \
           if constexpr (ACT == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);                      \
+          if constexpr (ACT == ACX_ACT_GELU) v[e] = acx_gelu(v[e]);                                \
           if constexpr (ACT == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];          \
           if constexpr (ACT == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);                                \
         }                                                                                          \
@@ -266,6 +267,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_f32_p256_kernel(const Args g) {
         const int row = m0 + wm * 64 + (mi) * 32 + 4 * hh + (r & 3) + 8 * (r >> 2);                \
         float v = ACC[r] + bias;                                                                   \
         if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);                              \
+        if constexpr (ACT == ACX_ACT_GELU) v = acx_gelu(v);                                        \
         if constexpr (ACT == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;                       \
         if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);                                      \
         if constexpr (RES != 0) v += d.residual[(size_t)min(row, d.M - 1) * d.ldr + colc];         \

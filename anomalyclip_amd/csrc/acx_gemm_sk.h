@@ -21,12 +21,16 @@ constexpr int SK_OP_B = 32 * SK_CH * 4;            // one operand image of a chu
 constexpr int SK_STAGE_B = 2 * SK_OP_B;            // A | W
 constexpr int SK_LDS_B = 2 * SK_STAGE_B;           // 128 KB: two stages; the K-partials reuse them after the loop
 
-enum { SK_EPI_PLAIN = 0, SK_EPI_QUICKGELU = 1, SK_EPI_RES = 2, SK_EPI_GELUGRAD = 3 };
+enum { SK_EPI_PLAIN = 0, SK_EPI_QUICKGELU = 1, SK_EPI_RES = 2, SK_EPI_GELUGRAD = 3,
+       SK_EPI_GELU = 4, SK_EPI_GELUGRAD_ERF = 5 };   // the exact GELU (ACX_ACT_GELU) and its derivative (gelu_grad_of with act = ACX_ACT_GELU)
 
 // QuickGELU x * sigmoid(1.702 x) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence: the prologue variant runs
 // it on every A fragment of every column tile
 __device__ __forceinline__ float sk_sigmoid1702(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-1.702f * v)); }
 __device__ __forceinline__ float sk_quickgelu(float v) { return v * sk_sigmoid1702(v); }
+// the exact GELU x Phi(x) and its derivative Phi(x) + x phi(x) (acx_gelu.h); A_GELU = 2 is its prologue
+__device__ __forceinline__ float sk_gelu(float v) { return acx_gelu_erf(v); }
+__device__ __forceinline__ float sk_gelu_grad(float v) { return acx_gelu_erf_grad(v); }
 
 // A_NORM: LayerNorm over K applied to the A rows as they leave LDS (K == 512 = the whole row resident in the two stages):
 // y = LN(x) W^T + b without a LayerNorm launch and without materialising LN(x) (clip/model.py:214-216: ln_1 -> attention in-proj,
@@ -157,7 +161,10 @@ __global__ __launch_bounds__(512) void gemm_f32_sk_kernel(const Args g) {
     }
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
-      if constexpr (A_GELU != 0) {
+      if constexpr (A_GELU == 2) {
+        xa[cc].x = sk_gelu(xa[cc].x); xa[cc].y = sk_gelu(xa[cc].y);
+        xa[cc].z = sk_gelu(xa[cc].z); xa[cc].w = sk_gelu(xa[cc].w);
+      } else if constexpr (A_GELU != 0) {
         xa[cc].x = sk_quickgelu(xa[cc].x); xa[cc].y = sk_quickgelu(xa[cc].y);
         xa[cc].z = sk_quickgelu(xa[cc].z); xa[cc].w = sk_quickgelu(xa[cc].w);
       }
@@ -216,6 +223,7 @@ __global__ __launch_bounds__(512) void gemm_f32_sk_kernel(const Args g) {
   float o[2] = {v.x, v.y};
   if (d.bias) { o[0] += d.bias[gn]; o[1] += d.bias[gn + 1]; }
   if constexpr (EPI == SK_EPI_QUICKGELU) { o[0] = sk_quickgelu(o[0]); o[1] = sk_quickgelu(o[1]); }
+  if constexpr (EPI == SK_EPI_GELU) { o[0] = sk_gelu(o[0]); o[1] = sk_gelu(o[1]); }
   if constexpr (EPI == SK_EPI_RES) {
     const float2 r2 = *reinterpret_cast<const float2*>(d.residual + (size_t)gm * d.ldr + gn);
     o[0] += r2.x; o[1] += r2.y;
@@ -229,6 +237,10 @@ __global__ __launch_bounds__(512) void gemm_f32_sk_kernel(const Args g) {
       const float sg = sk_sigmoid1702(pp[j]);
       o[j] *= sg * (1.f + 1.702f * pp[j] * (1.f - sg));
     }
+  }
+  if constexpr (EPI == SK_EPI_GELUGRAD_ERF) {
+    const float2 p2 = *reinterpret_cast<const float2*>(d.gelu_grad_of + (size_t)gm * d.ldg + gn);
+    o[0] *= sk_gelu_grad(p2.x); o[1] *= sk_gelu_grad(p2.y);
   }
   *reinterpret_cast<float2*>((float*)d.C + (size_t)gm * d.ldc + gn) = make_float2(o[0], o[1]);
 }

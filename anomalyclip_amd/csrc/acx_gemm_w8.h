@@ -302,6 +302,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_w8_kernel(const Args g) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if constexpr (ACT == ACX_ACT_QUICKGELU) v[e] = acx_quickgelu(v[e]);
+          if constexpr (ACT == ACX_ACT_GELU) v[e] = acx_gelu(v[e]);
           if constexpr (ACT == ACX_ACT_LEAKYRELU) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
           if constexpr (ACT == ACX_ACT_RELU) v[e] = fmaxf(v[e], 0.f);
         }
@@ -341,6 +342,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_w8_kernel(const Args g) {
     for (int r = 0; r < 16; ++r) {
       float v = acc[mi][r] + bias;
       if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
+      if constexpr (ACT == ACX_ACT_GELU) v = acx_gelu(v);
       if constexpr (ACT == ACX_ACT_LEAKYRELU) v = v > 0.f ? v : 0.01f * v;
       if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);
       outv[r] += v;
@@ -471,6 +473,7 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_s64_kernel(const Args g) {
   for (int r = 0; r < 16; ++r) {
     float v = acc[r] + bias;
     if constexpr (ACT == ACX_ACT_QUICKGELU) v = acx_quickgelu(v);
+    if constexpr (ACT == ACX_ACT_GELU) v = acx_gelu(v);
     if constexpr (ACT == ACX_ACT_RELU) v = fmaxf(v, 0.f);
     outv[r] += v;
     if constexpr (ACT == ACX_ACT_RESRELU) outv[r] = fmaxf(outv[r], 0.f);

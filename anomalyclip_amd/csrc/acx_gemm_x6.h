@@ -821,6 +821,7 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
                        vb_.x * osc_ + bib[ni].x, vb_.y * osc_ + bib[ni].y, vb_.z * osc_ + bib[ni].z, vb_.w * osc_ + bib[ni].w};  \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                            \
           if constexpr (ACT == ACX_ACT_QUICKGELU) ov[e] = acx_quickgelu(ov[e]);                    \
+          else if constexpr (ACT == ACX_ACT_GELU) ov[e] = acx_gelu(ov[e]);                         \
           else if constexpr (ACT == ACX_ACT_LEAKYRELU) ov[e] = ov[e] > 0.f ? ov[e] : 0.01f * ov[e]; \
           else if constexpr (ACT == ACX_ACT_RELU) ov[e] = fmaxf(ov[e], 0.f);                       \
           if constexpr (X6_R16 != 0 && X3 == 2) ov[e] *= csc_;   /* exact: a power of two */       \
@@ -861,6 +862,8 @@ __global__ __launch_bounds__(256, 1) void X6_KERNEL(const Args g) {
       if constexpr (ACT == ACX_ACT_QUICKGELU) {                                                    \
         v.x = acx_quickgelu(v.x); v.y = acx_quickgelu(v.y);                                        \
         v.z = acx_quickgelu(v.z); v.w = acx_quickgelu(v.w);                                        \
+      } else if constexpr (ACT == ACX_ACT_GELU) {                                                  \
+        v.x = acx_gelu(v.x); v.y = acx_gelu(v.y); v.z = acx_gelu(v.z); v.w = acx_gelu(v.w);        \
       } else if constexpr (ACT == ACX_ACT_LEAKYRELU) {                                             \
         v.x = v.x > 0.f ? v.x : 0.01f * v.x; v.y = v.y > 0.f ? v.y : 0.01f * v.y;                  \
         v.z = v.z > 0.f ? v.z : 0.01f * v.z; v.w = v.w > 0.f ? v.w : 0.01f * v.w;                  \

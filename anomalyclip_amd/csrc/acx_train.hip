@@ -2,6 +2,7 @@
 // All reductions over rows are two-stage and fixed-order (per-block partials -> acx_reduce_rows), so a
 // training step is bit-reproducible run to run; no float atomics on the gradient path.
 #include "acx_internal.h"
+#include "acx_gelu.h"        // the exact GELU (acx_act modes 3 / 4)
 
 namespace {
 
@@ -223,6 +224,24 @@ __global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ save
       if (mode == 1) gv[k] *= sg * (1.f + 1.702f * sv[k] * (1.f - sg));
       else gv[k] = sv[k] * sg;
     }
+  }
+  reinterpret_cast<float4*>(out)[i] = make_float4(gv[0], gv[1], gv[2], gv[3]);
+}
+
+// mode 3: exact GELU backward from the saved pre-activation: d *= Phi(x) + x phi(x);  mode 4: exact GELU forward (acx_gelu.h).
+// A kernel of its own: act_kernel stays the instruction stream it was.
+__global__ __launch_bounds__(256) void act_gelu_kernel(const float* __restrict__ saved, const float* __restrict__ d,
+                                                       float* __restrict__ out, int64_t n4, int mode) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const float4 s = reinterpret_cast<const float4*>(saved)[i];
+  float4 g = make_float4(1.f, 1.f, 1.f, 1.f);
+  if (d) g = reinterpret_cast<const float4*>(d)[i];
+  float sv[4] = {s.x, s.y, s.z, s.w}, gv[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (mode == 3) gv[k] *= acx_gelu_erf_grad(sv[k]);
+    else gv[k] = acx_gelu_erf(sv[k]);
   }
   reinterpret_cast<float4*>(out)[i] = make_float4(gv[0], gv[1], gv[2], gv[3]);
 }
@@ -1821,7 +1840,9 @@ extern "C" int acx_act(acx_ctx* ctx, const float* saved, const float* d, float* 
   if (n <= 0) return ACX_OK;
   if (n % 4) return acx_fail(ctx, ACX_E_BADARG, "acx_act: n%%4%s");
   AcxProfScope prof__(ctx, ACX_K_OTHER, (hipStream_t)stream);
-  hipLaunchKernelGGL(act_kernel, GRID1(n / 4), dim3(256), 0, (hipStream_t)stream, saved, d, out, n / 4, mode);
+  if (mode < 0 || mode > 4) return acx_fail(ctx, ACX_E_BADARG, "acx_act: unknown mode%s");
+  if (mode >= 3) hipLaunchKernelGGL(act_gelu_kernel, GRID1(n / 4), dim3(256), 0, (hipStream_t)stream, saved, d, out, n / 4, mode);
+  else hipLaunchKernelGGL(act_kernel, GRID1(n / 4), dim3(256), 0, (hipStream_t)stream, saved, d, out, n / 4, mode);
   ACX_CHECK_LAUNCH(ctx, "acx_act");
   return ACX_OK;
 }

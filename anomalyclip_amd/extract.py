@@ -833,26 +833,30 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
-def build_image_encoder(arch: str, precision: str = "auto", chunk: int = 512):
-    """the CLIP image encoder of `arch`, as AnomalyCLIP builds it"""
+def build_image_encoder(arch: str, precision: str = "auto", chunk: int = 512, act: str = "quick_gelu"):
+    """the CLIP image encoder of `arch`, as AnomalyCLIP builds it.  act: the ViT MLP's activation, "quick_gelu" (OpenAI's weights) or
+    "gelu" (open_clip's LAION-2B / DataComp weights); "gelu" with precision "bf16" or a ResNet arch is a ValueError naming both"""
     from .components.anomaly_clip import geometry_of_arch
     from .components.clip_resnet import ModifiedResNet
-    from .components.clip_vit import VisionTransformer
+    from .components.clip_vit import VisionTransformer, check_act
     geom = geometry_of_arch(arch)
+    check_act(act, precision, arch if geom.is_resnet else None)
     if geom.is_resnet:
         return ModifiedResNet(geom.vision_layers, geom.embed_dim, geom.resnet_heads, geom.image_resolution, geom.vision_width,
                               precision=precision, chunk=chunk, arch=arch)
     return VisionTransformer(geom.image_resolution, geom.vision_patch_size, geom.vision_width, geom.vision_layers,
-                             geom.vision_heads, geom.embed_dim, precision=precision, chunk=chunk, arch=arch)
+                             geom.vision_heads, geom.embed_dim, precision=precision, chunk=chunk, arch=arch, act=act)
 
 
 def load_encoder_weights(encoder, arch: str, weights) -> None:
     """weights: a Lightning .ckpt (`net.image_encoder.*`), a dict holding `state_dict`, an AnomalyCLIP state_dict
-    (`image_encoder.*`) or the encoder's own state_dict; a checkpoint of another backbone is a ValueError naming both."""
-    from .checkpoint import split_lightning_state_dict
+    (`image_encoder.*`), the encoder's own state_dict, or a plain CLIP state_dict (`visual.*`: OpenAI's model.state_dict(),
+    open_clip's open_clip_pytorch_model.bin); a checkpoint of another backbone is a ValueError naming both."""
+    from .checkpoint import from_clip_state_dict, is_clip_state_dict, split_lightning_state_dict
     from .components.anomaly_clip import _describe, geometry_from_state_dict, geometry_of_arch
     ck = torch.load(weights, map_location="cpu", weights_only=False) if isinstance(weights, str) else weights
-    sd = split_lightning_state_dict(ck.get("state_dict", ck) if isinstance(ck, dict) else ck)
+    sd = ck.get("state_dict", ck) if isinstance(ck, dict) else ck
+    sd = from_clip_state_dict(sd) if is_clip_state_dict(sd) else split_lightning_state_dict(sd)
     if not any(k.startswith("image_encoder.") for k in sd):
         sd = {"image_encoder." + k: v for k, v in sd.items()}
     theirs, mine = geometry_from_state_dict(sd), geometry_of_arch(arch)
@@ -869,7 +873,10 @@ def _parser():
     from .components.clip_vit import PRECISIONS
     p = argparse.ArgumentParser(prog="python -m anomalyclip_amd.extract", description="CLIP feature files from frame folders")
     p.add_argument("--arch", required=True, choices=sorted(_ARCH))
-    p.add_argument("--weights", required=True, help="Lightning .ckpt, AnomalyCLIP state_dict or image-encoder state_dict")
+    p.add_argument("--weights", required=True, help="Lightning .ckpt, AnomalyCLIP state_dict, image-encoder state_dict or plain CLIP state_dict")
+    p.add_argument("--act", default="quick_gelu", choices=("quick_gelu", "gelu"),
+                   help="the ViT MLP's activation: quick_gelu for OpenAI's weights, gelu for open_clip weights trained without quick_gelu "
+                        "(LAION-2B, DataComp); the weights do not say which")
     p.add_argument("--frames-root", required=True)
     p.add_argument("--out-root", required=True)
     p.add_argument("--annotations", default=None, help="rows `path start end label...`; default: every folder of --frames-root")
@@ -893,7 +900,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     that contradict each other: a --scale-size below the arch's resolution, a --precision the arch's encoder does not run."""
     from .components.anomaly_clip import geometry_of_arch
     from .components.clip_resnet import check_resnet_precision
-    from .components.clip_vit import check_vit_precision
+    from .components.clip_vit import check_act, check_vit_precision
     p = _parser()
     a = p.parse_args(argv)
     geom = geometry_of_arch(a.arch)
@@ -906,6 +913,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
             check_vit_precision(a.precision, geom.grid ** 2 + 1, geom.vision_width, a.arch, geom.image_resolution, geom.vision_patch_size)
     except ValueError as e:
         p.error(f"--precision {a.precision} conflicts with --arch {a.arch}: {e}")
+    try:
+        check_act(a.act, a.precision, a.arch if geom.is_resnet else None, key="--act")
+    except ValueError as e:
+        p.error(f"--act {a.act} conflicts with --precision {a.precision} / --arch {a.arch}: {e}")
     for name, path in (("--weights", a.weights), ("--frames-root", a.frames_root), ("--annotations", a.annotations)):
         if path is not None and not os.path.exists(path):
             p.error(f"{name} {path}: no such file or directory")
@@ -914,7 +925,7 @@ def parse_args(argv: Optional[Sequence[str]] = None):
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
     a = parse_args(argv)
-    enc = build_image_encoder(a.arch, a.precision)
+    enc = build_image_encoder(a.arch, a.precision, act=a.act)
     load_encoder_weights(enc, a.arch, a.weights)
     enc = enc.to(torch.device("cuda", torch.cuda.current_device())).eval()
     counts = extract_dataset(enc, a.annotations, a.frames_root, a.out_root, a.ncrops, a.scale_size, a.overwrite,

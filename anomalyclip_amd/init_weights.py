@@ -34,6 +34,8 @@ class ClipGeometry:
     transformer_width: int = 512
     transformer_heads: int = 8
     transformer_layers: int = 12
+    act: str = "quick_gelu"     # the MLPs' activation: "quick_gelu" (OpenAI's checkpoints) or "gelu" (open_clip configs without quick_gelu);
+                                # not a constructor argument of the reference's CLIP: as_kwargs() leaves it out
 
     @property
     def is_resnet(self) -> bool:

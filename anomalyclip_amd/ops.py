@@ -362,7 +362,8 @@ def unpanel(planes: torch.Tensor) -> torch.Tensor:
 def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] = None, bias=None, act=L.ACT_NONE,
             residual=None, out_dtype=torch.float32, amap=L.AMAP_IDENTITY, gn=0, gl=0, cin=0, M: Optional[int] = None,
             planes_out: bool = False, split_k: bool = True, panels: int = 0, panel_out: bool = False, pairs: int = 6,
-            out_scale: float = 0.0, ln=None, planes_bf16: bool = False, c_scale: float = 0.0) -> torch.Tensor:
+            out_scale: float = 0.0, ln=None, planes_bf16: bool = False, c_scale: float = 0.0,
+            route: Optional["L.GemmRoute"] = None) -> torch.Tensor:
     """out[M, N] = epilogue(amap(A) W^T) with A = sum of the three bf16 planes a3 [3, rows, Ka] and W = sum of w3 [3, N, K]
     (split_bf16x3): the six leading cross products on the bf16 matrix cores, f32 accumulation -- the accuracy of an f32
     product (acx_gemm_desc.pairs = 6; acx_gemm_x6.h).  amap = AMAP_CONV3X3: implicit 3x3 convolution over the (gn, gl) token
@@ -373,7 +374,8 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
     fourth entry `scale` and y fp16 [2, M, N]: the two fp16 planes of scale * LayerNorm (layernorm_f16x2).
     planes_bf16 (fp16 operands, planes_out, panel_out): the output planes are the THREE bf16 planes of the f32 value (ACX_BF16X3P) --
     what a six-product GEMM reads -- instead of fp16 pairs.
-    c_scale (fp16 operands, fp16 planes out): the output planes hold c_scale * value, a power of two (acx_gemm_desc.c_scale)."""
+    c_scale (fp16 operands, fp16 planes out): the output planes hold c_scale * value, a power of two (acx_gemm_desc.c_scale).
+    route: an L.GemmRoute that acx_gemm_route fills for this very descriptor, scratch included (as gemm's)."""
     f16 = a3.dtype == torch.float16          # two fp16 planes per operand (split_f16x2): pairs = 3 only, out_scale undoes the planes' scales
     if f16:
         assert pairs == 3 and a3.shape[0] == 2 and w3.shape[0] == 2 and w3.dtype == torch.float16 and (panel_out or not planes_out)
@@ -409,6 +411,8 @@ def gemm_x6(a3: torch.Tensor, w3: torch.Tensor, *, out: Optional[torch.Tensor] =
         d.zero_page = _zero_page(a3.device).data_ptr()
     h, lib, pd = _h(a3), L.lib(), C.byref(d)
     _bring_scratch(lib, h, d, pd, a3.device, split_k)
+    if route is not None:
+        L.check(lib.acx_gemm_route(h, pd, C.byref(route)), h)
     if ln is not None:
         lw, lb, ly = ln[:3]
         ln16 = len(ln) > 3

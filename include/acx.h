@@ -79,10 +79,11 @@ enum { ACX_PREC_F32X6_LN16 = 6 }; /* acx_vit_encode_ln16 only: ACX_PREC_F32X6 wi
                                  measures the in-projection alone): acx_transformer_plan's ln2_dtype tells the caller which it is */
 enum { ACX_PREC_F32X6_R16 = 7 };  /* acx_vit_encode_r16 only: ACX_PREC_F32X6_LN16 one step wider -- in every body layer the two residual
                                  products (out-proj, c_proj) read fp16 pair planes as well, where they and their producers take the plane
-                                 kernels: the planes attention (acx_attention_p3f16) writes the two planes of s_att * o, c_fc's QuickGELU
+                                 kernels: the planes attention (acx_attention_p3f16) writes the two planes of s_att * o, c_fc's activation
                                  epilogue those of s_hid * hidden (acx_gemm_desc.c_scale); the weights come as acx_split_f16x2(2^10 w).
                                  s_att and s_hid are per-layer powers of two the CALLER proves from the weights alone (|o| is a convex
-                                 combination of V rows; |QuickGELU(x)| <= |x|).  Everything else is ACX_PREC_F32X6_LN16's plan, record for
+                                 combination of V rows; |act(x)| <= |x| for QuickGELU and for the exact GELU alike: x times a factor in [0, 1],
+                                 sigmoid(1.702 x) or Phi(x)).  Everything else is ACX_PREC_F32X6_LN16's plan, record for
                                  record.  Tools builds: -DACX_R16_OUT_DEFAULT=0 / -DACX_R16_PROJ_DEFAULT=0 keep that product six-product */
 #define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
@@ -94,6 +95,12 @@ enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
                                  identity or CONV3X3 rows to f32 or plane output (ACX_BF16X3[P]: the planes of the value AFTER the
                                  ReLU), without a residual; RESRELU on identity rows to f32 output (whole tiles, no K split: both).
                                  pairs = 3 takes neither; ACX_E_UNSUPPORTED otherwise */
+enum { ACX_ACT_GELU = 5 };    /* the exact GELU 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU: every CLIP checkpoint NOT trained with QuickGELU --
+                                 open_clip's LAION-2B / DataComp ViT-B/32, B/16, L/14), f32-accurate (erf, no tanh / sigmoid form).  The
+                                 routes the two towers take: f32 products (prec ACX_PREC_F32, f32 A and C: the few-row, 64 x 64, 8-wave,
+                                 strip-stream and generic kernels, with their K splits) and pairs = 6 / 3 products of planes, everywhere
+                                 QuickGELU is taken, on identity rows.  ACX_E_UNSUPPORTED on the bf16 MFMA routes (prec ACX_PREC_BF16
+                                 with pairs <= 1: no parity path) and on the CONV3X3 / tile row maps (no CLIP tower has a GELU there) */
 enum { ACX_AMAP_IDENTITY = 0, ACX_AMAP_CONV3X3 = 1, ACX_AMAP_TESTTILE = 2, ACX_AMAP_TILETABLE = 3 };
 enum { ACX_NORM_LAYER = 0, ACX_NORM_CHAN = 1 };     /* nn.LayerNorm vs axial_attention ChanLayerNorm (eps added to std) */
 
@@ -189,8 +196,10 @@ typedef struct acx_gemm_desc {
   const void* zero_page;  /* optional: >= 256 bytes of zeros, 16-byte aligned, caller-owned.  With it, large CONV3X3 problems
                              (N >= 512, power-of-two grid, no residual) run on the LDS-DMA strip kernel: a tap outside the
                              token grid is a DMA from this page */
-  int32_t a_act;          /* ACX_ACT_QUICKGELU: the activation is applied to A as it is read (x_next = gelu(pre) @ W^T) */
-  const float* gelu_grad_of; /* [M, ldg] saved pre-activation p: C = (A W^T + bias) * d gelu(p)/dp  (no act / residual) */
+  int32_t a_act;          /* ACX_ACT_QUICKGELU / ACX_ACT_GELU: the activation is applied to A as it is read (x_next = gelu(pre) @ W^T) */
+  const float* gelu_grad_of; /* [M, ldg] saved pre-activation p: C = (A W^T + bias) * d gelu(p)/dp  (no residual).  WHICH gelu: `act`
+                                names it -- act = 0 (ACX_ACT_NONE) keeps meaning QuickGELU's derivative, act = ACX_ACT_GELU selects the
+                                exact GELU's, Phi(p) + p phi(p); no activation is applied to C either way.  Any other act: refused */
   int32_t ldg;
   const float* a_norm_w;  /* LayerNorm over K applied to the A rows as they are read (y = LN(A) W^T + bias): weight / bias [K], or
                              NULL.  Few-row f32 kernel only, K == 512, no a_act / residual / gelu_grad_of / activation
@@ -214,7 +223,7 @@ typedef struct acx_gemm_desc {
                              f32 dot product, at 6/16 of the f32 MFMA's cost (2.5 PFLOP/s bf16 against 157 TFLOP/s f32 on gfx950).
                              Kernel: gemm_x6_p4_kernel (csrc/acx_gemm_x6.h).  K % 32 == 0, N % 4 == 0, 16-byte aligned planes; row
                              maps IDENTITY and CONV3X3 (cin % 32 == 0, zero_page, an A plane below 4 GiB); epilogues bias,
-                             QuickGELU / LeakyReLU / ReLU, residual (f32 C), c_dtype ACX_F32 / ACX_BF16 / ACX_BF16X3[P] (plane output:
+                             QuickGELU / GELU / LeakyReLU / ReLU, residual (f32 C), c_dtype ACX_F32 / ACX_BF16 / ACX_BF16X3[P] (plane output:
                              N % 8 == 0, no residual).  CONV3X3 on a power-of-two (gn, gl) grid with M % 256 == 0 takes every one of
                              these; on ANY other grid or row count (gn, gl >= 1, M % (gn gl) == 0: a 256-row tile may straddle frames
                              and end behind M) the row map works by division and the epilogues are bias / ReLU to f32 and ReLU to
@@ -223,7 +232,7 @@ typedef struct acx_gemm_desc {
                              the ReLU epilogues and the general convolution map, which never split (acx_gemm_scratch answers 0).
                              3: the same planes and kernel with the THREE leading products only -- (mid,hi) (hi,mid) (hi,hi); the lo
                              planes are never read.  The dropped terms are <= 2^-16 of the leading one: NOT f32-accurate (about 1e-5 of
-                             sum |a||w|).  Identity rows, f32 or plane outputs, bias / QuickGELU / residual epilogues. */
+                             sum |a||w|).  Identity rows, f32 or plane outputs, bias / QuickGELU / GELU / residual epilogues. */
   int32_t panels;         /* pairs = 6: bit 0 -- the A planes are in K-panel layout (ACX_BF16X3P, rows = a_plane_stride / (2 K));
                              bit 1 -- the W planes are (rows = N).  Identity row map only. */
   int64_t a_plane_stride, w_plane_stride;   /* bytes */
@@ -408,6 +417,11 @@ typedef struct acx_vit_weights {
 typedef struct acx_vit_desc {
   int32_t resolution, patch, width, layers, heads, embed_dim;
   int32_t prec;               /* ACX_PREC_* */
+  int32_t act;                /* the MLP's activation: 0 or ACX_ACT_QUICKGELU = QuickGELU (OpenAI's checkpoints), ACX_ACT_GELU = the exact GELU
+                                 (open_clip configs without quick_gelu); anything else ACX_E_BADARG, ACX_ACT_GELU with prec = ACX_PREC_BF16
+                                 ACX_E_UNSUPPORTED.  The struct GREW by this trailing member (as acx_ln_job did by y_scale): 0 is the
+                                 activation every caller of the earlier header got, and such a caller must zero the descriptor's tail --
+                                 memset(&desc, 0, sizeof desc) before filling it, as for every descriptor of this header */
 } acx_vit_desc;
 
 /* acx_vit_encode: VisionTransformer.forward (clip/model.py:266-290): frames [F,3,R,R] f32 ->
@@ -525,6 +539,12 @@ int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, in
                             int32_t heads, int32_t layers, int32_t causal, int32_t prec,
                             const acx_block_weights* blocks, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* the same with the MLP's activation named: act = 0 / ACX_ACT_QUICKGELU (what acx_transformer_forward passes) or ACX_ACT_GELU; anything
+ * else ACX_E_BADARG, ACX_ACT_GELU with prec = ACX_PREC_BF16 ACX_E_UNSUPPORTED. */
+int acx_transformer_forward_act(acx_ctx* ctx, float* x, int32_t batch, int32_t L, int32_t width,
+                                int32_t heads, int32_t layers, int32_t causal, int32_t prec, int32_t act,
+                                const acx_block_weights* blocks, void* workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* acx_transformer_plan: what acx_transformer_forward / acx_vit_encode launch for every layer of a geometry -- answered by the plan
  * step the drivers themselves execute (there is no second copy of the gates).  Host arithmetic, no device, nothing launched.
@@ -545,7 +565,9 @@ int acx_transformer_forward(acx_ctx* ctx, float* x, int32_t batch, int32_t L, in
  *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0);
  *                  att_out_dtype: ACX_F16X2P where ACX_TF_ATT_P3F goes out as acx_attention_p3f16, else 0
  *   split_att, split_mlp  1: acx_split_bf16x3_panel of the attention output / the MLP hidden is launched
- *   pruned         1: the last layer, CLS rows only */
+ *   pruned         1: the last layer, CLS rows only
+ * The plan does not depend on the MLP's activation (acx_vit_desc.act, acx_transformer_forward_act): QuickGELU and the exact GELU take
+ * the same kernels with another template value in c_fc's epilogue, so one query answers for both. */
 enum { ACX_TF_LN_ROWS = 0, ACX_TF_LN_PLANES = 1, ACX_TF_LN_RIDDEN = 2, ACX_TF_LN_CLS = 3 };
 enum { ACX_TF_GEMM_ROWS = 0, ACX_TF_GEMM_X6 = 1 };
 enum { ACX_TF_BUF_NONE = 0, ACX_TF_BUF_SPLITK = 1, ACX_TF_BUF_H = 2, ACX_TF_BUF_QKV = 3, ACX_TF_BUF_MLP = 4 };
@@ -787,7 +809,8 @@ int acx_cls_head_bwd(acx_ctx* ctx, const float* x1, const float* x2, const float
                      const float* lin_w, const float* scores, const float* dscores, float* dx, float* part,
                      int64_t rows, int32_t E, void* stream);
 /* elementwise: mode 0 LeakyReLU' from saved output, 1 QuickGELU' from saved pre-activation (out = d * f'),
- * 2 QuickGELU forward (d ignored). */
+ * 2 QuickGELU forward (d ignored), 3 the exact GELU's derivative Phi(x) + x phi(x) from the saved pre-activation (out = d * f'),
+ * 4 the exact GELU forward (d ignored).  n % 4 == 0; any other mode ACX_E_BADARG. */
 int acx_act(acx_ctx* ctx, const float* saved, const float* d, float* out, int64_t n, int32_t mode, void* stream);
 /* LeakyReLU(0.01) backward for the bf16 x 6 path of the temporal model's feed-forward (temporal_model.py:32-39 under autograd):
  * u_hi = the hi bf16 plane of the saved activation (its sign is the activation's), d [n] the upstream gradient; out [n] f32 and

@@ -1,6 +1,11 @@
 """Frames/s of the CLIP image encoder per `net.arch` backbone and precision, with the library's per-kind kernel times.
 
     python tools/bench_vit_arch.py --arch ViT-L/14 --precision auto --frames 512 [--steps 5 --warmup 2]
+    python tools/bench_vit_arch.py --arch ViT-B/16 --frames 512 --precision auto --act quick_gelu,gelu --reps 2
+
+`--act A[,B]` names the MLP's activation (quick_gelu, gelu); several activations and / or `--reps N` time the legs ALTERNATELY in
+one process (A B A B ...: clock and thermal drift hit both alike), one JSON line with every leg's frames/s and the spread of each
+activation's legs -- the run-to-run spread a difference has to exceed.
 
 One launch of `--frames` frames (seeded random weights and frames) is timed with HIP events after the warm-up; a separate profiled
 pass (acx_prof_*: HIP-event pairs around every kernel, summed by kind) gives attention / GEMM / other times and the GEMMs'
@@ -42,12 +47,17 @@ def main():
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--act", default="quick_gelu", help="quick_gelu | gelu, or both separated by a comma: alternating legs")
+    ap.add_argument("--reps", type=int, default=1, help="legs per activation")
     a = ap.parse_args()
+    acts = a.act.split(",")
+    if any(t not in ("quick_gelu", "gelu") for t in acts) or a.reps < 1:
+        ap.error("--act takes quick_gelu, gelu or both separated by a comma; --reps >= 1")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     g = geometry_of_arch(a.arch)
     vit = VisionTransformer(g.image_resolution, g.vision_patch_size, g.vision_width, g.vision_layers, g.vision_heads, g.embed_dim,
-                            precision=a.precision, chunk=a.frames, arch=a.arch)
+                            precision=a.precision, chunk=a.frames, arch=a.arch, act=acts[0])
     vit.load_state_dict(IW.init_vit_state_dict(g, 0, prefix=""), strict=True)
     vit = vit.to(dev)
     x = torch.randn(a.frames, 3, g.image_resolution, g.image_resolution, generator=torch.Generator().manual_seed(1)).to(dev)
@@ -62,6 +72,8 @@ def main():
     ev[1].record()
     torch.cuda.synchronize()
     ms = ev[0].elapsed_time(ev[1]) / a.steps
+    if len(acts) > 1 or a.reps > 1:
+        return alternate(a, vit, x, acts, t0)
     # profiled pass: per-kind kernel times
     lib, h = L.lib(), L.ctx(0)
     lib.acx_prof_enable(h, 1)
@@ -84,6 +96,34 @@ def main():
            "gemm_roof_tflops": round(PEAK_TFLOPS[a.precision], 1),
            "gemm_frac_of_roof": round(gemm_tflops / PEAK_TFLOPS[a.precision], 4) if gemm_tflops else None,
            "finite": bool(torch.isfinite(out).all()), "wall_s": round(time.time() - t0, 1)}
+    print(json.dumps(res))
+
+
+def alternate(a, vit, x, acts, t0):
+    """legs of a.steps launches each, the activations in turn, a.reps rounds; every leg behind a.warmup launches of its own"""
+    legs = []
+    for r in range(a.reps):
+        for act in acts:
+            vit.act = vit.transformer.act = act
+            for _ in range(a.warmup):
+                vit(x)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            for _ in range(a.steps):
+                out = vit(x)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms = ev[0].elapsed_time(ev[1]) / a.steps
+            legs.append({"act": act, "rep": r, "ms_per_launch": round(ms, 3), "frames_per_s": round(a.frames / (ms / 1e3), 1),
+                         "finite": bool(torch.isfinite(out).all())})
+    by = {act: [l["frames_per_s"] for l in legs if l["act"] == act] for act in acts}
+    res = {"arch": a.arch, "precision": a.precision, "frames": a.frames, "steps": a.steps, "legs": legs,
+           "frames_per_s": {act: round(sum(v) / len(v), 1) for act, v in by.items()},
+           "spread": {act: round((max(v) - min(v)) / (sum(v) / len(v)), 5) for act, v in by.items()},
+           "wall_s": round(time.time() - t0, 1)}
+    if len(acts) == 2:
+        m = res["frames_per_s"]
+        res["ratio"] = {f"{acts[1]}/{acts[0]}": round(m[acts[1]] / m[acts[0]], 5)}
     print(json.dumps(res))
 
 
