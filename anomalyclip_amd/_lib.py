@@ -16,6 +16,7 @@ PREC_F32, PREC_BF16, PREC_F32X6, PREC_F32X3, PREC_F16X3 = 0, 1, 2, 3, 4
 PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet encoder on the plane kernel (precision "bf16x6")
 PREC_F32X6_LN16 = 6                     # acx_vit_encode_ln16 only: PREC_F32X6 with the LayerNorm-fed products on fp16 planes (what "auto" resolves to)
 PREC_F32X6_R16 = 7                      # acx_vit_encode_r16 only: PREC_F32X6_LN16 with out-proj and c_proj on fp16 planes too ("auto", every proof passing)
+PREC_F32X6_QKV16 = 8                    # acx_vit_encode_qkv16 only: PREC_F32X6_R16 with q | k | v as fp16 planes into the three-product planes attention
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 ACT_GELU = 5                            # the exact GELU 0.5 x (1 + erf(x / sqrt 2)): CLIP checkpoints not trained with QuickGELU
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
@@ -203,6 +204,7 @@ _SIGS = {
     "acx_attention_p3n": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3f": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3f16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_p3h16": (C.c_int, [c_void_p, c_void_p, c_float, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3_panel": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls_fold_workspace_bytes": (c_size_t, [c_int32, c_int32]),
@@ -228,6 +230,8 @@ _SIGS = {
                                       c_void_p, c_size_t, c_void_p]),
     "acx_vit_encode_r16": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_void_p, c_int32, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),
+    "acx_vit_encode_qkv16": (C.c_int, [c_void_p, C.POINTER(VitDesc), C.POINTER(VitWeights), c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
     "acx_transformer_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "acx_transformer_workspace_bytes_prec": (c_size_t, [c_int32, c_int32, c_int32]),
     "acx_transformer_forward": (C.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

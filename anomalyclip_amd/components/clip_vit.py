@@ -34,6 +34,8 @@ from .. import ops
 # weights alone, that their operands stay inside fp16's range whatever the frames are; otherwise -- and always under "f32x6" -- six
 # products everywhere.  One step wider (ACX_PREC_F32X6_R16), when r16_scales() also proves the attention output and the MLP hidden inside
 # fp16's range from the weights: out-proj and c_proj read fp16 planes as well, written by the attention's and c_fc's epilogues.
+# A third step (ACX_PREC_F32X6_QKV16), when qkv16_scales() bounds the Q and K rows of the in-projection as it bounds the V rows: q | k | v
+# leave the in-projection as fp16 planes and the planes attention runs its three-product fp16 form on them.
 PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32x6": L.PREC_F32X6, "bf16x3": L.PREC_F32X3,
               "f16x3": L.PREC_F16X3}
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
@@ -112,7 +114,7 @@ def r16_bounds(ln_w, ln_b, w, b):
 
 @torch.no_grad()
 def _range_proofs(blocks, width: int):
-    """(ln16_scales, r16_scales) of a list of blocks from ONE device-to-host transfer; see the two functions"""
+    """(ln16_scales, r16_scales, qkv16_scales) of a list of blocks from ONE device-to-host transfer; see the three functions"""
     vals = []
     D = width
     root = float(D - 1) ** 0.5
@@ -124,33 +126,43 @@ def _range_proofs(blocks, width: int):
         for wt in (b.attn.in_proj_weight, b.mlp.c_fc.weight):
             vals.append(wt.detach().abs().max().double())
             vals.append(wt.detach().double().abs().sum())
-        # the operands of the two residual products: rows of V = W_v ln_1(x) + b_v, of the c_fc pre-activation W_fc ln_2(x) + b_fc
-        for ln, wt, bias in ((b.ln_1, b.attn.in_proj_weight[2 * D:], b.attn.in_proj_bias[2 * D:]), (b.ln_2, b.mlp.c_fc.weight, b.mlp.c_fc.bias)):
-            l1, l2 = r16_bounds(ln.weight, ln.bias, wt, bias)
+        # the operands of the two residual products: rows of V = W_v ln_1(x) + b_v (the last third of the in-projection's bounds, which
+        # serve q | k | v below as a whole), of the c_fc pre-activation W_fc ln_2(x) + b_fc
+        q1, q2 = r16_bounds(b.ln_1.weight, b.ln_1.bias, b.attn.in_proj_weight, b.attn.in_proj_bias)
+        for l1, l2 in ((q1[2 * D:], q2[2 * D:]), r16_bounds(b.ln_2.weight, b.ln_2.bias, b.mlp.c_fc.weight, b.mlp.c_fc.bias)):
             vals.append(torch.minimum(l1, l2).max() + 0.0 * (l1.sum() + l2.sum()))   # (0 * inf = NaN: nothing non-finite hides behind the min)
         for wt in (b.attn.out_proj.weight, b.mlp.c_proj.weight):
             vals.append(wt.detach().abs().max().double())
             vals.append(wt.detach().double().abs().sum())
+        # all 3 W rows of the in-projection: q | k | v as the fp16 planes the attention reads
+        vals.append(torch.minimum(q1, q2).max() + 0.0 * (q1.sum() + q2.sum()))
     if not vals:
-        return None, None
+        return None, None, None
     v = torch.stack(vals).tolist()                                         # one transfer
     ln16: Optional[List[float]] = []
     r16: Optional[List[float]] = []
-    for i in range(0, len(v), 14):
-        b1, f1, b2, f2, w1, g1, w2, g2, ba, bh, w3, g3, w4, g4 = v[i:i + 14]
+    qkv: Optional[List[float]] = []
+    for i in range(0, len(v), 15):
+        b1, f1, b2, f2, w1, g1, w2, g2, ba, bh, w3, g3, w4, g4, bq = v[i:i + 15]
         if ln16 is not None:
             s1, s2 = ln16_scale(b1), ln16_scale(b2)
             if not all(math.isfinite(t) for t in (f1, f2, g1, g2)) or not (w1 <= LN16_WEIGHT_MAX and w2 <= LN16_WEIGHT_MAX) or s1 is None or s2 is None:
-                ln16 = r16 = None
+                ln16 = r16 = qkv = None
             else:
                 ln16 += [s1, s2]
         if r16 is not None:
             sa, sh = ln16_scale(ba), ln16_scale(bh)
             if not all(math.isfinite(t) for t in (g3, g4)) or not (w3 <= LN16_WEIGHT_MAX and w4 <= LN16_WEIGHT_MAX) or sa is None or sh is None:
-                r16 = None
+                r16 = qkv = None
             else:
                 r16 += [sa, sh]
-    return ln16, r16
+        if qkv is not None:
+            sq = ln16_scale(bq)
+            if sq is None:
+                qkv = None
+            else:
+                qkv.append(sq)
+    return ln16, r16, qkv
 
 
 def ln16_scales(blocks, width: int) -> Optional[List[float]]:
@@ -174,6 +186,15 @@ def r16_scales(blocks, width: int) -> Optional[List[float]]:
     an fp16 pair holds s * a only to an absolute 2^-25 once |s * a| < 2^-3, so s decides how small an element may be before it loses
     relative accuracy."""
     return _range_proofs(blocks, width)[1]
+
+
+def qkv16_scales(blocks, width: int) -> Optional[List[float]]:
+    """The weight-only proof behind ACX_PREC_F32X6_QKV16, on top of r16_scales': [s_qkv] per block -- the power-of-two scale of the fp16
+    planes of q | k | v, ONE for the three thirds -- or None when r16_scales refuses, the bound is not a finite positive number or the
+    scale leaves 2^-20 ... 2^20.  The bound is r16_scales' bound of the V rows taken over all 3 W rows of the in-projection:
+    max_j min(L1_j, L2_j) of r16_bounds(ln_1, in_proj_weight, in_proj_bias); s_qkv is the largest power of two with s_qkv * bound <= 2^14.
+    The frames play no part."""
+    return _range_proofs(blocks, width)[2]
 
 
 HEAD_MAX_AXIS = 128                                    # acx_axial_attention: 1 <= axis length <= 128 on either axis
@@ -362,6 +383,7 @@ class VisionTransformer(nn.Module):
         # graph now picks a stream that runs beside its caller's -- ops.side_stream_beside, profiles/r06_stream_queues.txt).
         self.streams = streams
         self._wcache = None
+        # the third entry, cached under the same key: ([ln_1, ln_2, att, hid, qkv] scales per layer, their ctypes array) or None
         self._ln16 = None                                  # (key, (scales, ctypes array, c_fc on fp16 planes, r16 or None) or None): "auto"'s resolution
         self._ws: Optional[torch.Tensor] = None
         self._ws2: Optional[torch.Tensor] = None
@@ -381,12 +403,14 @@ class VisionTransformer(nn.Module):
         (whatever the frames are, the patch embedding excepted: its A operand is the pixels themselves):
           LayerNorm outputs   |y_i| <= |gamma_i| sqrt(D - 1) + |beta_i|          (a unit-variance row has no element above sqrt(D - 1))
           attention outputs   convex combinations of V rows: |v_j| <= ln1_bound * ||W_v,j||_1 + |b_v,j|
+          q, k, v             rows of the in-projection: |W_j . ln_1(x) + b_j| <= ln1_bound * ||W_j||_1 + |b_j|, per third
           MLP hiddens         |x sigmoid(1.702 x)| <= |x| and |x Phi(x)| <= |x| (QuickGELU, exact GELU) <= ln2_bound * ||W_fc,j||_1 + |b_fc,j|
           weight planes       2^10 |w|
-        against fp16's largest finite number 65504.  `safe` says every bound is below it; `margin` is the smallest ratio 65504 / bound."""
+        against fp16's largest finite number 65504 (`bounds`; the three q | k | v figures under `qkv`).  `safe` says every bound is below it; `margin` is the smallest ratio 65504 / bound."""
         D = self.width
         lim = 65504.0
         worst = {"weight_planes": 0.0, "layernorm_out": 0.0, "attention_out": 0.0, "mlp_hidden": 0.0}
+        qkv = {"q": 0.0, "k": 0.0, "v": 0.0}               # reported beside `bounds` (whose keys are what they were), counted in `margin`
 
         def ln_bound(ln):
             return float((ln.weight.abs() * (D - 1) ** 0.5 + ln.bias.abs()).max())
@@ -396,11 +420,14 @@ class VisionTransformer(nn.Module):
             wv, bv = b.attn.in_proj_weight[2 * D:], b.attn.in_proj_bias[2 * D:]
             worst["layernorm_out"] = max(worst["layernorm_out"], l1, l2)
             worst["attention_out"] = max(worst["attention_out"], float((wv.abs().sum(1) * l1 + bv.abs()).max()))
+            for t, name in enumerate(("q", "k", "v")):
+                wt, bt = b.attn.in_proj_weight[t * D:(t + 1) * D], b.attn.in_proj_bias[t * D:(t + 1) * D]
+                qkv[name] = max(qkv[name], float((wt.abs().sum(1) * l1 + bt.abs()).max()))
             worst["mlp_hidden"] = max(worst["mlp_hidden"], float((b.mlp.c_fc.weight.abs().sum(1) * l2 + b.mlp.c_fc.bias.abs()).max()))
             mats += [b.attn.in_proj_weight, b.attn.out_proj.weight, b.mlp.c_fc.weight, b.mlp.c_proj.weight]
         worst["weight_planes"] = F16X3_WSCALE * max(float(m.abs().max()) for m in mats)
-        margin = min(lim / max(v, 1e-30) for v in worst.values())
-        return {"bounds": worst, "fp16_max": lim, "margin": margin, "safe": margin > 1.0}
+        margin = min(lim / max(v, 1e-30) for v in list(worst.values()) + list(qkv.values()))
+        return {"bounds": worst, "qkv": qkv, "fp16_max": lim, "margin": margin, "safe": margin > 1.0}
 
     def _ln16_bound(self):
         """(scales, their ctypes array, whether c_fc's weight is bound as fp16 planes, r16) or None, cached with the weights; r16: None, or
@@ -409,9 +436,9 @@ class VisionTransformer(nn.Module):
         key = (ops.WEIGHT_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in self.parameters())
         if self._ln16 is not None and self._ln16[0] == key:
             return self._ln16[1]
-        res = None
+        res = qkv16 = None
         if self.width in (768, 1024) and self.layers > 1 and L.exports("acx_vit_encode_ln16"):
-            scales, wide = _range_proofs(self.transformer.resblocks, self.width)
+            scales, wide, sq = _range_proofs(self.transformer.resblocks, self.width)
             if scales is not None:
                 # c_fc's weight format is a constant of the library's build (a tools build may keep c_fc six-product): its plan says which
                 # (asked at a shape whose c_fc is a plane product whatever this model's geometry is)
@@ -425,9 +452,19 @@ class VisionTransformer(nn.Module):
                     if any(fmt):
                         s4 = [t for l in range(self.layers) for t in (scales[2 * l], scales[2 * l + 1], wide[2 * l], wide[2 * l + 1])]
                         r16 = (s4, (C.c_float * len(s4))(*s4), fmt)
+                        # the third step where the library has it and moves the attention of this geometry at some batch (its plan
+                        # decides per launch: a layer whose in-projection would split K keeps ACX_PREC_F32X6_R16's record)
+                        if sq is not None and fmt[0] and L.exports("acx_vit_encode_qkv16"):
+                            s5 = [t for l in range(self.layers) for t in (*s4[4 * l:4 * l + 4], sq[l])]
+                            qkv16 = (s5, (C.c_float * len(s5))(*s5))
                 res = (scales, (C.c_float * len(scales))(*scales), fc16, r16)
-        self._ln16 = (key, res)
+        self._ln16 = (key, res, qkv16)
         return res
+
+    def _qkv16_bound(self):
+        """([ln_1, ln_2, att, hid, qkv] scales per layer, their ctypes array) or None: _ln16_bound's cache entry for the third step"""
+        self._ln16_bound()
+        return self._ln16[2]
 
     def ln16_resolution(self) -> Optional[List[float]]:
         """What precision "auto" resolves to for the weights as they are: the LayerNorm plane scales of ACX_PREC_F32X6_LN16 when the
@@ -443,6 +480,14 @@ class VisionTransformer(nn.Module):
         otherwise (ln16_resolution then says whether it is ACX_PREC_F32X6_LN16 or six products everywhere)."""
         res = self._ln16_bound()
         return None if res is None or res[3] is None else res[3][0]
+
+    def qkv16_resolution(self) -> Optional[List[float]]:
+        """The plane scales [ln_1, ln_2, att, hid, qkv] per layer of ACX_PREC_F32X6_QKV16 when "auto" resolves to it for the weights as
+        they are -- r16_resolution's conditions with out-proj on fp16 planes, qkv16_scales' proof and a library that exports
+        acx_vit_encode_qkv16; None otherwise (r16_resolution then says whether it is ACX_PREC_F32X6_R16).  Which launches take the fp16
+        attention is the driver's plan: body layers whose attention is the planes attention behind an unsplit in-projection."""
+        res = self._qkv16_bound()
+        return None if res is None else res[0]
 
     def _weights(self, prec: int, ln16_fc: bool = True, r16=(True, True)):
         key = (prec, bool(ln16_fc), bool(r16[0]), bool(r16[1]), ops.WEIGHT_EPOCH[0]) + tuple((p.data_ptr(), p._version) for p in self.parameters())
@@ -483,7 +528,15 @@ class VisionTransformer(nn.Module):
         lib = L.lib()
         bound = self._ln16_bound() if self.precision == "auto" and x.is_cuda else None
         ln16_fc, r16 = True, (True, True)
-        if bound is not None and bound[3] is not None:
+        wprec = None                                       # the precision the weights are bound for, where it is not the descriptor's
+        qkv16 = self._qkv16_bound() if bound is not None and bound[3] is not None else None
+        if qkv16 is not None:
+            prec, wprec = L.PREC_F32X6_QKV16, L.PREC_F32X6_R16
+            ln16_fc = bound[2]
+            r16 = bound[3][2]
+            sc5 = qkv16[1]
+            encode = lambda *a: lib.acx_vit_encode_qkv16(a[0], a[1], a[2], sc5, *a[3:])
+        elif bound is not None and bound[3] is not None:
             prec = L.PREC_F32X6_R16
             ln16_fc = bound[2]
             _s4, sc4, r16 = bound[3]
@@ -495,7 +548,7 @@ class VisionTransformer(nn.Module):
         else:
             encode = lib.acx_vit_encode
         d = L.VitDesc(self.input_resolution, self.patch_size, self.width, self.layers, self.heads, self.output_dim, prec, ACTS[self.act])
-        w, _keep = self._weights(prec, ln16_fc, r16)
+        w, _keep = self._weights(prec if wprec is None else wprec, ln16_fc, r16)
         F = x.shape[0]
         out = torch.empty(F, self.output_dim, dtype=torch.float32, device=x.device)
         chunk = min(self.chunk, F)

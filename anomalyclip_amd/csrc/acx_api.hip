@@ -21,6 +21,10 @@
 #define ACX_R16_PROJ_DEFAULT 1     // ACX_PREC_F32X6_R16: c_proj on fp16 planes (the A/B build that measures out-proj alone: 0)
 #endif
 
+#ifndef ACX_QKV16_DEFAULT
+#define ACX_QKV16_DEFAULT 1        // ACX_PREC_F32X6_QKV16: q | k | v as fp16 planes into the three-product attention (the A/B build that keeps ACX_PREC_F32X6_R16's records: 0)
+#endif
+
 #ifndef ACX_CLS_FOLD_DEFAULT
 #define ACX_CLS_FOLD_DEFAULT 1     // ACX_OPT_CLS_FOLD as acx_create sets it
 #endif
@@ -34,14 +38,17 @@ struct TfOpts {
   bool attn_f32in, cls_fold;                     // ACX_OPT_ATTN_F32IN, ACX_OPT_CLS_FOLD
   bool ln16_fc;                                  // ACX_LN16_FC_DEFAULT (a build constant)
   bool r16_out, r16_proj;                        // ACX_R16_OUT_DEFAULT, ACX_R16_PROJ_DEFAULT (build constants)
+  bool qkv16;                                    // ACX_QKV16_DEFAULT (a build constant)
 };
 constexpr TfOpts kCreateOpts = {18, ACX_ATTN_F32IN_DEFAULT != 0, ACX_CLS_FOLD_DEFAULT != 0, ACX_LN16_FC_DEFAULT != 0, ACX_R16_OUT_DEFAULT != 0,
-                                ACX_R16_PROJ_DEFAULT != 0};
-constexpr TfOpts kNoCtxOpts = {512, false, false, ACX_LN16_FC_DEFAULT != 0, ACX_R16_OUT_DEFAULT != 0, ACX_R16_PROJ_DEFAULT != 0};   // a driver called with ctx == NULL
+                                ACX_R16_PROJ_DEFAULT != 0, ACX_QKV16_DEFAULT != 0};
+constexpr TfOpts kNoCtxOpts = {512, false, false, ACX_LN16_FC_DEFAULT != 0, ACX_R16_OUT_DEFAULT != 0, ACX_R16_PROJ_DEFAULT != 0,
+                              ACX_QKV16_DEFAULT != 0};   // a driver called with ctx == NULL
 // query: acx_transformer_plan, which answers for a context as acx_create leaves it when it has none (like the other route queries)
 inline TfOpts tf_opts(const acx_ctx* ctx, bool query) {
   if (!ctx) return query ? kCreateOpts : kNoCtxOpts;
-  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0, kCreateOpts.ln16_fc, kCreateOpts.r16_out, kCreateOpts.r16_proj};
+  return {ctx->opt_x6_min_tiles, ctx->opt_attn_f32in != 0, ctx->opt_cls_fold != 0, kCreateOpts.ln16_fc, kCreateOpts.r16_out, kCreateOpts.r16_proj,
+          kCreateOpts.qkv16};
 }
 }  // namespace
 
@@ -224,10 +231,16 @@ struct TfWs {   // transformer scratch carved from the caller's workspace
 // the plane modes of the drivers: ACX_PREC_F32X6 (six products: f32-accurate) and ACX_PREC_F32X3 (the three leading products)
 static inline bool is_xmode(int prec) {
   return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3 || prec == ACX_PREC_F32X6_LN16 ||
-         prec == ACX_PREC_F32X6_R16;
+         prec == ACX_PREC_F32X6_R16 || prec == ACX_PREC_F32X6_QKV16;
 }
 // the six-product modes whose LayerNorm-fed products read fp16 planes (ACX_PREC_F32X6_R16: the residual products too)
-static inline bool is_ln16(int prec) { return prec == ACX_PREC_F32X6_LN16 || prec == ACX_PREC_F32X6_R16; }
+static inline bool is_r16(int prec) { return prec == ACX_PREC_F32X6_R16 || prec == ACX_PREC_F32X6_QKV16; }
+static inline bool is_ln16(int prec) { return prec == ACX_PREC_F32X6_LN16 || is_r16(prec); }
+// the plane scales a driver call brings per layer: ln_1, ln_2 | att, hid | qkv
+static inline int scales_per_layer(int prec) { return prec == ACX_PREC_F32X6_QKV16 ? 5 : prec == ACX_PREC_F32X6_R16 ? 4 : 2; }
+static inline const char* ln16_name(int prec) {
+  return prec == ACX_PREC_F32X6_QKV16 ? "ACX_PREC_F32X6_QKV16" : prec == ACX_PREC_F32X6_R16 ? "ACX_PREC_F32X6_R16" : "ACX_PREC_F32X6_LN16";
+}
 struct XMode {
   int pairs;                                     // acx_gemm_desc.pairs of the driver's plane products (and the attention's products)
   bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
@@ -406,6 +419,7 @@ struct TfPlan {
   TfMode mode;
   bool ln16_qkv, ln16_fc;      // ACX_PREC_F32X6_LN16: the in-projection / c_fc of the body layers run on fp16 planes (ln_1 / ln_2 write them)
   bool r16_out, r16_proj;      // ACX_PREC_F32X6_R16: out-proj / c_proj of the body layers run on fp16 planes (the attention / c_fc write them)
+  bool qkv16;                  // ACX_PREC_F32X6_QKV16: q | k | v of the body layers leave the in-projection as fp16 planes (the fp16 planes attention)
   acx_tf_layer_plan_t body, before_pruned, pruned;   // the three layer shapes (before_pruned: body with the pruned layer's ln_1 job)
   bool prune;
 };
@@ -421,7 +435,27 @@ acx_tf_layer_plan_t tf_layer(const TfPlan& p, int l, int layers) {
 inline acx_tf_product_t tf_rows(int c_dtype, int scratch) { return {ACX_TF_GEMM_ROWS, c_dtype, scratch, 0}; }
 inline acx_tf_product_t tf_x6(int c_dtype, int scratch, bool ln_job) { return {ACX_TF_GEMM_X6, c_dtype, scratch, ln_job ? 1 : 0}; }
 
-// Pure host arithmetic on its arguments (err: where a refusal's text goes, nothing else).
+// Whether a body layer's ACX_PREC_F32X6_R16 in-projection (fp16 A planes, f32 rows out) is a launch whose K acx_gemm may split across
+// workgroups: fewer tiles than workgroups, the small launches -- the dispatcher's own answers, its split model's scratch query
+// (acx_gemm_scratch: bytes > 0 = a split is possible for this shape) and its route with the scratch the driver hands it (acx_gemm_route;
+// no operand is dereferenced, any aligned address does).  Such a launch keeps its f32 rows: fp16 plane outputs never split K.
+bool in_proj_splits(acx_ctx* ctx, const TfGeom& g, int64_t rows) {
+  acx_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = d.W = d.C = d.workspace = (void*)(uintptr_t)256;
+  d.M = (int)rows; d.N = 3 * g.W; d.K = g.W; d.lda = d.ldw = g.W; d.ldc = 3 * g.W; d.ldr = d.ldc;
+  d.a_dtype = ACX_F16; d.c_dtype = ACX_F32; d.prec = ACX_PREC_BF16; d.pairs = 3; d.panels = 3;
+  d.out_scale = 1.f / ACX_F16X3_WSCALE;
+  d.a_plane_stride = rows * g.W * 2; d.w_plane_stride = (int64_t)3 * g.W * g.W * 2;
+  d.workspace_bytes = (size_t)rows * g.W * 4;
+  acx_gemm_scratch_t sc;
+  if (acx_gemm_scratch(ctx, &d, 1, &sc) != ACX_OK || sc.workspace_bytes > 0) return true;
+  acx_gemm_route_t r;
+  return acx_gemm_route(ctx, &d, &r) != ACX_OK || r.ksplit > 1;
+}
+
+// Pure host arithmetic on its arguments.  err: where a refusal's text goes; ACX_PREC_F32X6_QKV16 also hands it to acx_gemm's dry queries
+// (in_proj_splits), which read its workgroup count and options as acx_gemm itself would and launch nothing.
 int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, TfPlan* p) {
   memset(p, 0, sizeof(*p));
   const int W = g.W, L = g.L;
@@ -441,9 +475,9 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   const bool ln_ride = m.pdt == ACX_BF16X3P;
   // ACX_PREC_F32X6_LN16: the plane-kernel in-projection and (ACX_LN16_FC_DEFAULT) c_fc read fp16 pair planes -- their weights come in that
   // format, so the rule is per product and holds for every geometry; everything else is the six-product plan below, record for record
-  const bool ln16 = is_ln16(g.prec), r16 = g.prec == ACX_PREC_F32X6_R16;
+  const bool ln16 = is_ln16(g.prec), r16 = is_r16(g.prec);
   if (ln16 && W != 768 && W != 1024)
-    return acx_fail(err, ACX_E_UNSUPPORTED, "driver: %s is built for widths 768 and 1024", r16 ? "ACX_PREC_F32X6_R16" : "ACX_PREC_F32X6_LN16");
+    return acx_fail(err, ACX_E_UNSUPPORTED, "driver: %s is built for widths 768 and 1024", ln16_name(g.prec));
   p->ln16_qkv = ln16 && x6_qkv;
   p->ln16_fc = ln16 && x6_fc && o.ln16_fc;
   // bf16 mode, non-causal (the ViT): q/k/v, the attention and its output stay bf16 end to end -- half the
@@ -459,6 +493,10 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   p->r16_out = r16 && o.r16_out && att_p3;
   p->r16_proj = r16 && o.r16_proj && p->ln16_fc && x6_proj;
   const bool att_p3f = att_p3 && ln_ride && (o.attn_f32in || p->r16_out);
+  // ACX_PREC_F32X6_QKV16: behind an in-projection that reads fp16 planes, in front of an out-projection that reads them, q | k | v go
+  // as fp16 planes too and the attention is its three-product fp16 form.  An fp16 plane output never takes a K split, so a layer whose
+  // ACX_PREC_F32X6_R16 in-projection acx_gemm would split (few tiles: small launches) keeps that record.
+  p->qkv16 = g.prec == ACX_PREC_F32X6_QKV16 && o.qkv16 && p->r16_out && p->ln16_qkv && att_p3f && !in_proj_splits(err, g, rows);
   const bool qkv_planes = att_p3 && !att_p3f;
   // ... or on f32 rows, writing the out-projection's three planes itself
   const bool att_x3 = x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
@@ -497,6 +535,11 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
   b.att_products = b.att == ACX_TF_ATT_P3N ? (m.xm.f16 ? 103 : m.xm.pairs) : 0;
   b.att_out_dtype = p->r16_out ? ACX_F16X2P : 0;
+  if (p->qkv16) {
+    b.in_proj = tf_x6(ACX_F16X2P, ACX_TF_BUF_QKV, false);
+    b.att = ACX_TF_ATT_P3N;
+    b.att_products = 103;
+  }
   b.split_att = x6_out && !att_x3 && !att_p3;
   b.out_proj = x6_out ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_fc) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
   b.ln2 = !x6_fc ? ACX_TF_LN_ROWS : b.out_proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
@@ -539,13 +582,16 @@ int tf_plan_call(acx_ctx* ctx, const TfGeom& g, const acx_block_weights* blk, Tf
 // ---- the executor: walks the layers and launches what the records say ----------------------------------------------------------
 struct TfRun {
   acx_ctx* ctx; const TfGeom& g; const TfMode& m; const TfWs& ws; hipStream_t s;
-  const float* ln_scales;      // ACX_PREC_F32X6_LN16: [2 layers] plane scales of ln_1, ln_2; ACX_PREC_F32X6_R16: [4 layers] ln_1, ln_2, att, hid (host)
+  const float* ln_scales;      // ACX_PREC_F32X6_LN16: [2 layers] plane scales of ln_1, ln_2; ACX_PREC_F32X6_R16: [4 layers] ln_1, ln_2, att, hid;
+                               // ACX_PREC_F32X6_QKV16: [5 layers] ... and qkv (host)
   int64_t rows() const { return (int64_t)g.batch * g.L; }
-  bool r16() const { return g.prec == ACX_PREC_F32X6_R16; }
+  bool r16() const { return is_r16(g.prec); }
+  int nsc() const { return scales_per_layer(g.prec); }
   // the scale of LayerNorm `which` (0 ln_1, 1 ln_2) of layer l where it writes ACX_PREC_F32X6_LN16's fp16 planes, else 0
-  float lnsc(int dtype, int l, int which) const { return is_ln16(g.prec) && dtype == ACX_F16X2P ? ln_scales[(r16() ? 4 : 2) * l + which] : 0.f; }
+  float lnsc(int dtype, int l, int which) const { return is_ln16(g.prec) && dtype == ACX_F16X2P ? ln_scales[nsc() * l + which] : 0.f; }
   // ACX_PREC_F32X6_R16: the scale of layer l's attention output (which = 2) / MLP hidden (3) where `dtype` says it leaves as fp16 planes, else 0
-  float r16sc(int dtype, int l, int which) const { return r16() && dtype == ACX_F16X2P ? ln_scales[4 * l + which] : 0.f; }
+  // (ACX_PREC_F32X6_QKV16: which = 4, the in-projection's output planes)
+  float r16sc(int dtype, int l, int which) const { return r16() && dtype == ACX_F16X2P ? ln_scales[nsc() * l + which] : 0.f; }
 
   // product i (0 in_proj, 1 out_proj, 2 fc, 3 proj) of block b on M rows, run as r says; A, C and residual are the caller's to set
   Product product(const acx_block_weights& b, int i, const acx_tf_product_t& r, int64_t M) const {
@@ -591,12 +637,17 @@ struct TfRun {
     auto planes = [](const acx_tf_product_t& q) { return q.c_dtype != ACX_F32 && q.c_dtype != ACX_BF16; };
     const float sc1 = lnsc(r.ln1_dtype, l, 0), sc2 = lnsc(r.ln2_dtype, l, 1);
     const float s_att = r16sc(r.att_out_dtype, l, 2), s_hid = r16sc(r.fc.c_dtype, l, 3);
+    const float s_qkv = g.prec == ACX_PREC_F32X6_QKV16 ? r16sc(r.in_proj.c_dtype, l, 4) : 0.f;
     int rc;
     if ((rc = norm_all(r.ln1, r.ln1_dtype, x, b.ln1_w, b.ln1_b, sc1))) return rc;
     Product p = product(b, 0, r.in_proj, rows());
     p.a_scale = r.in_proj.kernel == ACX_TF_GEMM_X6 ? sc1 : 0.f;
     p.A = r.in_proj.kernel == ACX_TF_GEMM_X6 ? ws.hp : ws.h;
     p.C = planes(r.in_proj) ? ws.qkv3 : ws.qkv;
+    if (s_qkv > 0.f) {           // the two fp16 planes of s_qkv * (q | k | v) where the f32 rows would go: the same bytes; no K split, no scratch
+      p.C = ws.qkv; p.c_scale = s_qkv;
+      p.scratch = nullptr; p.scratch_bytes = 0;
+    }
     if ((rc = go(p))) return rc;
     switch (r.att) {
       case ACX_TF_ATT_BF16: rc = acx_attention_bf16(ctx, ws.qkv, 3 * W, ws.att, W, batch, L, heads, s); break;
@@ -604,7 +655,10 @@ struct TfRun {
         rc = s_att > 0.f ? acx_attention_p3f16(ctx, (const float*)ws.qkv, 3 * W, ws.hp, s_att, batch, L, heads, s)
                          : acx_attention_p3f(ctx, (const float*)ws.qkv, 3 * W, ws.hp, batch, L, heads, s);
         break;
-      case ACX_TF_ATT_P3N: rc = acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, r.att_products, s); break;        // planes in, planes out
+      case ACX_TF_ATT_P3N:                                                                                               // planes in, planes out
+        rc = s_qkv > 0.f ? acx_attention_p3h16(ctx, ws.qkv, s_qkv, ws.hp, s_att, batch, L, heads, s)
+                         : acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, r.att_products, s);
+        break;
       case ACX_TF_ATT_X3_PANEL: rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s); break;
       default: rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, g.causal, s); break;
     }
@@ -707,13 +761,16 @@ int transformer_layers(acx_ctx* ctx, float* x, const TfGeom& g, const TfPlan& pl
         return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_LN16: a LayerNorm plane scale is not a power of two in [2^-20, 2^20]%s");
     }
   }
-  if (g.prec == ACX_PREC_F32X6_R16) {
-    if (!ln_scales) return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
-    for (int i = 0; i < 4 * g.layers; ++i) {
+  if (is_r16(g.prec)) {
+    const bool q = g.prec == ACX_PREC_F32X6_QKV16;
+    if (!ln_scales)
+      return acx_fail(ctx, ACX_E_BADARG, q ? "driver: ACX_PREC_F32X6_QKV16 needs the plane scales (acx_vit_encode_qkv16)%s"
+                                           : "driver: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
+    for (int i = 0; i < scales_per_layer(g.prec) * g.layers; ++i) {
       int e = 0;
       const float sc = ln_scales[i];
       if (!(sc >= 0x1p-20f && sc <= 0x1p20f) || frexpf(sc, &e) != 0.5f)
-        return acx_fail(ctx, ACX_E_BADARG, "driver: ACX_PREC_F32X6_R16: a plane scale is not a power of two in [2^-20, 2^20]%s");
+        return acx_fail(ctx, ACX_E_BADARG, "driver: %s: a plane scale is not a power of two in [2^-20, 2^20]", ln16_name(g.prec));
     }
   }
   const TfRun exec = {ctx, g, plan.mode, ws, s, ln_scales};
@@ -809,6 +866,8 @@ static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_LN16 needs the LayerNorm plane scales (acx_vit_encode_ln16)%s");
   if (d->prec == ACX_PREC_F32X6_R16 && !ln_scales)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_R16 needs the plane scales (acx_vit_encode_r16)%s");
+  if (d->prec == ACX_PREC_F32X6_QKV16 && !ln_scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: ACX_PREC_F32X6_QKV16 needs the plane scales (acx_vit_encode_qkv16)%s");
   int mlp_act = 0, rc0;
   if ((rc0 = tf_act(ctx, "acx_vit_encode", d->act, d->prec, &mlp_act))) return rc0;
   if (nframes <= 0) return ACX_OK;
@@ -881,5 +940,12 @@ extern "C" int acx_vit_encode_r16(acx_ctx* ctx, const acx_vit_desc* d, const acx
                                   int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d || d->prec != ACX_PREC_F32X6_R16 || !scales)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode_r16: needs desc->prec = ACX_PREC_F32X6_R16 and the plane scales%s");
+  return vit_encode(ctx, d, w, scales, frames, nframes, features, workspace, workspace_bytes, stream);
+}
+
+extern "C" int acx_vit_encode_qkv16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* scales, const float* frames,
+                                    int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!d || d->prec != ACX_PREC_F32X6_QKV16 || !scales)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode_qkv16: needs desc->prec = ACX_PREC_F32X6_QKV16 and the plane scales%s");
   return vit_encode(ctx, d, w, scales, frames, nframes, features, workspace, workspace_bytes, stream);
 }

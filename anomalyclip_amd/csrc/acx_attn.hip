@@ -77,9 +77,10 @@ extern "C" int acx_attention(acx_ctx* ctx, const float* qkv, int64_t ldqkv, floa
 
 // The launch of attn_p3_kernel for acx_attention_p3n (form 6 / 3: products on bf16 planes, 103: three products on fp16 planes) and
 // acx_attention_p3f (form 0: `src` is the f32 matrix, ldqkv its leading dimension; form 16: acx_attention_p3f16, the same with the two
-// fp16 planes of oscale * o out): persistent, one workgroup per CU; `name` is the entry point's, for the launch check
+// fp16 planes of oscale * o out; form 116: acx_attention_p3h16, form 103 on scaled planes with a scaled output): persistent, one
+// workgroup per CU; `name` is the entry point's, for the launch check
 static int ap3_launch(acx_ctx* ctx, int form, const void* src, int64_t ldqkv, void* out_planes, int32_t batch, int32_t L, int32_t heads,
-                      void* stream, const char* name, float oscale = 1.f) {
+                      void* stream, const char* name, float oscale = 1.f, float sscale = 1.f) {
   const int64_t rows = (int64_t)batch * L;
   const int nitems = batch * heads;
   const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
@@ -101,6 +102,9 @@ static int ap3_launch(acx_ctx* ctx, int form, const void* src, int64_t ldqkv, vo
   else if (form == 16)
     acx_launch_lds<attn_p3_o16_kernel>(dev_slot, grid, dim3(512), (size_t)AP3_LDS_B, s, (const u16*)src, ldqkv, rows, (u16*)out_planes,
                                        rows * heads * 64, L, heads, nitems, trace_, oscale);
+  else if (form == 116)
+    acx_launch_lds<attn_p3_h16_kernel>(dev_slot, grid, dim3(512), (size_t)AP3_LDS_B, s, (const u16*)src, rows * 3 * heads * 64, rows,
+                                       (u16*)out_planes, rows * heads * 64, L, heads, nitems, trace_, oscale, sscale);
   else ACX_AP3(ldqkv, 6, 0, 1);
 #undef ACX_AP3
   ACX_CHECK_LAUNCH(ctx, name);
@@ -149,6 +153,22 @@ extern "C" int acx_attention_p3f16(acx_ctx* ctx, const float* qkv, int64_t ldqkv
   if (L <= 192 || L > AP3_ROWS || heads <= 0 || ldqkv < (int64_t)3 * heads * 64 || (ldqkv & 3) || (((uintptr_t)qkv | (uintptr_t)out_planes) & 15))
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3f16: 192 < L <= 208, 16-byte aligned qkv and planes, ldqkv %% 4 == 0 and >= 3 heads * 64%s");
   return ap3_launch(ctx, 16, qkv, ldqkv, out_planes, batch, L, heads, stream, "acx_attention_p3f16", out_scale);
+}
+
+// the fp16 planes form (acx_attention_p3n, products = 103) on the planes of in_scale * (q | k | v), writing those of out_scale * o: the
+// attention of ACX_PREC_F32X6_QKV16 between an in-projection and an out-projection that both run on fp16 planes
+extern "C" int acx_attention_p3h16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void* out_planes, float out_scale, int32_t batch,
+                                   int32_t L, int32_t heads, void* stream) {
+  if (!qkv_planes || !out_planes) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_p3h16: null pointer%s");
+  int e = 0;
+  if (!(in_scale >= 0x1p-20f && in_scale <= 0x1p20f) || frexpf(in_scale, &e) != 0.5f || !(out_scale >= 0x1p-20f && out_scale <= 0x1p20f) ||
+      frexpf(out_scale, &e) != 0.5f)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_attention_p3h16: in_scale and out_scale must be powers of two in [2^-20, 2^20]%s");
+  if (batch <= 0) return ACX_OK;
+  if (L <= 192 || L > AP3_ROWS || heads <= 0 || (((uintptr_t)qkv_planes | (uintptr_t)out_planes) & 15))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3h16: 192 < L <= 208, 16-byte aligned planes%s");
+  return ap3_launch(ctx, 116, qkv_planes, 0, out_planes, batch, L, heads, stream, "acx_attention_p3h16", out_scale / in_scale,
+                    1.f / (in_scale * in_scale));
 }
 
 extern "C" int acx_attention_x3(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,

@@ -106,13 +106,18 @@ __device__ __forceinline__ void ap3f_stage_k(char* smem, const float* __restrict
 //   * a query wave loads its Q fragments as f32 (8 x 16 B per lane) and splits them into qf[0..2][ks].
 // O16 (with F32IN: attn_p3_o16_kernel, acx_attention_p3f16): the epilogue writes the TWO fp16 planes of oscale * o (ACX_F16X2P, the F16
 // arm's pack sequence) instead of the three bf16 planes of o; oscale, a power of two, folds into the normaliser -- exact.  Everything
-// before the epilogue is the F32IN arm's six-product bf16 code.  The body is shared and inlined into the two kernels below:
+// before the epilogue is the F32IN arm's six-product bf16 code.  The body is shared and inlined into the kernels below:
 // attn_p3_kernel keeps its name, its arguments and its code.
+// O16 with F16 (attn_p3_h16_kernel, acx_attention_p3h16): the F16 arm -- two fp16 planes per operand by LDS-DMA, three fp16 products, fp16
+// pair planes out -- on planes that hold s * (q | k | v) and for an output of s_att * o: the scores come out multiplied by s^2, which
+// folds into the exponent's factor (sscale = 1 / s^2), the output by s, which folds into the normaliser (oscale = s_att / s).  Powers
+// of two, so both folds are exact.
 template <int NPROD, int F16, int F32IN, int O16>
 __device__ __forceinline__ void attn_p3_body(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
                                              u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
-                                             long long* __restrict__ trace, float oscale) {
-  static_assert(O16 == 0 || (F32IN != 0 && F16 == 0 && NPROD == 6), "fp16 output planes behind bf16 products: the f32-rows arm");
+                                             long long* __restrict__ trace, float oscale, float sscale = 1.f) {
+  static_assert(O16 == 0 || (F32IN != 0 && F16 == 0 && NPROD == 6) || (F32IN == 0 && F16 != 0 && NPROD == 3),
+                "scaled fp16 output planes: behind bf16 products the f32-rows arm, behind fp16 products the planes arm");
   constexpr int NPL = NPROD == 3 ? 2 : 3;               // planes of K / V / Q / the output in use
   constexpr int OF = (F16 != 0 || O16 != 0) ? 1 : 0;    // the output planes' format: fp16 pairs or bf16 triples
   constexpr int ONPL = O16 ? 2 : NPL;                   // ... and their number
@@ -172,7 +177,8 @@ __device__ __forceinline__ void attn_p3_body(const u16* __restrict__ qkv3, int64
 
   int item = blockIdx.x;
   if (item >= nitems) return;
-  const float sc = 0.125f * 1.44269504088896340736f;    // 1 / sqrt(64) and log2(e): p = exp2((s - max) sc)
+  const float sc0 = 0.125f * 1.44269504088896340736f;   // 1 / sqrt(64) and log2(e): p = exp2((s - max) sc)
+  const float sc = (O16 != 0 && F16 != 0) ? sc0 * sscale : sc0;
   if (wave == 7) {
     // ================================================================ the stager
     if constexpr (F32IN) ap3f_stage_k(smem, qf32, plane_elems, (int64_t)(item / heads) * L, W + (item % heads) * 64, L, lane); else
@@ -418,4 +424,11 @@ __global__ __launch_bounds__(512, 2) void attn_p3_o16_kernel(const u16* __restri
                                                              u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
                                                              long long* __restrict__ trace, float oscale) {
   attn_p3_body<6, 0, 1, 1>(qkv3, plane_elems, rows_total, out3, out_plane_elems, L, heads, nitems, trace, oscale);
+}
+
+// two fp16 planes of s * (q | k | v) in, three fp16 products, the two fp16 planes of s_att * o out: sscale = 1 / s^2, oscale = s_att / s
+__global__ __launch_bounds__(512, 2) void attn_p3_h16_kernel(const u16* __restrict__ qkv3, int64_t plane_elems, int64_t rows_total,
+                                                             u16* __restrict__ out3, int64_t out_plane_elems, int L, int heads, int nitems,
+                                                             long long* __restrict__ trace, float oscale, float sscale) {
+  attn_p3_body<3, 1, 0, 1>(qkv3, plane_elems, rows_total, out3, out_plane_elems, L, heads, nitems, trace, oscale, sscale);
 }

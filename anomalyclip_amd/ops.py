@@ -567,6 +567,18 @@ def attention_p3_f32_f16(qkv: torch.Tensor, batch: int, L_: int, heads: int, sca
     return out
 
 
+def attention_p3_h16(qkv2: torch.Tensor, batch: int, L_: int, heads: int, in_scale: float = 1.0, out_scale: float = 1.0) -> torch.Tensor:
+    """acx_attention_p3h16: attention_p3(products=103) on the two fp16 planes of in_scale * (q | k | v) (split_f16x2(in_scale * qkv,
+    panel=True)), returning the two fp16 planes of out_scale * o, [2, batch * L, heads * 64] in K-panel memory order.  Both scales are
+    powers of two in 2^-20 ... 2^20."""
+    W = heads * 64
+    assert qkv2.dtype == torch.float16 and qkv2.is_contiguous() and qkv2.shape == (2, batch * L_, 3 * W)
+    out = torch.empty(2, batch * L_, W, dtype=torch.float16, device=qkv2.device)
+    h = _h(qkv2)
+    L.check(L.lib().acx_attention_p3h16(h, qkv2.data_ptr(), float(in_scale), out.data_ptr(), float(out_scale), batch, L_, heads, _stream()), h)
+    return out
+
+
 def attention_bf16(qkv: torch.Tensor, batch: int, L_: int, heads: int) -> torch.Tensor:
     """bf16 attention (bf16 mode only): qkv [batch*L, 3*heads*64] bf16 -> [batch*L, heads*64] bf16."""
     assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous()

@@ -85,7 +85,15 @@ enum { ACX_PREC_F32X6_R16 = 7 };  /* acx_vit_encode_r16 only: ACX_PREC_F32X6_LN1
                                  combination of V rows; |act(x)| <= |x| for QuickGELU and for the exact GELU alike: x times a factor in [0, 1],
                                  sigmoid(1.702 x) or Phi(x)).  Everything else is ACX_PREC_F32X6_LN16's plan, record for
                                  record.  Tools builds: -DACX_R16_OUT_DEFAULT=0 / -DACX_R16_PROJ_DEFAULT=0 keep that product six-product */
-#define ACX_F16X3_WSCALE 1024.0f   /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
+enum { ACX_PREC_F32X6_QKV16 = 8 }; /* acx_vit_encode_qkv16 only: ACX_PREC_F32X6_R16 one step wider -- in every body layer whose attention is
+                                 the planes attention behind an UNSPLIT plane-kernel in-projection, the in-projection writes the two fp16
+                                 planes of s_qkv * (q | k | v) (acx_gemm_desc.c_scale, where ACX_PREC_F32X6_R16 writes f32 rows: the same
+                                 bytes) and the attention runs its three-product fp16 form on them (acx_attention_p3h16: planes in by
+                                 LDS-DMA, no split in the kernel), writing the planes of s_att * o.  s_qkv is a per-layer power of two the
+                                 CALLER proves from the weights alone for ALL 3 W in-projection rows (the bound of s_att, taken over the Q
+                                 and K rows too).  Everything else is ACX_PREC_F32X6_R16's plan, record for record; weights are bound as
+                                 for ACX_PREC_F32X6_R16.  A tools build with -DACX_QKV16_DEFAULT=0 keeps ACX_PREC_F32X6_R16's records */
+#define ACX_F16X3_WSCALE 1024.0f  /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
 enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
        ACX_ACT_RELU = 3,      /* max(x, 0) in the activation slot (clip/model.py:18-22,122-130 ReLU after a folded BatchNorm) */
@@ -353,6 +361,12 @@ int acx_attention_p3f(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_p
  * power of two in [2^-20, 2^20]; the caller keeps |out_scale * o| inside fp16's range (|o| <= max |v|). */
 int acx_attention_p3f16(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, float out_scale, int32_t batch, int32_t L,
                         int32_t heads, void* stream);
+/* acx_attention_p3n's products = 103 form on scaled planes: qkv_planes = the two fp16 planes (ACX_F16X2P, K-panel layout) of in_scale *
+ * (q | k | v), out_planes = those of out_scale * o.  in_scale^2 folds into the exponent's factor, out_scale / in_scale into the
+ * normaliser: both exact (powers of two in [2^-20, 2^20], checked).  The planes equal acx_split_f16x2(out_scale * o, panel) of the f32
+ * value o the kernel holds, bit for bit.  The caller keeps in_scale * |q, k, v| inside fp16's range.  Same L gate. */
+int acx_attention_p3h16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void* out_planes, float out_scale, int32_t batch, int32_t L,
+                        int32_t heads, void* stream);
 /* ... with the planes in K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo == heads * 64) */
 int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
                            int32_t batch, int32_t L, int32_t heads, void* stream);
@@ -443,6 +457,11 @@ int acx_vit_encode_ln16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weigh
  * 2^14 for a bound the caller proves from the weights; the driver checks only that they are such powers of two. */
 int acx_vit_encode_r16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* scales, const float* frames,
                        int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream);
+/* acx_vit_encode with desc->prec = ACX_PREC_F32X6_QKV16: scales [5 layers] (HOST array), layer l at 5 l: ln_1, ln_2, att, hid as
+ * acx_vit_encode_r16 and s_qkv, the scale of the in-projection's output planes -- one power of two in [2^-20, 2^20] for the three thirds,
+ * with s_qkv * bound <= 2^14 for a bound on every q, k and v element the caller proves from the weights. */
+int acx_vit_encode_qkv16(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights* w, const float* scales, const float* frames,
+                         int32_t nframes, float* features, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The CLIP ResNet image encoders (RN50, RN101, RN50x4, RN50x16, RN50x64: ModifiedResNet, clip/model.py:111-171), eval mode.
@@ -563,7 +582,8 @@ int acx_transformer_forward_act(acx_ctx* ctx, float* x, int32_t batch, int32_t L
  *                  pruned layer's in_proj is the K | V product of all rows (or none: ACX_TF_ATT_CLS_FOLD); Q, for the CLS rows, is
  *                  always a ROWS product
  *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0);
- *                  att_out_dtype: ACX_F16X2P where ACX_TF_ATT_P3F goes out as acx_attention_p3f16, else 0
+ *                  att_out_dtype: ACX_F16X2P where ACX_TF_ATT_P3F goes out as acx_attention_p3f16, or (ACX_PREC_F32X6_QKV16: in_proj's
+ *                  c_dtype is ACX_F16X2P, att ACX_TF_ATT_P3N, att_products 103) ACX_TF_ATT_P3N as acx_attention_p3h16; else 0
  *   split_att, split_mlp  1: acx_split_bf16x3_panel of the attention output / the MLP hidden is launched
  *   pruned         1: the last layer, CLS rows only
  * The plan does not depend on the MLP's activation (acx_vit_desc.act, acx_transformer_forward_act): QuickGELU and the exact GELU take
