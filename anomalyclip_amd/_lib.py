@@ -30,6 +30,8 @@ COMM_ID_BYTES = 128
 SAB_ROUTE_UNSUPPORTED, SAB_ROUTE_TEXT_MFMA, SAB_ROUTE_TEXT_BLOCK, SAB_ROUTE_TEXT_ROWS = 0, 1, 2, 3
 SAB_ROUTE_AXIAL_MFMA, SAB_ROUTE_AXIAL_MFMA_PADDED, SAB_ROUTE_GENERIC = 4, 5, 6
 AXF_ROUTE_UNSUPPORTED, AXF_ROUTE_PADDED_MFMA, AXF_ROUTE_EXACT_MFMA, AXF_ROUTE_THREAD_PER_ROW = 0, 1, 2, 3
+# acx_attention_route (include/acx.h ACX_ATTN_ROUTE_*); a negative answer is acx_attention's error code for the shape
+ATTN_ROUTE_BLOCK32, ATTN_ROUTE_STREAM16, ATTN_ROUTE_STREAM16_QB = 1, 2, 3
 # acx_gemm_route: the route function of csrc/acx_gemm.hip that takes a descriptor (include/acx.h ACX_GEMM_ROUTE_*)
 GEMM_ROUTE_NONE, GEMM_ROUTE_X6_TAIL_SPLIT, GEMM_ROUTE_SK, GEMM_ROUTE_X6, GEMM_ROUTE_S64, GEMM_ROUTE_P256, GEMM_ROUTE_W8 = 0, 1, 2, 3, 4, 5, 6
 GEMM_ROUTE_W8_CONV, GEMM_ROUTE_RING, GEMM_ROUTE_P8, GEMM_ROUTE_DMA_CONV, GEMM_ROUTE_DMA, GEMM_ROUTE_GENERIC = 7, 8, 9, 10, 11, 12
@@ -198,6 +200,7 @@ _SIGS = {
                                        c_float, c_void_p]),
     "acx_attention": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p]),
+    "acx_attention_route": (C.c_int, [c_void_p, c_int32, c_int32, c_int32]),
     "acx_attention_bf16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),

@@ -14,26 +14,50 @@ namespace {
 #include "acx_attn_cls.h"    // attn_cls_kernel, cls_fold_u_kernel, cls_fold_kernel, cls_fold_o_kernel: the CLS row only
 }  // namespace
 
+// The kernel choice of acx_attention / _x3 / _x3_panel: one rule, asked by the dispatcher below and by acx_attention_route.  *why: the
+// refusal's message; *late: the refusal comes after the argument checks of attention_impl (it depends on out, not on the shape alone)
+static int attn_route(const acx_ctx* ctx, int32_t L, int32_t causal, int32_t out_aligned, const char** why, bool* late) {
+  *late = false;
+  *why = "acx_attention: need 0 < L <= 224 (causal) or 0 < L <= 1024 (non-causal)%s";
+  if (L <= 0 || L > (causal ? 224 : 1024)) return ACX_E_UNSUPPORTED;
+  // Calls without a context keep the answer the ABI gave before sequences above 224 were supported (ACX_E_UNSUPPORTED, checked
+  // before any launch: tests/test_cpu_host.py pins it with a NULL context and a host buffer).  Nothing in the kernel needs the
+  // context -- it falls back to 256 CUs below -- this only keeps that earlier contract for context-free callers.
+  *why = "acx_attention: L > 224 needs a context%s";
+  if (L > 224 && !ctx) return ACX_E_UNSUPPORTED;
+  if (!causal && L > 128 && out_aligned && (L > 224 || ACX_DBG_SWITCH("ATTN16", true)))
+    return L > 256 ? ACX_ATTN_ROUTE_STREAM16_QB : ACX_ATTN_ROUTE_STREAM16;
+  *late = true;
+  *why = "acx_attention: L > 224 needs the streaming kernel (out 16-byte aligned, ldo %% 4 == 0)%s";
+  if (L > 224) return ACX_E_UNSUPPORTED;
+  return ACX_ATTN_ROUTE_BLOCK32;
+}
+
+extern "C" int acx_attention_route(const acx_ctx* ctx, int32_t L, int32_t causal, int32_t out_aligned) {
+  const char* why;
+  bool late;
+  return attn_route(ctx, L, causal, out_aligned, &why, &late);
+}
+
 static int attention_impl(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo,
                           int32_t batch, int32_t L, int32_t heads, int32_t causal, void* stream, int x3) {
   if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_attention: null pointer%s");
   if (batch <= 0) return ACX_OK;
-  if (L <= 0 || L > (causal ? 224 : 1024) || heads <= 0)
-    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: need 0 < L <= 224 (causal) or 0 < L <= 1024 (non-causal)%s");
-  // Calls without a context keep the answer the ABI gave before sequences above 224 were supported (ACX_E_UNSUPPORTED, checked
-  // before any launch: tests/test_cpu_host.py pins it with a NULL context and a host buffer).  Nothing in the kernel needs the
-  // context -- it falls back to 256 CUs below -- this only keeps that earlier contract for context-free callers.
-  if (L > 224 && !ctx) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: L > 224 needs a context%s");
+  const char* why;
+  bool late;
+  const int route = attn_route(ctx, L, causal, ldo % 4 == 0 && !((uintptr_t)out & 15), &why, &late);
+  if (heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: need 0 < L <= 224 (causal) or 0 < L <= 1024 (non-causal)%s");
+  if (route < 0 && !late) return acx_fail(ctx, route, why);
   if (ldqkv % 4 || ((uintptr_t)qkv & 15)) return acx_fail(ctx, ACX_E_BADARG, "acx_attention: qkv must be 16-byte aligned, ld%%4==0%s");
   const int nt = (L + 31) / 32;
   const bool nw4 = ACX_DBG_SWITCH("ATTN_NW4", false);
   const dim3 grid((unsigned)(batch * heads));
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_ATTN, (hipStream_t)stream);
-  if (!causal && L > 128 && ldo % 4 == 0 && !((uintptr_t)out & 15) && (L > 224 || ACX_DBG_SWITCH("ATTN16", true))) {
+  if (route == ACX_ATTN_ROUTE_STREAM16 || route == ACX_ATTN_ROUTE_STREAM16_QB) {
     // ViT sequence: 16-wide tiles (one or two query tiles per wave), chunked LDS-DMA staging, two workgroups per CU;
     // L > 256: several query blocks per (sequence, head)
-    const int nqb = L > 256 ? ((L + 15) / 16 + 15) / 16 : 1;
+    const int nqb = route == ACX_ATTN_ROUTE_STREAM16_QB ? ((L + 15) / 16 + 15) / 16 : 1;
     const int nitems = batch * heads * nqb;
     const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
     const int slots = 2 * ncu;                                            // two workgroups per CU
@@ -47,7 +71,7 @@ static int attention_impl(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* 
     return ACX_OK;
   }
   if (x3) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_x3: the ViT kernel only (non-causal, 128 < L <= 1024, out 16-byte aligned)%s");
-  if (L > 224) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention: L > 224 needs the streaming kernel (out 16-byte aligned, ldo %% 4 == 0)%s");
+  if (route != ACX_ATTN_ROUTE_BLOCK32) return acx_fail(ctx, route, why);
   const int dev_slot = (ctx ? ctx->device : 0) & 63;
 #define ACX_ATTN(NT, NW)                                                                           \
   acx_launch_lds<attn_kernel<NT, NW>>(dev_slot, grid, dim3(NW * 64), (size_t)NT * 32 * (KROW + VROW) * 4 + NW * 32 * 4 + 16, s, \

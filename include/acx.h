@@ -335,6 +335,13 @@ int acx_layernorm_scaled(acx_ctx* ctx, const float* x, int64_t ldx, const float*
  * in_proj output (q | k | v); out: [batch*L, heads*64]. */
 int acx_attention(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo,
                   int32_t batch, int32_t L, int32_t heads, int32_t causal, void* stream);
+/* acx_attention_route: which kernel acx_attention (and _x3 / _x3_panel, which take the two streaming routes only) runs a sequence
+ * on -- the rule the dispatcher itself switches on.  Arithmetic on the arguments: no device, nothing dereferenced, ctx may be NULL.
+ * out_aligned: out is 16-byte aligned and ldo % 4 == 0.  BLOCK32: attn_kernel<NT, NW>, one workgroup per (sequence, head), 32-key
+ * blocks, L <= 224; STREAM16: attn16_kernel, 16-key tiles streamed through LDS, 128 < L <= 256 non-causal; STREAM16_QB: the same
+ * with several query blocks per (sequence, head), L > 256.  A negative answer is the error code acx_attention gives for the shape. */
+enum { ACX_ATTN_ROUTE_BLOCK32 = 1, ACX_ATTN_ROUTE_STREAM16 = 2, ACX_ATTN_ROUTE_STREAM16_QB = 3 };
+int acx_attention_route(const acx_ctx* ctx, int32_t L, int32_t causal, int32_t out_aligned);
 /* the same (non-causal ViT sequences, 128 < L <= 1024) with the output as three bf16 planes hi | mid | lo (ACX_BF16X3:
  * plane p at (uint16_t*)out_planes + p * batch * L * ldo): the out-projection's A operand in ACX_PREC_F32X6 mode */
 int acx_attention_x3(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
