@@ -17,6 +17,7 @@ PREC_BF16X6 = 5                         # acx_resnet_desc.prec only: the ResNet 
 PREC_F32X6_LN16 = 6                     # acx_vit_encode_ln16 only: PREC_F32X6 with the LayerNorm-fed products on fp16 planes (what "auto" resolves to)
 PREC_F32X6_R16 = 7                      # acx_vit_encode_r16 only: PREC_F32X6_LN16 with out-proj and c_proj on fp16 planes too ("auto", every proof passing)
 PREC_F32X6_QKV16 = 8                    # acx_vit_encode_qkv16 only: PREC_F32X6_R16 with q | k | v as fp16 planes into the three-product planes attention
+PREC_F16X3S = 9                         # PREC_F16X3 on every ViT sequence length: the streaming fp16 planes attention outside 193..208 tokens (precision "f16x3s")
 ACT_NONE, ACT_QUICKGELU, ACT_LEAKYRELU, ACT_RELU, ACT_RESRELU = 0, 1, 2, 3, 4
 ACT_GELU = 5                            # the exact GELU 0.5 x (1 + erf(x / sqrt 2)): CLIP checkpoints not trained with QuickGELU
 AMAP_IDENTITY, AMAP_CONV3X3, AMAP_TESTTILE, AMAP_TILETABLE = 0, 1, 2, 3
@@ -42,7 +43,7 @@ TN_ROUTE_NONE, TN_ROUTE_W8, TN_ROUTE_P256, TN_ROUTE_X6_256x256, TN_ROUTE_X6_256x
 TF_LN_ROWS, TF_LN_PLANES, TF_LN_RIDDEN, TF_LN_CLS = 0, 1, 2, 3
 TF_GEMM_ROWS, TF_GEMM_X6 = 0, 1
 TF_BUF_NONE, TF_BUF_SPLITK, TF_BUF_H, TF_BUF_QKV, TF_BUF_MLP = 0, 1, 2, 3, 4
-TF_ATT_F32, TF_ATT_BF16, TF_ATT_X3_PANEL, TF_ATT_P3N, TF_ATT_P3F, TF_ATT_CLS, TF_ATT_CLS_FOLD = 0, 1, 2, 3, 4, 5, 6
+TF_ATT_F32, TF_ATT_BF16, TF_ATT_X3_PANEL, TF_ATT_P3N, TF_ATT_P3F, TF_ATT_CLS, TF_ATT_CLS_FOLD, TF_ATT_S16 = 0, 1, 2, 3, 4, 5, 6, 7
 
 
 class GemmDesc(C.Structure):
@@ -208,6 +209,7 @@ _SIGS = {
     "acx_attention_p3f": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3f16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3h16": (C.c_int, [c_void_p, c_void_p, c_float, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_s16": (C.c_int, [c_void_p, c_void_p, c_float, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3_panel": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_cls_fold_workspace_bytes": (c_size_t, [c_int32, c_int32]),

@@ -29,6 +29,8 @@ from .. import ops
 # kernels everywhere (v_mfma_f32_32x32x2_f32: an fmaf chain).  "bf16": bf16 operands, not a parity path.
 # "bf16x3" (opt-in, NOT f32-accurate): the plane kernels with the three leading cross products only (ACX_PREC_F32X3)
 # "f16x3" (opt-in): TWO fp16 planes per operand, three exact products -- f32-MFMA-level results for operands inside fp16's range
+# "f16x3s" (opt-in): the "f16x3" arithmetic on EVERY ViT geometry up to 1024 tokens -- outside 193..208 tokens the attention is the
+# streaming fp16 planes kernel (acx_attention_s16); on the ViT-B/16 geometry it is "f16x3", bit for bit.  Same fp16-range caveat.
 # "auto" on the CLIP ViT widths (768, 1024) additionally runs the two LayerNorm-fed products of every body layer (in-projection, c_fc)
 # as three-product GEMMs of fp16 planes (ACX_PREC_F32X6_LN16) wherever they take the plane kernel, when ln16_scales() proves, from the
 # weights alone, that their operands stay inside fp16's range whatever the frames are; otherwise -- and always under "f32x6" -- six
@@ -37,7 +39,7 @@ from .. import ops
 # A third step (ACX_PREC_F32X6_QKV16), when qkv16_scales() bounds the Q and K rows of the in-projection as it bounds the V rows: q | k | v
 # leave the in-projection as fp16 planes and the planes attention runs its three-product fp16 form on them.
 PRECISIONS = {"auto": L.PREC_F32X6, "f32": L.PREC_F32, "bf16": L.PREC_BF16, "f32x6": L.PREC_F32X6, "bf16x3": L.PREC_F32X3,
-              "f16x3": L.PREC_F16X3}
+              "f16x3": L.PREC_F16X3, "f16x3s": L.PREC_F16X3S}
 F16X3_WSCALE = 1024.0                                  # include/acx.h ACX_F16X3_WSCALE
 # The MLP's activation.  "quick_gelu" (the default): x sigmoid(1.702 x), what OpenAI's checkpoints were trained with.  "gelu": nn.GELU,
 # 0.5 x (1 + erf(x / sqrt 2)), what open_clip's LAION-2B / DataComp checkpoints of the same architectures were trained with (configs
@@ -66,7 +68,8 @@ def check_vit_precision(precision: str, tokens: int, width: int, arch: str, reso
     """A ValueError, before any launch, for a precision a ViT geometry cannot honour.  "bf16x3" and "f16x3" are stated for the
     ViT-B/16 geometry (f16x3 needs the planes attention, 192 < tokens <= 208, whenever a product takes the plane kernels; bf16x3's
     accuracy is measured there only): they are refused for the ViT-B/32 / ViT-L/14 / ViT-L/14@336px geometries and for anything
-    above 224 tokens (which no earlier release ran).  Other geometries keep what they did before (small ones, such as the test
+    above 224 tokens (which no earlier release ran); "f16x3s" is the f16x3 arithmetic for every geometry up to 1024 tokens (the
+    streaming planes attention).  Other geometries keep what they did before (small ones, such as the test
     geometry, run those launches on the f32 kernels).  "auto", "f32" and "bf16" run every geometry up to 1024 tokens."""
     if precision == "bf16x6":
         raise ValueError(f"precision 'bf16x6' is a ResNet encoder precision: for {arch} 'auto' already is that arithmetic (every large "
@@ -313,14 +316,14 @@ class Transformer(nn.Module):
             mixed = prec in (L.PREC_F32X6_LN16, L.PREC_F32X6_R16)
             f16w = {"in_proj_w_bf16": mixed, "fc_w_bf16": mixed and ln16_fc, "out_proj_w_bf16": prec == L.PREC_F32X6_R16 and r16[0],
                     "proj_w_bf16": prec == L.PREC_F32X6_R16 and r16[1]}
-            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16, L.PREC_F32X6_R16):
+            if prec in (L.PREC_BF16, L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F16X3S, L.PREC_F32X6_LN16, L.PREC_F32X6_R16):
                 for name, p in (("in_proj_w_bf16", b.attn.in_proj_weight), ("out_proj_w_bf16", b.attn.out_proj.weight),
                                 ("fc_w_bf16", b.mlp.c_fc.weight), ("proj_w_bf16", b.mlp.c_proj.weight)):
                     # bf16 mode: one rounded copy; f32x6: the three planes hi | mid | lo of the f32 weight, each in K-panel
                     # layout [K / 32][N][32] (ACX_BF16X3P: what acx_transformer_forward's bf16 x 6 products read)
                     # PREC_F32X6_LN16: fp16 planes for the LayerNorm-fed products, the six-product planes for the other two
                     # PREC_F32X6_R16: fp16 planes for the residual products the plan moves as well
-                    if prec == L.PREC_F16X3 or f16w[name]:
+                    if prec in (L.PREC_F16X3, L.PREC_F16X3S) or f16w[name]:
                         # two fp16 planes of 2^10 w (K-panel layout)
                         t = ops.split_f16x2(p.detach(), panel=True, scale=F16X3_WSCALE)
                     else:
@@ -503,10 +506,10 @@ class VisionTransformer(nn.Module):
             cb, pb = ops.cast_bf16(conv), ops.cast_bf16(proj_t)
             keep += [cb, pb]
             w.conv1_w_bf16, w.proj_t_bf16 = cb.data_ptr(), pb.data_ptr()
-        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F32X6_LN16, L.PREC_F32X6_R16) and self.patch_size % 4 == 0:
+        elif prec in (L.PREC_F32X6, L.PREC_F32X3, L.PREC_F16X3, L.PREC_F16X3S, L.PREC_F32X6_LN16, L.PREC_F32X6_R16) and self.patch_size % 4 == 0:
             # the patch embedding as a bf16 x 6 product: the weight's three planes in K-panel layout (ACX_BF16X3P; a patch of 14,
             # K = 588, is not a whole number of 32-column panels: acx_vit_encode embeds it on the f32 kernels)
-            cb = ops.split_f16x2(conv, panel=True, scale=F16X3_WSCALE) if prec == L.PREC_F16X3 else ops.split_bf16x3(conv, panel=True)
+            cb = ops.split_f16x2(conv, panel=True, scale=F16X3_WSCALE) if prec in (L.PREC_F16X3, L.PREC_F16X3S) else ops.split_bf16x3(conv, panel=True)
             keep.append(cb)
             w.conv1_w_bf16 = cb.data_ptr()
         w.class_embedding = self.class_embedding.data_ptr()

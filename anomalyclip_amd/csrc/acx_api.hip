@@ -231,7 +231,7 @@ struct TfWs {   // transformer scratch carved from the caller's workspace
 // the plane modes of the drivers: ACX_PREC_F32X6 (six products: f32-accurate) and ACX_PREC_F32X3 (the three leading products)
 static inline bool is_xmode(int prec) {
   return prec == ACX_PREC_F32X6 || prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3 || prec == ACX_PREC_F32X6_LN16 ||
-         prec == ACX_PREC_F32X6_R16 || prec == ACX_PREC_F32X6_QKV16;
+         prec == ACX_PREC_F32X6_R16 || prec == ACX_PREC_F32X6_QKV16 || prec == ACX_PREC_F16X3S;
 }
 // the six-product modes whose LayerNorm-fed products read fp16 planes (ACX_PREC_F32X6_R16: the residual products too)
 static inline bool is_r16(int prec) { return prec == ACX_PREC_F32X6_R16 || prec == ACX_PREC_F32X6_QKV16; }
@@ -245,9 +245,11 @@ struct XMode {
   int pairs;                                     // acx_gemm_desc.pairs of the driver's plane products (and the attention's products)
   bool f16;                                      // ACX_PREC_F16X3: two fp16 planes per operand (weights scaled by ACX_F16X3_WSCALE)
 };
-static inline XMode xmode_of(int prec) { return {(prec == ACX_PREC_F32X3 || prec == ACX_PREC_F16X3) ? 3 : 6, prec == ACX_PREC_F16X3}; }
+// ACX_PREC_F16X3S: ACX_PREC_F16X3 in everything but the attention rule (tf_plan)
+static inline bool is_f16x3(int prec) { return prec == ACX_PREC_F16X3 || prec == ACX_PREC_F16X3S; }
+static inline XMode xmode_of(int prec) { return {(prec == ACX_PREC_F32X3 || is_f16x3(prec)) ? 3 : 6, is_f16x3(prec)}; }
 // what LayerNorm / acx_vit_patches write for the plane products of a mode
-static inline int plane_dtype_of(int prec) { return prec == ACX_PREC_F16X3 ? ACX_F16X2P : prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P; }
+static inline int plane_dtype_of(int prec) { return is_f16x3(prec) ? ACX_F16X2P : prec == ACX_PREC_F32X3 ? ACX_BF16X2P : ACX_BF16X3P; }
 
 TfWs carve_tf(char* base, int64_t rows, int W, int prec = ACX_PREC_F32) {
   TfWs w;
@@ -485,6 +487,8 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   const bool ab = m.prec == ACX_PREC_BF16 && !g.causal && L <= 224 && ACX_DBG_SWITCH("ATTN_BF16", true);
   // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
   const bool att_p3 = x6_qkv && x6_out && !g.causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
+  // ACX_PREC_F16X3S: every other non-causal sequence takes the streaming fp16 planes attention (acx_attention_s16)
+  const bool att_s16 = g.prec == ACX_PREC_F16X3S && x6_qkv && x6_out && !g.causal && L <= 1024 && !att_p3;
   // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
   // ACX_PREC_F32X6_R16: a residual product goes fp16 only where it AND its producer take the plane kernels -- out-proj behind the planes
   // attention (whose f32-rows arm writes the fp16 planes: taken whatever ACX_OPT_ATTN_F32IN says, out-proj's weights come as fp16 planes
@@ -497,7 +501,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   // as fp16 planes too and the attention is its three-product fp16 form.  An fp16 plane output never takes a K split, so a layer whose
   // ACX_PREC_F32X6_R16 in-projection acx_gemm would split (few tiles: small launches) keeps that record.
   p->qkv16 = g.prec == ACX_PREC_F32X6_QKV16 && o.qkv16 && p->r16_out && p->ln16_qkv && att_p3f && !in_proj_splits(err, g, rows);
-  const bool qkv_planes = att_p3 && !att_p3f;
+  const bool qkv_planes = (att_p3 && !att_p3f) || att_s16;
   // ... or on f32 rows, writing the out-projection's three planes itself
   const bool att_x3 = x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
   // ACX_OPT_CLS_FOLD (every precision but bf16): the pruned layer without K and V -- ln_1 and Q for the CLS rows, then
@@ -513,7 +517,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   int rc;
   if (g.layers > (g.prune ? 1 : 0)) {
     if ((rc = need(x6_qkv, 0))) return rc;
-    if (m.xm.f16 && (x6_qkv || x6_out || x6_fc || x6_proj) && !(att_p3 && x6_fc && x6_proj))
+    if (m.xm.f16 && (x6_qkv || x6_out || x6_fc || x6_proj) && !((att_p3 || att_s16) && x6_fc && x6_proj))
       return acx_fail(err, ACX_E_UNSUPPORTED, "driver: ACX_PREC_F16X3 needs the planes attention (192 < L <= 208) and all four products on the plane kernel%s");
     if ((rc = need(x6_out, 1)) || (rc = need(x6_fc, 2)) || (rc = need(x6_proj, 3))) return rc;
   }
@@ -532,7 +536,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   b.ln1_dtype = p->ln16_qkv ? ACX_F16X2P : x6_qkv ? m.pdt : m.hdt;
   b.in_proj = !x6_qkv ? tf_rows(ab ? ACX_BF16 : ACX_F32, ACX_TF_BUF_SPLITK)
                       : qkv_planes ? tf_x6(cpl, ACX_TF_BUF_QKV, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
-  b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
+  b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_s16 ? ACX_TF_ATT_S16 : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
   b.att_products = b.att == ACX_TF_ATT_P3N ? (m.xm.f16 ? 103 : m.xm.pairs) : 0;
   b.att_out_dtype = p->r16_out ? ACX_F16X2P : 0;
   if (p->qkv16) {
@@ -540,7 +544,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
     b.att = ACX_TF_ATT_P3N;
     b.att_products = 103;
   }
-  b.split_att = x6_out && !att_x3 && !att_p3;
+  b.split_att = x6_out && !att_x3 && !att_p3 && !att_s16;
   b.out_proj = x6_out ? tf_x6(ACX_F32, ACX_TF_BUF_H, ln_ride && x6_fc) : tf_rows(ACX_F32, ACX_TF_BUF_SPLITK);
   b.ln2 = !x6_fc ? ACX_TF_LN_ROWS : b.out_proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
   b.ln2_dtype = p->ln16_fc ? ACX_F16X2P : x6_fc ? m.pdt : m.hdt;
@@ -659,6 +663,7 @@ struct TfRun {
         rc = s_qkv > 0.f ? acx_attention_p3h16(ctx, ws.qkv, s_qkv, ws.hp, s_att, batch, L, heads, s)
                          : acx_attention_p3n(ctx, ws.qkv3, ws.hp, batch, L, heads, r.att_products, s);
         break;
+      case ACX_TF_ATT_S16: rc = acx_attention_s16(ctx, ws.qkv3, 1.f, ws.hp, 1.f, batch, L, heads, s); break;                  // fp16 planes in, fp16 planes out
       case ACX_TF_ATT_X3_PANEL: rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s); break;
       default: rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, g.causal, s); break;
     }

@@ -10,6 +10,7 @@
 namespace {
 #include "acx_attn_f32.h"    // attn_kernel, attn16_kernel: f32 MFMAs
 #include "acx_attn_p3.h"     // attn_p3_kernel: bf16 / fp16 operand planes (or f32 rows split in the kernel), f32-accurate products
+#include "acx_attn_s16.h"    // attn_s16_kernel: two fp16 planes per operand, streaming over the keys (any L <= 1024)
 #include "acx_attn_bf16.h"   // attn_bf16_kernel: bf16 operands, the bf16 mode of the ViT
 #include "acx_attn_cls.h"    // attn_cls_kernel, cls_fold_u_kernel, cls_fold_kernel, cls_fold_o_kernel: the CLS row only
 }  // namespace
@@ -193,6 +194,31 @@ extern "C" int acx_attention_p3h16(acx_ctx* ctx, const void* qkv_planes, float i
     return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_p3h16: 192 < L <= 208, 16-byte aligned planes%s");
   return ap3_launch(ctx, 116, qkv_planes, 0, out_planes, batch, L, heads, stream, "acx_attention_p3h16", out_scale / in_scale,
                     1.f / (in_scale * in_scale));
+}
+
+// the same contract without the L gate: the streaming kernel (attn_s16_kernel), 1 <= L <= 1024.  Every refusal comes before the launch.
+extern "C" int acx_attention_s16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void* out_planes, float out_scale, int32_t batch,
+                                 int32_t L, int32_t heads, void* stream) {
+  if (!qkv_planes || !out_planes) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_s16: null pointer%s");
+  int e = 0;
+  if (!(in_scale >= 0x1p-20f && in_scale <= 0x1p20f) || frexpf(in_scale, &e) != 0.5f || !(out_scale >= 0x1p-20f && out_scale <= 0x1p20f) ||
+      frexpf(out_scale, &e) != 0.5f)
+    return acx_fail(ctx, ACX_E_BADARG, "acx_attention_s16: in_scale and out_scale must be powers of two in [2^-20, 2^20]%s");
+  if (batch < 1 || heads < 1) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_s16: need batch >= 1 and heads >= 1%s");
+  if (L < 1 || L > 1024) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_s16: need 1 <= L <= 1024%s");
+  if (((uintptr_t)qkv_planes | (uintptr_t)out_planes) & 15) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_s16: planes must be 16-byte aligned%s");
+  const int nt = (L + 31) / 32, nqb = (nt + AS16_NW - 1) / AS16_NW;
+  const int64_t rows = (int64_t)batch * L, items = (int64_t)batch * heads * nqb;
+  if (items > INT32_MAX || rows * 3 * heads * 64 > ((int64_t)1 << 40))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_s16: batch * heads too large%s");
+  const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
+  hipStream_t s = (hipStream_t)stream;
+  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+  const dim3 grid((unsigned)(items < 2 * ncu ? items : 2 * ncu));   // two workgroups per CU
+  hipLaunchKernelGGL(attn_s16_kernel, grid, dim3(AS16_NW * 64), (size_t)AS16_LDS_B, s, (const u16*)qkv_planes, rows * 3 * heads * 64, rows,
+                     (u16*)out_planes, rows * heads * 64, L, heads, batch * heads, (int)items, out_scale / in_scale, 1.f / (in_scale * in_scale));
+  ACX_CHECK_LAUNCH(ctx, "acx_attention_s16");
+  return ACX_OK;
 }
 
 extern "C" int acx_attention_x3(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,

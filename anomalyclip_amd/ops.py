@@ -579,6 +579,20 @@ def attention_p3_h16(qkv2: torch.Tensor, batch: int, L_: int, heads: int, in_sca
     return out
 
 
+def attention_s16(planes: torch.Tensor, batch: int, L_: int, heads: int, in_scale: float = 1.0, out_scale: float = 1.0) -> torch.Tensor:
+    """acx_attention_s16: attention_p3_h16's contract at any sequence length 1 <= L <= 1024 (the streaming kernel: keys in chunks of 64,
+    running max and sum, 64 KB of LDS whatever L).  planes: the two fp16 planes of in_scale * (q | k | v), [2, batch * L, 3 * heads * 64]
+    in K-panel memory order (split_f16x2(in_scale * qkv, panel=True)); returns the two fp16 planes of out_scale * o, [2, batch * L,
+    heads * 64], K-panel memory order as well.  Both scales are powers of two in 2^-20 ... 2^20; the library refuses anything else
+    before a launch."""
+    W = heads * 64
+    assert planes.dtype == torch.float16 and planes.is_contiguous() and planes.shape == (2, max(batch, 0) * max(L_, 0), 3 * W)
+    out = torch.empty(2, max(batch, 0) * max(L_, 0), W, dtype=torch.float16, device=planes.device)
+    h = _h(planes)
+    L.check(L.lib().acx_attention_s16(h, planes.data_ptr(), float(in_scale), out.data_ptr(), float(out_scale), batch, L_, heads, _stream()), h)
+    return out
+
+
 def attention_bf16(qkv: torch.Tensor, batch: int, L_: int, heads: int) -> torch.Tensor:
     """bf16 attention (bf16 mode only): qkv [batch*L, 3*heads*64] bf16 -> [batch*L, heads*64] bf16."""
     assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous()

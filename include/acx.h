@@ -93,6 +93,12 @@ enum { ACX_PREC_F32X6_QKV16 = 8 }; /* acx_vit_encode_qkv16 only: ACX_PREC_F32X6_
                                  CALLER proves from the weights alone for ALL 3 W in-projection rows (the bound of s_att, taken over the Q
                                  and K rows too).  Everything else is ACX_PREC_F32X6_R16's plan, record for record; weights are bound as
                                  for ACX_PREC_F32X6_R16.  A tools build with -DACX_QKV16_DEFAULT=0 keeps ACX_PREC_F32X6_R16's records */
+enum { ACX_PREC_F16X3S = 9 };     /* ACX_PREC_F16X3 on every ViT sequence length: the same planes (ACX_F16X2P), the same weights
+                                 (acx_split_f16x2(2^10 w)), the same three products, the same "all four products on the plane kernel, or
+                                 none" rule and the same fall-back to the f32 plan with an f32-sized workspace -- except the attention
+                                 rule: non-causal 192 < L <= 208 keeps ACX_TF_ATT_P3N (products 103: ACX_PREC_F16X3's plan, record for
+                                 record), every other non-causal L <= 1024 takes the streaming planes attention (ACX_TF_ATT_S16,
+                                 acx_attention_s16).  Operands must lie inside fp16's range, as for ACX_PREC_F16X3: opt-in */
 #define ACX_F16X3_WSCALE 1024.0f  /* ACX_PREC_F16X3: the weights' fp16 planes hold 2^10 * w (acx_split_f16x2: lifts CLIP-sized weights into
                                       fp16's normal range so that the lo plane keeps its 11 bits; |w| < 63.9); the drivers' products undo it */
 enum { ACX_ACT_NONE = 0, ACX_ACT_QUICKGELU = 1, ACX_ACT_LEAKYRELU = 2,
@@ -374,6 +380,15 @@ int acx_attention_p3f16(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out
  * value o the kernel holds, bit for bit.  The caller keeps in_scale * |q, k, v| inside fp16's range.  Same L gate. */
 int acx_attention_p3h16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void* out_planes, float out_scale, int32_t batch, int32_t L,
                         int32_t heads, void* stream);
+/* acx_attention_p3h16's contract without the L gate -- the streaming kernel.  qkv_planes: the two fp16 planes (ACX_F16X2P, K-panel
+ * layout) of in_scale * (q | k | v), [batch * L, 3 * heads * 64]; out_planes: those of out_scale * o, [batch * L, heads * 64].  Products
+ * hi.hi, hi.lo, lo.hi in both contractions (v_mfma_f32_*_f16, f32 accumulation), softmax in f32 with a running max and sum over chunks
+ * of 64 keys, P split into an fp16 pair as it is consumed.  Non-causal, head dim 64, 1 <= L <= 1024; in_scale / out_scale powers of two
+ * in [2^-20, 2^20] (in_scale^2 folds into the exponent's factor, out_scale / in_scale into the normaliser: exact).  64 KB of LDS whatever
+ * L; nothing outside the [batch * L] rows of either buffer is read or written.  Refusals, all before any launch: ACX_E_UNSUPPORTED for
+ * L outside 1..1024, ACX_E_BADARG for batch < 1, heads < 1, a scale that is no power of two in range, planes not 16-byte aligned. */
+int acx_attention_s16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void* out_planes, float out_scale, int32_t batch, int32_t L,
+                      int32_t heads, void* stream);
 /* ... with the planes in K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo == heads * 64) */
 int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
                            int32_t batch, int32_t L, int32_t heads, void* stream);
@@ -590,7 +605,8 @@ int acx_transformer_forward_act(acx_ctx* ctx, float* x, int32_t batch, int32_t L
  *                  always a ROWS product
  *   att            ACX_TF_ATT_*: the attention entry point; att_products: acx_attention_p3n's product count (6 / 3 / 103, else 0);
  *                  att_out_dtype: ACX_F16X2P where ACX_TF_ATT_P3F goes out as acx_attention_p3f16, or (ACX_PREC_F32X6_QKV16: in_proj's
- *                  c_dtype is ACX_F16X2P, att ACX_TF_ATT_P3N, att_products 103) ACX_TF_ATT_P3N as acx_attention_p3h16; else 0
+ *                  c_dtype is ACX_F16X2P, att ACX_TF_ATT_P3N, att_products 103) ACX_TF_ATT_P3N as acx_attention_p3h16; else 0.
+ *                  ACX_TF_ATT_S16 (ACX_PREC_F16X3S): acx_attention_s16 on in_proj's ACX_F16X2P planes, writing out_proj's (scales 1)
  *   split_att, split_mlp  1: acx_split_bf16x3_panel of the attention output / the MLP hidden is launched
  *   pruned         1: the last layer, CLS rows only
  * The plan does not depend on the MLP's activation (acx_vit_desc.act, acx_transformer_forward_act): QuickGELU and the exact GELU take
@@ -599,7 +615,7 @@ enum { ACX_TF_LN_ROWS = 0, ACX_TF_LN_PLANES = 1, ACX_TF_LN_RIDDEN = 2, ACX_TF_LN
 enum { ACX_TF_GEMM_ROWS = 0, ACX_TF_GEMM_X6 = 1 };
 enum { ACX_TF_BUF_NONE = 0, ACX_TF_BUF_SPLITK = 1, ACX_TF_BUF_H = 2, ACX_TF_BUF_QKV = 3, ACX_TF_BUF_MLP = 4 };
 enum { ACX_TF_ATT_F32 = 0, ACX_TF_ATT_BF16 = 1, ACX_TF_ATT_X3_PANEL = 2, ACX_TF_ATT_P3N = 3, ACX_TF_ATT_P3F = 4, ACX_TF_ATT_CLS = 5,
-       ACX_TF_ATT_CLS_FOLD = 6 };
+       ACX_TF_ATT_CLS_FOLD = 6, ACX_TF_ATT_S16 = 7 };
 typedef struct acx_tf_product_t {
   int32_t kernel, c_dtype, scratch, ln_job;
 } acx_tf_product_t;
