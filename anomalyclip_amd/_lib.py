@@ -33,6 +33,8 @@ SAB_ROUTE_AXIAL_MFMA, SAB_ROUTE_AXIAL_MFMA_PADDED, SAB_ROUTE_GENERIC = 4, 5, 6
 AXF_ROUTE_UNSUPPORTED, AXF_ROUTE_PADDED_MFMA, AXF_ROUTE_EXACT_MFMA, AXF_ROUTE_THREAD_PER_ROW = 0, 1, 2, 3
 # acx_attention_route (include/acx.h ACX_ATTN_ROUTE_*); a negative answer is acx_attention's error code for the shape
 ATTN_ROUTE_BLOCK32, ATTN_ROUTE_STREAM16, ATTN_ROUTE_STREAM16_QB = 1, 2, 3
+# acx_attention_hd_route (include/acx.h ACX_ATTN_HD_ROUTE_*): head dimension 80
+ATTN_HD_ROUTE_STREAM, ATTN_HD_ROUTE_STREAM_QB = 1, 2
 # acx_gemm_route: the route function of csrc/acx_gemm.hip that takes a descriptor (include/acx.h ACX_GEMM_ROUTE_*)
 GEMM_ROUTE_NONE, GEMM_ROUTE_X6_TAIL_SPLIT, GEMM_ROUTE_SK, GEMM_ROUTE_X6, GEMM_ROUTE_S64, GEMM_ROUTE_P256, GEMM_ROUTE_W8 = 0, 1, 2, 3, 4, 5, 6
 GEMM_ROUTE_W8_CONV, GEMM_ROUTE_RING, GEMM_ROUTE_P8, GEMM_ROUTE_DMA_CONV, GEMM_ROUTE_DMA, GEMM_ROUTE_GENERIC = 7, 8, 9, 10, 11, 12
@@ -44,6 +46,7 @@ TF_LN_ROWS, TF_LN_PLANES, TF_LN_RIDDEN, TF_LN_CLS = 0, 1, 2, 3
 TF_GEMM_ROWS, TF_GEMM_X6 = 0, 1
 TF_BUF_NONE, TF_BUF_SPLITK, TF_BUF_H, TF_BUF_QKV, TF_BUF_MLP = 0, 1, 2, 3, 4
 TF_ATT_F32, TF_ATT_BF16, TF_ATT_X3_PANEL, TF_ATT_P3N, TF_ATT_P3F, TF_ATT_CLS, TF_ATT_CLS_FOLD, TF_ATT_S16 = 0, 1, 2, 3, 4, 5, 6, 7
+TF_ATT_HD_F32, TF_ATT_HD_X3_PANEL, TF_ATT_HD_CLS = 8, 9, 10          # width == 80 heads
 
 
 class GemmDesc(C.Structure):
@@ -202,6 +205,10 @@ _SIGS = {
     "acx_attention": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p]),
     "acx_attention_route": (C.c_int, [c_void_p, c_int32, c_int32, c_int32]),
+    "acx_attention_hd": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_x3_hd": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_cls_hd": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "acx_attention_hd_route": (C.c_int, [c_void_p, c_int32, c_int32, c_int32]),
     "acx_attention_bf16": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_x3": (C.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "acx_attention_p3": (C.c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),

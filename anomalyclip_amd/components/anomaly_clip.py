@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, RN50, RN101, RN50X4, RN50X16, RN50X64, TINY
+from ..init_weights import ClipGeometry, VIT_B16, VIT_B32, VIT_L14, VIT_L14_336, VIT_H14, RN50, RN101, RN50X4, RN50X16, RN50X64, TINY
 from .clip_resnet import ModifiedResNet, check_resnet_precision
 from .clip_vit import VisionTransformer, check_act, check_head_geometry, check_vit_precision
 from .coop import PromptLearner
@@ -30,8 +30,9 @@ from .selector_model import SelectorModel
 from .temporal_model import TemporalModel
 from .text_encoder import TextEncoder
 
-# `net.arch`: the nine backbones of clip.load (clip/clip.py:31-41); "tiny" is the test geometry
-_ARCH = {"ViT-B/16": VIT_B16, "ViT-B/32": VIT_B32, "ViT-L/14": VIT_L14, "ViT-L/14@336px": VIT_L14_336,
+# `net.arch`: the nine backbones of clip.load (clip/clip.py:31-41) under clip.load's names, open_clip's ViT-H-14 under open_clip's
+# name (there is no "ViT-H/14": clip.load has no such model); "tiny" is the test geometry
+_ARCH = {"ViT-B/16": VIT_B16, "ViT-B/32": VIT_B32, "ViT-L/14": VIT_L14, "ViT-L/14@336px": VIT_L14_336, "ViT-H-14": VIT_H14,
          "RN50": RN50, "RN101": RN101, "RN50x4": RN50X4, "RN50x16": RN50X16, "RN50x64": RN50X64, "tiny": TINY}
 
 
@@ -79,6 +80,10 @@ def geometry_from_state_dict(sd) -> Optional[ClipGeometry]:
             kw["image_resolution"] = P * int(round(math.sqrt(int(pos.shape[0]) - 1)))
         if proj is not None:
             kw["embed_dim"] = int(proj.shape[1])
+        if kw["vision_width"] == 1280:
+            # the weights do not hold the head count.  The one CLIP at this width is open_clip's ViT-H-14: head_width 80, trained
+            # with the exact GELU.  Every other width keeps head dimension 64 and the default activation
+            kw.update(vision_head_dim=80, act="gelu")
     tpos = sd.get("text_encoder.positional_embedding")
     if tpos is not None:
         kw.update(context_length=int(tpos.shape[0]), transformer_width=int(tpos.shape[1]),
@@ -89,7 +94,7 @@ def geometry_from_state_dict(sd) -> Optional[ClipGeometry]:
             kw["embed_dim"] = int(tproj.shape[1])
     if not kw:
         return None
-    base = VIT_B16.as_kwargs()
+    base = VIT_B16.as_kwargs()                               # (leaves act and vision_head_dim to kw or the defaults)
     base.update(kw)
     return ClipGeometry(**base)
 _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data", "prompts.json")
@@ -170,7 +175,7 @@ class AnomalyCLIP(nn.Module):
                                  "encoder (components.clip_resnet.ModifiedResNet) on its own as a feature extractor")
         else:
             check_vit_precision(vit_precision, geom.grid ** 2 + 1, geom.vision_width, self.arch, geom.image_resolution,
-                                geom.vision_patch_size)                                # (before anything is allocated)
+                                geom.vision_patch_size, geom.vision_head_dim)                             # (before anything is allocated)
 
         classnames = g("classnames")
         tokenized = g("tokenized_prompts")

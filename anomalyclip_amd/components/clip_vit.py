@@ -64,18 +64,23 @@ def check_act(act, precision: Optional[str] = None, arch: Optional[str] = None, 
 _NEW_ARCH_VISION = {(224, 32, 768), (224, 14, 1024), (336, 14, 1024)}
 
 
-def check_vit_precision(precision: str, tokens: int, width: int, arch: str, resolution: int = 0, patch: int = 0):
+def check_vit_precision(precision: str, tokens: int, width: int, arch: str, resolution: int = 0, patch: int = 0, head_dim: int = 64):
     """A ValueError, before any launch, for a precision a ViT geometry cannot honour.  "bf16x3" and "f16x3" are stated for the
     ViT-B/16 geometry (f16x3 needs the planes attention, 192 < tokens <= 208, whenever a product takes the plane kernels; bf16x3's
     accuracy is measured there only): they are refused for the ViT-B/32 / ViT-L/14 / ViT-L/14@336px geometries and for anything
     above 224 tokens (which no earlier release ran); "f16x3s" is the f16x3 arithmetic for every geometry up to 1024 tokens (the
     streaming planes attention).  Other geometries keep what they did before (small ones, such as the test
-    geometry, run those launches on the f32 kernels).  "auto", "f32" and "bf16" run every geometry up to 1024 tokens."""
+    geometry, run those launches on the f32 kernels).  "auto", "f32" and "bf16" run every geometry up to 1024 tokens.
+    head_dim 80 (ViT-H-14): the attention exists in exact f32 only, so "bf16", "bf16x3", "f16x3" and "f16x3s" are refused; "auto",
+    "f32" and "f32x6" run ("auto" is six bf16-plane products everywhere: the fp16-plane steps are built for widths 768 and 1024)."""
     if precision == "bf16x6":
         raise ValueError(f"precision 'bf16x6' is a ResNet encoder precision: for {arch} 'auto' already is that arithmetic (every large "
                          "product as an f32-accurate six-product GEMM of bf16 planes); use 'auto'")
     if precision not in PRECISIONS:
         raise ValueError(f"unknown precision {precision!r}: one of {', '.join(PRECISIONS)}")
+    if head_dim != 64 and precision in ("bf16", "bf16x3", "f16x3", "f16x3s"):
+        raise ValueError(f"precision {precision!r} is not available for {arch}: its head dimension is {head_dim}, where the attention "
+                         "runs in exact f32 only; use 'auto', 'f32' or 'f32x6'")
     if precision in ("bf16x3", "f16x3") and (tokens > 224 or (resolution, patch, width) in _NEW_ARCH_VISION):
         raise ValueError(f"precision {precision!r} is not available for {arch} ({tokens} tokens, width {width}): it is stated for the "
                          "ViT-B/16 geometry, whose planes attention (192 < tokens <= 208) it needs; use 'auto', 'f32' or 'bf16'")
@@ -285,8 +290,9 @@ class Transformer(nn.Module):
 
     def __init__(self, width: int, layers: int, heads: int, causal: bool = False, act: str = "quick_gelu"):
         super().__init__()
-        if width != heads * 64:
-            raise ValueError("libacx attention kernels are built for head dim 64 (every CLIP ViT/text tower)")
+        if width != heads * 64 and (causal or width != heads * 80):
+            raise ValueError(f"width {width} with {heads} heads: libacx attention kernels are built for head dim 64 (every CLIP ViT / text "
+                             "tower of clip.load) and, non-causal, 80 (open_clip's ViT-H-14)")
         self.width, self.layers, self.heads, self.causal = width, layers, heads, causal
         check_act(act)
         self.act = act
@@ -397,7 +403,8 @@ class VisionTransformer(nn.Module):
         return (self.input_resolution // self.patch_size) ** 2 + 1
 
     def check_precision(self):
-        check_vit_precision(self.precision, self.tokens, self.width, self.arch, self.input_resolution, self.patch_size)
+        check_vit_precision(self.precision, self.tokens, self.width, self.arch, self.input_resolution, self.patch_size,
+                            self.width // self.heads)
         check_act(self.act, self.precision)
 
     @torch.no_grad()

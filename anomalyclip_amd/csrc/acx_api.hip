@@ -416,6 +416,8 @@ int tf_act(acx_ctx* ctx, const char* who, int32_t given, int prec, int* act) {
   *act = given == ACX_ACT_GELU ? ACX_ACT_GELU : ACX_ACT_QUICKGELU;
   return ACX_OK;
 }
+// the head dimension of a driver geometry: 64, 80, or 0 (neither)
+inline int tf_head_dim(int width, int heads) { return heads <= 0 ? 0 : width == heads * 64 ? 64 : width == heads * 80 ? 80 : 0; }
 struct TfHave { bool f32[4], alt[4]; };   // in_proj, out_proj, fc, proj of every block: the f32 weight, the *_w_bf16 copy / planes
 struct TfPlan {
   TfMode mode;
@@ -469,12 +471,18 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   m.prec = xmode ? ACX_PREC_F32 : g.prec;         // everything that is not one of the four large GEMMs runs as in f32 mode
   m.hdt = m.prec == ACX_PREC_BF16 ? ACX_BF16 : ACX_F32;
   p->prune = g.prune;
+  // head dimension 80 (width == 80 heads: ViT-H-14's image tower): the f32 attentions of acx_attn_hd.h, non-causal, under ACX_PREC_F32 and
+  // the six bf16-plane products only; no planes attention, no fold of the pruned layer, no LayerNorm rider.  Every other geometry keeps
+  // head dimension 64's rules below, record for record.
+  const bool hd80 = tf_head_dim(W, g.heads) == 80;
+  if (hd80 && (g.causal || (g.prec != ACX_PREC_F32 && g.prec != ACX_PREC_F32X6)))
+    return acx_fail(err, ACX_E_UNSUPPORTED, "driver: head dimension 80 runs non-causal under ACX_PREC_F32 or ACX_PREC_F32X6 only%s");
   const int cpl = m.xm.f16 ? ACX_F16X2P : ACX_BF16X3P;   // a plane product's plane output
   auto x6 = [&](int N, int K) { return xmode && x6_takes(o, g.planes_ws, rows, N, K, K); };
   const bool x6_qkv = x6(3 * W, W), x6_out = x6(W, W), x6_fc = x6(4 * W, W), x6_proj = x6(W, 4 * W), x6_kv = x6(2 * W, W);
   // ACX_PREC_F32X6: the LayerNorm behind a residual product (out-proj -> ln_2, c_proj -> the next layer's ln_1, K | V LayerNorm of the
   // pruned last layer included) is handed to the product (acx_gemm_ln: the idle workgroups of its last round of tiles run part of it)
-  const bool ln_ride = m.pdt == ACX_BF16X3P;
+  const bool ln_ride = m.pdt == ACX_BF16X3P && !hd80;
   // ACX_PREC_F32X6_LN16: the plane-kernel in-projection and (ACX_LN16_FC_DEFAULT) c_fc read fp16 pair planes -- their weights come in that
   // format, so the rule is per product and holds for every geometry; everything else is the six-product plan below, record for record
   const bool ln16 = is_ln16(g.prec), r16 = is_r16(g.prec);
@@ -486,7 +494,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   // QKV store traffic, bf16-MFMA attention, and a bf16 A operand (LDS-DMA kernels) for the out-projection
   const bool ab = m.prec == ACX_PREC_BF16 && !g.causal && L <= 224 && ACX_DBG_SWITCH("ATTN_BF16", true);
   // the attention on the bf16 matrix cores (acx_attention_p3): q | k | v leave the in-projection as three bf16 planes
-  const bool att_p3 = x6_qkv && x6_out && !g.causal && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
+  const bool att_p3 = x6_qkv && x6_out && !g.causal && !hd80 && L > 192 && L <= 208 && ACX_DBG_SWITCH("ATTN_P3", true);
   // ACX_PREC_F16X3S: every other non-causal sequence takes the streaming fp16 planes attention (acx_attention_s16)
   const bool att_s16 = g.prec == ACX_PREC_F16X3S && x6_qkv && x6_out && !g.causal && L <= 1024 && !att_p3;
   // ... or, six products (ACX_OPT_ATTN_F32IN), as f32 rows the attention splits itself (acx_attention_p3f): no plane round trip
@@ -503,12 +511,13 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   p->qkv16 = g.prec == ACX_PREC_F32X6_QKV16 && o.qkv16 && p->r16_out && p->ln16_qkv && att_p3f && !in_proj_splits(err, g, rows);
   const bool qkv_planes = (att_p3 && !att_p3f) || att_s16;
   // ... or on f32 rows, writing the out-projection's three planes itself
-  const bool att_x3 = x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
+  // (head dimension 80: acx_attention_x3_hd, at every L)
+  const bool att_x3 = hd80 ? x6_out : x6_out && !g.causal && L > 128 && L <= 1024 && (L > 224 || ACX_DBG_SWITCH("ATTN16", true));
   // ACX_OPT_CLS_FOLD (every precision but bf16): the pruned layer without K and V -- ln_1 and Q for the CLS rows, then
   // acx_attention_cls_fold reads the residual stream itself.  Its u | z scratch (2 heads W floats per frame) lives in the f32 q | k | v
   // buffer (3 L W floats per frame): a geometry with 2 heads > 3 L tokens (fewer than 11 tokens at 16 heads; no CLIP backbone) keeps
   // the K | V path, whatever the option says.
-  const bool cls_fold = g.prune && m.prec != ACX_PREC_BF16 && o.cls_fold && L <= 1024 &&
+  const bool cls_fold = g.prune && m.prec != ACX_PREC_BF16 && o.cls_fold && !hd80 && L <= 1024 &&
                         acx_attention_cls_fold_workspace_bytes(g.batch, g.heads) <= (size_t)rows * 3 * W * 4;
   const bool kv_planes = g.prune && !cls_fold && x6_kv;   // the pruned layer's K | V product runs on the plane kernel
 
@@ -536,7 +545,8 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   b.ln1_dtype = p->ln16_qkv ? ACX_F16X2P : x6_qkv ? m.pdt : m.hdt;
   b.in_proj = !x6_qkv ? tf_rows(ab ? ACX_BF16 : ACX_F32, ACX_TF_BUF_SPLITK)
                       : qkv_planes ? tf_x6(cpl, ACX_TF_BUF_QKV, false) : tf_x6(ACX_F32, ACX_TF_BUF_H, false);
-  b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_s16 ? ACX_TF_ATT_S16 : att_x3 ? ACX_TF_ATT_X3_PANEL : ACX_TF_ATT_F32;
+  b.att = ab ? ACX_TF_ATT_BF16 : att_p3f ? ACX_TF_ATT_P3F : att_p3 ? ACX_TF_ATT_P3N : att_s16 ? ACX_TF_ATT_S16
+          : att_x3 ? (hd80 ? ACX_TF_ATT_HD_X3_PANEL : ACX_TF_ATT_X3_PANEL) : hd80 ? ACX_TF_ATT_HD_F32 : ACX_TF_ATT_F32;
   b.att_products = b.att == ACX_TF_ATT_P3N ? (m.xm.f16 ? 103 : m.xm.pairs) : 0;
   b.att_out_dtype = p->r16_out ? ACX_F16X2P : 0;
   if (p->qkv16) {
@@ -563,7 +573,7 @@ int tf_plan(acx_ctx* err, const TfGeom& g, const TfHave& have, const TfOpts& o, 
   c.ln1 = cls_fold ? ACX_TF_LN_CLS : !kv_planes ? ACX_TF_LN_ROWS : p->before_pruned.proj.ln_job ? ACX_TF_LN_RIDDEN : ACX_TF_LN_PLANES;
   c.ln1_dtype = kv_planes ? (p->ln16_qkv ? ACX_F16X2P : m.pdt) : m.hdt;
   c.in_proj = kv_planes ? tf_x6(ACX_F32, ACX_TF_BUF_NONE, false) : tf_rows(ACX_F32, ACX_TF_BUF_NONE);
-  c.att = cls_fold ? ACX_TF_ATT_CLS_FOLD : ACX_TF_ATT_CLS;
+  c.att = cls_fold ? ACX_TF_ATT_CLS_FOLD : hd80 ? ACX_TF_ATT_HD_CLS : ACX_TF_ATT_CLS;
   c.out_proj = c.proj = tf_rows(ACX_F32, ACX_TF_BUF_NONE);
   c.ln2 = ACX_TF_LN_CLS;
   c.ln2_dtype = m.hdt;
@@ -665,6 +675,8 @@ struct TfRun {
         break;
       case ACX_TF_ATT_S16: rc = acx_attention_s16(ctx, ws.qkv3, 1.f, ws.hp, 1.f, batch, L, heads, s); break;                  // fp16 planes in, fp16 planes out
       case ACX_TF_ATT_X3_PANEL: rc = acx_attention_x3_panel(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, s); break;
+      case ACX_TF_ATT_HD_X3_PANEL: rc = acx_attention_x3_hd(ctx, (const float*)ws.qkv, 3 * W, ws.hp, W, batch, L, heads, W / heads, 1, s); break;
+      case ACX_TF_ATT_HD_F32: rc = acx_attention_hd(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, W / heads, s); break;
       default: rc = acx_attention(ctx, (const float*)ws.qkv, 3 * W, (float*)ws.att, W, batch, L, heads, g.causal, s); break;
     }
     if (rc) return rc;
@@ -737,7 +749,8 @@ struct TfRun {
       q.A = ws.h; q.lda = L * W;
       q.C = ws.qkv; q.ldc = L * 3 * W;
       if ((rc = go(q))) return rc;
-      if ((rc = acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, c.attc, W, batch, L, g.heads, s))) return rc;
+      if ((rc = r.att == ACX_TF_ATT_HD_CLS ? acx_attention_cls_hd(ctx, (const float*)ws.qkv, 3 * W, c.attc, W, batch, L, g.heads, W / g.heads, s)
+                                           : acx_attention_cls(ctx, (const float*)ws.qkv, 3 * W, c.attc, W, batch, L, g.heads, s))) return rc;
     }
     p = product(b, 1, r.out_proj, batch);
     p.A = c.attc; p.a_dtype = ACX_F32;
@@ -825,7 +838,8 @@ extern "C" int acx_transformer_forward_act(acx_ctx* ctx, float* x, int32_t batch
   if (!x || !blocks || !workspace) return acx_fail(ctx, ACX_E_BADARG, "acx_transformer_forward: null pointer%s");
   int mlp_act = 0, rc0;
   if ((rc0 = tf_act(ctx, "acx_transformer_forward", act, prec, &mlp_act))) return rc0;
-  if (width != heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_transformer_forward: head dim must be 64%s");
+  if (tf_head_dim(width, heads) != 64 && !(tf_head_dim(width, heads) == 80 && !causal))
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_transformer_forward: head dim must be 64 (or 80, non-causal)%s");
   // ACX_PREC_F32X6 with a workspace sized for it (acx_transformer_workspace_bytes_prec); a smaller (f32-sized) workspace runs
   // the f32 kernels
   TfWs ws = carve_tf((char*)workspace, (int64_t)batch * L, width, prec);
@@ -876,7 +890,7 @@ static int vit_encode(acx_ctx* ctx, const acx_vit_desc* d, const acx_vit_weights
   int mlp_act = 0, rc0;
   if ((rc0 = tf_act(ctx, "acx_vit_encode", d->act, d->prec, &mlp_act))) return rc0;
   if (nframes <= 0) return ACX_OK;
-  if (d->width != d->heads * 64) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64%s");
+  if (!tf_head_dim(d->width, d->heads)) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_vit_encode: head dim must be 64 or 80%s");
   if (d->patch <= 0 || d->resolution % d->patch || d->patch % 2)
     return acx_fail(ctx, ACX_E_BADARG, "acx_vit_encode: bad patch geometry (need resolution %% patch == 0 and an even patch)%s");
   const int g = d->resolution / d->patch, T = g * g, W = d->width, F = nframes;

@@ -13,6 +13,7 @@ namespace {
 #include "acx_attn_s16.h"    // attn_s16_kernel: two fp16 planes per operand, streaming over the keys (any L <= 1024)
 #include "acx_attn_bf16.h"   // attn_bf16_kernel: bf16 operands, the bf16 mode of the ViT
 #include "acx_attn_cls.h"    // attn_cls_kernel, cls_fold_u_kernel, cls_fold_kernel, cls_fold_o_kernel: the CLS row only
+#include "acx_attn_hd.h"     // attn_hd_kernel, attn_cls_hd_kernel: f32 MFMAs at head dimension 80
 }  // namespace
 
 // The kernel choice of acx_attention / _x3 / _x3_panel: one rule, asked by the dispatcher below and by acx_attention_route.  *why: the
@@ -321,5 +322,78 @@ extern "C" int acx_attention_cls_fold(acx_ctx* ctx, const float* x, const float*
   hipLaunchKernelGGL(cls_fold_o_kernel, dim3((unsigned)heads, (unsigned)((batch + CF_OF - 1) / CF_OF)), dim3(256), 0, s, (const float*)z,
                      wv, in_proj_b + 2 * W, out, ldo, (int)batch, (int)W);
   ACX_CHECK_LAUNCH(ctx, "acx_attention_cls_fold");
+  return ACX_OK;
+}
+
+// ---- head dimension 80 (acx_attn_hd.h).  64 is refused, not forwarded: acx_attention and its variants are the entry points of that
+// head dimension, with their own routes and error codes, and one meaning per entry point keeps both contracts short.
+static int attn_hd_dim(acx_ctx* ctx, const char* who, int32_t head_dim) {
+  if (head_dim == 80) return ACX_OK;
+  return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: head_dim %ld is not supported (80; head dimension 64 is acx_attention's)", who, (long)head_dim);
+}
+
+extern "C" int acx_attention_hd_route(const acx_ctx* ctx, int32_t L, int32_t head_dim, int32_t out_aligned) {
+  (void)ctx;                                                             // (no device property enters the rule)
+  if (head_dim != 80 || L <= 0 || L > 1024 || !out_aligned) return ACX_E_UNSUPPORTED;
+  return L > 128 ? ACX_ATTN_HD_ROUTE_STREAM_QB : ACX_ATTN_HD_ROUTE_STREAM;
+}
+
+// x3: 0 f32 rows, 1 three row-major bf16 planes, 2 three K-panel planes
+static int attention_hd_impl(acx_ctx* ctx, const char* who, const float* qkv, int64_t ldqkv, void* out, int64_t ldo, int32_t batch, int32_t L,
+                             int32_t heads, int32_t head_dim, void* stream, int x3) {
+  if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "%s: null pointer", who);
+  int rc = attn_hd_dim(ctx, who, head_dim);
+  if (rc) return rc;
+  if (L <= 0 || L > 1024 || heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: need 1 <= L <= 1024 and heads >= 1", who);
+  if (batch <= 0) return ACX_OK;
+  const int64_t W = (int64_t)heads * head_dim;
+  if (ldqkv % 4 || ldqkv < 3 * W || ((uintptr_t)qkv & 15)) return acx_fail(ctx, ACX_E_BADARG, "%s: qkv must be 16-byte aligned, ldqkv %% 4 == 0 and >= 3 heads head_dim", who);
+  if (ldo < W) return acx_fail(ctx, ACX_E_BADARG, "%s: ldo < heads head_dim", who);
+  if (x3 == 2 && ldo % 32) return acx_fail(ctx, ACX_E_BADARG, "%s: K-panel planes need ldo %% 32 == 0", who);
+  const int route = acx_attention_hd_route(ctx, L, head_dim, ldo % 4 == 0 && !((uintptr_t)out & 15));
+  if (route < 0) return acx_fail(ctx, route, "%s: out must be 16-byte aligned with ldo %% 4 == 0", who);
+  const int nqb = route == ACX_ATTN_HD_ROUTE_STREAM_QB ? ((L + 15) / 16 + 7) / 8 : 1;
+  const int64_t items = (int64_t)batch * heads * nqb;
+  if (items > INT32_MAX || (int64_t)batch * L > INT32_MAX) return acx_fail(ctx, ACX_E_UNSUPPORTED, "%s: batch * heads too large", who);
+  const int nitems = (int)items;
+  const int ncu = ctx && ctx->multiprocessors > 0 ? ctx->multiprocessors : 256;
+  const int slots = 2 * ncu;                                              // two workgroups per CU
+  const dim3 grid((unsigned)(nitems < slots ? nitems : slots));
+  const int64_t x3plane = x3 ? (int64_t)batch * L * ldo : (int64_t)0, prows = x3 == 2 ? (int64_t)batch * L : (int64_t)0;
+  hipStream_t s = (hipStream_t)stream;
+  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+  hipLaunchKernelGGL(attn_hd_kernel<80>, grid, dim3(512), AhdGeom<80>::LDS_B, s, qkv, ldqkv, (float*)out, ldo, L, heads, nitems, nqb, x3plane, prows);
+  ACX_CHECK_LAUNCH(ctx, who);
+  return ACX_OK;
+}
+
+extern "C" int acx_attention_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch, int32_t L,
+                                int32_t heads, int32_t head_dim, void* stream) {
+  return attention_hd_impl(ctx, "acx_attention_hd", qkv, ldqkv, out, ldo, batch, L, heads, head_dim, stream, 0);
+}
+
+extern "C" int acx_attention_x3_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo, int32_t batch, int32_t L,
+                                   int32_t heads, int32_t head_dim, int32_t panel, void* stream) {
+  return attention_hd_impl(ctx, "acx_attention_x3_hd", qkv, ldqkv, out_planes, ldo, batch, L, heads, head_dim, stream, panel ? 2 : 1);
+}
+
+extern "C" int acx_attention_cls_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch, int32_t L,
+                                    int32_t heads, int32_t head_dim, void* stream) {
+  if (!qkv || !out) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls_hd: null pointer%s");
+  int rc = attn_hd_dim(ctx, "acx_attention_cls_hd", head_dim);
+  if (rc) return rc;
+  if (L <= 0 || L > 1024 || heads <= 0) return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls_hd: need 1 <= L <= 1024 and heads >= 1%s");
+  if (batch <= 0) return ACX_OK;
+  const int64_t W = (int64_t)heads * head_dim;
+  if (ldqkv % 4 || ldqkv < 3 * W || ((uintptr_t)qkv & 15))
+    return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls_hd: qkv must be 16-byte aligned, ldqkv %% 4 == 0 and >= 3 heads head_dim%s");
+  if (ldo < W) return acx_fail(ctx, ACX_E_BADARG, "acx_attention_cls_hd: ldo < heads head_dim%s");
+  if ((int64_t)batch * heads > INT32_MAX || (int64_t)batch * L > INT32_MAX)
+    return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_attention_cls_hd: batch * heads too large%s");
+  hipStream_t s = (hipStream_t)stream;
+  AcxProfScope prof__(ctx, ACX_K_ATTN, s);
+  const int64_t n = (int64_t)batch * heads;
+  hipLaunchKernelGGL(attn_cls_hd_kernel<80>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, qkv, ldqkv, out, ldo, batch, L, heads);
+  ACX_CHECK_LAUNCH(ctx, "acx_attention_cls_hd");
   return ACX_OK;
 }

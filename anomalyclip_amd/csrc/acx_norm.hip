@@ -178,17 +178,25 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float* __restrict__
 
 #define COMMA ,
 // (a width that is no multiple of 64 takes the default: D / 64 alone would hand 96 or 130 to the 64- or 128-wide kernel)
-#define DISPATCH_VPL(D, CALL)                          \
-  switch ((D) % 64 ? 0 : (D) / 64) {                   \
-    case 1: { constexpr int V = 1; CALL; } break;      \
-    case 2: { constexpr int V = 2; CALL; } break;      \
-    case 4: { constexpr int V = 4; CALL; } break;      \
-    case 8: { constexpr int V = 8; CALL; } break;      \
-    case 10: { constexpr int V = 10; CALL; } break;    \
-    case 12: { constexpr int V = 12; CALL; } break;    \
-    case 16: { constexpr int V = 16; CALL; } break;    \
-    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in {64,128,256,512,640,768,1024}", "", (long)(D)); \
+// DISPATCH_VPL: the widths of the classification head.  DISPATCH_VPL_VIT: those and 1280 (20 values per lane: the ViT-H-14 width) for
+// acx_layernorm and acx_vit_embed.  One switch (DISPATCH_VPL_); the launch goes in as the variadic tail because its commas arrive
+// expanded.  The refusal of the longer list keeps the shorter one's text as it stands and names 1280 behind it.
+#define VPL_NO_20(...)
+#define VPL_CASE_20(...) case 20: { constexpr int V = 20; __VA_ARGS__; } break;
+#define DISPATCH_VPL_(D, CASE20, WIDTHS, ...)                 \
+  switch ((D) % 64 ? 0 : (D) / 64) {                          \
+    case 1: { constexpr int V = 1; __VA_ARGS__; } break;      \
+    case 2: { constexpr int V = 2; __VA_ARGS__; } break;      \
+    case 4: { constexpr int V = 4; __VA_ARGS__; } break;      \
+    case 8: { constexpr int V = 8; __VA_ARGS__; } break;      \
+    case 10: { constexpr int V = 10; __VA_ARGS__; } break;    \
+    case 12: { constexpr int V = 12; __VA_ARGS__; } break;    \
+    case 16: { constexpr int V = 16; __VA_ARGS__; } break;    \
+    CASE20(__VA_ARGS__)                                       \
+    default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "row width %s%ld not in " WIDTHS, "", (long)(D)); \
   }
+#define DISPATCH_VPL(D, CALL) DISPATCH_VPL_(D, VPL_NO_20, "{64,128,256,512,640,768,1024}", CALL)
+#define DISPATCH_VPL_VIT(D, CALL) DISPATCH_VPL_(D, VPL_CASE_20, "{64,128,256,512,640,768,1024} or 1280", CALL)
 
 // row0 > 0 (acx_layernorm_rows; even, K-panel bf16 x 3 planes on the two-rows-per-wave kernel only): rows row0 .. rows
 static int layernorm_impl(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
@@ -225,16 +233,17 @@ static int layernorm_impl(acx_ctx* ctx, const float* x, int64_t ldx, const float
         case 8: layernorm_panel2_kernel<8><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
         case 12: layernorm_panel2_kernel<12><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
         case 16: layernorm_panel2_kernel<16><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
-        default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_BF16X3P needs D in {256, 512, 768, 1024}%s");
+        case 20: layernorm_panel2_kernel<20><<<grid2, block, 0, s>>>(x, ldx, w, b, (u16*)y, rows, eps, mode, row0, 1.f); break;
+        default: return acx_fail(ctx, ACX_E_UNSUPPORTED, "acx_layernorm: ACX_BF16X3P needs D in {256, 512, 768, 1024, 1280}%s");
       }
     } else
-    DISPATCH_VPL(D, layernorm_kernel<V COMMA 3><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
+    DISPATCH_VPL_VIT(D, layernorm_kernel<V COMMA 3><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
   } else if (y_dtype == ACX_BF16X3) {  // three dense planes [rows, ldy] each, y + p * rows * ldy
-    DISPATCH_VPL(D, layernorm_kernel<V COMMA 2><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
+    DISPATCH_VPL_VIT(D, layernorm_kernel<V COMMA 2><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
   } else if (y_dtype == ACX_BF16) {
-    DISPATCH_VPL(D, layernorm_kernel<V COMMA 1><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
+    DISPATCH_VPL_VIT(D, layernorm_kernel<V COMMA 1><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
   } else {
-    DISPATCH_VPL(D, layernorm_kernel<V COMMA 0><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
+    DISPATCH_VPL_VIT(D, layernorm_kernel<V COMMA 0><<<grid COMMA block COMMA 0 COMMA s>>>(x, ldx, w, b, y, ldy, rows, eps, mode));
   }
   ACX_CHECK_LAUNCH(ctx, "acx_layernorm");
   return ACX_OK;
@@ -271,7 +280,7 @@ extern "C" int acx_vit_embed(acx_ctx* ctx, const float* patch_out, const float* 
   const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   hipStream_t s = (hipStream_t)stream;
   AcxProfScope prof__(ctx, ACX_K_NORM, s);
-  DISPATCH_VPL(W, vit_embed_kernel<V><<<grid COMMA block COMMA 0 COMMA s>>>(patch_out, cls, pos, ln_w, ln_b, x, rows, T));
+  DISPATCH_VPL_VIT(W, vit_embed_kernel<V><<<grid COMMA block COMMA 0 COMMA s>>>(patch_out, cls, pos, ln_w, ln_b, x, rows, T));
   ACX_CHECK_LAUNCH(ctx, "acx_vit_embed");
   return ACX_OK;
 }

@@ -833,13 +833,15 @@ def extract_dataset(net_or_encoder, annotation_file: Optional[str], frames_root:
 
 
 # ---------------------------------------------------------------------------------------------------------------- command line
-def build_image_encoder(arch: str, precision: str = "auto", chunk: int = 512, act: str = "quick_gelu"):
+def build_image_encoder(arch: str, precision: str = "auto", chunk: int = 512, act: Optional[str] = None):
     """the CLIP image encoder of `arch`, as AnomalyCLIP builds it.  act: the ViT MLP's activation, "quick_gelu" (OpenAI's weights) or
-    "gelu" (open_clip's LAION-2B / DataComp weights); "gelu" with precision "bf16" or a ResNet arch is a ValueError naming both"""
+    "gelu" (open_clip's LAION-2B / DataComp weights), None: the arch's own ("gelu" for ViT-H-14, "quick_gelu" otherwise); "gelu" with
+    precision "bf16" or a ResNet arch is a ValueError naming both"""
     from .components.anomaly_clip import geometry_of_arch
     from .components.clip_resnet import ModifiedResNet
     from .components.clip_vit import VisionTransformer, check_act
     geom = geometry_of_arch(arch)
+    act = act or geom.act
     check_act(act, precision, arch if geom.is_resnet else None)
     if geom.is_resnet:
         return ModifiedResNet(geom.vision_layers, geom.embed_dim, geom.resnet_heads, geom.image_resolution, geom.vision_width,
@@ -874,9 +876,13 @@ def _parser():
     p = argparse.ArgumentParser(prog="python -m anomalyclip_amd.extract", description="CLIP feature files from frame folders")
     p.add_argument("--arch", required=True, choices=sorted(_ARCH))
     p.add_argument("--weights", required=True, help="Lightning .ckpt, AnomalyCLIP state_dict, image-encoder state_dict or plain CLIP state_dict")
-    p.add_argument("--act", default="quick_gelu", choices=("quick_gelu", "gelu"),
+    class _Act(argparse.Action):                         # (the parser's default stays "quick_gelu"; parse_args reads whether it was given)
+        def __call__(self, parser, namespace, values, option_string=None):
+            namespace.act, namespace.act_given = values, True
+    p.set_defaults(act_given=False)
+    p.add_argument("--act", default="quick_gelu", choices=("quick_gelu", "gelu"), action=_Act,
                    help="the ViT MLP's activation: quick_gelu for OpenAI's weights, gelu for open_clip weights trained without quick_gelu "
-                        "(LAION-2B, DataComp); the weights do not say which")
+                        "(LAION-2B, DataComp); the weights do not say which.  Left out with --arch ViT-H-14 (open_clip weights only): gelu")
     p.add_argument("--frames-root", required=True)
     p.add_argument("--out-root", required=True)
     p.add_argument("--annotations", default=None, help="rows `path start end label...`; default: every folder of --frames-root")
@@ -910,9 +916,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
         if geom.is_resnet:
             check_resnet_precision(a.precision, a.arch, geom.vision_width)
         else:
-            check_vit_precision(a.precision, geom.grid ** 2 + 1, geom.vision_width, a.arch, geom.image_resolution, geom.vision_patch_size)
+            check_vit_precision(a.precision, geom.grid ** 2 + 1, geom.vision_width, a.arch, geom.image_resolution, geom.vision_patch_size,
+                                geom.vision_head_dim)
     except ValueError as e:
         p.error(f"--precision {a.precision} conflicts with --arch {a.arch}: {e}")
+    if not a.act_given:
+        a.act = geom.act                                   # the arch's own: "gelu" for ViT-H-14, the parser's default otherwise
     try:
         check_act(a.act, a.precision, a.arch if geom.is_resnet else None, key="--act")
     except ValueError as e:

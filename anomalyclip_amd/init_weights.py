@@ -36,6 +36,8 @@ class ClipGeometry:
     transformer_layers: int = 12
     act: str = "quick_gelu"     # the MLPs' activation: "quick_gelu" (OpenAI's checkpoints) or "gelu" (open_clip configs without quick_gelu);
                                 # not a constructor argument of the reference's CLIP: as_kwargs() leaves it out
+    vision_head_dim: int = 64   # the ViT image tower's head dimension: 64 for every CLIP of clip.load, 80 for open_clip's ViT-H-14 (its
+                                # `head_width`).  The reference's CLIP always divides by 64: as_kwargs() leaves this out too
 
     @property
     def is_resnet(self) -> bool:
@@ -45,7 +47,7 @@ class ClipGeometry:
     def vision_heads(self) -> int:
         if self.is_resnet:
             raise ValueError("vision_heads is a ViT field: a ResNet's attention pool has resnet_heads = vision_width * 32 // 64")
-        return self.vision_width // 64
+        return self.vision_width // self.vision_head_dim
 
     @property
     def grid(self) -> int:
@@ -75,6 +77,9 @@ VIT_L14 = ClipGeometry(embed_dim=768, image_resolution=224, vision_layers=24, vi
                        transformer_width=768, transformer_heads=12, transformer_layers=12)
 VIT_L14_336 = ClipGeometry(embed_dim=768, image_resolution=336, vision_layers=24, vision_width=1024, vision_patch_size=14,
                            transformer_width=768, transformer_heads=12, transformer_layers=12)
+# open_clip's ViT-H-14 (LAION-2B): 16 heads of 80 in the image tower, a 24-layer text tower of 16 heads of 64, exact GELU
+VIT_H14 = ClipGeometry(embed_dim=1024, image_resolution=224, vision_layers=32, vision_width=1280, vision_patch_size=14, vision_head_dim=80,
+                       transformer_width=1024, transformer_heads=16, transformer_layers=24, act="gelu")
 # the ResNet backbones of clip.load (clip/clip.py:31-41), CLIP's published shapes (vision_layers: blocks of layer1..4)
 RN50 = ClipGeometry(embed_dim=1024, image_resolution=224, vision_layers=(3, 4, 6, 3), vision_width=64, vision_patch_size=None,
                     transformer_width=512, transformer_heads=8, transformer_layers=12)
@@ -86,7 +91,7 @@ RN50X16 = ClipGeometry(embed_dim=768, image_resolution=384, vision_layers=(6, 8,
                        transformer_width=768, transformer_heads=12, transformer_layers=12)
 RN50X64 = ClipGeometry(embed_dim=1024, image_resolution=448, vision_layers=(3, 15, 36, 10), vision_width=128, vision_patch_size=None,
                        transformer_width=1024, transformer_heads=16, transformer_layers=12)
-# tiny geometry used by fixtures (head dim stays 64 like every CLIP ViT)
+# tiny geometry used by fixtures (head dim stays 64 like every CLIP ViT of clip.load)
 TINY = ClipGeometry(embed_dim=128, image_resolution=32, vision_layers=2, vision_width=128,
                     vision_patch_size=16, context_length=77, vocab_size=49408,
                     transformer_width=128, transformer_heads=2, transformer_layers=2)

@@ -509,6 +509,34 @@ def attention(qkv: torch.Tensor, batch: int, L_: int, heads: int, causal: bool) 
     return out
 
 
+def attention_hd(qkv: torch.Tensor, batch: int, L_: int, heads: int, head_dim: int = 80, *, planes_out: bool = False, panel_out: bool = False,
+                 cls: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acx_attention_hd / _x3_hd / _cls_hd: exact-f32 non-causal attention at head dimension `head_dim` (80) on qkv [batch * L, 3 heads
+    head_dim].  Default: f32 rows [batch * L, heads head_dim].  planes_out: three bf16 planes [3, batch * L, ldo] (hi | mid | lo),
+    row-major with ldo = heads head_dim, or (panel_out) in K-panel memory order with ldo = heads head_dim rounded up to whole 32-column
+    panels (unpanel() for row-major; the columns past heads head_dim are not written).  cls: query row 0 of every sequence only,
+    [batch, heads head_dim].  out: the buffer to write (tests poison it first) instead of a fresh one."""
+    W = heads * head_dim
+    assert qkv.is_contiguous() and qkv.shape == (batch * L_, 3 * W) and not (cls and planes_out)
+    h = _h(qkv)
+    lib = L.lib()
+    if cls:
+        out = torch.empty(batch, W, dtype=torch.float32, device=qkv.device) if out is None else out
+        L.check(lib.acx_attention_cls_hd(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), batch, L_, heads, head_dim,
+                                         _stream()), h)
+    elif planes_out:
+        ldo = (W + 31) // 32 * 32 if panel_out else W
+        out = torch.empty(3, batch * L_, ldo, dtype=_BF16, device=qkv.device) if out is None else out
+        assert out.is_contiguous() and out.shape == (3, batch * L_, ldo)
+        L.check(lib.acx_attention_x3_hd(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), ldo, batch, L_, heads, head_dim, int(panel_out),
+                                        _stream()), h)
+    else:
+        out = torch.empty(batch * L_, W, dtype=torch.float32, device=qkv.device) if out is None else out
+        L.check(lib.acx_attention_hd(h, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), batch, L_, heads, head_dim,
+                                     _stream()), h)
+    return out
+
+
 def attention_cls_fold(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, in_proj_w: torch.Tensor, in_proj_b: torch.Tensor,
                        q: torch.Tensor, batch: int, L_: int, heads: int, eps: float = 1e-5) -> torch.Tensor:
     """acx_attention_cls_fold: the CLS-row attention of a layer from its residual stream x [batch * L, W], ln_1, the f32

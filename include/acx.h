@@ -324,7 +324,7 @@ int64_t acx_gemm_ln_plan(int32_t M, int32_t N, int32_t K, int32_t ncu, int32_t k
 /* ------------------------------------------------------------------------------------------
  * acx_layernorm: y[r,:] = norm(x[r,:]) * w + b     (HBM-bound; one wavefront per row)
  * replaces clip/model.py:174-180 (LayerNorm), classification_head.py:7,12, axial PreNorm and
- * ChanLayerNorm.  D must be a multiple of 64 and <= 1024... rows gathered with stride ldx. */
+ * ChanLayerNorm.  D in {64, 128, 256, 512, 640, 768, 1024, 1280} (1280: every y_dtype but ACX_F16X2P)... rows gathered with stride ldx. */
 int acx_layernorm(acx_ctx* ctx, const float* x, int64_t ldx, const float* w, const float* b,
                   void* y, int64_t ldy, int32_t y_dtype, int64_t rows, int32_t D, float eps,
                   int32_t mode, void* stream);
@@ -392,6 +392,31 @@ int acx_attention_s16(acx_ctx* ctx, const void* qkv_planes, float in_scale, void
 /* ... with the planes in K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo == heads * 64) */
 int acx_attention_x3_panel(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo,
                            int32_t batch, int32_t L, int32_t heads, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Head dimension 80 (open_clip's ViT-H-14: width 1280 = 16 heads of 80).  Exact f32, non-causal, 1 <= L <= 1024: softmax(q k^T /
+ * sqrt(head_dim)) v with the scale head_dim^-0.5 applied to q in f32.  qkv [batch * L, ldqkv] packed q | k | v of heads * head_dim
+ * columns each (16-byte aligned, ldqkv % 4 == 0); out [batch * L, ldo], 16-byte aligned with ldo % 4 == 0.  One streaming kernel
+ * (f32 MFMAs, K and V through LDS in chunks of 32 keys, online softmax) serves every L.
+ * Error codes, all before any launch: null pointer ACX_E_BADARG; head_dim other than 80 ACX_E_UNSUPPORTED with the value in
+ * acx_last_error -- 64 is REFUSED, not forwarded: acx_attention and its variants stay the entry points of head dimension 64; L outside
+ * 1..1024 or heads <= 0 ACX_E_UNSUPPORTED; a misaligned qkv or a leading dimension too small ACX_E_BADARG; an out that is not 16-byte
+ * aligned with ldo % 4 == 0 ACX_E_UNSUPPORTED.  batch <= 0 is ACX_OK (nothing to do). */
+int acx_attention_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch, int32_t L, int32_t heads,
+                     int32_t head_dim, void* stream);
+/* ... with the output as three bf16 planes hi | mid | lo, plane p at (uint16_t*)out_planes + p * batch * L * ldo.  panel = 0: row-major
+ * (ACX_BF16X3); panel != 0: K-panel layout (ACX_BF16X3P: [ldo / 32][batch * L][32] each; ldo % 32 == 0, ldo >= heads * head_dim -- with an
+ * odd number of heads the last panel is half used) */
+int acx_attention_x3_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, void* out_planes, int64_t ldo, int32_t batch, int32_t L,
+                        int32_t heads, int32_t head_dim, int32_t panel, void* stream);
+/* ... for query row 0 of every sequence only (out [batch, ldo]; no alignment asked of out): the pruned last ViT layer */
+int acx_attention_cls_hd(acx_ctx* ctx, const float* qkv, int64_t ldqkv, float* out, int64_t ldo, int32_t batch, int32_t L, int32_t heads,
+                         int32_t head_dim, void* stream);
+/* which kernel route acx_attention_hd / _x3_hd take: STREAM one item per (sequence, head), L <= 128 (up to 8 query tiles, one per wave);
+ * STREAM_QB ceil(ceil(L / 16) / 8) query blocks per (sequence, head), L > 128.  Arithmetic on the arguments, ctx may be NULL.  A negative answer is
+ * the error code the entry points give: ACX_E_UNSUPPORTED for head_dim != 80, L outside 1..1024, or out_aligned == 0. */
+enum { ACX_ATTN_HD_ROUTE_STREAM = 1, ACX_ATTN_HD_ROUTE_STREAM_QB = 2 };
+int acx_attention_hd_route(const acx_ctx* ctx, int32_t L, int32_t head_dim, int32_t out_aligned);
 
 /* bf16 variant of acx_attention for the bf16 mode of the ViT (NOT a parity path): qkv [batch*L, ldqkv] and out
  * [batch*L, ldo] are bf16, QK^T and PV run on the bf16 MFMA, softmax in f32.  Non-causal only. */
@@ -615,7 +640,9 @@ enum { ACX_TF_LN_ROWS = 0, ACX_TF_LN_PLANES = 1, ACX_TF_LN_RIDDEN = 2, ACX_TF_LN
 enum { ACX_TF_GEMM_ROWS = 0, ACX_TF_GEMM_X6 = 1 };
 enum { ACX_TF_BUF_NONE = 0, ACX_TF_BUF_SPLITK = 1, ACX_TF_BUF_H = 2, ACX_TF_BUF_QKV = 3, ACX_TF_BUF_MLP = 4 };
 enum { ACX_TF_ATT_F32 = 0, ACX_TF_ATT_BF16 = 1, ACX_TF_ATT_X3_PANEL = 2, ACX_TF_ATT_P3N = 3, ACX_TF_ATT_P3F = 4, ACX_TF_ATT_CLS = 5,
-       ACX_TF_ATT_CLS_FOLD = 6, ACX_TF_ATT_S16 = 7 };
+       ACX_TF_ATT_CLS_FOLD = 6, ACX_TF_ATT_S16 = 7,
+       /* width == 80 heads (non-causal only): acx_attention_hd (f32 rows), acx_attention_x3_hd with panel = 1, acx_attention_cls_hd */
+       ACX_TF_ATT_HD_F32 = 8, ACX_TF_ATT_HD_X3_PANEL = 9, ACX_TF_ATT_HD_CLS = 10 };
 typedef struct acx_tf_product_t {
   int32_t kernel, c_dtype, scratch, ln_job;
 } acx_tf_product_t;

@@ -45,15 +45,16 @@ def macs_per_frame(g):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", default="ViT-L/14", choices=["ViT-B/16", "ViT-B/32", "ViT-L/14", "ViT-L/14@336px"])
+    ap.add_argument("--arch", default="ViT-L/14", choices=["ViT-B/16", "ViT-B/32", "ViT-L/14", "ViT-L/14@336px", "ViT-H-14"])
     ap.add_argument("--precision", default="auto", help="auto | f32 | bf16 | f32x6 | f16x3 | f16x3s, or several separated by commas: alternating legs")
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--act", default="quick_gelu", help="quick_gelu | gelu, or both separated by a comma: alternating legs")
+    ap.add_argument("--act", default=None, help="quick_gelu | gelu, or both separated by a comma: alternating legs (default: the arch's own)")
     ap.add_argument("--reps", type=int, default=1, help="legs per activation")
     a = ap.parse_args()
-    acts = a.act.split(",")
+    g = geometry_of_arch(a.arch)
+    acts = (a.act or g.act).split(",")
     if any(t not in ("quick_gelu", "gelu") for t in acts) or a.reps < 1:
         ap.error("--act takes quick_gelu, gelu or both separated by a comma; --reps >= 1")
     precs = a.precision.split(",")
@@ -62,7 +63,6 @@ def main():
     a.precision = precs[0]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    g = geometry_of_arch(a.arch)
     vit = VisionTransformer(g.image_resolution, g.vision_patch_size, g.vision_width, g.vision_layers, g.vision_heads, g.embed_dim,
                             precision=a.precision, chunk=a.frames, arch=a.arch, act=acts[0])
     vit.load_state_dict(IW.init_vit_state_dict(g, 0, prefix=""), strict=True)
